@@ -22,6 +22,10 @@ Prints ONE JSON line on rank 0.  Besides the contract fields it carries
 Everything inside the timed region is real work: no step is skipped, the optimizer step and the
 weight re-packing it triggers are included; the reference loop's per-step .item()/.cpu() syncs
 (train_DC_focal.py:257-269) are not part of the metric and are excluded.
+
+``--dump-outputs DIR`` writes, right after the timed region, what its last step computed as DIR/<name>.npy (Job.outputs,
+quantify_bench).  The inputs and the initial weights are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import json
@@ -387,9 +391,16 @@ def quantify_bench(args, real_stdout):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tabs, _ = batch_once()
+        tabs, masks = batch_once()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    dumped = None
+    if args.dump_outputs:                                  # the masks and the droplet tables (image, area, centroid, diameter)
+        rows = [np.stack([np.full(len(t), i, np.float64)] + [t[c].to_numpy(np.float64) for c in
+                          ("area", "centroid-0", "centroid-1", "equivalent_diameter")], axis=1) for i, t in enumerate(tabs) if len(t)]
+        dumped = write_outputs(args.dump_outputs, {
+            "masks": seeded_sample(torch.stack(masks).float().numpy(), DUMP_MAX_ELEMS, 0),
+            "droplets": np.concatenate(rows) if rows else np.zeros((0, 5))})
     out = {"metric": "images/sec droplet quantification (preprocess + forward + mask + connected components), "
                      "1040x1388 RGB -> 512x512x3 U-Net-DC, bs=8",
            "value": B / dt, "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -400,6 +411,8 @@ def quantify_bench(args, real_stdout):
                                   "droplet tables + uint8 masks back on the host; PNG decode / PNG+CSV writes excluded",
                       "global_batch": B, "parallelism": "dp1"},
            "droplets_per_image": float(np.mean([len(t) for t in tabs]))}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if not args.no_cpu_baseline:
         ncpu = 2
         cores = host_cores()
@@ -600,6 +613,34 @@ def igemm_leg(step, dtype, mode, nsteps=3, headline=False):
 
 NOMINAL_GFLOP_IMG = {("train", 512): 1153.9, ("infer", 512): 384.74, ("train", 1024): 4615.6, ("infer", 1024): 1538.94}   # SURVEY 8d, C_in = 1
 
+# --dump-outputs: every array together stays under DUMP_MAX_BYTES; an output larger than DUMP_MAX_ELEMS elements is written as a
+# fixed, seeded sample of them (the headline's 8 x 512 x 512 probabilities are written whole)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 8 << 20
+
+
+def seeded_sample(a, k, seed):
+    """`a` itself when it has at most k elements, else k of its elements (flattened) at positions drawn once from `seed`, in
+    index order: the same positions on every run for the same shape."""
+    a = np.asarray(a)
+    if a.size <= k:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def write_outputs(path, arrays):
+    """Write {name: float32/float64 array} as path/<name>.npy; returns {name: shape} for the result line."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"{name}: {a.dtype}")
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
 
 class Job:
     """One workload of this rank: module, optimizer, resident synthetic batch, step()."""
@@ -619,6 +660,8 @@ class Job:
         x, t = synthetic_batch(1000 + rank, batch, size, size, cin)
         self.x, self.t = x.to(dev), t.to(dev)
         self._loss = focal_dice_loss
+        self.keep_outputs = False                              # --dump-outputs: keep the network's output of the latest step
+        self.probs = None
 
     def make_optimizer(self):
         # train_DC_focal.py:224 (Adam, lr 1e-3): the same update rule in ONE HIP kernel that also rewrites the packed weight
@@ -638,10 +681,37 @@ class Job:
             loss = self._loss(p, self.t, alpha=1.0, gamma=2.0, ratio=0.3)      # train_DC_focal.py:222
             loss.backward()
             self.opt.step()
+            if self.keep_outputs:
+                self.probs = p.detach()
             return loss
         with torch.no_grad():                                   # quantify_droplets_batch.py:51-56 on device
             p = self.model(self.x)
+            if self.keep_outputs:
+                self.probs = p
             return (p > 0.3).sum()
+
+    def outputs(self, last):
+        """What a caller of step() holds after its last call (`last` = what that call returned), as numpy arrays: the network's
+        output and the loss (train) or the number of pixels above the threshold (infer, float64); training adds the gradients,
+        the updated parameters and the BatchNorm running statistics.  Float32 unless stated; gradients and parameters are a
+        fixed, seeded sample of every tensor (all of a small one), the same positions for both."""
+        out = {"probs": seeded_sample(self.probs.float().cpu().numpy(), DUMP_MAX_ELEMS, 0)}
+        if self.mode != "train":
+            out["mask_pixels"] = np.asarray(float(last.detach()), dtype=np.float64)
+            return out
+        out["loss"] = np.asarray(float(last.detach()), dtype=np.float32)
+        grads, params = [], []
+        for i, p in enumerate(self.model.parameters()):
+            n = p.numel()
+            idx = torch.from_numpy(np.sort(np.random.default_rng(1 + i).choice(n, min(n, max(256, n // 16)), replace=False)))
+            idx = idx.to(p.device)
+            grads.append(p.grad.detach().reshape(-1)[idx].float().cpu().numpy())
+            params.append(p.detach().reshape(-1)[idx].float().cpu().numpy())
+        out["grad_sample"], out["param_sample"] = np.concatenate(grads), np.concatenate(params)
+        out["bn_running_stats"] = np.concatenate([b.detach().float().cpu().numpy().reshape(-1)
+                                                  for name, b in self.model.named_buffers()
+                                                  if name.endswith(("running_mean", "running_var"))])
+        return out
 
     def workload(self, world=1):
         if self.mode == "train":
@@ -697,7 +767,13 @@ def main():
     ap.add_argument("--mode", default="train", choices=["train", "infer", "quantify"],
                     help="train = the headline metric (default); infer = forward-only eval (BASELINE configs[1]); "
                          "quantify = the droplet-quantification flow of quantify_droplets_batch.py (SURVEY 8 f1/f2)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / "
+                         "float64, at most 64 MB in all, seeded samples of the large arrays) so that two builds can be compared "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
 
@@ -727,6 +803,7 @@ def main():
     import torch.distributed as dist
 
     job = Job(args.mode, args.dtype, args.batch, args.size, args.in_channels, args.arch, args.adam, dev, rank)
+    job.keep_outputs = bool(args.dump_outputs)
     model = job.model
     # UNETDC_DP_FORCE=1: a one-rank process group whose collectives are really issued (RCCL rehearsal on a one-GPU box)
     force_dp = os.environ.get("UNETDC_DP_FORCE") == "1"
@@ -762,6 +839,7 @@ def main():
                  "step_ms_median_across_ranks": {"min": med[0], "median": med[len(med) // 2], "max": med[-1]},
                  "step_ms_max_across_ranks": float(per[:, 2].max())}
     final_loss = float(loss.item())
+    dumped = write_outputs(args.dump_outputs, job.outputs(loss)) if args.dump_outputs and rank == 0 else None
     # ---- instrumented passes, all AFTER the timed region (every rank runs them: the collectives need all ranks) ----
     roofline = igemm_leg(step, args.dtype, args.mode, nsteps=3, headline=(args.mode == "train" and args.dtype == "bf16"))
     hbm = hbm_leg(step, 2 if args.dtype == "bf16" else 4) if args.mode == "train" else None
@@ -793,6 +871,8 @@ def main():
             "step_ms": step_stats,
             "final_value": final_loss,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if nominal_gflop_img:
             out["whole_step_tflops_nominal"] = nominal_gflop_img * 1e9 * imgs / elapsed / 1e12
             out["whole_step_frac_of_mfma_peak"] = out["whole_step_tflops_nominal"] / (PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS)

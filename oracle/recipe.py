@@ -46,12 +46,13 @@ def seeded_target(seed, shape, frac=0.3):
 
 def sd_checksums(state_dict):
     """Per-key (sum, abs-sum) in float64: lets a test prove two state dicts are identical
-    without committing 124 MB of weights."""
+    without committing 124 MB of weights.  Summed by numpy (pairwise, one thread, fixed order): the
+    same bits on every host -- torch's CPU sum splits the reduction by thread count."""
     keys = sorted(state_dict)
     out = np.zeros((len(keys), 2))
     for i, k in enumerate(keys):
-        v = state_dict[k].detach().double()
-        out[i] = (float(v.sum()), float(v.abs().sum()))
+        v = state_dict[k].detach().cpu().double().numpy().reshape(-1)
+        out[i] = (float(v.sum()), float(np.abs(v).sum()))
     return keys, out
 
 

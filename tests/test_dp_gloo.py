@@ -148,6 +148,9 @@ def _train_worker(rank, world, port, q, args):
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                           LOCAL_RANK=str(rank))
         torch.set_num_threads(2)
+        # --device cpu runs on gloo whatever the host has: on a host with a GPU dp.init_from_env() would choose RCCL (and
+        # bind rank r to GPU r); a process group that is already up is the one train_DC_focal.py uses
+        dist.init_process_group("gloo", rank=rank, world_size=world)
         import train_DC_focal as t
         hist = t.main(args)
         q.put((rank, "ok", hist))

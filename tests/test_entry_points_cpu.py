@@ -317,6 +317,48 @@ def test_bench_timed_region_has_no_collector_pass_and_no_per_call_events():
     assert len(stats2["gc_events"]) == 3 and all(e["generation"] == 2 and e["ms"] >= 0 for e in stats2["gc_events"])
 
 
+def test_bench_dump_outputs_are_the_last_step_and_repeat_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs: Job.outputs gives what the LAST step computed (its loss, the network's output, the gradients and
+    the updated parameters at fixed sampled positions), two identically configured jobs give identical arrays, and
+    write_outputs keeps to float32 / float64 and to the 64 MB bound.  The same Job class as on the GPU, on PyTorch-CPU."""
+    import bench
+
+    def run(steps):
+        job = bench.Job("train", "f32", 2, 32, 1, "unetdc", "foreach", torch.device("cpu"))
+        job.keep_outputs = True
+        job.make_optimizer()
+        for _ in range(steps):
+            loss = job.step()
+        return job, loss
+    job, loss = run(2)
+    out = job.outputs(loss)
+    assert set(out) == {"probs", "loss", "grad_sample", "param_sample", "bn_running_stats"}
+    assert out["probs"].shape == (2, 1, 32, 32) and float(out["loss"]) == loss.item()
+    assert np.array_equal(out["probs"], job.probs.numpy())
+    params = list(job.model.parameters())
+    n_sampled = sum(min(p.numel(), max(256, p.numel() // 16)) for p in params)
+    assert out["grad_sample"].shape == out["param_sample"].shape == (n_sampled,)
+    w = params[-2]                                        # out_conv.weight: 64 elements, written whole, in order
+    assert np.array_equal(out["grad_sample"][-65:-1], w.grad.reshape(-1).numpy())
+    assert np.array_equal(out["param_sample"][-65:-1], w.detach().reshape(-1).numpy())
+    again, loss2 = run(2)
+    for k, v in again.outputs(loss2).items():
+        assert np.array_equal(v, out[k]), k
+    third, loss3 = run(3)                                 # one more step: other parameters, other outputs
+    assert not np.array_equal(third.outputs(loss3)["param_sample"], out["param_sample"])
+
+    s = bench.seeded_sample(np.arange(100, dtype=np.float32), 10, 0)
+    assert s.shape == (10,) and np.all(np.diff(s) > 0) and np.array_equal(s, bench.seeded_sample(np.arange(100.0), 10, 0))
+    shapes = bench.write_outputs(str(tmp_path / "d"), out)
+    assert shapes["probs"] == [2, 1, 32, 32]
+    for k, v in out.items():
+        back = np.load(tmp_path / "d" / f"{k}.npy")
+        assert back.dtype in (np.float32, np.float64) and np.array_equal(back, v)
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+
+
 def test_engine_flat_gradient_buffer_is_reused_only_when_unreferenced():
     """engine.UNetEngine._flat_grads: ONE flat gradient buffer across steps while nothing else refers to its storage; a fresh
     one while gradient views of the previous backward are still alive (accumulation, kept gradients).  Pure host logic: run on

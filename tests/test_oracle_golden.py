@@ -115,11 +115,13 @@ def test_e2e_eval_numpy_and_torch_port(tag):
         p, z = otc.unet_forward(torch.from_numpy(g["eval_x"]), sdt, dil, train=False, return_logits=True)
     assert float((z - torch.from_numpy(z_ref)).abs().max()) < 1e-5
     assert np.array_equal((p > 0.3).numpy(), mask_ref)          # same ATen ops: exact incl. guard band
-    # the drop-in module's own CPU path (BASELINE config 0 plumbing)
+    # the drop-in module's own CPU path (BASELINE config 0 plumbing): the same ATen ops as the port, so the same bits on any
+    # host; the golden was written on another host, whose oneDNN kernels may round the last bits differently (<= 1.5e-7 seen)
     model.eval()
     with torch.no_grad():
         p2 = model(torch.from_numpy(g["eval_x"]))
-    np.testing.assert_array_equal(p2.numpy(), g["eval_probs"])
+    np.testing.assert_array_equal(p2.numpy(), p.numpy())
+    np.testing.assert_allclose(p2.numpy(), g["eval_probs"], rtol=0, atol=3e-7)
 
 
 @pytest.mark.parametrize("tag", ["dc_c1", "plain_c3"])
