@@ -1,0 +1,181 @@
+"""CPU checks of tests/exact_ref.py (no GPU): the exact references agree with ATen in float64, the fixtures keep the
+exactness rule they claim, the bf16 rounding helper is torch's, the guard check catches a stray write in every region,
+and the replay's argument table matches include/unetdc_hip.h."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import exact_ref as X
+from unet_dc_segmentation_amd._lib import SIGNATURES
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("case", [(2, 7, 9, 3, 5, 1), (1, 6, 10, 4, 3, 2), (1, 5, 5, 2, 2, 4), (2, 16, 24, 8, 4, 8),
+                                  (1, 33, 40, 3, 4, 16), (1, 40, 36, 2, 3, 32), (1, 1, 3, 2, 2, 1)])
+def test_conv3x3_reference_matches_autograd(case):
+    n, h, w, ci, co, d = case
+    g = gen(1)
+    x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(co, ci, 3, 3, generator=g, dtype=torch.float64)
+    b = torch.randn(co, generator=g, dtype=torch.float64)
+    dy = torch.randn(n, co, h, w, generator=g, dtype=torch.float64)
+    xr, wr = x.clone().requires_grad_(True), wt.clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, b, padding=d, dilation=d)
+    gx, gw = torch.autograd.grad(y, (xr, wr), dy)
+    torch.testing.assert_close(X.conv3x3_fwd(nhwc(x), wt, d, b), nhwc(y.detach()))
+    torch.testing.assert_close(X.conv3x3_dgrad(nhwc(dy), wt, d), nhwc(gx))
+    torch.testing.assert_close(X.conv3x3_wgrad(nhwc(x), nhwc(dy), d), gw)
+    # an off > 0 view of a wider buffer (concat-style) is just another [N,H,W,C] tensor for the reference
+    wide = torch.randn(n, h, w, ci + 6, generator=g, dtype=torch.float64)
+    wide[..., 4:4 + ci] = nhwc(x)
+    torch.testing.assert_close(X.conv3x3_fwd(wide[..., 4:4 + ci], wt, d, b), nhwc(y.detach()))
+
+
+@pytest.mark.parametrize("case", [(2, 6, 8, 5, 3, 1), (1, 9, 7, 8, 4, 2), (2, 12, 20, 6, 9, 4), (1, 8, 8, 4, 5, 32)])
+def test_onehot_and_separable_references_match_the_gemm_forms(case):
+    n, h, w, ci, co, d = case
+    g = gen(2)
+    x = X.ints((n, h, w, ci), 2, g, lo=1)
+    wt, route = X.onehot_conv3x3(co, ci)
+    assert int((wt != 0).sum()) == co
+    assert torch.equal(X.conv3x3_fwd_onehot(x, route, co, d).double(), X.conv3x3_fwd(x, wt, d))
+    dy = X.ints((n, h, w, co), 2, g)
+    assert torch.equal(X.conv3x3_dgrad_onehot(dy, route, ci, d).double(), X.conv3x3_dgrad(dy, wt, d))
+    a, u = X.ints((n, h, w), 2, g), X.ints((ci,), 2, g)
+    assert torch.equal(X.conv3x3_wgrad_separable(a, u, dy, d), X.conv3x3_wgrad(a[..., None] * u, dy, d))
+    # the fp32 GEMM form is exact under the rule, and equal to the fp64 one
+    assert torch.equal(X.conv3x3_fwd(x, wt, d, fast=True).double(), X.conv3x3_fwd(x, wt, d))
+
+
+@pytest.mark.parametrize("case", [(2, 3, 5, 6, 4), (1, 4, 4, 3, 8)])
+def test_conv_transpose_reference_matches_autograd(case):
+    n, h, w, ci, co = case
+    g = gen(3)
+    x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(ci, co, 2, 2, generator=g, dtype=torch.float64)
+    b = torch.randn(co, generator=g, dtype=torch.float64)
+    dup = torch.randn(n, co, 2 * h, 2 * w, generator=g, dtype=torch.float64)
+    xr, wr = x.clone().requires_grad_(True), wt.clone().requires_grad_(True)
+    up = F.conv_transpose2d(xr, wr, b, stride=2)
+    gx, gw = torch.autograd.grad(up, (xr, wr), dup)
+    torch.testing.assert_close(X.convT2x2_fwd(nhwc(x), wt, b), nhwc(up.detach()))
+    torch.testing.assert_close(X.convT2x2_dgrad(nhwc(dup), wt), nhwc(gx))
+    torch.testing.assert_close(X.convT2x2_wgrad(nhwc(x), nhwc(dup)), gw)
+    wo = X.onehot_convT2x2(ci, co)
+    assert torch.equal((wo != 0).sum(0), torch.ones(co, 2, 2, dtype=torch.long))     # each (co, tap) reads one channel
+
+
+@pytest.mark.parametrize("cin", [1, 3])
+@pytest.mark.parametrize("shape", [(2, 7, 9, 1), (1, 10, 12, 2), (1, 5, 6, 8)])
+def test_first_layer_reference_matches_autograd(cin, shape):
+    n, h, w, d = shape
+    g = gen(4)
+    x = torch.randn(n, cin, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(8, cin, 3, 3, generator=g, dtype=torch.float64)
+    dy = torch.randn(n, 8, h, w, generator=g, dtype=torch.float64)
+    xr, wr = x.clone().requires_grad_(True), wt.clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, None, padding=d, dilation=d)
+    gx, gw = torch.autograd.grad(y, (xr, wr), dy)
+    torch.testing.assert_close(X.first_fwd(x, wt, d), nhwc(y.detach()))
+    torch.testing.assert_close(X.first_wgrad(x, nhwc(dy), d), gw)
+    torch.testing.assert_close(X.first_dgrad(nhwc(dy), wt, d), gx)
+
+
+def test_bn_relu_pool_and_column_sums():
+    g = gen(5)
+    y = torch.randn(2, 6, 8, 5, generator=g, dtype=torch.float64)
+    s, t = torch.rand(5, generator=g, dtype=torch.float64) + 0.5, torch.randn(5, generator=g, dtype=torch.float64)
+    a = X.bn_relu(y, s, t)
+    ref = torch.relu(y * s + t)
+    torch.testing.assert_close(a, ref)
+    torch.testing.assert_close(X.maxpool2(a), nhwc(F.max_pool2d(ref.permute(0, 3, 1, 2), 2)))
+    torch.testing.assert_close(X.colsum(a), ref.sum(dim=(0, 1, 2)))
+
+
+def test_exactness_rule():
+    X.assert_exact(9 * 1024, 2, 2)
+    X.assert_exact(4 * 1024 * 1024 - 1, 2, 2)
+    with pytest.raises(AssertionError):
+        X.assert_exact(4 * 1024 * 1024, 2, 2)
+    # weight gradient at 1024^2 bs 4: K = 4.19 M products -> {-1..1}
+    assert X.value_range(4 * 1024 * 1024) == 1 and X.value_range(2 * 1024 * 1024) == 2
+    with pytest.raises(AssertionError):
+        X.value_range(1 << 24)
+    # what the GPU fixtures use: dense weights / inputs in {-2..2} for the deepest K of the network (9 * 1024),
+    # one-hot inputs positive {1, 2}, and exact sums after a power-of-two BatchNorm scale and an integer shift
+    g = gen(6)
+    w = X.dense_conv3x3(64, 1024, g)
+    assert float(w.abs().max()) <= 2 and bool((w == w.round()).all())
+    assert not torch.equal(w, w.flip(2, 3))
+    X.assert_exact(9 * 1024, 2 * 2 + 2, w.abs().max())          # relu(2 * x + t), |x| <= 2, t in {-2..2}
+    s = X.pow2(64, g, (-1, 0, 1))
+    assert bool((torch.log2(s) == torch.log2(s).round()).all())
+    ci_of, tap_of, v_of = X.onehot_route(1024, 512)
+    assert set(tap_of.tolist()) == set(range(9)) and set(v_of.tolist()) == {1, 2, -1}
+    assert set((ci_of // 64).tolist()) == set(range(8))        # every 64-channel block of the input is read
+
+
+def test_bf16_rounding_helper_is_torchs():
+    g = gen(7)
+    x = torch.randn(1 << 16, generator=g) * torch.pow(2.0, torch.randint(-30, 30, (1 << 16,), generator=g).float())
+    bits = torch.randint(-(1 << 31), (1 << 31) - 1, (1 << 16,), generator=g, dtype=torch.int64).to(torch.int32)
+    edge = torch.tensor([0.0, -0.0, 1.0 + 2 ** -8, 1.0 + 3 * 2 ** -8, 257.0, 259.0, 3.4e38, -3.4e38, float("inf"),
+                         float("-inf"), 2 ** -130])
+    for v in (x, bits.view(torch.float32), edge):
+        fin = torch.isfinite(v) | torch.isinf(v)
+        assert torch.equal(X.round_bf16(v[fin]).view(torch.int16), v[fin].to(torch.bfloat16).view(torch.int16))
+        assert bool(torch.isnan(X.round_bf16(v[~fin]).float()).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("where", ["before", "after", "padding", "left_padding"])
+def test_guard_catches_a_single_stray_write(dtype, where):
+    c = X.carve(5, 6, 16, 4, dtype, 2, device="cpu")
+    c.view.fill_(3.0)
+    assert X.guard_violations(c)[1] == 0
+    flat = c.buf
+    pos = {"before": 2 * 16 - 1, "after": (2 + 5) * 16, "padding": (2 + 3) * 16 + 4 + 6, "left_padding": (2 + 1) * 16 + 3}[where]
+    flat[pos] = 0.0
+    where_, nbad = X.guard_violations(c)
+    assert nbad == 1
+    with pytest.raises(AssertionError, match="outside the view"):
+        X.assert_guard(c, "stray")
+    # a different NaN is a write too: the check compares bits, not values
+    flat[pos] = float("nan")
+    assert X.guard_violations(c)[1] == (0 if flat.view(X.INT_VIEW[dtype])[pos] == X._signed(X.NAN_BITS[dtype], dtype) else 1)
+
+
+def test_stats_guard_catches_a_write_past_the_declared_rows():
+    declared = (3 + 64) * 2 * 8
+    c = X.stats_guard(declared, device="cpu")
+    c.view.zero_()
+    assert X.guard_violations(c)[1] == 0
+    c.buf[declared] = 1.0
+    assert X.guard_violations(c) == ([(0, declared)], 1)
+
+
+def test_input_sentinel_is_finite_after_the_bn_affine():
+    for dt in (torch.bfloat16, torch.float32):
+        c = X.carve(2, 2, 4, 1, dt, 1, fill="sentinel", device="cpu")
+        s = torch.tensor(4.0, dtype=dt)
+        assert bool(torch.isfinite(c.buf * s - 2).all())
+
+
+def test_argument_table_matches_the_header():
+    hdr = X.parse_header()
+    assert len(hdr) >= len(SIGNATURES) - 1
+    for sym, names in X.ARGS.items():
+        assert hdr[sym] == names, (sym, hdr[sym], names)
+        assert len(SIGNATURES[sym][1]) == len(names), sym
+        kinds = ["P" if t.__name__ == "c_void_p" else "I" if t.__name__ == "c_int" else "L" for t in SIGNATURES[sym][1]]
+        pos = X.positions(sym, kinds)
+        for key in ("n", "h", "w", "dtype"):
+            assert key in pos, (sym, key)
+        assert all(names[i].startswith("ld") for k, i in pos.items() if k.startswith("ld"))

@@ -1,0 +1,736 @@
+"""Exact-integer and out-of-view-write tests of every convolution route (tests/exact_ref.py explains the exactness rule).
+
+Every output is compared element by element with the exact reference -- no tolerance -- and every byte of an output
+buffer outside its view (padding columns, the other half of a concat buffer, margins, stats rows past the declared
+size) must still hold the NaN guard pattern after the call.  Inputs sit at off > 0 in wider buffers whose unused bytes
+hold a large finite sentinel: a read of the wrong columns or rows that reaches the arithmetic ruins the result.
+
+Route cases: the operator shapes of tests/test_gpu_ops.py, dense and one-hot fixtures, both dtypes.  Production replay:
+one training step of UNetDC(1, 1) per configuration is recorded, and every distinct call (symbol, shapes, lds, dtype,
+optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must reach the same kernel."""
+import ctypes
+import os
+
+import pytest
+import torch
+
+from tests import exact_ref as X
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from tests.test_gpu_ops import CONV_CASES
+    from unet_dc_segmentation_amd import _lib
+    from unet_dc_segmentation_amd._lib import call
+else:
+    CONV_CASES = []
+
+TD = {0: torch.float32, 1: torch.bfloat16}
+MARGIN = 3                      # guard rows before and after every view
+SUM_TOL = 4e-6                  # fp32 statistics / column / BatchNorm-backward sums: |err| <= SUM_TOL * sum|terms| (~64 ulp)
+THIN = os.environ.get("UNETDC_TEST_THIN") == "1"
+SWITCHED = any(k in os.environ for k in ("UNETDC_IGEMM", "UNETDC_WGRAD", "UNETDC_FIRST", "UNETDC_LATTICE", "UNETDC_WGRAD_RING",
+                                         "UNETDC_WGRAD_SPLIT", "UNETDC_WGRAD_RECT", "UNETDC_FIRST_ROWS", "UNETDC_FUSE_BNBWD"))
+KERNELS = set()                 # unetdc_last_kernel() of every route-case call (coverage test at the end)
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def lib():
+    return _lib.load()
+
+
+def last_kernel():
+    return lib().unetdc_last_kernel().decode()
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def wide_range(k, wmax=2):
+    """Largest r <= 255 with k * r * wmax < 2^24: dense activations this wide make most outputs need bf16 rounding (small
+    integers are exact in bf16 and would hide a store that truncates), while staying exact in bf16 storage and fp32 sums."""
+    return min(255, (X.EXACT_LIMIT - 1) // (k * wmax))
+
+
+def big(shape, r, g, lo=None):
+    """Integer fixture of activation size, drawn on the device (seeded from g).  The references run where their inputs are,
+    in fp64: exact for integer data whatever computes it (tests/exact_ref.py)."""
+    gd = torch.Generator(device="cuda").manual_seed(int(torch.randint(1 << 30, (1,), generator=g)))
+    return X.ints(shape, r, gd, lo, device="cuda")
+
+
+def put(data, ld, dt, off=None):
+    """Input view holding `data` ([rows, cols]) at column ld - cols of a sentinel-filled buffer."""
+    rows, cols = data.shape
+    c = X.carve(rows, cols, ld, ld - cols if off is None else off, dt, MARGIN, fill="sentinel")
+    c.view.copy_(data.cuda().to(dt))
+    return c
+
+
+def out(rows, cols, ld, dt, off=None):
+    return X.carve(rows, cols, ld, ld - cols if off is None else off, dt, MARGIN)
+
+
+def dev(t):
+    return t.float().contiguous().cuda()
+
+
+def expect_equal(c, exp, dt, what, shape=None, route=None):
+    """Output view == the storage rounding of the exact value, element by element (torch's round-to-nearest-even
+    conversion, == exact_ref.round_bf16: tests/test_exact_ref_cpu.py), and nothing written outside the view."""
+    want = exp.reshape(c.view.shape).to(torch.float32).cuda().to(dt)
+    if not torch.equal(c.view, want):
+        got = c.view.float().cpu().contiguous()
+        want = want.float().cpu()
+        msg = X.describe_mismatch(got.view(shape) if shape else got, want.view(shape) if shape else want, what, route)
+        assert msg is None, msg
+    X.assert_guard(c, what)
+
+
+def expect_sums(got, terms, what):
+    """fp32 sums (per channel) vs fp64 sums of exact terms [rows, C]."""
+    got = got.double().cpu()
+    assert bool(torch.isfinite(got).all()), f"{what}: channel {int((~torch.isfinite(got)).nonzero()[0])} holds {got[~torch.isfinite(got)][0]} (not written?)"
+    ref, scale = terms.sum(0).cpu(), terms.abs().sum(0).cpu()
+    err = (got - ref).abs()
+    bad = ~(err <= SUM_TOL * scale)                 # NaN-strict
+    assert not bool(bad.any()), f"{what}: channel {int(bad.nonzero()[0])} off by {float(err.max())} (sum|terms| {float(scale.max())})"
+
+
+# ---------------------------------------------------------------------------------------------------- runners
+# kw: the header's argument names -> values (shapes, lds, dtype; 'ptr:<name>' = whether an optional pointer is given;
+# 'workspace_bytes').  fix: 'dense' or 'onehot'.  Every runner returns the kernel the call reached.
+
+def conv_fwd(kw, fix, seed=1):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    affine, stats = kw.get("ptr:scale", False), kw.get("ptr:stats_part", True)
+    if fix == "dense":
+        x, wt, route = big((P, ci), wide_range(9 * ci), g), X.dense_conv3x3(co, ci, g), None
+    else:
+        x = big((P, ci), 2, g, lo=1)
+        wt, route = X.onehot_conv3x3(co, ci)
+    X.assert_exact(9 * ci, x.abs().max(), 2)
+    x4 = x.view(n, h, w, ci)
+    acc = X.conv3x3_fwd_onehot(x4, route, co, d) if route else X.conv3x3_fwd(x4, wt, d)
+    bias = None if affine else X.ints((co,), 2, g)
+    sc, sh = (X.pow2(co, g, (-1, 0, 1)), X.ints((co,), 2, g)) if affine else (None, None)
+    exp = X.bn_relu(acc, sc, sh) if affine else acc.double() + bias.to(acc.device, torch.float64)
+    xc = put(x, kw.get("ldx", ci + 64), dt)
+    yc = out(P, co, kw.get("ldy", 2 * co), dt)
+    wf = pack_conv(wt, dt)[0]
+    rows = lib().unetdc_conv3x3_stats_rows(P, co)
+    st = X.stats_guard((rows + 64) * 2 * co) if stats and not affine else None
+    live = ctypes.c_int(-1)
+    bd, scd, shd = (None if t is None else dev(t) for t in (bias, sc, sh))
+    call("unetdc_conv3x3_fwd", xc.view.data_ptr(), xc.ld, wf.data_ptr(), ptr(bd), ptr(scd), ptr(shd), yc.view.data_ptr(), yc.ld,
+         None if st is None else st.view.data_ptr(), ctypes.byref(live), n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(yc, exp, dt, f"conv3x3_fwd[{name}]", (n, h, w, co), route)
+    if st is not None:
+        check_stats(st, rows, live.value, yc, co, f"conv3x3_fwd stats[{name}]")
+    return name
+
+
+def check_stats(st, rows, live, yc, co, what):
+    torch.cuda.synchronize()
+    X.assert_guard(st, what)
+    part = st.view.cpu().reshape(-1)[: rows * 2 * co].view(rows, 2, co)
+    if live >= 0:                                   # rows past the live count are declared zero
+        assert 1 <= live <= rows, (what, live, rows)
+        assert bool((part[live:] == 0).all()), f"{what}: declared zero rows {live}..{rows} are not zero"
+    else:                                           # no live count: every declared row carries data
+        live = rows
+    bad = ~torch.isfinite(part[:live])
+    assert not bool(bad.any()), f"{what}: partial row {int(bad.nonzero()[0][0])} not written"
+    y = yc.view.double()
+    tot = part.double().sum(0)
+    expect_sums(tot[0], y, what + " sum")
+    expect_sums(tot[1], y * y, what + " sum of squares")
+
+
+def conv_fwd_bnin(kw, fix, seed=2):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    act_out = kw.get("ptr:act_out", False)
+    mode = lib().unetdc_conv3x3_bnin_supported(n, h, w, ci, co, d, kw["dtype"])
+    assert mode >= (2 if act_out else 1), (kw, mode)
+    g = gen(seed)
+    s = X.pow2(ci, g, (0, 1))
+    if fix == "dense":
+        xr, t, wt, route = big((P, ci), 2, g), X.ints((ci,), 2, g), X.dense_conv3x3(co, ci, g), None
+    else:
+        xr, t = big((P, ci), 2, g, lo=1), X.ints((ci,), 1, g, lo=-2)        # relu clamps where s x + t <= 0
+        wt, route = X.onehot_conv3x3(co, ci)
+    act = X.bn_relu(xr, s, t)
+    X.assert_exact(9 * ci, act.abs().max(), 2)
+    a4 = act.view(n, h, w, ci)
+    acc = X.conv3x3_fwd_onehot(a4, route, co, d) if route else X.conv3x3_fwd(a4, wt, d)
+    bias = X.ints((co,), 2, g)
+    xc = put(xr, kw.get("ldx", ci + 64), dt)
+    yc = out(P, co, kw.get("ldy", 2 * co), dt)
+    ac = out(P, ci, kw.get("ldact", ci + 32), dt) if act_out else None
+    wf = pack_conv(wt, dt)[0]
+    rows = lib().unetdc_conv3x3_stats_rows(P, co)
+    st = X.stats_guard((rows + 64) * 2 * co)
+    live = ctypes.c_int(-1)
+    sd, td, bd = dev(s), dev(t), dev(bias)
+    call("unetdc_conv3x3_fwd_bnin", xc.view.data_ptr(), xc.ld, sd.data_ptr(), td.data_ptr(), wf.data_ptr(), bd.data_ptr(),
+         yc.view.data_ptr(), yc.ld, st.view.data_ptr(), ctypes.byref(live), None if ac is None else ac.view.data_ptr(),
+         0 if ac is None else ac.ld, n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(yc, acc.double() + bias.to(acc.device, torch.float64), dt, f"conv3x3_fwd_bnin[{name}]", (n, h, w, co), route)
+    check_stats(st, rows, live.value, yc, co, f"conv3x3_fwd_bnin stats[{name}]")
+    if ac is not None:
+        expect_equal(ac, act, dt, f"conv3x3_fwd_bnin act_out[{name}]", (n, h, w, ci))
+    return name
+
+
+def conv_dgrad(kw, fix, variant, seed=3):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    dy = big((P, co), wide_range(9 * co) if fix == "dense" else 2, g)
+    wt, route = (X.dense_conv3x3(co, ci, g), None) if fix == "dense" else X.onehot_conv3x3(co, ci)
+    X.assert_exact(9 * co, dy.abs().max(), 2)
+    d4 = dy.view(n, h, w, co)
+    exp = X.conv3x3_dgrad_onehot(d4, route, ci, d) if route else X.conv3x3_dgrad(d4, wt, d)
+    dyc = put(dy, kw.get("lddy", co + 64), dt)
+    dxc = out(P, ci, kw.get("lddx", ci + 32), dt)
+    wd = pack_conv(wt, dt)[1]
+    args = (dyc.view.data_ptr(), dyc.ld, wd.data_ptr(), dxc.view.data_ptr(), dxc.ld)
+    tail = (n, h, w, ci, co, d, kw["dtype"], stream())
+    extra = None
+    if variant == "plain":
+        call("unetdc_conv3x3_dgrad", *args, *tail)
+    elif variant == "colsum":
+        c0, c = kw.get("c0", 0), kw.get("c", ci // 2)
+        cs = X.stats_guard(c)
+        nb = max(lib().unetdc_conv3x3_dgrad_colsum_workspace(n, h, w, ci), kw.get("workspace_bytes", 0))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device="cuda")
+        call("unetdc_conv3x3_dgrad_colsum", *args, cs.view.data_ptr(), c0, c, ws.data_ptr(), nb, *tail)
+        extra = ("colsum", cs, c0, c)
+    else:
+        extra = bnstats_call("unetdc_conv3x3_dgrad_bnstats", args, tail, P, ci, dt, g, kw)
+    name = last_kernel()
+    expect_equal(dxc, exp, dt, f"conv3x3_dgrad/{variant}[{name}]", (n, h, w, ci), None)
+    check_extra(extra, dxc, f"conv3x3_dgrad/{variant}[{name}]")
+    return name
+
+
+def bnstats_call(sym, args, tail, P, ci, dt, g, kw):
+    """The BatchNorm-backward partial sums of the consuming stage, with exact constants: integer y_prev / shift / mean,
+    power-of-two scale / rstd (gate and xhat are exact; the sums are compared with SUM_TOL)."""
+    yp = big((P, ci), 2, g)
+    sc, sh, mu, rs = X.pow2(ci, g, (-1, 0, 1)), X.ints((ci,), 2, g), X.ints((ci,), 1, g), X.pow2(ci, g, (-1, 0))
+    ypc = put(yp, kw.get("ldy_prev", ci + 64), dt)
+    rows = lib().unetdc_conv3x3_stats_rows(P, ci)
+    parts = X.stats_guard((rows + 64) * 3 * ci)
+    npart = ctypes.c_int(-1)
+    dv = [dev(t) for t in (sc, sh, mu, rs)]
+    call(sym, *args, ypc.view.data_ptr(), ypc.ld, *(t.data_ptr() for t in dv), parts.view.data_ptr(), (rows + 64) * 3 * ci,
+         ctypes.byref(npart), *tail)
+    return ("bnstats", parts, yp, (sc, sh, mu, rs), npart, rows, dv)
+
+
+def check_extra(extra, dxc, what):
+    if extra is None:
+        return
+    torch.cuda.synchronize()
+    if extra[0] == "colsum":
+        _, cs, c0, c = extra
+        X.assert_guard(cs, what + " colsum")
+        expect_sums(cs.view.cpu().reshape(-1), dxc.view.double()[:, c0:c0 + c], what + " colsum")
+        return
+    _, parts, yp, (sc, sh, mu, rs), npart, rows, _ = extra
+    X.assert_guard(parts, what + " parts")
+    ci = yp.shape[1]
+    assert 1 <= npart.value <= rows + 64, (what, npart.value)
+    rows_ = parts.view.cpu().reshape(-1)[: npart.value * 3 * ci].view(npart.value, 3, ci)
+    bad = ~torch.isfinite(rows_)
+    assert not bool(bad.any()), f"{what}: parts row {int(bad.nonzero()[0][0])} not written"
+    pc = rows_.double().sum(0)
+    dx, y = dxc.view.double(), yp.cuda().double()
+    sc, sh, mu, rs = (t.cuda().double() for t in (sc, sh, mu, rs))
+    gate = (y * sc + sh) > 0
+    gh = torch.where(gate, dx, torch.zeros_like(dx))
+    xh = (y - mu) * rs
+    expect_sums(pc[0], gh, what + " S1")
+    expect_sums(pc[1], gh * xh, what + " S2")
+    if not SWITCHED:                             # the fused epilogues leave the third row zero (include/unetdc_hip.h)
+        assert bool((rows_[:, 2] == 0).all()), f"{what}: third parts row is not zero"
+    elif not bool((rows_[:, 2] == 0).all()):     # the stand-alone reduction behind the first-generation kernels sums xhat
+        expect_sums(pc[2], xh, what + " S3")
+
+
+def conv_wgrad(kw, fix, bnin=False, seed=4):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    s = X.pow2(ci, g, (0, 1)) if bnin else None
+    if fix == "dense":              # x, dy and (bnin) the shift in {-1..1}: relu(s x + t) <= 3
+        x = big((P, ci), 1, g)
+        t = X.ints((ci,), 1, g) if bnin else None
+        dy = big((P, co), 1, g)
+        xa = X.bn_relu(x, s, t) if bnin else x
+        X.assert_exact(P, xa.abs().max(), 1)
+        exp = X.conv3x3_wgrad(xa.view(n, h, w, ci), dy.view(n, h, w, co), d)
+    else:                           # separable input x = a (x) u: nine matrix-vector products on the host
+        if bnin:                    # a in {0, 1}, t <= 0: act = relu(s a u + t) = a relu(s u + t), mixed signs and clamps
+            s = X.pow2(ci, g, (0, 1) if 2 * P * 2 < X.EXACT_LIMIT else (0,))
+        r = X.value_range(P * int(s.max()) if bnin else P, 1)
+        a = big((n, h, w), 1, g, lo=0 if bnin else -1)
+        u = X.ints((ci,), r, g)
+        t = X.ints((ci,), 0, g, lo=-2) if bnin else None
+        dy = big((P, co), 1, g)
+        x = (a.view(P, 1) * u.to(a.device).view(1, ci))
+        exp = X.conv3x3_wgrad_separable(a, X.bn_relu(u, s, t) if bnin else u, dy.view(n, h, w, co), d)
+    xc = put(x, kw.get("ldx", ci + 64), dt)
+    dyc = put(dy, kw.get("lddy", co + 32), dt)
+    dw = X.stats_guard(co * ci * 9)
+    nb = max(lib().unetdc_conv3x3_wgrad_workspace(n, h, w, ci, co, kw["dtype"]), kw.get("workspace_bytes", 0))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device="cuda")
+    if bnin:
+        sd, td = dev(s), dev(t)
+        call("unetdc_conv3x3_wgrad_bnin", xc.view.data_ptr(), xc.ld, sd.data_ptr(), td.data_ptr(), dyc.view.data_ptr(), dyc.ld,
+             dw.view.data_ptr(), ws.data_ptr(), nb, n, h, w, ci, co, d, kw["dtype"], stream())
+    else:
+        call("unetdc_conv3x3_wgrad", xc.view.data_ptr(), xc.ld, dyc.view.data_ptr(), dyc.ld, dw.view.data_ptr(), ws.data_ptr(), nb,
+             n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(dw, exp, torch.float32, f"conv3x3_wgrad{'_bnin' if bnin else ''}[{name}]", (co, ci, 3, 3))
+    return name
+
+
+def first_fwd(kw, fix, seed=5):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    affine, stats = kw.get("ptr:scale", False), kw.get("ptr:stats_part", True)
+    x = big((n, ci, h, w), 2, g, lo=1 if fix == "onehot" else None)
+    wt, route = (X.dense_conv3x3(co, ci, g), None) if fix == "dense" else X.onehot_conv3x3(co, ci)
+    acc = X.first_fwd(x, wt, d)
+    bias = None if affine else X.ints((co,), 2, g)
+    sc, sh = (X.pow2(co, g, (-1, 0, 1)), X.ints((co,), 2, g)) if affine else (None, None)
+    exp = X.bn_relu(acc, sc, sh) if affine else acc.double() + bias.to(acc.device, torch.float64)
+    xc = put(x.view(n * ci, h * w), h * w, torch.float32)
+    yc = out(P, co, kw.get("ldy", co + 64), dt)
+    rows = lib().unetdc_conv3x3_first_stats_rows(P, ci, co)
+    st = X.stats_guard((rows + 64) * 2 * co) if stats and not affine else None
+    wd_, bd, scd, shd = (None if t is None else dev(t) for t in (wt, bias, sc, sh))
+    call("unetdc_conv3x3_first_fwd", xc.view.data_ptr(), wd_.data_ptr(), ptr(bd), ptr(scd), ptr(shd), yc.view.data_ptr(), yc.ld,
+         None if st is None else st.view.data_ptr(), n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(yc, exp, dt, f"first_fwd[{name}]", (n, h, w, co), route)
+    if st is not None:
+        check_stats(st, rows, -1, yc, co, f"first_fwd stats[{name}]")
+    return name
+
+
+def first_wgrad(kw, fix, seed=6):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    r = X.value_range(P)
+    x = big((n, ci, h, w), r, g, lo=0 if fix == "onehot" else None)
+    dy = big((P, co), r, g)
+    exp = X.first_wgrad(x, dy.view(n, h, w, co), d)
+    xc = put(x.view(n * ci, h * w), h * w, torch.float32)
+    dyc = put(dy, kw.get("lddy", co + 64), dt)
+    dw = X.stats_guard(co * ci * 9)
+    nb = max(lib().unetdc_conv3x3_first_wgrad_workspace(n, h, w, ci, co), kw.get("workspace_bytes", 0))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device="cuda")
+    call("unetdc_conv3x3_first_wgrad", xc.view.data_ptr(), dyc.view.data_ptr(), dyc.ld, dw.view.data_ptr(), ws.data_ptr(), nb,
+         n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(dw, exp, torch.float32, f"first_wgrad[{name}]", (co, ci, 3, 3))
+    return name
+
+
+def first_dgrad(kw, fix, seed=7):
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    dy = big((P, co), 2, g)
+    wt = X.dense_conv3x3(co, ci, g) if fix == "dense" else X.onehot_conv3x3(co, ci)[0]
+    exp = X.first_dgrad(dy.view(n, h, w, co), wt, d)
+    dyc = put(dy, kw.get("lddy", co + 64), dt)
+    dxc = out(n * ci, h * w, h * w, torch.float32)
+    wd_ = dev(wt)
+    call("unetdc_conv3x3_first_dgrad", dyc.view.data_ptr(), dyc.ld, wd_.data_ptr(), dxc.view.data_ptr(), n, h, w, ci, co, d,
+         kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(dxc, exp.reshape(n * ci, h * w), torch.float32, f"first_dgrad[{name}]", (n, ci, h, w))
+    return name
+
+
+def first_wgrad_bn(kw, fix, seed=12):
+    """The first layer's weight gradient with the BatchNorm + ReLU backward applied on load: dy = k1 [s y + t > 0] dz - k2
+    - k3 xhat, xhat = (y - mean) rstd.  Integer y / dz / shift / mean / k2 / k3 and power-of-two scale / rstd / k1 make
+    dy exact (and exactly representable in bf16), so dw is compared bit for bit."""
+    n, h, w, ci, co, d, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], kw["dilation"], TD[kw["dtype"]]
+    P = n * h * w
+    assert lib().unetdc_conv3x3_first_wgrad_bn_supported(n, h, w, ci, co, d, kw["dtype"]) == 1, kw
+    g = gen(seed)
+    wide = 6 * P < X.EXACT_LIMIT                 # |dy| <= 6, else k1 = 1 and k3 = 0: |dy| <= 2
+    x = big((n, ci, h, w), 1, g, lo=0 if fix == "onehot" else -1)
+    dz, y = big((P, co), 1, g), big((P, co), 2, g)
+    sc, sh = X.pow2(co, g, (-1, 0, 1)), X.ints((co,), 2, g)
+    mu, rs = X.ints((co,), 1, g), X.pow2(co, g, (-1, 0))
+    k1 = X.pow2(co, g, (0, 1) if wide else (0,))
+    k2, k3 = X.ints((co,), 1, g), X.ints((co,), 1 if wide else 0, g)
+    to = lambda t_: t_.to(y.device, torch.float64)    # noqa: E731
+    gate = (y.double() * to(sc) + to(sh)) > 0
+    dy = to(k1) * torch.where(gate, dz.double(), torch.zeros_like(y, dtype=torch.float64)) - to(k2) \
+        - to(k3) * (y.double() - to(mu)) * to(rs)
+    X.assert_exact(P, 1, dy.abs().max())
+    exp = X.first_wgrad(x, dy.view(n, h, w, co), d)
+    xc = put(x.view(n * ci, h * w), h * w, torch.float32)
+    dzc = put(dz, kw.get("lddz", co + 64), dt)
+    yc = put(y, kw.get("ldy", co + 32), dt)
+    dw = X.stats_guard(co * ci * 9)
+    nb = max(lib().unetdc_conv3x3_first_wgrad_workspace(n, h, w, ci, co), kw.get("workspace_bytes", 0))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device="cuda")
+    dv = [dev(t) for t in (sc, sh, mu, rs, torch.cat([k1, k2, k3]))]
+    call("unetdc_conv3x3_first_wgrad_bn", xc.view.data_ptr(), dzc.view.data_ptr(), dzc.ld, yc.view.data_ptr(), yc.ld,
+         *(t.data_ptr() for t in dv), dw.view.data_ptr(), ws.data_ptr(), nb, n, h, w, ci, co, d, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(dw, exp, torch.float32, f"first_wgrad_bn[{name}]", (co, ci, 3, 3))
+    return name
+
+
+def convt_fwd(kw, fix, seed=8):
+    n, h, w, ci, co, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    x = big((P, ci), 2, g, lo=1 if fix == "onehot" else None)
+    wt = X.ints((ci, co, 2, 2), 2, g) if fix == "dense" else X.onehot_convT2x2(ci, co)
+    bias = X.ints((co,), 2, g)
+    exp = X.convT2x2_fwd(x.view(n, h, w, ci), wt, bias)
+    xc = put(x, kw.get("ldx", ci + 64), dt)
+    uc = out(4 * P, co, kw.get("ldup", 2 * co), dt, off=0)      # the first half of a concat buffer
+    wf = pack_convt(wt, dt)[0]
+    bd = dev(bias)
+    call("unetdc_convT2x2_fwd", xc.view.data_ptr(), xc.ld, wf.data_ptr(), bd.data_ptr(), uc.view.data_ptr(), uc.ld, n, h, w, ci, co,
+         kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(uc, exp, dt, f"convT2x2_fwd[{name}]", (n, 2 * h, 2 * w, co))
+    return name
+
+
+def convt_dgrad(kw, fix, bnstats=False, seed=9):
+    n, h, w, ci, co, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    dup = big((4 * P, co), 2, g)
+    wt = X.ints((ci, co, 2, 2), 2, g) if fix == "dense" else X.onehot_convT2x2(ci, co)
+    exp = X.convT2x2_dgrad(dup.view(n, 2 * h, 2 * w, co), wt)
+    dc = put(dup, kw.get("lddup", 2 * co), dt, off=0)
+    dxc = out(P, ci, kw.get("lddx", ci + 32), dt)
+    wd = pack_convt(wt, dt)[1]
+    args = (dc.view.data_ptr(), dc.ld, wd.data_ptr(), dxc.view.data_ptr(), dxc.ld)
+    tail = (n, h, w, ci, co, kw["dtype"], stream())
+    extra = None
+    if bnstats:
+        extra = bnstats_call("unetdc_convT2x2_dgrad_bnstats", args, tail, P, ci, dt, g, kw)
+    else:
+        call("unetdc_convT2x2_dgrad", *args, *tail)
+    name = last_kernel()
+    expect_equal(dxc, exp, dt, f"convT2x2_dgrad{'_bnstats' if bnstats else ''}[{name}]", (n, h, w, ci))
+    check_extra(extra, dxc, f"convT2x2_dgrad_bnstats[{name}]")
+    return name
+
+
+def convt_wgrad(kw, fix, seed=10):
+    n, h, w, ci, co, dt = kw["n"], kw["h"], kw["w"], kw["cin"], kw["cout"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    r = X.value_range(P)
+    x = big((P, ci), r, g, lo=0 if fix == "onehot" else None)
+    dup = big((4 * P, co), r, g)
+    exp = X.convT2x2_wgrad(x.view(n, h, w, ci), dup.view(n, 2 * h, 2 * w, co))
+    xc = put(x, kw.get("ldx", ci + 64), dt)
+    dc = put(dup, kw.get("lddup", 2 * co), dt, off=0)
+    dw = X.stats_guard(ci * co * 4)
+    nb = max(lib().unetdc_convT2x2_wgrad_workspace(n, h, w, ci, co, kw["dtype"]), kw.get("workspace_bytes", 0))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device="cuda")
+    call("unetdc_convT2x2_wgrad", xc.view.data_ptr(), xc.ld, dc.view.data_ptr(), dc.ld, dw.view.data_ptr(), ws.data_ptr(), nb,
+         n, h, w, ci, co, kw["dtype"], stream())
+    name = last_kernel()
+    expect_equal(dw, exp, torch.float32, f"convT2x2_wgrad[{name}]", (ci, co, 2, 2))
+    return name
+
+
+def bn_relu_apply(kw, fix, seed=11):
+    """relu(s y + t) with a power-of-two s and an integer t, and the 2x2 max-pool of the stored activation."""
+    n, h, w, c, dt = kw["n"], kw["h"], kw["w"], kw["c"], TD[kw["dtype"]]
+    P = n * h * w
+    g = gen(seed)
+    affine, pool, store = kw.get("ptr:scale", True), kw.get("ptr:pooled", True), kw.get("ptr:a", True)
+    y = big((P, c), 2, g) if fix == "dense" else big((P, c), 2, g) * 64 + big((P, c), 1, g)
+    sc, sh = X.pow2(c, g, (-1, 0, 1)), X.ints((c,), 2, g)
+    a = X.bn_relu(y, sc, sh) if affine else y.double()
+    yc = put(y, kw.get("ldy", c + 64), dt)
+    ac = out(P, c, kw.get("lda", 2 * c), dt) if store else None
+    pc = out(P // 4, c, kw.get("ldp", c + 32), dt) if pool else None
+    scd, shd = (dev(sc), dev(sh)) if affine else (None, None)
+    call("unetdc_bn_relu_apply", yc.view.data_ptr(), yc.ld, ptr(scd), ptr(shd), None if ac is None else ac.view.data_ptr(),
+         0 if ac is None else ac.ld, None if pc is None else pc.view.data_ptr(), 0 if pc is None else pc.ld, n, h, w, c, kw["dtype"],
+         stream())
+    if ac is not None:
+        expect_equal(ac, a, dt, "bn_relu_apply", (n, h, w, c))
+    if pc is not None:
+        stored = X.to_storage(a, dt).float().view(n, h, w, c)
+        expect_equal(pc, X.maxpool2(stored), dt, "bn_relu_apply pooled", (n, h // 2, w // 2, c))
+    return None
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def pack_conv(wt, dt):
+    co, ci = wt.shape[:2]
+    wd = dev(wt)
+    wf = torch.empty(9 * co * ci, dtype=dt, device="cuda")
+    wg = torch.empty(9 * co * ci, dtype=dt, device="cuda")
+    call("unetdc_pack_conv3x3", wd.data_ptr(), wf.data_ptr(), wg.data_ptr(), co, ci, 1 if dt == torch.bfloat16 else 0, stream())
+    return wf, wg
+
+
+def pack_convt(wt, dt):
+    ci, co = wt.shape[:2]
+    wd = dev(wt)
+    wf = torch.empty(4 * co * ci, dtype=dt, device="cuda")
+    wg = torch.empty(4 * co * ci, dtype=dt, device="cuda")
+    call("unetdc_pack_convT2x2", wd.data_ptr(), wf.data_ptr(), wg.data_ptr(), ci, co, 1 if dt == torch.bfloat16 else 0, stream())
+    return wf, wg
+
+
+# ---------------------------------------------------------------------------------------------------- route cases
+FIXTURES = ["dense", "onehot"]
+DTYPES = {"f32": 0, "bf16": 1}
+ROUTE_CASES = list(CONV_CASES)
+WGRAD_CASES = [(2, 512, 256, 64, 64, 1), (1, 520, 512, 128, 64, 1), (4, 256, 256, 64, 128, 2), (2, 128, 128, 256, 128, 8),
+               (8, 64, 64, 128, 256, 4), (5, 64, 64, 1024, 512, 1),                      # tap-fused (wgrad_fused.hip)
+               (2, 32, 32, 256, 256, 16), (1, 16, 24, 256, 512, 8), (3, 24, 40, 512, 256, 16),    # valid rectangles (bf16)
+               (2, 96, 80, 64, 64, 2)]                                                   # K split with a ragged last slice
+BNIN_CASES = [(2, 256, 256, 64, 64, 1), (2, 64, 256, 64, 64, 2), (2, 128, 128, 128, 128, 1), (2, 64, 256, 128, 128, 2),
+              (3, 64, 192, 128, 256, 1), (1, 128, 256, 256, 256, 1)]
+CONVT_CASES = [(2, 8, 12, 128, 64), (1, 16, 16, 256, 128), (1, 4, 4, 1024, 512), (2, 32, 32, 256, 128), (1, 64, 64, 128, 64),
+               (2, 16, 96, 512, 256), (1, 4, 32, 128, 64), (3, 8, 32, 128, 64)]
+FIRST_CASES = [(2, 24, 40, 1), (2, 64, 64, 2), (3, 10, 10, 1), (1, 8, 8, 1), (2, 96, 136, 1)]
+FIRST_BN_CASES = [(2, 16, 24), (1, 64, 64), (3, 40, 96)]
+if THIN:                        # (CONV_CASES arrives thinned from tests/test_gpu_ops.py already)
+    WGRAD_CASES, CONVT_CASES = WGRAD_CASES[::3], CONVT_CASES[::2]
+ROUTE_RUN = []                  # route-case items run in this session (test_route_coverage needs all of them)
+
+
+def dense_affordable(case, fix):
+    """The dense fixture needs a full GEMM on the host: maps of >= 128K pixels run the one-hot fixture only (their routes'
+    dense arithmetic is the same kernel code as at the smaller maps)."""
+    if fix == "dense" and case[0] * case[1] * case[2] >= 131072:
+        pytest.skip("large map: one-hot fixture only (host reference cost)")
+
+
+def kwargs(case, dtype, **extra):
+    n, h, w, cin, cout, d = case
+    return dict(n=n, h=h, w=w, cin=cin, cout=cout, dilation=d, dtype=DTYPES[dtype], **extra)
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case", ROUTE_CASES)
+def test_exact_conv3x3_routes(case, dtype, fix):
+    """conv3x3_fwd in store / stats / affine-ReLU modes, dgrad, dgrad_colsum, dgrad_bnstats and wgrad."""
+    ROUTE_RUN.append(1)
+    dense_affordable(case, fix)
+    kw = kwargs(case, dtype)
+    for mode in ({"ptr:stats_part": False}, {"ptr:stats_part": True}, {"ptr:scale": True}):
+        KERNELS.add(conv_fwd(dict(kw, **mode), fix))
+    for variant in ("plain", "colsum", "bnstats"):
+        KERNELS.add(conv_dgrad(kw, fix, variant))
+    KERNELS.add(conv_wgrad(kw, fix))
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case", WGRAD_CASES)
+def test_exact_wgrad_routes(case, dtype, fix):
+    """Tap-fused, valid-rectangle and K-split weight gradients."""
+    ROUTE_RUN.append(1)
+    dense_affordable(case, fix)
+    KERNELS.add(conv_wgrad(kwargs(case, dtype), fix))
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("case", BNIN_CASES)
+def test_exact_normalise_on_load(case, fix):
+    """conv3x3_fwd_bnin with and without act_out, conv3x3_wgrad_bnin (bf16)."""
+    ROUTE_RUN.append(1)
+    kw = kwargs(case, "bf16")
+    if os.environ.get("UNETDC_LATTICE") == "0" or lib().unetdc_conv3x3_bnin_supported(*case, 1) == 0:
+        pytest.skip("no normalise-on-load form under this switch set")
+    KERNELS.add(conv_fwd_bnin(kw, fix))
+    if case[4] % 128 == 0:
+        KERNELS.add(conv_fwd_bnin(dict(kw, **{"ptr:act_out": True}), fix))
+    KERNELS.add(conv_wgrad(kw, fix, bnin=True))
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case", CONVT_CASES)
+def test_exact_conv_transpose_routes(case, dtype, fix):
+    ROUTE_RUN.append(1)
+    n, h, w, cin, cout = case
+    kw = dict(n=n, h=h, w=w, cin=cin, cout=cout, dtype=DTYPES[dtype])
+    KERNELS.add(convt_fwd(kw, fix))
+    KERNELS.add(convt_dgrad(kw, fix))
+    KERNELS.add(convt_dgrad(kw, fix, bnstats=True))
+    KERNELS.add(convt_wgrad(kw, fix))
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("cin", [1, 3])
+@pytest.mark.parametrize("shape", FIRST_CASES)
+def test_exact_first_layer_routes(shape, cin, dtype, fix):
+    ROUTE_RUN.append(1)
+    n, h, w, d = shape
+    kw = dict(n=n, h=h, w=w, cin=cin, cout=64, dilation=d, dtype=DTYPES[dtype])
+    KERNELS.add(first_fwd(kw, fix))
+    KERNELS.add(first_fwd(dict(kw, **{"ptr:scale": True}), fix))
+    KERNELS.add(first_wgrad(kw, fix))
+    KERNELS.add(first_dgrad(kw, fix))
+
+
+@pytest.mark.parametrize("fix", FIXTURES)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case", FIRST_BN_CASES)
+def test_exact_first_layer_wgrad_bn_on_load(case, dtype, fix):
+    """unetdc_conv3x3_first_wgrad_bn: one input channel, dilation 1 (the production first-layer weight gradient)."""
+    ROUTE_RUN.append(1)
+    n, h, w = case
+    if SWITCHED and lib().unetdc_conv3x3_first_wgrad_bn_supported(n, h, w, 1, 64, 1, DTYPES[dtype]) == 0:
+        pytest.skip("no on-load form under this switch set (the row-run kernel is off)")
+    KERNELS.add(first_wgrad_bn(dict(n=n, h=h, w=w, cin=1, cout=64, dilation=1, dtype=DTYPES[dtype]), fix))
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("pool", [False, True])
+@pytest.mark.parametrize("case", [(2, 16, 24, 64), (1, 8, 8, 1024), (3, 4, 4, 256), (2, 64, 96, 128)])
+def test_exact_bn_relu_apply(case, pool, dtype):
+    n, h, w, c = case
+    bn_relu_apply(dict(n=n, h=h, w=w, c=c, dtype=DTYPES[dtype], **{"ptr:pooled": pool}), "dense")
+
+
+FAMILIES = ["igemm_lattice_wide_kernel<1>", "igemm_lattice_wide_kernel<2>", "igemm_lattice_wide_kernel<4>",
+            "igemm_lattice_wide_kernel<1> bnin", "igemm_lattice_kernel<", "blocks16x16", "igemm_halo", "igemm_dma_kernel",
+            "wgrad_ring", "wgrad_fused", "wgrad_rect_kernel", "convt_wgrad_kernel", "first_mfma_fwd_kernel", "first_mfma_wgrad_kernel",
+            "first_wgrad_rows_kernel", "first_conv_fwd_kernel", "first_dgrad_kernel", "first_wgrad_rows_kernel<__bf16> bn",
+            "first_wgrad_rows_kernel<float> bn"]
+ROUTE_ITEMS = lambda: 4 * (len(ROUTE_CASES) + len(WGRAD_CASES) + len(CONVT_CASES) + len(FIRST_BN_CASES)) \
+    + 2 * len(BNIN_CASES) + 8 * len(FIRST_CASES)    # noqa: E731
+
+
+def test_route_coverage():
+    """The route cases above reached every kernel family the default build dispatches to."""
+    if SWITCHED or THIN:
+        pytest.skip("coverage is asserted for the default routes over the full case list")
+    if len(ROUTE_RUN) != ROUTE_ITEMS():           # it reads the kernels those items reached: a subset proves nothing
+        pytest.skip(f"needs every route-case item in this session before it ({len(ROUTE_RUN)} of {ROUTE_ITEMS()} ran)")
+    names = sorted(k for k in KERNELS if k)
+    print("\n".join(["kernels reached:"] + names))
+    missing = [f for f in FAMILIES if not any(f in k for k in names)]
+    assert not missing, (missing, names)
+    for mode in (0, 1, 2, 4):                     # the narrow lattice kernel in every epilogue mode (4: BatchNorm-backward sums)
+        assert any(k.startswith("igemm_lattice_kernel<") and f", {mode}>" in k for k in names), (mode, names)
+    assert any(k.startswith("igemm_lattice_kernel<") and k.endswith("bnin") for k in names), names
+
+
+# ---------------------------------------------------------------------------------------------------- production replay
+RUNNERS = {
+    "unetdc_conv3x3_fwd": lambda kw: conv_fwd(kw, "onehot"),
+    "unetdc_conv3x3_fwd_bnin": lambda kw: conv_fwd_bnin(kw, "onehot"),
+    "unetdc_conv3x3_dgrad": lambda kw: conv_dgrad(kw, "onehot", "plain"),
+    "unetdc_conv3x3_dgrad_colsum": lambda kw: conv_dgrad(kw, "onehot", "colsum"),
+    "unetdc_conv3x3_dgrad_bnstats": lambda kw: conv_dgrad(kw, "onehot", "bnstats"),
+    "unetdc_conv3x3_wgrad": lambda kw: conv_wgrad(kw, "onehot"),
+    "unetdc_conv3x3_wgrad_bnin": lambda kw: conv_wgrad(kw, "onehot", bnin=True),
+    "unetdc_conv3x3_first_fwd": lambda kw: first_fwd(kw, "onehot"),
+    "unetdc_conv3x3_first_wgrad": lambda kw: first_wgrad(kw, "onehot"),
+    "unetdc_conv3x3_first_wgrad_bn": lambda kw: first_wgrad_bn(kw, "onehot"),
+    "unetdc_convT2x2_fwd": lambda kw: convt_fwd(kw, "onehot"),
+    "unetdc_convT2x2_dgrad": lambda kw: convt_dgrad(kw, "onehot"),
+    "unetdc_convT2x2_dgrad_bnstats": lambda kw: convt_dgrad(kw, "onehot", bnstats=True),
+    "unetdc_convT2x2_wgrad": lambda kw: convt_wgrad(kw, "onehot"),
+    "unetdc_bn_relu_apply": lambda kw: bn_relu_apply(kw, "onehot"),
+}
+REPLAY_CONFIGS = {"bf16_8x512": ("bf16", 8, 512), "f32_8x512": ("f32", 8, 512), "bf16_4x1024": ("bf16", 4, 1024)}
+# 1024^2: the forward and weight-gradient calls only (the host reference of the whole step is over the time budget;
+# its input-gradient calls take the same kernels as at 512^2 with twice the items per workgroup)
+REPLAY_ONLY = {"bf16_4x1024": ("fwd", "wgrad")}
+
+
+def record_step(dtype, bs, size):
+    from models.model_2 import UNetDC
+    from oracle import recipe
+    from utils.metrics_DC import focal_dice_loss
+    torch.manual_seed(5)
+    model = UNetDC(1, 1).cuda().train()
+    if dtype == "bf16":
+        model.set_compute_dtype("bf16")
+    x = recipe.seeded_input(8, (bs, 1, size, size)).cuda()
+    t = recipe.seeded_target(9, (bs, 1, size, size), frac=0.1).cuda()
+    _lib.start_timing(RUNNERS)
+    try:
+        focal_dice_loss(model(x), t, alpha=1.0, gamma=2.0, ratio=0.3).backward()
+    finally:
+        recs = _lib.stop_timing()
+    del model, x, t
+    torch.cuda.empty_cache()
+    return recs
+
+
+def distinct_calls(recs):
+    """(symbol, shapes, lds, dtype, optional pointers given) -> (kw, recorded kernel): one replay per distinct call."""
+    out = {}
+    for name_kernel, args, _ in recs:
+        sym, kernel = name_kernel.split("|", 1)
+        kinds = ["P" if t.__name__ == "c_void_p" else "I" if t.__name__ == "c_int" else "L" for t in _lib.SIGNATURES[sym][1]]
+        kw = {}
+        for key, i in X.positions(sym, kinds).items():
+            kw[key] = (args[i] is not None) if key.startswith("ptr:") else args[i]
+        key = (sym,) + tuple(sorted((k, v) for k, v in kw.items() if k != "workspace_bytes"))
+        if key not in out:
+            out[key] = (kw, kernel)
+        elif "workspace_bytes" in kw:
+            out[key][0]["workspace_bytes"] = max(out[key][0]["workspace_bytes"], kw["workspace_bytes"])
+    return out
+
+
+@pytest.mark.skipif(THIN or SWITCHED, reason="the replay runs on the default routes only")
+@pytest.mark.parametrize("config", list(REPLAY_CONFIGS))
+def test_production_step_replay(config):
+    """Every distinct convolution call of one training step, replayed with exact fixtures at its own shapes and leading
+    dimensions: the same kernel, a bit-exact output, intact guards."""
+    dtype, bs, size = REPLAY_CONFIGS[config]
+    calls = distinct_calls(record_step(dtype, bs, size))
+    if config in REPLAY_ONLY:
+        calls = {k: v for k, v in calls.items() if any(part in k[0] for part in REPLAY_ONLY[config])}
+    print(f"\n{config}: {len(calls)} distinct calls")
+    reached = {}
+    for key, (kw, kernel) in sorted(calls.items(), key=lambda kv: str(kv[0])):
+        sym = key[0]
+        name = RUNNERS[sym](kw)
+        if name is not None:                       # (bn_relu_apply names no matrix-core kernel)
+            assert name == kernel, (sym, kw, kernel, name)
+            reached.setdefault(sym, set()).add(name)
+        torch.cuda.empty_cache()
+    for sym in sorted(reached):
+        print(f"  {sym}: {sorted(reached[sym])}")

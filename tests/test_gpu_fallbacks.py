@@ -30,13 +30,15 @@ def test_operator_parity_under_switches():
     procs = {}
     for name in sorted(SWITCH_SETS):
         env = dict(os.environ, UNETDC_TEST_THIN="1", OMP_NUM_THREADS="4", **SWITCH_SETS[name])   # thinned shape lists: tests/test_gpu_ops.py
-        sel = "conv3x3_fwd_dgrad_wgrad or first_conv or conv_transpose or fused_bn_backward_statistics"
+        # (test_gpu_exact.py: the exact-integer and guard checks of the same routes, thinned the same way)
+        sel = ("conv3x3_fwd_dgrad_wgrad or first_conv or conv_transpose or fused_bn_backward_statistics or exact_conv3x3_routes"
+               " or exact_first_layer or exact_conv_transpose or exact_wgrad_routes")
         if name == "unfused_epilogues":
-            sel = "wgrad_tap_fused or conv3x3_fwd_dgrad_wgrad"
+            sel = "wgrad_tap_fused or conv3x3_fwd_dgrad_wgrad or exact_conv3x3_routes or exact_wgrad_routes"
         if name == "round1_kernels":
-            sel = "(" + sel + " or wgrad_tap_fused) and not f32"
-        cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_ops.py"), "-m", "gpu", "-x", "-q",
-               "-k", sel, "-p", "no:cacheprovider"]
+            sel = "(" + sel + " or wgrad_tap_fused or exact_normalise_on_load) and not f32"
+        cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_ops.py"),
+               os.path.join(ROOT, "tests", "test_gpu_exact.py"), "-m", "gpu", "-x", "-q", "-k", sel, "-p", "no:cacheprovider"]
         procs[name] = subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     for name, pr in procs.items():
         out, _ = pr.communicate(timeout=900)

@@ -321,6 +321,7 @@ int launch_first_fwd(FirstParams& p, int dtype, hipStream_t stream) {
     hipLaunchKernelGGL(first_conv_fwd_kernel<bf16_t>, dim3(nb), dim3(256), lds, stream, p);
   else
     hipLaunchKernelGGL(first_conv_fwd_kernel<float>, dim3(nb), dim3(256), lds, stream, p);
+  note_kernel(dtype == UNETDC_BF16 ? "first_conv_fwd_kernel<__bf16>" : "first_conv_fwd_kernel<float>");
   return check_launch("first_conv_fwd_kernel");
 }
 
@@ -431,6 +432,7 @@ int launch_first_dgrad(const void* dy, int lddy, const float* w, float* dx, int 
     if (Cin == 1) hipLaunchKernelGGL((first_dgrad_kernel<float, 1>), dim3((unsigned)nb), dim3(256), lds, stream, p, dx);
     else hipLaunchKernelGGL((first_dgrad_kernel<float, 3>), dim3((unsigned)nb), dim3(256), lds, stream, p, dx);
   }
+  note_kernel(dtype == UNETDC_BF16 ? "first_dgrad_kernel<__bf16>" : "first_dgrad_kernel<float>");
   return check_launch("first_dgrad_kernel");
 }
 
@@ -458,6 +460,7 @@ int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long wor
       hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, true>), dim3((unsigned)nr, p.Cin), dim3(256), lds_r, stream, p);
     else
       hipLaunchKernelGGL((first_wgrad_rows_kernel<float, true>), dim3((unsigned)nr, p.Cin), dim3(256), lds_r, stream, p);
+    note_kernel(dtype == UNETDC_BF16 ? "first_wgrad_rows_kernel<__bf16> bn" : "first_wgrad_rows_kernel<float> bn");
     int rc = check_launch("first_wgrad_rows_kernel(bn)");
     if (rc != UNETDC_OK) return rc;
     const int n = p.Cin * 9 * p.Cout;
@@ -491,6 +494,7 @@ int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long wor
         hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, false>), dim3((unsigned)nr, p.Cin), dim3(256), lds, stream, p);
       else
         hipLaunchKernelGGL((first_wgrad_rows_kernel<float, false>), dim3((unsigned)nr, p.Cin), dim3(256), lds, stream, p);
+      note_kernel(dtype == UNETDC_BF16 ? "first_wgrad_rows_kernel<__bf16>" : "first_wgrad_rows_kernel<float>");
       int rc = check_launch("first_wgrad_rows_kernel");
       if (rc != UNETDC_OK) return rc;
       const int n = p.Cin * 9 * p.Cout;
@@ -503,6 +507,7 @@ int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long wor
     hipLaunchKernelGGL(first_conv_wgrad_kernel<bf16_t>, dim3((unsigned)nb, p.Cin), dim3(256), lds, stream, p);
   else
     hipLaunchKernelGGL(first_conv_wgrad_kernel<float>, dim3((unsigned)nb, p.Cin), dim3(256), lds, stream, p);
+  note_kernel(dtype == UNETDC_BF16 ? "first_conv_wgrad_kernel<__bf16>" : "first_conv_wgrad_kernel<float>");
   int rc = check_launch("first_conv_wgrad_kernel");
   if (rc != UNETDC_OK) return rc;
   const int n = p.Cin * 9 * p.Cout;

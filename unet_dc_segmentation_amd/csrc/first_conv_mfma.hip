@@ -138,6 +138,7 @@ int launch_first_mfma_fwd(FirstParams& f, int dtype, hipStream_t stream) {
     if (f.Cin == 1) hipLaunchKernelGGL((first_mfma_fwd_kernel<float, 1>), grid, block, 0, stream, p, f.dil);
     else hipLaunchKernelGGL((first_mfma_fwd_kernel<float, 3>), grid, block, 0, stream, p, f.dil);
   }
+  note_kernel(dtype == UNETDC_BF16 ? "first_mfma_fwd_kernel<__bf16>" : "first_mfma_fwd_kernel<float>");
   return check_launch("first_mfma_fwd_kernel");
 }
 
@@ -263,6 +264,7 @@ int launch_first_mfma_wgrad(FirstWgradParams& p, int* nblk_out, int dtype, hipSt
     else hipLaunchKernelGGL((first_mfma_wgrad_kernel<float, 3>), grid, block, 0, stream, p, ppw, ws, hs);
   }
   *nblk_out = nb;
+  note_kernel(dtype == UNETDC_BF16 ? "first_mfma_wgrad_kernel<__bf16>" : "first_mfma_wgrad_kernel<float>");
   return check_launch("first_mfma_wgrad_kernel");
 }
 
