@@ -326,6 +326,36 @@ int unetdc_resize_linear_u8_to_chw_f32(const uint8_t* src_hwc, int h, int w, int
                                        const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
                                        unetdc_stream_t s);
 
+/* ---- training augmentation on a device-resident cache (utils/data_loader.py:TrainAugment restated; augment.hip) ------
+ * unetdc_elastic_fields: for each of n field slots, the displacement pair of TrainAugment's elastic step,
+ *   fields[i][0] = dx, fields[i][1] = dy, each [h][w] float32 = alpha * gaussian_filter(noise, sigma, mode="constant",
+ *   truncate=4.0), where noise(seed, component, y, x) in [-1, 1) is a counter-based hash (no RNG state on the device):
+ *     f(h) = murmur3 fmix32;  key = f(f(f(seed) ^ component * 0x9E3779B9) ^ y);  noise = (f(key ^ x) >> 8) * 2^-23 - 1.
+ *   seeds: HOST array of n seeds (passed to the kernels by value).  h, w <= 1024; int(4 sigma + 0.5) <= 1024.
+ * unetdc_augment_gather: out_img[i] ([c][h][w] float32) and out_mask[i] ([1][h][w] float32 in {0, 1}) for n samples, each
+ *   made from cache_img[params[i].src] ([ncache][c][h][w] float32) and cache_mask[params[i].src] ([ncache][h][w] uint8) by
+ *   hflip, vflip, np.rot90(k, axes (0, 1)), brightness / contrast clip(alpha * x + beta_max, 0, 1) (two float32 roundings,
+ *   no FMA) and, when params[i].field >= 0, the elastic warp with the fields of that slot (image: bilinear, mask: nearest,
+ *   both with scipy.ndimage's mode "reflect").  params: HOST array of n records.  An odd k needs h == w. */
+#define UNETDC_AUG_HFLIP 1
+#define UNETDC_AUG_VFLIP 2
+#define UNETDC_AUG_BC 4
+typedef struct unetdc_augment_params {
+  int32_t src;          /* index into the cache */
+  int32_t flags;        /* UNETDC_AUG_* bits */
+  int32_t k;            /* 90-degree rotations, 0..3 */
+  int32_t field;        /* field slot, -1 = no elastic */
+  float alpha;          /* contrast factor, float32(alpha) */
+  float beta_max;       /* float32(beta * max of the source image), the product formed in double */
+  int32_t reserved[2];
+} unetdc_augment_params;
+int64_t unetdc_elastic_fields_workspace(int n, int h, int w, double sigma);
+int unetdc_elastic_fields(const uint32_t* seeds, int n, int h, int w, double sigma, float alpha, float* fields,
+                          void* workspace, int64_t workspace_bytes, unetdc_stream_t s);
+int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int ncache, int channels, int h, int w,
+                          const unetdc_augment_params* params, int n, const float* fields, int nfields, float* out_img,
+                          float* out_mask, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

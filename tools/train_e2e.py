@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Training throughput of train_DC_focal.py on N synthetic 1040 x 1388 PNG pairs (bench.synthetic_micrograph images, masks by
+threshold), three arms, each in a fresh child process, bf16, batch 8:
+    synthetic    --synthetic --synthetic_len N        (generated tiles: the loader is not the limit)
+    device_data  --device_data                        (cache on the device, augmentation kernels per batch)
+    cpu_loader   the host loader (SegmentationDataset + TrainAugment, --workers 4), capped with --steps
+Prints the per-epoch training img/s of every arm and one JSON line with the mean from epoch 2 on.
+
+    python tools/train_e2e.py [N] [--epochs E] [--cpu_steps S] [--only ARM]"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ARMS = ("synthetic", "device_data", "cpu_loader")
+
+
+def write_pairs(d, n):
+    import numpy as np
+    from PIL import Image
+
+    import bench
+    ind, md = os.path.join(d, "images"), os.path.join(d, "masks")
+    os.makedirs(ind)
+    os.makedirs(md)
+    base = [bench.synthetic_micrograph(7 + i) for i in range(8)]
+    for i in range(n):
+        img = np.roll(base[i % 8], 53 * (i // 8), axis=1)
+        Image.fromarray(img).save(os.path.join(ind, f"img_{i:04d}.png"), compress_level=1)
+        Image.fromarray(((img[..., 0] > 110) * 255).astype(np.uint8)).save(os.path.join(md, f"img_{i:04d}.png"),
+                                                                            compress_level=1)
+    return ind, md
+
+
+def run_arm(arm, n, ind, md, epochs, cpu_steps, d):
+    common = ["--dtype", "bf16", "--batch", "8", "--epochs", str(epochs), "--patience", str(epochs + 1), "--no_test_eval",
+              "--ckpt_path", os.path.join(d, f"{arm}.pth")]
+    if arm == "synthetic":
+        extra = ["--synthetic", "--synthetic_len", str(n)]
+    elif arm == "device_data":
+        extra = ["--image_dir", ind, "--mask_dir", md, "--device_data"]
+    else:
+        extra = ["--image_dir", ind, "--mask_dir", md, "--steps", str(cpu_steps), "--workers", "4"]
+    cmd = [sys.executable, os.path.join(ROOT, "train_DC_focal.py"), *common, *extra]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+    sys.stdout.write(f"--- {arm}: exit {r.returncode}\n" + "\n".join(l for l in r.stdout.splitlines() if "img/s" in l) + "\n")
+    if r.returncode != 0:
+        sys.stdout.write(r.stdout[-2000:] + r.stderr[-4000:])
+        raise SystemExit(f"arm {arm} failed (exit {r.returncode})")
+    return [float(v) for v in re.findall(r"\|\s*([0-9.]+) img/s", r.stdout)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", type=int, nargs="?", default=400)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--cpu_steps", type=int, default=3)
+    ap.add_argument("--only", choices=ARMS)
+    a = ap.parse_args()
+    res = {"n_pairs": a.n, "epochs": a.epochs, "batch": 8, "dtype": "bf16", "cpu_loader_steps_per_epoch": a.cpu_steps}
+    with tempfile.TemporaryDirectory() as d:
+        ind, md = write_pairs(d, a.n)
+        for arm in ([a.only] if a.only else ARMS):
+            ips = run_arm(arm, a.n, ind, md, a.epochs, a.cpu_steps, d)
+            res[f"{arm}_img_per_s_by_epoch"] = ips
+            res[f"{arm}_img_per_s"] = sum(ips[1:]) / max(1, len(ips[1:]))
+    if "synthetic_img_per_s" in res and "device_data_img_per_s" in res:
+        res["device_data_over_synthetic"] = res["device_data_img_per_s"] / res["synthetic_img_per_s"]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -8,7 +8,8 @@ to ``best_UNetDC_focal_model.pth``) behind argparse flags whose defaults are tho
 New: ``--synthetic`` (seeded droplet tiles, no dataset needed), ``--dtype`` (f32 | bf16 compute on
 the HIP path), ``--steps`` (cap the steps per epoch), and data-parallel training when launched with
 ``python -m torch.distributed.run --nproc-per-node N train_DC_focal.py ...`` (RCCL all-reduce
-overlapped with backward, unet_dc_segmentation_amd/dp.py).  The numbers of the reference's test section (:365-402, :452-467:
+overlapped with backward, unet_dc_segmentation_amd/dp.py), and ``--device_data`` (images preprocessed once into a cache on the
+device, each batch augmented there: unet_dc_segmentation_amd/device_data.py).  The numbers of the reference's test section (:365-402, :452-467:
 best checkpoint reloaded, test loss / Dice / pixel accuracy, precision / recall / F1 / specificity / confusion matrix) are
 computed and printed; its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
 """
@@ -44,6 +45,9 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--optimizer", default="hip", choices=["hip", "torch"],
                    help="Adam implementation on a GPU: hip = fused step + weight re-pack kernel, torch = torch.optim.Adam")
     p.add_argument("--workers", type=int, default=4)
+    p.add_argument("--device_data", action="store_true",
+                   help="decode and preprocess every image once into a cache on the HIP device and augment each batch there "
+                        "(csrc/augment.hip; its own counter-based random stream); --workers is ignored")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -60,6 +64,14 @@ def make_datasets(args):
         n_test, n_val = max(1, n // 5), max(1, n // 5)                    # 60/20/20 like the reference
         return (Subset(full, idx[n_test + n_val:]), Subset(full, idx[n_test:n_test + n_val]),
                 Subset(full, idx[:n_test]))
+    tr, va, te = split_files(args)
+    mk = lambda pair, tf: SegmentationDataset(args.image_dir, args.mask_dir, pair[0], pair[1], transform=tf,  # noqa: E731
+                                              size=args.img_size)
+    return mk(tr, TrainAugment(args.seed)), mk(va, None), mk(te, None)
+
+
+def split_files(args):
+    """(image names, mask names) of the train, validation and test splits of --image_dir / --mask_dir."""
     if not args.image_dir or not args.mask_dir:
         raise SystemExit("--image_dir and --mask_dir are required unless --synthetic is given")
     exts = (".png", ".jpg", ".jpeg", ".tif")
@@ -70,10 +82,24 @@ def make_datasets(args):
     n_test = max(1, len(imgs) // 5)
     n_val = max(1, (len(imgs) - n_test) // 4)
     pick = lambda ids: ([imgs[i] for i in ids], [masks[i] for i in ids])   # noqa: E731
-    tr, va, te = pick(idx[n_test + n_val:]), pick(idx[n_test:n_test + n_val]), pick(idx[:n_test])
-    mk = lambda pair, tf: SegmentationDataset(args.image_dir, args.mask_dir, pair[0], pair[1], transform=tf,  # noqa: E731
-                                              size=args.img_size)
-    return mk(tr, TrainAugment(args.seed)), mk(va, None), mk(te, None)
+    return pick(idx[n_test + n_val:]), pick(idx[n_test:n_test + n_val]), pick(idx[:n_test])
+
+
+def make_device_loaders(args, rank, world, device):
+    """--device_data: (train, validation, test) loaders over caches on the device (unet_dc_segmentation_amd/device_data.py).
+    A data-parallel rank caches only its training shard, the one the host path's Subset picks."""
+    from unet_dc_segmentation_amd.device_data import DeviceEvalLoader, DeviceImageCache, DeviceTrainLoader
+    if args.synthetic:
+        raise SystemExit("--device_data caches the files of --image_dir / --mask_dir; --synthetic tiles need no cache")
+    tr, va, te = split_files(args)
+    ids = list(range(len(tr[0])))
+    if world > 1:
+        per_rank = len(ids) // world
+        ids = list(range(rank, per_rank * world, world))
+    cache = lambda names, masks: DeviceImageCache(args.image_dir, args.mask_dir, names, args.img_size,  # noqa: E731
+                                                  device=device, mask_names=masks)
+    train = DeviceTrainLoader(cache([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.seed, ids)
+    return train, DeviceEvalLoader(cache(*va), args.batch), DeviceEvalLoader(cache(*te), args.batch)
 
 
 class History(list):
@@ -110,6 +136,8 @@ def main(argv=None, parser=None):
     args = (parser or build_parser()).parse_args(argv)
     rank, local, world = dpmod.init_from_env()
     device = torch.device(args.device if args.device != "cuda" else f"cuda:{local}")
+    if args.device_data and device.type != "cuda":
+        raise SystemExit(f"--device_data keeps the data set on the HIP device and cannot run on --device {args.device}")
     if device.type == "cuda":
         torch.cuda.set_device(device)
     torch.manual_seed(args.seed)
@@ -132,22 +160,26 @@ def main(argv=None, parser=None):
     else:
         optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, fused=next(model.parameters()).is_cuda)
 
-    train_ds, val_ds, test_ds = make_datasets(args)
-    if world > 1:
-        # each rank draws its own shard; shards are truncated to EQUAL length (as DistributedSampler with
-        # drop_last does) so that every rank runs the same number of steps -- an extra step on one rank would
-        # leave its gradient all-reduce without partners
-        per_rank = len(train_ds) // world
-        train_ds = Subset(train_ds, list(range(rank, per_rank * world, world)))
-    pin = device.type == "cuda"
-    # worker processes live across epochs (re-spawning them costs seconds per epoch: an interpreter + torch import each)
-    keep = args.workers > 0
-    # no drop_last, like the reference's loader (train_DC_focal.py:200): the ragged last batch trains too (the engines of both
-    # batch shapes stay alive, unet.py::_engine_for; under data parallelism the shards are equal, so is every rank's last batch)
-    train_loader = DataLoader(train_ds, batch_size=args.batch, shuffle=True, num_workers=args.workers,
-                              pin_memory=pin, persistent_workers=keep)
-    val_loader = DataLoader(val_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers, pin_memory=pin,
-                            persistent_workers=keep)
+    if args.device_data:
+        train_loader, val_loader, test_loader = make_device_loaders(args, rank, world, device)
+        train_ds, val_ds, test_ds = train_loader.dataset, val_loader.dataset, test_loader.dataset
+    else:
+        train_ds, val_ds, test_ds = make_datasets(args)
+        if world > 1:
+            # each rank draws its own shard; shards are truncated to EQUAL length (as DistributedSampler with
+            # drop_last does) so that every rank runs the same number of steps -- an extra step on one rank would
+            # leave its gradient all-reduce without partners
+            per_rank = len(train_ds) // world
+            train_ds = Subset(train_ds, list(range(rank, per_rank * world, world)))
+        pin = device.type == "cuda"
+        # worker processes live across epochs (re-spawning them costs seconds per epoch: an interpreter + torch import each)
+        keep = args.workers > 0
+        # no drop_last, like the reference's loader (train_DC_focal.py:200): the ragged last batch trains too (the engines of both
+        # batch shapes stay alive, unet.py::_engine_for; under data parallelism the shards are equal, so is every rank's last batch)
+        train_loader = DataLoader(train_ds, batch_size=args.batch, shuffle=True, num_workers=args.workers,
+                                  pin_memory=pin, persistent_workers=keep)
+        val_loader = DataLoader(val_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers, pin_memory=pin,
+                                persistent_workers=keep)
     if rank == 0:
         print(f"Training set: {len(train_ds)} images/rank, validation set: {len(val_ds)} images, "
               f"{world} rank(s), device {device}, compute {args.dtype}")
@@ -250,7 +282,9 @@ def main(argv=None, parser=None):
             # validation Dice never rose above 0: nothing was written by THIS run, and a file of that name left by an earlier
             # run (possibly another architecture) is not this run's result
             print(f"No checkpoint was written this run ({args.ckpt_path} not reloaded): evaluating the current weights")
-        test_loader = DataLoader(test_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers, pin_memory=pin)
+        if not args.device_data:
+            test_loader = DataLoader(test_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers,
+                                     pin_memory=pin)
         history.test = evaluate_test(model, test_loader, criterion, device)       # every rank: same weights, same split
         if rank == 0:
             t = history.test

@@ -77,6 +77,9 @@ SIGNATURES = {
     "unetdc_mask_from_probs_linear": (I, [P, I, I, F, P, I, I, P, P, P, P, P]),
     "unetdc_ccl_workspace": (L, [I, I]),
     "unetdc_ccl_stats": (I, [P, I, I, I, P, L, P, P, P, P, P, I, P]),
+    "unetdc_elastic_fields_workspace": (L, [I, I, I, D]),
+    "unetdc_elastic_fields": (I, [P, I, I, I, D, F, P, P, L, P]),
+    "unetdc_augment_gather": (I, [P, P, I, I, I, I, P, I, P, I, P, P, P]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // extern "C" entry points of libunetdc_hip.so (declared in include/unetdc_hip.h).
 // Thin argument validation + geometry setup; the kernels live in the other translation units.
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 
 #include <mutex>
@@ -550,6 +551,28 @@ int unetdc_resize_linear_u8_to_chw_f32(const uint8_t* src_hwc, int h, int w, int
                                        const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef,
                                        unetdc_stream_t s) {
   return launch_resize_linear_chw(src_hwc, h, w, channels, dst_chw, dh, dw, xofs, xcoef, yofs, ycoef, (hipStream_t)s);
+}
+
+static_assert(sizeof(unetdc_augment_params) == sizeof(unetdc::AugRecord) &&
+                  offsetof(unetdc_augment_params, beta_max) == offsetof(unetdc::AugRecord, beta_max),
+              "unetdc_augment_params and AugRecord must share one layout");
+static_assert(UNETDC_AUG_HFLIP == unetdc::AUG_HFLIP && UNETDC_AUG_VFLIP == unetdc::AUG_VFLIP && UNETDC_AUG_BC == unetdc::AUG_BC,
+              "augmentation flag bits");
+
+int64_t unetdc_elastic_fields_workspace(int n, int h, int w, double sigma) {
+  return elastic_fields_workspace_bytes(n, h, w, sigma);
+}
+
+int unetdc_elastic_fields(const uint32_t* seeds, int n, int h, int w, double sigma, float alpha, float* fields,
+                          void* workspace, int64_t workspace_bytes, unetdc_stream_t s) {
+  return launch_elastic_fields(seeds, n, h, w, sigma, alpha, fields, workspace, (long)workspace_bytes, (hipStream_t)s);
+}
+
+int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int ncache, int channels, int h, int w,
+                          const unetdc_augment_params* params, int n, const float* fields, int nfields, float* out_img,
+                          float* out_mask, unetdc_stream_t s) {
+  return launch_augment_gather(cache_img, cache_mask, ncache, channels, h, w, reinterpret_cast<const AugRecord*>(params), n,
+                               fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
 }  // extern "C"

@@ -1,0 +1,304 @@
+// Training augmentation on the GPU: the per-batch random part of utils/data_loader.py:TrainAugment, in its order,
+//   1. hflip  2. vflip  3. np.rot90(k, axes (0, 1))  4. brightness / contrast clip(alpha*img + beta*max, 0, 1)
+//   5. elastic: displacement fields gaussian_filter(noise, sigma, mode="constant") * alpha; image map_coordinates(order=1,
+//      mode="reflect"), mask map_coordinates(order=0, mode="reflect")
+// over a device-resident cache of preprocessed images (unet_dc_segmentation_amd/device_data.py).
+//
+// Noise: a counter-based hash of (field seed, component, y, x) -- no RNG state on the device; the restatement the tests check
+// against is tests/augment_ref.py:noise.  Component 0 is dx (the first field _elastic draws), component 1 is dy.
+//
+// Fields (elastic_rows_kernel + elastic_cols_kernel): the separable Gaussian as two passes of 2r+1 taps, r = int(4 sigma + 0.5)
+// (scipy's truncate=4.0), taps outside the image read 0 (mode="constant"), so r may exceed the image.  Each lane computes
+// AUG_R consecutive outputs from a register window of 2 AUG_R inputs: AUG_R^2 FMAs per AUG_R new inputs (the two halves of the window swap roles,
+// so it slides without register moves), the tap weights
+// come through scalar loads (uniform over the wave).  The row pass builds its noise rows in LDS straight from the hash; the
+// column pass reads the row-pass result with lanes along x (coalesced) and a window along y.
+//
+// Gather (augment_gather_kernel): one thread per output pixel, all channels and the mask.  Flips and rotation are an index
+// permutation; brightness / contrast is applied per source tap BEFORE interpolation (the CPU path clips, then warps) as
+// __fadd_rn(__fmul_rn(alpha32, x), b32): numpy's float32 arithmetic for `alpha * img + beta * max` (NEP 50 weak scalars,
+// beta * max formed in double on the host), so without elastic the output is bit-exact.  Elastic taps take their integer
+// part and fraction from the displacement alone (floor(d), d - floor(d): exact in float32), not from y + d, which would drop
+// bits of the fraction near y = 512.
+#include "kernels.h"
+
+namespace unetdc {
+
+constexpr int AUG_R = 8;          // outputs per lane in both field passes
+constexpr int AUG_ROWS = 4;       // rows per row-pass block (one wave each)
+constexpr int AUG_MAX_SIDE = 1024;
+constexpr int AUG_MAX_RADIUS = 1024;
+
+struct AugSeeds {
+  unsigned s[AUG_MAX_SEEDS];
+};
+
+struct AugBatch {
+  AugRecord r[AUG_MAX_BATCH];
+};
+
+__host__ __device__ inline unsigned aug_fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+// hash of (seed, component, y) -- the per-row part of the noise counter
+__device__ inline unsigned aug_row_key(unsigned seed, int comp, int y) {
+  return aug_fmix32(aug_fmix32(aug_fmix32(seed) ^ ((unsigned)comp * 0x9E3779B9u)) ^ (unsigned)y);
+}
+
+// uniform in [-1, 1): the top 24 bits of the hash, (h >> 8) * 2^-23 - 1 (exact in float32)
+__device__ inline float aug_noise(unsigned row_key, int x) {
+  return (float)(aug_fmix32(row_key ^ (unsigned)x) >> 8) * 0x1p-23f - 1.0f;                 // (FMA or not: exact)
+}
+
+// 2r + 1 taps padded with zero weights to a multiple of 2 AUG_R (the window loops take two blocks of AUG_R taps per turn)
+__host__ __device__ inline int aug_taps_padded(int r) { return (2 * r + 1 + 2 * AUG_R - 1) / (2 * AUG_R) * (2 * AUG_R); }
+__host__ __device__ inline int aug_row_lds_floats(int w, int r) {
+  return (w + 64 * AUG_R - 1) / (64 * AUG_R) * (64 * AUG_R) + aug_taps_padded(r);
+}
+
+// acc[i] += sum_j w[j] * window[i + j] over the window lo[0..R) hi[0..R): one block of AUG_R taps.  Called with lo / hi
+// swapped on alternate blocks, so the window slides without register moves.
+__device__ inline void aug_tap_block(float (&acc)[AUG_R], const float (&lo)[AUG_R], const float (&hi)[AUG_R],
+                                     const float* __restrict__ w) {
+#pragma unroll
+  for (int j = 0; j < AUG_R; ++j) {
+    const float wj = w[j];
+#pragma unroll
+    for (int i = 0; i < AUG_R; ++i) acc[i] = fmaf(wj, i + j < AUG_R ? lo[i + j] : hi[i + j - AUG_R], acc[i]);
+  }
+}
+
+// normalised Gaussian taps of scipy.ndimage.gaussian_filter1d (exp(-x^2 / (2 sigma^2)) / sum, in double), zero-padded to
+// `taps` entries.  One block; the sum is a fixed-order tree, so every call writes the same weights.
+__global__ __launch_bounds__(256) void gauss_weights_kernel(float* __restrict__ w, int r, int taps, double sigma) {
+  __shared__ double part[256];
+  const double k = -0.5 / (sigma * sigma);
+  double s = 0.0;
+  for (int t = threadIdx.x; t <= 2 * r; t += 256) s += exp(k * (double)(t - r) * (double)(t - r));
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double total = part[0];
+  for (int t = threadIdx.x; t < taps; t += 256)
+    w[t] = t <= 2 * r ? (float)(exp(k * (double)(t - r) * (double)(t - r)) / total) : 0.0f;
+}
+
+// Row pass: tmp[slot][comp][y][x] = sum_t w[t] * noise(y, x + t - r).  grid (ceil(H / AUG_ROWS), 2, nslots), block 256: wave
+// v of the block takes row blockIdx.x * AUG_ROWS + v, staged in LDS as row[p] = noise(x = p - r) (0 outside [0, W)).
+__global__ __launch_bounds__(256) void elastic_rows_kernel(const AugSeeds seeds, int slot0, int H, int W, int r, int taps,
+                                                           const float* __restrict__ wts, float* __restrict__ tmp) {
+  extern __shared__ float lds[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int comp = blockIdx.y, slot = blockIdx.z;
+  const int y = blockIdx.x * AUG_ROWS + wave;
+  const int L = aug_row_lds_floats(W, r);
+  float* row = lds + wave * L;
+  const unsigned key = aug_row_key(seeds.s[slot], comp, y);
+#pragma clang loop vectorize(disable)
+  for (int p = lane; p < L; p += 64) {
+    const int x = p - r;
+    row[p] = (unsigned)x < (unsigned)W ? aug_noise(key, x) : 0.0f;
+  }
+  __syncthreads();
+  if (y >= H) return;
+  float* out = tmp + (((long)(slot0 + slot) * 2 + comp) * H + y) * W;
+  for (int c0 = 0; c0 < W; c0 += 64 * AUG_R) {
+    const int x0 = c0 + lane * AUG_R;
+    const float* src = row + x0;                            // src[m] = input at x0 + m - r
+    float acc[AUG_R], a[AUG_R], b[AUG_R];
+#pragma unroll
+    for (int i = 0; i < AUG_R; ++i) { acc[i] = 0.0f; a[i] = src[i]; }
+    for (int tb = 0; tb < taps; tb += 2 * AUG_R) {
+#pragma unroll
+      for (int i = 0; i < AUG_R; ++i) b[i] = src[tb + AUG_R + i];
+      aug_tap_block(acc, a, b, wts + tb);
+#pragma unroll
+      for (int i = 0; i < AUG_R; ++i) a[i] = src[tb + 2 * AUG_R + i];       // (the last turn's reads stay inside the row)
+      aug_tap_block(acc, b, a, wts + tb + AUG_R);
+    }
+#pragma unroll
+    for (int i = 0; i < AUG_R; ++i)
+      if (x0 + i < W) out[x0 + i] = acc[i];
+  }
+}
+
+// Column pass: fields[slot][comp][y][x] = alpha * sum_t w[t] * tmp[slot][comp][y + t - r][x] (0 outside [0, H)).
+// grid (ceil(W / 64), ceil(H / (4 AUG_R)), 2 nslots), block 256: lane = column, wave = a group of AUG_R output rows.
+__global__ __launch_bounds__(256) void elastic_cols_kernel(int slot0, int H, int W, int r, int taps, float alpha,
+                                                           const float* __restrict__ wts, const float* __restrict__ tmp,
+                                                           float* __restrict__ fields) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int x = blockIdx.x * 64 + lane;
+  const int y0 = (blockIdx.y * 4 + wave) * AUG_R;
+  const long plane = ((long)slot0 * 2 + blockIdx.z) * H * W;
+  if (y0 >= H) return;
+  const int xc = x < W ? x : W - 1;
+  const float* src = tmp + plane + xc;
+  auto ld = [&](int yy) { return (unsigned)yy < (unsigned)H ? src[(long)yy * W] : 0.0f; };
+  float acc[AUG_R], a[AUG_R], b[AUG_R];
+#pragma unroll
+  for (int i = 0; i < AUG_R; ++i) { acc[i] = 0.0f; a[i] = ld(y0 - r + i); }
+  for (int tb = 0; tb < taps; tb += 2 * AUG_R) {
+#pragma unroll
+    for (int i = 0; i < AUG_R; ++i) b[i] = ld(y0 - r + tb + AUG_R + i);
+    aug_tap_block(acc, a, b, wts + tb);
+#pragma unroll
+    for (int i = 0; i < AUG_R; ++i) a[i] = ld(y0 - r + tb + 2 * AUG_R + i);
+    aug_tap_block(acc, b, a, wts + tb + AUG_R);
+  }
+  if (x >= W) return;
+  float* out = fields + plane + x;
+#pragma unroll
+  for (int i = 0; i < AUG_R; ++i)
+    if (y0 + i < H) out[(long)(y0 + i) * W] = alpha * acc[i];
+}
+
+// scipy.ndimage mode "reflect" (half-sample symmetric, period 2n) applied to an integer tap index
+__device__ inline int aug_reflect(int i, int n) {
+  const int p = 2 * n;
+  int m = i % p;
+  m = m < 0 ? m + p : m;
+  return m < n ? m : p - 1 - m;
+}
+
+// (y, x) in the flipped + rotated image -> (sy, sx) in the source image (H x W; H == W whenever k is odd)
+__device__ inline void aug_source(int y, int x, int H, int W, int flags, int k, int& sy, int& sx) {
+  int fy = y, fx = x;
+  if (k == 1) { fy = x; fx = W - 1 - y; }
+  else if (k == 2) { fy = H - 1 - y; fx = W - 1 - x; }
+  else if (k == 3) { fy = H - 1 - x; fx = y; }
+  sy = (flags & AUG_VFLIP) ? H - 1 - fy : fy;
+  sx = (flags & AUG_HFLIP) ? W - 1 - fx : fx;
+}
+
+__device__ inline float aug_bc(float v, const AugRecord& p) {
+  if (!(p.flags & AUG_BC)) return v;
+  // two roundings, as numpy's float32 steps.  __fmul_rn / __fadd_rn are plain operators in HIP, which the backend fuses into
+  // one FMA under -ffp-contract=fast (1-ulp differences from numpy); the empty asm makes the product opaque to that fusion
+  float m = __fmul_rn(p.alpha, v);
+  asm volatile("" : "+v"(m));
+  const float t = __fadd_rn(m, p.beta_max);
+  return fminf(fmaxf(t, 0.0f), 1.0f);
+}
+
+// grid (ceil(W / 16), ceil(H / 16), n), block 16 x 16: thread = output pixel (y, x) of sample n0 + blockIdx.z, every channel
+// plus the mask.  out_img [N][C][H][W] fp32, out_mask [N][1][H][W] fp32.
+__global__ __launch_bounds__(256) void augment_gather_kernel(const float* __restrict__ cache_img,
+                                                             const unsigned char* __restrict__ cache_mask, int C, int H, int W,
+                                                             const float* __restrict__ fields, const AugBatch b, int n0,
+                                                             float* __restrict__ out_img, float* __restrict__ out_mask) {
+  const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (x >= W || y >= H) return;
+  const AugRecord& p = b.r[blockIdx.z];
+  const long hw = (long)H * W, pix = (long)y * W + x;
+  const float* img = cache_img + (long)p.src * C * hw;
+  const unsigned char* msk = cache_mask + (long)p.src * hw;
+  const long n = n0 + blockIdx.z;
+  float* oi = out_img + n * C * hw + pix;
+  if (p.field < 0) {
+    int sy, sx;
+    aug_source(y, x, H, W, p.flags, p.k, sy, sx);
+    const long s = (long)sy * W + sx;
+    for (int c = 0; c < C; ++c) oi[c * hw] = aug_bc(img[c * hw + s], p);
+    out_mask[n * hw + pix] = (float)msk[s];
+    return;
+  }
+  const float* f = fields + (long)p.field * 2 * hw;
+  const float dx = f[pix], dy = f[hw + pix];
+  const float fx = floorf(dx), fy = floorf(dy);
+  const float tx = dx - fx, ty = dy - fy;                   // exact: the fraction of a float32
+  const int ix = x + (int)fx, iy = y + (int)fy;
+  int sy, sx;
+  long s[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    aug_source(aug_reflect(iy + (q >> 1), H), aug_reflect(ix + (q & 1), W), H, W, p.flags, p.k, sy, sx);
+    s[q] = (long)sy * W + sx;
+  }
+  const float wx0 = 1.0f - tx, wy0 = 1.0f - ty;
+  for (int c = 0; c < C; ++c) {
+    const float* ic = img + c * hw;
+    const float a00 = aug_bc(ic[s[0]], p), a01 = aug_bc(ic[s[1]], p);
+    const float a10 = aug_bc(ic[s[2]], p), a11 = aug_bc(ic[s[3]], p);
+    oi[c * hw] = wy0 * (wx0 * a00 + tx * a01) + ty * (wx0 * a10 + tx * a11);
+  }
+  // order 0: the nearest tap, round half up (ties are measure-zero for a smooth float field)
+  aug_source(aug_reflect(iy + (ty >= 0.5f), H), aug_reflect(ix + (tx >= 0.5f), W), H, W, p.flags, p.k, sy, sx);
+  out_mask[n * hw + pix] = (float)msk[(long)sy * W + sx];
+}
+
+int aug_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
+
+long elastic_fields_workspace_bytes(int n, int h, int w, double sigma) {
+  if (n < 0 || h <= 0 || w <= 0 || !(sigma > 0.0) || sigma > AUG_MAX_RADIUS / 4.0) return -1;
+  return 4L * ((long)n * 2 * h * w + aug_taps_padded(aug_radius(sigma)));
+}
+
+int launch_elastic_fields(const unsigned* seeds, int n, int h, int w, double sigma, float alpha, float* fields,
+                          void* workspace, long workspace_bytes, hipStream_t stream) {
+  UNETDC_REQUIRE(n >= 0 && h > 0 && w > 0 && h <= AUG_MAX_SIDE && w <= AUG_MAX_SIDE,
+                 "elastic_fields: bad geometry n=%d h=%d w=%d (sides up to %d)", n, h, w, AUG_MAX_SIDE);
+  UNETDC_REQUIRE(sigma > 0.0 && aug_radius(sigma) <= AUG_MAX_RADIUS, "elastic_fields: sigma must be in (0, %g]",
+                 AUG_MAX_RADIUS / 4.0);
+  if (n == 0) return UNETDC_OK;
+  UNETDC_REQUIRE(seeds && fields && workspace, "elastic_fields: null pointer");
+  if (workspace_bytes < elastic_fields_workspace_bytes(n, h, w, sigma)) {
+    set_error("elastic_fields: workspace too small (%ld bytes)", workspace_bytes);
+    return UNETDC_EWORKSPACE;
+  }
+  const int r = aug_radius(sigma), taps = aug_taps_padded(r);
+  float* tmp = reinterpret_cast<float*>(workspace);
+  float* wts = tmp + (long)n * 2 * h * w;
+  hipLaunchKernelGGL(gauss_weights_kernel, dim3(1), dim3(256), 0, stream, wts, r, taps, sigma);
+  const int lds = AUG_ROWS * aug_row_lds_floats(w, r) * (int)sizeof(float);       // <= 4 x (1024 + 2056) floats = 48 KB
+  for (int s0 = 0; s0 < n; s0 += AUG_MAX_SEEDS) {
+    const int m = n - s0 < AUG_MAX_SEEDS ? n - s0 : AUG_MAX_SEEDS;
+    AugSeeds sd = {};
+    for (int i = 0; i < m; ++i) sd.s[i] = seeds[s0 + i];
+    hipLaunchKernelGGL(elastic_rows_kernel, dim3((h + AUG_ROWS - 1) / AUG_ROWS, 2, m), dim3(256), lds, stream, sd, s0, h, w,
+                       r, taps, wts, tmp);
+    hipLaunchKernelGGL(elastic_cols_kernel, dim3((w + 63) / 64, (h + 4 * AUG_R - 1) / (4 * AUG_R), 2 * m), dim3(256), 0,
+                       stream, s0, h, w, r, taps, alpha, wts, tmp, fields);
+  }
+  return check_launch("elastic field kernels");
+}
+
+int launch_augment_gather(const float* cache_img, const unsigned char* cache_mask, int ncache, int c, int h, int w,
+                          const AugRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
+                          hipStream_t stream) {
+  UNETDC_REQUIRE(ncache > 0 && c >= 1 && h > 0 && w > 0 && n >= 0, "augment_gather: bad geometry ncache=%d c=%d h=%d w=%d n=%d",
+                 ncache, c, h, w, n);
+  if (n == 0) return UNETDC_OK;
+  UNETDC_REQUIRE(cache_img && cache_mask && params && out_img && out_mask, "augment_gather: null pointer");
+  for (int i = 0; i < n; ++i) {
+    const AugRecord& p = params[i];
+    UNETDC_REQUIRE(p.src >= 0 && p.src < ncache, "augment_gather: sample %d: source index %d outside the cache of %d", i,
+                   p.src, ncache);
+    UNETDC_REQUIRE(p.k >= 0 && p.k <= 3, "augment_gather: sample %d: k = %d (0..3)", i, p.k);
+    UNETDC_REQUIRE(!(p.k & 1) || h == w, "augment_gather: sample %d: an odd k needs a square image (%d x %d)", i, h, w);
+    UNETDC_REQUIRE((p.flags & ~(AUG_HFLIP | AUG_VFLIP | AUG_BC)) == 0, "augment_gather: sample %d: bad flags 0x%x", i,
+                   p.flags);
+    UNETDC_REQUIRE(p.field >= -1 && p.field < nfields, "augment_gather: sample %d: field slot %d outside [-1, %d)", i,
+                   p.field, nfields);
+    UNETDC_REQUIRE(p.field < 0 || fields, "augment_gather: sample %d draws elastic but fields is null", i);
+  }
+  for (int s0 = 0; s0 < n; s0 += AUG_MAX_BATCH) {
+    const int m = n - s0 < AUG_MAX_BATCH ? n - s0 : AUG_MAX_BATCH;
+    AugBatch b;
+    for (int i = 0; i < m; ++i) b.r[i] = params[s0 + i];
+    hipLaunchKernelGGL(augment_gather_kernel, dim3((w + 15) / 16, (h + 15) / 16, m), dim3(256), 0, stream, cache_img,
+                       cache_mask, c, h, w, fields, b, s0, out_img, out_mask);
+  }
+  return check_launch("augment_gather_kernel");
+}
+
+}  // namespace unetdc

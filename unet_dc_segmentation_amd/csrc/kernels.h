@@ -172,6 +172,23 @@ int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void
                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
                      hipStream_t stream);
 
+// augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
+// unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).
+constexpr int AUG_HFLIP = 1, AUG_VFLIP = 2, AUG_BC = 4;
+constexpr int AUG_MAX_SEEDS = 64;         // field slots per row/column-pass launch (seeds go by value in the kernel arguments)
+constexpr int AUG_MAX_BATCH = 32;         // samples per gather launch (records go by value: 1 KB of kernel arguments)
+struct AugRecord {
+  int src, flags, k, field;
+  float alpha, beta_max;
+  int reserved[2];
+};
+long elastic_fields_workspace_bytes(int n, int h, int w, double sigma);
+int launch_elastic_fields(const unsigned* seeds, int n, int h, int w, double sigma, float alpha, float* fields,
+                          void* workspace, long workspace_bytes, hipStream_t stream);
+int launch_augment_gather(const float* cache_img, const unsigned char* cache_mask, int ncache, int c, int h, int w,
+                          const AugRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
+                          hipStream_t stream);
+
 // preprocess.hip: rolling-ball correction + bilinear resize to the network input
 long rolling_ball_workspace_bytes(int h, int w, int cn);
 int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int w, int cn, int k, void* workspace,
