@@ -234,6 +234,256 @@ def colsum(x):
     return x.to(torch.float64).reshape(-1, x.shape[-1]).sum(0)
 
 
+# ---------------------------------------------------------------------------------------------------- BatchNorm, head, loss
+# Plain fp64 statements of the arithmetic around the convolutions.  Inputs are the values as STORED (what the kernel reads);
+# every result is the exact mathematical value in fp64.  Where a fixture makes the fp32 arithmetic exact, the kernel's fp32
+# result equals the fp32 rounding of these values; elsewhere a test compares against them under a bound (within_bound).
+EPS32 = 2.0 ** -24                       # unit roundoff of fp32
+
+
+def _f64(t, dev):
+    return None if t is None else t.to(device=dev, dtype=torch.float64)
+
+
+def bn_finalize(parts, count, gamma, beta, eps, momentum, running_mean=None, running_var=None):
+    """nn.BatchNorm2d training statistics from [rows, 2, C] partial (sum, sum of squares) rows: batch mean, biased variance,
+    rstd = 1 / sqrt(var + eps), scale = gamma * rstd, shift = beta - mean * scale, and the running buffers updated with
+    momentum and the UNBIASED variance (var * count / (count - 1))."""
+    dev = parts.device
+    p = parts.to(torch.float64)
+    s, q = p[:, 0].sum(0), p[:, 1].sum(0)
+    mean = s / count
+    var = (q / count - mean * mean).clamp_min(0.0)
+    rstd = 1.0 / torch.sqrt(var + float(eps))
+    scale = _f64(gamma, dev) * rstd
+    out = dict(mean=mean, var=var, rstd=rstd, scale=scale, shift=_f64(beta, dev) - mean * scale)
+    if running_mean is not None:
+        m = float(momentum)
+        unbiased = var * (count / (count - 1.0 if count > 1 else 1.0))
+        out["running_mean"] = (1.0 - m) * _f64(running_mean, dev) + m * mean
+        out["running_var"] = (1.0 - m) * _f64(running_var, dev) + m * unbiased
+    return out
+
+
+def bn_eval_affine(gamma, beta, running_mean, running_var, eps, conv_bias=None):
+    """Eval-mode BatchNorm folded with the conv bias: scale = gamma / sqrt(rv + eps), shift = beta + (bias - rm) * scale."""
+    dev = gamma.device
+    scale = _f64(gamma, dev) / torch.sqrt(_f64(running_var, dev) + float(eps))
+    bias = torch.zeros_like(scale) if conv_bias is None else _f64(conv_bias, dev)
+    return dict(scale=scale, shift=_f64(beta, dev) + (bias - _f64(running_mean, dev)) * scale)
+
+
+def bn_frozen_affine(gamma, beta, running_mean, running_var, eps):
+    """Frozen statistics: mean = rm, rstd = 1 / sqrt(rv + eps), scale = gamma * rstd, shift = beta - rm * scale."""
+    dev = gamma.device
+    rstd = 1.0 / torch.sqrt(_f64(running_var, dev) + float(eps))
+    scale = _f64(gamma, dev) * rstd
+    mean = _f64(running_mean, dev)
+    return dict(mean=mean, rstd=rstd, scale=scale, shift=_f64(beta, dev) - mean * scale)
+
+
+def pool_argmax(a):
+    """Index k = 2 * row + col of the FIRST maximum of every 2x2 window of a [N, H, W, C] (ATen's max_pool2d tie rule)."""
+    n, h, w, c = a.shape
+    win = a.reshape(n, h // 2, 2, w // 2, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(n, h // 2, w // 2, 4, c)
+    hit = (win == win.amax(dim=3, keepdim=True)).to(torch.uint8)
+    return hit.argmax(dim=3)             # first True: torch.argmax returns the first maximal index
+
+
+def pool_scatter(dpool, arg, h, w):
+    """The pooled gradient routed to the window arg-max: [N, H/2, W/2, C] -> [N, H, W, C]."""
+    n, hq, wq, c = dpool.shape
+    g = torch.zeros(n, hq, wq, 4, c, dtype=torch.float64, device=dpool.device)
+    g.scatter_(3, arg.unsqueeze(3), dpool.to(torch.float64).unsqueeze(3))
+    return g.reshape(n, hq, wq, 2, 2, c).permute(0, 1, 3, 2, 4, 5).reshape(n, h, w, c)
+
+
+def bn_relu_bwd(y, scale, shift, mean, rstd, gamma, dskip=None, dpool=None, dtype=torch.float32, frozen=False, sums=None):
+    """Backward of y -> BatchNorm -> ReLU (-> skip and/or 2x2 max-pool).  y, dskip: [N, H, W, C]; dpool [N, H/2, W/2, C].
+    The pool arg-max is taken on the activation as stored (relu(scale y + shift) rounded through `dtype`), first maximum
+    wins.  gh = [scale y + shift > 0] * gradient, xhat = (y - mean) rstd; S1 = sum gh, S2 = sum gh xhat, S3 = sum xhat.
+    k1 = gamma rstd, k2 = k1 S1 / M, k3 = k1 S2 / M; dy = k1 gh - k2 - k3 xhat; dgamma = S2, dbeta = S1, dbias = -k3 S3.
+    frozen: k2 = k3 = 0, dbias = k1 S1.  sums: (S1, S2, S3) given by a producer (the pre_parts forms) instead."""
+    dev = y.device
+    n, h, w, c = y.shape
+    yd = y.to(torch.float64)
+    sc, sh, mu, rs, ga = (_f64(t, dev) for t in (scale, shift, mean, rstd, gamma))
+    nrm = yd * sc + sh
+    gin = torch.zeros_like(yd) if dskip is None else dskip.to(torch.float64).clone()
+    if dpool is not None:
+        a = to_storage(torch.relu(nrm), dtype).to(torch.float64)
+        gin += pool_scatter(dpool, pool_argmax(a), h, w)
+    gh = torch.where(nrm > 0, gin, torch.zeros_like(gin))
+    xh = (yd - mu) * rs
+    if sums is None:
+        sums = tuple(t.reshape(-1, c).sum(0) for t in (gh, gh * xh, xh))
+    s1, s2, s3 = (_f64(t, dev) for t in sums)
+    m = float(n * h * w)
+    k1 = ga * rs
+    if frozen:
+        k2, k3, dbias = torch.zeros_like(k1), torch.zeros_like(k1), k1 * s1
+    else:
+        k2, k3 = k1 * s1 / m, k1 * s2 / m
+        dbias = -k3 * s3
+    dy = k1 * gh - k2 - k3 * xh
+    dy_bound = 4 * EPS32 * ((k1 * gh).abs() + k2.abs() + (k3 * xh).abs())
+    return dict(dy=dy, dy_bound=dy_bound, gh=gh, xh=xh, s1=s1, s2=s2, s3=s3, dgamma=s2, dbeta=s1, dbias=dbias, k1=k1, k2=k2, k3=k3)
+
+
+def head_dz(dprobs, probs):
+    """Gradient of the head's pre-sigmoid output: dz = dprobs * p * (1 - p)."""
+    p = probs.to(torch.float64)
+    return dprobs.to(torch.float64) * p * (1.0 - p)
+
+
+def head_fwd(a, w, b, n, h, wd):
+    """Conv2d(C, OC, 1) + sigmoid: a [P, C] NHWC pixels -> z, probs [N, OC, H, W]."""
+    z = a.to(torch.float64) @ _f64(w, a.device).t() + _f64(b, a.device)
+    z = z.view(n, h, wd, -1).permute(0, 3, 1, 2)
+    return z, torch.sigmoid(z)
+
+
+def head_bwd(dprobs, probs, a, w, dtype=torch.float32, bn=None):
+    """Backward of head_fwd: dz [P, OC], dW [OC, C] = sum dz a, db [OC] = sum dz, da [P, C] = dz @ W.  bn = (y, scale, shift,
+    mean, rstd) of the stage whose activation `a` is: its BatchNorm-backward sums taken on da as stored (rounded through
+    `dtype`), as unetdc_head_bwd_bnstats leaves them."""
+    dev = a.device
+    oc = w.shape[0]
+    dz = head_dz(dprobs, probs).permute(0, 2, 3, 1).reshape(-1, oc)
+    ad = a.to(torch.float64)
+    wd = _f64(w, dev)
+    out = dict(dz=dz, dw=dz.t() @ ad, db=dz.sum(0), da=dz @ wd)
+    if bn is not None:
+        y, sc, sh, mu, rs = bn
+        yd = y.to(torch.float64)
+        g = to_storage(out["da"], dtype).to(torch.float64)
+        gh = torch.where(yd * _f64(sc, dev) + _f64(sh, dev) > 0, g, torch.zeros_like(g))
+        xh = (yd - _f64(mu, dev)) * _f64(rs, dev)
+        out.update(gh=gh, xh=xh, s1=gh.sum(0), s2=(gh * xh).sum(0), s3=xh.sum(0))
+    return out
+
+
+def _log_clamped(x):
+    """torch's BCE clamp: max(log x, -100) (log 0 = -inf -> -100)."""
+    return torch.log(x).clamp_min(-100.0)
+
+
+def focal_dice(p, t, alpha, gamma, ratio, smooth):
+    """The fused Focal + Dice loss of csrc/loss.hip on [nimg, hw] maps, fp64: bce = -(t max(log p, -100) + (1-t) max(log(1-p),
+    -100)), pt = exp(-bce), focal = mean alpha (1-pt)^gamma bce; dice_i = (2 I + s) / (P + T + s);
+    loss = ratio focal + (1 - ratio)(1 - mean dice).  d loss / d p for grad_out = 1: the clamped log contributes no
+    gradient (its derivative term is dropped where log <= -100), dice through c1 = 2 / U, c2 = (2 I + s) / U^2."""
+    p, t = p.to(torch.float64), t.to(torch.float64)
+    nimg, hw = p.shape
+    numel = float(nimg * hw)
+    lp, lq = torch.log(p), torch.log1p(-p)
+    bce = -(t * lp.clamp_min(-100.0) + (1 - t) * lq.clamp_min(-100.0))
+    pt = torch.exp(-bce)
+    om = 1 - pt
+    focal = alpha * om.pow(gamma) * bce
+    dbce = -(torch.where(lp > -100, t / p, torch.zeros_like(p)) - torch.where(lq > -100, (1 - t) / (1 - p), torch.zeros_like(p)))
+    dfocal = alpha * (gamma * om.pow(gamma - 1) * pt * bce + om.pow(gamma)) * dbce
+    inter, psum, tsum = (p * t).sum(1), p.sum(1), t.sum(1)
+    u = psum + tsum + smooth
+    dice = (2 * inter + smooth) / u
+    c1, c2 = 2 / u, (2 * inter + smooth) / (u * u)
+    loss = ratio * focal.sum() / numel + (1 - ratio) * (1 - dice.mean())
+    dp = ratio * dfocal / numel - (1 - ratio) / nimg * (t * c1[:, None] - c2[:, None])
+    return dict(loss=loss, dp=dp, focal=focal, dfocal=dfocal, bce=bce, c1=c1, c2=c2, inter=inter, psum=psum, tsum=tsum)
+
+
+_TINY = 2.0 ** -147                      # absolute slack of one fp32 operation whose result is subnormal
+
+
+def _widen(lo, hi, rel):
+    """[lo, hi] widened by `rel` times the larger magnitude (plus the subnormal slack): one rounded fp32 operation."""
+    m = torch.maximum(lo.abs(), hi.abs()) * rel + _TINY
+    return lo - m, hi + m
+
+
+def _mul(alo, ahi, blo, bhi):
+    c = torch.stack([alo * blo, alo * bhi, ahi * blo, ahi * bhi])
+    return c.amin(0), c.amax(0)
+
+
+def focal_dice_bounds(p, t, alpha, gamma, ratio, smooth, grad_out, nsum):
+    """Interval bounds on what csrc/loss.hip's fp32 arithmetic can produce: every fp32 operation is widened by one rounding
+    (2^-24 relative), logf / log1pf / expf / powf by 4 ulp, and the three fp32 sums per map by nsum roundings (nsum = the
+    longest chain of additions any partial sum goes through).  alpha / gamma / ratio / smooth must be the fp32 values the
+    kernel receives.  Returns (loss_lo, loss_hi) and per-element (dp_lo, dp_hi) for dprobs = grad_out * d loss / d p."""
+    E, LIB = EPS32, 8 * EPS32
+    p, t = p.to(torch.float64), t.to(torch.float64)
+    nimg, hw = p.shape
+    numel = float(nimg * hw)
+    lp, lq = torch.log(p), torch.log1p(-p)
+    tl, ql = (t * lp.clamp_min(-100.0)).abs(), ((1 - t) * lq.clamp_min(-100.0)).abs()
+    bce = tl + ql
+    db = 2 * LIB * (tl + ql) + _TINY
+    b_lo, b_hi = (bce - db).clamp_min(0.0), bce + db
+    pt_lo, pt_hi = torch.exp(-b_hi) * (1 - LIB) - _TINY, (torch.exp(-b_lo) * (1 + LIB) + _TINY).clamp_max(1.0)
+    pt_lo = pt_lo.clamp_min(0.0)
+    om_lo, om_hi = ((1 - pt_hi) * (1 - E) - _TINY).clamp_min(0.0), (1 - pt_lo) * (1 + E) + _TINY
+    if gamma == 2.0:
+        o1_lo, o1_hi = om_lo, om_hi
+    else:
+        o1_lo, o1_hi = om_lo.pow(gamma - 1) * (1 - LIB) - _TINY, om_hi.pow(gamma - 1) * (1 + LIB) + _TINY
+        o1_lo = o1_lo.clamp_min(0.0)
+    og_lo, og_hi = (o1_lo * om_lo * (1 - E) - _TINY).clamp_min(0.0), o1_hi * om_hi * (1 + E) + _TINY
+    f_lo, f_hi = alpha * og_lo * b_lo * (1 - 2 * E) - _TINY, alpha * og_hi * b_hi * (1 + 2 * E) + _TINY
+    # forward: the sums of focal terms, p * t, p and t
+    ferr = nsum * E * f_hi.abs().sum()
+    F_lo, F_hi = f_lo.sum() - ferr, f_hi.sum() + ferr
+    pt_, ps_, ts_ = p * t, p, t
+    I, P, T = pt_.sum(1), ps_.sum(1), ts_.sum(1)
+    dI, dP, dT = (nsum * E * x.abs().sum(1) for x in (pt_, ps_, ts_))
+    U_lo, U_hi = (P - dP) + (T - dT) + smooth, (P + dP) + (T + dT) + smooth
+    I_lo, I_hi = I - dI, I + dI
+    D_lo, D_hi = ((2 * I_lo + smooth) / U_hi).sum(), ((2 * I_hi + smooth) / U_lo).sum()
+    loss_lo = ratio * F_lo / numel + (1 - ratio) * (1 - D_hi / nimg)
+    loss_hi = ratio * F_hi / numel + (1 - ratio) * (1 - D_lo / nimg)
+    loss_lo, loss_hi = _widen(loss_lo, loss_hi, 2 * E)
+    # backward
+    a1 = torch.where(lp > -100, t / p, torch.zeros_like(p)).abs()
+    a2 = torch.where(lq > -100, (1 - t) / (1 - p), torch.zeros_like(p)).abs()
+    dbce = -(torch.where(lp > -100, t / p, torch.zeros_like(p)) - torch.where(lq > -100, (1 - t) / (1 - p), torch.zeros_like(p)))
+    dd = 3 * E * a1 + 5 * E * a2 + _TINY
+    d_lo, d_hi = dbce - dd, dbce + dd
+    A_lo = ((gamma * o1_lo * pt_lo * b_lo) * (1 - 3 * E) + og_lo) * (1 - E)
+    A_hi = ((gamma * o1_hi * pt_hi * b_hi) * (1 + 3 * E) + og_hi) * (1 + E) + _TINY
+    df_lo, df_hi = _widen(*_mul(alpha * A_lo, alpha * A_hi, d_lo, d_hi), 2 * E)
+    c1_lo, c1_hi = 2 / U_hi * (1 - E), 2 / U_lo * (1 + E)
+    c2_lo, c2_hi = (2 * I_lo + smooth) / (U_hi * U_hi) * (1 - E), (2 * I_hi + smooth) / (U_lo * U_lo) * (1 + E)
+    kf = torch.tensor(ratio / numel, dtype=torch.float64).float().double().item()
+    kd = (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(ratio, dtype=torch.float32)) / torch.tensor(float(nimg))
+    kd = float(kd.double())
+    u_lo, u_hi = _widen(kf * df_lo, kf * df_hi, E)
+    tc_lo, tc_hi = _widen(*_mul(t, t, c1_lo[:, None], c1_hi[:, None]), E)
+    v_lo, v_hi = _widen(tc_lo - c2_hi[:, None], tc_hi - c2_lo[:, None], E)
+    w_lo, w_hi = _widen(kd * v_lo, kd * v_hi, E)
+    r_lo, r_hi = _widen(u_lo - w_hi, u_hi - w_lo, E)
+    g = float(grad_out)
+    dp_lo, dp_hi = _widen(*_mul(torch.full_like(r_lo, g), torch.full_like(r_hi, g), r_lo, r_hi), E)
+    return (loss_lo, loss_hi), (dp_lo, dp_hi)
+
+
+def within_bound(got, ref, bound, dtype):
+    """Elementwise check of a stored value against an fp64 reference whose fp32 computation can be off by `bound`: the stored
+    value must lie in [store(ref - bound), store(ref + bound)] where store is the storage rounding (round-to-nearest-even is
+    monotone, so this is 'the rounding of the reference, or either neighbour when the reference lies within the bound of a
+    rounding boundary'; bound 0 = equality).  NaN-strict.  Returns a boolean mask of the elements that fail."""
+    ref, bound = ref.to(torch.float64), torch.as_tensor(bound, dtype=torch.float64, device=ref.device)
+    lo = to_storage(ref - bound, dtype).to(torch.float64)
+    hi = to_storage(ref + bound, dtype).to(torch.float64)
+    g = got.to(device=ref.device, dtype=torch.float64).reshape(ref.shape)
+    return ~((g >= lo) & (g <= hi))
+
+
+def sum_is_exact(terms, res):
+    """Every fp32 partial sum of `terms` ([rows, C], multiples of `res`) is exact in any order: sum |terms| / res < 2^24."""
+    t = terms.to(torch.float64).reshape(-1, terms.shape[-1]) / res
+    return bool((t == t.round()).all()) and float(t.abs().sum(0).max()) < EXACT_LIMIT
+
+
 # ---------------------------------------------------------------------------------------------------- fixtures
 def ints(shape, r, g, lo=None, device="cpu"):
     """Uniform integers in {lo..r} (lo = -r by default) as fp32."""
@@ -362,18 +612,53 @@ ARGS = {
     "unetdc_convT2x2_dgrad_bnstats": "dup lddup w_dgrad dx lddx y_prev ldy_prev scale shift mean rstd parts parts_floats nparts n h "
                                      "w cin cout dtype s",
     "unetdc_conv3x3_dgrad_colsum": "dy lddy w_dgrad dx lddx colsum c0 c workspace workspace_bytes n h w cin cout dilation dtype s",
+    "unetdc_bn_finalize": "stats_part rows count gamma beta eps momentum running_mean running_var scale shift mean rstd c s",
+    "unetdc_bn_eval_affine": "gamma beta running_mean running_var conv_bias eps scale shift c s",
+    "unetdc_bn_frozen_affine": "gamma beta running_mean running_var eps scale shift mean rstd c s",
+    "unetdc_bn_relu_bwd": "dskip ldskip dpool ldpool y ldy scale shift mean rstd gamma dy lddy dgamma dbeta dbias workspace "
+                          "workspace_bytes pre_parts pre_nparts n h w c dtype s",
+    "unetdc_bn_relu_bwd_frozen": "dskip ldskip dpool ldpool y ldy scale shift mean rstd gamma dy lddy dgamma dbeta dbias workspace "
+                                 "workspace_bytes pre_parts pre_nparts n h w c dtype s",
+    "unetdc_bn_relu_bwd_head": "dprobs probs head_w y ldy scale shift mean rstd gamma dy lddy dgamma dbeta dbias workspace "
+                               "workspace_bytes pre_parts pre_nparts n h w c dtype s",
+    "unetdc_bn_relu_bwd_coeffs": "pre_parts pre_nparts gamma rstd dgamma dbeta dbias coeffs n h w c s",
+    "unetdc_head_fwd": "a lda w b probs n h wd c oc dtype s",
+    "unetdc_head_fwd_bn": "y ldy scale shift w b probs n h wd c oc dtype s",
+    "unetdc_head_bwd": "dprobs probs a lda w da ldda dw db workspace workspace_bytes n h wd c oc dtype s",
+    "unetdc_head_bwd_bnstats": "dprobs probs a lda w da ldda dw db workspace workspace_bytes y_prev ldy_prev scale shift mean rstd "
+                               "parts parts_floats nparts n h wd c oc dtype s",
+    "unetdc_focal_dice_loss_fwd": "probs target loss_out coef workspace workspace_bytes nimg hw alpha gamma ratio smooth s",
+    "unetdc_focal_dice_loss_bwd": "probs target coef grad_out dprobs nimg hw alpha gamma ratio s",
 }
 ARGS = {k: tuple(v.split()) for k, v in ARGS.items()}
-SHAPE_NAMES = ("n", "h", "w", "wd", "cin", "cout", "dilation", "c0", "c")
+SHAPE_NAMES = ("n", "h", "w", "wd", "cin", "cout", "dilation", "c0", "c", "oc", "rows", "count", "pre_nparts", "nimg", "hw",
+               "parts_floats")
+# the fields of every replayed symbol a runner needs (tests/test_exact_ref_cpu.py checks them against the table)
+REPLAY_KEYS = {"unetdc_bn_finalize": ("rows", "count", "c", "eps", "momentum", "ptr:running_mean"),
+               "unetdc_bn_eval_affine": ("c", "eps", "ptr:conv_bias"),
+               "unetdc_bn_frozen_affine": ("c", "eps"),
+               "unetdc_bn_relu_bwd_coeffs": ("n", "h", "w", "c", "pre_nparts"),
+               "unetdc_focal_dice_loss_fwd": ("nimg", "hw", "alpha", "gamma", "ratio", "smooth", "workspace_bytes"),
+               "unetdc_focal_dice_loss_bwd": ("nimg", "hw", "alpha", "gamma", "ratio")}
+FLOAT_NAMES = ("eps", "momentum", "alpha", "gamma", "ratio", "smooth")
 CANON = {"wd": "w"}                      # the first-layer symbols call the image width `wd` (their `w` is the weight)
 
 
+def arg_kinds(argtypes):
+    """ctypes argument types -> 'P' (pointer), 'I' (int), 'F' (float / double), 'L' (int64)."""
+    return ["P" if t.__name__ == "c_void_p" else "I" if t.__name__ == "c_int" else "F" if t.__name__ in ("c_float", "c_double")
+            else "L" for t in argtypes]
+
+
 def positions(sym, kinds):
-    """name -> position for the arguments of `sym` that the replay reads: shapes (int), lds, dtype, pointers, workspace."""
+    """name -> position for the arguments of `sym` that the replay reads: shapes (int / int64), lds, dtype, scalar parameters
+    (float), pointers, workspace."""
     out = {}
     for i, (name, kind) in enumerate(zip(ARGS[sym], kinds)):
-        if kind == "I" and (name in SHAPE_NAMES or name.startswith("ld") or name == "dtype"):
+        if kind in "IL" and (name in SHAPE_NAMES or name.startswith("ld") or name == "dtype"):
             out[CANON.get(name, name)] = i
+        elif kind == "F" and name in FLOAT_NAMES:
+            out[name] = i
         elif kind == "P" and name != "s":
             out["ptr:" + name] = i
         elif name == "workspace_bytes":

@@ -174,8 +174,170 @@ def test_argument_table_matches_the_header():
     for sym, names in X.ARGS.items():
         assert hdr[sym] == names, (sym, hdr[sym], names)
         assert len(SIGNATURES[sym][1]) == len(names), sym
-        kinds = ["P" if t.__name__ == "c_void_p" else "I" if t.__name__ == "c_int" else "L" for t in SIGNATURES[sym][1]]
+        kinds = X.arg_kinds(SIGNATURES[sym][1])
         pos = X.positions(sym, kinds)
-        for key in ("n", "h", "w", "dtype"):
+        for key in X.REPLAY_KEYS.get(sym, ("n", "h", "w", "dtype")):
             assert key in pos, (sym, key)
         assert all(names[i].startswith("ld") for k, i in pos.items() if k.startswith("ld"))
+
+
+# ---------------------------------------------------------------------------------------------------- BatchNorm, head, loss
+@pytest.mark.parametrize("rows,count", [(1, 64), (7, 3 * 5 * 7), (600, 1 << 12)])
+def test_bn_finalize_reference_matches_batch_norm(rows, count):
+    g = gen(11)
+    c = 6
+    y = torch.randn(count, c, generator=g, dtype=torch.float64) * 2 + 0.5
+    cut = torch.sort(torch.randperm(count - 1, generator=g)[: rows - 1] + 1).values.tolist()
+    parts = torch.stack([torch.stack([b.sum(0), (b * b).sum(0)]) for b in torch.tensor_split(y, cut)])
+    gamma, beta = torch.rand(c, generator=g, dtype=torch.float64) + 0.5, torch.randn(c, generator=g, dtype=torch.float64)
+    rm, rv = torch.randn(c, generator=g, dtype=torch.float64), torch.rand(c, generator=g, dtype=torch.float64) + 0.5
+    ref = X.bn_finalize(parts, count, gamma, beta, 1e-5, 0.1, rm, rv)
+    rm2, rv2 = rm.clone(), rv.clone()
+    out = F.batch_norm(y, rm2, rv2, gamma, beta, training=True, momentum=0.1, eps=1e-5)
+    torch.testing.assert_close(ref["running_mean"], rm2)
+    torch.testing.assert_close(ref["running_var"], rv2)
+    torch.testing.assert_close(y * ref["scale"] + ref["shift"], out)
+    torch.testing.assert_close(ref["mean"], y.mean(0))
+    fr = X.bn_frozen_affine(gamma, beta, rm, rv, 1e-5)
+    torch.testing.assert_close(y * fr["scale"] + fr["shift"], F.batch_norm(y, rm, rv, gamma, beta, training=False, eps=1e-5))
+    bias = torch.randn(c, generator=g, dtype=torch.float64)
+    ev = X.bn_eval_affine(gamma, beta, rm, rv, 1e-5, bias)
+    torch.testing.assert_close(y * ev["scale"] + ev["shift"], F.batch_norm(y + bias, rm, rv, gamma, beta, training=False, eps=1e-5))
+
+
+def _bn_autograd(y, gamma, beta, rm, rv, dskip, dpool, frozen):
+    """dL/dy, dL/dgamma, dL/dbeta, dL/dbias (bias added to the conv output in front of the BatchNorm) by autograd, NCHW."""
+    yr, gr, br = y.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    a = torch.relu(F.batch_norm(yr, rm.clone(), rv.clone(), gr, br, training=not frozen, momentum=0.1, eps=1e-5))
+    out = (a * dskip).sum() if dskip is not None else 0
+    if dpool is not None:
+        out = out + (F.max_pool2d(a, 2) * dpool).sum()
+    gy, gg, gb = torch.autograd.grad(out, (yr, gr, br))
+    return gy, gg, gb, gy.sum(dim=(0, 2, 3))
+
+
+@pytest.mark.parametrize("form", ["skip", "pool", "skip+pool", "frozen", "frozen+pool"])
+def test_bn_relu_backward_reference_matches_autograd(form):
+    g = gen(12)
+    n, c, h, w = 2, 5, 6, 8
+    y = torch.randn(n, c, h, w, generator=g, dtype=torch.float64)
+    gamma, beta = torch.rand(c, generator=g, dtype=torch.float64) + 0.5, torch.randn(c, generator=g, dtype=torch.float64) * 0.3
+    rm, rv = torch.randn(c, generator=g, dtype=torch.float64) * 0.2, torch.rand(c, generator=g, dtype=torch.float64) + 0.5
+    dskip = torch.randn(n, c, h, w, generator=g, dtype=torch.float64) if "skip" in form or form == "frozen" else None
+    dpool = torch.randn(n, c, h // 2, w // 2, generator=g, dtype=torch.float64) if "pool" in form else None
+    frozen = form.startswith("frozen")
+    if frozen:
+        st = X.bn_frozen_affine(gamma, beta, rm, rv, 1e-5)
+        mean, rstd = st["mean"], st["rstd"]
+    else:
+        mean = y.mean(dim=(0, 2, 3))
+        rstd = 1 / torch.sqrt(y.var(dim=(0, 2, 3), unbiased=False) + 1e-5)
+        st = dict(scale=gamma * rstd, shift=beta - mean * gamma * rstd)
+    ref = X.bn_relu_bwd(nhwc(y), st["scale"], st["shift"], mean, rstd, gamma, None if dskip is None else nhwc(dskip),
+                        None if dpool is None else nhwc(dpool), torch.float64, frozen=frozen)
+    gy, gg, gb, gbias = _bn_autograd(y, gamma, beta, rm, rv, dskip, dpool, frozen)
+    torch.testing.assert_close(ref["dy"], nhwc(gy))
+    torch.testing.assert_close(ref["dgamma"], gg)
+    torch.testing.assert_close(ref["dbeta"], gb)
+    torch.testing.assert_close(ref["dbias"], gbias, atol=1e-12, rtol=1e-9)
+
+
+def test_pool_argmax_is_atens_first_maximum():
+    """Windows full of ties (and ReLU zeros): the reference routes the pooled gradient like ATen's max_pool2d backward."""
+    g = gen(13)
+    a = torch.relu(X.ints((2, 3, 8, 10), 1, g).double())          # {0, 1}: almost every window has a tie
+    dpool = torch.randn(2, 3, 4, 5, generator=g, dtype=torch.float64)
+    ar = a.clone().requires_grad_(True)
+    ga, = torch.autograd.grad((F.max_pool2d(ar, 2) * dpool).sum(), ar)
+    mine = X.pool_scatter(nhwc(dpool), X.pool_argmax(nhwc(a)), 8, 10)
+    assert torch.equal(mine, nhwc(ga))
+    assert int((X.pool_argmax(nhwc(a)) == 0).sum()) > 0 and int((X.pool_argmax(nhwc(a)) == 3).sum()) > 0
+
+
+@pytest.mark.parametrize("oc", [1, 2])
+def test_head_reference_matches_autograd(oc):
+    g = gen(14)
+    n, c, h, w = 2, 16, 5, 7
+    a = torch.relu(torch.randn(n, c, h, w, generator=g, dtype=torch.float64))
+    wt, b = torch.randn(oc, c, generator=g, dtype=torch.float64), torch.randn(oc, generator=g, dtype=torch.float64)
+    dprobs = torch.randn(n, oc, h, w, generator=g, dtype=torch.float64)
+    ar, wr, br = a.clone().requires_grad_(True), wt.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    probs = torch.sigmoid(F.conv2d(ar, wr[:, :, None, None], br))
+    ga, gw, gb = torch.autograd.grad(probs, (ar, wr, br), dprobs)
+    am = nhwc(a).reshape(-1, c)
+    _, p = X.head_fwd(am, wt, b, n, h, w)
+    torch.testing.assert_close(p, probs.detach())
+    ref = X.head_bwd(dprobs, p, am, wt, torch.float64)
+    torch.testing.assert_close(ref["dw"], gw)
+    torch.testing.assert_close(ref["db"], gb)
+    torch.testing.assert_close(ref["da"], nhwc(ga).reshape(-1, c))
+    # the fused BatchNorm-backward sums are bn_relu_bwd's sums with dskip = da
+    y = torch.randn(n * h * w, c, generator=g, dtype=torch.float64)
+    sc, sh, mu, rs = (torch.randn(c, generator=g, dtype=torch.float64) for _ in range(4))
+    ref = X.head_bwd(dprobs, p, am, wt, torch.float64, bn=(y, sc, sh, mu, rs))
+    bn = X.bn_relu_bwd(y.view(n, h, w, c), sc, sh, mu, rs, torch.ones(c, dtype=torch.float64), ref["da"].view(n, h, w, c),
+                       None, torch.float64)
+    for k in ("s1", "s2", "s3"):
+        torch.testing.assert_close(ref[k], bn[k])
+
+
+@pytest.mark.parametrize("gamma", [2.0, 1.5])
+def test_focal_dice_reference_matches_autograd(gamma):
+    from utils.metrics_DC import focal_dice_loss
+    g = gen(15)
+    n, h, w = 3, 6, 9
+    p = torch.rand(n, 1, h, w, generator=g, dtype=torch.float64) * 0.98 + 0.01
+    t = (torch.rand(n, 1, h, w, generator=g, dtype=torch.float64) < 0.3).double()
+    t[0, 0, 0, :3] = torch.tensor([0.25, 0.5, 0.75], dtype=torch.float64)       # soft targets too
+    pr = p.clone().requires_grad_(True)
+    loss = focal_dice_loss(pr, t, alpha=0.8, gamma=gamma, ratio=0.3)
+    gp, = torch.autograd.grad(loss, pr)
+    ref = X.focal_dice(p.view(n, -1), t.view(n, -1), 0.8, gamma, 0.3, 1e-7)
+    torch.testing.assert_close(ref["loss"], loss.detach())
+    torch.testing.assert_close(ref["dp"], gp.view(n, -1))
+
+
+def _loss_fp32(p, t, alpha, gamma, ratio, smooth, gout):
+    """csrc/loss.hip restated in fp32 torch arithmetic (sums in fp32 over one chain per map)."""
+    f32 = torch.float32
+    lp, lq = torch.log(p), torch.log1p(-p)
+    bce = -(t * lp.clamp_min(-100) + (1 - t) * lq.clamp_min(-100))
+    dbce = -(torch.where(lp > -100, t / p, torch.zeros_like(p)) - torch.where(lq > -100, (1 - t) / (1 - p), torch.zeros_like(p)))
+    pt = torch.exp(-bce)
+    om = 1 - pt
+    omg1 = om if gamma == 2.0 else torch.pow(om, torch.tensor(gamma - 1, dtype=f32))
+    omg = omg1 * om
+    focal = alpha * omg * bce
+    dfocal = alpha * (gamma * omg1 * pt * bce + omg) * dbce
+    nimg, hw = p.shape
+    sums = [torch.cumsum(x, 1, dtype=f32)[:, -1].double() for x in (focal, p * t, p, t)]
+    u = sums[2] + sums[3] + float(smooth)
+    dice = (2 * sums[1] + float(smooth)) / u
+    loss = (ratio * (float(sums[0].sum()) / (nimg * hw)) + (1 - ratio) * (1 - float(dice.sum()) / nimg))
+    c1, c2 = (2 / u).float(), ((2 * sums[1] + float(smooth)) / (u * u)).float()
+    kf = torch.tensor(ratio / (nimg * hw), dtype=torch.float64).float()
+    kd = (1 - torch.tensor(ratio, dtype=f32)) / torch.tensor(float(nimg))
+    dp = gout * (kf * dfocal - kd * (t * c1[:, None] - c2[:, None]))
+    return torch.tensor(loss).float(), dp
+
+
+@pytest.mark.parametrize("gamma", [2.0, 1.5])
+def test_focal_dice_bounds_hold_an_fp32_evaluation(gamma):
+    """The interval bounds the GPU tests use contain an fp32 evaluation of the same formula, at the edge values they test
+    (p of 0, 1, 1e-45 and 1 - 2^-24, i.e. the log clamp), and stay tight on ordinary values."""
+    g = gen(16)
+    nimg, hw = 3, 4096
+    p = torch.rand(nimg, hw, generator=g)
+    p[:, :8] = torch.tensor([0.0, 1.0, 1e-45, 1 - 2 ** -24] * 2)
+    t = (torch.rand(nimg, hw, generator=g) < 0.2).float()
+    t[:, :8] = torch.tensor([0.0, 0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0])
+    alpha, ratio, smooth, gout = (float(torch.tensor(v, dtype=torch.float32)) for v in (0.8, 0.3, 1e-7, -1.75))
+    loss, dp = _loss_fp32(p, t, alpha, gamma, ratio, smooth, gout)
+    (llo, lhi), (dlo, dhi) = X.focal_dice_bounds(p, t, alpha, gamma, ratio, smooth, gout, nsum=hw + 8)
+    assert float(llo) <= float(loss) <= float(lhi)
+    dpd = dp.double()
+    assert bool(((dpd >= dlo) & (dpd <= dhi)).all())
+    ref = X.focal_dice(p, t, alpha, gamma, ratio, smooth)
+    assert float(lhi - llo) < 4 * (hw + 8) * X.EPS32 * abs(float(ref["loss"]))       # the summation term dominates
+    width = (dhi - dlo)[:, 8:]
+    assert float((width / (gout * ref["dp"][:, 8:]).abs()).max()) < 1e-2         # (nsum = hw here: the GPU sums are far shorter)

@@ -7,7 +7,8 @@ hold a large finite sentinel: a read of the wrong columns or rows that reaches t
 
 Route cases: the operator shapes of tests/test_gpu_ops.py, dense and one-hot fixtures, both dtypes.  Production replay:
 one training step of UNetDC(1, 1) per configuration is recorded, and every distinct call (symbol, shapes, lds, dtype,
-optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must reach the same kernel."""
+optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must reach the same kernel.  The
+BatchNorm, head and loss calls of the step are replayed through the runners of tests/test_gpu_exact_norm.py."""
 import ctypes
 import os
 
@@ -17,6 +18,8 @@ import torch
 from tests import exact_ref as X
 
 pytestmark = pytest.mark.gpu
+
+from tests import test_gpu_exact_norm as N
 
 if torch.cuda.is_available():
     from tests.test_gpu_ops import CONV_CASES
@@ -670,26 +673,56 @@ RUNNERS = {
     "unetdc_convT2x2_dgrad_bnstats": lambda kw: convt_dgrad(kw, "onehot", bnstats=True),
     "unetdc_convT2x2_wgrad": lambda kw: convt_wgrad(kw, "onehot"),
     "unetdc_bn_relu_apply": lambda kw: bn_relu_apply(kw, "onehot"),
+    # BatchNorm, head and loss (tests/test_gpu_exact_norm.py): exact or fp64-bounded, no matrix-core kernel name
+    "unetdc_bn_finalize": lambda kw: N.bn_finalize(kw),
+    "unetdc_bn_eval_affine": lambda kw: N.bn_affine(kw, frozen=False),
+    "unetdc_bn_frozen_affine": lambda kw: N.bn_affine(kw, frozen=True),
+    "unetdc_bn_relu_bwd": lambda kw: N.bn_relu_bwd(kw, "plain"),
+    "unetdc_bn_relu_bwd_frozen": lambda kw: N.bn_relu_bwd(kw, "frozen"),
+    "unetdc_bn_relu_bwd_head": lambda kw: N.bn_relu_bwd(kw, "head"),
+    "unetdc_bn_relu_bwd_coeffs": lambda kw: N.bn_relu_bwd_coeffs(kw),
+    "unetdc_head_fwd": lambda kw: N.head_fwd(kw),
+    "unetdc_head_fwd_bn": lambda kw: N.head_fwd(kw, bn=True),
+    "unetdc_head_bwd": lambda kw: N.head_bwd(kw, bnstats=False),
+    "unetdc_head_bwd_bnstats": lambda kw: N.head_bwd(kw),
+    "unetdc_focal_dice_loss_fwd": lambda kw: N.focal_dice_loss(kw),
+    "unetdc_focal_dice_loss_bwd": lambda kw: N.focal_dice_loss(kw),
 }
-REPLAY_CONFIGS = {"bf16_8x512": ("bf16", 8, 512), "f32_8x512": ("f32", 8, 512), "bf16_4x1024": ("bf16", 4, 1024)}
-# 1024^2: the forward and weight-gradient calls only (the host reference of the whole step is over the time budget;
-# its input-gradient calls take the same kernels as at 512^2 with twice the items per workgroup)
+# symbols a step may issue that the replay does not run, with the reason and the test that covers them
+REPLAY_EXEMPT = {
+    "unetdc_pack_many": "weight re-packing, not step arithmetic: tests/test_gpu_ops.py::test_pack_many_matches_per_layer_packers",
+}
+NON_CONV = {s for s in RUNNERS if not any(k in s for k in ("conv3x3", "convT2x2"))}
+# config -> (dtype, batch, size, mode): train = one training step; eval = an eval-mode forward (BatchNorm folded from the
+# running statistics); frozen = eval mode under autograd (frozen statistics), forward and backward
+REPLAY_CONFIGS = {"bf16_8x512": ("bf16", 8, 512, "train"), "f32_8x512": ("f32", 8, 512, "train"),
+                  "bf16_4x1024": ("bf16", 4, 1024, "train"), "bf16_8x512_eval": ("bf16", 8, 512, "eval"),
+                  "bf16_8x512_frozen": ("bf16", 8, 512, "frozen")}
+# 1024^2: the forward and weight-gradient convolution calls and every non-convolution call (the host reference of the
+# whole step is over the time budget; its input-gradient calls take the same kernels as at 512^2 with twice the items per
+# workgroup)
 REPLAY_ONLY = {"bf16_4x1024": ("fwd", "wgrad")}
+REPLAYED = set()                # distinct calls replayed by an earlier config of this session (not replayed again)
 
 
-def record_step(dtype, bs, size):
+def record_step(dtype, bs, size, mode="train"):
     from models.model_2 import UNetDC
     from oracle import recipe
     from utils.metrics_DC import focal_dice_loss
     torch.manual_seed(5)
-    model = UNetDC(1, 1).cuda().train()
+    model = UNetDC(1, 1).cuda()
+    model.train(mode == "train")
     if dtype == "bf16":
         model.set_compute_dtype("bf16")
     x = recipe.seeded_input(8, (bs, 1, size, size)).cuda()
     t = recipe.seeded_target(9, (bs, 1, size, size), frac=0.1).cuda()
-    _lib.start_timing(RUNNERS)
+    _lib.start_timing(_lib.SIGNATURES)            # every ABI name: the completeness check sees whatever the step issued
     try:
-        focal_dice_loss(model(x), t, alpha=1.0, gamma=2.0, ratio=0.3).backward()
+        if mode == "eval":
+            with torch.no_grad():
+                model(x)
+        else:
+            focal_dice_loss(model(x), t, alpha=1.0, gamma=2.0, ratio=0.3).backward()
     finally:
         recs = _lib.stop_timing()
     del model, x, t
@@ -698,11 +731,15 @@ def record_step(dtype, bs, size):
 
 
 def distinct_calls(recs):
-    """(symbol, shapes, lds, dtype, optional pointers given) -> (kw, recorded kernel): one replay per distinct call."""
+    """(symbol, shapes, lds, dtype, scalar parameters, optional pointers given) -> (kw, recorded kernel): one replay per
+    distinct call.  Symbols outside the argument table are returned by name with no kw."""
     out = {}
     for name_kernel, args, _ in recs:
         sym, kernel = name_kernel.split("|", 1)
-        kinds = ["P" if t.__name__ == "c_void_p" else "I" if t.__name__ == "c_int" else "L" for t in _lib.SIGNATURES[sym][1]]
+        if sym not in X.ARGS:
+            out.setdefault((sym,), (None, kernel))
+            continue
+        kinds = X.arg_kinds(_lib.SIGNATURES[sym][1])
         kw = {}
         for key, i in X.positions(sym, kinds).items():
             kw[key] = (args[i] is not None) if key.startswith("ptr:") else args[i]
@@ -717,20 +754,39 @@ def distinct_calls(recs):
 @pytest.mark.skipif(THIN or SWITCHED, reason="the replay runs on the default routes only")
 @pytest.mark.parametrize("config", list(REPLAY_CONFIGS))
 def test_production_step_replay(config):
-    """Every distinct convolution call of one training step, replayed with exact fixtures at its own shapes and leading
-    dimensions: the same kernel, a bit-exact output, intact guards."""
-    dtype, bs, size = REPLAY_CONFIGS[config]
-    calls = distinct_calls(record_step(dtype, bs, size))
+    """Every distinct call of one training step (or eval forward, or frozen-statistics step), replayed with exact fixtures
+    at its own shapes and leading dimensions: the same kernel, a bit-exact (or fp64-bounded) output, intact guards.  Every
+    symbol the step issued has a runner or a named exemption."""
+    dtype, bs, size, mode = REPLAY_CONFIGS[config]
+    calls = distinct_calls(record_step(dtype, bs, size, mode))
+    issued = sorted({k[0] for k in calls})
+    missing = [s for s in issued if s not in RUNNERS and s not in REPLAY_EXEMPT]
+    assert not missing, f"{config}: symbols issued by the step with neither a replay runner nor an exemption: {missing}"
+    calls = {k: v for k, v in calls.items() if k[0] in RUNNERS}
     if config in REPLAY_ONLY:
-        calls = {k: v for k, v in calls.items() if any(part in k[0] for part in REPLAY_ONLY[config])}
-    print(f"\n{config}: {len(calls)} distinct calls")
+        calls = {k: v for k, v in calls.items() if k[0] in NON_CONV or any(part in k[0] for part in REPLAY_ONLY[config])}
+    print(f"\n{config}: {len(calls)} distinct calls, symbols issued: {issued}")
     reached = {}
     for key, (kw, kernel) in sorted(calls.items(), key=lambda kv: str(kv[0])):
         sym = key[0]
+        if key in REPLAYED:                        # the same call, already replayed under an earlier config
+            reached.setdefault(sym, set()).add("(replayed earlier)")
+            continue
         name = RUNNERS[sym](kw)
-        if name is not None:                       # (bn_relu_apply names no matrix-core kernel)
+        REPLAYED.add(key)
+        reached.setdefault(sym, set()).add(name or "-")
+        if name is not None:                       # (the elementwise / reduction kernels name no matrix-core kernel)
             assert name == kernel, (sym, kw, kernel, name)
-            reached.setdefault(sym, set()).add(name)
         torch.cuda.empty_cache()
     for sym in sorted(reached):
         print(f"  {sym}: {sorted(reached[sym])}")
+    for sym in issued:
+        assert sym in reached or sym in REPLAY_EXEMPT or config in REPLAY_ONLY, (config, sym)
+    if mode == "train":
+        for sym in ("unetdc_bn_finalize", "unetdc_focal_dice_loss_fwd", "unetdc_focal_dice_loss_bwd", "unetdc_head_fwd_bn",
+                    "unetdc_head_bwd_bnstats", "unetdc_bn_relu_bwd", "unetdc_bn_relu_bwd_head", "unetdc_bn_relu_bwd_coeffs"):
+            assert sym in reached, (config, sym, sorted(reached))
+    elif mode == "eval":
+        assert {"unetdc_bn_eval_affine", "unetdc_head_fwd"} <= set(reached), (config, sorted(reached))
+    else:
+        assert {"unetdc_bn_frozen_affine", "unetdc_bn_relu_bwd_frozen"} <= set(reached), (config, sorted(reached))
