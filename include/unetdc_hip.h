@@ -356,6 +356,48 @@ int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int
                           const unetdc_augment_params* params, int n, const float* fields, int nfields, float* out_img,
                           float* out_mask, unetdc_stream_t s);
 
+
+/* ---- radial and spatial droplet density maps (the reference's quantify_pipline.py:44-142 restated; density.hip) ---------
+ * unetdc_density_maps: for one image of h x w pixels (both sides >= UNETDC_DENSITY_MIN_SIDE):
+ *   roi      = cv2 RGB2GRAY -> GaussianBlur((15, 15), 0) in OpenCV's bit-exact 8-bit form (BORDER_REFLECT_101) -> Otsu ->
+ *              MORPH_CLOSE then MORPH_OPEN with the 15 x 15 rectangle -> > 0;
+ *   (cx, cy) = int(m10 / m00), int(m01 / m00) of roi, (w / 2, h / 2) when the ROI is empty;
+ *   rings    = np.linspace(0, max ROI distance, nb_layers + 1); ring_count[i] = droplets whose centroid distance d has
+ *              b_i < d <= b_{i+1} (droplets: the first min(*droplet_count, max_droplets) entries of unetdc_ccl_stats
+ *              outputs, which must have been made with min_area = 1); the radial map paints ring_count[i] on ring i's ROI pixels;
+ *   spatial  = gaussian_filter(mask, sigma) / (gaussian_filter(roi, sigma) + 1e-5) * 100 in float32 (scipy's mode
+ *              "reflect", truncate 4: radius int(4 sigma + 0.5) <= UNETDC_DENSITY_MAX_RADIUS);
+ *   index planes = min(int(normalize(map) * 256), 255), 0 for a constant map (the pixels of plt.imsave(cmap=...) are
+ *              lut[index]).
+ *   rgb_hwc: [h][w][3] uint8, mask: [h][w] uint8 {0, 1}; taps: HOST array of radius + 1 fp64 weights, centre first, as
+ *   scipy.ndimage's _gaussian_kernel1d(sigma, 0, radius)[radius:].  out_stats, out_radial_index and out_spatial_index
+ *   ([h][w] uint8 each) are DEVICE pointers; out_blur, out_roi, out_ring (ring index + 1, 0 = none) [h][w] uint8 and
+ *   out_radial, out_spatial [h][w] float32 are optional DEVICE outputs of the intermediate planes (NULL: kept in the workspace).
+ *   1 <= nb_layers <= UNETDC_DENSITY_MAX_LAYERS.
+ * unetdc_density_sqrt: out[i] = sqrt((double)x[i]) with the square root the density kernels use (DEVICE pointers). */
+#define UNETDC_DENSITY_MIN_SIDE 2
+#define UNETDC_DENSITY_MAX_LAYERS 255
+#define UNETDC_DENSITY_MAX_RADIUS 128
+typedef struct unetdc_density_stats {
+  int64_t roi_area;            /* m00 */
+  int64_t m10, m01;            /* sums of x and y over the ROI */
+  int32_t cx, cy;              /* ROI centroid (truncated) */
+  int32_t otsu_threshold;
+  int32_t nb_layers;
+  double max_ring_distance;    /* largest ROI pixel distance from (cx, cy); 0 for an empty ROI */
+  int32_t ndroplets;           /* *droplet_count as read */
+  uint32_t radial_min_bits, radial_max_bits, spatial_min_bits, spatial_max_bits;     /* float32 bit patterns */
+  int32_t ring_count[UNETDC_DENSITY_MAX_LAYERS];
+} unetdc_density_stats;
+int64_t unetdc_density_workspace(int h, int w);
+int unetdc_density_maps(const uint8_t* rgb_hwc, const uint8_t* mask, int h, int w, const int32_t* droplet_count,
+                        const int32_t* droplet_area, const int64_t* droplet_sumy, const int64_t* droplet_sumx,
+                        int max_droplets, int nb_layers, double sigma, const double* taps, void* workspace,
+                        int64_t workspace_bytes, unetdc_density_stats* out_stats, uint8_t* out_radial_index,
+                        uint8_t* out_spatial_index, uint8_t* out_blur, uint8_t* out_roi, uint8_t* out_ring,
+                        float* out_radial, float* out_spatial, unetdc_stream_t s);
+int unetdc_density_sqrt(const int64_t* x, double* out, int64_t n, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,12 +44,20 @@ def decode_rgb(path):
     return np.array(Image.open(path).convert("RGB"))
 
 
-def preprocess(path, background_radius, im=None):
+def preprocess(path, background_radius, im=None, keep_rgb=False):
+    """-> (network input, (oh, ow)), and with keep_rgb the decoded original image as well (a device tensor on the GPU
+    path: the density maps read it there without a second upload)."""
     im = decode_rgb(path) if im is None else im
     oh, ow = im.shape[:2]
     if DEVICE == "cuda":                                 # rolling ball + resize + /255 + CHW on the GPU (csrc/preprocess.hip)
         from unet_dc_segmentation_amd.preprocess import preprocess_device
+        if keep_rgb:
+            x, rgb = preprocess_device(im, background_radius, IMG_SIZE, DEVICE, return_rgb=True)
+            return x, (oh, ow), rgb
         return preprocess_device(im, background_radius, IMG_SIZE, DEVICE), (oh, ow)
+    if keep_rgb:
+        t, osize = preprocess(path, background_radius, im)
+        return t, osize, im
     im = rolling_ball_correction_rgb(im, background_radius)
     im = resize_image(im, IMG_SIZE).astype(np.float32) / 255.0
     return torch.from_numpy(im).permute(2, 0, 1), (oh, ow)
@@ -109,15 +117,35 @@ def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir):
         Image.fromarray(img).save(str(overlay_dir / f"{name}_overlay.png"))
 
 
+def _density(density, dres, rgb, mask, fpath, name, writers):
+    """--density_maps for one image: the row of density_per_image.csv, and the two heat-map PNGs (colormap gather and deflate
+    in the writer pool).  dres: the device results of the batch for this image, or None on the CPU path."""
+    from utils import density as hd
+    r = hd.density_maps(rgb, mask, density["nb_layers"], density["kernel"]) if dres is None else dres
+    density["rows"].append(hd.csv_row(Path(fpath).name, r, density["nb_layers"]))
+    job = (hd.write_pngs, r["radial_index"], r["spatial_index"], density["out_dir"], name)
+    if writers is None:
+        job[0](*job[1:])
+    else:
+        writers[1].append(writers[0].submit(*job))
+
+
 @torch.no_grad()
-def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None):
+def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
+              density=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
     masks512 = None if on_device else (probs[:, 0] > thresh).to(torch.uint8).numpy()
     if on_device:                                        # the whole batch enqueued back to back, ONE host wait (droplets.py)
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
-        dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area)
+        if density is None:
+            dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area)
+        else:                                            # the maps count every component: the table's sums serve when min_area <= 1
+            from unet_dc_segmentation_amd.density import density_maps_batch
+            dev_out, sums = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, keep_sums=True)
+            dres = density_maps_batch(density["rgbs"], [o[0] for o in dev_out], sums if min_area <= 1 else None,
+                                      density["nb_layers"], density["kernel"])
     for i in range(len(tensors)):
         fpath, (oh, ow) = meta[i]
         name = Path(fpath).stem
@@ -137,6 +165,9 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
             _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir)
         else:
             writers[1].append(writers[0].submit(_write_outputs, mask, df, fpath, name, mask_dir, overlay_dir))
+        if density is not None:
+            _density(density, dres[i] if on_device else None, density["rgbs"][i], mask, fpath, name, writers)
+        if writers is not None:
             # back-pressure: at most ~4 batches of masks / tables wait for the writers; waiting on the OLDEST write also surfaces a
             # failed write while the run is still going
             while len(writers[1]) > writers[2]:
@@ -157,6 +188,10 @@ def build_parser():
     p.add_argument("--skip_excel", action="store_true", help="skip generation of the Excel workbook")
     p.add_argument("--skip_histogram", action="store_true", help="skip histogram plot generation")
     p.add_argument("--dtype", default="f32", choices=["f32", "bf16"], help="compute type of the HIP path")
+    p.add_argument("--density_maps", action="store_true",
+                   help="also write radial / spatial droplet density heat maps and density_per_image.csv")
+    p.add_argument("--nb_layers", type=int, default=10, help="concentric rings of the radial density map")
+    p.add_argument("--density_kernel", type=int, default=21, help="spatial density Gaussian: sigma = density_kernel / 6")
     return p
 
 
@@ -169,6 +204,13 @@ def main(argv=None):
     mask_dir.mkdir(exist_ok=True)
     if overlay_dir:
         overlay_dir.mkdir(exist_ok=True)
+    density = None
+    if args.density_maps:
+        # the limits of the device path (UNETDC_DENSITY_MAX_LAYERS, UNETDC_DENSITY_MAX_RADIUS), checked before any image on
+        # either path: the Gaussian radius int(4 sigma + 0.5), sigma = density_kernel / 6, is at most 128
+        if not 1 <= args.nb_layers <= 255 or not 0 < args.density_kernel or int(4 * args.density_kernel / 6 + 0.5) > 128:
+            raise SystemExit("--nb_layers must be in 1..255 and --density_kernel in 1..192")
+        density = {"nb_layers": args.nb_layers, "kernel": args.density_kernel, "rows": [], "rgbs": [], "out_dir": out_dir}
     model = load_model(args.ckpt_path, args.dtype)
     tensors, meta, per_image_rows, all_props = [], [], [], []
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in {".png", ".jpg", ".jpeg", ".tif", ".tiff"})
@@ -194,18 +236,26 @@ def main(argv=None):
         while ahead:
             img, fut = ahead.popleft()
             refill()
-            t, osize = preprocess(img, args.background_radius, fut.result())
+            if density is None:
+                t, osize = preprocess(img, args.background_radius, fut.result())
+            else:
+                t, osize, rgb = preprocess(img, args.background_radius, fut.result(), keep_rgb=True)
+                density["rgbs"].append(rgb)
             tensors.append(t)
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers)
+                          args.px_per_micron, per_image_rows, all_props, writers, density)
                 tensors, meta = [], []
+                if density is not None:
+                    density["rgbs"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers)
+                      args.px_per_micron, per_image_rows, all_props, writers, density)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
+    if density is not None:
+        pd.DataFrame(density["rows"]).to_csv(out_dir / "density_per_image.csv", index=False)
     summary_df = pd.DataFrame(per_image_rows)
     summary_df.to_csv(out_dir / "summary_per_image.csv", index=False)
     props = [d for d in all_props if not d.empty]

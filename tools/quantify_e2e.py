@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end throughput of the quantify_droplets_batch.py SCRIPT (file decode, preprocessing, network, droplet tables,
-mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG files:  python3 tools/quantify_e2e.py [N] [dtype]"""
+mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG files:
+    python3 tools/quantify_e2e.py [N] [dtype] [--density_maps]
+--density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image)."""
 import os
 import sys
 import tempfile
@@ -14,8 +16,10 @@ import bench
 import quantify_droplets_batch as qdb
 from models.model_2 import UNetDC
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-dtype = sys.argv[2] if len(sys.argv) > 2 else "bf16"
+density = "--density_maps" in sys.argv
+pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+n = int(pos[0]) if len(pos) > 0 else 64
+dtype = pos[1] if len(pos) > 1 else "bf16"
 with tempfile.TemporaryDirectory() as d:
     ind, out = os.path.join(d, "in"), os.path.join(d, "out")
     os.makedirs(ind)
@@ -36,8 +40,9 @@ with tempfile.TemporaryDirectory() as d:
     ck = os.path.join(d, "ck.pth")
     torch.save({k: v.detach().cpu() for k, v in m.state_dict().items()}, ck)
     argv = ["--img_dir", ind, "--ckpt_path", ck, "--out_dir", out, "--dtype", dtype, "--skip_excel", "--skip_histogram"]
+    argv += ["--density_maps"] if density else []
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''})")

@@ -575,4 +575,27 @@ int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int
                                fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
+int64_t unetdc_density_workspace(int h, int w) { return density_workspace_bytes(h, w); }
+
+static_assert(sizeof(unetdc_density_stats) == 1088 && offsetof(unetdc_density_stats, max_ring_distance) == 40 &&
+                  offsetof(unetdc_density_stats, ring_count) == 68,
+              "unetdc_density_stats layout (unet_dc_segmentation_amd/density.py:STATS_DTYPE mirrors it)");
+
+int unetdc_density_maps(const uint8_t* rgb_hwc, const uint8_t* mask, int h, int w, const int32_t* droplet_count,
+                        const int32_t* droplet_area, const int64_t* droplet_sumy, const int64_t* droplet_sumx,
+                        int max_droplets, int nb_layers, double sigma, const double* taps, void* workspace,
+                        int64_t workspace_bytes, unetdc_density_stats* out_stats, uint8_t* out_radial_index,
+                        uint8_t* out_spatial_index, uint8_t* out_blur, uint8_t* out_roi, uint8_t* out_ring,
+                        float* out_radial, float* out_spatial, unetdc_stream_t s) {
+  return launch_density_maps(rgb_hwc, mask, h, w, droplet_count, droplet_area,
+                             reinterpret_cast<const long long*>(droplet_sumy), reinterpret_cast<const long long*>(droplet_sumx),
+                             max_droplets, nb_layers, sigma, taps, workspace, (long)workspace_bytes, out_stats,
+                             out_radial_index, out_spatial_index, out_blur, out_roi, out_ring, out_radial, out_spatial,
+                             (hipStream_t)s);
+}
+
+int unetdc_density_sqrt(const int64_t* x, double* out, int64_t n, unetdc_stream_t s) {
+  return launch_density_sqrt(reinterpret_cast<const long long*>(x), out, (long)n, (hipStream_t)s);
+}
+
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Parameter blocks and host launchers shared between the kernel files and the C-ABI layer.
 #pragma once
 #include "common.h"
+#include "../../include/unetdc_hip.h"
 
 namespace unetdc {
 
@@ -195,6 +196,18 @@ int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int
                         long workspace_bytes, hipStream_t stream);
 int launch_resize_linear_chw(const unsigned char* src, int h, int w, int cn, float* dst, int dh, int dw, const int* xofs,
                              const short* xa, const int* yofs, const short* ya, hipStream_t stream);
+// erosion (is_max false) / dilation of a single-channel plane by the k x k rectangle (morph_kernel, outside pixels ignored)
+int launch_morph_rect(const unsigned char* src, unsigned char* dst, int h, int w, int k, bool is_max, hipStream_t stream);
+
+// density.hip: ROI, radial and spatial droplet density maps (include/unetdc_hip.h, unetdc_density_maps)
+long density_workspace_bytes(int h, int w);
+int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int h, int w, const int* dcount, const int* darea,
+                        const long long* dsumy, const long long* dsumx, int dcap, int nb_layers, double sigma,
+                        const double* taps, void* workspace, long workspace_bytes, unetdc_density_stats* stats,
+                        unsigned char* radial_index, unsigned char* spatial_index, unsigned char* out_blur,
+                        unsigned char* out_roi, unsigned char* out_ring, float* out_radial, float* out_spatial,
+                        hipStream_t stream);
+int launch_density_sqrt(const long long* x, double* out, long n, hipStream_t stream);
 
 long loss_workspace_bytes(int nimg, long hw);
 int launch_loss_fwd(const float* p, const float* t, float* loss_out, float* coef, void* workspace, long workspace_bytes,

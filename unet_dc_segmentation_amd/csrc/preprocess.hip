@@ -292,6 +292,20 @@ int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int
   return check_launch("rolling ball kernels");
 }
 
+int launch_morph_rect(const unsigned char* src, unsigned char* dst, int h, int w, int k, bool is_max, hipStream_t stream) {
+  UNETDC_REQUIRE(src && dst && src != dst && h > 0 && w > 0 && k >= 1 && k <= PP_MAXK, "morph_rect: bad arguments");
+  MorphSpans sp;
+  for (int i = 0; i < k; ++i) {                             // every row of the rectangle spans the whole width
+    sp.j1[i] = 0;
+    sp.j2[i] = (short)k;
+  }
+  const dim3 grid((w + PP_TILE - 1) / PP_TILE, (h + PP_TILE - 1) / PP_TILE, 1);
+  const int lds = (PP_TILE + k) * (PP_TILE + k);
+  if (is_max) hipLaunchKernelGGL(morph_kernel<true>, grid, dim3(PP_THREADS), lds, stream, src, dst, h, w, 1, k, sp);
+  else hipLaunchKernelGGL(morph_kernel<false>, grid, dim3(PP_THREADS), lds, stream, src, dst, h, w, 1, k, sp);
+  return check_launch("morph_kernel (rectangle)");
+}
+
 int launch_resize_linear_chw(const unsigned char* src, int h, int w, int cn, float* dst, int dh, int dw, const int* xofs,
                              const short* xa, const int* yofs, const short* ya, hipStream_t stream) {
   UNETDC_REQUIRE(src && dst && xofs && xa && yofs && ya && h > 0 && w > 0 && dh > 0 && dw > 0 && cn >= 1 && cn <= 4,

@@ -38,12 +38,14 @@ def resize_mask_like_reference(mask, ow, oh):
     return resize_linear_cv2_u8(np.ascontiguousarray(mask, dtype=np.uint8), ow, oh)
 
 
-def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14):
+def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14, keep_sums=False):
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs.  Every launch of the batch (mask,
     union-find, per-label sums, compaction) is enqueued back to back on the current stream into ONE set of output
     planes; the host then waits ONCE: one device->host copy brings the B droplet counts, a second the filled part of the
     per-droplet integers.  Returns a list of (mask uint8 [oh, ow] DEVICE tensor, area int64 [n], centroid_row float64
-    [n], centroid_col float64 [n]) -- droplets in the reference's label order."""
+    [n], centroid_col float64 [n]) -- droplets in the reference's label order.  keep_sums=True returns (that list, the
+    device outputs (count, area, sumy, sumx) or None when an image had more droplets than they hold) for
+    density.density_maps_batch."""
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -85,6 +87,8 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
         a = a_h[i, :n[i]]
         d = np.maximum(a, 1)
         out.append((masks[i], a, s_h[0, i, :n[i]].astype(np.float64) / d, s_h[1, i, :n[i]].astype(np.float64) / d))
+    if keep_sums:
+        return out, ((count, area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
     return out
 
 

@@ -66,12 +66,16 @@ def _upload(img_u8_host, device):
     return torch.from_numpy(np.ascontiguousarray(img_u8_host)).to(device)
 
 
-def preprocess_device(img_u8_host, radius, size, device="cuda"):
+def preprocess_device(img_u8_host, radius, size, device="cuda", return_rgb=False):
     """numpy [H, W, 3] uint8 (a decoded image) -> network input [3, size, size] float32 on the device.
     A structuring element larger than the kernel's LDS tile allows (--background_radius > 128) takes the host operator for
     the rolling ball only (utils.data_loader.rolling_ball_correction_rgb, the same arithmetic); resize, /255 and CHW stay
-    on the device."""
+    on the device.  return_rgb=True returns (input, the uploaded original [H, W, 3] uint8 device tensor) for the density
+    maps (unet_dc_segmentation_amd/density.py), which read the image before the rolling ball."""
     if int(radius) > MAX_ELEMENT:
         from utils.data_loader import rolling_ball_correction_rgb
-        return resize_to_input_device(_upload(rolling_ball_correction_rgb(img_u8_host, int(radius)), device), size)
-    return resize_to_input_device(rolling_ball_device(_upload(img_u8_host, device), radius), size)
+        x = resize_to_input_device(_upload(rolling_ball_correction_rgb(img_u8_host, int(radius)), device), size)
+        return (x, _upload(img_u8_host, device)) if return_rgb else x
+    rgb = _upload(img_u8_host, device)
+    x = resize_to_input_device(rolling_ball_device(rgb, radius), size)
+    return (x, rgb) if return_rgb else x
