@@ -552,12 +552,13 @@ class Carved:
 
 
 def carve(rows, cols, ld, off, dtype, margin, fill="nan", device="cuda"):
-    """Output views (fill='nan') are surrounded by the NaN pattern of NAN_BITS; input views (fill='sentinel') by SENTINEL."""
+    """Output views (fill='nan') are surrounded by the NaN pattern of NAN_BITS; input views (fill='sentinel') by SENTINEL;
+    fill=None leaves the buffer as allocated (the caller writes the view)."""
     assert 0 <= off and off + cols <= ld
     buf = torch.empty((rows + 2 * margin) * ld, dtype=dtype, device=device)
     if fill == "nan":
         buf.view(INT_VIEW[dtype]).fill_(_signed(NAN_BITS[dtype], dtype))
-    else:
+    elif fill == "sentinel":
         buf.fill_(SENTINEL)
     return Carved(buf, rows, cols, ld, off, margin)
 

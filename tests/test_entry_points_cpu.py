@@ -144,6 +144,36 @@ def test_hip_path_fails_loudly_without_library(monkeypatch, tmp_path):
         _lib.load()
 
 
+def test_library_of_another_abi_version_is_refused(monkeypatch, tmp_path):
+    """load() asks unetdc_version() before binding the table: a library of another C ABI (a base build of an older
+    revision under UNETDC_LIB) is refused instead of being called with shifted arguments."""
+    import pytest
+    from unet_dc_segmentation_amd import _lib
+
+    def stub_of_version(v):
+        class Fn:
+            def __call__(self):
+                return v
+
+        class Stub:
+            def __init__(self, path):
+                self.unetdc_version = Fn()
+        return Stub
+
+    so = tmp_path / "libunetdc_hip_base.so"
+    so.write_bytes(b"")
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "LIB_PATH", str(so))
+    monkeypatch.setattr(_lib.ctypes, "CDLL", stub_of_version(1))
+    with pytest.raises(_lib.UnetdcError, match="ABI v1, this package binds v2"):
+        _lib.load()
+    assert _lib._lib is None
+    # the expected version passes the check and goes on to bind the table (which the stub does not have)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", stub_of_version(_lib.EXPECTED_ABI))
+    with pytest.raises(AttributeError, match="unetdc_last_error"):
+        _lib.load()
+
+
 def test_calculate_metrics_matches_sklearn():
     """Five return values like the reference (utils/metrics_DC.py:75-85, which calls sklearn): checked against
     sklearn itself, including the all-negative corner (zero_division=1)."""

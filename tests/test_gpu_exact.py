@@ -10,7 +10,7 @@ one training step of UNetDC(1, 1) per configuration is recorded, and every disti
 optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must reach the same kernel.  The
 BatchNorm, head and loss calls of the step are replayed through the runners of tests/test_gpu_exact_norm.py."""
 import ctypes
-import os
+import re
 
 import pytest
 import torch
@@ -31,9 +31,6 @@ else:
 TD = {0: torch.float32, 1: torch.bfloat16}
 MARGIN = 3                      # guard rows before and after every view
 SUM_TOL = 4e-6                  # fp32 statistics / column / BatchNorm-backward sums: |err| <= SUM_TOL * sum|terms| (~64 ulp)
-THIN = os.environ.get("UNETDC_TEST_THIN") == "1"
-SWITCHED = any(k in os.environ for k in ("UNETDC_IGEMM", "UNETDC_WGRAD", "UNETDC_FIRST", "UNETDC_LATTICE", "UNETDC_WGRAD_RING",
-                                         "UNETDC_WGRAD_SPLIT", "UNETDC_WGRAD_RECT", "UNETDC_FIRST_ROWS", "UNETDC_FUSE_BNBWD"))
 KERNELS = set()                 # unetdc_last_kernel() of every route-case call (coverage test at the end)
 
 
@@ -67,9 +64,11 @@ def big(shape, r, g, lo=None):
 
 
 def put(data, ld, dt, off=None):
-    """Input view holding `data` ([rows, cols]) at column ld - cols of a sentinel-filled buffer."""
+    """Input view holding `data` ([rows, cols]) at column ld - cols of a sentinel-filled buffer (of a buffer of >= 2 GiB only
+    the view is written)."""
     rows, cols = data.shape
-    c = X.carve(rows, cols, ld, ld - cols if off is None else off, dt, MARGIN, fill="sentinel")
+    huge = (rows + 2 * MARGIN) * ld * dt.itemsize >= 1 << 31
+    c = X.carve(rows, cols, ld, ld - cols if off is None else off, dt, MARGIN, fill=None if huge else "sentinel")
     c.view.copy_(data.cuda().to(dt))
     return c
 
@@ -222,7 +221,7 @@ def conv_dgrad(kw, fix, variant, seed=3):
         extra = bnstats_call("unetdc_conv3x3_dgrad_bnstats", args, tail, P, ci, dt, g, kw)
     name = last_kernel()
     expect_equal(dxc, exp, dt, f"conv3x3_dgrad/{variant}[{name}]", (n, h, w, ci), None)
-    check_extra(extra, dxc, f"conv3x3_dgrad/{variant}[{name}]")
+    check_extra(extra, dxc, f"conv3x3_dgrad/{variant}[{name}]", name)
     return name
 
 
@@ -241,7 +240,7 @@ def bnstats_call(sym, args, tail, P, ci, dt, g, kw):
     return ("bnstats", parts, yp, (sc, sh, mu, rs), npart, rows, dv)
 
 
-def check_extra(extra, dxc, what):
+def check_extra(extra, dxc, what, kernel):
     if extra is None:
         return
     torch.cuda.synchronize()
@@ -265,10 +264,10 @@ def check_extra(extra, dxc, what):
     xh = (y - mu) * rs
     expect_sums(pc[0], gh, what + " S1")
     expect_sums(pc[1], gh * xh, what + " S2")
-    if not SWITCHED:                             # the fused epilogues leave the third row zero (include/unetdc_hip.h)
-        assert bool((rows_[:, 2] == 0).all()), f"{what}: third parts row is not zero"
-    elif not bool((rows_[:, 2] == 0).all()):     # the stand-alone reduction behind the first-generation kernels sums xhat
+    if kernel.startswith("igemm_conv_kernel<"):   # the stand-alone reduction behind the first-generation kernel sums xhat
         expect_sums(pc[2], xh, what + " S3")
+    else:                                         # the fused epilogues leave the third row zero (include/unetdc_hip.h)
+        assert bool((rows_[:, 2] == 0).all()), f"{what}: third parts row is not zero"
 
 
 def conv_wgrad(kw, fix, bnin=False, seed=4):
@@ -445,7 +444,7 @@ def convt_dgrad(kw, fix, bnstats=False, seed=9):
         call("unetdc_convT2x2_dgrad", *args, *tail)
     name = last_kernel()
     expect_equal(dxc, exp, dt, f"convT2x2_dgrad{'_bnstats' if bnstats else ''}[{name}]", (n, h, w, ci))
-    check_extra(extra, dxc, f"convT2x2_dgrad_bnstats[{name}]")
+    check_extra(extra, dxc, f"convT2x2_dgrad_bnstats[{name}]", name)
     return name
 
 
@@ -518,7 +517,9 @@ def pack_convt(wt, dt):
 # ---------------------------------------------------------------------------------------------------- route cases
 FIXTURES = ["dense", "onehot"]
 DTYPES = {"f32": 0, "bf16": 1}
-ROUTE_CASES = list(CONV_CASES)
+ROUTE_CASES = list(CONV_CASES) + [
+    (1, 9, 13, 64, 64, 1),       # M = 117, not a multiple of 16: bf16 on the 32x32x16 DMA kernel (igemm_dma.hip)
+    (1, 264, 512, 64, 64, 2)]    # bf16, d = 2, H / d = 132 not a multiple of the lattice tile: the 16x16x32 halo kernel
 WGRAD_CASES = [(2, 512, 256, 64, 64, 1), (1, 520, 512, 128, 64, 1), (4, 256, 256, 64, 128, 2), (2, 128, 128, 256, 128, 8),
                (8, 64, 64, 128, 256, 4), (5, 64, 64, 1024, 512, 1),                      # tap-fused (wgrad_fused.hip)
                (2, 32, 32, 256, 256, 16), (1, 16, 24, 256, 512, 8), (3, 24, 40, 512, 256, 16),    # valid rectangles (bf16)
@@ -529,8 +530,6 @@ CONVT_CASES = [(2, 8, 12, 128, 64), (1, 16, 16, 256, 128), (1, 4, 4, 1024, 512),
                (2, 16, 96, 512, 256), (1, 4, 32, 128, 64), (3, 8, 32, 128, 64)]
 FIRST_CASES = [(2, 24, 40, 1), (2, 64, 64, 2), (3, 10, 10, 1), (1, 8, 8, 1), (2, 96, 136, 1)]
 FIRST_BN_CASES = [(2, 16, 24), (1, 64, 64), (3, 40, 96)]
-if THIN:                        # (CONV_CASES arrives thinned from tests/test_gpu_ops.py already)
-    WGRAD_CASES, CONVT_CASES = WGRAD_CASES[::3], CONVT_CASES[::2]
 ROUTE_RUN = []                  # route-case items run in this session (test_route_coverage needs all of them)
 
 
@@ -577,8 +576,7 @@ def test_exact_normalise_on_load(case, fix):
     """conv3x3_fwd_bnin with and without act_out, conv3x3_wgrad_bnin (bf16)."""
     ROUTE_RUN.append(1)
     kw = kwargs(case, "bf16")
-    if os.environ.get("UNETDC_LATTICE") == "0" or lib().unetdc_conv3x3_bnin_supported(*case, 1) == 0:
-        pytest.skip("no normalise-on-load form under this switch set")
+    assert lib().unetdc_conv3x3_bnin_supported(*case, 1) > 0, case
     KERNELS.add(conv_fwd_bnin(kw, fix))
     if case[4] % 128 == 0:
         KERNELS.add(conv_fwd_bnin(dict(kw, **{"ptr:act_out": True}), fix))
@@ -619,8 +617,6 @@ def test_exact_first_layer_wgrad_bn_on_load(case, dtype, fix):
     """unetdc_conv3x3_first_wgrad_bn: one input channel, dilation 1 (the production first-layer weight gradient)."""
     ROUTE_RUN.append(1)
     n, h, w = case
-    if SWITCHED and lib().unetdc_conv3x3_first_wgrad_bn_supported(n, h, w, 1, 64, 1, DTYPES[dtype]) == 0:
-        pytest.skip("no on-load form under this switch set (the row-run kernel is off)")
     KERNELS.add(first_wgrad_bn(dict(n=n, h=h, w=w, cin=1, cout=64, dilation=1, dtype=DTYPES[dtype]), fix))
 
 
@@ -632,24 +628,76 @@ def test_exact_bn_relu_apply(case, pool, dtype):
     bn_relu_apply(dict(n=n, h=h, w=w, c=c, dtype=DTYPES[dtype], **{"ptr:pooled": pool}), "dense")
 
 
-FAMILIES = ["igemm_lattice_wide_kernel<1>", "igemm_lattice_wide_kernel<2>", "igemm_lattice_wide_kernel<4>",
-            "igemm_lattice_wide_kernel<1> bnin", "igemm_lattice_kernel<", "blocks16x16", "igemm_halo", "igemm_dma_kernel",
-            "wgrad_ring", "wgrad_fused", "wgrad_rect_kernel", "convt_wgrad_kernel", "first_mfma_fwd_kernel", "first_mfma_wgrad_kernel",
-            "first_wgrad_rows_kernel", "first_conv_fwd_kernel", "first_dgrad_kernel", "first_wgrad_rows_kernel<__bf16> bn",
-            "first_wgrad_rows_kernel<float> bn"]
+# >= 2 GiB operands: the input is a channel slice of a buffer of 2^31 bytes (64 x 64 pixels, leading dimension HUGE_LD), more
+# than the buffer descriptors of the DMA / lattice / halo kernels take, so every call below reaches a first-generation kernel
+# (64-bit addressing; at bs 8 x 1024^2 bf16 the decoder's dec1.0 forward and weight gradient do).  Only the slice is filled.
+HUGE_LD = {"f32": 131072, "bf16": 262144}
+
+
+def huge(**kw):
+    return dict(dict(n=1, h=64, w=64, cin=64, cout=64, dilation=1), **kw)
+
+
+HUGE_CASES = {   # case -> (runner, kw, the leading dimension that is huge, kernel; {T}: __bf16 / float)
+    "fwd_store_64": (lambda kw: conv_fwd(kw, "dense"), huge(**{"ptr:stats_part": False}), "ldx", "igemm_conv_kernel<{T}, 4, 1>"),
+    "fwd_store_128": (lambda kw: conv_fwd(kw, "dense"), huge(cout=128, **{"ptr:stats_part": False}), "ldx",
+                      "igemm_conv_kernel<{T}, 2, 2>"),
+    "fwd_stats_64": (lambda kw: conv_fwd(kw, "dense"), huge(), "ldx", "igemm_conv_kernel<{T}, 4, 1>"),
+    "fwd_stats_128": (lambda kw: conv_fwd(kw, "dense"), huge(cout=128), "ldx", "igemm_conv_kernel<{T}, 4, 1>"),  # BM = 256 rows
+    "fwd_affine_64": (lambda kw: conv_fwd(kw, "dense"), huge(**{"ptr:scale": True}), "ldx", "igemm_conv_kernel<{T}, 4, 1>"),
+    "fwd_affine_128": (lambda kw: conv_fwd(kw, "dense"), huge(cout=128, **{"ptr:scale": True}), "ldx",
+                       "igemm_conv_kernel<{T}, 2, 2>"),
+    "dgrad": (lambda kw: conv_dgrad(kw, "dense", "plain"), huge(), "lddy", "igemm_conv_kernel<{T}, 4, 1>"),
+    "dgrad_colsum": (lambda kw: conv_dgrad(kw, "dense", "colsum"), huge(), "lddy", "igemm_conv_kernel<{T}, 4, 1>"),
+    # the first-generation kernel has no BatchNorm-backward epilogue: plain dgrad, then the stand-alone reduction (abi.hip)
+    "dgrad_bnstats": (lambda kw: conv_dgrad(kw, "dense", "bnstats"), huge(), "lddy", "igemm_conv_kernel<{T}, 4, 1>"),
+    "wgrad_64": (lambda kw: conv_wgrad(kw, "dense"), huge(), "ldx", "wgrad_kernel<{T}, 1>"),
+    "wgrad_128": (lambda kw: conv_wgrad(kw, "dense"), huge(cin=128, cout=128), "ldx", "wgrad_kernel<{T}, 2>"),
+    "convT_fwd": (lambda kw: convt_fwd(kw, "dense"), huge(), "ldx", "igemm_conv_kernel<{T}, 2, 2>"),
+    "convT_dgrad": (lambda kw: convt_dgrad(kw, "dense"), huge(h=32, w=32), "lddup", "igemm_conv_kernel<{T}, 4, 1>"),
+    "convT_dgrad_bnstats": (lambda kw: convt_dgrad(kw, "dense", bnstats=True), huge(h=32, w=32), "lddup",
+                            "igemm_conv_kernel<{T}, 4, 1>"),
+}
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case", list(HUGE_CASES))
+def test_exact_first_generation_routes_at_2gib(case, dtype):
+    ROUTE_RUN.append(1)
+    run, kw, ld, kernel = HUGE_CASES[case]
+    try:
+        name = run(dict(kw, dtype=DTYPES[dtype], **{ld: HUGE_LD[dtype]}))
+    finally:
+        torch.cuda.empty_cache()
+    assert name == kernel.format(T="__bf16" if dtype == "bf16" else "float"), (case, dtype, name)
+    KERNELS.add(name)
+
+
+# every kernel family the library contains (regular expressions over unetdc_last_kernel(); per dtype where both exist)
+FAMILIES = [r"igemm_lattice_wide_kernel<1>$", r"igemm_lattice_wide_kernel<2>", r"igemm_lattice_wide_kernel<4>",
+            r"igemm_lattice_wide_kernel<1> bnin", r"igemm_lattice_kernel<", r"igemm_dma16_kernel<.*blocks16x16",
+            r"igemm_dma16_kernel<[^>]*>( ring3)?$", r"igemm_halo16_kernel<", r"igemm_halo_kernel<float",
+            r"igemm_dma_kernel<__bf16", r"igemm_dma_kernel<float", r"igemm_conv_kernel<__bf16", r"igemm_conv_kernel<float",
+            r"wgrad_kernel<__bf16", r"wgrad_kernel<float", r"wgrad_dma_kernel<__bf16", r"wgrad_dma_kernel<float",
+            r"wgrad_ring_split_kernel<\d, 16x16x32>$", r"wgrad_ring_split_kernel<\d, 16x16x32> paired$",
+            r"wgrad_ring_split_kernel<\d, 16x16x32>( paired)? bnin", r"wgrad_fused_split_kernel<16x16x32>$",
+            r"wgrad_fused_split_kernel<16x16x32> paired", r"wgrad_ring_kernel<float", r"wgrad_fused_kernel<float",
+            r"wgrad_rect_kernel", r"convt_wgrad_kernel", r"first_mfma_fwd_kernel<__bf16", r"first_mfma_fwd_kernel<float",
+            r"first_mfma_wgrad_kernel<__bf16", r"first_mfma_wgrad_kernel<float", r"first_wgrad_rows_kernel<__bf16>$",
+            r"first_wgrad_rows_kernel<float>$", r"first_wgrad_rows_kernel<__bf16> bn", r"first_wgrad_rows_kernel<float> bn",
+            r"first_conv_wgrad_kernel<__bf16", r"first_conv_wgrad_kernel<float", r"first_conv_fwd_kernel<__bf16",
+            r"first_conv_fwd_kernel<float", r"first_dgrad_kernel<__bf16", r"first_dgrad_kernel<float"]
 ROUTE_ITEMS = lambda: 4 * (len(ROUTE_CASES) + len(WGRAD_CASES) + len(CONVT_CASES) + len(FIRST_BN_CASES)) \
-    + 2 * len(BNIN_CASES) + 8 * len(FIRST_CASES)    # noqa: E731
+    + 2 * len(BNIN_CASES) + 8 * len(FIRST_CASES) + 2 * len(HUGE_CASES)    # noqa: E731
 
 
 def test_route_coverage():
     """The route cases above reached every kernel family the default build dispatches to."""
-    if SWITCHED or THIN:
-        pytest.skip("coverage is asserted for the default routes over the full case list")
     if len(ROUTE_RUN) != ROUTE_ITEMS():           # it reads the kernels those items reached: a subset proves nothing
         pytest.skip(f"needs every route-case item in this session before it ({len(ROUTE_RUN)} of {ROUTE_ITEMS()} ran)")
     names = sorted(k for k in KERNELS if k)
     print("\n".join(["kernels reached:"] + names))
-    missing = [f for f in FAMILIES if not any(f in k for k in names)]
+    missing = [f for f in FAMILIES if not any(re.search(f, k) for k in names)]
     assert not missing, (missing, names)
     for mode in (0, 1, 2, 4):                     # the narrow lattice kernel in every epilogue mode (4: BatchNorm-backward sums)
         assert any(k.startswith("igemm_lattice_kernel<") and f", {mode}>" in k for k in names), (mode, names)
@@ -751,7 +799,6 @@ def distinct_calls(recs):
     return out
 
 
-@pytest.mark.skipif(THIN or SWITCHED, reason="the replay runs on the default routes only")
 @pytest.mark.parametrize("config", list(REPLAY_CONFIGS))
 def test_production_step_replay(config):
     """Every distinct call of one training step (or eval forward, or frozen-statistics step), replayed with exact fixtures

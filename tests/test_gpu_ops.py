@@ -6,7 +6,6 @@ bf16 path -- inputs are pre-rounded to bf16 so both sides see identical operands
 left is fp32-accumulate order + one bf16 rounding of the output (2^-9): rel-L2 <= 6e-3.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -58,13 +57,6 @@ CONV_CASES = [  # n, h, w, cin, cout, d
     (1, 64, 64, 64, 128, 32),    # d = 32 on a 64 x 64 map: a tap moves a block by two blocks
 ]
 
-if os.environ.get("UNETDC_TEST_THIN") == "1":
-    # re-runs under the A/B switch sets (tests/test_gpu_fallbacks.py, child processes): the fallback kernels take every shape
-    # the same way, so the small shapes plus one large shape per routing rule are enough (the CPU reference convolutions of the
-    # large shapes were most of those re-runs' time)
-    CONV_CASES = [c for i, c in enumerate(CONV_CASES) if i < 8 or i in (8, 10, 12, 17)]
-
-
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv3x3_fwd_dgrad_wgrad(dtype, case):
@@ -92,8 +84,7 @@ def test_conv3x3_fwd_dgrad_wgrad(dtype, case):
     np.testing.assert_allclose(stc[1].numpy(), (yq * yq).sum(dim=(0, 2, 3)).numpy(), rtol=1e-4, atol=1e-2)
     # rows that carry data (the persistent kernel writes one row per workgroup and zeros into the rest of the bound)
     live = G.LIVE_ROWS.value
-    default_route = not any(k in os.environ for k in ("UNETDC_IGEMM", "UNETDC_QUAD"))   # (test_gpu_fallbacks.py re-runs this file under switches)
-    if default_route and dtype == "bf16" and d % 16 == 0 and h % 16 == 0 and w % 16 == 0:
+    if dtype == "bf16" and d % 16 == 0 and h % 16 == 0 and w % 16 == 0:
         assert _lib.load().unetdc_last_kernel().decode().endswith("blocks16x16")        # routed to the block-order form
     assert 1 <= live <= rows
     sta = st.cpu()[: rows * 2 * cout].reshape(rows, 2, cout)

@@ -106,5 +106,4 @@ e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
 fl = 2.0 * n * h * w * cin * cout * (4 if is_t else 9)
-print(f"{op} {n}x{h}x{w} {cin}->{cout} d={d} {dtype}: {ms * 1e3:.1f} us  {fl / ms / 1e9:.1f} TFLOP/s "
-      f"(UNETDC_IGEMM={os.environ.get('UNETDC_IGEMM', '')})")
+print(f"{op} {n}x{h}x{w} {cin}->{cout} d={d} {dtype}: {ms * 1e3:.1f} us  {fl / ms / 1e9:.1f} TFLOP/s")

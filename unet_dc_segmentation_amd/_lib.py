@@ -19,6 +19,10 @@ LIB_PATH = os.environ.get("UNETDC_LIB") or os.path.join(os.path.dirname(os.path.
 
 P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
 
+# UNETDC_ABI_VERSION of include/unetdc_hip.h that SIGNATURES describes.  load() refuses a library reporting another version
+# (e.g. a UNETDC_LIB base build of an older revision), which would otherwise be called with shifted arguments.
+EXPECTED_ABI = 2
+
 # name -> (restype, argtypes); mirrors include/unetdc_hip.h one to one
 SIGNATURES = {
     "unetdc_version": (I, []),
@@ -103,6 +107,12 @@ def load():
             "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU/PyTorch "
             "fallback for tensors on a HIP device.")
     lib = ctypes.CDLL(LIB_PATH)
+    lib.unetdc_version.restype = c_int
+    lib.unetdc_version.argtypes = []
+    version = lib.unetdc_version()
+    if version != EXPECTED_ABI:
+        raise UnetdcError(f"{LIB_PATH} implements C ABI v{version}, this package binds v{EXPECTED_ABI}: rebuild it from "
+                          "the sources of this revision")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.restype = res

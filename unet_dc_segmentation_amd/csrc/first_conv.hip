@@ -339,10 +339,8 @@ static long first_rows_blocks(long P, int Cout) {          // row-run kernel: on
 // One input channel only: the row-run kernel makes one pass over dY PER input channel, and with the BatchNorm backward on load
 // every pass would also re-read y.
 bool first_wgrad_bn_supported(int N, int H, int W, int Cin, int Cout, int dil, int dtype) {
-  static int off = -1;                                   // UNETDC_FIRST_ROWS=0 also turns this form off (it is the row-run kernel)
-  if (off < 0) { const char* e = getenv("UNETDC_FIRST_ROWS"); off = (e && e[0] == '0') ? 1 : 0; }
   (void)N; (void)H;
-  return !off && (dtype == UNETDC_F32 || dtype == UNETDC_BF16) && Cin == 1 && dil == 1 && W % 8 == 0 && Cout % 8 == 0 &&
+  return (dtype == UNETDC_F32 || dtype == UNETDC_BF16) && Cin == 1 && dil == 1 && W % 8 == 0 && Cout % 8 == 0 &&
          Cout / 8 <= 16 && 64 % (Cout / 8) == 0;
 }
 
@@ -485,9 +483,7 @@ int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long wor
     return check_launch("first_wgrad_reduce_kernel");
   }
   const size_t lds = (size_t)4 * (p.Cout / 8) * 72 * 4;
-  static int rows_off = -1;                              // UNETDC_FIRST_ROWS=0: the per-pixel kernel (A/B)
-  if (rows_off < 0) { const char* e = getenv("UNETDC_FIRST_ROWS"); rows_off = (e && e[0] == '0') ? 1 : 0; }
-  if (!rows_off && p.dil == 1 && p.W % 8 == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0) {
+  if (p.dil == 1 && p.W % 8 == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0) {
     const long nr = first_rows_blocks(P, p.Cout);
     if (nr * p.Cin * 9 * p.Cout * 4 <= workspace_bytes) {
       if (dtype == UNETDC_BF16)

@@ -114,9 +114,7 @@ __global__ __launch_bounds__(256) void first_mfma_fwd_kernel(const IgemmParams p
 }
 
 bool first_mfma_supported(long P, int Cin, int Cout) {
-  static int off = -1;                                   // UNETDC_FIRST=valu: the VALU kernels of first_conv.hip (A/B)
-  if (off < 0) { const char* e = getenv("UNETDC_FIRST"); off = (e && e[0] == 'v') ? 1 : 0; }
-  return !off && Cout == 64 && (Cin == 1 || Cin == 3) && P % 32 == 0 && P < (1L << 23);
+  return Cout == 64 && (Cin == 1 || Cin == 3) && P % 32 == 0 && P < (1L << 23);
 }
 int first_mfma_mblocks(long P) { return ceil_div(P, FM_BM); }
 

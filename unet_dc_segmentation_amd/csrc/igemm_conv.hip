@@ -283,18 +283,6 @@ int launch_igemm_halo(IgemmParams& p, int dtype, hipStream_t stream);
 // number of partial-statistics rows is a function of the pixel count only.
 int igemm_mblocks(long M, int Cout) { (void)Cout; return ceil_div(M, 256); }
 
-// UNETDC_IGEMM=legacy: first-generation register-staged kernel; =dma: per-tap LDS-DMA kernel only
-// (no halo-patch kernel).  Default: best kernel per layer.  For A/B measurements in one binary.
-static int igemm_choice() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("UNETDC_IGEMM");
-    v = (e && e[0] == 'l') ? 1 : ((e && e[0] == 'd') ? 2 : 0);
-  }
-  return v;
-}
-static bool use_legacy() { return igemm_choice() == 1; }
-
 template <typename T, int WM, int WN>
 static int launch_cfg(IgemmParams& p, hipStream_t stream) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -335,17 +323,17 @@ int launch_igemm(IgemmParams& p, int dtype, hipStream_t stream) {
     p.howo_shift = p2 ? __builtin_ctzl((unsigned long)howo) : -1;
   }
   if (p.in_scale) {
-    // input normalisation on load exists in the lattice kernel ONLY: no A/B switch may route this call to a kernel that would
-    // read the raw tensor as if it were the activation
+    // input normalisation on load exists in the lattice kernel ONLY: no other kernel may take this call, it would read the
+    // raw tensor as if it were the activation
     if (!igemm_lattice_bnin_supported(p, dtype)) {
       set_error("igemm: input normalisation asked for a shape / configuration the lattice kernel does not take");
       return UNETDC_EUNSUPPORTED;
     }
     return launch_igemm_lattice(p, stream);
   }
-  if (igemm_choice() == 0 && igemm_lattice_supported(p, dtype)) return launch_igemm_lattice(p, stream);
-  if (igemm_choice() == 0 && igemm_halo_supported(p, dtype)) return launch_igemm_halo(p, dtype, stream);
-  if (!use_legacy() && igemm_dma_supported(p, dtype)) return launch_igemm_dma(p, dtype, stream);
+  if (igemm_lattice_supported(p, dtype)) return launch_igemm_lattice(p, stream);
+  if (igemm_halo_supported(p, dtype)) return launch_igemm_halo(p, dtype, stream);
+  if (igemm_dma_supported(p, dtype)) return launch_igemm_dma(p, dtype, stream);
   if (p.mode == MODE_BNBWD) return UNETDC_EUNSUPPORTED;      // first-generation kernel: caller reduces separately
   const bool wide = (p.Cout % 128 == 0) && p.mode != MODE_STATS;     // statistics rows assume BM = 256
   if (dtype == UNETDC_BF16)

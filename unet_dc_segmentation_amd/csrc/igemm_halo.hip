@@ -24,37 +24,29 @@
 
 namespace unetdc {
 
-template <typename T> struct MmaH;
-template <> struct MmaH<bf16_t> {
-  __device__ static __forceinline__ void run(f32x16& acc, const u32x4& a, const u32x4& b) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                  acc, 0, 0, 0);
-  }
-};
-template <> struct MmaH<float> {
-  __device__ static __forceinline__ void run(f32x16& acc, const u32x4& a, const u32x4& b) {
+// one 16-byte fragment pair: four fp32 32x32x2 MFMAs
+__device__ static __forceinline__ void mma_halo_f32(f32x16& acc, const u32x4& a, const u32x4& b) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const unsigned int ua = a[s], ub = b[s];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bits_f32(ua), bits_f32(ub), acc, 0, 0, 0);
-    }
+  for (int s = 0; s < 4; ++s) {
+    const unsigned int ua = a[s], ub = b[s];
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bits_f32(ua), bits_f32(ub), acc, 0, 0, 0);
   }
-};
+}
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 constexpr unsigned HOOB = 0x80000000u;
 constexpr int TH = 8, TW = 32;                  // output tile in pixels
 constexpr int MAXPJ = 14;                       // patch DMA instructions per wave (d <= 2, 4 waves: 54/4)
 
+// fp32 (bf16 runs igemm_halo16_kernel below).
 // WN = 1: 4 waves (4 x 1), BN = 64;   WN = 2: 8 waves (4 x 2), BN = 128.  Wave tile 64 x 64.
-template <typename T, int WN>
+template <int WN>
 __global__ __launch_bounds__(512, 2) void igemm_halo_kernel(const IgemmParams p, int d, int npatch_bufs, int rcp_pw) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int NW = 4 * WN;
   constexpr int BN = 64 * WN;
   constexpr int BI = BN / 8 / NW;               // weight DMA instructions per wave per tap (= 2)
-  constexpr int ES = (int)sizeof(T);
-  constexpr int KE = 128 / ES;
+  constexpr int ES = 4, KE = 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -178,7 +170,7 @@ __global__ __launch_bounds__(512, 2) void igemm_halo_kernel(const IgemmParams p,
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) MmaH<T>::run(acc[i][j], a[i], b[j]);
+        for (int j = 0; j < 2; ++j) mma_halo_f32(acc[i][j], a[i], b[j]);
     }
     if (npatch_bufs == 1 && tap == 8 && kc + 1 < nkc) {
       __syncthreads();                                   // everyone is done with the single patch buffer
@@ -200,10 +192,10 @@ __global__ __launch_bounds__(512, 2) void igemm_halo_kernel(const IgemmParams p,
   }
   float st[4] = {0.f, 0.f, 0.f, 0.f};
   switch (p.mode) {
-    case MODE_STATS: epilogue_tiles<T, MODE_STATS, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
-    case MODE_AFFINE_RELU: epilogue_tiles<T, MODE_AFFINE_RELU, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
-    case MODE_BNBWD: epilogue_tiles<T, MODE_BNBWD, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
-    default: epilogue_tiles<T, MODE_STORE, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
+    case MODE_STATS: epilogue_tiles<float, MODE_STATS, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
+    case MODE_AFFINE_RELU: epilogue_tiles<float, MODE_AFFINE_RELU, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
+    case MODE_BNBWD: epilogue_tiles<float, MODE_BNBWD, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
+    default: epilogue_tiles<float, MODE_STORE, 2>(p, acc, tile_ok, voff, ldob, yoff, ldyb, col, st); break;
   }
   if (p.mode == MODE_STATS || p.mode == MODE_BNBWD) write_stat_rows<4, WN>(p, smem, st, mtile, n0, tid, wave, r, h);
 #endif  // __HIP_DEVICE_COMPILE__
@@ -386,25 +378,22 @@ bool igemm_halo_supported(const IgemmParams& p, int dtype) {
   return xbytes < (1L << 31) && obytes < (1L << 32) && ybytes < (1L << 32);
 }
 
-static bool halo_mfma16() { return true; }            // bf16: the 16x16x32 form (the A/B against 32x32x16 was settled in round 1)
-
-template <typename T, int WN>
-static int launch_halo_cfg(IgemmParams& p, int d, hipStream_t stream) {
+template <int WN>
+static int launch_halo_cfg(IgemmParams& p, int dtype, int d, hipStream_t stream) {
   const int PP = (TH + 2 * d) * (TW + 2 * d);
   const int patch = ((PP + 7) / 8) * 1024;
-  const int es = (int)sizeof(T);
+  const int es = dtype == UNETDC_BF16 ? 2 : 4;
   const int nkc = p.Cin / (128 / es);
   // single patch buffer for the 4-wave config (2 workgroups per CU hide the reload); the 8-wave
   // config is alone on its CU, so it double-buffers the patch when there is more than one chunk
   const int nbuf = (WN == 2 && nkc > 1) ? 2 : 1;
   const int lds = nbuf * patch + 2 * (64 * WN) * 128;
-  if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&igemm_halo_kernel<T, WN>), 160 * 1024, "igemm_halo_kernel")) return rc_;
   p.mblocks = (int)((long)p.M / 256);
   p.nblocks = p.Cout / (64 * WN);
   const long nwg = (long)p.mblocks * p.nblocks;
   const int rcp_pw = (65536 + (TW + 2 * d) - 1) / (TW + 2 * d);     // pr / PW == (pr * rcp_pw) >> 16 for pr < 1024 (PW <= 36)
   char nm[96];
-  if (sizeof(T) == 2 && halo_mfma16()) {
+  if (dtype == UNETDC_BF16) {
     if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&igemm_halo16_kernel<WN>), 160 * 1024, "igemm_halo16_kernel"))
       return rc_;
     hipLaunchKernelGGL((igemm_halo16_kernel<WN>), dim3((unsigned)nwg), dim3(256 * WN), lds, stream, p, d, nbuf, rcp_pw);
@@ -412,17 +401,16 @@ static int launch_halo_cfg(IgemmParams& p, int d, hipStream_t stream) {
     note_kernel(nm);
     return check_launch("igemm_halo16_kernel");
   }
-  hipLaunchKernelGGL((igemm_halo_kernel<T, WN>), dim3((unsigned)nwg), dim3(256 * WN), lds, stream, p, d, nbuf, rcp_pw);
-  snprintf(nm, sizeof(nm), "igemm_halo_kernel<%s, %d>", sizeof(T) == 2 ? "__bf16" : "float", WN);
+  if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&igemm_halo_kernel<WN>), 160 * 1024, "igemm_halo_kernel")) return rc_;
+  hipLaunchKernelGGL((igemm_halo_kernel<WN>), dim3((unsigned)nwg), dim3(256 * WN), lds, stream, p, d, nbuf, rcp_pw);
+  snprintf(nm, sizeof(nm), "igemm_halo_kernel<float, %d>", WN);
   note_kernel(nm);
   return check_launch("igemm_halo_kernel");
 }
 
 int launch_igemm_halo(IgemmParams& p, int dtype, hipStream_t stream) {
   const int d = p.offy[8];
-  if (p.Cout % 128 == 0)
-    return dtype == UNETDC_BF16 ? launch_halo_cfg<bf16_t, 2>(p, d, stream) : launch_halo_cfg<float, 2>(p, d, stream);
-  return dtype == UNETDC_BF16 ? launch_halo_cfg<bf16_t, 1>(p, d, stream) : launch_halo_cfg<float, 1>(p, d, stream);
+  return p.Cout % 128 == 0 ? launch_halo_cfg<2>(p, dtype, d, stream) : launch_halo_cfg<1>(p, dtype, d, stream);
 }
 
 }  // namespace unetdc

@@ -923,14 +923,8 @@ __global__ __launch_bounds__(256, 2) void igemm_lattice_wide_kernel(const IgemmP
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-static int lattice_enabled() {
-  static int v = -1;                              // UNETDC_LATTICE=0: round-1 kernels (A/B measurements)
-  if (v < 0) { const char* e = getenv("UNETDC_LATTICE"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
-
 bool igemm_lattice_supported(const IgemmParams& p, int dtype) {
-  if (!lattice_enabled() || dtype != UNETDC_BF16) return false;
+  if (dtype != UNETDC_BF16) return false;
   if (p.ntaps != 9 || p.stride != 1 || p.mode == MODE_SHUFFLE) return false;
   if (p.Ho != p.Hi || p.Wo != p.Wi) return false;
   const int d = p.offy[8];

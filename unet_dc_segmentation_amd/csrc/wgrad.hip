@@ -243,18 +243,6 @@ bool wgrad_rect_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb,
 int launch_wgrad_rect(const void* dy, int lddy, const void* x, int ldx, float* out, void* workspace, long workspace_bytes,
                       int N, int H, int W, int CI, int CJ, int d, hipStream_t stream);
 
-// UNETDC_WGRAD=legacy: first-generation register-staged kernel; =dma: per-tap LDS-DMA kernels only
-// (no tap-fused kernel).  Default: best kernel per layer.
-static int wgrad_choice() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("UNETDC_WGRAD");
-    v = (e && e[0] == 'l') ? 1 : ((e && e[0] == 'd') ? 2 : 0);
-  }
-  return v;
-}
-static bool wgrad_legacy() { return wgrad_choice() == 1; }
-
 static int pixel_step(int dtype, bool wide) {
   const int rb = (wide ? 2 : 1) * 64 * (dtype == UNETDC_BF16 ? 2 : 4);
   return 16384 / rb;
@@ -331,7 +319,7 @@ int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_byt
                        wgrad_bnin_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], dtype),
                    "wgrad (bnin): shape not supported by the input-normalising kernel");
   }
-  if (!p.in_scale && wgrad_choice() == 0 && p.ntaps == 4 && p.stride == 2 && p.Hb == 2 * p.H && p.Wb == 2 * p.W &&
+  if (!p.in_scale && p.ntaps == 4 && p.stride == 2 && p.Hb == 2 * p.H && p.Wb == 2 * p.W &&
       p.offy[3] == 1 && p.offx[3] == 1 && convt_wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, dtype)) {
     // ConvTranspose2d(2, 2): one GEMM [Cin] x [4 Cout] with the input staged once for the four taps (convt_wgrad.hip)
     const long need_c = convt_wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ);
@@ -348,11 +336,11 @@ int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_byt
                        reinterpret_cast<float*>(workspace), out, units, 4, p.CI, p.CJ);
     return check_launch("wgrad_reduce_kernel");
   }
-  if (!p.in_scale && wgrad_choice() == 0 && p.Hb == p.H && p.Wb == p.W &&
+  if (!p.in_scale && p.Hb == p.H && p.Wb == p.W &&
       wgrad_rect_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], p.ntaps, p.stride, dtype))
     return launch_wgrad_rect(p.a, p.lda, p.b, p.ldb, out, workspace, workspace_bytes, p.N, p.H, p.W, p.CI, p.CJ, p.offy[8],
                              stream);
-  if ((p.in_scale || wgrad_choice() == 0) && p.Hb == p.H && p.Wb == p.W &&
+  if (p.Hb == p.H && p.Wb == p.W &&
       wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], p.ntaps, p.stride, dtype)) {
     const long need_f = wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ, dtype);
     if (need_f > workspace_bytes) {
@@ -368,7 +356,7 @@ int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_byt
                        reinterpret_cast<float*>(workspace), out, units, p.ntaps, p.CI, p.CJ);
     return check_launch("wgrad_reduce_kernel");
   }
-  const bool dma = !wgrad_legacy() && wgrad_dma_supported(p, dtype);
+  const bool dma = wgrad_dma_supported(p, dtype);
   const bool wide = wgrad_wide(p.CI, p.CJ);
   const int tw = dma ? wgrad_dma_tile(p.CI, p.CJ) : (wide ? 2 : 1);
   if (dma) plan_dma(P, p.CI, p.CJ, p.ntaps, dtype, p.ksplit, p.chunk);

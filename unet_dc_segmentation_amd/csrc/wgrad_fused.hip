@@ -9,10 +9,10 @@
 //   * three X row segments y-d,y,y+d [SEG + 2d (padded to SEG+16) pixels][64 ci]  (zero outside)
 // by LDS-DMA and accumulates ALL NINE taps from them: tap (ky,kx) reads X segment ky at pixel rows
 // shifted by kx*d.  9x the MFMA work per staged byte and per barrier.
-// Waves: 2x2 quadrants of the 64x64 (co x ci) tile, 9 accumulators (one per tap) each.
-// Fragments as in wgrad_frag.h: bf16 via ds_read_b64_tr_b16 on the [pixel][channel] image (64-byte
-// units XOR-swizzled by pixel row), fp32 via scalar reads.  Strips x y-ranges give the K split;
-// partial slabs are reduced by wgrad_reduce_kernel (deterministic).
+// fp32 (wgrad_fused_kernel, wgrad_ring_kernel): 2x2 quadrants of the 64x64 (co x ci) tile per wave,
+// 9 accumulators (one per tap) each, fragments by scalar reads.  bf16 (the tap-split kernels): wave
+// roles below, fragments via ds_read_b64_tr_b16 on the [pixel][channel] image (wgrad_frag.h).
+// Strips x y-ranges give the K split; partial slabs are reduced by wgrad_reduce_kernel (deterministic).
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -54,9 +54,10 @@ template <typename T> struct FusedCfg;
 template <> struct FusedCfg<bf16_t> { static constexpr int SEG = 64; };
 template <> struct FusedCfg<float> { static constexpr int SEG = 32; };
 
-template <typename T>
+// fp32 (bf16 runs the tap-split kernels below)
 __global__ __launch_bounds__(256, 2) void wgrad_fused_kernel(const WgradFusedParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  using T = float;
   constexpr int SEG = FusedCfg<T>::SEG;
   constexpr int XR = SEG + 16;                         // X segment rows (x0-d .. x0+SEG-1+d, d <= 8)
   constexpr int ES = (int)sizeof(T);
@@ -147,26 +148,16 @@ __global__ __launch_bounds__(256, 2) void wgrad_fused_kernel(const WgradFusedPar
     const unsigned char* sx = sdy + DYB;
 #pragma unroll
     for (int k16 = 0; k16 < SEG / 16; ++k16) {
-      if constexpr (sizeof(T) == 2) {
-        const bf16x8 fa = Frag<bf16_t, 1>::frag(sdy, lane, qi * 32, 16 * k16);
+      const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+      for (int kp = 0; kp < 8; ++kp) {
+        const int krow = 16 * k16 + 2 * kp + h;
+        const float fa = *reinterpret_cast<const float*>(sdy + krow * RB + (qi * 32 + r) * 4);
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
           const int ky = t / 3, kx = t - ky * 3;
-          const bf16x8 fb = Frag<bf16_t, 1>::frag(sx + ky * XB, lane, qj * 32, 16 * k16 + kx * p.d);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[t], 0, 0, 0);
-        }
-      } else {
-        const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int kp = 0; kp < 8; ++kp) {
-          const int krow = 16 * k16 + 2 * kp + h;
-          const float fa = *reinterpret_cast<const float*>(sdy + krow * RB + (qi * 32 + r) * 4);
-#pragma unroll
-          for (int t = 0; t < 9; ++t) {
-            const int ky = t / 3, kx = t - ky * 3;
-            const float fb = *reinterpret_cast<const float*>(sx + ky * XB + (krow + kx * p.d) * RB + (qj * 32 + r) * 4);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[t], 0, 0, 0);
-          }
+          const float fb = *reinterpret_cast<const float*>(sx + ky * XB + (krow + kx * p.d) * RB + (qj * 32 + r) * 4);
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[t], 0, 0, 0);
         }
       }
     }
@@ -187,7 +178,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_fused_kernel(const WgradFusedPar
 }
 
 // ------------------------------------------------------------------------------------------------
-// Ring variant for d <= 2 (every decoder level, enc1, enc2: most of the weight-gradient time).
+// Ring variant for d <= 2 (every decoder level, enc1, enc2: most of the weight-gradient time).  The bf16 form it was built
+// and measured as is now the tap-split ring kernel below; in fp32 only PF = 1 at d = 1 fits (ring_lds).
 //
 // SQ counters of the kernel above on enc1 (64->64, 512x512): MFMA pipe busy 40 %; a step lasts ~4.8K cycles of
 // which the two resident waves of a SIMD keep the MFMA pipe busy 2.3K -- the rest is the LDS-DMA of the NEXT
@@ -199,9 +191,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_fused_kernel(const WgradFusedPar
 //   step s: wait for group s (counted vmcnt: the younger group may stay in flight) ; barrier (everyone's
 //   group s has landed AND everyone is done with step s-1, whose oldest X row / dY slot are now free) ;
 //   issue group s+PF into exactly those slots ; 36 MFMAs per wave.
-template <typename T, int PF>
+template <int PF>
 __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(const WgradFusedParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  using T = float;
   constexpr int SEG = FusedCfg<T>::SEG;
   constexpr int XR = SEG + 16;
   constexpr int ES = (int)sizeof(T);
@@ -316,46 +309,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(const WgradFusedPara
     }
     const unsigned char* sdyp = smem + sdy * DYB;
     const unsigned char* sx[3] = {xring + sl0 * XB, xring + sl1 * XB, xring + sl2 * XB};
-    if constexpr (sizeof(T) == 2) {
-      // Fragment reads two groups ahead of the MFMAs that consume them (group = one k16 x one X row = 3 taps).
-      // Left to itself the compiler reads each fragment one MFMA before its use, and every MFMA then waits out the
-      // LDS latency: 36 x ~130 cycles per step instead of 36 x 32.
-      constexpr int NG = (SEG / 16) * 3;
-      bf16x8 fa[2], fb[3][3];
-      auto load_group = [&](int g) {
-        const int k16 = g / 3, ky = g - k16 * 3;
-        if (ky == 0) fa[k16 & 1] = Frag<bf16_t, 1>::frag(sdyp, lane, qi * 32, 16 * k16);
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) fb[g % 3][kx] = Frag<bf16_t, 1>::frag(sx[ky], lane, qj * 32, 16 * k16 + kx * d);
-      };
-      load_group(0);
-      load_group(1);
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        if (g + 2 < NG) load_group(g + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        const int k16 = g / 3, ky = g - k16 * 3;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-          acc[3 * ky + kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[k16 & 1], fb[g % 3][kx], acc[3 * ky + kx], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
 #pragma unroll
     for (int k16 = 0; k16 < SEG / 16; ++k16) {
-      if constexpr (sizeof(T) == 2) {
-      } else {
-        const int r = lane & 31, h = lane >> 5;
+      const int r = lane & 31, h = lane >> 5;
 #pragma unroll
-        for (int kp = 0; kp < 8; ++kp) {
-          const int krow = 16 * k16 + 2 * kp + h;
-          const float fa = *reinterpret_cast<const float*>(sdyp + krow * RB + (qi * 32 + r) * 4);
+      for (int kp = 0; kp < 8; ++kp) {
+        const int krow = 16 * k16 + 2 * kp + h;
+        const float fa = *reinterpret_cast<const float*>(sdyp + krow * RB + (qi * 32 + r) * 4);
 #pragma unroll
-          for (int t = 0; t < 9; ++t) {
-            const int ky = t / 3, kx = t - ky * 3;
-            const float fb = *reinterpret_cast<const float*>(sx[ky] + (krow + kx * d) * RB + (qj * 32 + r) * 4);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[t], 0, 0, 0);
-          }
+        for (int t = 0; t < 9; ++t) {
+          const int ky = t / 3, kx = t - ky * 3;
+          const float fb = *reinterpret_cast<const float*>(sx[ky] + (krow + kx * d) * RB + (qj * 32 + r) * 4);
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, fb, acc[t], 0, 0, 0);
         }
       }
     }
@@ -908,9 +873,7 @@ static int ring_lds(int d, int dtype, int pf) {
   return lds <= 80 * 1024 ? lds : 0;
 }
 static int ring_pf(int d, int dtype) {
-  static int off = -1;                                   // UNETDC_WGRAD_RING=0: always the three-segment kernel (A/B)
-  if (off < 0) { const char* e = getenv("UNETDC_WGRAD_RING"); off = (e && e[0] == '0') ? 1 : 0; }
-  if (off || d > 2) return 0;
+  if (d > 2) return 0;
   if (ring_lds(d, dtype, 2)) return 2;
   if (ring_lds(d, dtype, 1)) return 1;
   return 0;
@@ -951,9 +914,7 @@ long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype)
 
 // Fills the slabs; the caller reduces `units` slabs with wgrad_reduce_kernel.
 bool wgrad_bnin_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int dtype) {
-  static int splits = -1;
-  if (splits < 0) { const char* e = getenv("UNETDC_WGRAD_SPLIT"); splits = (e && e[0] == '0') ? 0 : 1; }
-  return dtype == UNETDC_BF16 && splits && wgrad_fused_supported(N, H, W, CI, CJ, lda, ldb, d, 9, 1, dtype) &&
+  return dtype == UNETDC_BF16 && wgrad_fused_supported(N, H, W, CI, CJ, lda, ldb, d, 9, 1, dtype) &&
          ring_pf(d, dtype) > 0;
 }
 
@@ -970,11 +931,9 @@ int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* 
   *units_out = units;
   const long nwg = (long)units * p.itiles * p.jtiles;
   const int pf = ring_pf(d, dtype);
-  static int split = -1;                                 // UNETDC_WGRAD_SPLIT=0: quadrant ring kernel (A/B)
-  if (split < 0) { const char* e = getenv("UNETDC_WGRAD_SPLIT"); split = (e && e[0] == '0') ? 0 : 1; }
   // (the tap-split kernels run on v_mfma_f32_16x16x32_bf16: settled in round 3, profiles/r03_wgrad_m16_ab.txt; the 32x32x16
   //  instantiations are no longer built)
-  if (in_scale && !(pf && dtype == UNETDC_BF16 && split)) {
+  if (in_scale && !(pf && dtype == UNETDC_BF16)) {
     set_error("wgrad (bnin): the input-normalising form exists for the 16x16x32 tap-split ring kernel only");
     return UNETDC_EUNSUPPORTED;
   }
@@ -983,7 +942,7 @@ int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* 
   // (one per CU: the two rings fill the LDS), i.e. every half does exactly the work a 256-thread workgroup did.
   // (three-segment staging, d = 4 / 8, waits for ALL its DMAs at every step: in lock step the two halves expose that wait
   //  together -- measured 155.4 vs 157.9 us at d = 4 but 175.3 vs 166.3 us at d = 8, profiles/r04_wgrad_pair_ab.txt)
-  if (dtype == UNETDC_BF16 && split && (pf || d <= 4)) {
+  if (dtype == UNETDC_BF16 && (pf || d <= 4)) {
     const int strips = N * (W / fused_seg(dtype)), tiles = p.itiles * p.jtiles;
     int ys = 256 / (strips * tiles);
     if (ys < 1) ys = 1;
@@ -1026,7 +985,7 @@ int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* 
       return check_launch("paired wgrad kernel");
     }
   }
-  if (pf && dtype == UNETDC_BF16 && split) {
+  if (pf && dtype == UNETDC_BF16) {
     const int lds = ring_lds(d, dtype, pf) + (in_scale ? 512 : 0);
     long nwg = (long)units * p.itiles * p.jtiles;
     if (p.ysplit == 1 && nwg > 512 && N > 1) {           // more than two workgroups per CU: walk several images per workgroup
@@ -1053,44 +1012,28 @@ int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* 
     note_kernel(pf == 2 ? "wgrad_ring_split_kernel<2, 16x16x32>" : "wgrad_ring_split_kernel<1, 16x16x32>");
     return check_launch("wgrad_ring_split_kernel");
   }
-  if (pf) {
-    const int lds = ring_lds(d, dtype, pf);
-    const void* fn;
-    if (dtype == UNETDC_BF16) fn = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_kernel<bf16_t, 2>)
-                                            : reinterpret_cast<const void*>(&wgrad_ring_kernel<bf16_t, 1>);
-    else fn = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_kernel<float, 2>)
-                      : reinterpret_cast<const void*>(&wgrad_ring_kernel<float, 1>);
-    if (const int rc_ = ensure_dynamic_lds(fn, 80 * 1024, "wgrad_ring_kernel")) return rc_;
-    if (dtype == UNETDC_BF16) {
-      if (pf == 2) hipLaunchKernelGGL((wgrad_ring_kernel<bf16_t, 2>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((wgrad_ring_kernel<bf16_t, 1>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-    } else {
-      if (pf == 2) hipLaunchKernelGGL((wgrad_ring_kernel<float, 2>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((wgrad_ring_kernel<float, 1>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-    }
-    char nm[64];
-    snprintf(nm, sizeof(nm), "wgrad_ring_kernel<%s, %d>", dtype == UNETDC_BF16 ? "__bf16" : "float", pf);
-    note_kernel(nm);
-    return check_launch("wgrad_ring_kernel");
-  }
   const int es = dtype == UNETDC_BF16 ? 2 : 4;
   const int seg = fused_seg(dtype);
-  const int lds = 2 * (seg * 64 * es + 3 * (seg + 16) * 64 * es);
-  if (dtype == UNETDC_BF16 && split) {                   // d = 4, 8 in bf16: tap-split wave roles on the three-segment staging
-    if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_fused_split_kernel<true>), lds, "wgrad_fused_split_kernel"))
+  const int lds3 = 2 * (seg * 64 * es + 3 * (seg + 16) * 64 * es);     // three-segment staging, double buffered
+  if (dtype == UNETDC_BF16) {                            // d = 4, 8: tap-split wave roles on the three-segment staging
+    if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_fused_split_kernel<true>), lds3, "wgrad_fused_split_kernel"))
       return rc_;
-    hipLaunchKernelGGL(wgrad_fused_split_kernel<true>, dim3((unsigned)nwg), dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(wgrad_fused_split_kernel<true>, dim3((unsigned)nwg), dim3(256), lds3, stream, p);
     note_kernel("wgrad_fused_split_kernel<16x16x32>");
     return check_launch("wgrad_fused_split_kernel");
   }
-  const void* fn = dtype == UNETDC_BF16 ? reinterpret_cast<const void*>(&wgrad_fused_kernel<bf16_t>)
-                                        : reinterpret_cast<const void*>(&wgrad_fused_kernel<float>);
-  if (const int rc_ = ensure_dynamic_lds(fn, lds, "wgrad_fused_kernel")) return rc_;
-  if (dtype == UNETDC_BF16)
-    hipLaunchKernelGGL(wgrad_fused_kernel<bf16_t>, dim3((unsigned)nwg), dim3(256), lds, stream, p);
-  else
-    hipLaunchKernelGGL(wgrad_fused_kernel<float>, dim3((unsigned)nwg), dim3(256), lds, stream, p);
-  note_kernel(dtype == UNETDC_BF16 ? "wgrad_fused_kernel<__bf16>" : "wgrad_fused_kernel<float>");
+  // fp32: the quadrant kernels, the ring where it fits (d = 1: one prefetch stage; a second one, or d = 2, exceeds the 80 KB
+  // of ring_lds), three-segment otherwise
+  if (pf) {
+    UNETDC_REQUIRE(pf == 1, "wgrad_ring: no fp32 form with %d prefetch stages", pf);
+    if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_ring_kernel<1>), 80 * 1024, "wgrad_ring_kernel")) return rc_;
+    hipLaunchKernelGGL((wgrad_ring_kernel<1>), dim3((unsigned)nwg), dim3(256), ring_lds(d, dtype, 1), stream, p);
+    note_kernel("wgrad_ring_kernel<float, 1>");
+    return check_launch("wgrad_ring_kernel");
+  }
+  if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_fused_kernel), lds3, "wgrad_fused_kernel")) return rc_;
+  hipLaunchKernelGGL(wgrad_fused_kernel, dim3((unsigned)nwg), dim3(256), lds3, stream, p);
+  note_kernel("wgrad_fused_kernel<float>");
   return check_launch("wgrad_fused_kernel");
 }
 

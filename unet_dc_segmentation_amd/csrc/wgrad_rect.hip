@@ -159,12 +159,6 @@ __global__ __launch_bounds__(256) void wgrad_rect_reduce_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-static int rect_enabled() {
-  static int v = -1;                                    // UNETDC_WGRAD_RECT=0: per-tap kernel over the padded K (A/B)
-  if (v < 0) { const char* e = getenv("UNETDC_WGRAD_RECT"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v;
-}
-
 // plan: K unit = the smallest tap rectangle list (rounded up to 64 pixels); returns the number of units or 0
 // tiles = number of 256 x 256 channel tiles: with few tiles the K unit is halved so that units x tiles still gives every
 // CU a workgroup (512 -> 1024 channels: 8 tiles x 16 units = 128 workgroups ran on half of the chip)
@@ -201,7 +195,7 @@ static int rect_plan(int N, int H, int W, int d, int tiles, WgradRectParams* out
 }
 
 bool wgrad_rect_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride, int dtype) {
-  if (!rect_enabled() || dtype != UNETDC_BF16 || ntaps != 9 || stride != 1) return false;
+  if (dtype != UNETDC_BF16 || ntaps != 9 || stride != 1) return false;
   if (CI % 256 != 0 || CJ % 256 != 0 || d < 1) return false;
   const long P = (long)N * H * W;
   if (P * lda * 2 >= (1L << 31) || P * ldb * 2 >= (1L << 31)) return false;

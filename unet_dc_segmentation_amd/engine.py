@@ -24,7 +24,6 @@ Data layout in HBM
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
@@ -36,19 +35,15 @@ _byref = ctypes.byref
 _storage_use_count = getattr(torch._C, "_storage_Use_Count", None)
 
 ENCODER = ("enc1", "enc2", "enc3", "enc4")
-# fuse the BatchNorm-backward reduction into the dgrad epilogue that produces the gradient (A/B switch; the stand-alone
-# reduction is also the fallback of the first-generation kernels)
-FUSE_BN_BWD = os.environ.get("UNETDC_FUSE_BNBWD", "1") != "0"
-# The head reads dec1's RAW conv output and applies that stage's BatchNorm + ReLU on load (unetdc_head_fwd_bn; the backward
-# recomputes the activation the same way): dec1.3's normalisation pass and its 268 MB activation tensor disappear from the
-# training step.  UNETDC_FUSE_HEAD_BN=0: stand-alone pass (A/B switch)
-FUSE_HEAD_BN = os.environ.get("UNETDC_FUSE_HEAD_BN", "1") != "0" and FUSE_BN_BWD
-# Second stage of a block fed from the first stage's RAW conv output ("bnin"): the consumer convolution and its weight gradient
-# apply the first stage's BatchNorm + ReLU per staged tile in LDS (unetdc_conv3x3_fwd_bnin / unetdc_conv3x3_wgrad_bnin), so
-# that stage's normalisation pass and activation tensor disappear.  Used where the library has the kernels (bf16, 64-channel
-# blocks: enc1 and dec1, the two largest normalisation passes of the step).  UNETDC_FUSE_BNIN=0: stand-alone passes (A/B)
-FUSE_BNIN = os.environ.get("UNETDC_FUSE_BNIN", "1") != "0"
-# Settled in rounds 3-4 (bit-identical to the forms they replaced, which are gone from the schedule):
+# The training schedule fuses (settled in rounds 1-4; bit-identical to the forms they replaced, which are gone from it):
+#  * the BatchNorm-backward reduction into the dgrad epilogue that produces the gradient (the library falls back to a
+#    stand-alone reduction behind the first-generation kernels);
+#  * the head reads dec1's RAW conv output and applies that stage's BatchNorm + ReLU on load (unetdc_head_fwd_bn; the
+#    backward recomputes the activation the same way): dec1.3's normalisation pass and its 268 MB activation tensor disappear;
+#  * second stage of a block fed from the first stage's RAW conv output ("bnin"): the consumer convolution and its weight
+#    gradient apply the first stage's BatchNorm + ReLU per staged tile in LDS (unetdc_conv3x3_fwd_bnin /
+#    unetdc_conv3x3_wgrad_bnin), so that stage's normalisation pass and activation tensor disappear.  Used where the library
+#    has the kernels (bf16, 64-channel blocks: enc1 and dec1, the two largest normalisation passes of the step);
 #  * the ConvTranspose2d bias gradient = column sums of the concat gradient, produced by the dgrad epilogue that writes it;
 #  * one-channel head: the gradient of the head's input is dz * w[c] per pixel, so dec1's last stage recomputes it in its
 #    BatchNorm-backward pass (unetdc_bn_relu_bwd_head) instead of reading a tensor the head backward wrote;
@@ -254,12 +249,11 @@ class UNetEngine:
         # (value 1: the activation of stage 0 is never stored, the weight gradient normalises on load too; 2: the second stage's
         #  forward stores it as a by-product and the plain weight-gradient kernel reads it -- unetdc_conv3x3_bnin_supported)
         self.bnin_blocks = {}
-        if FUSE_BNIN:
-            for (name, idx), st in self.stages.items():
-                h, w = st.hw
-                mode = lib.unetdc_conv3x3_bnin_supported(N, h, w, st.cin, st.cout, st.dil, self.dt) if idx == 3 else 0
-                if mode:
-                    self.bnin_blocks[name] = mode
+        for (name, idx), st in self.stages.items():
+            h, w = st.hw
+            mode = lib.unetdc_conv3x3_bnin_supported(N, h, w, st.cin, st.cout, st.dil, self.dt) if idx == 3 else 0
+            if mode:
+                self.bnin_blocks[name] = mode
         # gradient-side buffers (allocated lazily on the first backward)
         self.grad_bufs = None
         # parameter order == model.parameters() order; flat gradient offsets
@@ -414,7 +408,7 @@ class UNetEngine:
             call("unetdc_convT2x2_fwd", hin.data_ptr(), hin.stride(0), u["w_fwd"].data_ptr(),
                  u["mod"].bias.data_ptr(), upv.data_ptr(), upv.stride(0), N, h, w, u["cin"], c, self.dt, s)
             name = f"dec{lvl}"
-            head_norm = train and FUSE_HEAD_BN and lvl == 1          # dec1.3: normalised by the head while loading
+            head_norm = train and lvl == 1          # dec1.3: normalised by the head while loading
             s0 = self.stages[(name, 0)]
             fuse = train and name in self.bnin_blocks
             self._stage_fwd(s0, self.cat[lvl], self.a0[name], train, frozen=frozen, apply=not fuse)
@@ -424,7 +418,7 @@ class UNetEngine:
             hin = self.a3[name]
         probs = torch.empty(N, self.oc, self.H, self.W, device=self.device, dtype=torch.float32)
         oc = self.model.out_conv
-        if train and FUSE_HEAD_BN:
+        if train:
             last = self.stages[("dec1", 3)]
             call("unetdc_head_fwd_bn", last.y.data_ptr(), last.y.stride(0), last.scale.data_ptr(), last.shift.data_ptr(),
                  oc.weight.data_ptr(), oc.bias.data_ptr(), probs.data_ptr(), N, self.H, self.W, 64, self.oc, self.dt, s)
@@ -550,7 +544,7 @@ class UNetEngine:
 
     def _stage_dgrad(self, st, dx_out, fuse_prev, colsum, dy, ws, wsb, N, h, w, s):
         if not st.first:
-            if dx_out is not None and fuse_prev is not None and FUSE_BN_BWD:
+            if dx_out is not None and fuse_prev is not None:
                 call("unetdc_conv3x3_dgrad_bnstats", dy.data_ptr(), dy.stride(0), st.w_dgrad.data_ptr(),
                      dx_out.data_ptr(), dx_out.stride(0), *self._bnstats_args(fuse_prev), N, h, w, st.cin, st.cout,
                      st.dil, self.dt, s)
@@ -606,19 +600,14 @@ class UNetEngine:
         da = g[("da", 0)]
         last = self.stages[("dec1", 3)]                  # its activated output feeds out_conv
         # one output channel, training statistics: the head's input gradient is never stored (dec1.3 recomputes it)
-        head = (dprobs, probs, oc.weight) if (FUSE_BN_BWD and self.oc == 1 and not self._frozen) else None
-        if FUSE_BN_BWD:                                  # da's BatchNorm-backward sums come out of the same pass
-            call("unetdc_head_bwd_bnstats", dprobs.data_ptr(), probs.data_ptr(), _ptr(self.head_in),
-                 self.head_in.stride(0) if self.head_in is not None else 64, oc.weight.data_ptr(),
-                 None if head is not None else da.data_ptr(), da.stride(0),
-                 self._gview(flat, oc.weight).data_ptr(), self._gview(flat, oc.bias).data_ptr(), ws, wsb,
-                 *self._bnstats_args(last), N, self.H, self.W, 64, self.oc, self.dt, s)
-            last.bwd_nparts = self._np.value
-        else:
-            call("unetdc_head_bwd", dprobs.data_ptr(), probs.data_ptr(), self.head_in.data_ptr(),
-                 self.head_in.stride(0), oc.weight.data_ptr(), da.data_ptr(), da.stride(0),
-                 self._gview(flat, oc.weight).data_ptr(), self._gview(flat, oc.bias).data_ptr(), ws, wsb,
-                 N, self.H, self.W, 64, self.oc, self.dt, s)
+        head = (dprobs, probs, oc.weight) if (self.oc == 1 and not self._frozen) else None
+        # da's BatchNorm-backward sums come out of the same pass
+        call("unetdc_head_bwd_bnstats", dprobs.data_ptr(), probs.data_ptr(), _ptr(self.head_in),
+             self.head_in.stride(0) if self.head_in is not None else 64, oc.weight.data_ptr(),
+             None if head is not None else da.data_ptr(), da.stride(0),
+             self._gview(flat, oc.weight).data_ptr(), self._gview(flat, oc.bias).data_ptr(), ws, wsb,
+             *self._bnstats_args(last), N, self.H, self.W, 64, self.oc, self.dt, s)
+        last.bwd_nparts = self._np.value
         self._notify(flat, [self.model.out_conv])
         # decoder, level 1 (full resolution) up to level 4
         dact = da                               # gradient of the current block's activated output
@@ -637,13 +626,9 @@ class UNetEngine:
                  self._gview(flat, u["mod"].weight).data_ptr(), ws, wsb, N, h, w, u["cin"], c, self.dt, s)
             dnext = g[("da", lvl)]               # gradient w.r.t. the up-conv input (level lvl+1 resolution)
             prev = self.stages[("bottleneck" if lvl == 4 else f"dec{lvl + 1}", 3)]     # producer of the up-conv input
-            if FUSE_BN_BWD:
-                call("unetdc_convT2x2_dgrad_bnstats", dup.data_ptr(), dup.stride(0), u["w_dgrad"].data_ptr(),
-                     dnext.data_ptr(), dnext.stride(0), *self._bnstats_args(prev), N, h, w, u["cin"], c, self.dt, s)
-                prev.bwd_nparts = self._np.value
-            else:
-                call("unetdc_convT2x2_dgrad", dup.data_ptr(), dup.stride(0), u["w_dgrad"].data_ptr(),
-                     dnext.data_ptr(), dnext.stride(0), N, h, w, u["cin"], c, self.dt, s)
+            call("unetdc_convT2x2_dgrad_bnstats", dup.data_ptr(), dup.stride(0), u["w_dgrad"].data_ptr(),
+                 dnext.data_ptr(), dnext.stride(0), *self._bnstats_args(prev), N, h, w, u["cin"], c, self.dt, s)
+            prev.bwd_nparts = self._np.value
             self._notify(flat, [u["mod"]])
             dact = dnext
         # bottleneck: input is pool[4]

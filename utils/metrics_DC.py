@@ -10,8 +10,6 @@ reference's confusion-matrix PLOT (:87-116) is reporting, out of scope (SURVEY s
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -62,8 +60,8 @@ def focal_dice_loss(pred, target, alpha=1.0, gamma=2.0, ratio=0.3):
 
     fp32 probability maps on a HIP device take the fused kernels of
     ``unet_dc_segmentation_amd/csrc/loss.hip`` (same arithmetic, three launches instead of ~25 ATen
-    ones); set UNETDC_FUSED_LOSS=0 to force the PyTorch formulation."""
-    if pred.is_cuda and os.environ.get("UNETDC_FUSED_LOSS", "1") != "0":
+    ones)."""
+    if pred.is_cuda:
         from unet_dc_segmentation_amd import loss as fused
         if fused.supported(pred, target):
             return fused.focal_dice_loss(pred, target, alpha, gamma, ratio)
