@@ -61,6 +61,35 @@ static void taps3x3(int d, int* offy, int* offx) {
   }
 }
 
+// The implicit GEMM of a dilated 3 x 3 convolution over n x h x w with cin input and cout output channels (the input
+// gradient passes them swapped), and of the input gradient of ConvTranspose2d(2, 2, stride 2): four taps of stride 2.
+static IgemmParams conv3x3_igemm(int n, int h, int w, int cin, int cout, int ldx, int ldo, int d) {
+  IgemmParams p{};
+  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cin; p.Cout = cout; p.ldx = ldx; p.ldo = ldo;
+  p.ntaps = 9; p.stride = 1;
+  taps3x3(d, p.offy, p.offx);
+  return p;
+}
+static IgemmParams convT2x2_dgrad_igemm(int n, int h, int w, int cin, int cout, int lddup, int lddx) {
+  IgemmParams p{};
+  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = 2 * h; p.Wi = 2 * w; p.Cin = cout; p.Cout = cin; p.ldx = lddup;
+  p.ldo = lddx; p.ntaps = 4; p.stride = 2;
+  for (int t = 0; t < 4; ++t) { p.offy[t] = t >> 1; p.offx[t] = t & 1; }
+  return p;
+}
+
+// The weight gradient of the same dilated 3 x 3 convolution: a = dy [P][lddy], b = x [P][ldx], out [cout][cin][9].
+static WgradParams conv3x3_wgrad(int n, int h, int w, int cin, int cout, int ldx, int lddy, int d) {
+  WgradParams p{};
+  p.N = n; p.H = h; p.W = w; p.Hb = h; p.Wb = w; p.CI = cout; p.CJ = cin;
+  p.lda = lddy; p.ldb = ldx; p.ntaps = 9; p.stride = 1;
+  taps3x3(d, p.offy, p.offx);
+  return p;
+}
+
+// Capability queries plan a call without launching it; a non-null in_scale only says "normalise the input on load".
+static const float g_plan_marker = 0.f;
+
 }  // namespace unetdc
 
 using namespace unetdc;
@@ -101,12 +130,9 @@ int unetdc_conv3x3_fwd(const void* x, int ldx, const void* w_fwd, const float* b
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(dilation >= 1, "conv3x3_fwd: dilation must be >= 1");
   UNETDC_REQUIRE(ldx >= cin && ldy >= cout, "conv3x3_fwd: ld smaller than channel count");
-  IgemmParams p{};
+  IgemmParams p = conv3x3_igemm(n, h, w, cin, cout, ldx, ldy, dilation);
   p.x = x; p.w = w_fwd; p.out = y; p.bias = bias; p.scale = scale; p.shift = shift; p.stats = stats_part;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cin; p.Cout = cout; p.ldx = ldx; p.ldo = ldy;
-  p.ntaps = 9; p.stride = 1;
   p.mode = scale ? MODE_AFFINE_RELU : (stats_part ? MODE_STATS : MODE_STORE);
-  taps3x3(dilation, p.offy, p.offx);
   const int rc = launch_igemm(p, dtype, (hipStream_t)s);
   if (rc == UNETDC_OK && p.mode == MODE_STATS && stats_rows) *stats_rows = p.mblocks;   // rows that carry data (the rest are zeros)
   return rc;
@@ -115,13 +141,14 @@ int unetdc_conv3x3_fwd(const void* x, int ldx, const void* w_fwd, const float* b
 // forward conv fed from the RAW output of the stage in front of it: that stage's BatchNorm + ReLU is applied per staged patch
 int unetdc_conv3x3_bnin_supported(int n, int h, int w, int cin, int cout, int dilation, int dtype) {
   if (n <= 0 || h <= 0 || w <= 0 || dilation < 1) return 0;
-  IgemmParams p{};
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cin; p.Cout = cout; p.ldx = cin; p.ldo = cout;
-  p.ntaps = 9; p.stride = 1; p.mode = MODE_STATS;
-  taps3x3(dilation, p.offy, p.offx);
-  if (!igemm_lattice_bnin_supported(p, dtype)) return 0;
-  if (igemm_lattice_bnin_writes_activation(p, dtype)) return 2;      // forward stores the activation: any weight-gradient kernel follows
-  return wgrad_bnin_supported(n, h, w, cout, cin, cout, cin, dilation, dtype) ? 1 : 0;
+  IgemmParams p = conv3x3_igemm(n, h, w, cin, cout, cin, cout, dilation);
+  p.mode = MODE_STATS; p.in_scale = &g_plan_marker;
+  const IgemmPlan pl = plan_igemm(p, dtype);
+  if (pl.route != IGEMM_LATTICE) return 0;
+  if (pl.writes_act) return 2;       // forward stores the activation: any weight-gradient kernel follows
+  WgradParams g = conv3x3_wgrad(n, h, w, cin, cout, cin, cout, dilation);
+  g.in_scale = &g_plan_marker;
+  return plan_wgrad(g, dtype).route != WGRAD_UNSUPPORTED ? 1 : 0;
 }
 
 int unetdc_conv3x3_fwd_bnin(const void* x_raw, int ldx, const float* in_scale, const float* in_shift, const void* w_fwd,
@@ -132,13 +159,12 @@ int unetdc_conv3x3_fwd_bnin(const void* x_raw, int ldx, const float* in_scale, c
   UNETDC_REQUIRE(in_scale && in_shift && stats_part, "conv3x3_fwd_bnin: null pointer");
   UNETDC_REQUIRE(act_out == nullptr || (ldact >= cin && ldact % 8 == 0 && (int64_t)n * h * w * ldact * 2 < (1LL << 32)),
                  "conv3x3_fwd_bnin: bad activation ld (or an activation tensor of 4 GiB and more)");
-  IgemmParams p{};
+  IgemmParams p = conv3x3_igemm(n, h, w, cin, cout, ldx, ldy, dilation);
   p.act_out = act_out; p.ld_act = ldact;
   p.x = x_raw; p.w = w_fwd; p.out = y; p.bias = bias; p.stats = stats_part; p.in_scale = in_scale; p.in_shift = in_shift;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cin; p.Cout = cout; p.ldx = ldx; p.ldo = ldy;
-  p.ntaps = 9; p.stride = 1; p.mode = MODE_STATS;
-  taps3x3(dilation, p.offy, p.offx);
-  if (!igemm_lattice_bnin_supported(p, dtype) || (act_out && !igemm_lattice_bnin_writes_activation(p, dtype))) {
+  p.mode = MODE_STATS;
+  const IgemmPlan pl = plan_igemm(p, dtype);
+  if (pl.route != IGEMM_LATTICE || (act_out && !pl.writes_act)) {
     set_error("conv3x3_fwd_bnin: shape not supported by the input-normalising kernel%s (ask unetdc_conv3x3_bnin_supported)",
               act_out ? " that also stores the activation" : "");
     return UNETDC_EUNSUPPORTED;
@@ -153,10 +179,8 @@ int unetdc_conv3x3_wgrad_bnin(const void* x_raw, int ldx, const float* in_scale,
                               int cout, int dilation, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(dilation >= 1 && in_scale && in_shift, "conv3x3_wgrad_bnin: bad arguments");
-  WgradParams p{};
-  p.a = dy; p.b = x_raw; p.N = n; p.H = h; p.W = w; p.Hb = h; p.Wb = w; p.CI = cout; p.CJ = cin;
-  p.lda = lddy; p.ldb = ldx; p.ntaps = 9; p.stride = 1; p.in_scale = in_scale; p.in_shift = in_shift;
-  taps3x3(dilation, p.offy, p.offx);
+  WgradParams p = conv3x3_wgrad(n, h, w, cin, cout, ldx, lddy, dilation);
+  p.a = dy; p.b = x_raw; p.in_scale = in_scale; p.in_shift = in_shift;
   return launch_wgrad(p, dw, workspace, (long)workspace_bytes, dtype, (hipStream_t)s);
 }
 
@@ -165,11 +189,8 @@ int unetdc_conv3x3_dgrad(const void* dy, int lddy, const void* w_dgrad, void* dx
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(dilation >= 1, "conv3x3_dgrad: dilation must be >= 1");
   UNETDC_REQUIRE(lddy >= cout && lddx >= cin, "conv3x3_dgrad: ld smaller than channel count");
-  IgemmParams p{};
-  p.x = dy; p.w = w_dgrad; p.out = dx;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cout; p.Cout = cin; p.ldx = lddy; p.ldo = lddx;
-  p.ntaps = 9; p.stride = 1; p.mode = MODE_STORE;
-  taps3x3(dilation, p.offy, p.offx);
+  IgemmParams p = conv3x3_igemm(n, h, w, cout, cin, lddy, lddx, dilation);
+  p.x = dy; p.w = w_dgrad; p.out = dx; p.mode = MODE_STORE;
   return launch_igemm(p, dtype, (hipStream_t)s);
 }
 
@@ -189,11 +210,8 @@ int unetdc_conv3x3_dgrad_colsum(const void* dy, int lddy, const void* w_dgrad, v
     set_error("conv3x3_dgrad_colsum: workspace too small (%ld bytes)", (long)workspace_bytes);
     return UNETDC_EWORKSPACE;
   }
-  IgemmParams p{};
-  p.x = dy; p.w = w_dgrad; p.out = dx;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cout; p.Cout = cin; p.ldx = lddy; p.ldo = lddx;
-  p.ntaps = 9; p.stride = 1; p.mode = MODE_STATS; p.stats = reinterpret_cast<float*>(workspace);
-  taps3x3(dilation, p.offy, p.offx);
+  IgemmParams p = conv3x3_igemm(n, h, w, cout, cin, lddy, lddx, dilation);
+  p.x = dy; p.w = w_dgrad; p.out = dx; p.mode = MODE_STATS; p.stats = reinterpret_cast<float*>(workspace);
   int rc = launch_igemm(p, dtype, (hipStream_t)s);
   if (rc != UNETDC_OK) return rc;
   return launch_stats_colsum(p.stats, p.mblocks, cin, c0, c, colsum, (hipStream_t)s);       // rows the kernel wrote
@@ -209,12 +227,14 @@ static int dgrad_bnstats_common(IgemmParams& p, const void* y_prev, int ldy_prev
   UNETDC_REQUIRE((int64_t)(rows + 64) * 3 * c_prev <= parts_floats, "dgrad_bnstats: partial buffer too small");
   p.mode = MODE_BNBWD;
   p.stats = parts; p.bn_y = y_prev; p.bn_ldy = ldy_prev; p.scale = scale; p.shift = shift; p.bn_mean = mean; p.bn_rstd = rstd;
-  int rc = launch_igemm(p, dtype, stream);
-  if (rc == UNETDC_OK) { *nparts = p.mblocks; return rc; }                   // rows that carry data (<= rows; the rest are zeros)
-  if (rc != UNETDC_EUNSUPPORTED) return rc;
-  // first-generation kernel selected: plain dgrad, then the standalone reduction pass
+  if (plan_igemm(p, dtype).route != IGEMM_FIRSTGEN) {
+    const int rc = launch_igemm(p, dtype, stream);
+    if (rc == UNETDC_OK) *nparts = p.mblocks;                               // rows that carry data (<= rows; the rest are zeros)
+    return rc;
+  }
+  // the first-generation kernel has no fused sums: plain dgrad, then the standalone reduction pass
   p.mode = MODE_STORE; p.stats = nullptr;
-  rc = launch_igemm(p, dtype, stream);
+  const int rc = launch_igemm(p, dtype, stream);
   if (rc != UNETDC_OK) return rc;
   BnBwdParams b{};
   b.dskip = p.out; b.lds = p.ldo; b.y = y_prev; b.ldy = ldy_prev; b.scale = scale; b.shift = shift; b.mean = mean;
@@ -229,11 +249,8 @@ int unetdc_conv3x3_dgrad_bnstats(const void* dy, int lddy, const void* w_dgrad, 
                                             int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(dilation >= 1 && lddy >= cout && lddx >= cin, "conv3x3_dgrad_bnstats: bad dilation/ld");
-  IgemmParams p{};
+  IgemmParams p = conv3x3_igemm(n, h, w, cout, cin, lddy, lddx, dilation);
   p.x = dy; p.w = w_dgrad; p.out = dx;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = h; p.Wi = w; p.Cin = cout; p.Cout = cin; p.ldx = lddy; p.ldo = lddx;
-  p.ntaps = 9; p.stride = 1;
-  taps3x3(dilation, p.offy, p.offx);
   return dgrad_bnstats_common(p, y_prev, ldy_prev, scale, shift, mean, rstd, parts, parts_floats, nparts, n, h, w,
                               cin, dtype, (hipStream_t)s);
 }
@@ -245,26 +262,14 @@ int unetdc_convT2x2_dgrad_bnstats(const void* dup, int lddup, const void* w_dgra
                                              int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(lddup >= cout && lddx >= cin, "convT2x2_dgrad_bnstats: ld smaller than channel count");
-  IgemmParams p{};
+  IgemmParams p = convT2x2_dgrad_igemm(n, h, w, cin, cout, lddup, lddx);
   p.x = dup; p.w = w_dgrad; p.out = dx;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = 2 * h; p.Wi = 2 * w; p.Cin = cout; p.Cout = cin; p.ldx = lddup;
-  p.ldo = lddx; p.ntaps = 4; p.stride = 2;
-  for (int t = 0; t < 4; ++t) { p.offy[t] = t >> 1; p.offx[t] = t & 1; }
   return dgrad_bnstats_common(p, y_prev, ldy_prev, scale, shift, mean, rstd, parts, parts_floats, nparts, n, h, w,
                               cin, dtype, (hipStream_t)s);
 }
 
 int64_t unetdc_conv3x3_wgrad_workspace(int n, int h, int w, int cin, int cout, int dtype) {
-  long b = wgrad_workspace_bytes((long)n * h * w, cout, cin, 9, dtype);
-  // the tap-fused kernel may be chosen (launch_wgrad decides with wgrad_fused_supported; the query returns 0 for
-  // shapes that kernel never takes, so the same condition governs both sides)
-  const long f = wgrad_fused_workspace_bytes(n, h, w, cout, cin, dtype);
-  if (f > b) b = f;
-  for (int d = 1; d <= 64; d *= 2) {          // the valid-rectangle kernel (strongly dilated layers); dilation is not an argument here
-    const long r = wgrad_rect_workspace_bytes(n, h, w, cout, cin, d);
-    if (r > b) b = r;
-  }
-  return b;
+  return wgrad_workspace_bound(n, h, w, cout, cin, 9, dtype);
 }
 
 int unetdc_conv3x3_wgrad(const void* x, int ldx, const void* dy, int lddy, float* dw, void* workspace,
@@ -272,15 +277,13 @@ int unetdc_conv3x3_wgrad(const void* x, int ldx, const void* dy, int lddy, float
                          unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(dilation >= 1, "conv3x3_wgrad: dilation must be >= 1");
-  WgradParams p{};
-  p.a = dy; p.b = x; p.N = n; p.H = h; p.W = w; p.Hb = h; p.Wb = w; p.CI = cout; p.CJ = cin;
-  p.lda = lddy; p.ldb = ldx; p.ntaps = 9; p.stride = 1;
-  taps3x3(dilation, p.offy, p.offx);
+  WgradParams p = conv3x3_wgrad(n, h, w, cin, cout, ldx, lddy, dilation);
+  p.a = dy; p.b = x;
   return launch_wgrad(p, dw, workspace, (long)workspace_bytes, dtype, (hipStream_t)s);
 }
 
 int unetdc_conv3x3_first_stats_rows(int64_t npixels, int cin, int cout) {
-  return first_conv_mblocks((long)npixels, cin, cout);
+  return plan_first((long)npixels, cin, cout).fwd_blocks;
 }
 
 int unetdc_conv3x3_first_fwd(const float* x_nchw, const float* w, const float* bias, const float* scale,
@@ -296,7 +299,7 @@ int unetdc_conv3x3_first_fwd(const float* x_nchw, const float* w, const float* b
 }
 
 int64_t unetdc_conv3x3_first_wgrad_workspace(int n, int h, int w, int cin, int cout) {
-  return first_wgrad_workspace_bytes((long)n * h * w, cin, cout);
+  return plan_first((long)n * h * w, cin, cout).workspace;
 }
 
 int unetdc_conv3x3_first_wgrad(const float* x_nchw, const void* dy, int lddy, float* dw, void* workspace,
@@ -352,18 +355,13 @@ int unetdc_convT2x2_dgrad(const void* dup, int lddup, const void* w_dgrad, void*
                           int cin, int cout, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
   UNETDC_REQUIRE(lddup >= cout && lddx >= cin, "convT2x2_dgrad: ld smaller than channel count");
-  IgemmParams p{};
-  p.x = dup; p.w = w_dgrad; p.out = dx;
-  p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = 2 * h; p.Wi = 2 * w; p.Cin = cout; p.Cout = cin; p.ldx = lddup;
-  p.ldo = lddx; p.ntaps = 4; p.stride = 2; p.mode = MODE_STORE;
-  for (int t = 0; t < 4; ++t) { p.offy[t] = t >> 1; p.offx[t] = t & 1; }
+  IgemmParams p = convT2x2_dgrad_igemm(n, h, w, cin, cout, lddup, lddx);
+  p.x = dup; p.w = w_dgrad; p.out = dx; p.mode = MODE_STORE;
   return launch_igemm(p, dtype, (hipStream_t)s);
 }
 
 int64_t unetdc_convT2x2_wgrad_workspace(int n, int h, int w, int cin, int cout, int dtype) {
-  const long a = wgrad_workspace_bytes((long)n * h * w, cin, cout, 4, dtype);
-  const long b = convt_wgrad_fused_workspace_bytes(n, h, w, cin, cout);          // the tap-fused kernel may be chosen
-  return a > b ? a : b;
+  return wgrad_workspace_bound(n, h, w, cin, cout, 4, dtype);
 }
 
 int unetdc_convT2x2_wgrad(const void* x, int ldx, const void* dup, int lddup, float* dw, void* workspace,

@@ -164,7 +164,8 @@ __global__ __launch_bounds__(512, 2) void convt_wgrad_kernel(const ConvtWgradPar
 }
 
 // ------------------------------------------------------------------------------------------------
-static bool convt_wgrad_plan(int N, int H, int W, int CI, int CJ, int& ksplit, int& steps_per_half) {
+// K split of the tap-fused ConvTranspose2d weight gradient (plan_wgrad), false for shapes the kernel does not take
+bool convt_wgrad_split(int N, int H, int W, int CI, int CJ, int& ksplit, int& steps_per_half) {
   const long P = (long)N * H * W;
   if (W % 32 != 0 || CI % 128 != 0 || CJ % 64 != 0 || P % 64 != 0) return false;
   const long steps = P / 32;
@@ -178,34 +179,16 @@ static bool convt_wgrad_plan(int N, int H, int W, int CI, int CJ, int& ksplit, i
   return true;
 }
 
-bool convt_wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int ldx, int lddy, int dtype) {
-  if (dtype != UNETDC_BF16) return false;
-  int ks, sh;
-  if (!convt_wgrad_plan(N, H, W, CI, CJ, ks, sh)) return false;
-  const long P = (long)N * H * W;
-  return P * ldx * 2 < (1L << 32) && 4 * P * lddy * 2 < (1L << 32) && ldx % 8 == 0 && lddy % 8 == 0;
-}
-
-long convt_wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ) {
-  int ks, sh;
-  if (!convt_wgrad_plan(N, H, W, CI, CJ, ks, sh)) return 0;
-  return (long)ks * 4 * CI * CJ * 4;
-}
-
-// Fills ksplit slabs [4][CI][CJ]; the caller reduces them with wgrad_reduce_kernel.
-int launch_convt_wgrad_fused(const void* x, int ldx, const void* dy, int lddy, float* part, int N, int H, int W, int CI, int CJ,
-                             int* units_out, hipStream_t stream) {
+// Fills pl.ksplit slabs [4][CI][CJ] (x = w.a, dy = w.b); the caller reduces them with wgrad_reduce_kernel.
+int launch_convt_wgrad_fused(const WgradParams& w, const WgradPlan& pl, hipStream_t stream) {
   ConvtWgradParams p{};
-  p.x = x; p.dy = dy; p.part = part; p.N = N; p.H = H; p.W = W; p.CI = CI; p.CJ = CJ; p.ldx = ldx; p.lddy = lddy;
-  if (!convt_wgrad_plan(N, H, W, CI, CJ, p.ksplit, p.steps_per_half)) {
-    set_error("convT wgrad (fused): unsupported shape");
-    return UNETDC_EUNSUPPORTED;
-  }
-  p.itiles = CI / 128;
-  p.jtiles = CJ / 64;
+  p.x = w.a; p.dy = w.b; p.part = w.part; p.N = w.N; p.H = w.H; p.W = w.W; p.CI = w.CI; p.CJ = w.CJ; p.ldx = w.lda; p.lddy = w.ldb;
+  p.ksplit = pl.ksplit;
+  p.steps_per_half = pl.steps_per_half;
+  p.itiles = p.CI / 128;
+  p.jtiles = p.CJ / 64;
   constexpr int LDS = 2 * CWG_HALF;
   if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&convt_wgrad_kernel), LDS, "convt_wgrad_kernel")) return rc_;
-  *units_out = p.ksplit;
   const long nwg = (long)p.ksplit * p.itiles * p.jtiles;
   hipLaunchKernelGGL(convt_wgrad_kernel, dim3((unsigned)nwg), dim3(512), LDS, stream, p);
   note_kernel("convt_wgrad_kernel");

@@ -302,8 +302,31 @@ static int first_blocks(long P, int Cout) {
   return (int)nb;
 }
 
-int first_conv_mblocks(long P, int Cin, int Cout) {
-  return first_mfma_supported(P, Cin, Cout) ? first_mfma_mblocks(P) : first_blocks(P, Cout);
+constexpr long FIRST_ROWS_MAXB = 512;     // measured at 8 x 512 x 512: 2048 -> 122 us, 1024 -> 106, 512 -> 79, 256 -> 98
+static long first_rows_blocks(long P, int Cout) {          // row-run kernel: one run of 8 pixels per lane group and trip
+  const long ppb = 256 / (Cout / 8);
+  long nb = (P / 8 + ppb - 1) / ppb;
+  return nb > FIRST_ROWS_MAXB ? FIRST_ROWS_MAXB : (nb < 1 ? 1 : nb);
+}
+
+// The one place that decides the first layer's kernels and grids: the launchers and the C-ABI queries read it.
+FirstPlan plan_first(long P, int Cin, int Cout) {
+  FirstPlan pl{};
+  pl.mfma = Cout == 64 && (Cin == 1 || Cin == 3) && P % 32 == 0 && P < (1L << 23);
+  pl.fwd_blocks = pl.mfma ? first_mfma_mblocks(P) : first_blocks(P, Cout);
+  // The MFMA weight-gradient kernel takes all 9*Cin taps in ONE pass over dY; the VALU kernel needs one pass per input
+  // channel but is as fast for Cin = 1 (measured 155 vs 169 us at 8 x 512 x 512), so the MFMA kernel serves Cin = 3.
+  pl.wgrad_mfma = Cin > 1 && pl.mfma;
+  if (pl.wgrad_mfma) {
+    pl.wgrad_blocks = first_mfma_wgrad_blocks(P);
+  } else {
+    pl.wgrad_blocks = first_blocks(P, Cout) > 512 ? 512 : first_blocks(P, Cout);
+    pl.rows_blocks = (int)first_rows_blocks(P, Cout);
+  }
+  // whichever VALU kernel the launch picks (dilation / W / the workspace decide there)
+  const long blocks = pl.wgrad_blocks > pl.rows_blocks ? pl.wgrad_blocks : pl.rows_blocks;
+  pl.workspace = blocks * Cin * 9 * Cout * 4;
+  return pl;
 }
 
 int launch_first_fwd(FirstParams& p, int dtype, hipStream_t stream) {
@@ -313,9 +336,9 @@ int launch_first_fwd(FirstParams& p, int dtype, hipStream_t stream) {
   UNETDC_REQUIRE(p.Cout % 8 == 0 && p.Cout >= 8 && p.Cout / 8 <= 16 && 64 % (p.Cout / 8) == 0,
                  "first_conv: Cout=%d unsupported (8,16,32,64,128)", p.Cout);
   UNETDC_REQUIRE(p.ldy % 8 == 0 && (uintptr_t)p.y % 16 == 0, "first_conv: output not 16-byte aligned");
-  const long P = (long)p.N * p.H * p.W;
-  if (first_mfma_supported(P, p.Cin, p.Cout)) return launch_first_mfma_fwd(p, dtype, stream);     // first_conv_mfma.hip
-  const int nb = first_blocks(P, p.Cout);
+  const FirstPlan pl = plan_first((long)p.N * p.H * p.W, p.Cin, p.Cout);
+  if (pl.mfma) return launch_first_mfma_fwd(p, pl.fwd_blocks, dtype, stream);     // first_conv_mfma.hip
+  const int nb = pl.fwd_blocks;
   const size_t lds = (size_t)(9 * p.Cin * p.Cout + 256 * 16) * 4;
   if (dtype == UNETDC_BF16)
     hipLaunchKernelGGL(first_conv_fwd_kernel<bf16_t>, dim3(nb), dim3(256), lds, stream, p);
@@ -325,31 +348,12 @@ int launch_first_fwd(FirstParams& p, int dtype, hipStream_t stream) {
   return check_launch("first_conv_fwd_kernel");
 }
 
-// The MFMA weight-gradient kernel takes all 9*Cin taps in ONE pass over dY; the VALU kernel needs one pass per input
-// channel but is as fast for Cin = 1 (measured 155 vs 169 us at 8 x 512 x 512), so the MFMA kernel serves Cin = 3.
-static bool first_wgrad_mfma(long P, int Cin, int Cout) { return Cin > 1 && first_mfma_supported(P, Cin, Cout); }
-
-constexpr long FIRST_ROWS_MAXB = 512;     // measured at 8 x 512 x 512: 2048 -> 122 us, 1024 -> 106, 512 -> 79, 256 -> 98
-static long first_rows_blocks(long P, int Cout) {          // row-run kernel: one run of 8 pixels per lane group and trip
-  const long ppb = 256 / (Cout / 8);
-  long nb = (P / 8 + ppb - 1) / ppb;
-  return nb > FIRST_ROWS_MAXB ? FIRST_ROWS_MAXB : (nb < 1 ? 1 : nb);
-}
-
 // One input channel only: the row-run kernel makes one pass over dY PER input channel, and with the BatchNorm backward on load
 // every pass would also re-read y.
 bool first_wgrad_bn_supported(int N, int H, int W, int Cin, int Cout, int dil, int dtype) {
   (void)N; (void)H;
   return (dtype == UNETDC_F32 || dtype == UNETDC_BF16) && Cin == 1 && dil == 1 && W % 8 == 0 && Cout % 8 == 0 &&
          Cout / 8 <= 16 && 64 % (Cout / 8) == 0;
-}
-
-long first_wgrad_workspace_bytes(long P, int Cin, int Cout) {
-  if (first_wgrad_mfma(P, Cin, Cout)) return first_mfma_wgrad_workspace_bytes(P, Cin, Cout);
-  long nb = first_blocks(P, Cout);
-  if (nb > 512) nb = 512;
-  const long nr = first_rows_blocks(P, Cout);            // whichever VALU kernel the launch picks (dilation / W decide there)
-  return (nb > nr ? nb : nr) * Cin * 9 * Cout * 4;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -440,75 +444,45 @@ int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long wor
   UNETDC_REQUIRE(p.x && p.dy && dw && workspace, "first_wgrad: null pointer");
   UNETDC_REQUIRE(p.Cin >= 1 && p.Cin <= 8, "first_wgrad: Cin=%d unsupported", p.Cin);
   UNETDC_REQUIRE(p.Cout % 8 == 0 && p.Cout / 8 <= 16 && 64 % (p.Cout / 8) == 0, "first_wgrad: Cout=%d unsupported", p.Cout);
-  const long P = (long)p.N * p.H * p.W;
+  const FirstPlan pl = plan_first((long)p.N * p.H * p.W, p.Cin, p.Cout);
+  const long slab = (long)p.Cin * 9 * p.Cout * 4;
+  const bool bf16 = dtype == UNETDC_BF16, x16 = (reinterpret_cast<uintptr_t>(p.x) & 15) == 0;
   if (p.bn_y) {                                          // BatchNorm backward on load: the row-run kernel only
     UNETDC_REQUIRE(p.bn_scale && p.bn_shift && p.bn_mean && p.bn_rstd && p.bn_k, "first_wgrad (bn): null pointer");
-    UNETDC_REQUIRE(first_wgrad_bn_supported(p.N, p.H, p.W, p.Cin, p.Cout, p.dil, dtype) && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0 &&
-                       p.bn_ldy % (dtype == UNETDC_BF16 ? 8 : 4) == 0,
+    UNETDC_REQUIRE(first_wgrad_bn_supported(p.N, p.H, p.W, p.Cin, p.Cout, p.dil, dtype) && x16 && p.bn_ldy % (bf16 ? 8 : 4) == 0,
                    "first_wgrad (bn): shape not supported (ask unetdc_conv3x3_first_wgrad_bn_supported)");
-    const long nr = first_rows_blocks(P, p.Cout);
-    const long need_r = nr * p.Cin * 9 * p.Cout * 4;
-    if (need_r > workspace_bytes) {
-      set_error("first_wgrad (bn): workspace too small (%ld < %ld bytes)", workspace_bytes, need_r);
-      return UNETDC_EWORKSPACE;
-    }
-    p.part = reinterpret_cast<float*>(workspace);
-    const size_t lds_r = (size_t)4 * (p.Cout / 8) * 72 * 4;
-    if (dtype == UNETDC_BF16)
-      hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, true>), dim3((unsigned)nr, p.Cin), dim3(256), lds_r, stream, p);
-    else
-      hipLaunchKernelGGL((first_wgrad_rows_kernel<float, true>), dim3((unsigned)nr, p.Cin), dim3(256), lds_r, stream, p);
-    note_kernel(dtype == UNETDC_BF16 ? "first_wgrad_rows_kernel<__bf16> bn" : "first_wgrad_rows_kernel<float> bn");
-    int rc = check_launch("first_wgrad_rows_kernel(bn)");
-    if (rc != UNETDC_OK) return rc;
-    const int n = p.Cin * 9 * p.Cout;
-    hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, p.part, dw, (int)nr, p.Cin, p.Cout);
-    return check_launch("first_wgrad_reduce_kernel");
   }
-  const bool mfma = first_wgrad_mfma(P, p.Cin, p.Cout);
-  long nb = first_blocks(P, p.Cout);
-  if (nb > 512) nb = 512;
-  const long need = mfma ? first_mfma_wgrad_workspace_bytes(P, p.Cin, p.Cout) : nb * p.Cin * 9 * p.Cout * 4;
-  if (need > workspace_bytes) {
-    set_error("first_wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, need);
+  const long nb = p.bn_y ? pl.rows_blocks : pl.wgrad_blocks;
+  if (nb * slab > workspace_bytes) {
+    set_error("first_wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, nb * slab);
     return UNETDC_EWORKSPACE;
   }
   p.part = reinterpret_cast<float*>(workspace);
-  if (mfma) {                                            // first_conv_mfma.hip
-    int nblk = 0;
-    int rc = launch_first_mfma_wgrad(p, &nblk, dtype, stream);
-    if (rc != UNETDC_OK) return rc;
-    const int n = p.Cin * 9 * p.Cout;
-    hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, p.part, dw, nblk, p.Cin, p.Cout);
-    return check_launch("first_wgrad_reduce_kernel");
-  }
   const size_t lds = (size_t)4 * (p.Cout / 8) * 72 * 4;
-  if (p.dil == 1 && p.W % 8 == 0 && (reinterpret_cast<uintptr_t>(p.x) & 15) == 0) {
-    const long nr = first_rows_blocks(P, p.Cout);
-    if (nr * p.Cin * 9 * p.Cout * 4 <= workspace_bytes) {
-      if (dtype == UNETDC_BF16)
-        hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, false>), dim3((unsigned)nr, p.Cin), dim3(256), lds, stream, p);
-      else
-        hipLaunchKernelGGL((first_wgrad_rows_kernel<float, false>), dim3((unsigned)nr, p.Cin), dim3(256), lds, stream, p);
-      note_kernel(dtype == UNETDC_BF16 ? "first_wgrad_rows_kernel<__bf16>" : "first_wgrad_rows_kernel<float>");
-      int rc = check_launch("first_wgrad_rows_kernel");
-      if (rc != UNETDC_OK) return rc;
-      const int n = p.Cin * 9 * p.Cout;
-      hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, p.part, dw, (int)nr,
-                         p.Cin, p.Cout);
-      return check_launch("first_wgrad_reduce_kernel");
-    }
+  const dim3 grid_r((unsigned)pl.rows_blocks, p.Cin), block(256);
+  int nblk = (int)nb, rc;
+  if (p.bn_y) {
+    if (bf16) hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, true>), grid_r, block, lds, stream, p);
+    else hipLaunchKernelGGL((first_wgrad_rows_kernel<float, true>), grid_r, block, lds, stream, p);
+    note_kernel(bf16 ? "first_wgrad_rows_kernel<__bf16> bn" : "first_wgrad_rows_kernel<float> bn");
+    rc = check_launch("first_wgrad_rows_kernel(bn)");
+  } else if (pl.wgrad_mfma) {                            // first_conv_mfma.hip
+    rc = launch_first_mfma_wgrad(p, nblk, dtype, stream);
+  } else if (p.dil == 1 && p.W % 8 == 0 && x16 && pl.rows_blocks * slab <= workspace_bytes) {
+    nblk = pl.rows_blocks;
+    if (bf16) hipLaunchKernelGGL((first_wgrad_rows_kernel<bf16_t, false>), grid_r, block, lds, stream, p);
+    else hipLaunchKernelGGL((first_wgrad_rows_kernel<float, false>), grid_r, block, lds, stream, p);
+    note_kernel(bf16 ? "first_wgrad_rows_kernel<__bf16>" : "first_wgrad_rows_kernel<float>");
+    rc = check_launch("first_wgrad_rows_kernel");
+  } else {
+    if (bf16) hipLaunchKernelGGL(first_conv_wgrad_kernel<bf16_t>, dim3(nblk, p.Cin), block, lds, stream, p);
+    else hipLaunchKernelGGL(first_conv_wgrad_kernel<float>, dim3(nblk, p.Cin), block, lds, stream, p);
+    note_kernel(bf16 ? "first_conv_wgrad_kernel<__bf16>" : "first_conv_wgrad_kernel<float>");
+    rc = check_launch("first_conv_wgrad_kernel");
   }
-  if (dtype == UNETDC_BF16)
-    hipLaunchKernelGGL(first_conv_wgrad_kernel<bf16_t>, dim3((unsigned)nb, p.Cin), dim3(256), lds, stream, p);
-  else
-    hipLaunchKernelGGL(first_conv_wgrad_kernel<float>, dim3((unsigned)nb, p.Cin), dim3(256), lds, stream, p);
-  note_kernel(dtype == UNETDC_BF16 ? "first_conv_wgrad_kernel<__bf16>" : "first_conv_wgrad_kernel<float>");
-  int rc = check_launch("first_conv_wgrad_kernel");
   if (rc != UNETDC_OK) return rc;
   const int n = p.Cin * 9 * p.Cout;
-  hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((n + 7) / 8), dim3(256), 0, stream, p.part, dw, (int)nb,
-                     p.Cin, p.Cout);
+  hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((n + 7) / 8), block, 0, stream, p.part, dw, nblk, p.Cin, p.Cout);
   return check_launch("first_wgrad_reduce_kernel");
 }
 

@@ -113,12 +113,9 @@ __global__ __launch_bounds__(256) void first_mfma_fwd_kernel(const IgemmParams p
 #endif
 }
 
-bool first_mfma_supported(long P, int Cin, int Cout) {
-  return Cout == 64 && (Cin == 1 || Cin == 3) && P % 32 == 0 && P < (1L << 23);
-}
 int first_mfma_mblocks(long P) { return ceil_div(P, FM_BM); }
 
-int launch_first_mfma_fwd(FirstParams& f, int dtype, hipStream_t stream) {
+int launch_first_mfma_fwd(FirstParams& f, int blocks, int dtype, hipStream_t stream) {
   IgemmParams p{};
   p.x = f.x; p.w = f.w; p.out = f.y; p.bias = f.bias; p.scale = f.scale; p.shift = f.shift; p.stats = f.stats;
   p.M = f.N * f.H * f.W; p.Ho = f.H; p.Wo = f.W; p.Hi = f.H; p.Wi = f.W; p.Cin = f.Cin; p.Cout = f.Cout; p.ldo = f.ldy;
@@ -128,7 +125,7 @@ int launch_first_mfma_fwd(FirstParams& f, int dtype, hipStream_t stream) {
   p.wo_shift = p2 ? __builtin_ctz((unsigned)f.W) : -1;
   p.howo_shift = p2 ? __builtin_ctzl((unsigned long)howo) : -1;
   UNETDC_REQUIRE((long)p.M * f.ldy * (dtype == UNETDC_BF16 ? 2 : 4) < (1L << 32), "first_conv: output too large");
-  const dim3 grid((unsigned)first_mfma_mblocks(p.M)), block(256);
+  const dim3 grid((unsigned)blocks), block(256);
   if (dtype == UNETDC_BF16) {
     if (f.Cin == 1) hipLaunchKernelGGL((first_mfma_fwd_kernel<bf16_t, 1>), grid, block, 0, stream, p, f.dil);
     else hipLaunchKernelGGL((first_mfma_fwd_kernel<bf16_t, 3>), grid, block, 0, stream, p, f.dil);
@@ -236,17 +233,15 @@ __global__ __launch_bounds__(256) void first_mfma_wgrad_kernel(const FirstWgradP
 #endif
 }
 
-static int first_mfma_wgrad_blocks(long P) {
+int first_mfma_wgrad_blocks(long P) {
   long nb = (P / 2 + 4 * 64 - 1) / (4 * 64);          // >= 64 pixel pairs per wave
   if (nb > 1024) nb = 1024;
   if (nb < 1) nb = 1;
   return (int)nb;
 }
-long first_mfma_wgrad_workspace_bytes(long P, int Cin, int Cout) { return (long)first_mfma_wgrad_blocks(P) * Cin * 9 * Cout * 4; }
 
-int launch_first_mfma_wgrad(FirstWgradParams& p, int* nblk_out, int dtype, hipStream_t stream) {
+int launch_first_mfma_wgrad(FirstWgradParams& p, int nb, int dtype, hipStream_t stream) {
   const long P = (long)p.N * p.H * p.W;
-  const int nb = first_mfma_wgrad_blocks(P);
   const long pairs = (P + 1) / 2;
   int ppw = (int)((pairs + (long)nb * 4 - 1) / ((long)nb * 4));
   ppw = (ppw + FW_UNROLL - 1) / FW_UNROLL * FW_UNROLL;
@@ -261,7 +256,6 @@ int launch_first_mfma_wgrad(FirstWgradParams& p, int* nblk_out, int dtype, hipSt
     if (p.Cin == 1) hipLaunchKernelGGL((first_mfma_wgrad_kernel<float, 1>), grid, block, 0, stream, p, ppw, ws, hs);
     else hipLaunchKernelGGL((first_mfma_wgrad_kernel<float, 3>), grid, block, 0, stream, p, ppw, ws, hs);
   }
-  *nblk_out = nb;
   note_kernel(dtype == UNETDC_BF16 ? "first_mfma_wgrad_kernel<__bf16>" : "first_mfma_wgrad_kernel<float>");
   return check_launch("first_mfma_wgrad_kernel");
 }

@@ -272,13 +272,6 @@ __global__ __launch_bounds__(256, 2) void igemm_conv_kernel(const IgemmParams p)
 }
 
 // ------------------------------------------------------------------------------------------------
-// defined in igemm_dma.hip (second-generation kernel, used whenever the tensors are < 2 GiB)
-bool igemm_dma_supported(const IgemmParams& p, int dtype);
-int launch_igemm_dma(IgemmParams& p, int dtype, hipStream_t stream);
-// defined in igemm_halo.hip (LDS-staged input patch shared by all 9 taps; narrow layers, d <= 2)
-bool igemm_halo_supported(const IgemmParams& p, int dtype);
-int launch_igemm_halo(IgemmParams& p, int dtype, hipStream_t stream);
-
 // Every configuration that can be asked for BatchNorm statistics uses 256-pixel M blocks, so the
 // number of partial-statistics rows is a function of the pixel count only.
 int igemm_mblocks(long M, int Cout) { (void)Cout; return ceil_div(M, 256); }
@@ -296,6 +289,62 @@ static int launch_cfg(IgemmParams& p, hipStream_t stream) {
   snprintf(nm, sizeof(nm), "igemm_conv_kernel<%s, %d, %d>", sizeof(T) == 2 ? "__bf16" : "float", WM, WN);
   note_kernel(nm);
   return check_launch("igemm_conv_kernel");
+}
+
+// The one place that decides which kernel family takes a call: launch_igemm and the C-ABI queries read it.
+IgemmPlan plan_igemm(const IgemmParams& p, int dtype) {
+  IgemmPlan pl{};
+  const bool lattice = igemm_lattice_supported(p, dtype);
+  if (p.in_scale) {
+    // input normalisation on load exists in the lattice kernel ONLY: no other kernel may take this call, it would read the
+    // raw tensor as if it were the activation.  The statistics forward of the 4-wave forms has it (64-channel n-blocks:
+    // constants in LDS, Cin <= 256; 128-channel n-blocks: constants through the scalar cache, any Cin), and the wide form
+    // can also store the normalised activation (IgemmParams::act_out)
+    if (lattice && p.mode == MODE_STATS && (p.Cout % 128 == 0 || p.Cin <= 256)) {
+      pl.route = IGEMM_LATTICE;
+      pl.writes_act = p.Cout % 128 == 0 && (long)p.M * p.Cin * 2 < (1L << 32);
+    }
+    return pl;
+  }
+  if (lattice) {
+    pl.route = IGEMM_LATTICE;
+    return pl;
+  }
+  if (igemm_halo_supported(p, dtype)) {
+    pl.route = IGEMM_HALO;
+    return pl;
+  }
+  // the second-generation (LDS-DMA) kernels whenever the tensors are < 2 GiB
+  const long es = dtype == UNETDC_BF16 ? 2 : 4;
+  const long HoWo = (long)p.Ho * p.Wo;
+  const long xbytes = (p.M / HoWo) * p.Hi * p.Wi * p.ldx * es;
+  const long wbytes = (long)p.ntaps * p.Cout * p.Cin * es;
+  const long opix = p.mode == MODE_SHUFFLE ? 4L * p.M : (long)p.M;
+  const long obytes = opix * p.ldo * es, ybytes = p.mode == MODE_BNBWD ? (long)p.M * p.bn_ldy * es : 0;
+  if (!(xbytes < (1L << 31) && wbytes < (1L << 31) && obytes < (1L << 32) && ybytes < (1L << 32) && p.M % HoWo == 0)) {
+    pl.route = IGEMM_FIRSTGEN;
+    pl.cfg = (p.Cout % 128 == 0) && p.mode != MODE_STATS;         // statistics rows assume BM = 256
+    return pl;
+  }
+  // 256x256 tiles only when they still give every CU a workgroup; small maps (bottleneck: 8192 pixels)
+  // take 256x128 so that the grid covers the chip
+  const long blocks_a = (long)((p.M + 255) / 256) * (p.Cout / 256);
+  const bool use_a = p.Cout % 256 == 0 && p.M >= 256 * 64 && blocks_a >= 200;
+  const bool use_b = !use_a && p.Cout % 128 == 0;
+  pl.route = IGEMM_DMA;
+  pl.cfg = use_a ? 1 : (use_b ? 2 : 3);
+  if (dtype == UNETDC_BF16 && p.M % 16 == 0 && !(p.mode == MODE_SHUFFLE && p.Wo % 16 != 0)) {
+    pl.route = IGEMM_DMA16;                                         // bf16: 16x16x32 MFMA shape (igemm_dma16.hip)
+    // two measured refinements of the rule above (MI355X, bs 8):
+    //  * ConvTranspose2d forward with N = 4 * Cout >= 2048 on a small map (upconv4: 8192 pixels): 256 workgroups of
+    //    256 x 256 cover the chip and stage 25 % fewer bytes per MFMA: 46 -> 39 us
+    //  * 256 x 128 tiles that leave half of the CUs without a workgroup (bottleneck.0 dgrad: 128 workgroups) while
+    //    256 x 64 tiles fill the chip: 101 -> 85 us
+    const long blocks_b = (long)((p.M + 255) / 256) * (p.Cout / 128);
+    if (pl.cfg == 2 && p.mode == MODE_SHUFFLE && p.Cout % 256 == 0 && blocks_a >= 200) pl.cfg = 1;
+    else if (pl.cfg == 2 && blocks_b >= 100 && blocks_b < 200) pl.cfg = 3;
+  }
+  return pl;
 }
 
 int launch_igemm(IgemmParams& p, int dtype, hipStream_t stream) {
@@ -322,23 +371,22 @@ int launch_igemm(IgemmParams& p, int dtype, hipStream_t stream) {
     p.wo_shift = p2 ? __builtin_ctz((unsigned)p.Wo) : -1;
     p.howo_shift = p2 ? __builtin_ctzl((unsigned long)howo) : -1;
   }
-  if (p.in_scale) {
-    // input normalisation on load exists in the lattice kernel ONLY: no other kernel may take this call, it would read the
-    // raw tensor as if it were the activation
-    if (!igemm_lattice_bnin_supported(p, dtype)) {
-      set_error("igemm: input normalisation asked for a shape / configuration the lattice kernel does not take");
-      return UNETDC_EUNSUPPORTED;
-    }
-    return launch_igemm_lattice(p, stream);
+  const IgemmPlan pl = plan_igemm(p, dtype);
+  switch (pl.route) {
+    case IGEMM_LATTICE: return launch_igemm_lattice(p, stream);
+    case IGEMM_HALO: return launch_igemm_halo(p, dtype, stream);
+    case IGEMM_DMA: return launch_igemm_dma(p, pl.cfg, dtype, stream);
+    case IGEMM_DMA16: return launch_igemm_dma16(p, pl.cfg, stream);
+    case IGEMM_FIRSTGEN:
+      if (p.mode == MODE_BNBWD) {
+        set_error("igemm: the first-generation kernel has no fused BatchNorm-backward sums");
+        return UNETDC_EUNSUPPORTED;
+      }
+      if (dtype == UNETDC_BF16) return pl.cfg ? launch_cfg<bf16_t, 2, 2>(p, stream) : launch_cfg<bf16_t, 4, 1>(p, stream);
+      return pl.cfg ? launch_cfg<float, 2, 2>(p, stream) : launch_cfg<float, 4, 1>(p, stream);
   }
-  if (igemm_lattice_supported(p, dtype)) return launch_igemm_lattice(p, stream);
-  if (igemm_halo_supported(p, dtype)) return launch_igemm_halo(p, dtype, stream);
-  if (igemm_dma_supported(p, dtype)) return launch_igemm_dma(p, dtype, stream);
-  if (p.mode == MODE_BNBWD) return UNETDC_EUNSUPPORTED;      // first-generation kernel: caller reduces separately
-  const bool wide = (p.Cout % 128 == 0) && p.mode != MODE_STATS;     // statistics rows assume BM = 256
-  if (dtype == UNETDC_BF16)
-    return wide ? launch_cfg<bf16_t, 2, 2>(p, stream) : launch_cfg<bf16_t, 4, 1>(p, stream);
-  return wide ? launch_cfg<float, 2, 2>(p, stream) : launch_cfg<float, 4, 1>(p, stream);
+  set_error("igemm: input normalisation asked for a shape / configuration the lattice kernel does not take");
+  return UNETDC_EUNSUPPORTED;
 }
 
 }  // namespace unetdc

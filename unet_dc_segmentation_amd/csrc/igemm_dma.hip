@@ -344,43 +344,10 @@ static int launch_dma_cfg(IgemmParams& p, hipStream_t stream) {
   return check_launch("igemm_dma_kernel");
 }
 
-// rows of BatchNorm partial statistics the chosen configuration produces (all use BM = 256)
-int igemm_dma_mblocks(long M) { return ceil_div(M, 256); }
-
-bool igemm_dma_supported(const IgemmParams& p, int dtype) {
-  const long es = dtype == UNETDC_BF16 ? 2 : 4;
-  const long HoWo = (long)p.Ho * p.Wo;
-  const long xbytes = (p.M / HoWo) * p.Hi * p.Wi * p.ldx * es;
-  const long wbytes = (long)p.ntaps * p.Cout * p.Cin * es;
-  const long opix = p.mode == MODE_SHUFFLE ? 4L * p.M : (long)p.M;
-  const long obytes = opix * p.ldo * es, ybytes = p.mode == MODE_BNBWD ? (long)p.M * p.bn_ldy * es : 0;
-  return xbytes < (1L << 31) && wbytes < (1L << 31) && obytes < (1L << 32) && ybytes < (1L << 32) && p.M % HoWo == 0;
-}
-
-int launch_igemm_dma(IgemmParams& p, int dtype, hipStream_t stream) {
-  // 256x256 tiles only when they still give every CU a workgroup; small maps (bottleneck: 8192 pixels)
-  // take 256x128 so that the grid covers the chip
-  const long blocks_a = (long)((p.M + 255) / 256) * (p.Cout / 256);
-  const bool use_a = p.Cout % 256 == 0 && p.M >= 256 * 64 && blocks_a >= 200;
-  const bool use_b = !use_a && p.Cout % 128 == 0;
-  if (igemm_dma16_supported(p, dtype)) {               // bf16: 16x16x32 MFMA shape (igemm_dma16.hip)
-    int cfg = use_a ? 1 : (use_b ? 2 : 3);
-    // two measured refinements of the rule above (MI355X, bs 8):
-    //  * ConvTranspose2d forward with N = 4 * Cout >= 2048 on a small map (upconv4: 8192 pixels): 256 workgroups of
-    //    256 x 256 cover the chip and stage 25 % fewer bytes per MFMA: 46 -> 39 us
-    //  * 256 x 128 tiles that leave half of the CUs without a workgroup (bottleneck.0 dgrad: 128 workgroups) while
-    //    256 x 64 tiles fill the chip: 101 -> 85 us
-    const long blocks_b = (long)((p.M + 255) / 256) * (p.Cout / 128);
-    if (cfg == 2 && p.mode == MODE_SHUFFLE && p.Cout % 256 == 0 && blocks_a >= 200) cfg = 1;
-    else if (cfg == 2 && blocks_b >= 100 && blocks_b < 200) cfg = 3;
-    return launch_igemm_dma16(p, cfg, stream);
-  }
-  if (use_a) {
-    return dtype == UNETDC_BF16 ? launch_dma_cfg<bf16_t, 2, 4, 4>(p, stream) : launch_dma_cfg<float, 2, 4, 4>(p, stream);
-  }
-  if (use_b) {
-    return dtype == UNETDC_BF16 ? launch_dma_cfg<bf16_t, 4, 2, 2>(p, stream) : launch_dma_cfg<float, 4, 2, 2>(p, stream);
-  }
+// cfg (plan_igemm): 1 = 256x256, 2 = 256x128, 3 = 256x64
+int launch_igemm_dma(IgemmParams& p, int cfg, int dtype, hipStream_t stream) {
+  if (cfg == 1) return dtype == UNETDC_BF16 ? launch_dma_cfg<bf16_t, 2, 4, 4>(p, stream) : launch_dma_cfg<float, 2, 4, 4>(p, stream);
+  if (cfg == 2) return dtype == UNETDC_BF16 ? launch_dma_cfg<bf16_t, 4, 2, 2>(p, stream) : launch_dma_cfg<float, 4, 2, 2>(p, stream);
   return dtype == UNETDC_BF16 ? launch_dma_cfg<bf16_t, 4, 1, 2>(p, stream) : launch_dma_cfg<float, 4, 1, 2>(p, stream);
 }
 

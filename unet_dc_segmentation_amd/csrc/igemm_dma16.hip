@@ -306,14 +306,7 @@ static int launch_dma16_cfg(IgemmParams& p, hipStream_t stream) {
   return check_launch("igemm_dma16_kernel");
 }
 
-bool igemm_dma16_supported(const IgemmParams& p, int dtype) {
-  if (dtype != UNETDC_BF16) return false;
-  if (p.M % 16 != 0) return false;
-  if (p.mode == MODE_SHUFFLE && p.Wo % 16 != 0) return false;
-  return true;
-}
-
-// cfg: 1 = 256x256 (8 waves), 2 = 256x128 (8 waves), 3 = 256x64 (4 waves) -- chosen by launch_igemm_dma
+// cfg: 1 = 256x256 (8 waves), 2 = 256x128 (8 waves), 3 = 256x64 (4 waves) -- chosen by plan_igemm
 int launch_igemm_dma16(IgemmParams& p, int cfg, hipStream_t stream) {
   // ring depth per tile (settled in round 3, profiles/r03_dma16_tile_configs.txt): three stages where they fit
   if (cfg == 1) return launch_dma16_cfg<2, 4, 8, 2>(p, stream);              // 3 x 64 KB does not fit

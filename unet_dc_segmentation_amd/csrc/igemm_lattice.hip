@@ -945,17 +945,6 @@ bool igemm_lattice_supported(const IgemmParams& p, int dtype) {
   return xbytes < (1L << 31) && wbytes < (1L << 31) && obytes < (1L << 32) && ybytes < (1L << 32);
 }
 
-// input normalisation on load: the statistics forward of the 4-wave forms (64-channel n-blocks: constants in LDS, Cin <= 256;
-// 128-channel n-blocks: constants through the scalar cache, any Cin)
-bool igemm_lattice_bnin_supported(const IgemmParams& p, int dtype) {
-  return igemm_lattice_supported(p, dtype) && p.mode == MODE_STATS && (p.Cout % 128 == 0 || p.Cin <= 256);
-}
-
-// the wide form can also store the normalised activation (IgemmParams::act_out)
-bool igemm_lattice_bnin_writes_activation(const IgemmParams& p, int dtype) {
-  return igemm_lattice_bnin_supported(p, dtype) && p.Cout % 128 == 0 && (long)p.M * p.Cin * 2 < (1L << 32);
-}
-
 static long lattice_grid(long items, int wgs_per_cu) {
   const long g = 256L * wgs_per_cu;
   return g > items ? items : g;
@@ -1041,7 +1030,7 @@ int launch_igemm_lattice(IgemmParams& p, hipStream_t stream) {
     return launch_lattice_wide_cfg<MODE_AFFINE_RELU>(p, q, stream);
   }
   if (wide) return launch_lattice_cfg<4, 2, 4, 2, MODE_STORE>(p, q, 1, stream);   // (wide && !ww: the plain-store mode only)
-  if (p.in_scale) return launch_lattice_cfg<4, 1, 4, 1, MODE_STATS, true>(p, q, 2, stream);      // igemm_lattice_bnin_supported
+  if (p.in_scale) return launch_lattice_cfg<4, 1, 4, 1, MODE_STATS, true>(p, q, 2, stream);      // Cin <= 256 (plan_igemm)
   return launch_lattice_mode<4, 1, 4, 1>(p, q, 2, stream);
 }
 

@@ -38,13 +38,28 @@ struct IgemmParams {
   int offy[9];
   int offx[9];
 };
+// The kernel family of an implicit-GEMM call, decided once by plan_igemm (igemm_conv.hip).
+enum IgemmRoute {
+  IGEMM_UNSUPPORTED = 0,  // input normalisation asked for a shape the lattice kernel does not take
+  IGEMM_LATTICE,          // igemm_lattice.hip: persistent lattice-halo conv (bf16), the only one with input normalisation
+  IGEMM_HALO,             // igemm_halo.hip: LDS-staged input patch shared by all 9 taps (narrow layers, d <= 2)
+  IGEMM_DMA,              // igemm_dma.hip: second generation, tensors < 2 GiB
+  IGEMM_DMA16,            // igemm_dma16.hip: the same on the 16x16x32 bf16 MFMA shape
+  IGEMM_FIRSTGEN,         // igemm_conv.hip: any size; no fused BatchNorm-backward sums
+};
+struct IgemmPlan {
+  int route;
+  int cfg;          // DMA / DMA16 tile: 1 = 256x256, 2 = 256x128, 3 = 256x64; first generation: 1 = 128x128, 0 = 256x64
+  bool writes_act;  // input normalisation: the form can also store the normalised activation (IgemmParams::act_out)
+};
+IgemmPlan plan_igemm(const IgemmParams& p, int dtype);
 int launch_igemm(IgemmParams& p, int dtype, hipStream_t stream);
 int igemm_mblocks(long M, int Cout);
-bool igemm_lattice_supported(const IgemmParams& p, int dtype);      // igemm_lattice.hip: persistent lattice-halo conv (bf16)
+bool igemm_lattice_supported(const IgemmParams& p, int dtype);
+bool igemm_halo_supported(const IgemmParams& p, int dtype);
 int launch_igemm_lattice(IgemmParams& p, hipStream_t stream);
-bool igemm_lattice_bnin_supported(const IgemmParams& p, int dtype);  // x = raw conv output, BatchNorm + ReLU applied per staged patch
-bool igemm_lattice_bnin_writes_activation(const IgemmParams& p, int dtype);   // ... and that form can store the normalised activation
-bool igemm_dma16_supported(const IgemmParams& p, int dtype);
+int launch_igemm_halo(IgemmParams& p, int dtype, hipStream_t stream);
+int launch_igemm_dma(IgemmParams& p, int cfg, int dtype, hipStream_t stream);
 int launch_igemm_dma16(IgemmParams& p, int cfg, hipStream_t stream);
 
 struct WgradParams {
@@ -61,16 +76,36 @@ struct WgradParams {
   const float* in_scale;   // "bnin": b (the conv input) is the RAW output of the producing stage, normalised on load
   const float* in_shift;
 };
+// The kernel of a weight gradient and its sizing, decided once by plan_wgrad (wgrad.hip).
+enum WgradRoute {
+  WGRAD_UNSUPPORTED = 0,  // input normalisation asked for a shape the tap-split ring kernel does not take
+  WGRAD_CONVT,            // convt_wgrad.hip: tap-fused ConvTranspose2d(2, 2) (bf16), X staged once for the four taps
+  WGRAD_RECT,             // wgrad_rect.hip: valid-rectangle kernel for strongly dilated 3x3 layers (bf16)
+  WGRAD_FUSED,            // wgrad_fused.hip: tap-fused ring / tap-split kernels for narrow 3x3 layers
+  WGRAD_DMA,              // wgrad_dma.hip: K split over the pixels, second generation (operands < 2 GiB)
+  WGRAD_LEGACY,           // wgrad.hip: K split over the pixels, first generation
+};
+struct WgradPlan {
+  int route;
+  int ksplit;           // K split (DMA / legacy / ConvT): slabs to reduce; rect: K units of all taps
+  int chunk, tw, step;  // DMA / legacy: pixels per K slice, tile width in 64-channel units, pixel step of a block
+  int steps_per_half;   // ConvT
+  long workspace;       // bytes of partial slabs the route needs
+};
+WgradPlan plan_wgrad(const WgradParams& p, int dtype);
+long wgrad_workspace_bound(int N, int H, int W, int CI, int CJ, int ntaps, int dtype);
 int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_bytes, int dtype, hipStream_t stream);
-bool wgrad_bnin_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int dtype);
-long wgrad_workspace_bytes(long P, int CI, int CJ, int ntaps, int dtype);
+bool convt_wgrad_split(int N, int H, int W, int CI, int CJ, int& ksplit, int& steps_per_half);
+int launch_convt_wgrad_fused(const WgradParams& w, const WgradPlan& pl, hipStream_t stream);
+int wgrad_rect_units(int N, int H, int W, int CI, int CJ, int d);
+int launch_wgrad_rect(const WgradParams& w, const WgradPlan& pl, float* out, hipStream_t stream);
+bool wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride, int dtype);
+bool wgrad_fused_bnin_supported(int d, int dtype);
 long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype);
-long wgrad_rect_workspace_bytes(int N, int H, int W, int CI, int CJ, int d);
-// convt_wgrad.hip: tap-fused ConvTranspose2d weight gradient (bf16): X staged once for the four taps
-bool convt_wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int ldx, int lddy, int dtype);
-long convt_wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ);
-int launch_convt_wgrad_fused(const void* x, int ldx, const void* dy, int lddy, float* part, int N, int H, int W, int CI, int CJ,
-                             int* units_out, hipStream_t stream);
+int launch_wgrad_fused(const WgradParams& w, int dtype, int* units_out, hipStream_t stream);
+int wgrad_dma_tile(int CI, int CJ);
+int wgrad_dma_pixel_step(int dtype, int tw);
+int launch_wgrad_dma_kernel(WgradParams& p, int tw, int dtype, hipStream_t stream);
 
 struct FirstParams {
   const float* x;        // [N][Cin][H][W] fp32
@@ -93,17 +128,24 @@ struct FirstWgradParams {
   const void* bn_y; int bn_ldy;
   const float* bn_scale; const float* bn_shift; const float* bn_mean; const float* bn_rstd; const float* bn_k;   // bn_k: [3][Cout]
 };
+// The first layer's kernels and grids, decided once by plan_first (first_conv.hip).
+struct FirstPlan {
+  bool mfma;          // forward on the matrix cores (first_conv_mfma.hip), else the VALU kernel
+  int fwd_blocks;     // forward grid = rows of partial statistics
+  bool wgrad_mfma;    // weight gradient on the matrix cores, else a VALU kernel
+  int wgrad_blocks;   // grid of the MFMA / general VALU weight-gradient kernel
+  int rows_blocks;    // grid of the VALU row-run kernel (0 with the MFMA kernel)
+  long workspace;     // bytes of partial slabs that cover the weight-gradient kernel a launch can pick
+};
+FirstPlan plan_first(long P, int Cin, int Cout);
 int launch_first_fwd(FirstParams& p, int dtype, hipStream_t stream);
 bool first_wgrad_bn_supported(int N, int H, int W, int Cin, int Cout, int dil, int dtype);
 int launch_bn_bwd_coeffs(const float* pre_parts, int pre_nparts, long count, const float* gamma, const float* rstd, float* dgamma,
                          float* dbeta, float* dbias, float* coeffs, int C, hipStream_t stream);
-int first_conv_mblocks(long P, int Cin, int Cout);
-bool first_mfma_supported(long P, int Cin, int Cout);
 int first_mfma_mblocks(long P);
-int launch_first_mfma_fwd(FirstParams& p, int dtype, hipStream_t stream);
-long first_mfma_wgrad_workspace_bytes(long P, int Cin, int Cout);
-int launch_first_mfma_wgrad(FirstWgradParams& p, int* nblk_out, int dtype, hipStream_t stream);
-long first_wgrad_workspace_bytes(long P, int Cin, int Cout);
+int first_mfma_wgrad_blocks(long P);
+int launch_first_mfma_fwd(FirstParams& p, int blocks, int dtype, hipStream_t stream);
+int launch_first_mfma_wgrad(FirstWgradParams& p, int blocks, int dtype, hipStream_t stream);
 int launch_first_wgrad(FirstWgradParams& p, float* dw, void* workspace, long workspace_bytes, int dtype,
                        hipStream_t stream);
 int launch_first_dgrad(const void* dy, int lddy, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, int dil,

@@ -224,25 +224,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// second-generation (LDS-DMA) kernel, wgrad_dma.hip
-int wgrad_dma_tile(int CI, int CJ);
-int wgrad_dma_pixel_step(int dtype, int tw);
-bool wgrad_dma_supported(const WgradParams& p, int dtype);
-int launch_wgrad_dma_kernel(WgradParams& p, int tw, int dtype, hipStream_t stream);
-// tap-fused kernel for narrow 3x3 layers, wgrad_fused.hip
-bool wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride,
-                           int dtype);
-long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype);
-int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* part, int N, int H, int W, int CI,
-                       int CJ, int d, int dtype, int* units_out, hipStream_t stream, const float* in_scale = nullptr,
-                       const float* in_shift = nullptr);
-
-// valid-rectangle kernel for strongly dilated layers, wgrad_rect.hip
-bool wgrad_rect_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride, int dtype);
-int launch_wgrad_rect(const void* dy, int lddy, const void* x, int ldx, float* out, void* workspace, long workspace_bytes,
-                      int N, int H, int W, int CI, int CJ, int d, hipStream_t stream);
-
 static int pixel_step(int dtype, bool wide) {
   const int rb = (wide ? 2 : 1) * 64 * (dtype == UNETDC_BF16 ? 2 : 4);
   return 16384 / rb;
@@ -285,13 +266,6 @@ static void plan_dma(long P, int CI, int CJ, int ntaps, int dtype, int& ksplit, 
        2.0 * P * CI * CJ * ntaps, ksplit, chunk);
 }
 
-long wgrad_workspace_bytes(long P, int CI, int CJ, int ntaps, int dtype) {
-  int k1, c1, k2, c2;
-  plan_legacy(P, CI, CJ, ntaps, dtype, k1, c1);
-  plan_dma(P, CI, CJ, ntaps, dtype, k2, c2);
-  return (long)(k1 > k2 ? k1 : k2) * ntaps * CI * CJ * 4;
-}
-
 template <typename T, int TW>
 static int launch_w(WgradParams& p, hipStream_t stream) {
   if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_kernel<T, TW>), 65536, "wgrad_kernel")) return rc_;
@@ -301,6 +275,74 @@ static int launch_w(WgradParams& p, hipStream_t stream) {
   snprintf(nm, sizeof(nm), "wgrad_kernel<%s, %d>", sizeof(T) == 2 ? "__bf16" : "float", TW);
   note_kernel(nm);
   return check_launch("wgrad_kernel");
+}
+
+// The one place that decides which kernel takes a weight gradient, and how it is sized: launch_wgrad and the C-ABI
+// queries read it.
+WgradPlan plan_wgrad(const WgradParams& p, int dtype) {
+  WgradPlan pl{};
+  const long P = (long)p.N * p.H * p.W;
+  const int d = p.offy[8];
+  const bool bf16 = dtype == UNETDC_BF16, same = p.Hb == p.H && p.Wb == p.W;
+  const bool fused = same && wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, d, p.ntaps, p.stride, dtype);
+  auto plan_fused = [&]() {
+    pl.route = WGRAD_FUSED;
+    pl.workspace = wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ, dtype);
+    return pl;
+  };
+  if (p.in_scale) {               // input normalisation on load: the tap-split ring kernel only
+    if (fused && wgrad_fused_bnin_supported(d, dtype)) return plan_fused();
+    return pl;
+  }
+  // ConvTranspose2d(2, 2): one GEMM [Cin] x [4 Cout] with the input staged once for the four taps (convt_wgrad.hip)
+  if (bf16 && p.ntaps == 4 && p.stride == 2 && p.Hb == 2 * p.H && p.Wb == 2 * p.W && p.offy[3] == 1 && p.offx[3] == 1 &&
+      convt_wgrad_split(p.N, p.H, p.W, p.CI, p.CJ, pl.ksplit, pl.steps_per_half) && P * p.lda * 2 < (1L << 32) &&
+      4 * P * p.ldb * 2 < (1L << 32) && p.lda % 8 == 0 && p.ldb % 8 == 0) {
+    pl.route = WGRAD_CONVT;
+    pl.workspace = (long)pl.ksplit * 4 * p.CI * p.CJ * 4;
+    return pl;
+  }
+  // valid-rectangle kernel for strongly dilated layers (wgrad_rect.hip)
+  if (same && bf16 && p.ntaps == 9 && p.stride == 1 && p.CI % 256 == 0 && p.CJ % 256 == 0 && d >= 1 &&
+      P * p.lda * 2 < (1L << 31) && P * p.ldb * 2 < (1L << 31)) {
+    pl.ksplit = wgrad_rect_units(p.N, p.H, p.W, p.CI, p.CJ, d);
+    if (pl.ksplit > 0) {
+      pl.route = WGRAD_RECT;
+      pl.workspace = (long)pl.ksplit * p.CI * p.CJ * 4;
+      return pl;
+    }
+  }
+  if (fused) return plan_fused();     // tap-fused kernel for narrow 3x3 layers (wgrad_fused.hip)
+  // K-split over the pixels: the second-generation (LDS-DMA) kernel while the operands are < 2 GiB (wgrad_dma.hip)
+  const long es = bf16 ? 2 : 4;
+  const bool dma = P * p.lda * es < (1L << 31) && (long)p.N * p.Hb * p.Wb * p.ldb * es < (1L << 31);
+  pl.route = dma ? WGRAD_DMA : WGRAD_LEGACY;
+  pl.tw = dma ? wgrad_dma_tile(p.CI, p.CJ) : (wgrad_wide(p.CI, p.CJ) ? 2 : 1);
+  pl.step = dma ? wgrad_dma_pixel_step(dtype, pl.tw) : pixel_step(dtype, pl.tw == 2);
+  if (dma) plan_dma(P, p.CI, p.CJ, p.ntaps, dtype, pl.ksplit, pl.chunk);
+  else plan_legacy(P, p.CI, p.CJ, p.ntaps, dtype, pl.ksplit, pl.chunk);
+  pl.workspace = (long)pl.ksplit * p.ntaps * p.CI * p.CJ * 4;
+  return pl;
+}
+
+// Workspace that covers every route plan_wgrad can pick for a weight gradient of this geometry, whatever the leading
+// dimensions and -- for ntaps = 9 -- the dilation (the C-ABI workspace queries do not get them).
+long wgrad_workspace_bound(int N, int H, int W, int CI, int CJ, int ntaps, int dtype) {
+  const long P = (long)N * H * W;
+  int k1, c1, k2, c2;
+  plan_legacy(P, CI, CJ, ntaps, dtype, k1, c1);
+  plan_dma(P, CI, CJ, ntaps, dtype, k2, c2);
+  long b = (long)(k1 > k2 ? k1 : k2) * ntaps * CI * CJ * 4;
+  auto cover = [&b](long v) { if (v > b) b = v; };
+  if (ntaps == 4) {
+    int ks, sh;
+    if (convt_wgrad_split(N, H, W, CI, CJ, ks, sh)) cover((long)ks * 4 * CI * CJ * 4);
+    return b;
+  }
+  cover(wgrad_fused_workspace_bytes(N, H, W, CI, CJ, dtype));
+  if (CI % 256 == 0 && CJ % 256 == 0)
+    for (int d = 1; d <= 64; d *= 2) cover((long)wgrad_rect_units(N, H, W, CI, CJ, d) * CI * CJ * 4);
+  return b;
 }
 
 // Generic driver: fills partial slabs in `workspace` and reduces them into `out`.
@@ -314,75 +356,34 @@ int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_byt
   const long P = (long)p.N * p.H * p.W;
   UNETDC_REQUIRE(P > 0 && P < (1L << 31) - 4096, "wgrad: pixel count out of range");
   p.P = (int)P;
-  if (p.in_scale) {                               // input normalisation on load: the tap-split ring kernel only (caller asked wgrad_bnin_supported)
-    UNETDC_REQUIRE(p.in_shift && p.Hb == p.H && p.Wb == p.W && p.ntaps == 9 && p.stride == 1 &&
-                       wgrad_bnin_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], dtype),
-                   "wgrad (bnin): shape not supported by the input-normalising kernel");
-  }
-  if (!p.in_scale && p.ntaps == 4 && p.stride == 2 && p.Hb == 2 * p.H && p.Wb == 2 * p.W &&
-      p.offy[3] == 1 && p.offx[3] == 1 && convt_wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, dtype)) {
-    // ConvTranspose2d(2, 2): one GEMM [Cin] x [4 Cout] with the input staged once for the four taps (convt_wgrad.hip)
-    const long need_c = convt_wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ);
-    if (need_c > workspace_bytes) {
-      set_error("wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, need_c);
-      return UNETDC_EWORKSPACE;
-    }
-    int units = 0;
-    int rc = launch_convt_wgrad_fused(p.a, p.lda, p.b, p.ldb, reinterpret_cast<float*>(workspace), p.N, p.H, p.W, p.CI, p.CJ,
-                                      &units, stream);
-    if (rc != UNETDC_OK) return rc;
-    const long n = (long)p.CI * p.CJ * 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, stream,
-                       reinterpret_cast<float*>(workspace), out, units, 4, p.CI, p.CJ);
-    return check_launch("wgrad_reduce_kernel");
-  }
-  if (!p.in_scale && p.Hb == p.H && p.Wb == p.W &&
-      wgrad_rect_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], p.ntaps, p.stride, dtype))
-    return launch_wgrad_rect(p.a, p.lda, p.b, p.ldb, out, workspace, workspace_bytes, p.N, p.H, p.W, p.CI, p.CJ, p.offy[8],
-                             stream);
-  if (p.Hb == p.H && p.Wb == p.W &&
-      wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, p.offy[8], p.ntaps, p.stride, dtype)) {
-    const long need_f = wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ, dtype);
-    if (need_f > workspace_bytes) {
-      set_error("wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, need_f);
-      return UNETDC_EWORKSPACE;
-    }
-    int units = 0;
-    int rc = launch_wgrad_fused(p.a, p.lda, p.b, p.ldb, reinterpret_cast<float*>(workspace), p.N, p.H, p.W, p.CI,
-                                p.CJ, p.offy[8], dtype, &units, stream, p.in_scale, p.in_shift);
-    if (rc != UNETDC_OK) return rc;
-    const long n = (long)p.CI * p.CJ * p.ntaps;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, stream,
-                       reinterpret_cast<float*>(workspace), out, units, p.ntaps, p.CI, p.CJ);
-    return check_launch("wgrad_reduce_kernel");
-  }
-  const bool dma = wgrad_dma_supported(p, dtype);
-  const bool wide = wgrad_wide(p.CI, p.CJ);
-  const int tw = dma ? wgrad_dma_tile(p.CI, p.CJ) : (wide ? 2 : 1);
-  if (dma) plan_dma(P, p.CI, p.CJ, p.ntaps, dtype, p.ksplit, p.chunk);
-  else plan_legacy(P, p.CI, p.CJ, p.ntaps, dtype, p.ksplit, p.chunk);
-  const long need = (long)p.ksplit * p.ntaps * p.CI * p.CJ * 4;
-  if (need > workspace_bytes) {
-    set_error("wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, need);
+  const WgradPlan pl = plan_wgrad(p, dtype);
+  UNETDC_REQUIRE(!p.in_scale || (p.in_shift && pl.route == WGRAD_FUSED),
+                 "wgrad (bnin): shape not supported by the input-normalising kernel");
+  if (pl.workspace > workspace_bytes) {
+    set_error("wgrad: workspace too small (%ld < %ld bytes)", workspace_bytes, pl.workspace);
     return UNETDC_EWORKSPACE;
   }
   p.part = reinterpret_cast<float*>(workspace);
-  p.itiles = p.CI / (tw * 64);
-  p.jtiles = p.CJ / (tw * 64);
-  const int step = dma ? wgrad_dma_pixel_step(dtype, tw) : pixel_step(dtype, wide);
-  p.adv_y = step / p.W;
-  p.adv_x = step % p.W;
-  int rc;
-  if (dma)
-    rc = launch_wgrad_dma_kernel(p, tw, dtype, stream);
-  else if (dtype == UNETDC_BF16)
-    rc = wide ? launch_w<bf16_t, 2>(p, stream) : launch_w<bf16_t, 1>(p, stream);
-  else
-    rc = wide ? launch_w<float, 2>(p, stream) : launch_w<float, 1>(p, stream);
+  int slabs = pl.ksplit, rc;
+  switch (pl.route) {
+    case WGRAD_CONVT: rc = launch_convt_wgrad_fused(p, pl, stream); break;
+    case WGRAD_RECT: return launch_wgrad_rect(p, pl, out, stream);        // reduces the units of every tap itself
+    case WGRAD_FUSED: rc = launch_wgrad_fused(p, dtype, &slabs, stream); break;
+    default:
+      p.ksplit = pl.ksplit;
+      p.chunk = pl.chunk;
+      p.itiles = p.CI / (pl.tw * 64);
+      p.jtiles = p.CJ / (pl.tw * 64);
+      p.adv_y = pl.step / p.W;
+      p.adv_x = pl.step % p.W;
+      if (pl.route == WGRAD_DMA) rc = launch_wgrad_dma_kernel(p, pl.tw, dtype, stream);
+      else if (dtype == UNETDC_BF16) rc = pl.tw == 2 ? launch_w<bf16_t, 2>(p, stream) : launch_w<bf16_t, 1>(p, stream);
+      else rc = pl.tw == 2 ? launch_w<float, 2>(p, stream) : launch_w<float, 1>(p, stream);
+  }
   if (rc != UNETDC_OK) return rc;
   const long n = (long)p.CI * p.CJ * p.ntaps;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, stream, p.part, out,
-                     p.ksplit, p.ntaps, p.CI, p.CJ);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 63) / 64)), dim3(256), 0, stream, p.part, out, slabs,
+                     p.ntaps, p.CI, p.CJ);
   return check_launch("wgrad_reduce_kernel");
 }
 

@@ -169,12 +169,6 @@ int wgrad_dma_pixel_step(int dtype, int tw) {
   return (tw == 4 ? 32768 : 16384) / rb;
 }
 
-bool wgrad_dma_supported(const WgradParams& p, int dtype) {
-  const long es = dtype == UNETDC_BF16 ? 2 : 4;
-  const long P = (long)p.N * p.H * p.W;
-  return P * p.lda * es < (1L << 31) && (long)p.N * p.Hb * p.Wb * p.ldb * es < (1L << 31);
-}
-
 template <typename T, int TW>
 static int launch_wd(WgradParams& p, hipStream_t stream) {
   constexpr int LDS = (TW == 4) ? 131072 : 65536;

@@ -912,18 +912,16 @@ long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype)
   return (long)N * (W / fused_seg(dtype)) * ys * 9 * CI * CJ * 4;
 }
 
-// Fills the slabs; the caller reduces `units` slabs with wgrad_reduce_kernel.
-bool wgrad_bnin_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int dtype) {
-  return dtype == UNETDC_BF16 && wgrad_fused_supported(N, H, W, CI, CJ, lda, ldb, d, 9, 1, dtype) &&
-         ring_pf(d, dtype) > 0;
-}
+// the input-normalising form (on top of wgrad_fused_supported): the 16x16x32 tap-split ring kernel only
+bool wgrad_fused_bnin_supported(int d, int dtype) { return dtype == UNETDC_BF16 && ring_pf(d, dtype) > 0; }
 
-int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* part, int N, int H, int W, int CI,
-                       int CJ, int d, int dtype, int* units_out, hipStream_t stream, const float* in_scale,
-                       const float* in_shift) {
+// Fills the slabs (dy = w.a, x = w.b); the caller reduces `units` slabs with wgrad_reduce_kernel.
+int launch_wgrad_fused(const WgradParams& w, int dtype, int* units_out, hipStream_t stream) {
+  const int N = w.N, H = w.H, W = w.W, CI = w.CI, CJ = w.CJ, d = w.offy[8];
+  const float* in_scale = w.in_scale;
   WgradFusedParams p{};
-  p.dy = dy; p.x = x; p.part = part; p.N = N; p.H = H; p.W = W; p.CI = CI; p.CJ = CJ; p.lddy = lddy; p.ldx = ldx;
-  p.d = d; p.in_scale = in_scale; p.in_shift = in_shift;
+  p.dy = w.a; p.x = w.b; p.part = w.part; p.N = N; p.H = H; p.W = W; p.CI = CI; p.CJ = CJ; p.lddy = w.lda; p.ldx = w.ldb;
+  p.d = d; p.in_scale = in_scale; p.in_shift = w.in_shift;
   fused_plan(N, H, W, CI, CJ, dtype, p.ysplit, p.rows_per_unit);
   p.itiles = CI / 64;
   p.jtiles = CJ / 64;
@@ -933,10 +931,6 @@ int launch_wgrad_fused(const void* dy, int lddy, const void* x, int ldx, float* 
   const int pf = ring_pf(d, dtype);
   // (the tap-split kernels run on v_mfma_f32_16x16x32_bf16: settled in round 3, profiles/r03_wgrad_m16_ab.txt; the 32x32x16
   //  instantiations are no longer built)
-  if (in_scale && !(pf && dtype == UNETDC_BF16)) {
-    set_error("wgrad (bnin): the input-normalising form exists for the 16x16x32 tap-split ring kernel only");
-    return UNETDC_EUNSUPPORTED;
-  }
   // PAIRED FORM (round 4): 512-thread workgroups whose two halves walk the two halves of a unit's rows and meet in LDS
   // (split_finish): half as many fp32 slabs written and reduced.  The plan is the one above at a target of 256 workgroups
   // (one per CU: the two rings fill the LDS), i.e. every half does exactly the work a 256-thread workgroup did.

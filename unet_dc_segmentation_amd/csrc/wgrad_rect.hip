@@ -194,34 +194,20 @@ static int rect_plan(int N, int H, int W, int d, int tiles, WgradRectParams* out
   return nu;
 }
 
-bool wgrad_rect_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride, int dtype) {
-  if (dtype != UNETDC_BF16 || ntaps != 9 || stride != 1) return false;
-  if (CI % 256 != 0 || CJ % 256 != 0 || d < 1) return false;
-  const long P = (long)N * H * W;
-  if (P * lda * 2 >= (1L << 31) || P * ldb * 2 >= (1L << 31)) return false;
-  return rect_plan(N, H, W, d, (CI / 256) * (CJ / 256), nullptr) > 0;
+// K units of the kernel at dilation d (plan_wgrad), 0 when it does not take the shape
+int wgrad_rect_units(int N, int H, int W, int CI, int CJ, int d) {
+  return rect_plan(N, H, W, d, (CI / 256) * (CJ / 256), nullptr);
 }
 
-long wgrad_rect_workspace_bytes(int N, int H, int W, int CI, int CJ, int d) {
-  if (CI % 256 != 0 || CJ % 256 != 0) return 0;
-  const int nu = rect_plan(N, H, W, d, (CI / 256) * (CJ / 256), nullptr);
-  return (long)nu * CI * CJ * 4;
-}
-
-int launch_wgrad_rect(const void* dy, int lddy, const void* x, int ldx, float* out, void* workspace, long workspace_bytes,
-                      int N, int H, int W, int CI, int CJ, int d, hipStream_t stream) {
+// Writes the pl.ksplit unit slabs into w.part and reduces them per tap into `out`.
+int launch_wgrad_rect(const WgradParams& w, const WgradPlan& pl, float* out, hipStream_t stream) {
   WgradRectParams p{};
-  p.dy = dy; p.x = x; p.part = reinterpret_cast<float*>(workspace);
-  p.N = N; p.H = H; p.W = W; p.CI = CI; p.CJ = CJ; p.lddy = lddy; p.ldx = ldx; p.d = d;
-  p.itiles = CI / 256; p.jtiles = CJ / 256;
+  p.dy = w.a; p.x = w.b; p.part = w.part;
+  p.N = w.N; p.H = w.H; p.W = w.W; p.CI = w.CI; p.CJ = w.CJ; p.lddy = w.lda; p.ldx = w.ldb; p.d = w.offy[8];
+  p.itiles = p.CI / 256; p.jtiles = p.CJ / 256;
   int utap[RECT_MAXU];
-  const int nu = rect_plan(N, H, W, d, p.itiles * p.jtiles, &p, utap);
-  UNETDC_REQUIRE(nu > 0, "wgrad_rect: unsupported geometry");
-  const long need = (long)nu * CI * CJ * 4;
-  if (need > workspace_bytes) {
-    set_error("wgrad_rect: workspace too small (%ld < %ld bytes)", workspace_bytes, need);
-    return UNETDC_EWORKSPACE;
-  }
+  const int nu = rect_plan(p.N, p.H, p.W, p.d, p.itiles * p.jtiles, &p, utap);
+  UNETDC_REQUIRE(nu == pl.ksplit, "wgrad_rect: unit count %d differs from the plan's %d", nu, pl.ksplit);
   if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_rect_kernel), 131072, "wgrad_rect_kernel")) return rc_;
   const long nwg = (long)nu * p.itiles * p.jtiles;
   hipLaunchKernelGGL(wgrad_rect_kernel, dim3((unsigned)nwg), dim3(512), 131072, stream, p);
@@ -234,7 +220,7 @@ int launch_wgrad_rect(const void* dy, int lddy, const void* x, int ldx, float* o
   for (int u = 0; u < nu; ++u)
     while (tcur < utap[u]) rp.ufirst[++tcur] = u;
   while (tcur < 9) rp.ufirst[++tcur] = nu;
-  const long n = (long)CI * CJ;
+  const long n = (long)p.CI * p.CJ;
   hipLaunchKernelGGL(wgrad_rect_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream, p.part, out, rp, n);
   return check_launch("wgrad_rect_reduce_kernel");
 }
