@@ -3,7 +3,7 @@
 backward, plus the Adam step and -- for N > 1 -- the RCCL gradient all-reduce), 512x512x1,
 batch 8 per GPU, bf16 storage / fp32 accumulate (BASELINE.json metric, configs[2]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With ``--gpus N`` (N > 1) and no torchrun environment, bench.py launches its own N ranks: the parent -- before any
@@ -11,14 +11,19 @@ HIP call -- checks that N devices exist (else it exits non-zero: it never report
 one), starts N child processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, relays rank 0's JSON line and
 fails if any rank fails.
 
-Prints ONE JSON line on rank 0.  Besides the contract fields it carries
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up, runs one initialisation
+step and the warm-up steps, times the steps, writes --dump-outputs and prints the line (contract fields, per-step
+times, final loss).  With ``--full`` it goes on to measure, each after the timed region,
   roofline     -- the dominant kernel (bf16 implicit-GEMM conv): algorithmic dense FLOPs per launch /
                   average launch time measured live with HIP events on the launch stream over the
                   timed steps, against the 2.5 PFLOP/s dense bf16 MFMA peak;
   hbm_leg      -- the HBM-bound kernels (BatchNorm passes, first layer, head): algorithmic bytes / launch time from a
                   short HIP-event-instrumented pass after the timed region, against the 8 TB/s HBM peak;
+  collective   -- (N > 1 or UNETDC_DP_FORCE=1) the all-reduce timeline of 3 traced steps;
+  secondary    -- the other single-GPU BASELINE configurations (N = 1 training), each with its own timed region;
   cpu_baseline -- the CPU port of the reference path (oracle/unetdc_torch_cpu.py, the same ATen ops
-                  the reference calls) timed on this host's cores on a bounded sample (N = 1 only): median of 3 steps.
+                  the reference calls) timed on this host's cores on a bounded sample (N = 1 only): median of 3 steps
+                  (--mode quantify: the script's own CPU path on 2 images).
 Everything inside the timed region is real work: no step is skipped, the optimizer step and the
 weight re-packing it triggers are included; the reference loop's per-step .item()/.cpu() syncs
 (train_DC_focal.py:257-269) are not part of the metric and are excluded.
@@ -413,7 +418,7 @@ def quantify_bench(args, real_stdout):
            "droplets_per_image": float(np.mean([len(t) for t in tabs]))}
     if dumped is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         ncpu = 2
         cores = host_cores()
         torch.set_num_threads(cores)
@@ -756,10 +761,14 @@ def main():
     ap.add_argument("--in-channels", type=int, default=1)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--arch", default="unetdc", choices=["unetdc", "unet"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-kernel roofline and HBM legs, the collective timeline, the "
+                         "other single-GPU BASELINE configurations and the CPU baseline (each in runs of its own after the "
+                         "timed region); a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the other single-GPU BASELINE configurations (fp32 inference, 1024x1024 bs 4, fp32 training) "
-                         "that the default N = 1 training run measures after the headline")
+                    help="with --full: skip the other single-GPU BASELINE configurations (fp32 inference, 1024x1024 bs 4, "
+                         "fp32 training) that an N = 1 training run measures after the headline")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--adam", choices=["hip", "fused", "foreach"], default="hip",
                     help="hip = this repo's one-kernel Adam + weight re-pack (default); fused / foreach = torch.optim.Adam")
@@ -840,16 +849,17 @@ def main():
                  "step_ms_max_across_ranks": float(per[:, 2].max())}
     final_loss = float(loss.item())
     dumped = write_outputs(args.dump_outputs, job.outputs(loss)) if args.dump_outputs and rank == 0 else None
-    # ---- instrumented passes, all AFTER the timed region (every rank runs them: the collectives need all ranks) ----
-    roofline = igemm_leg(step, args.dtype, args.mode, nsteps=3, headline=(args.mode == "train" and args.dtype == "bf16"))
-    hbm = hbm_leg(step, 2 if args.dtype == "bf16" else 4) if args.mode == "train" else None
-    coll = None
-    if wrapper is not None and args.mode == "train":
-        wrapper.start_trace()
-        for _ in range(3):
-            wrapper.mark_step_start()
-            step()
-        coll = wrapper.stop_trace()
+    # ---- --full: instrumented passes, all AFTER the timed region (every rank runs them: the collectives need all ranks) ----
+    roofline = hbm = coll = None
+    if args.full:
+        roofline = igemm_leg(step, args.dtype, args.mode, nsteps=3, headline=(args.mode == "train" and args.dtype == "bf16"))
+        hbm = hbm_leg(step, 2 if args.dtype == "bf16" else 4) if args.mode == "train" else None
+        if wrapper is not None and args.mode == "train":
+            wrapper.start_trace()
+            for _ in range(3):
+                wrapper.mark_step_start()
+                step()
+            coll = wrapper.stop_trace()
 
     if rank == 0:
         nominal_gflop_img = NOMINAL_GFLOP_IMG.get((args.mode, args.size)) if args.in_channels == 1 else None
@@ -866,11 +876,11 @@ def main():
                        "global_batch": args.batch * world, "parallelism": f"dp{world}", "init_steps_before_warmup": 1,
                        "timed_region": "zero_grad, model(x), focal_dice_loss, backward, all-reduce, Adam step (" + args.adam + "), weight re-pack"
                                        if args.mode == "train" else "model(x) under no_grad + threshold, input resident in HBM"},
-            "roofline": roofline,
-            "hbm_leg": hbm,
             "step_ms": step_stats,
             "final_value": final_loss,
         }
+        if args.full:
+            out["roofline"], out["hbm_leg"] = roofline, hbm
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if nominal_gflop_img:
@@ -884,7 +894,7 @@ def main():
                 out["collective"].update(coll)
         if ranks:
             out["ranks"] = ranks
-        if world == 1 and wrapper is None and args.mode == "train" and not args.no_secondary:
+        if args.full and world == 1 and wrapper is None and args.mode == "train" and not args.no_secondary:
             # the other single-GPU BASELINE configurations, each with its own timed region (<= 10 s together)
             del job, model, step
             torch.cuda.empty_cache()
@@ -893,7 +903,7 @@ def main():
                 secondary_entry(dev, "BASELINE configs[4] per GPU: 1024x1024 tiles bs 4", "train", "bf16", 4, 1024, steps=15),
                 secondary_entry(dev, "configs[2] in the parity dtype: fp32 training step", "train", "f32", 8, 512, steps=8),
             ]
-        if world == 1 and not args.no_cpu_baseline and args.mode == "train":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "train":
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.size, args.size, args.in_channels)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if dist.is_initialized():

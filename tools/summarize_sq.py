@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Summarise the rocprofv3 --pmc passes of tools/pmc_sq.sh into <dir>/summary.json (and stdout).
 
-    python tools/summarize_sq.py gpurun_out/pmc_<tag> <tag> "<op_bench args>"
+    python tools/summarize_sq.py $OUT_DIR/pmc_<tag> <tag> "<op_bench args>"
 
 Per kernel (MFMA kernels only): average counter value per dispatch, and
   mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024)
       (matrix-pipe busy cycles summed over the chip's 1024 SIMDs -- 16 per v_mfma_f32_16x16x32_bf16, 32 per
        32x32x16, MI355X_MICROARCH.md cycle constants -- over the kernel-active cycles of one XCD x 1024).
-The raw rocprofv3 output stays under gpurun_out/ (scratch); copy summary.json to profiles/ to keep it."""
+The raw rocprofv3 output stays under $OUT_DIR/ (scratch, tools/pmc_sq.sh); copy summary.json to profiles/ to keep it."""
 import collections
 import csv
 import glob
