@@ -23,9 +23,22 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 ENCODER = ("enc1", "enc2", "enc3", "enc4")
-BLOCK_ORDER = ("enc1", "enc2", "enc3", "enc4", "bottleneck", "dec4", "dec3", "dec2", "dec1")
+BLOCK_ORDER = ENCODER + ("bottleneck", "dec4", "dec3", "dec2", "dec1")
 WIDTHS = {"enc1": 64, "enc2": 128, "enc3": 256, "enc4": 512, "bottleneck": 1024,
           "dec4": 512, "dec3": 256, "dec2": 128, "dec1": 64}
+
+
+def conv_stages(in_channels, dilations):
+    """(block, index, level, C_in, C_out, dilation) of every conv3x3 stage in forward order.  Level l runs at 1/2**l of the
+    input resolution; a decoder block's first conv reads the concat of the up-convolution and the skip, 2 * C_out channels."""
+    stages, prev = [], in_channels
+    for block in BLOCK_ORDER:
+        c, d = WIDTHS[block], dilations[block]
+        level = len(ENCODER) if block == "bottleneck" else int(block[-1]) - 1
+        cin = 2 * c if block.startswith("dec") else prev
+        stages += [(block, 0, level, cin, c, d), (block, 3, level, c, c, d)]
+        prev = c
+    return stages
 
 
 def _stage_pair(cin, cout, d):
@@ -55,7 +68,7 @@ class _UNetFamily(nn.Module):
             w = WIDTHS[f"dec{lvl}"]
             setattr(self, f"upconv{lvl}", nn.ConvTranspose2d(2 * w, w, kernel_size=2, stride=2))
             setattr(self, f"dec{lvl}", _stage_pair(2 * w, w, d[f"dec{lvl}"]))
-        self.out_conv = nn.Conv2d(64, out_channels, kernel_size=1)
+        self.out_conv = nn.Conv2d(WIDTHS["dec1"], out_channels, kernel_size=1)
         # compute configuration of the HIP path (not part of the reference surface):
         #   "f32"  -- fp32 storage, exact-fp32 MFMA (parity configuration)
         #   "bf16" -- bf16 activations/weights, fp32 accumulate (throughput configuration)
@@ -120,9 +133,7 @@ class _UNetFamily(nn.Module):
             return
         self._warned_live = True
         import warnings
-        per = sum(t.numel() * t.element_size() for t in
-                  [st.y for st in eng.stages.values()] + list(eng.a0.values()) + list(eng.a3.values())
-                  + list(eng.cat.values()) + list(eng.pool.values())) / 2 ** 30
+        per = eng.saved_bytes() / 2 ** 30
         warnings.warn(f"{type(self).__name__}: {live} forwards of this module are alive at once (each keeps ~{per:.1f} GiB of "
                       f"activations for its backward; only {self.MAX_ENGINES} sets are kept for re-use).  If no backward is "
                       "meant to follow, run the forward under torch.no_grad(); otherwise call backward() (or drop the "
@@ -140,9 +151,6 @@ class _UNetFamily(nn.Module):
     def _engine(self):
         """The most recently used engine (None before the first HIP forward)."""
         return next(reversed(self._engines.values()))[-1] if self._engines else None
-
-    def dilation_of(self, block):
-        return self.DILATIONS[block]
 
     # ------------------------------------------------------------------ forward
     def forward(self, x):
