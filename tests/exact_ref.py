@@ -10,6 +10,7 @@ Layout of the references: NHWC tensors [N, H, W, C] (the kernels' activation lay
 holds (asserted before use: fp32 GEMMs are then exact and several times faster).  The references run on the device of
 their inputs: on integer data fp64 arithmetic has no rounding at all (every value and partial sum is far below 2^53), so
 the result is the same exact integer on the host or on a GPU, whatever library or summation order computes it."""
+import math
 import os
 import re
 
@@ -482,6 +483,125 @@ def sum_is_exact(terms, res):
     """Every fp32 partial sum of `terms` ([rows, C], multiples of `res`) is exact in any order: sum |terms| / res < 2^24."""
     t = terms.to(torch.float64).reshape(-1, terms.shape[-1]) / res
     return bool((t == t.round()).all()) and float(t.abs().sum(0).max()) < EXACT_LIMIT
+
+
+# ---------------------------------------------------------------------------------------------------- optimizer
+_FLUSH = 2.0 ** -126                     # absolute slack of one fp32 operation whose result is subnormal, flushed or not
+
+
+def adam_step(p, m, v, g, step, lr, beta1, beta2, eps, grad_scale=1.0):
+    """One Adam step in fp64 from the state as it was just before it (csrc/optim.hip, torch's _fused_adam_ formulation):
+    g <- grad_scale g;  m <- m + (1 - b1)(g - m);  v <- b2 v + (1 - b2) g^2;
+    p <- p - lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps).   Returns (p, m, v), fp64."""
+    p, m, v, g = (t.to(torch.float64) for t in (p, m, v, g))
+    g = g * grad_scale
+    m = m + (1 - beta1) * (g - m)
+    v = beta2 * v + (1 - beta2) * g * g
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    return p - lr / bc1 * m / (v.sqrt() / math.sqrt(bc2) + eps), m, v
+
+
+def adam_bounds(p, m, v, g, step, lr, beta1, beta2, eps, grad_scale=1.0):
+    """Per-element bounds on how far the fp32 arithmetic of csrc/optim.hip adam_update can lie from adam_step: (bp, bm, bv).
+
+    Interval arithmetic over the kernel's operation sequence; the inputs p, m, v, g are exact (the fp32 values it reads).
+      constants  gscale, omb1 = 1-b1, b2, omb2 = 1-b2, eps, step_size = lr/bc1, inv_bc2_sqrt = 1/sqrt(bc2): formed in
+                 double, rounded to fp32 once -> each one in c (1 +- E)            (E = 2^-24; double errors are < 2^-50)
+      g' = g * gscale                  one rounding (none when grad_scale == 1: the product is exact)
+      m' = fmaf(omb1, g' - m, m)       g' - m rounded, then ONE rounding of the fused result
+      v' = fmaf(v, b2, omb2 g' g')     (omb2 g') g' two roundings, then ONE rounding of the fused result; v' >= 0
+      s  = sqrtf(v')                   correctly rounded by default for HIP; 2E allowed
+      den = s * inv_bc2_sqrt + eps     two roundings (whether or not the compiler contracts it to one fma)
+      q  = m' / den                    2E allowed, as for sqrtf; den > 0 for eps > 0
+      p' = p - step_size * q           two roundings (contracted or not)
+    Every rounded result r also carries an absolute 2^-126 (a subnormal result, flushed to zero or not).  The interval of each
+    result is widened by the rounding of its larger end; the bound is the distance from the exact fp64 value (adam_step with
+    the exact hyper-parameters) to the farther end.  First-order in E, so a few ulp of each output: a wrong bias correction,
+    a lost grad_scale or a lost update is off by far more.  Returns fp64 tensors."""
+    E = EPS32
+    p, m, v, g = (t.to(torch.float64) for t in (p, m, v, g))
+
+    def wid(lo, hi, rel=E):
+        s = torch.maximum(lo.abs(), hi.abs()) * rel + _FLUSH
+        return lo - s, hi + s
+
+    def const(c):
+        c = torch.tensor(float(c), dtype=torch.float64, device=p.device)
+        return c * (1 - E), c * (1 + E)
+
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    if grad_scale == 1.0:
+        g_lo, g_hi = g, g
+    else:
+        g_lo, g_hi = wid(*_mul(g, g, *const(grad_scale)))
+    d_lo, d_hi = wid(g_lo - m, g_hi - m)
+    o_lo, o_hi = _mul(*const(1 - beta1), d_lo, d_hi)
+    m_lo, m_hi = wid(o_lo + m, o_hi + m)
+    t_lo, t_hi = wid(*_mul(*const(1 - beta2), g_lo, g_hi))
+    t_lo, t_hi = wid(*_mul(t_lo, t_hi, g_lo, g_hi))
+    b_lo, b_hi = _mul(v, v, *const(beta2))
+    v_lo, v_hi = wid(b_lo + t_lo.clamp_min(0.0), b_hi + t_hi)
+    v_lo = v_lo.clamp_min(0.0)
+    s_lo, s_hi = wid(v_lo.sqrt(), v_hi.sqrt(), 2 * E)
+    s_lo = s_lo.clamp_min(0.0)
+    e_lo, e_hi = const(eps)
+    den_lo, den_hi = wid(*_mul(s_lo, s_hi, *const(1 / math.sqrt(bc2))))
+    den_lo, den_hi = wid(den_lo + e_lo, den_hi + e_hi)
+    assert bool((den_lo > 0).all()), "adam_bounds: the denominator may reach 0 (eps = 0 and v = 0)"
+    q_lo, q_hi = wid(*_mul(m_lo, m_hi, 1 / den_hi, 1 / den_lo), 2 * E)
+    u_lo, u_hi = wid(*_mul(*const(lr / bc1), q_lo, q_hi))
+    np_lo, np_hi = wid(p - u_hi, p - u_lo)
+    rp, rm, rv = adam_step(p, m, v, g, step, lr, beta1, beta2, eps, grad_scale)
+    far = lambda lo, hi, r: torch.maximum(r - lo, hi - r)        # noqa: E731
+    return far(np_lo, np_hi, rp), far(m_lo, m_hi, rm), far(v_lo, v_hi, rv)
+
+
+def pack_conv3x3(w):
+    """Host form of the packed 3x3 images (engine.PackedWeights): w [Co,Ci,3,3] -> (w_fwd [9][Co][Ci], w_dgrad [9][Ci][Co]) with
+    tap t = 3 ky + kx; the dgrad image holds the flipped taps, w_dgrad[t] = w[..., 8 - t]^T."""
+    co, ci = w.shape[:2]
+    t = w.reshape(co, ci, 9)
+    return t.permute(2, 0, 1).contiguous(), t.flip(2).permute(2, 1, 0).contiguous()
+
+
+def pack_convT2x2(w):
+    """Host form of the packed ConvTranspose2d images: w [Ci,Co,2,2] -> (w_fwd [4][Co][Ci] (= [4*Co][Ci]), w_dgrad [4][Ci][Co])
+    with ab = 2 a + b the output sub-pixel."""
+    ci, co = w.shape[:2]
+    t = w.reshape(ci, co, 4)
+    return t.permute(2, 1, 0).contiguous(), t.permute(2, 0, 1).contiguous()
+
+
+def conv3x3_packed(x, wk, d):
+    """x [N,H,W,C] through one packed 3x3 image wk [9][Cout][C] as nine shifted GEMMs (the packed operand as the kernels read
+    it, K = C contiguous): forward with w_fwd, input gradient with w_dgrad (the flipped taps make it the same form)."""
+    n, h, wd, c = x.shape
+    xp = F.pad(x, (0, 0, d, d, d, d))
+    acc = torch.zeros(n * h * wd, wk.shape[1], dtype=x.dtype)
+    for t in range(9):
+        ky, kx = divmod(t, 3)
+        acc += xp[:, ky * d:ky * d + h, kx * d:kx * d + wd, :].reshape(-1, c) @ wk[t].t()
+    return acc.view(n, h, wd, -1)
+
+
+def convT2x2_packed(x, wk):
+    """x [N,H,W,C] through one packed 2x2 image wk [4][Cout][C]: out[2y + a, 2x + b] = x[y, x] @ wk[2a + b]^T for the forward
+    image (w_fwd); for the dgrad image it is the adjoint, dx[y, x] = sum_ab dup[2y + a, 2x + b] @ wk[ab]^T (convT2x2_packed_adj)."""
+    n, h, wd, c = x.shape
+    out = torch.empty(n, 2 * h, 2 * wd, wk.shape[1], dtype=x.dtype)
+    for ab in range(4):
+        a, b = divmod(ab, 2)
+        out[:, a::2, b::2, :] = (x.reshape(-1, c) @ wk[ab].t()).view(n, h, wd, -1)
+    return out
+
+
+def convT2x2_packed_adj(dup, wk):
+    n, h2, w2, c = dup.shape
+    acc = torch.zeros(n * (h2 // 2) * (w2 // 2), wk.shape[1], dtype=dup.dtype)
+    for ab in range(4):
+        a, b = divmod(ab, 2)
+        acc += dup[:, a::2, b::2, :].reshape(-1, c) @ wk[ab].t()
+    return acc.view(n, h2 // 2, w2 // 2, -1)
 
 
 # ---------------------------------------------------------------------------------------------------- fixtures

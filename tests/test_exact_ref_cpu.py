@@ -1,6 +1,8 @@
 """CPU checks of tests/exact_ref.py (no GPU): the exact references agree with ATen in float64, the fixtures keep the
 exactness rule they claim, the bf16 rounding helper is torch's, the guard check catches a stray write in every region,
 and the replay's argument table matches include/unetdc_hip.h."""
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -341,3 +343,107 @@ def test_focal_dice_bounds_hold_an_fp32_evaluation(gamma):
     assert float(lhi - llo) < 4 * (hw + 8) * X.EPS32 * abs(float(ref["loss"]))       # the summation term dominates
     width = (dhi - dlo)[:, 8:]
     assert float((width / (gout * ref["dp"][:, 8:]).abs()).max()) < 1e-2         # (nsum = hw here: the GPU sums are far shorter)
+
+
+# ---------------------------------------------------------------------------------------------------- optimizer
+def _adam_fixture(n, g):
+    """Parameters, signed first moments, non-negative second moments and gradients spanning many decades, with exact zeros."""
+    p = torch.randn(n, generator=g) * 0.05
+    mag = lambda lo, hi: torch.exp(torch.empty(n).uniform_(lo, hi, generator=g))     # noqa: E731
+    grad = torch.randn(n, generator=g).sign() * mag(-30.0, 6.0)
+    m = torch.randn(n, generator=g).sign() * mag(-25.0, 2.0)
+    v = mag(-40.0, 4.0)
+    grad[::7], m[::11], v[::13] = 0.0, 0.0, 0.0
+    return p, m, v, grad
+
+
+@pytest.mark.parametrize("step", [1, 2, 10000])
+@pytest.mark.parametrize("hyper", [(1e-3, 0.9, 0.999, 1e-8, 1.0), (3e-4, 0.8, 0.95, 1e-6, 1 / 3)])
+def test_adam_reference_matches_torch_adam(step, hyper):
+    """exact_ref.adam_step is torch.optim.Adam's step (fp64, CPU) from a given state; grad_scale multiplies the gradient."""
+    lr, b1, b2, eps, gs = hyper
+    p, m, v, grad = (t.double() for t in _adam_fixture(4096, gen(20)))
+    w = torch.nn.Parameter(p.clone())
+    opt = torch.optim.Adam([w], lr=lr, betas=(b1, b2), eps=eps, foreach=False)
+    opt.state[w] = {"step": torch.tensor(float(step - 1), dtype=torch.float64), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+    w.grad = grad * gs
+    opt.step()
+    rp, rm, rv = X.adam_step(p, m, v, grad, step, lr, b1, b2, eps, gs)
+    torch.testing.assert_close(rm, opt.state[w]["exp_avg"], rtol=1e-13, atol=0)
+    torch.testing.assert_close(rv, opt.state[w]["exp_avg_sq"], rtol=1e-13, atol=0)
+    torch.testing.assert_close(rp, w.detach(), rtol=1e-13, atol=1e-300)
+
+
+def _fma32(a, b, c):
+    """fmaf in fp64 arithmetic: a * b is exact in fp64, the sum rounds once more before the fp32 rounding (never an issue
+    at the bound's slack)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _adam_fp32(p, m, v, g, step, lr, b1, b2, eps, gs, bc_step=None):
+    """csrc/optim.hip adam_update restated in fp32 torch arithmetic (constants formed in double, rounded once)."""
+    f = lambda x: torch.tensor(x, dtype=torch.float64).float()           # noqa: E731
+    s = step if bc_step is None else bc_step
+    bc1, bc2 = 1.0 - b1 ** s, 1.0 - b2 ** s
+    g = g * f(gs)
+    m = _fma32(f(1.0 - b1), g - m, m)
+    v = _fma32(v, f(b2), f(1.0 - b2) * g * g)
+    den = torch.sqrt(v) * f(1.0 / math.sqrt(bc2)) + f(eps)
+    return p - f(lr / bc1) * (m / den), m, v
+
+
+@pytest.mark.parametrize("step", [1, 2, 12345])
+@pytest.mark.parametrize("hyper", [(1e-3, 0.9, 0.999, 1e-8, 1.0), (3e-4, 0.8, 0.95, 1e-6, 1 / 3)])
+def test_adam_bounds_hold_an_fp32_evaluation(step, hyper):
+    """The per-element bounds the GPU test uses contain an fp32 evaluation of adam_update, are a few ulp wide, and exclude
+    the same step with the bias corrections of step - 1 (at the small step counts where that differs)."""
+    lr, b1, b2, eps, gs = hyper
+    p, m, v, grad = _adam_fixture(1 << 15, gen(21))
+    got = _adam_fp32(p, m, v, grad, step, lr, b1, b2, eps, gs)
+    ref = X.adam_step(p, m, v, grad, step, lr, b1, b2, eps, gs)
+    bounds = X.adam_bounds(p, m, v, grad, step, lr, b1, b2, eps, gs)
+    # the scale of each output's terms: the update for p, the moment and the scaled gradient for m (they may cancel), v itself
+    scales = ((p.double() - ref[0]).abs() + p.double().abs(), m.double().abs() + (grad.double() * gs).abs(), ref[2])
+    for name, gt, r, b, sc in zip("pmv", got, ref, bounds, scales):
+        assert not bool(X.within_bound(gt, r, b, torch.float32).any()), name
+        assert float((b / (X.EPS32 * sc + 2.0 ** -126)).max()) < 32, name       # a few ulp of the terms, nowhere wider
+    assert bool(X.within_bound(torch.zeros(1), torch.ones(1), torch.zeros(1), torch.float32).all())
+    if step <= 2:
+        wrong = _adam_fp32(p, m, v, grad, step, lr, b1, b2, eps, gs, bc_step=step + 1)
+        assert bool(X.within_bound(wrong[0], ref[0], bounds[0], torch.float32).any())
+    if gs != 1.0:
+        wrong = _adam_fp32(p, m, v, grad, step, lr, b1, b2, eps, 1.0)
+        assert float(X.within_bound(wrong[1], ref[1], bounds[1], torch.float32).double().mean()) > 0.5
+
+
+@pytest.mark.parametrize("case", [(2, 6, 7, 5, 3, 1), (1, 9, 8, 4, 6, 2), (1, 12, 10, 3, 4, 4)])
+def test_packed_conv3x3_images_are_the_gemm_operands(case):
+    """exact_ref.pack_conv3x3 (the host form of engine.PackedWeights' 3x3 images): nine shifted GEMMs against w_fwd are
+    F.conv2d, and against w_dgrad the input gradient."""
+    n, h, w, ci, co, d = case
+    g = gen(22)
+    x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64, requires_grad=True)
+    wt = torch.randn(co, ci, 3, 3, generator=g, dtype=torch.float64)
+    dy = torch.randn(n, co, h, w, generator=g, dtype=torch.float64)
+    y = F.conv2d(x, wt, padding=d, dilation=d)
+    gx, = torch.autograd.grad(y, x, dy)
+    wf, wd = X.pack_conv3x3(wt)
+    assert wf.shape == (9, co, ci) and wd.shape == (9, ci, co)
+    torch.testing.assert_close(X.conv3x3_packed(nhwc(x.detach()), wf, d), nhwc(y.detach()))
+    torch.testing.assert_close(X.conv3x3_packed(nhwc(dy), wd, d), nhwc(gx))
+
+
+@pytest.mark.parametrize("case", [(2, 3, 5, 6, 4), (1, 4, 4, 3, 8)])
+def test_packed_conv_transpose_images_are_the_gemm_operands(case):
+    """exact_ref.pack_convT2x2: w_fwd ([4*Cout][Cin]) gives F.conv_transpose2d, w_dgrad ([4][Cin][Cout]) its input gradient."""
+    n, h, w, ci, co = case
+    g = gen(23)
+    x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64, requires_grad=True)
+    wt = torch.randn(ci, co, 2, 2, generator=g, dtype=torch.float64)
+    dup = torch.randn(n, co, 2 * h, 2 * w, generator=g, dtype=torch.float64)
+    up = F.conv_transpose2d(x, wt, stride=2)
+    gx, = torch.autograd.grad(up, x, dup)
+    wf, wd = X.pack_convT2x2(wt)
+    assert wf.shape == (4, co, ci) and wd.shape == (4, ci, co)
+    torch.testing.assert_close(X.convT2x2_packed(nhwc(x.detach()), wf), nhwc(up.detach()))
+    torch.testing.assert_close(X.convT2x2_packed_adj(nhwc(dup), wd), nhwc(gx))

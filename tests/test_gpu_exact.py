@@ -6,9 +6,11 @@ size) must still hold the NaN guard pattern after the call.  Inputs sit at off >
 hold a large finite sentinel: a read of the wrong columns or rows that reaches the arithmetic ruins the result.
 
 Route cases: the operator shapes of tests/test_gpu_ops.py, dense and one-hot fixtures, both dtypes.  Production replay:
-one training step of UNetDC(1, 1) per configuration is recorded, and every distinct call (symbol, shapes, lds, dtype,
-optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must reach the same kernel.  The
-BatchNorm, head and loss calls of the step are replayed through the runners of tests/test_gpu_exact_norm.py."""
+one training step (or eval forward) per configuration is recorded -- UNetDC(1, 1), and the configurations the entry points
+and the benchmark run: UNetDC(3, 1) and UNet(3, 1) in both dtypes, ragged last batches, dL/dx -- and every distinct call
+(symbol, shapes, lds, dtype, optional pointers) is replayed through the same symbol with fresh exact fixtures -- it must
+reach the same kernel.  The BatchNorm, head and loss calls of the step are replayed through the runners of
+tests/test_gpu_exact_norm.py."""
 import ctypes
 import re
 
@@ -716,6 +718,7 @@ RUNNERS = {
     "unetdc_conv3x3_first_fwd": lambda kw: first_fwd(kw, "onehot"),
     "unetdc_conv3x3_first_wgrad": lambda kw: first_wgrad(kw, "onehot"),
     "unetdc_conv3x3_first_wgrad_bn": lambda kw: first_wgrad_bn(kw, "onehot"),
+    "unetdc_conv3x3_first_dgrad": lambda kw: first_dgrad(kw, "onehot"),
     "unetdc_convT2x2_fwd": lambda kw: convt_fwd(kw, "onehot"),
     "unetdc_convT2x2_dgrad": lambda kw: convt_dgrad(kw, "onehot"),
     "unetdc_convT2x2_dgrad_bnstats": lambda kw: convt_dgrad(kw, "onehot", bnstats=True),
@@ -739,41 +742,76 @@ RUNNERS = {
 # symbols a step may issue that the replay does not run, with the reason and the test that covers them
 REPLAY_EXEMPT = {
     "unetdc_pack_many": "weight re-packing, not step arithmetic: tests/test_gpu_ops.py::test_pack_many_matches_per_layer_packers",
+    "unetdc_adam_step": "the optimizer step, not convolution / BatchNorm arithmetic: fp64-bounded p, m, v and bit-exact packed "
+                        "images in tests/test_gpu_exact_optim.py",
 }
 NON_CONV = {s for s in RUNNERS if not any(k in s for k in ("conv3x3", "convT2x2"))}
-# config -> (dtype, batch, size, mode): train = one training step; eval = an eval-mode forward (BatchNorm folded from the
-# running statistics); frozen = eval mode under autograd (frozen statistics), forward and backward
-REPLAY_CONFIGS = {"bf16_8x512": ("bf16", 8, 512, "train"), "f32_8x512": ("f32", 8, 512, "train"),
-                  "bf16_4x1024": ("bf16", 4, 1024, "train"), "bf16_8x512_eval": ("bf16", 8, 512, "eval"),
-                  "bf16_8x512_frozen": ("bf16", 8, 512, "frozen")}
+
+
+def cfg(dtype, bs, size=512, mode="train", arch="unetdc", cin=1, loss="focal", dx=False, adam=False):
+    return dict(dtype=dtype, bs=bs, size=size, mode=mode, arch=arch, cin=cin, loss=loss, dx=dx, adam=adam)
+
+
+# config -> what record_step runs.  mode: train = one training step; eval = an eval-mode forward (BatchNorm folded from the
+# running statistics); frozen = eval mode under autograd (frozen statistics), forward and backward.  arch / cin: UNetDC or
+# the plain UNet (all dilations 1) with 1 or 3 input channels; loss: focal_dice_loss or train.py's combined_loss (BCE + Dice,
+# ATen ops); dx: the input requires grad (dL/dx through the first layer); adam: FusedAdam.step() after the backward.
+REPLAY_CONFIGS = {"bf16_8x512": cfg("bf16", 8), "f32_8x512": cfg("f32", 8),
+                  "bf16_4x1024": cfg("bf16", 4, 1024), "bf16_8x512_eval": cfg("bf16", 8, mode="eval"),
+                  "bf16_8x512_frozen": cfg("bf16", 8, mode="frozen"),
+                  # the entry points' and the benchmark's own configurations
+                  "dc3_f32_8x512": cfg("f32", 8, cin=3, adam=True),                          # train_DC_focal.py defaults
+                  "unet3_f32_8x512": cfg("f32", 8, arch="unet", cin=3, loss="bce_dice", adam=True),   # train.py defaults
+                  "unet3_bf16_8x512": cfg("bf16", 8, arch="unet", cin=3, adam=True),         # bench.py --arch unet
+                  "dc3_f32_8x512_eval": cfg("f32", 8, mode="eval", cin=3),                  # quantify_droplets_batch.py
+                  "dc3_bf16_8x512_eval": cfg("bf16", 8, mode="eval", cin=3),                # bench.py --mode quantify
+                  # the ragged last batch of every epoch (the loaders have no drop_last)
+                  "dc3_bf16_1x512": cfg("bf16", 1, cin=3, adam=True), "dc3_bf16_3x512": cfg("bf16", 3, cin=3, adam=True),
+                  "dc3_f32_1x512": cfg("f32", 1, cin=3, adam=True), "dc3_f32_3x512": cfg("f32", 3, cin=3, adam=True),
+                  # dL/dx at the production shape: the first layer's input-gradient kernel
+                  "dc3_bf16_8x512_dx": cfg("bf16", 8, cin=3, dx=True), "dc3_f32_8x512_dx": cfg("f32", 8, cin=3, dx=True)}
 # 1024^2: the forward and weight-gradient convolution calls and every non-convolution call (the host reference of the
 # whole step is over the time budget; its input-gradient calls take the same kernels as at 512^2 with twice the items per
 # workgroup)
 REPLAY_ONLY = {"bf16_4x1024": ("fwd", "wgrad")}
+# batch 3: every pixel count of the step is 3 * 2^k, and the exact fixtures of the BatchNorm runners (tests/test_gpu_exact_norm.py)
+# need power-of-two counts (k2 = k1 S1 / M must be exact).  These configs replay their convolution calls, whose routes depend
+# on the pixel count; their BatchNorm, head and loss calls take the kernels the batch-1 and batch-8 configs replay.
+REPLAY_CONV_ONLY = {"dc3_bf16_3x512", "dc3_f32_3x512"}
 REPLAYED = set()                # distinct calls replayed by an earlier config of this session (not replayed again)
 
 
-def record_step(dtype, bs, size, mode="train"):
+def record_step(dtype, bs, size, mode="train", arch="unetdc", cin=1, loss="focal", dx=False, adam=False):
+    from models.model import UNet
     from models.model_2 import UNetDC
     from oracle import recipe
-    from utils.metrics_DC import focal_dice_loss
+    from unet_dc_segmentation_amd.optim import FusedAdam
+    from utils.metrics_DC import combined_loss, focal_dice_loss
     torch.manual_seed(5)
-    model = UNetDC(1, 1).cuda()
+    model = (UNetDC if arch == "unetdc" else UNet)(cin, 1).cuda()
     model.train(mode == "train")
     if dtype == "bf16":
         model.set_compute_dtype("bf16")
-    x = recipe.seeded_input(8, (bs, 1, size, size)).cuda()
+    x = recipe.seeded_input(8, (bs, cin, size, size)).cuda()
     t = recipe.seeded_target(9, (bs, 1, size, size), frac=0.1).cuda()
+    if dx:
+        x.requires_grad_()
+    opt = FusedAdam(model) if adam else None
     _lib.start_timing(_lib.SIGNATURES)            # every ABI name: the completeness check sees whatever the step issued
     try:
         if mode == "eval":
             with torch.no_grad():
                 model(x)
         else:
-            focal_dice_loss(model(x), t, alpha=1.0, gamma=2.0, ratio=0.3).backward()
+            p = model(x)
+            (focal_dice_loss(p, t, alpha=1.0, gamma=2.0, ratio=0.3) if loss == "focal" else combined_loss(p, t)).backward()
+            if dx:
+                assert x.grad is not None and bool(torch.isfinite(x.grad).all())
+            if opt is not None:
+                opt.step()
     finally:
         recs = _lib.stop_timing()
-    del model, x, t
+    del model, x, t, opt
     torch.cuda.empty_cache()
     return recs
 
@@ -804,14 +842,17 @@ def test_production_step_replay(config):
     """Every distinct call of one training step (or eval forward, or frozen-statistics step), replayed with exact fixtures
     at its own shapes and leading dimensions: the same kernel, a bit-exact (or fp64-bounded) output, intact guards.  Every
     symbol the step issued has a runner or a named exemption."""
-    dtype, bs, size, mode = REPLAY_CONFIGS[config]
-    calls = distinct_calls(record_step(dtype, bs, size, mode))
+    c = REPLAY_CONFIGS[config]
+    mode = c["mode"]
+    calls = distinct_calls(record_step(**c))
     issued = sorted({k[0] for k in calls})
     missing = [s for s in issued if s not in RUNNERS and s not in REPLAY_EXEMPT]
     assert not missing, f"{config}: symbols issued by the step with neither a replay runner nor an exemption: {missing}"
     calls = {k: v for k, v in calls.items() if k[0] in RUNNERS}
     if config in REPLAY_ONLY:
         calls = {k: v for k, v in calls.items() if k[0] in NON_CONV or any(part in k[0] for part in REPLAY_ONLY[config])}
+    if config in REPLAY_CONV_ONLY:
+        calls = {k: v for k, v in calls.items() if k[0] not in NON_CONV}
     print(f"\n{config}: {len(calls)} distinct calls, symbols issued: {issued}")
     reached = {}
     for key, (kw, kernel) in sorted(calls.items(), key=lambda kv: str(kv[0])):
@@ -828,12 +869,23 @@ def test_production_step_replay(config):
     for sym in sorted(reached):
         print(f"  {sym}: {sorted(reached[sym])}")
     for sym in issued:
-        assert sym in reached or sym in REPLAY_EXEMPT or config in REPLAY_ONLY, (config, sym)
+        assert sym in reached or sym in REPLAY_EXEMPT or config in REPLAY_ONLY or \
+            (config in REPLAY_CONV_ONLY and sym in NON_CONV), (config, sym)
     if mode == "train":
-        for sym in ("unetdc_bn_finalize", "unetdc_focal_dice_loss_fwd", "unetdc_focal_dice_loss_bwd", "unetdc_head_fwd_bn",
-                    "unetdc_head_bwd_bnstats", "unetdc_bn_relu_bwd", "unetdc_bn_relu_bwd_head", "unetdc_bn_relu_bwd_coeffs"):
+        assert ("unetdc_adam_step" in issued) == c["adam"], (config, issued)
+        # the first layer's weight gradient: BatchNorm backward on load (with its coefficients) where the library supports it
+        # (C_in = 1), the plain form after unetdc_bn_relu_bwd otherwise
+        first = ("unetdc_conv3x3_first_wgrad_bn", "unetdc_bn_relu_bwd_coeffs") if c["cin"] == 1 else ("unetdc_conv3x3_first_wgrad",)
+        for sym in first + ("unetdc_bn_finalize", "unetdc_focal_dice_loss_fwd", "unetdc_focal_dice_loss_bwd", "unetdc_head_fwd_bn",
+                            "unetdc_head_bwd_bnstats", "unetdc_bn_relu_bwd", "unetdc_bn_relu_bwd_head"):
+            if c["loss"] != "focal" and "focal" in sym:         # combined_loss (train.py) is ATen arithmetic, no loss kernel
+                continue
+            if config in REPLAY_CONV_ONLY and sym in NON_CONV:
+                continue
             assert sym in reached, (config, sym, sorted(reached))
     elif mode == "eval":
         assert {"unetdc_bn_eval_affine", "unetdc_head_fwd"} <= set(reached), (config, sorted(reached))
     else:
         assert {"unetdc_bn_frozen_affine", "unetdc_bn_relu_bwd_frozen"} <= set(reached), (config, sorted(reached))
+    if c["dx"]:
+        assert "unetdc_conv3x3_first_dgrad" in reached, (config, sorted(reached))
