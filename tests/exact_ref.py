@@ -240,6 +240,7 @@ def colsum(x):
 # every result is the exact mathematical value in fp64.  Where a fixture makes the fp32 arithmetic exact, the kernel's fp32
 # result equals the fp32 rounding of these values; elsewhere a test compares against them under a bound (within_bound).
 EPS32 = 2.0 ** -24                       # unit roundoff of fp32
+EPS64 = 2.0 ** -53                       # unit roundoff of fp64
 
 
 def _f64(t, dev):
@@ -327,8 +328,26 @@ def bn_relu_bwd(y, scale, shift, mean, rstd, gamma, dskip=None, dpool=None, dtyp
         k2, k3 = k1 * s1 / m, k1 * s2 / m
         dbias = -k3 * s3
     dy = k1 * gh - k2 - k3 * xh
+    # dy = fmaf(k1, gh, -k2) - k3 * xh in fp32 from the fp32 k1, k2, k3 (gh and xh are exact in the fixtures): the stored k2
+    # and k3 are roundings of the exact ones (E each; none at a power-of-two count), k3 * xh rounds (E), the fused term
+    # rounds once (E (|k1 gh| + |k2|)), the difference once more (E of everything): at most
+    # E (2 |k1 gh| + 3 |k2| + 4 |k3 xh|) to first order, within the 4 E (...) below at any pixel count.
     dy_bound = 4 * EPS32 * ((k1 * gh).abs() + k2.abs() + (k3 * xh).abs())
-    return dict(dy=dy, dy_bound=dy_bound, gh=gh, xh=xh, s1=s1, s2=s2, s3=s3, dgamma=s2, dbeta=s1, dbias=dbias, k1=k1, k2=k2, k3=k3)
+    out = dict(dy=dy, dy_bound=dy_bound, gh=gh, xh=xh, s1=s1, s2=s2, s3=s3, dgamma=s2, dbeta=s1, dbias=dbias, k1=k1, k2=k2, k3=k3)
+    out.update(bn_bwd_coeff_bounds(k2, k3, dbias))
+    return out
+
+
+def bn_bwd_coeff_bounds(k2, k3, dbias):
+    """How far the DOUBLE value that bn_bwd_finalize_kernel rounds to fp32 can lie from the fp64 reference when the pixel
+    count M is not a power of two (at a power of two, with the integer fixtures, every operation is exact and the tests ask
+    for equality).  The kernel forms a = gamma rstd (exact in double: two 24-bit significands), then a S / M in double -- one
+    product and one division, each within 2^-53 -- and rounds to fp32 once; the reference does the same two operations in
+    fp64, in whatever association, with the same two roundings at most: the two doubles differ by at most 4 * 2^-53 |k|.
+    dbias = -(a S2 / M) S3 has one more product on each side: 6 * 2^-53 |dbias|.  exact_ref.within_bound then accepts the fp32
+    rounding of the reference, and its neighbour only where the reference lies that close to an fp32 rounding boundary.
+    (Far tighter than one fp32 division and one fp32 product, 2 * 2^-24 |k|, which an fp32 finalize would need.)"""
+    return dict(k2_bound=4 * EPS64 * k2.abs(), k3_bound=4 * EPS64 * k3.abs(), dbias_bound=6 * EPS64 * dbias.abs())
 
 
 def head_dz(dprobs, probs):

@@ -37,18 +37,22 @@ def close(got, exp, what, tol=1e-10, floor=0.0):
     assert err <= tol * max(scale, 1e-300), f"{what}: max |err| {err:.3e} vs max |ref| {scale:.3e}"
 
 
+# the last three: non-square maps with odd pooled sizes (45- and 120-pixel bottlenecks) and a two-output-channel head, the
+# geometries tests/test_gpu_dataflow.py runs off the production shape
 @pytest.mark.parametrize("arch,shape", [("unetdc", (2, 1, 32, 32)), ("unetdc", (1, 3, 64, 64)), ("unet", (2, 1, 32, 32)),
-                                        ("unet", (1, 3, 64, 64))])
+                                        ("unet", (1, 3, 64, 64)), ("unetdc", (3, 1, 48, 80)), ("unetdc", (2, 3, 96, 160)),
+                                        ("unetdc2", (2, 1, 32, 48))])
 def test_fp64_chain_reproduces_the_module(arch, shape):
     from models.model import UNet
     from models.model_2 import UNetDC
     from utils.metrics_DC import focal_dice_loss
     torch.manual_seed(3)
     n, c, h, w = shape
-    model = (UNetDC if arch == "unetdc" else UNet)(c, 1).double().train()
+    oc = 2 if arch == "unetdc2" else 1
+    model = (UNet if arch == "unet" else UNetDC)(c, oc).double().train()
     gen = torch.Generator().manual_seed(4)
     x = torch.rand(shape, generator=gen, dtype=F64)
-    t = (torch.rand(n, 1, h, w, generator=gen) < 0.3).to(F64)
+    t = (torch.rand(n, oc, h, w, generator=gen) < 0.3).to(F64)
     g, vals = chain(model, x, t)
     # the module, fp64, autograd
     xr = x.clone().requires_grad_()
@@ -146,3 +150,90 @@ def test_derived_activation_rounds_once_to_fp32_then_to_storage():
     a = R.derive_act(y, torch.ones(1, dtype=F64), sh, torch.bfloat16)
     assert a.item() == 1.0
     assert R.derive_act(y, torch.ones(1, dtype=F64), -torch.ones(1, dtype=F64) * 2, torch.bfloat16).item() == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------- bounds at small counts
+def _f32_bn_stage(y, gamma, beta, rm, rv, eps, mom, gin):
+    """One BatchNorm + ReLU stage forward and backward in plain fp32 torch from the stored inputs, every sum taken in an order
+    of its own (pixels reversed, pairwise over two interleaved halves) -- neither the reference's nor the kernels'."""
+    f = torch.float32
+    y32, g32 = y.to(f), gin.to(f)
+    M = y32.shape[0]
+
+    def colsum(t):
+        t = t.flip(0)
+        return t[0::2].sum(0) + t[1::2].sum(0)
+    s, q = colsum(y32), colsum(y32 * y32)
+    m = torch.tensor(float(M), dtype=f)
+    mean = s / m
+    var = (q / m - mean * mean).clamp_min(0)
+    rstd = 1 / torch.sqrt(var + torch.tensor(eps, dtype=f))
+    scale = gamma.to(f) * rstd
+    shift = beta.to(f) - mean * scale
+    mo = torch.tensor(mom, dtype=f)
+    out = {"mean": mean, "rstd": rstd, "scale": scale, "shift": shift,
+           "running_mean": (1 - mo) * rm.to(f) + mo * mean, "running_var": (1 - mo) * rv.to(f) + mo * (var * (m / (m - 1)))}
+    return out, y32, g32, colsum, m
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+# (no encoder's second stage here: its gradient arrives through the max-pool in two parts, which the operator-level pooled
+# cases of tests/test_gpu_exact_norm.py cover; every stage below takes one incoming gradient g:<S>.a)
+@pytest.mark.parametrize("dims,stage", [((3, 48, 80), "bottleneck.3"), ((2, 96, 160), "bottleneck.0"), ((1, 32, 32), "bottleneck.3"),
+                                        ((3, 48, 80), "dec4.3"), ((5, 32, 48), "enc4.0")])
+def test_bn_bounds_hold_an_fp32_evaluation_at_small_and_odd_counts(dims, stage, dt):
+    """The condition that keeps tests/test_gpu_dataflow.py honest off the production shape: at 45 (3 x 3 x 5), 120 (2 x 6 x
+    10) and 4 (1 x 2 x 2) samples per channel, and at 180 and 120 on the levels above, the BatchNorm-family values of a stage
+    -- statistics, running statistics, dy, dgamma, dbeta and the conv bias gradient (through which the k-coefficients
+    k1 S / M act) -- evaluated in plain fp32 from the same stored inputs, in another summation order, lie within the
+    reference's bounds, EVERY element (no masking, no sampling).  The inputs are what a trained-from-init network sees: y
+    of unit scale with a per-channel offset, gradients of mixed sign.  With four samples a channel's variance is a chi-square
+    of 3 degrees of freedom times the spread of y: never near zero against eps for a continuous y, so no shape had to be
+    replaced."""
+    from models.model_2 import UNetDC
+    g = R.Graph(UNetDC(1, 1))
+    st = g.by_name[stage]
+    N, H, W = dims
+    h, w = H >> st.level, W >> st.level
+    P, c = N * h * w, st.cout
+    gen = torch.Generator().manual_seed(7 + P)
+    y = R.store((torch.randn(P, c, generator=gen, dtype=F64) * (0.5 + torch.rand(c, generator=gen, dtype=F64))
+                 + torch.randn(c, generator=gen, dtype=F64)), dt)
+    gin = R.store(torch.randn(P, c, generator=gen, dtype=F64) * 1e-3, dt)
+    gamma = (torch.rand(c, generator=gen) + 0.5).to(F64)
+    beta = (torch.randn(c, generator=gen) * 0.2).to(F64)
+    rm, rv = torch.randn(c, generator=gen).to(F64) * 0.1, (torch.rand(c, generator=gen) + 0.5).to(F64)
+    S, B = st.name, st.bn_name
+    got, y32, g32, colsum, m = _f32_bn_stage(y, gamma, beta, rm, rv, st.eps, st.momentum, gin)
+    vals = {f"{S}.y": y, f"P:{B}.weight": gamma, f"P:{B}.bias": beta, f"P:{B}.running_mean": rm, f"P:{B}.running_var": rv}
+    get = lambda k: (vals[k], None)                                   # noqa: E731
+    fwd = [f"{S}.{k}" for k in ("mean", "rstd", "scale", "shift", "running_mean", "running_var")]
+    refs = R.reference(g, fwd, get, dt, "train", dims)
+    worst = {}
+
+    def inside(name, value):
+        ref, bnd = refs[name]
+        bad = X.within_bound(value, ref, bnd, torch.float32 if value.dim() == 1 else dt)
+        u = R.unit(dt) if value.dim() > 1 else R.unit(torch.float32)     # as the GPU test reports it: the storage rounding counted in
+        worst[name.split(".")[-1]] = float(((value.to(F64).reshape(ref.shape) - ref).abs() / (bnd + u * ref.abs() + 2.0 ** -126)).max())
+        assert not bad.any(), f"{name} at {dims}: {int(bad.sum())} of {bad.numel()} fp32-evaluated elements outside the bound"
+    for k in fwd:
+        inside(k, got[k.split(".", 2)[2]])
+    # backward, from the STORED fp32 statistics (teacher forcing), as the kernels read them
+    f = torch.float32
+    for k in ("mean", "rstd", "scale", "shift"):
+        vals[f"{S}.{k}"] = got[k].to(F64)
+    vals[f"g:{S}.a"] = gin
+    refs = R.reference(g, [f"{S}.dy", f"G:{B}.weight", f"G:{B}.bias", f"G:{st.conv_name}.bias"], get, dt, "train", dims)
+    nrm = torch.addcmul(got["shift"], y32, got["scale"])
+    gh = torch.where(nrm > 0, g32, torch.zeros_like(g32))
+    xh = (y32 - got["mean"]) * got["rstd"]
+    s1, s2, s3 = colsum(gh), colsum(gh * xh), colsum(xh)
+    k1 = gamma.to(f) * got["rstd"]
+    k2, k3 = k1 * s1 / m, k1 * s2 / m
+    dy = (k1 * gh - k2) - k3 * xh
+    inside(f"{S}.dy", R.store(dy.to(F64), dt).reshape(N, h, w, c))
+    inside(f"G:{B}.weight", s2)
+    inside(f"G:{B}.bias", s1)
+    inside(f"G:{st.conv_name}.bias", -k3 * s3)
+    print(f"\n{stage} at {dims} ({P} samples, {dt}): worst fp32-evaluation err / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))

@@ -207,6 +207,57 @@ def test_bn_finalize_reference_matches_batch_norm(rows, count):
     torch.testing.assert_close(y * ev["scale"] + ev["shift"], F.batch_norm(y + bias, rm, rv, gamma, beta, training=False, eps=1e-5))
 
 
+def test_bn_finalize_fixture_is_exact_at_any_count():
+    """tests/test_gpu_exact_norm.py finalize_parts at the counts of its off-grid cases: the kernel's own double arithmetic
+    (total / count, total_q / count - mean^2, 1 / sqrt, one rounding to fp32, the fp32 products of scale and shift) lands on
+    the fp32 rounding of the fp64 reference exactly, so those cases keep bound 0 for mean, var, rstd, scale and shift."""
+    from tests import test_gpu_exact_norm as N
+    assert any(not N.pow2_count(count) for _, count, _ in N.ODD_FINALIZE_CASES)
+    for rows, count, c in N.FINALIZE_CASES + N.ODD_FINALIZE_CASES:
+        if rows * c > 1 << 20:                   # (the largest power-of-two cases: minutes of host time for nothing new)
+            continue
+        g = gen(31)
+        parts, m, var = N.finalize_parts(rows, count, c, g, dev="cpu")
+        gamma = X.pow2(c, g, (-1, 0, 1)) * (1 - 2 * (torch.rand(c, generator=g) < 0.3).float())
+        beta = X.ints((c,), 3, g)
+        ref = X.bn_finalize(parts.double(), count, gamma, beta, 0.0, 0.1)
+        # the kernel, statement by statement (bn_finalize_kernel): fp32 rows summed in double, any order (integers: exact)
+        s, q = parts[:, 0].double().flip(0).sum(0), parts[:, 1].double().flip(0).sum(0)
+        mean = s / float(count)
+        v = (q / float(count) - mean * mean).clamp_min(0.0)
+        rstd = (1.0 / torch.sqrt(v)).float()
+        sc = gamma * rstd
+        sh = beta - mean.float() * sc
+        assert torch.equal(mean, m) and torch.equal(v, var), (rows, count, c)
+        for got, k in ((mean.float(), "mean"), (rstd, "rstd"), (sc, "scale"), (sh, "shift")):
+            assert not X.within_bound(got, ref[k], 0, torch.float32).any(), (rows, count, c, k)
+        if rows > 2 and rows == -(-count // 256) and count % 256:      # one row per 256-pixel block: the last one is partial
+            assert float(parts[-1, 1].abs().max()) < float(parts[1, 1].abs().max()), (rows, count)
+
+
+@pytest.mark.parametrize("count", [45, 120, 4, 3 << 18, 4800, 5 * 384 * 384, 1 << 12])
+def test_bn_bwd_coefficient_bounds_hold_the_kernels_double_arithmetic(count):
+    """exact_ref.bn_bwd_coeff_bounds: the kernel's double evaluation, in its own association (a S / M, a = gamma rstd) and in
+    another one (a (S / M)), rounded to fp32 once, lies within the bound of the reference for integer sums and power-of-two
+    k1; an fp32 division by a count rounded up to a multiple of 256 does not; at a power-of-two count the bound is not needed
+    (equality)."""
+    g = gen(41)
+    c = 512
+    s1, s2, s3 = (X.ints((c,), 4000, g).double() for _ in range(3))
+    gamma, rs = (X.pow2(c, g, (-1, 0, 1)) * (1 - 2 * (torch.rand(c, generator=g) < 0.3).float())).double(), X.pow2(c, g, (-1, 0)).double()
+    k1 = gamma * rs
+    k2, k3 = k1 * s1 / count, k1 * s2 / count
+    dbias = -k3 * s3
+    b = X.bn_bwd_coeff_bounds(k2, k3, dbias)
+    for assoc in (lambda s: k1 * s / float(count), lambda s: k1 * (s / float(count))):
+        for got, ref, bnd in ((assoc(s1), k2, "k2_bound"), (assoc(s2), k3, "k3_bound"), (-assoc(s2) * s3, dbias, "dbias_bound")):
+            zero = torch.zeros_like(ref) if count & (count - 1) == 0 else b[bnd]
+            assert not X.within_bound(got.float(), ref, zero, torch.float32).any(), (count, bnd)
+    if count % 256:
+        wrong = k1 * s1 / float(-(-count // 256) * 256)
+        assert X.within_bound(wrong.float(), k2, b["k2_bound"], torch.float32)[s1 != 0].all()
+
+
 def _bn_autograd(y, gamma, beta, rm, rv, dskip, dpool, frozen):
     """dL/dy, dL/dgamma, dL/dbeta, dL/dbias (bias added to the conv output in front of the BatchNorm) by autograd, NCHW."""
     yr, gr, br = y.clone().requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)

@@ -79,6 +79,7 @@ class Tracer:
         self.target = None
         self.issued = collections.Counter()
         self.kernels = set()
+        self.calls_at = {}                 # (symbol, h, w of the call) -> kernel names it reached ('' where it names none)
         self.forms = set()
         self.failures = []
         self.worst = {}
@@ -223,6 +224,9 @@ class Tracer:
         torch.cuda.synchronize()
         if "conv" in sym:                  # (the elementwise / reduction kernels name no matrix-core kernel)
             self.kernels.add(f"{sym}|{self.lib.unetdc_last_kernel().decode()}")
+        if "h" in kw and "w" in kw:
+            self.calls_at.setdefault((sym, kw["h"], kw["w"]), set()).add(
+                self.lib.unetdc_last_kernel().decode() if "conv" in sym else "")
         self.forms.add(sym)
         if sym == "unetdc_conv3x3_fwd_bnin":
             self.forms.add("bnin_store" if kw.get("ptr:act_out") else "bnin")
@@ -357,12 +361,12 @@ def tracer(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------- configurations
-def make_model(arch, cin, dtype, perturb=False):
+def make_model(arch, cin, dtype, perturb=False, oc=1):
     from models.model import UNet
     from models.model_2 import UNetDC
     from oracle import recipe
     torch.manual_seed(5)
-    model = (UNetDC if arch == "unetdc" else UNet)(cin, 1)
+    model = (UNetDC if arch == "unetdc" else UNet)(cin, oc)
     if perturb:                                    # non-trivial running statistics for the eval / frozen forms
         sd = model.state_dict()
         recipe.perturb_bn(sd, 11)
@@ -373,10 +377,12 @@ def make_model(arch, cin, dtype, perturb=False):
     return model
 
 
-def batch(seed, n, cin, size):
+def batch(seed, n, cin, size, oc=1):
+    """size: the side of a square image, or (H, W)."""
     from oracle import recipe
-    x = recipe.seeded_input(seed, (n, cin, size, size)).cuda()
-    t = recipe.seeded_target(seed + 1, (n, 1, size, size), frac=0.1).cuda()
+    h, w = (size, size) if isinstance(size, int) else size
+    x = recipe.seeded_input(seed, (n, cin, h, w)).cuda()
+    t = recipe.seeded_target(seed + 1, (n, oc, h, w), frac=0.1).cuda()
     return x, t
 
 
@@ -533,3 +539,200 @@ def test_dataflow_fp32_self_test(tracer):
     x, t = batch(80, 2, 1, 512)
     train_step(model, tr, x, t)
     report("f32_self_test", tr, t0)
+
+
+# ---------------------------------------------------------------------------------------------------- off the production shape
+PRODUCTION = {}                            # (arch, cin) -> (per-stage plan, forms, kernels) of one 8 x 512^2 bf16 training step
+
+
+def stage_plan(eng):
+    """The decisions UNetEngine._build took: per stage (forward form, weight-gradient form, activation stored), the head."""
+    plan = {f"{b}.{i}": (st.fwd, st.wgrad, bool(st.store)) for (b, i), st in eng.stages.items()}
+    plan["head_fused"] = bool(eng.head_fused)
+    return plan
+
+
+def production_plan(arch, cin):
+    """Plan, forms and kernels of the 8 x 512^2 bf16 training step of the one-output-channel model (no tracer: the recorded
+    calls of one step, as tests/test_gpu_exact.py::record_step takes them)."""
+    if (arch, cin) not in PRODUCTION:
+        from unet_dc_segmentation_amd import _lib, engine
+        from utils.metrics_DC import focal_dice_loss
+        model = make_model(arch, cin, "bf16").train()
+        x, t = batch(20, 8, cin, 512)
+        plan = stage_plan(engine.UNetEngine(model, x))
+        _lib.start_timing(_lib.SIGNATURES)
+        try:
+            focal_dice_loss(model(x), t, alpha=1.0, gamma=2.0, ratio=0.3).backward()
+        finally:
+            recs = _lib.stop_timing()
+        forms, kernels = set(), set()
+        for name_kernel, args, _ in recs:
+            sym = name_kernel.split("|", 1)[0]
+            if sym in EXEMPT:
+                continue
+            forms.add(sym)
+            if "conv" in sym:
+                kernels.add(name_kernel)
+            if sym == "unetdc_conv3x3_fwd_bnin":
+                pos = X.positions(sym, X.arg_kinds(_lib.SIGNATURES[sym][1]))
+                forms.add("bnin_store" if args[pos["ptr:act_out"]] else "bnin")
+        PRODUCTION[(arch, cin)] = (plan, forms, kernels)
+        del model, x, t
+        torch.cuda.empty_cache()
+    return PRODUCTION[(arch, cin)]
+
+
+def off_production(tracer, config, arch, cin, dims, seed, oc=1, dx=False, adam=False, different=True):
+    """One traced bf16 training step at `dims`, reported like the configurations above, and compared with the production
+    plan: `different` asserts that a form, a stored-vs-derived decision or a kernel (route) name differs from the
+    8 x 512^2 step's."""
+    t0 = time.time()
+    torch.cuda.empty_cache()
+    prod_plan, prod_forms, prod_kernels = production_plan(arch, cin)
+    model = make_model(arch, cin, "bf16", oc=oc).train()
+    tr = tracer(model, torch.bfloat16, dims)
+    opt = None
+    if adam:
+        from unet_dc_segmentation_amd.optim import FusedAdam
+        opt = FusedAdam(model, lr=1e-2)
+    x, t = batch(seed, dims[0], cin, dims[1:], oc)
+    if dx:
+        x.requires_grad_()
+    derived = train_step(model, tr, x, t, opt)
+    eng = next(iter(tr.engines.values()))
+    plan = stage_plan(eng)
+    forms = {f for f in tr.forms}
+    dplan = {k: (prod_plan[k], v) for k, v in plan.items() if prod_plan[k] != v}
+    print(f"\n[{config}] pixel counts per level: {eng.npix}; never materialised (derived): {sorted(derived)}")
+    print(f"[{config}] plan entries that differ from 8 x 512^2 (production, here): {dplan}")
+    print(f"[{config}] forms only here: {sorted(forms - prod_forms)}; only at 8 x 512^2: {sorted(prod_forms - forms)}")
+    print(f"[{config}] kernels only here: {sorted(tr.kernels - prod_kernels)}")
+    print(f"[{config}] kernels only at 8 x 512^2: {sorted(prod_kernels - tr.kernels)}")
+    report(config, tr, t0)
+    if different:
+        assert dplan or forms != prod_forms or tr.kernels != prod_kernels, f"{config} reaches exactly the production plan"
+    del model, opt
+    torch.cuda.empty_cache()
+    return tr, plan, dplan
+
+
+def test_dataflow_bf16_ragged_last_batch(tracer):
+    """UNetDC(3, 1), 3 x 512^2, one FusedAdam step: the step every epoch of train_DC_focal.py ends with (no drop_last).  Every
+    pixel count is 3 * 2^k: the statistics and the k-coefficients divide by a count that is not a power of two, the
+    256-pixel statistics rows come in numbers that are not powers of two.  The maps are the production ones, so the plan
+    may be the production plan (printed; not asserted to differ): it is kept for its pixel counts."""
+    tr, _, _ = off_production(tracer, "bf16_dc3_3x512", "unetdc", 3, (3, 512, 512), 90, adam=True, different=False)
+    assert {"unetdc_conv3x3_first_wgrad", "unetdc_bn_relu_bwd_head", "unetdc_head_fwd_bn"} <= tr.forms, sorted(tr.forms)
+
+
+def test_dataflow_bf16_single_image(tracer):
+    """UNetDC(1, 1), 1 x 512^2: batch 1 -- the normalise-on-load decisions (unetdc_conv3x3_bnin_supported) and the kernel
+    routes at an eighth of the production pixel counts."""
+    tr, plan, dplan = off_production(tracer, "bf16_1x512", "unetdc", 1, (1, 512, 512), 92)
+    # the decisions of unetdc_conv3x3_bnin_supported and unetdc_conv3x3_first_wgrad_bn_supported depend on the maps, not on the
+    # batch: at N = 1 every stage keeps the production form and no stage flips `store` ...
+    assert not dplan, dplan
+    assert plan["enc1.0"] == ("first", "first_bn", False) and plan["enc1.3"] == ("bnin", "bnin", True), plan
+    assert plan["dec1.3"] == ("bnin", "bnin", False) and plan["enc2.3"] == ("bnin_store", "plain", True), plan
+    assert {"bnin", "bnin_store", "unetdc_conv3x3_first_wgrad_bn", "unetdc_bn_relu_bwd_coeffs", "unetdc_bn_relu_bwd_head"} <= tr.forms
+    # ... what changes with an eighth of the pixels is the weight-gradient route: the split-K DMA kernel where 8 x 512^2 takes
+    # the fused split kernel, and the ring3 dma16 forward at the small levels
+    _, _, prod_kernels = production_plan("unetdc", 1)
+    here = tr.kernels - prod_kernels
+    assert {"unetdc_conv3x3_wgrad|wgrad_dma_kernel<__bf16, 2>", "unetdc_conv3x3_wgrad|wgrad_dma_kernel<__bf16, 4>",
+            "unetdc_conv3x3_fwd|igemm_dma16_kernel<4, 2, 4> ring3"} <= here, sorted(here)
+    assert not any("wgrad_fused_split_kernel" in k for k in tr.kernels), sorted(tr.kernels)
+    assert any("wgrad_fused_split_kernel" in k for k in prod_kernels), sorted(prod_kernels)
+
+
+def test_dataflow_bf16_odd_maps(tracer):
+    """UNetDC(1, 1), 3 x 48 x 80: a 45-pixel bottleneck (3 x 3 x 5: M % 16 != 0, so no 16x16x32 tile route takes it; odd map
+    height and width under dilation 16), pooled maps with an odd number of rows (3, from 6), every count 15 * 2^k or 45, and the
+    first layer's BatchNorm-on-load weight gradient at W % 8 == 0."""
+    tr, plan, _ = off_production(tracer, "bf16_3x48x80", "unetdc", 1, (3, 48, 80), 94)
+    eng = next(iter(tr.engines.values()))
+    assert eng.npix[-1] == 45 and eng.npix[-1] % 16, eng.npix
+    # first_bn at W = 80 (W % 8 == 0): chosen, and issued with its coefficients
+    assert plan["enc1.0"] == ("first", "first_bn", True), plan["enc1.0"]
+    assert {"unetdc_conv3x3_first_wgrad_bn", "unetdc_bn_relu_bwd_coeffs"} <= tr.forms, sorted(tr.forms)
+    assert ("unetdc_conv3x3_first_wgrad_bn", 48, 80) in tr.calls_at, sorted(tr.calls_at)
+    # no map of this step takes a normalise-on-load form: every other stage is plain and stores its activation
+    assert all(v[:2] == ("plain", "plain") for k, v in plan.items() if k not in ("enc1.0", "head_fused")), plan
+    assert not {"bnin", "bnin_store", "unetdc_conv3x3_fwd_bnin", "unetdc_conv3x3_wgrad_bnin"} & tr.forms, sorted(tr.forms)
+    # the 45-pixel maps (M % 16 != 0): every matrix-core call on them -- both bottleneck stages forward, input gradient and
+    # weight gradient, and the up-convolution that reads them -- leaves the 16x16x32 routes (dma16, the split weight-gradient
+    # kernels) and the lattice / halo routes for the first-generation DMA kernels, which the production step never reaches
+    _, _, prod_kernels = production_plan("unetdc", 1)
+    at45 = {k: v for k, v in tr.calls_at.items() if (k[1], k[2]) == (3, 5) and "conv" in k[0]}
+    print(f"[bf16_3x48x80] kernels on the 3 x 5 maps: { {k[0]: sorted(v) for k, v in sorted(at45.items())} }")
+    assert {"unetdc_conv3x3_fwd", "unetdc_conv3x3_wgrad", "unetdc_conv3x3_dgrad", "unetdc_conv3x3_dgrad_bnstats", "unetdc_convT2x2_fwd",
+            "unetdc_convT2x2_wgrad", "unetdc_convT2x2_dgrad_bnstats"} <= {k[0] for k in at45}, sorted(at45)
+    for (sym, _, _), names in at45.items():
+        for name in names:
+            assert not any(t in name for t in ("dma16", "16x16x32", "lattice", "halo")), (sym, name)
+            if "wgrad" not in sym:
+                assert name.startswith("igemm_dma_kernel<__bf16"), (sym, name)
+                assert f"{sym}|{name}" not in prod_kernels, (sym, name)
+    # odd pooled rows: enc4's 6 x 10 map pools to 3 x 5, forward and backward
+    assert eng.res[3] == (6, 10) and eng.res[4] == (3, 5), eng.res
+    assert ("unetdc_bn_relu_apply", 6, 10) in tr.calls_at and ("unetdc_bn_relu_bwd", 6, 10) in tr.calls_at, sorted(tr.calls_at)
+
+
+def test_dataflow_bf16_odd_maps_three_channels_dx(tracer):
+    """UNetDC(3, 1) with x.requires_grad, 2 x 96 x 160: the plain first-layer weight gradient, first_dgrad and dL/dx on a
+    non-square map; 120-pixel bottleneck (2 x 6 x 10), below one 256-pixel statistics block."""
+    tr, plan, _ = off_production(tracer, "bf16_dc3_2x96x160_dx", "unetdc", 3, (2, 96, 160), 96, dx=True)
+    assert {"unetdc_conv3x3_first_wgrad", "unetdc_conv3x3_first_dgrad"} <= tr.forms, sorted(tr.forms)
+    assert plan["enc1.0"] == ("first", "first", True), plan["enc1.0"]
+    assert tr.calls_at[("unetdc_conv3x3_first_dgrad", 96, 160)] == {"first_dgrad_kernel<__bf16>"}, tr.calls_at
+    assert all(v[:2] == ("plain", "plain") for k, v in plan.items() if k not in ("enc1.0", "head_fused")), plan
+    # the 120-pixel bottleneck (M % 16 != 0 as well: 120 = 7.5 * 16) takes the first-generation DMA kernel
+    at120 = set().union(*(v for k, v in tr.calls_at.items() if (k[1], k[2]) == (6, 10) and "conv" in k[0]))
+    print(f"[bf16_dc3_2x96x160_dx] kernels on the 6 x 10 maps: {sorted(at120)}")
+    assert "igemm_dma_kernel<__bf16, 4, 2, 2>" in at120 and not any("dma16" in k or "16x16x32" in k for k in at120), sorted(at120)
+
+
+def test_dataflow_bf16_1024_tiles(tracer):
+    """UNetDC(1, 1), 4 x 1024^2 (BASELINE.json configs[4]): the pixel counts of 8 x 512^2 on rows twice as wide -- the tile
+    geometry of the lattice / halo routes, the pool and up-convolution decodes."""
+    tr, plan, dplan = off_production(tracer, "bf16_4x1024", "unetdc", 1, (4, 1024, 1024), 98)
+    # the same plan as 8 x 512^2 (the forms depend on maps the lattice kernels take at both sizes) ...
+    assert not dplan, dplan
+    # ... and the same lattice / halo kernels, on rows twice as wide; what moves is the dma16 tile choice of the levels
+    # whose maps doubled: the 2x4x8 tiling with 16x16 blocks appears, the ring3 one of the 512^2 step is gone
+    _, _, prod_kernels = production_plan("unetdc", 1)
+    lattice = lambda ks: {k for k in ks if "lattice" in k or "halo" in k}           # noqa: E731
+    assert lattice(tr.kernels) == lattice(prod_kernels), (sorted(lattice(tr.kernels)), sorted(lattice(prod_kernels)))
+    here = tr.kernels - prod_kernels
+    assert {"unetdc_conv3x3_fwd|igemm_dma16_kernel<2, 4, 8> blocks16x16",
+            "unetdc_conv3x3_dgrad_bnstats|igemm_dma16_kernel<2, 4, 8> blocks16x16"} <= here, sorted(here)
+    assert "unetdc_conv3x3_fwd|igemm_dma16_kernel<4, 2, 4> ring3 blocks16x16" in prod_kernels - tr.kernels
+    # every pool and up-convolution of the step ran at the doubled row width
+    assert {("unetdc_bn_relu_apply", 1024, 1024), ("unetdc_convT2x2_fwd", 512, 512), ("unetdc_convT2x2_fwd", 64, 64)} <= set(tr.calls_at)
+
+
+def test_dataflow_bf16_two_output_channels(tracer):
+    """UNetDC(1, 2), 2 x 128^2, a (N, 2, H, W) target through the fused loss (it takes any [N, OC, H, W] pair of equal shapes):
+    head_fused is False, so the head backward stores dA and dec1.3 takes the plain unetdc_bn_relu_bwd."""
+    tr, plan, dplan = off_production(tracer, "bf16_oc2_2x128", "unetdc", 1, (2, 128, 128), 100, oc=2)
+    assert plan["head_fused"] is False and "head_fused" in dplan
+    assert "unetdc_bn_relu_bwd_head" not in tr.forms and "unetdc_bn_relu_bwd" in tr.forms, sorted(tr.forms)
+    eng = next(iter(tr.engines.values()))
+    assert "g:dec1.3.a" in tr.produced[id(eng)], "the head's input gradient should be stored, not derived"
+
+
+def test_dataflow_bf16_unet_384_batch_5(tracer):
+    """UNet(3, 1), 5 x 384^2 (train.py --img_size 384 --batch 5 on the bf16 path): every count 45 * 2^k, maps of 384 ... 24
+    pixels a side."""
+    tr, plan, dplan = off_production(tracer, "bf16_unet3_5x384", "unet", 3, (5, 384, 384), 102)
+    # the 48 x 48 level leaves the normalise-on-load forms (bnin_store at 64 x 64): enc4 and dec4 run plain and store
+    assert set(dplan) == {"enc4.0", "enc4.3", "dec4.0", "dec4.3"}, dplan
+    assert dplan["enc4.3"] == (("bnin_store", "plain", True), ("plain", "plain", True)), dplan
+    assert dplan["dec4.3"] == (("bnin_store", "plain", True), ("plain", "plain", True)) and plan["enc4.0"][2] and plan["dec4.0"][2], dplan
+    # the 24 x 24 bottleneck's up-convolution takes the first-generation DMA kernel and the DMA weight gradient
+    _, _, prod_kernels = production_plan("unet", 3)
+    here = tr.kernels - prod_kernels
+    assert {"unetdc_convT2x2_fwd|igemm_dma_kernel<__bf16, 4, 2, 2>", "unetdc_convT2x2_wgrad|wgrad_dma_kernel<__bf16, 4>"} <= here, \
+        sorted(here)
+    assert tr.calls_at[("unetdc_convT2x2_fwd", 24, 24)] == {"igemm_dma_kernel<__bf16, 4, 2, 2>"}, tr.calls_at

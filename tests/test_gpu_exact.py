@@ -769,15 +769,16 @@ REPLAY_CONFIGS = {"bf16_8x512": cfg("bf16", 8), "f32_8x512": cfg("f32", 8),
                   "dc3_bf16_1x512": cfg("bf16", 1, cin=3, adam=True), "dc3_bf16_3x512": cfg("bf16", 3, cin=3, adam=True),
                   "dc3_f32_1x512": cfg("f32", 1, cin=3, adam=True), "dc3_f32_3x512": cfg("f32", 3, cin=3, adam=True),
                   # dL/dx at the production shape: the first layer's input-gradient kernel
-                  "dc3_bf16_8x512_dx": cfg("bf16", 8, cin=3, dx=True), "dc3_f32_8x512_dx": cfg("f32", 8, cin=3, dx=True)}
+                  "dc3_bf16_8x512_dx": cfg("bf16", 8, cin=3, dx=True), "dc3_f32_8x512_dx": cfg("f32", 8, cin=3, dx=True),
+                  # train_DC_focal.py --img_size 384 --batch 5 --dtype bf16: no pixel count of the step is a power of two
+                  # (5 * 9 * 2^k: 737280 ... 2880), maps of 384, 192, 96, 48 and 24 pixels a side (see the test's docstring)
+                  "dc3_bf16_5x384": cfg("bf16", 5, 384, cin=3, adam=True)}
 # 1024^2: the forward and weight-gradient convolution calls and every non-convolution call (the host reference of the
 # whole step is over the time budget; its input-gradient calls take the same kernels as at 512^2 with twice the items per
 # workgroup)
 REPLAY_ONLY = {"bf16_4x1024": ("fwd", "wgrad")}
-# batch 3: every pixel count of the step is 3 * 2^k, and the exact fixtures of the BatchNorm runners (tests/test_gpu_exact_norm.py)
-# need power-of-two counts (k2 = k1 S1 / M must be exact).  These configs replay their convolution calls, whose routes depend
-# on the pixel count; their BatchNorm, head and loss calls take the kernels the batch-1 and batch-8 configs replay.
-REPLAY_CONV_ONLY = {"dc3_bf16_3x512", "dc3_f32_3x512"}
+# (batch 3 and 5 x 384^2: every pixel count is 3 * 2^k or 45 * 2^k; the BatchNorm runners of tests/test_gpu_exact_norm.py take any
+# count -- sums and statistics stay exact, k2 / k3 / dbias are fp64-bounded there -- so every call of those steps is replayed)
 REPLAYED = set()                # distinct calls replayed by an earlier config of this session (not replayed again)
 
 
@@ -841,7 +842,13 @@ def distinct_calls(recs):
 def test_production_step_replay(config):
     """Every distinct call of one training step (or eval forward, or frozen-statistics step), replayed with exact fixtures
     at its own shapes and leading dimensions: the same kernel, a bit-exact (or fp64-bounded) output, intact guards.  Every
-    symbol the step issued has a runner or a named exemption."""
+    symbol the step issued has a runner or a named exemption.
+
+    dc3_bf16_5x384 (train_DC_focal.py --img_size 384 --batch 5 --dtype bf16) reaches, where neither the 8 x 512^2 nor the
+    3 x 512^2 bf16 step does: the first-generation DMA kernel in bf16 (igemm_dma_kernel<__bf16, 4, 2, 2>) for the
+    up-convolution of the 24 x 24 bottleneck, wgrad_dma_kernel<__bf16, 4> for that up-convolution's weight gradient and
+    wgrad_dma_kernel<__bf16, 2> for a 3x3 one, and igemm_dma16_kernel<4, 2, 4> ring3 under unetdc_conv3x3_dgrad_colsum (at
+    512^2 every column-sum call takes the wide lattice kernel); its BatchNorm, head and loss calls run at counts 45 * 2^k."""
     c = REPLAY_CONFIGS[config]
     mode = c["mode"]
     calls = distinct_calls(record_step(**c))
@@ -851,8 +858,6 @@ def test_production_step_replay(config):
     calls = {k: v for k, v in calls.items() if k[0] in RUNNERS}
     if config in REPLAY_ONLY:
         calls = {k: v for k, v in calls.items() if k[0] in NON_CONV or any(part in k[0] for part in REPLAY_ONLY[config])}
-    if config in REPLAY_CONV_ONLY:
-        calls = {k: v for k, v in calls.items() if k[0] not in NON_CONV}
     print(f"\n{config}: {len(calls)} distinct calls, symbols issued: {issued}")
     reached = {}
     for key, (kw, kernel) in sorted(calls.items(), key=lambda kv: str(kv[0])):
@@ -869,8 +874,7 @@ def test_production_step_replay(config):
     for sym in sorted(reached):
         print(f"  {sym}: {sorted(reached[sym])}")
     for sym in issued:
-        assert sym in reached or sym in REPLAY_EXEMPT or config in REPLAY_ONLY or \
-            (config in REPLAY_CONV_ONLY and sym in NON_CONV), (config, sym)
+        assert sym in reached or sym in REPLAY_EXEMPT or config in REPLAY_ONLY, (config, sym)
     if mode == "train":
         assert ("unetdc_adam_step" in issued) == c["adam"], (config, issued)
         # the first layer's weight gradient: BatchNorm backward on load (with its coefficients) where the library supports it
@@ -880,12 +884,16 @@ def test_production_step_replay(config):
                             "unetdc_head_bwd_bnstats", "unetdc_bn_relu_bwd", "unetdc_bn_relu_bwd_head"):
             if c["loss"] != "focal" and "focal" in sym:         # combined_loss (train.py) is ATen arithmetic, no loss kernel
                 continue
-            if config in REPLAY_CONV_ONLY and sym in NON_CONV:
-                continue
             assert sym in reached, (config, sym, sorted(reached))
     elif mode == "eval":
         assert {"unetdc_bn_eval_affine", "unetdc_head_fwd"} <= set(reached), (config, sorted(reached))
     else:
         assert {"unetdc_bn_frozen_affine", "unetdc_bn_relu_bwd_frozen"} <= set(reached), (config, sorted(reached))
+    if config == "dc3_bf16_5x384":
+        # the routes the docstring names (no other config has batch 5, so none of these calls was replayed earlier)
+        assert "igemm_dma_kernel<__bf16, 4, 2, 2>" in reached["unetdc_convT2x2_fwd"], reached
+        assert "wgrad_dma_kernel<__bf16, 4>" in reached["unetdc_convT2x2_wgrad"], reached
+        assert "wgrad_dma_kernel<__bf16, 2>" in reached["unetdc_conv3x3_wgrad"], reached
+        assert "igemm_dma16_kernel<4, 2, 4> ring3" in reached["unetdc_conv3x3_dgrad_colsum"], reached
     if c["dx"]:
         assert "unetdc_conv3x3_first_dgrad" in reached, (config, sorted(reached))

@@ -2,10 +2,14 @@
 backward in all its forms, the eval and frozen affines, the sigmoid head and the fused Focal + Dice loss.
 
 Comparison rule (tests/exact_ref.py has the references):
-  - where a fixture makes the fp32 arithmetic exact (integer / power-of-two / dyadic values, power-of-two pixel counts, every
-    fp32 partial sum below 2^24 -- asserted on the fixture), the stored value must EQUAL the storage rounding of the fp64
-    reference: BatchNorm statistics (eps = 0), BatchNorm-backward sums, dgamma / dbeta / dbias, k1..k3, the head's dW / db /
-    dA and its BatchNorm sums;
+  - where a fixture makes the fp32 arithmetic exact (integer / power-of-two / dyadic values, every fp32 partial sum below
+    2^24 -- asserted on the fixture), the stored value must EQUAL the storage rounding of the fp64 reference, at ANY pixel
+    count: BatchNorm statistics (eps = 0: the totals are multiples of the count), BatchNorm-backward sums, dgamma / dbeta,
+    k1, the frozen forms' dbias, the head's dW / db / dA and its BatchNorm sums; at a power-of-two pixel count also k2, k3
+    and dbias;
+  - k2 = k1 S1 / M, k3 = k1 S2 / M and dbias = -k3 S3 at a pixel count M that is not a power of two: the fp32 rounding of the
+    fp64 reference, or its neighbour only where the reference lies within a few 2^-53 of an fp32 rounding boundary
+    (exact_ref.bn_bwd_coeff_bounds: the kernel divides in double and rounds once);
   - everything else (dy = fmaf(k1, gh, -k2) - k3 xhat, sigmoid, logs and powers of the loss, running statistics) is compared
     element by element with the fp64 reference under a bound derived from the fp32 operations of that output
     (exact_ref.within_bound: in bf16, either neighbour only where the reference lies within the bound of a rounding boundary).
@@ -96,15 +100,26 @@ def pow2_count(m):
 # ---------------------------------------------------------------------------------------------------- BatchNorm statistics
 def finalize_parts(rows, count, c, g, dev="cuda"):
     """[rows, 2, C] integer partial rows whose totals give mean m in {-2..2} and variance 4^k (k in {0, 1, 2}) per channel:
-    with eps = 0 every statistic is exact.  Rows carry a zero-sum integer wobble, so no row equals another."""
-    assert pow2_count(count), count
+    with eps = 0 every statistic is exact AT ANY COUNT (the totals are the integers m count and (var + m^2) count, and a
+    correctly rounded double division gives m and var + m^2 back: tests/test_exact_ref_cpu.py).  Rows carry a zero-sum integer
+    wobble, so no row equals another.  Where rows is the number of 256-pixel blocks of a count that is not a multiple of 256,
+    the rows are weighted as a producer leaves them: the last one carries the count % 256 remaining pixels' share."""
     m = X.ints((c,), 2, g).double()
     var = torch.pow(4.0, torch.randint(0, 3, (c,), generator=g).double())
     tot = torch.stack([m * count, (var + m * m) * count]).to(torch.int64)          # [2, C]
-    base, rem = tot // rows, tot % rows
     i = torch.arange(rows).view(rows, 1, 1)
     noise = torch.randint(-3, 4, (rows, 2, c), generator=g)
-    parts = base.view(1, 2, c) + (i < rem.view(1, 2, c)).to(torch.int64) + noise - noise.roll(1, 0)
+    if rows > 1 and rows == -(-count // 256) and count % 256:
+        wts = torch.full((rows,), 256, dtype=torch.int64)
+        wts[-1] = count % 256
+        share = (tot.view(1, 2, c) * wts.view(rows, 1, 1)) // count                # floor toward -inf: |share| <= |tot|
+        share[0] += tot - share.sum(0)
+        if rows > 2:                               # (row 0 also takes the rounding remainder, so compare with a middle row)
+            assert int(share[-1].abs().max()) < int(share[1].abs().max()), "the last row should carry the smaller share"
+    else:
+        base, rem = tot // rows, tot % rows
+        share = base.view(1, 2, c) + (i < rem.view(1, 2, c)).to(torch.int64)
+    parts = share + noise - noise.roll(1, 0)
     assert torch.equal(parts.sum(0), tot)
     assert int(parts.abs().max()) < X.EXACT_LIMIT
     if rows > 512:                              # the fp32 pre-reduction adds groups of ceil(rows / 64) rows
@@ -214,18 +229,20 @@ def head_grad_fixture(n, h, w, g, oc=1, dev="cuda"):
     return dp, p
 
 
-def bn_bwd_ref_check(ref, dyc, outs, dt, what, n, h, w, c):
+def bn_bwd_ref_check(ref, dyc, outs, dt, what, n, h, w, c, frozen=False):
+    """dy under its fp32 bound; dgamma / dbeta (integer sums) equal at any count; dbias = -k3 S3 equal at a power-of-two count
+    and in the frozen form (k1 S1: a power of two times an integer), else under exact_ref.bn_bwd_coeff_bounds."""
     check(dyc, ref["dy"], ref["dy_bound"], dt, what + " dy", (n, h, w, c))
+    exact = frozen or pow2_count(n * h * w)
     for k, o in outs.items():
         if o is not None:
-            check(o, ref[k], 0, torch.float32, f"{what} {k}")
+            check(o, ref[k], ref["dbias_bound"] if k == "dbias" and not exact else 0, torch.float32, f"{what} {k}")
 
 
 def bn_relu_bwd(kw, variant="plain", seed=33):
     """unetdc_bn_relu_bwd / _frozen / _head.  kw: the header's names (n, h, w, c, dtype, lds, optional pointers, pre_nparts)."""
     n, h, w, c, dt = kw["n"], kw["h"], kw["w"], kw["c"], TD[kw["dtype"]]
     P = n * h * w
-    assert pow2_count(P), P                       # k2 = k1 S1 / M and k3 = k1 S2 / M exact
     head = variant == "head"
     pooled = kw.get("ptr:dpool", False)
     skip = kw.get("ptr:dskip", not pooled) and not head
@@ -278,7 +295,7 @@ def bn_relu_bwd(kw, variant="plain", seed=33):
         assert X.sum_is_exact((ref["gh"] * ref["xh"]).reshape(-1, c), 0.5), "gh * xh"
     what = f"bn_relu_bwd/{variant}(N {n}, {h}x{w}, C {c}, {dt}, {'pool' if pooled else ''}{'+skip' if skip else ''}" \
            f"{f', {rows} pre rows' if pre else ''})"
-    bn_bwd_ref_check(ref, dyc, outs, dt, what, n, h, w, c)
+    bn_bwd_ref_check(ref, dyc, outs, dt, what, n, h, w, c, frozen=variant == "frozen")
     X.assert_guard(ws, what + " workspace")
     if pc is not None:
         X.assert_guard(pc, what + " pre_parts")
@@ -288,7 +305,6 @@ def bn_relu_bwd(kw, variant="plain", seed=33):
 def bn_relu_bwd_coeffs(kw, seed=34):
     n, h, w, c = kw["n"], kw["h"], kw["w"], kw["c"]
     P = n * h * w
-    assert pow2_count(P), P
     g = gen(seed)
     rows = kw.get("pre_nparts") or lib().unetdc_conv3x3_stats_rows(P, c)
     pp = pre_parts_fixture(rows, c, g)
@@ -303,11 +319,15 @@ def bn_relu_bwd_coeffs(kw, seed=34):
     torch.cuda.synchronize()
     s = pp.double().sum(0)
     k1 = gamma.double().cuda() * rs.double().cuda()
-    ref = dict(dgamma=s[1], dbeta=s[0], dbias=-(k1 * s[1] / P) * s[2], coeffs=torch.cat([k1, k1 * s[0] / P, k1 * s[1] / P]))
+    k2, k3 = k1 * s[0] / P, k1 * s[1] / P
+    ref = dict(dgamma=s[1], dbeta=s[0], dbias=-k3 * s[2], coeffs=torch.cat([k1, k2, k3]))
     what = f"bn_relu_bwd_coeffs(N {n}, {h}x{w}, C {c}, {rows} rows)"
+    # k1 = gamma rstd is a power of two at any count; k2, k3 and dbias are exact at a power-of-two count only
+    b = {k: torch.zeros_like(v) for k, v in X.bn_bwd_coeff_bounds(k2, k3, ref["dbias"]).items()} if pow2_count(P) \
+        else X.bn_bwd_coeff_bounds(k2, k3, ref["dbias"])
     for k, o in outs.items():
-        check(o, ref[k], 0, torch.float32, f"{what} {k}")
-    check(co, ref["coeffs"], 0, torch.float32, what + " k1/k2/k3")
+        check(o, ref[k], b["dbias_bound"] if k == "dbias" else 0, torch.float32, f"{what} {k}")
+    check(co, ref["coeffs"], torch.cat([torch.zeros_like(k1), b["k2_bound"], b["k3_bound"]]), torch.float32, what + " k1/k2/k3")
     X.assert_guard(pc, what + " pre_parts")
     return None
 
@@ -465,13 +485,30 @@ def focal_dice_loss(kw, seed=37):
 
 # ---------------------------------------------------------------------------------------------------- route cases
 # channel counts of the network: 64..1024 -> C / EPC = 8..128 (bf16) and 16..256 (fp32): one or several workgroup rows per
-# chunk lane set ('seg' = 256 splits) in bn_bwd_kernel; pixel counts are powers of two as at every production stage
+# chunk lane set ('seg' = 256 splits) in bn_bwd_kernel; pixel counts are powers of two as at every stage of a batch of 1, 2,
+# 4 or 8 square power-of-two images
 BN_CASES = [(2, 16, 32, 64), (1, 32, 32, 128), (2, 8, 16, 256), (1, 8, 8, 512), (2, 4, 4, 1024), (8, 64, 64, 64)]
+
+
+def levels(n, h, w):
+    """The per-level (N, h, w, C) of a step on N images of h x w: 64 channels at full size ... 1024 at 1/16."""
+    return [(n, h >> l, w >> l, 64 << l) for l in range(5)]
+
+
+# Off the power-of-two grid (counts 3 * 2^k, 5 * 2^k, 15 * 2^k, 45, 120, 4): the ragged last batch of an epoch (3 x 512^2),
+# 3 x 48 x 80 (45-pixel bottleneck, 3 x 3 x 5: below the 64-lane width, odd rows) and 2 x 96 x 160 (120-pixel bottleneck, below
+# one 256-pixel block), 5 x 24 x 40 (4800 pixels: 18 full 256-pixel blocks and a partial one, an odd number of rows) and
+# 1 x 2 x 2 (four samples per channel).
+ODD_BN_CASES = levels(3, 512, 512) + levels(3, 48, 80) + levels(2, 96, 160) + [(5, 24, 40, 128), (1, 2, 2, 1024)]
 FINALIZE_CASES = [(1, 64, 64), (37, 1 << 12, 6), (512, 1 << 17, 64), (513, 1 << 17, 128), (8192, 1 << 21, 64),
                   (2048, 1 << 19, 1024)]
+# (rows, count, C) at counts that are not powers of two; (12, 2880, 256), (19, 4800, 128) and (386, 3 * 2^15 + 300, 64): one row
+# per 256-pixel block, the last one partial (64, 192 and 44 pixels: finalize_parts gives it the smaller share)
+ODD_FINALIZE_CASES = [(3, 768, 64), (1, 45, 1024), (1, 120, 1024), (1, 4, 1024), (513, 3 * (1 << 15) + 256, 128),
+                      (3072, 3 << 18, 64), (12, 2880, 256), (19, 4800, 128), (386, 3 * (1 << 15) + 300, 64), (577, 5 * 384 * 384, 64)]
 
 
-@pytest.mark.parametrize("case", FINALIZE_CASES)
+@pytest.mark.parametrize("case", FINALIZE_CASES + ODD_FINALIZE_CASES)
 def test_exact_bn_finalize(case):
     rows, count, c = case
     bn_finalize(dict(rows=rows, count=count, c=c, eps=0.0, momentum=0.1))
@@ -494,20 +531,44 @@ def test_exact_bn_relu_bwd(case, form, dtype):
     bn_relu_bwd(kw, "frozen" if form.startswith("frozen") else "plain")
 
 
+BN_FORMS = ["skip", "pool", "skip+pool", "frozen+skip", "frozen+pool"]
+# every form at every off-grid case, except the three pooled forms at (3, 3, 5, 1024): a 2x2 max-pool needs even H and W, and
+# the network never pools such a map (H and W are multiples of 16 and the 1/16 map is not pooled).  Nothing else is left out.
+ODD_BN_ITEMS = [(case, form) for case in ODD_BN_CASES for form in BN_FORMS if not ("pool" in form and (case[1] % 2 or case[2] % 2))]
+assert len(ODD_BN_ITEMS) == len(ODD_BN_CASES) * len(BN_FORMS) - 3
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("case,form", ODD_BN_ITEMS)
+def test_bn_relu_bwd_off_the_power_of_two_grid(case, form, dtype):
+    """The same runner at pixel counts that are not powers of two (and at 4 samples per channel, 1 x 2 x 2, which is one):
+    dgamma, dbeta, the partial rows and the frozen forms stay exact; dbias under exact_ref.bn_bwd_coeff_bounds (the runner
+    chooses: equality at a power-of-two count), dy under the fp32 rule of exact_ref.bn_relu_bwd."""
+    n, h, w, c = case
+    kw = dict(n=n, h=h, w=w, c=c, dtype=DTYPES[dtype], **{"ptr:dskip": "skip" in form, "ptr:dpool": "pool" in form})
+    bn_relu_bwd(kw, "frozen" if form.startswith("frozen") else "plain")
+
+
 # (shape, rows): 300 rows (<= 512: read directly) and the unetdc_conv3x3_stats_rows count of a production map (thousands:
 # through the fp32 pre-stage)
 PRE_CASES = [((2, 16, 32, 64), "few"), ((1, 16, 16, 512), "few"), ((8, 512, 512, 64), "few"), ((8, 512, 512, 64), "production"),
              ((8, 256, 256, 128), "few"), ((8, 256, 256, 128), "production")]
+# off the power-of-two grid.  "step": the unetdc_conv3x3_stats_rows count of that map whatever it is (3072 rows at
+# 3 x 512^2 x 64, through the fp32 pre-stage; one partial row at 45 pixels); "few": 300 rows, as above
+ODD_PRE_CASES = [(c, "step") for c in ODD_BN_CASES] + [((3, 512, 512, 64), "few"), ((3, 3, 5, 1024), "few"), ((5, 24, 40, 128), "few")]
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
-@pytest.mark.parametrize("case,rows", PRE_CASES)
+@pytest.mark.parametrize("case,rows", PRE_CASES + ODD_PRE_CASES)
 def test_exact_bn_relu_bwd_pre_parts(case, rows, dtype):
     """The non-pooled form fed with a producer's partial rows: <= 512 rows read directly, thousands through the fp32 pre-stage
     (unetdc_conv3x3_stats_rows at 8 x 512^2), also through _coeffs and the head form."""
     n, h, w, c = case
     nrows = 300 if rows == "few" else lib().unetdc_conv3x3_stats_rows(n * h * w, c)
-    assert (nrows > 512) == (rows == "production"), nrows
+    if rows != "step":
+        assert (nrows > 512) == (rows == "production"), nrows
+    elif case == (3, 512, 512, 64):
+        assert nrows > 512, nrows                 # the ragged batch's first level still goes through the pre-stage
     kw = dict(n=n, h=h, w=w, c=c, dtype=DTYPES[dtype], pre_nparts=nrows, **{"ptr:pre_parts": True, "ptr:dskip": True})
     bn_relu_bwd(kw, "plain")
     bn_relu_bwd(dict(kw, **{"ptr:dbias": False}), "frozen")
@@ -517,6 +578,8 @@ def test_exact_bn_relu_bwd_pre_parts(case, rows, dtype):
 
 
 HEAD_CASES = [(2, 16, 24, 64), (1, 40, 56, 32), (3, 8, 8, 128), (8, 512, 512, 64)]
+# the head's maps of the ragged batch and of the odd geometries, a 45-pixel map (below the 64-lane width) and a 4-pixel one
+HEAD_CASES += [(3, 512, 512, 64), (3, 48, 80, 64), (2, 96, 160, 64), (5, 24, 40, 128), (3, 3, 5, 64), (1, 2, 2, 64)]
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))

@@ -549,7 +549,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
     for (long pb = (long)blockIdx.x * ppb * U; pb < P; pb += (long)gridDim.x * ppb * U) {
       long pix[U];
       bool ok[U];
-      u32x4 yraw[U], araw[U], draw[U];
+      u32x4 yraw[U], araw[U];
       float pr[U], dpv[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -562,12 +562,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
         dpv[u] = p.dprobs[o];
         if (BN && (last || !ag)) yraw[u] = ld16(yg + px * p.bn_ldy + cl * EPC);
         if (!BN || ag) araw[u] = ld16(ag + px * p.lda + cl * EPC);
-        if (oc > 0) draw[u] = ld16(dag + px * p.ldda + cl * EPC);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (!ok[u]) continue;
-        const float dz = dpv[u] * pr[u] * (1.f - pr[u]);
+        float dz = dpv[u] * pr[u] * (1.f - pr[u]);
+        asm volatile("" : "+v"(dz));                       // a rounded product in every form: no contraction into `gb += dz`
         float av[EPC], d[EPC], yv[EPC];
         if (BN && (last || !ag)) Chunk<T>::unpack(yraw[u], yv);
         if (!BN || ag) Chunk<T>::unpack(araw[u], av);
@@ -575,14 +575,28 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
 #pragma unroll
           for (int e = 0; e < EPC; ++e) av[e] = round_through<T>(fmaxf(fmaf(yv[e], sc[e], sh[e]), 0.f));
         }
-        if (oc > 0) Chunk<T>::unpack(draw[u], d);
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-          gw[e] = fmaf(dz, av[e], gw[e]);
-          d[e] = (oc > 0 ? d[e] : 0.f) + dz * wv[e];
-        }
+        for (int e = 0; e < EPC; ++e) gw[e] = fmaf(dz, av[e], gw[e]);
         if (cl == 0) gb += dz;
-        if (dag) st16(dag + pix[u] * p.ldda + cl * EPC, Chunk<T>::pack(d));     // null: the consumer recomputes it (BnBwdParams::head_w)
+        if (last) {
+          // dA = sum over the output channels of dz[oc] * w[oc][c], summed in fp32 in channel order and rounded to the
+          // storage type ONCE, on this last pass.  (Accumulating it through the stored tensor, one pass per output
+          // channel, rounded every partial sum to bf16: an extra half bf16 ulp per output channel beyond the first.)
+          const long n = pix[u] / HW, rem = pix[u] - n * HW;
+#pragma unroll
+          for (int e = 0; e < EPC; ++e) d[e] = 0.f;
+          for (int o = 0; o < p.OC; ++o) {
+            float dzo = dz;
+            if (o != oc) {
+              const long oo = (n * p.OC + o) * HW + rem;
+              const float pro = p.probs[oo];
+              dzo = p.dprobs[oo] * pro * (1.f - pro);
+            }
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) d[e] += dzo * (o == oc ? wv[e] : p.w[o * p.C + cl * EPC + e]);
+          }
+          if (dag) st16(dag + pix[u] * p.ldda + cl * EPC, Chunk<T>::pack(d));   // null: the consumer recomputes it (BnBwdParams::head_w)
+        }
         if (BN && last) {
 #pragma unroll
           for (int e = 0; e < EPC; ++e) {
