@@ -398,6 +398,35 @@ int unetdc_density_maps(const uint8_t* rgb_hwc, const uint8_t* mask, int h, int 
                         float* out_radial, float* out_spatial, unetdc_stream_t s);
 int unetdc_density_sqrt(const int64_t* x, double* out, int64_t n, unetdc_stream_t s);
 
+
+/* ---- splitting touching droplets (split.hip; the definition is DESIGN.md, "Splitting touching droplets") -----------------
+ * unetdc_edt_sq: out_d2[p] ([h][w] int32) = the exact squared Euclidean distance from pixel p of the uint8 mask [h][w]
+ *   (nonzero = foreground) to the nearest zero pixel INSIDE the image, 0 on zero pixels (scipy.ndimage's
+ *   distance_transform_edt convention: the outside of the image is not background).  A mask without any zero pixel has
+ *   no finite distance: every pixel gets UNETDC_EDT_INF.  Sides 1..16384.  workspace: at least 4 * h * w + 64 bytes
+ *   (unetdc_split_workspace(h, w) covers it).
+ * unetdc_split_stats: the outputs of unetdc_ccl_stats (same meaning, same order rule, *out_count may exceed max_out) for
+ *   the droplets that remain when every 4-connected component is cut along the saddles of its distance transform that
+ *   lie deeper than split_depth_half_px / 2 pixels below the lower of the two peaks they separate:
+ *     basins   every foreground pixel points to the largest key (D2, -index) among itself and its foreground
+ *              4-neighbours; pixels whose chains end in the same pixel form a basin, peak = D2 there;
+ *     merging  4-adjacent foreground pixels p, q of basins A != B are united iff, with S = min(D2[p], D2[q]),
+ *              P = min(peak(A), peak(B)), H2 = split_depth_half_px:  t = 4P - 4S - H2^2 <= 0  or  t^2 <= 16 H2^2 S
+ *              (that is sqrt(P) - sqrt(S) <= H2 / 2, in integers);
+ *     droplets the classes of that union-find with at least max(min_area, 1) pixels, numbered in raster order of their
+ *              first pixel.
+ *   H2 >= 2 * ceil(sqrt(h^2 + w^2)) unites everything that touches: the outputs then equal unetdc_ccl_stats bit for bit.
+ *   out_root (nullable): first-pixel index of each droplet; out_label (nullable): [h][w] int32, the 1-based number of
+ *   the droplet of every pixel, 0 on background and on dropped droplets (numbers run past max_out).
+ *   Sides 1..16384; split_depth_half_px >= 0; workspace: unetdc_split_workspace(h, w) bytes (0 for a non-positive side). */
+#define UNETDC_EDT_INF 2147483647
+int unetdc_edt_sq(const uint8_t* mask, int h, int w, int32_t* out_d2, void* workspace, int64_t workspace_bytes,
+                  unetdc_stream_t s);
+int64_t unetdc_split_workspace(int h, int w);
+int unetdc_split_stats(const uint8_t* mask, int h, int w, int min_area, int split_depth_half_px, void* workspace,
+                       int64_t workspace_bytes, int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx,
+                       int32_t* out_root, int32_t* out_label, int max_out, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

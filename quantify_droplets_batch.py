@@ -15,6 +15,9 @@ copied back.  cv2 / scikit-image are optional on the CPU path: SciPy's ``ndimage
 cross-shaped structure is skimage's ``label(connectivity=1)``; the resize of the mask to the original size reproduces what the
 reference's call computes (its interpolation flag sits in the positional slot of ``dst``, so OpenCV's default 8-bit bilinear
 runs on the {0,1} mask: unet_dc_segmentation_amd/droplets.py:MASK_RESIZE).
+``--split_touching`` counts a droplet per basin of the mask's distance transform instead of per connected component
+("Splitting touching droplets": csrc/split.hip on the device, utils/droplet_split.py on the CPU) and writes a
+16-bit label image next to every mask.
 """
 import argparse
 from pathlib import Path
@@ -78,8 +81,19 @@ def _droplet_table(area, cen_row, cen_col, px_per_um):
     return df
 
 
-def quantify(bin_mask, min_area, px_per_um):
-    """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy)."""
+def quantify_split(bin_mask, min_area, px_per_um, split_depth):
+    """CPU path of --split_touching: (the per-droplet table of the split droplets, their int32 label map)."""
+    from utils.droplet_split import half_pixels, split_labels
+    labels, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
+    d = np.maximum(area, 1)
+    return _droplet_table(area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, px_per_um), labels
+
+
+def quantify(bin_mask, min_area, px_per_um, split_depth=None):
+    """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
+    split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
+    if split_depth is not None:
+        return quantify_split(bin_mask, min_area, px_per_um, split_depth)[0]
     from scipy import ndimage
     lbl, n = ndimage.label(bin_mask)                     # 4-connectivity, labels in raster order of the first pixel
     if n:
@@ -107,13 +121,20 @@ def _outline(mask):
     return mask.astype(bool) & ~ndimage.binary_erosion(mask.astype(bool), iterations=2)
 
 
-def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir):
-    """The per-image files of run_batch (reference :66-79): mask PNG, droplet CSV, optional overlay."""
+def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels=None):
+    """The per-image files of run_batch (reference :66-79): mask PNG, droplet CSV, optional overlay; with --split_touching
+    (labels given) the 16-bit label image as well, and the overlay's outline follows the cuts."""
     Image.fromarray(mask * 255).save(str(mask_dir / f"{name}_pred.png"))
     df.to_csv(mask_dir.parent / f"{name}_droplets.csv", index=False)
+    if labels is not None:
+        from utils.droplet_split import labels_u16
+        Image.fromarray(labels_u16(labels)).save(str(mask_dir / f"{name}_labels.png"))
     if overlay_dir is not None:
         img = np.array(Image.open(fpath).convert("RGB"))
         img[_outline(mask)] = (0, 255, 0)
+        if labels is not None:
+            from utils.droplet_split import label_boundaries
+            img[label_boundaries(labels)] = (0, 255, 0)
         Image.fromarray(img).save(str(overlay_dir / f"{name}_overlay.png"))
 
 
@@ -132,29 +153,37 @@ def _density(density, dres, rgb, mask, fpath, name, writers):
 
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None):
+              density=None, split_depth=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
     masks512 = None if on_device else (probs[:, 0] > thresh).to(torch.uint8).numpy()
     if on_device:                                        # the whole batch enqueued back to back, ONE host wait (droplets.py)
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
+        split = {} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
         if density is None:
-            dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area)
+            dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, **split)
         else:                                            # the maps count every component: the table's sums serve when min_area <= 1
             from unet_dc_segmentation_amd.density import density_maps_batch
-            dev_out, sums = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, keep_sums=True)
-            dres = density_maps_batch(density["rgbs"], [o[0] for o in dev_out], sums if min_area <= 1 else None,
+            dev_out, sums = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, keep_sums=True, **split)
+            # ... and when the table is not one of split droplets: the maps keep counting connected components
+            dres = density_maps_batch(density["rgbs"], [o[0] for o in dev_out], sums if min_area <= 1 and not split else None,
                                       density["nb_layers"], density["kernel"])
     for i in range(len(tensors)):
         fpath, (oh, ow) = meta[i]
         name = Path(fpath).stem
+        labels = None
         if on_device:
-            mask_d, area, cy, cx = dev_out[i]
+            mask_d, area, cy, cx = dev_out[i][:4]
             mask, df = mask_d.cpu().numpy(), _droplet_table(area, cy, cx, px_per_um)
+            if split_depth is not None:
+                labels = dev_out[i][4].cpu().numpy()
         else:
             mask = resize_mask_like_reference(masks512[i], ow, oh)
-            df = quantify(mask, min_area, px_per_um)
+            if split_depth is None:
+                df = quantify(mask, min_area, px_per_um)
+            else:
+                df, labels = quantify_split(mask, min_area, px_per_um, split_depth)
         df.insert(0, "filename", Path(fpath).name) if not df.empty else None
         all_props.append(df)
         per_image_rows.append({"filename": Path(fpath).name, "droplet_count": len(df),
@@ -162,9 +191,9 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
         # PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
         # the writer pool (same files, same contents; main() waits for them before the summary is written)
         if writers is None:
-            _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir)
+            _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels)
         else:
-            writers[1].append(writers[0].submit(_write_outputs, mask, df, fpath, name, mask_dir, overlay_dir))
+            writers[1].append(writers[0].submit(_write_outputs, mask, df, fpath, name, mask_dir, overlay_dir, labels))
         if density is not None:
             _density(density, dres[i] if on_device else None, density["rgbs"][i], mask, fpath, name, writers)
         if writers is not None:
@@ -192,12 +221,25 @@ def build_parser():
                    help="also write radial / spatial droplet density heat maps and density_per_image.csv")
     p.add_argument("--nb_layers", type=int, default=10, help="concentric rings of the radial density map")
     p.add_argument("--density_kernel", type=int, default=21, help="spatial density Gaussian: sigma = density_kernel / 6")
+    p.add_argument("--split_touching", action="store_true",
+                   help="count touching droplets separately: cut every connected component where its distance transform dips "
+                        "more than --split_depth below the lower of two peaks; also writes predicted_masks/NAME_labels.png "
+                        "(16-bit label image).  The --density_maps outputs keep counting connected components")
+    p.add_argument("--split_depth", type=float, default=2.0,
+                   help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
+    from utils.droplet_split import half_pixels
+    try:                                                 # checked before any image, and before any output directory exists
+        split_depth = half_pixels(args.split_depth) / 2.0
+    except ValueError:
+        raise SystemExit("--split_depth must be a non-negative multiple of 0.5")
+    if not args.split_touching:
+        split_depth = None
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -245,13 +287,13 @@ def main(argv=None):
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:

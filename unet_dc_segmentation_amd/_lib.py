@@ -14,6 +14,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 import torch  # noqa: F401  (must be imported before the CDLL below -- see module docstring)
 
 F32, BF16 = 0, 1
+EDT_INF = 2 ** 31 - 1      # UNETDC_EDT_INF: the squared distance of every pixel of a mask without background
 LIB_NAME = "libunetdc_hip.so"
 LIB_PATH = os.environ.get("UNETDC_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
@@ -87,6 +88,9 @@ SIGNATURES = {
     "unetdc_density_workspace": (L, [I, I]),
     "unetdc_density_maps": (I, [P, P, I, I, P, P, P, P, I, I, D, P, P, L, P, P, P, P, P, P, P, P, P]),
     "unetdc_density_sqrt": (I, [P, P, L, P]),
+    "unetdc_edt_sq": (I, [P, I, I, P, P, L, P]),
+    "unetdc_split_workspace": (L, [I, I]),
+    "unetdc_split_stats": (I, [P, I, I, I, I, P, L, P, P, P, P, P, P, I, P]),
 }
 
 _lib = None

@@ -538,6 +538,21 @@ int unetdc_ccl_stats(const uint8_t* mask, int h, int w, int min_area, void* work
                           (hipStream_t)s);
 }
 
+int64_t unetdc_split_workspace(int h, int w) { return h > 0 && w > 0 ? split_workspace_bytes(h, w) : 0; }
+
+int unetdc_edt_sq(const uint8_t* mask, int h, int w, int32_t* out_d2, void* workspace, int64_t workspace_bytes,
+                  unetdc_stream_t s) {
+  return launch_edt_sq(mask, h, w, out_d2, workspace, (long)workspace_bytes, (hipStream_t)s);
+}
+
+int unetdc_split_stats(const uint8_t* mask, int h, int w, int min_area, int split_depth_half_px, void* workspace,
+                       int64_t workspace_bytes, int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx,
+                       int32_t* out_root, int32_t* out_label, int max_out, unetdc_stream_t s) {
+  return launch_split_stats(mask, h, w, min_area, split_depth_half_px, workspace, (long)workspace_bytes, out_count, out_area,
+                            reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root,
+                            out_label, max_out, (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

@@ -16,6 +16,7 @@
 //   ccl_count/scan/emit   roots with area >= min_area, compacted in increasing root order (three-level exclusive scan)
 // All byte / integer work: HBM-bound and tiny next to the network (a 512 x 512 mask is 256 KB).
 #include "kernels.h"
+#include "ccl_uf.h"
 
 namespace unetdc {
 
@@ -28,27 +29,6 @@ __global__ void mask_kernel(const float* __restrict__ probs, int ph, int pw, flo
     sy = sy < ph - 1 ? sy : ph - 1;
     sx = sx < pw - 1 ? sx : pw - 1;
     mask[i] = probs[(long)sy * pw + sx] > thresh ? 1 : 0;
-  }
-}
-
-// parent pointers only ever decrease and every value ever stored in L[x] is an ancestor of x in the final forest, so a
-// stale read costs extra hops, never correctness; the agent-scope relaxed loads read through to L2 anyway, where the
-// atomicMin of the merges executes
-__device__ __forceinline__ int ccl_find(const int* L, int x) {
-  int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != x) { x = p; p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  return x;
-}
-
-__device__ __forceinline__ void ccl_unite(int* L, int a, int b) {
-  for (;;) {
-    a = ccl_find(L, a);
-    b = ccl_find(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }           // a < b: hang the larger root under the smaller
-    const int old = atomicMin(&L[b], a);
-    if (old == b) return;                                   // b was still a root: done
-    b = old;                                                // somebody re-parented b meanwhile: continue from there
   }
 }
 
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __re
                                                        const unsigned long long* __restrict__ sx, int n, int min_area,
                                                        const int* __restrict__ blockoff, int max_out, int* __restrict__ out_area,
                                                        long long* __restrict__ out_sy, long long* __restrict__ out_sx,
-                                                       int* __restrict__ out_root) {
+                                                       int* __restrict__ out_root, int* __restrict__ rank_of_root) {
   // one wave per block of 1024 pixels would suffice; keep it simple: thread 0..255 handle 4 consecutive pixels each and a
   // block-level exclusive scan of the 256 per-thread counts gives every kept root its rank
   __shared__ int cnt[256];
@@ -173,6 +153,7 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __re
       if (out_root) out_root[rank] = i;
     }
     ++rank;
+    if (rank_of_root) rank_of_root[i] = rank;               // 1-based, also past max_out (split.hip's label map)
   }
 }
 
@@ -229,6 +210,31 @@ long ccl_workspace_bytes(int h, int w) {
   return n * (4 + 4 + 8 + 8) + (nb + 16) * 4 + 64;
 }
 
+CclPlanes ccl_planes(void* workspace, int n) {
+  CclPlanes p;
+  p.sy = reinterpret_cast<unsigned long long*>(workspace);
+  p.sx = p.sy + n;
+  p.L = reinterpret_cast<int*>(p.sx + n);
+  p.area = p.L + n;
+  p.blocksum = p.area + n;
+  return p;
+}
+
+void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(ccl_init_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n);
+}
+
+void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
+                       int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
+                       hipStream_t stream) {
+  const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK, g = ccl_grid(n);
+  hipLaunchKernelGGL(ccl_stats_kernel, dim3(g), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, h, w);
+  hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, stream, mask, p.L, p.area, n, min_area, p.blocksum);
+  hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, stream, p.blocksum, nb, out_count);
+  hipLaunchKernelGGL(ccl_emit_kernel, dim3(nb), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n, min_area, p.blocksum,
+                     max_out, out_area, out_sumy, out_sumx, out_root, rank_of_root);
+}
+
 int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
                      hipStream_t stream) {
@@ -240,20 +246,10 @@ int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void
   }
   const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK;
   UNETDC_REQUIRE(nb <= 1024 * 1024, "ccl_stats: image too large");
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  unsigned long long* sy = reinterpret_cast<unsigned long long*>(ws);
-  unsigned long long* sx = sy + n;
-  int* L = reinterpret_cast<int*>(sx + n);
-  int* area = L + n;
-  int* blocksum = area + n;
-  const int g = ccl_grid(n);
-  hipLaunchKernelGGL(ccl_init_kernel, dim3(g), dim3(256), 0, stream, mask, L, area, sy, sx, n);
-  hipLaunchKernelGGL(ccl_merge_kernel, dim3(g), dim3(256), 0, stream, mask, L, h, w);
-  hipLaunchKernelGGL(ccl_stats_kernel, dim3(g), dim3(256), 0, stream, mask, L, area, sy, sx, h, w);
-  hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, stream, mask, L, area, n, min_area, blocksum);
-  hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, stream, blocksum, nb, out_count);
-  hipLaunchKernelGGL(ccl_emit_kernel, dim3(nb), dim3(256), 0, stream, mask, L, area, sy, sx, n, min_area, blocksum, max_out,
-                     out_area, out_sumy, out_sumx, out_root);
+  const CclPlanes p = ccl_planes(workspace, n);
+  launch_ccl_init(mask, p, n, stream);
+  hipLaunchKernelGGL(ccl_merge_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, h, w);
+  launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, nullptr, max_out, stream);
   return check_launch("ccl kernels");
 }
 

@@ -214,6 +214,28 @@ long ccl_workspace_bytes(int h, int w);
 int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
                      hipStream_t stream);
+// the stages of launch_ccl_stats around its merge kernel, for split.hip: the planes of a ccl workspace (the first
+// ccl_workspace_bytes(h, w) bytes), their initialisation (L[i] = i, sums 0), and per-class sums -> min_area filter ->
+// raster-order compaction on whatever union-find the caller left in L.  rank_of_root (nullable, [h * w]) receives the
+// 1-based output rank at the root pixel of every kept class.  No checks, no check_launch: the caller does both.
+struct CclPlanes {
+  unsigned long long *sy, *sx;
+  int *L, *area, *blocksum;
+};
+CclPlanes ccl_planes(void* workspace, int n);
+void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipStream_t stream);
+void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
+                       int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
+                       hipStream_t stream);
+
+// split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
+long edt_workspace_bytes(int h, int w);
+int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,
+                  hipStream_t stream);
+long split_workspace_bytes(int h, int w);
+int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, int split_depth_half_px, void* workspace,
+                       long workspace_bytes, int* out_count, int* out_area, long long* out_sumy, long long* out_sumx,
+                       int* out_root, int* out_label, int max_out, hipStream_t stream);
 
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).

@@ -38,14 +38,39 @@ def resize_mask_like_reference(mask, ow, oh):
     return resize_linear_cv2_u8(np.ascontiguousarray(mask, dtype=np.uint8), ow, oh)
 
 
-def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14, keep_sums=False):
+def _stats(lib, mask, oh, ow, min_area, ws, wsb, count_ptr, area_ptr, sy_ptr, sx_ptr, cap, s, h2, label):
+    """One image's labelling + sums + compaction: unetdc_ccl_stats, or with a split depth (h2 half pixels, not None)
+    unetdc_split_stats, which also fills the int32 label plane `label` when one is given."""
+    if h2 is None:
+        _lib.call("unetdc_ccl_stats", mask.data_ptr(), oh, ow, int(max(min_area, 1)), ws.data_ptr(), wsb, count_ptr, area_ptr,
+                  sy_ptr, sx_ptr, None, cap, s)
+    else:
+        _lib.call("unetdc_split_stats", mask.data_ptr(), oh, ow, int(max(min_area, 1)), h2, ws.data_ptr(), wsb, count_ptr,
+                  area_ptr, sy_ptr, sx_ptr, None, None if label is None else label.data_ptr(), cap, s)
+
+
+def _half_pixels(split_depth):
+    if split_depth is None:
+        return None
+    from utils.droplet_split import half_pixels
+    return half_pixels(split_depth)
+
+
+def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14, keep_sums=False, split_depth=None,
+                            return_labels=False):
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs.  Every launch of the batch (mask,
     union-find, per-label sums, compaction) is enqueued back to back on the current stream into ONE set of output
     planes; the host then waits ONCE: one device->host copy brings the B droplet counts, a second the filled part of the
     per-droplet integers.  Returns a list of (mask uint8 [oh, ow] DEVICE tensor, area int64 [n], centroid_row float64
     [n], centroid_col float64 [n]) -- droplets in the reference's label order.  keep_sums=True returns (that list, the
     device outputs (count, area, sumy, sumx) or None when an image had more droplets than they hold) for
-    density.density_maps_batch."""
+    density.density_maps_batch.
+    split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
+    than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py) -- same launches otherwise, still one
+    host wait.  return_labels=True (needs a split depth) appends the int32 [oh, ow] DEVICE label map to every tuple."""
+    h2 = _half_pixels(split_depth)
+    if return_labels and h2 is None:
+        raise _lib.UnetdcError("return_labels needs a split_depth")
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -55,14 +80,16 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     lib = _lib.load()
     out_hws = [(int(h), int(w)) for h, w in out_hws]
     cap = int(min(max_droplets, max(h * w for h, w in out_hws)))
-    wsb = max(lib.unetdc_ccl_workspace(h, w) for h, w in out_hws)
+    ws_query = lib.unetdc_ccl_workspace if h2 is None else lib.unetdc_split_workspace
+    wsb = max(ws_query(h, w) for h, w in out_hws)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)           # one workspace: the launches are stream-ordered
     count = torch.zeros(B, dtype=torch.int32, device=dev)
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
     sums = torch.empty(2, B, cap, dtype=torch.int64, device=dev)
-    masks = []
+    masks, labels = [], []
     for i, (oh, ow) in enumerate(out_hws):
         mask = torch.empty(oh, ow, dtype=torch.uint8, device=dev)
+        label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels else None
         p2 = probs[i]
         if MASK_RESIZE == "nearest" or (ph == oh and pw == ow):      # same size: both rules are the identity
             _lib.call("unetdc_mask_from_probs", p2.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow, s)
@@ -72,9 +99,10 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
             yo, ya = _resize_tables(ph, oh, dev, False)
             _lib.call("unetdc_mask_from_probs_linear", p2.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow,
                       xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr(), s)
-        _lib.call("unetdc_ccl_stats", mask.data_ptr(), oh, ow, int(max(min_area, 1)), ws.data_ptr(), wsb,
-                  count[i:].data_ptr(), area[i].data_ptr(), sums[0, i].data_ptr(), sums[1, i].data_ptr(), None, cap, s)
+        _stats(lib, mask, oh, ow, min_area, ws, wsb, count[i:].data_ptr(), area[i].data_ptr(), sums[0, i].data_ptr(),
+               sums[1, i].data_ptr(), cap, s, h2, label)
         masks.append(mask)
+        labels.append(label)
     n = count.cpu().numpy().astype(np.int64)                        # the batch's only host wait
     nmax = int(min(n.max(initial=0), cap))
     a_h = area[:, :nmax].cpu().numpy().astype(np.int64)
@@ -82,19 +110,25 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     out = []
     for i, (oh, ow) in enumerate(out_hws):
         if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
-            out.append(mask_and_droplets(probs[i], thresh, (oh, ow), min_area, max_droplets=int(n[i])))
+            out.append(mask_and_droplets(probs[i], thresh, (oh, ow), min_area, max_droplets=int(n[i]), split_depth=split_depth,
+                                         return_labels=return_labels))
             continue
         a = a_h[i, :n[i]]
         d = np.maximum(a, 1)
-        out.append((masks[i], a, s_h[0, i, :n[i]].astype(np.float64) / d, s_h[1, i, :n[i]].astype(np.float64) / d))
+        out.append((masks[i], a, s_h[0, i, :n[i]].astype(np.float64) / d, s_h[1, i, :n[i]].astype(np.float64) / d)
+                   + ((labels[i],) if return_labels else ()))
     if keep_sums:
         return out, ((count, area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
     return out
 
 
-def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16):
+def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, split_depth=None, return_labels=False):
     """probs2d: [H, W] fp32 probabilities on the HIP device.  Returns (mask uint8 [oh, ow] DEVICE tensor,
-    area int64 [n], centroid_row float64 [n], centroid_col float64 [n]) -- droplets in the reference's label order."""
+    area int64 [n], centroid_row float64 [n], centroid_col float64 [n]) -- droplets in the reference's label order.
+    split_depth / return_labels: as in mask_and_droplets_batch."""
+    h2 = _half_pixels(split_depth)
+    if return_labels and h2 is None:
+        raise _lib.UnetdcError("return_labels needs a split_depth")
     if not probs2d.is_cuda or probs2d.dtype != torch.float32:
         raise _lib.UnetdcError("mask_and_droplets needs an fp32 tensor on the HIP device")
     probs2d = probs2d.contiguous()
@@ -111,19 +145,24 @@ def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16):
         yo, ya = _resize_tables(ph, oh, dev, False)
         _lib.call("unetdc_mask_from_probs_linear", probs2d.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow,
                   xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr(), s)
-    nbytes = _lib.load().unetdc_ccl_workspace(oh, ow)
+    lib = _lib.load()
+    nbytes = lib.unetdc_ccl_workspace(oh, ow) if h2 is None else lib.unetdc_split_workspace(oh, ow)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     cap = int(min(max_droplets, oh * ow))
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     area = torch.empty(cap, dtype=torch.int32, device=dev)
     sy = torch.empty(cap, dtype=torch.int64, device=dev)
     sx = torch.empty(cap, dtype=torch.int64, device=dev)
-    _lib.call("unetdc_ccl_stats", mask.data_ptr(), oh, ow, int(max(min_area, 1)), ws.data_ptr(), nbytes, count.data_ptr(),
-              area.data_ptr(), sy.data_ptr(), sx.data_ptr(), None, cap, s)
+    label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels else None
+    _stats(lib, mask, oh, ow, min_area, ws, nbytes, count.data_ptr(), area.data_ptr(), sy.data_ptr(), sx.data_ptr(), cap, s, h2,
+           label)
     n = int(count.item())
     if n > cap:                                   # more droplets than the output capacity: run again with room for all
-        return mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=n)
+        return mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=n, split_depth=split_depth,
+                                 return_labels=return_labels)
     a = area[:n].cpu().numpy().astype(np.int64)
     cy = sy[:n].cpu().numpy().astype(np.float64) / np.maximum(a, 1)
     cx = sx[:n].cpu().numpy().astype(np.float64) / np.maximum(a, 1)
+    if return_labels:
+        return mask, a, cy, cx, label
     return mask, a, cy, cx
