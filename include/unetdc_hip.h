@@ -427,6 +427,34 @@ int unetdc_split_stats(const uint8_t* mask, int h, int w, int min_area, int spli
                        int64_t workspace_bytes, int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx,
                        int32_t* out_root, int32_t* out_label, int max_out, unetdc_stream_t s);
 
+
+/* ---- per-droplet shape and intensity integers (ccl.hip, shape.hip; the definition is DESIGN.md section 11) -----------------
+ * unetdc_ccl_labels: the outputs of unetdc_ccl_stats (same meaning, same order rule, *out_count may exceed max_out, out_root
+ *   nullable) plus out_label ([h][w] int32, required): the 1-based number of the droplet of every pixel, 0 on background
+ *   and on components below min_area (numbers run past max_out), as unetdc_split_stats writes it.
+ *   workspace: unetdc_ccl_labels_workspace(h, w) bytes (0 for a non-positive side).
+ * unetdc_label_props: label ([h][w] int32: 0 = background, droplets 1..K; any label map, touching labels allowed) and
+ *   optionally gray ([h][w] uint8, NULL = none) -> out[UNETDC_SHAPE_QUANTITIES][max_out] int64, row q of droplet k at
+ *   out[q * max_out + k - 1]:
+ *     0..2   Syy, Sxx, Sxy      sums of y^2, x^2, x * y over the droplet's pixels
+ *     3..6   min_y, min_x, max_y, max_x   bounding box, inclusive
+ *     7..9   P1, P2, P3         border pixels by perimeter class: a pixel of label k is a border pixel if one of its
+ *                               4-neighbours lies outside the image or has another label; its code is 1 + 2 * (border
+ *                               4-neighbours of label k) + 10 * (border diagonal neighbours of label k); P1 counts the codes
+ *                               {5, 7, 15, 17, 25, 27}, P2 {21, 33}, P3 {13, 23}
+ *                               (perimeter = P1 + sqrt(2) P2 + (1 + sqrt(2)) / 2 P3, applied by the caller)
+ *     10..13 Sg, Sgg, min_g, max_g   sum, sum of squares, minimum, maximum of gray over the droplet's pixels
+ *   Every row is initialised for all max_out droplets: sums and counts 0, minima INT64_MAX, maxima -1; that is what a
+ *   number without pixels keeps, and what rows 10..13 keep when gray is NULL.  Labels below 1 or above max_out are
+ *   skipped.  Sides 1..16384.  No workspace.  Integer atomics only: bitwise reproducible. */
+#define UNETDC_SHAPE_QUANTITIES 14
+int64_t unetdc_ccl_labels_workspace(int h, int w);
+int unetdc_ccl_labels(const uint8_t* mask, int h, int w, int min_area, void* workspace, int64_t workspace_bytes,
+                      int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx, int32_t* out_root,
+                      int32_t* out_label, int max_out, unetdc_stream_t s);
+int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, int64_t* out, int max_out,
+                       unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ runs on the {0,1} mask: unet_dc_segmentation_amd/droplets.py:MASK_RESIZE).
 ``--split_touching`` counts a droplet per basin of the mask's distance transform instead of per connected component
 ("Splitting touching droplets": csrc/split.hip on the device, utils/droplet_split.py on the CPU) and writes a
 16-bit label image next to every mask.
+``--droplet_shape`` adds the shape and intensity columns of DESIGN.md section 11 to every droplet table (perimeter,
+circularity, axes, eccentricity, orientation, bounding box, touches_border, intensity of the original image): exact integers
+per droplet from csrc/shape.hip on the device or utils/droplet_shape.py on the CPU, one derivation for both.
 """
 import argparse
 from pathlib import Path
@@ -89,6 +92,36 @@ def quantify_split(bin_mask, min_area, px_per_um, split_depth):
     return _droplet_table(area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, px_per_um), labels
 
 
+def add_shape_columns(df, props, hw, px_per_um):
+    """--droplet_shape: the columns of utils.droplet_shape.shape_columns behind the table's own."""
+    if df.empty:
+        return df
+    from utils.droplet_shape import shape_columns
+    for name, col in shape_columns(props, hw, px_per_um).items():
+        df[name] = col
+    return df
+
+
+def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
+    """CPU path of --droplet_shape: (table with the shape columns, label map or None without a split depth).  Centroids are
+    the integer sums over the area, as on the device."""
+    from scipy import ndimage
+    from utils.droplet_shape import label_props_numpy
+    if split_depth is not None:
+        from utils.droplet_split import half_pixels, split_labels
+        labels = split_labels(bin_mask, half_pixels(split_depth), min_area)[0]
+    else:
+        labels, n = ndimage.label(bin_mask)
+        if n:
+            keep = np.bincount(labels.ravel(), minlength=n + 1) >= max(min_area, 1)
+            keep[0] = False
+            labels = ndimage.label(keep[labels])[0]
+    props = label_props_numpy(labels, gray)
+    d = np.maximum(props["area"], 1)
+    df = _droplet_table(props["area"], props["Sy"].astype(np.float64) / d, props["Sx"].astype(np.float64) / d, px_per_um)
+    return add_shape_columns(df, props, bin_mask.shape, px_per_um), (labels if split_depth is not None else None)
+
+
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
     """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
     split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
@@ -153,7 +186,7 @@ def _density(density, dres, rgb, mask, fpath, name, writers):
 
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None):
+              density=None, split_depth=None, shape=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
@@ -161,6 +194,8 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
     if on_device:                                        # the whole batch enqueued back to back, ONE host wait (droplets.py)
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
         split = {} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
+        if shape is not None:                            # the grey planes go up behind the network's launches
+            split.update(shape=True, gray=[torch.from_numpy(g).to(DEVICE) for g in shape["grays"]])
         if density is None:
             dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, **split)
         else:                                            # the maps count every component: the table's sums serve when min_area <= 1
@@ -178,9 +213,13 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
             mask, df = mask_d.cpu().numpy(), _droplet_table(area, cy, cx, px_per_um)
             if split_depth is not None:
                 labels = dev_out[i][4].cpu().numpy()
+            if shape is not None:
+                df = add_shape_columns(df, dev_out[i][-1], (oh, ow), px_per_um)
         else:
             mask = resize_mask_like_reference(masks512[i], ow, oh)
-            if split_depth is None:
+            if shape is not None:
+                df, labels = quantify_shape(mask, min_area, px_per_um, split_depth, shape["grays"][i])
+            elif split_depth is None:
                 df = quantify(mask, min_area, px_per_um)
             else:
                 df, labels = quantify_split(mask, min_area, px_per_um, split_depth)
@@ -225,6 +264,10 @@ def build_parser():
                    help="count touching droplets separately: cut every connected component where its distance transform dips "
                         "more than --split_depth below the lower of two peaks; also writes predicted_masks/NAME_labels.png "
                         "(16-bit label image).  The --density_maps outputs keep counting connected components")
+    p.add_argument("--droplet_shape", action="store_true",
+                   help="add shape and intensity columns to the droplet tables: perimeter, circularity, major / minor axis, "
+                        "eccentricity, orientation, bounding box, touches_border, and mean / min / max / std of the original "
+                        "image (as grey) under each droplet")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -253,6 +296,7 @@ def main(argv=None):
         if not 1 <= args.nb_layers <= 255 or not 0 < args.density_kernel or int(4 * args.density_kernel / 6 + 0.5) > 128:
             raise SystemExit("--nb_layers must be in 1..255 and --density_kernel in 1..192")
         density = {"nb_layers": args.nb_layers, "kernel": args.density_kernel, "rows": [], "rgbs": [], "out_dir": out_dir}
+    shape = {"grays": []} if args.droplet_shape else None
     model = load_model(args.ckpt_path, args.dtype)
     tensors, meta, per_image_rows, all_props = [], [], [], []
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in {".png", ".jpg", ".jpeg", ".tif", ".tiff"})
@@ -278,22 +322,28 @@ def main(argv=None):
         while ahead:
             img, fut = ahead.popleft()
             refill()
+            im = fut.result()
+            if shape is not None:                        # the ORIGINAL image as grey, before the rolling ball
+                from utils.density import rgb_to_gray
+                shape["grays"].append(rgb_to_gray(im))
             if density is None:
-                t, osize = preprocess(img, args.background_radius, fut.result())
+                t, osize = preprocess(img, args.background_radius, im)
             else:
-                t, osize, rgb = preprocess(img, args.background_radius, fut.result(), keep_rgb=True)
+                t, osize, rgb = preprocess(img, args.background_radius, im, keep_rgb=True)
                 density["rgbs"].append(rgb)
             tensors.append(t)
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
+                if shape is not None:
+                    shape["grays"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:

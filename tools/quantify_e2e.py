@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """End-to-end throughput of the quantify_droplets_batch.py SCRIPT (file decode, preprocessing, network, droplet tables,
 mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG files:
-    python3 tools/quantify_e2e.py [N] [dtype] [--density_maps] [--split_touching]
+    python3 tools/quantify_e2e.py [N] [dtype] [--density_maps] [--split_touching] [--droplet_shape]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
---split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth)."""
+--split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
+--droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns)."""
 import os
 import sys
 import tempfile
@@ -19,6 +20,7 @@ from models.model_2 import UNetDC
 
 density = "--density_maps" in sys.argv
 split = "--split_touching" in sys.argv
+shape = "--droplet_shape" in sys.argv
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 64
 dtype = pos[1] if len(pos) > 1 else "bf16"
@@ -44,8 +46,9 @@ with tempfile.TemporaryDirectory() as d:
     argv = ["--img_dir", ind, "--ckpt_path", ck, "--out_dir", out, "--dtype", dtype, "--skip_excel", "--skip_histogram"]
     argv += ["--density_maps"] if density else []
     argv += ["--split_touching"] if split else []
+    argv += ["--droplet_shape"] if shape else []
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''})")

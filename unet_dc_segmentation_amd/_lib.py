@@ -91,6 +91,9 @@ SIGNATURES = {
     "unetdc_edt_sq": (I, [P, I, I, P, P, L, P]),
     "unetdc_split_workspace": (L, [I, I]),
     "unetdc_split_stats": (I, [P, I, I, I, I, P, L, P, P, P, P, P, P, I, P]),
+    "unetdc_ccl_labels_workspace": (L, [I, I]),
+    "unetdc_ccl_labels": (I, [P, I, I, I, P, L, P, P, P, P, P, P, I, P]),
+    "unetdc_label_props": (I, [P, P, I, I, P, I, P]),
 }
 
 _lib = None

@@ -553,6 +553,22 @@ int unetdc_split_stats(const uint8_t* mask, int h, int w, int min_area, int spli
                             out_label, max_out, (hipStream_t)s);
 }
 
+int64_t unetdc_ccl_labels_workspace(int h, int w) { return h > 0 && w > 0 ? ccl_labels_workspace_bytes(h, w) : 0; }
+
+int unetdc_ccl_labels(const uint8_t* mask, int h, int w, int min_area, void* workspace, int64_t workspace_bytes,
+                      int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx, int32_t* out_root,
+                      int32_t* out_label, int max_out, unetdc_stream_t s) {
+  return launch_ccl_labels(mask, h, w, min_area, workspace, (long)workspace_bytes, out_count, out_area,
+                           reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root, out_label,
+                           max_out, (hipStream_t)s);
+}
+
+static_assert(UNETDC_SHAPE_QUANTITIES == SHAPE_QUANTITIES, "unetdc_label_props output rows");
+
+int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, int64_t* out, int max_out, unetdc_stream_t s) {
+  return launch_label_props(label, gray, h, w, reinterpret_cast<long long*>(out), max_out, (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

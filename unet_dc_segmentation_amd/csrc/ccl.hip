@@ -14,6 +14,7 @@
 //   ccl_init/merge/compress   label equivalence by lock-free union-find (atomicMin towards the smaller root)
 //   ccl_stats        integer atomics into per-root accumulators: exact and order-independent (bitwise reproducible)
 //   ccl_count/scan/emit   roots with area >= min_area, compacted in increasing root order (three-level exclusive scan)
+//   ccl_label        the int32 label map from the rank the emit kernel left at every kept root (unetdc_ccl_labels, split.hip)
 // All byte / integer work: HBM-bound and tiny next to the network (a 512 x 512 mask is 256 KB).
 #include "kernels.h"
 #include "ccl_uf.h"
@@ -157,6 +158,19 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __re
   }
 }
 
+// label[i] = the 1-based output rank of pixel i's class, 0 on background and on classes below min_area
+__global__ void ccl_label_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ L, const int* __restrict__ area,
+                                 const int* __restrict__ rank_of_root, int min_area, int* __restrict__ label, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    int v = 0;
+    if (mask[i]) {
+      const int r = L[i];                                   // compressed by ccl_stats_kernel
+      if (area[r] >= min_area) v = rank_of_root[r];
+    }
+    label[i] = v;
+  }
+}
+
 static int ccl_grid(long n) {
   long nb = (n + 255) / 256;
   if (nb > 4096) nb = 4096;
@@ -235,6 +249,12 @@ void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, co
                      max_out, out_area, out_sumy, out_sumx, out_root, rank_of_root);
 }
 
+void launch_ccl_label(const unsigned char* mask, const CclPlanes& p, const int* rank_of_root, int min_area, int* label, int n,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL(ccl_label_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, p.area, rank_of_root, min_area, label,
+                     n);
+}
+
 int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
                      hipStream_t stream) {
@@ -251,6 +271,29 @@ int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void
   hipLaunchKernelGGL(ccl_merge_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, h, w);
   launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, nullptr, max_out, stream);
   return check_launch("ccl kernels");
+}
+
+// the ccl planes, then the rank of every kept component at its root pixel
+long ccl_labels_workspace_bytes(int h, int w) { return ((ccl_workspace_bytes(h, w) + 63) / 64) * 64 + (long)h * w * 4 + 64; }
+
+int launch_ccl_labels(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
+                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
+                      int max_out, hipStream_t stream) {
+  UNETDC_REQUIRE(mask && workspace && out_count && out_area && out_sumy && out_sumx && out_label, "ccl_labels: null pointer");
+  UNETDC_REQUIRE(h > 0 && w > 0 && (long)h * w < (1L << 30) && max_out >= 0, "ccl_labels: bad geometry");
+  if (workspace_bytes < ccl_labels_workspace_bytes(h, w)) {
+    set_error("ccl_labels: workspace too small (%ld < %ld bytes)", workspace_bytes, ccl_labels_workspace_bytes(h, w));
+    return UNETDC_EWORKSPACE;
+  }
+  const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK;
+  UNETDC_REQUIRE(nb <= 1024 * 1024, "ccl_labels: image too large");
+  const CclPlanes p = ccl_planes(workspace, n);
+  int* rank = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(workspace) + ((ccl_workspace_bytes(h, w) + 63) / 64) * 64);
+  launch_ccl_init(mask, p, n, stream);
+  hipLaunchKernelGGL(ccl_merge_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, h, w);
+  launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, rank, max_out, stream);
+  launch_ccl_label(mask, p, rank, min_area, out_label, n, stream);
+  return check_launch("ccl label kernels");
 }
 
 }  // namespace unetdc

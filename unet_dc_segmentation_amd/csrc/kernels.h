@@ -227,6 +227,19 @@ void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipSt
 void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
                        int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
                        hipStream_t stream);
+// label[i] = rank_of_root[L[i]] on the foreground pixels of classes with at least min_area pixels, 0 elsewhere (after
+// launch_ccl_finish, which compresses L and fills rank_of_root)
+void launch_ccl_label(const unsigned char* mask, const CclPlanes& p, const int* rank_of_root, int min_area, int* label, int n,
+                      hipStream_t stream);
+long ccl_labels_workspace_bytes(int h, int w);
+int launch_ccl_labels(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
+                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
+                      int max_out, hipStream_t stream);
+
+// shape.hip: per-label second moments, bounding box, perimeter classes and grey statistics of an int32 label map
+constexpr int SHAPE_QUANTITIES = 14;
+int launch_label_props(const int* label, const unsigned char* gray, int h, int w, long long* out, int max_out,
+                       hipStream_t stream);
 
 // split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
 long edt_workspace_bytes(int h, int w);

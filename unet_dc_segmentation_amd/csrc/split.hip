@@ -14,7 +14,7 @@
 //                     as they are walked, like ccl_stats_kernel compresses L
 //   split_merge       for every foreground pair (p, right / down neighbour): same basin, or
 //                     sqrt(min peak) - sqrt(min(D2[p], D2[q])) <= H2 / 2 in integers  ->  ccl_unite in the union-find L
-//   launch_ccl_finish (ccl.hip) per-class sums, min_area, raster-order compaction;  split_label: the int32 label map
+//   launch_ccl_finish (ccl.hip) per-class sums, min_area, raster-order compaction;  launch_ccl_label: the int32 label map
 #include "kernels.h"
 #include "ccl_uf.h"
 
@@ -129,18 +129,6 @@ __global__ void split_merge_kernel(const unsigned char* __restrict__ mask, const
   }
 }
 
-__global__ void split_label_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ L, const int* __restrict__ area,
-                                   const int* __restrict__ rank_of_root, int min_area, int* __restrict__ label, int n) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    int v = 0;
-    if (mask[i]) {
-      const int r = L[i];                                   // compressed by ccl_stats_kernel
-      if (area[r] >= min_area) v = rank_of_root[r];
-    }
-    label[i] = v;
-  }
-}
-
 static int split_grid(long n) {
   long nb = (n + 255) / 256;
   if (nb > 4096) nb = 4096;
@@ -196,8 +184,7 @@ int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, in
   // B is free again: it takes the rank of every kept class at its root pixel
   launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, out_label ? B : nullptr, max_out,
                     stream);
-  if (out_label)
-    hipLaunchKernelGGL(split_label_kernel, dim3(g), dim3(256), 0, stream, mask, p.L, p.area, B, min_area, out_label, n);
+  if (out_label) launch_ccl_label(mask, p, B, min_area, out_label, n, stream);
   return check_launch("split kernels");
 }
 

@@ -49,6 +49,38 @@ def _stats(lib, mask, oh, ow, min_area, ws, wsb, count_ptr, area_ptr, sy_ptr, sx
                   area_ptr, sy_ptr, sx_ptr, None, None if label is None else label.data_ptr(), cap, s)
 
 
+def _stats_labels(lib, mask, oh, ow, min_area, ws, wsb, count_ptr, area_ptr, sy_ptr, sx_ptr, cap, s, h2, label, gray, props_ptr):
+    """_stats with the label map on either path (unetdc_ccl_labels without a split depth), then unetdc_label_props on
+    that map and the optional uint8 grey plane: the shape integers [UNETDC_SHAPE_QUANTITIES][cap] at props_ptr."""
+    if h2 is None:
+        _lib.call("unetdc_ccl_labels", mask.data_ptr(), oh, ow, int(max(min_area, 1)), ws.data_ptr(), wsb, count_ptr, area_ptr,
+                  sy_ptr, sx_ptr, None, label.data_ptr(), cap, s)
+    else:
+        _stats(lib, mask, oh, ow, min_area, ws, wsb, count_ptr, area_ptr, sy_ptr, sx_ptr, cap, s, h2, label)
+    _lib.call("unetdc_label_props", label.data_ptr(), None if gray is None else gray.data_ptr(), oh, ow, props_ptr, cap, s)
+
+
+def _check_gray(gray, oh, ow):
+    if gray is not None and (not gray.is_cuda or gray.dtype != torch.uint8 or tuple(gray.shape) != (oh, ow)
+                             or not gray.is_contiguous()):
+        raise _lib.UnetdcError("gray must be a contiguous uint8 [oh, ow] tensor on the HIP device")
+
+
+def _props_dict(area, sumy, sumx, rows, with_gray):
+    """The integers utils.droplet_shape.shape_columns reads, under the names of label_props_numpy."""
+    from utils.droplet_shape import GRAY_QUANTITIES, QUANTITIES
+    out = {"area": area, "Sy": sumy, "Sx": sumx}
+    out.update((q, rows[j]) for j, q in enumerate(QUANTITIES) if with_gray or q not in GRAY_QUANTITIES)
+    return out
+
+
+def _ws_query(lib, h2, shape):
+    return lib.unetdc_split_workspace if h2 is not None else lib.unetdc_ccl_labels_workspace if shape else lib.unetdc_ccl_workspace
+
+
+NQ = 14    # UNETDC_SHAPE_QUANTITIES
+
+
 def _half_pixels(split_depth):
     if split_depth is None:
         return None
@@ -57,7 +89,7 @@ def _half_pixels(split_depth):
 
 
 def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14, keep_sums=False, split_depth=None,
-                            return_labels=False):
+                            return_labels=False, shape=False, gray=None):
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs.  Every launch of the batch (mask,
     union-find, per-label sums, compaction) is enqueued back to back on the current stream into ONE set of output
     planes; the host then waits ONCE: one device->host copy brings the B droplet counts, a second the filled part of the
@@ -67,10 +99,17 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     density.density_maps_batch.
     split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
     than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py) -- same launches otherwise, still one
-    host wait.  return_labels=True (needs a split depth) appends the int32 [oh, ow] DEVICE label map to every tuple."""
+    host wait.  return_labels=True (needs a split depth or shape=True) appends the int32 [oh, ow] DEVICE label map to
+    every tuple.
+    shape=True appends, last, the dict of per-droplet int64 arrays that utils.droplet_shape.shape_columns reads (area, Sy,
+    Sx and the rows of unetdc_label_props); gray: B uint8 [oh, ow] DEVICE tensors (or None: no intensity integers).  The
+    label map and the props launches follow each image's existing ones, and the integers travel in the copies the host
+    already waits for."""
     h2 = _half_pixels(split_depth)
-    if return_labels and h2 is None:
-        raise _lib.UnetdcError("return_labels needs a split_depth")
+    if return_labels and h2 is None and not shape:
+        raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
+    if gray is not None and not shape:
+        raise _lib.UnetdcError("gray needs shape=True")
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -80,16 +119,21 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     lib = _lib.load()
     out_hws = [(int(h), int(w)) for h, w in out_hws]
     cap = int(min(max_droplets, max(h * w for h, w in out_hws)))
-    ws_query = lib.unetdc_ccl_workspace if h2 is None else lib.unetdc_split_workspace
-    wsb = max(ws_query(h, w) for h, w in out_hws)
+    if gray is not None:
+        for g, (oh, ow) in zip(gray, out_hws):
+            _check_gray(g, oh, ow)
+    wsb = max(_ws_query(lib, h2, shape)(h, w) for h, w in out_hws)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)           # one workspace: the launches are stream-ordered
     count = torch.zeros(B, dtype=torch.int32, device=dev)
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    sums = torch.empty(2, B, cap, dtype=torch.int64, device=dev)
+    if shape:          # per image: sum y, sum x, then the rows of unetdc_label_props, which wants them [NQ][cap] in one piece
+        sums = torch.empty(B, 2 + NQ, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
+    else:
+        sums = torch.empty(2, B, cap, dtype=torch.int64, device=dev)
     masks, labels = [], []
     for i, (oh, ow) in enumerate(out_hws):
         mask = torch.empty(oh, ow, dtype=torch.uint8, device=dev)
-        label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels else None
+        label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels or shape else None
         p2 = probs[i]
         if MASK_RESIZE == "nearest" or (ph == oh and pw == ow):      # same size: both rules are the identity
             _lib.call("unetdc_mask_from_probs", p2.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow, s)
@@ -99,8 +143,12 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
             yo, ya = _resize_tables(ph, oh, dev, False)
             _lib.call("unetdc_mask_from_probs_linear", p2.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow,
                       xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr(), s)
-        _stats(lib, mask, oh, ow, min_area, ws, wsb, count[i:].data_ptr(), area[i].data_ptr(), sums[0, i].data_ptr(),
-               sums[1, i].data_ptr(), cap, s, h2, label)
+        if shape:
+            _stats_labels(lib, mask, oh, ow, min_area, ws, wsb, count[i:].data_ptr(), area[i].data_ptr(), sums[0, i].data_ptr(),
+                          sums[1, i].data_ptr(), cap, s, h2, label, None if gray is None else gray[i], sums[2, i].data_ptr())
+        else:
+            _stats(lib, mask, oh, ow, min_area, ws, wsb, count[i:].data_ptr(), area[i].data_ptr(), sums[0, i].data_ptr(),
+                   sums[1, i].data_ptr(), cap, s, h2, label)
         masks.append(mask)
         labels.append(label)
     n = count.cpu().numpy().astype(np.int64)                        # the batch's only host wait
@@ -111,24 +159,28 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     for i, (oh, ow) in enumerate(out_hws):
         if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
             out.append(mask_and_droplets(probs[i], thresh, (oh, ow), min_area, max_droplets=int(n[i]), split_depth=split_depth,
-                                         return_labels=return_labels))
+                                         return_labels=return_labels, shape=shape, gray=None if gray is None else gray[i]))
             continue
         a = a_h[i, :n[i]]
         d = np.maximum(a, 1)
         out.append((masks[i], a, s_h[0, i, :n[i]].astype(np.float64) / d, s_h[1, i, :n[i]].astype(np.float64) / d)
-                   + ((labels[i],) if return_labels else ()))
+                   + ((labels[i],) if return_labels else ())
+                   + ((_props_dict(a, s_h[0, i, :n[i]], s_h[1, i, :n[i]], s_h[2:, i, :n[i]], gray is not None),) if shape else ()))
     if keep_sums:
         return out, ((count, area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
     return out
 
 
-def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, split_depth=None, return_labels=False):
+def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, split_depth=None, return_labels=False,
+                      shape=False, gray=None):
     """probs2d: [H, W] fp32 probabilities on the HIP device.  Returns (mask uint8 [oh, ow] DEVICE tensor,
     area int64 [n], centroid_row float64 [n], centroid_col float64 [n]) -- droplets in the reference's label order.
-    split_depth / return_labels: as in mask_and_droplets_batch."""
+    split_depth / return_labels / shape / gray (one uint8 [oh, ow] DEVICE tensor): as in mask_and_droplets_batch."""
     h2 = _half_pixels(split_depth)
-    if return_labels and h2 is None:
-        raise _lib.UnetdcError("return_labels needs a split_depth")
+    if return_labels and h2 is None and not shape:
+        raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
+    if gray is not None and not shape:
+        raise _lib.UnetdcError("gray needs shape=True")
     if not probs2d.is_cuda or probs2d.dtype != torch.float32:
         raise _lib.UnetdcError("mask_and_droplets needs an fp32 tensor on the HIP device")
     probs2d = probs2d.contiguous()
@@ -146,23 +198,31 @@ def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, s
         _lib.call("unetdc_mask_from_probs_linear", probs2d.data_ptr(), ph, pw, float(thresh), mask.data_ptr(), oh, ow,
                   xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr(), s)
     lib = _lib.load()
-    nbytes = lib.unetdc_ccl_workspace(oh, ow) if h2 is None else lib.unetdc_split_workspace(oh, ow)
+    _check_gray(gray, oh, ow)
+    nbytes = _ws_query(lib, h2, shape)(oh, ow)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     cap = int(min(max_droplets, oh * ow))
     count = torch.zeros(1, dtype=torch.int32, device=dev)
     area = torch.empty(cap, dtype=torch.int32, device=dev)
     sy = torch.empty(cap, dtype=torch.int64, device=dev)
     sx = torch.empty(cap, dtype=torch.int64, device=dev)
-    label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels else None
-    _stats(lib, mask, oh, ow, min_area, ws, nbytes, count.data_ptr(), area.data_ptr(), sy.data_ptr(), sx.data_ptr(), cap, s, h2,
-           label)
+    label = torch.empty(oh, ow, dtype=torch.int32, device=dev) if return_labels or shape else None
+    if shape:
+        rows = torch.empty(NQ, cap, dtype=torch.int64, device=dev)
+        _stats_labels(lib, mask, oh, ow, min_area, ws, nbytes, count.data_ptr(), area.data_ptr(), sy.data_ptr(), sx.data_ptr(),
+                      cap, s, h2, label, gray, rows.data_ptr())
+    else:
+        _stats(lib, mask, oh, ow, min_area, ws, nbytes, count.data_ptr(), area.data_ptr(), sy.data_ptr(), sx.data_ptr(), cap, s,
+               h2, label)
     n = int(count.item())
     if n > cap:                                   # more droplets than the output capacity: run again with room for all
         return mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=n, split_depth=split_depth,
-                                 return_labels=return_labels)
+                                 return_labels=return_labels, shape=shape, gray=gray)
     a = area[:n].cpu().numpy().astype(np.int64)
-    cy = sy[:n].cpu().numpy().astype(np.float64) / np.maximum(a, 1)
-    cx = sx[:n].cpu().numpy().astype(np.float64) / np.maximum(a, 1)
-    if return_labels:
-        return mask, a, cy, cx, label
-    return mask, a, cy, cx
+    sy_h, sx_h = sy[:n].cpu().numpy(), sx[:n].cpu().numpy()
+    cy = sy_h.astype(np.float64) / np.maximum(a, 1)
+    cx = sx_h.astype(np.float64) / np.maximum(a, 1)
+    out = (mask, a, cy, cx) + ((label,) if return_labels else ())
+    if shape:
+        out += (_props_dict(a, sy_h, sx_h, rows[:, :n].cpu().numpy(), gray is not None),)
+    return out
