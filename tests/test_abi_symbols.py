@@ -61,6 +61,36 @@ def test_host_only_queries_and_error_reporting(lib):
     assert rc == -1 and b"geometry" in lib.unetdc_last_error()
 
 
+def test_wgrad_workspace_and_bnin_answers_are_the_recorded_ones(lib, golden_dir):
+    """The host-only planning answers of the 3x3 weight gradient, against tests/golden/wgrad_abi_answers.json: every
+    unetdc_conv3x3_wgrad_workspace and unetdc_conv3x3_bnin_supported value over fp32 / bf16, n in {1, 3, 5, 8}, five image
+    sizes from 64^2 to 1024^2, the 13 channel pairs of the networks and d in {1, 2, 4, 8}.  The table was recorded from the
+    library of the commit BEFORE the tap-fused route got its single plan (plan_wgrad_fused); a change of the planning code
+    must reproduce it, or say why an answer moves."""
+    import json
+    t = json.load(open(os.path.join(golden_dir, "wgrad_abi_answers.json")))
+    assert t["dtypes"] == [0, 1] and t["n"] == [1, 3, 5, 8] and t["d"] == [1, 2, 4, 8]
+    assert [64, 64] in t["hw"] and [96, 128] in t["hw"] and [1024, 1024] in t["hw"] and len(t["hw"]) == 5 and len(t["pairs"]) == 13
+    checked, bad = 0, []
+    for a, dt in enumerate(t["dtypes"]):
+        for b, n in enumerate(t["n"]):
+            for c, (h, w) in enumerate(t["hw"]):
+                for e, (cin, cout) in enumerate(t["pairs"]):
+                    got = lib.unetdc_conv3x3_wgrad_workspace(n, h, w, cin, cout, dt)
+                    want = t["workspace"][a][b][c][e]
+                    checked += 1
+                    if got != want:
+                        bad.append(("workspace", dt, n, h, w, cin, cout, got, want))
+                    for f, d in enumerate(t["d"]):
+                        got = lib.unetdc_conv3x3_bnin_supported(n, h, w, cin, cout, d, dt)
+                        want = t["bnin_supported"][a][b][c][e][f]
+                        checked += 1
+                        if got != want:
+                            bad.append(("bnin_supported", dt, n, h, w, cin, cout, d, got, want))
+    assert checked == 520 + 2080
+    assert not bad, bad[:10]
+
+
 def test_no_kernel_carries_packed_fp32(lib):
     """Build guard (widened in round 3 to EVERY kernel of the library): the packed-fp32 (SLP-vectorised) build
     of the fused BatchNorm-backward epilogue was not run-to-run deterministic on MI355X and the cause is not identified

@@ -85,8 +85,21 @@ enum WgradRoute {
   WGRAD_DMA,              // wgrad_dma.hip: K split over the pixels, second generation (operands < 2 GiB)
   WGRAD_LEGACY,           // wgrad.hip: K split over the pixels, first generation
 };
+// Kernel variant and sizing of the tap-fused route, decided once by plan_wgrad_fused (wgrad_fused.hip): a pure host function.
+struct WgradFusedPlan {
+  bool supported;       // the route takes the call (with WgradParams::in_scale set: its input-normalising form does)
+  bool paired;          // 512-thread workgroups: two halves walk the two halves of a unit's rows and meet in LDS
+  bool bnin;            // X rows are normalised in LDS
+  int pf;               // prefetch stages of the ring kernels (1 | 2); 0: three-segment staging
+  int ysplit, rows_per_unit, imgs_per_unit, half_lds;   // -> WgradFusedParams
+  int threads, nwg;     // workgroup size and count
+  int lds, lds_attr;    // dynamic LDS bytes of the launch; the kernel's dynamic-LDS attribute
+  int units;            // slabs to reduce
+  long workspace;       // slab bytes asked of the caller: wgrad_fused_workspace_bytes, >= units * 9 * CI * CJ * 4
+};
 struct WgradPlan {
   int route;
+  WgradFusedPlan fused; // WGRAD_FUSED
   int ksplit;           // K split (DMA / legacy / ConvT): slabs to reduce; rect: K units of all taps
   int chunk, tw, step;  // DMA / legacy: pixels per K slice, tile width in 64-channel units, pixel step of a block
   int steps_per_half;   // ConvT
@@ -99,10 +112,9 @@ bool convt_wgrad_split(int N, int H, int W, int CI, int CJ, int& ksplit, int& st
 int launch_convt_wgrad_fused(const WgradParams& w, const WgradPlan& pl, hipStream_t stream);
 int wgrad_rect_units(int N, int H, int W, int CI, int CJ, int d);
 int launch_wgrad_rect(const WgradParams& w, const WgradPlan& pl, float* out, hipStream_t stream);
-bool wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride, int dtype);
-bool wgrad_fused_bnin_supported(int d, int dtype);
+WgradFusedPlan plan_wgrad_fused(const WgradParams& w, int dtype);
 long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype);
-int launch_wgrad_fused(const WgradParams& w, int dtype, int* units_out, hipStream_t stream);
+int launch_wgrad_fused(const WgradParams& w, const WgradFusedPlan& pl, int dtype, hipStream_t stream);
 int wgrad_dma_tile(int CI, int CJ);
 int wgrad_dma_pixel_step(int dtype, int tw);
 int launch_wgrad_dma_kernel(WgradParams& p, int tw, int dtype, hipStream_t stream);

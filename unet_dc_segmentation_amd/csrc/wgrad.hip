@@ -284,14 +284,14 @@ WgradPlan plan_wgrad(const WgradParams& p, int dtype) {
   const long P = (long)p.N * p.H * p.W;
   const int d = p.offy[8];
   const bool bf16 = dtype == UNETDC_BF16, same = p.Hb == p.H && p.Wb == p.W;
-  const bool fused = same && wgrad_fused_supported(p.N, p.H, p.W, p.CI, p.CJ, p.lda, p.ldb, d, p.ntaps, p.stride, dtype);
+  pl.fused = plan_wgrad_fused(p, dtype);
   auto plan_fused = [&]() {
     pl.route = WGRAD_FUSED;
-    pl.workspace = wgrad_fused_workspace_bytes(p.N, p.H, p.W, p.CI, p.CJ, dtype);
+    pl.workspace = pl.fused.workspace;
     return pl;
   };
   if (p.in_scale) {               // input normalisation on load: the tap-split ring kernel only
-    if (fused && wgrad_fused_bnin_supported(d, dtype)) return plan_fused();
+    if (pl.fused.supported) return plan_fused();
     return pl;
   }
   // ConvTranspose2d(2, 2): one GEMM [Cin] x [4 Cout] with the input staged once for the four taps (convt_wgrad.hip)
@@ -312,7 +312,7 @@ WgradPlan plan_wgrad(const WgradParams& p, int dtype) {
       return pl;
     }
   }
-  if (fused) return plan_fused();     // tap-fused kernel for narrow 3x3 layers (wgrad_fused.hip)
+  if (pl.fused.supported) return plan_fused();     // tap-fused kernel for narrow 3x3 layers (wgrad_fused.hip)
   // K-split over the pixels: the second-generation (LDS-DMA) kernel while the operands are < 2 GiB (wgrad_dma.hip)
   const long es = bf16 ? 2 : 4;
   const bool dma = P * p.lda * es < (1L << 31) && (long)p.N * p.Hb * p.Wb * p.ldb * es < (1L << 31);
@@ -368,7 +368,7 @@ int launch_wgrad(WgradParams& p, float* out, void* workspace, long workspace_byt
   switch (pl.route) {
     case WGRAD_CONVT: rc = launch_convt_wgrad_fused(p, pl, stream); break;
     case WGRAD_RECT: return launch_wgrad_rect(p, pl, out, stream);        // reduces the units of every tap itself
-    case WGRAD_FUSED: rc = launch_wgrad_fused(p, dtype, &slabs, stream); break;
+    case WGRAD_FUSED: rc = launch_wgrad_fused(p, pl.fused, dtype, stream); slabs = pl.fused.units; break;
     default:
       p.ksplit = pl.ksplit;
       p.chunk = pl.chunk;

@@ -50,15 +50,13 @@ extern "C" int unetdc_dbg_wgrad_stamps(unsigned long long* dst) {
 #define STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
 
-template <typename T> struct FusedCfg;
-template <> struct FusedCfg<bf16_t> { static constexpr int SEG = 64; };
-template <> struct FusedCfg<float> { static constexpr int SEG = 32; };
+constexpr int SEG_BF16 = 64, SEG_F32 = 32;     // pixels of a strip's row segment
 
 // fp32 (bf16 runs the tap-split kernels below)
 __global__ __launch_bounds__(256, 2) void wgrad_fused_kernel(const WgradFusedParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using T = float;
-  constexpr int SEG = FusedCfg<T>::SEG;
+  constexpr int SEG = SEG_F32;
   constexpr int XR = SEG + 16;                         // X segment rows (x0-d .. x0+SEG-1+d, d <= 8)
   constexpr int ES = (int)sizeof(T);
   constexpr int RB = 64 * ES;                          // bytes per pixel row (64 channels)
@@ -195,7 +193,7 @@ template <int PF>
 __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(const WgradFusedParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using T = float;
-  constexpr int SEG = FusedCfg<T>::SEG;
+  constexpr int SEG = SEG_F32;
   constexpr int XR = SEG + 16;
   constexpr int ES = (int)sizeof(T);
   constexpr int RB = 64 * ES;
@@ -348,22 +346,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_ring_kernel(const WgradFusedPara
 // MFMA pipe busy 50 %.  With one 32x32 (co x ci) quadrant and all nine taps per wave, every MFMA needs a B fragment of
 // its own (two ds_read_b64_tr_b16 = 1 KB): 10 fragments per 9 MFMAs.  Four SIMDs x 1 KB per 32-cycle MFMA is more than the
 // LDS delivers, so the matrix pipe waits on fragment reads half the time.
-// Here a wave owns BOTH co halves (64 co x 32 ci) and HALF of the taps: a B fragment feeds two MFMAs.
-//   wave = (qj: ci half, tg: tap group);  tg 0: taps 0..3 and tap 4 on the first two k16 steps of a row,
-//                                         tg 1: taps 5..8 and tap 4 on the last two  (18 B fragments, 36 MFMAs each)
-//   per k16 step: 2 A fragments + 4.5 B fragments for 9 MFMAs  ->  1.44 LDS instructions per MFMA.
-// The two partial sums of tap 4 are added through LDS at the end, tg 0's + tg 1's (fixed order).
-// (That first form ran on v_mfma_f32_32x32x16_bf16; since round 3 only the 16x16x32 form below is built.)
-// ------------------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------------------
-// The same wave roles on v_mfma_f32_16x16x32_bf16 (M16 = true: the form that is built and launched).
-// These kernels are power bound like the convolutions (igemm_dma16.hip): MI355X_MICROARCH.md measures 1.12-1.15x the FLOP/s
-// for the 16x16x32 shape at equal cycles per FLOP with operands re-read from LDS.  LDS traffic per FLOP is unchanged (a
-// fragment is still two transposed 8-byte reads per lane for 512 multiply-adds per lane), the accumulators are the same
-// 160 registers: a wave owns 64 co x 32 ci = 4 x 2 tiles of 16 x 16 per tap slot.  A row of 64 pixels is two k32 steps;
-// tg 0 takes taps 0..4 on the first and 0..3 on the second, tg 1 taps 5..8 and 4..8 (tap 4 split over the two, joined through
-// LDS at the end as before).  Image swizzle and fragment addresses: wgrad_frag.h, Frag16.
+// Here a wave owns BOTH co halves (64 co x 32 ci) and HALF of the taps: a B fragment feeds every co tile of the wave.
+// The kernels run on v_mfma_f32_16x16x32_bf16: they are power bound like the convolutions (igemm_dma16.hip), and
+// MI355X_MICROARCH.md measures 1.12-1.15x the FLOP/s for that shape at equal cycles per FLOP with operands re-read from
+// LDS.  A wave holds 4 x 2 tiles of 16 x 16 per tap slot, 160 accumulator registers.
+//   wave = (qj: ci half, tg: tap group).  A row of 64 pixels is two k32 steps; tg 0 takes taps 0..4 on the first and 0..3
+//   on the second, tg 1 taps 5..8 and 4..8: nine items of 8 MFMAs each, tap 4 split over the two groups.
+// The two partial sums of tap 4 are added through LDS at the end, tg 0's + tg 1's (fixed order).  Image swizzle and fragment
+// addresses: wgrad_frag.h, Frag16.  (An earlier form of these wave roles ran on the 32x32x16 MFMA shape; its history is in
+// docs/optimisation_log.md, round 3.)
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int s16_k32(int tg, int i) { return tg == 0 ? (i < 5 ? 0 : 1) : (i < 4 ? 0 : 1); }
 __host__ __device__ constexpr int s16_tap(int tg, int i) { return tg == 0 ? (i < 5 ? i : i - 5) : (i < 4 ? 5 + i : i); }
@@ -373,10 +364,9 @@ struct Split16Offs {       // per-lane byte offsets of the transposed reads at k
   int x[3][2][2];          // [kx][ci tile][block jj], pixel rows shifted by kx * d
 };
 
-template <bool M16> struct SplitAcc;
-template <> struct SplitAcc<true> { f32x4 a[5][4][2]; };
+struct SplitAcc { f32x4 a[5][4][2]; };       // [tap slot][co tile][ci tile]
 
-__device__ __forceinline__ void split_zero(SplitAcc<true>& A) {
+__device__ __forceinline__ void split_zero(SplitAcc& A) {
 #pragma unroll
   for (int t = 0; t < 5; ++t)
 #pragma unroll
@@ -387,7 +377,7 @@ __device__ __forceinline__ void split_zero(SplitAcc<true>& A) {
         for (int e = 0; e < 4; ++e) A.a[t][c][j][e] = 0.f;
 }
 
-// `issue`: the row's DMA statements, placed behind the step's first fragment reads (those are in flight while the wave gets
+// One image row of the strip.  `issue`: the row's DMA statements, placed behind the step's first fragment reads (those are in flight while the wave gets
 // its DMA instructions accepted; round 4, as in igemm_lattice.hip)
 template <int TG, typename Issue>
 __device__ __forceinline__ void ring_split_step16(f32x4 (&acc)[5][4][2], const unsigned char* sdy, const unsigned char* sx0,
@@ -433,14 +423,6 @@ __device__ __forceinline__ void ring_split_step16(f32x4 (&acc)[5][4][2], const u
 #endif
 }
 
-// one image row of the strip: both forms behind one name
-template <int TG, typename Issue>
-__device__ __forceinline__ void split_step(SplitAcc<true>& A, const unsigned char* sdy, const unsigned char* sx0,
-                                           const unsigned char* sx1, const unsigned char* sx2, int, int, int,
-                                           const Split16Offs& o, Issue&& issue) {
-  ring_split_step16<TG>(A.a, sdy, sx0, sx1, sx2, o, issue);
-}
-
 // tap 4: tg 1's half (slot 0) joins tg 0's (slot 4) through LDS (fixed order), then the partial slab part[unit][t][i][j]:
 // tg 0 stores taps 0..4, tg 1 taps 5..8.  The caller guarantees that every DMA has landed and every fragment has been read.
 // PAIRED FORM (HV = 2, 512 threads): the workgroup is two halves of four waves with the roles above, each half walking its
@@ -449,7 +431,7 @@ __device__ __forceinline__ void split_step(SplitAcc<true>& A, const unsigned cha
 // Why: the fp32 slabs are the accumulator state of the whole chip (2 x 256 threads x 160 registers per CU = 84 MB per launch),
 // written once and re-read by the reduce kernel; two K ranges that meet in LDS halve both (round 4).
 template <int HV>
-__device__ __forceinline__ void split_finish(SplitAcc<true>& A, unsigned char* smem, unsigned char* smem_all, int half,
+__device__ __forceinline__ void split_finish(SplitAcc& A, unsigned char* smem, unsigned char* smem_all, int half,
                                              const WgradFusedParams& p, int unit, int i0, int j0, int qj, int tg, int lane) {
   float* xch = reinterpret_cast<float*>(smem);             // [qj][co tile][ci tile][v][lane]: 16 KB
   __syncthreads();
@@ -515,30 +497,26 @@ __device__ __forceinline__ void split_finish(SplitAcc<true>& A, unsigned char* s
   }
 }
 
-template <bool M16>
 __device__ __forceinline__ Split16Offs split_offsets(int lane, int qj, int d) {
   Split16Offs o;
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int jj = 0; jj < 2; ++jj) o.dy[c][jj] = M16 ? Frag16::rd_off(lane, 16 * c, 0, jj) : 0;
+    for (int jj = 0; jj < 2; ++jj) o.dy[c][jj] = Frag16::rd_off(lane, 16 * c, 0, jj);
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj) o.x[kx][j][jj] = M16 ? Frag16::rd_off(lane, qj * 32 + 16 * j, kx * d, jj) : 0;
+      for (int jj = 0; jj < 2; ++jj) o.x[kx][j][jj] = Frag16::rd_off(lane, qj * 32 + 16 * j, kx * d, jj);
   return o;
 }
-template <bool M16> __device__ __forceinline__ int split_src_chunk(int row, int pc) {
-  return M16 ? Frag16::src_chunk(row, pc) : Frag<bf16_t, 1>::src_chunk(row, pc);
-}
 
-template <int PF, int TG, bool M16, bool INORM, int HV>
+template <int PF, int TG, bool INORM, int HV>
 __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using T = bf16_t;
-  constexpr int SEG = FusedCfg<T>::SEG;
+  constexpr int SEG = SEG_BF16;
   constexpr int XR = SEG + 16;
   constexpr int ES = (int)sizeof(T);
   constexpr int RB = 64 * ES;
@@ -592,11 +570,11 @@ __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
     const int gi = wave + 4 * q;
     if (gi < DYI) {
       const int row = gi * RPI + sub;
-      colb[q] = (unsigned)(((x0 + row) * p.lddy + i0) * ES + split_src_chunk<M16>(row, pc) * 16);
+      colb[q] = (unsigned)(((x0 + row) * p.lddy + i0) * ES + Frag16::src_chunk(row, pc) * 16);
     } else if (gi < GI) {
       const int row = (gi - DYI) * RPI + sub;
       const int gx = x0 - d + row;
-      colb[q] = ((unsigned)gx < (unsigned)p.W) ? (unsigned)((gx * p.ldx + j0) * ES + split_src_chunk<M16>(row, pc) * 16) : FOOB;
+      colb[q] = ((unsigned)gx < (unsigned)p.W) ? (unsigned)((gx * p.ldx + j0) * ES + Frag16::src_chunk(row, pc) * 16) : FOOB;
     } else {
       colb[q] = FOOB;
     }
@@ -624,9 +602,9 @@ __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
     }
   };
 
-  SplitAcc<M16> acc;
+  SplitAcc acc;
   split_zero(acc);
-  const Split16Offs offs = split_offsets<M16>(lane, qj, d);
+  const Split16Offs offs = split_offsets(lane, qj, d);
   // INORM: the 64 (scale, shift) pairs of this workgroup's input-channel tile live in LDS behind the ring (no vector-memory
   // operation may join the hand-counted DMA queue inside the row loop); a thread owns logical chunk tid & 7 of every 32nd
   // pixel of a row.  Rows / pixels outside the image were zero-filled by the DMA and stay zero (zero padding of the
@@ -647,7 +625,7 @@ __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
       const int px = (tid >> 3) + 32 * i;
       const int gx = x0 - d + px;
       if (px < XR && (unsigned)gx < (unsigned)p.W) {
-        unsigned char* a = xring + slot * XB + px * RB + (split_src_chunk<M16>(px, lc) << 4);
+        unsigned char* a = xring + slot * XB + px * RB + (Frag16::src_chunk(px, lc) << 4);
         float v[8];
         Chunk<bf16_t>::unpack(ld16(a), v);
 #pragma unroll
@@ -716,9 +694,9 @@ __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
     // (the input-normalising form keeps its DMA statements in front: behind the reads it measured 221.7 vs 214.5 us)
     if (INORM) {
       issue_row();
-      split_step<TG>(acc, sdyp, xring + sl0 * XB, xring + sl1 * XB, xring + sl2 * XB, lane, qj, d, offs, []() {});
+      ring_split_step16<TG>(acc.a, sdyp, xring + sl0 * XB, xring + sl1 * XB, xring + sl2 * XB, offs, []() {});
     } else {
-      split_step<TG>(acc, sdyp, xring + sl0 * XB, xring + sl1 * XB, xring + sl2 * XB, lane, qj, d, offs, issue_row);
+      ring_split_step16<TG>(acc.a, sdyp, xring + sl0 * XB, xring + sl1 * XB, xring + sl2 * XB, offs, issue_row);
     }
 #ifdef UNETDC_WGRAD_STAMPS
     {
@@ -746,19 +724,19 @@ __device__ __forceinline__ void ring_split_body(const WgradFusedParams& p) {
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-template <int PF, bool M16, bool INORM = false, int HV = 1>
+template <int PF, bool INORM = false, int HV = 1>
 __global__ __launch_bounds__(256 * HV, 2) void wgrad_ring_split_kernel(const WgradFusedParams p) {
   // the tap group is wave-uniform: two specialisations of the whole body, so the 160 accumulator registers of a wave
   // never meet in a phi (a per-step branch made the allocator spill ~590 registers)
-  if (__builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 7) & 1)) == 0) ring_split_body<PF, 0, M16, INORM, HV>(p);
-  else ring_split_body<PF, 1, M16, INORM, HV>(p);
+  if (__builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 7) & 1)) == 0) ring_split_body<PF, 0, INORM, HV>(p);
+  else ring_split_body<PF, 1, INORM, HV>(p);
 }
 
-template <int TG, bool M16, int HV>
+template <int TG, int HV>
 __device__ __forceinline__ void fused_split_body(const WgradFusedParams& p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using T = bf16_t;
-  constexpr int SEG = FusedCfg<T>::SEG;
+  constexpr int SEG = SEG_BF16;
   constexpr int XR = SEG + 16;                         // X segment rows (x0-d .. x0+SEG-1+d, d <= 8)
   constexpr int ES = (int)sizeof(T);
   constexpr int RB = 64 * ES;                          // bytes per pixel row (64 channels)
@@ -805,22 +783,22 @@ __device__ __forceinline__ void fused_split_body(const WgradFusedParams& p) {
     const int gi = wave + 4 * q;
     if (gi < DYI) {
       const int row = gi * RPI + sub;                                  // pixel x0 + row
-      const int c = split_src_chunk<M16>(row, pc);
+      const int c = Frag16::src_chunk(row, pc);
       colb[q] = (unsigned)(((x0 + row) * p.lddy + i0) * ES + c * 16);
     } else if (gi < DYI + 3 * XI) {
       const int k = (gi - DYI) % XI;
       const int row = k * RPI + sub;                                   // pixel x0 - d + row
       const int gx = x0 - p.d + row;
-      const int c = split_src_chunk<M16>(row, pc);
+      const int c = Frag16::src_chunk(row, pc);
       colb[q] = ((unsigned)gx < (unsigned)p.W) ? (unsigned)((gx * p.ldx + j0) * ES + c * 16) : FOOB;
     } else {
       colb[q] = FOOB;
     }
   }
 
-  SplitAcc<M16> acc;
+  SplitAcc acc;
   split_zero(acc);
-  const Split16Offs offs = split_offsets<M16>(lane, qj, p.d);
+  const Split16Offs offs = split_offsets(lane, qj, p.d);
 
   auto issue = [&](int stage, int y) {
 #pragma unroll
@@ -850,7 +828,7 @@ __device__ __forceinline__ void fused_split_body(const WgradFusedParams& p) {
     };
     const unsigned char* sdy = smem + (s & 1) * STAGE;
     const unsigned char* sx = sdy + DYB;
-    split_step<TG>(acc, sdy, sx, sx + XB, sx + 2 * XB, lane, qj, p.d, offs, issue_row);
+    ring_split_step16<TG>(acc.a, sdy, sx, sx + XB, sx + 2 * XB, offs, issue_row);
   }
 
   // every DMA has landed (vmcnt(0) on the last step); join of tap 4, (paired form) of the two halves, and the slab stores
@@ -859,19 +837,26 @@ __device__ __forceinline__ void fused_split_body(const WgradFusedParams& p) {
 }
 
 // tap-split form of the three-segment kernel (d = 4, 8): same staging, the wave roles of wgrad_ring_split_kernel
-template <bool M16, int HV = 1>
+template <int HV = 1>
 __global__ __launch_bounds__(256 * HV, 2) void wgrad_fused_split_kernel(const WgradFusedParams p) {
-  if (__builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 7) & 1)) == 0) fused_split_body<0, M16, HV>(p);
-  else fused_split_body<1, M16, HV>(p);
+  if (__builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 7) & 1)) == 0) fused_split_body<0, HV>(p);
+  else fused_split_body<1, HV>(p);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Host side.  plan_wgrad_fused decides everything about a call -- kernel variant, row split, LDS, grid, slabs -- and
+// launch_wgrad_fused only fills the kernel's parameters from that plan.
+
+static int fused_seg(int dtype) { return dtype == UNETDC_BF16 ? SEG_BF16 : SEG_F32; }
 
 // LDS bytes of the ring kernel, or 0 when the configuration does not leave room for two workgroups per CU
 static int ring_lds(int d, int dtype, int pf) {
-  const int es = dtype == UNETDC_BF16 ? 2 : 4, seg = dtype == UNETDC_BF16 ? 64 : 32;
+  const int es = dtype == UNETDC_BF16 ? 2 : 4, seg = fused_seg(dtype);
   const int dyb = seg * 64 * es, xb = (seg + 16) * 64 * es;
   const int lds = (pf + 1) * dyb + (2 * d + pf + 1) * xb;
   return lds <= 80 * 1024 ? lds : 0;
 }
+// prefetch stages of the ring, 0: three-segment staging (fp32: the ring fits at d = 1 with one stage only)
 static int ring_pf(int d, int dtype) {
   if (d > 2) return 0;
   if (ring_lds(d, dtype, 2)) return 2;
@@ -879,156 +864,128 @@ static int ring_pf(int d, int dtype) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-static int fused_seg(int dtype) { return dtype == UNETDC_BF16 ? 64 : 32; }
-
-bool wgrad_fused_supported(int N, int H, int W, int CI, int CJ, int lda, int ldb, int d, int ntaps, int stride,
-                           int dtype) {
-  if (ntaps != 9 || stride != 1 || d < 1 || d > 8) return false;
-  if (CI % 64 != 0 || CJ % 64 != 0) return false;
-  if (CI > 1024 || CJ > 1024) return false;
-  if (W % fused_seg(dtype) != 0) return false;
-  const long P = (long)N * H * W;
-  const long minp = 32L * 1024;
-  if (P < minp) return false;
-  const long es = dtype == UNETDC_BF16 ? 2 : 4;
-  return P * lda * es < (1L << 31) && P * ldb * es < (1L << 31);
-}
-
-static void fused_plan(int N, int H, int W, int CI, int CJ, int dtype, int& ysplit, int& rows) {
-  const int strips = N * (W / fused_seg(dtype));
-  const int tiles = (CI / 64) * (CJ / 64);
-  int ys = 512 / (strips * tiles);                 // ~2 workgroups per CU
+// Rows of the image per unit: about `target` workgroups (`wgs` of them per y range), at least `min_rows` rows each.
+struct RowSplit { int rows, ysplit; };
+static RowSplit row_split(int H, int wgs, int target, int min_rows) {
+  int ys = target / wgs;
   if (ys < 1) ys = 1;
-  if (ys > H / 8) ys = H / 8 > 0 ? H / 8 : 1;
-  rows = (H + ys - 1) / ys;
-  ysplit = (H + rows - 1) / rows;
+  if (ys > H / min_rows) ys = H / min_rows > 0 ? H / min_rows : 1;
+  const int rows = (H + ys - 1) / ys;
+  return RowSplit{rows, (H + rows - 1) / rows};
 }
+// the two row splits of the route: 256-thread workgroups, two per CU; paired 512-thread workgroups, one per CU
+static RowSplit single_split(int H, int wgs) { return row_split(H, wgs, 512, 8); }
+static RowSplit paired_split(int H, int wgs) { return row_split(H, wgs, 256, 16); }
 
+// The slab bytes of the route for ANY dilation, leading dimensions and normalisation: what the C-ABI workspace query
+// promises and what launch_wgrad compares a caller's workspace with.  It is the slab count of the unpaired split, and no
+// plan has more slabs than that:
+//   * ysplit(y) = ceil(H / ceil(H / y)) does not decrease with y, and the paired split starts from a y that is not larger
+//     (256 / wgs <= 512 / wgs, H / 16 <= H / 8, and the clamps keep the order);
+//   * walking several images per workgroup (imgs_per_unit) only happens at ysplit == 1 and divides the units further.
+// launch_wgrad_fused checks it for the plan it is given.
 long wgrad_fused_workspace_bytes(int N, int H, int W, int CI, int CJ, int dtype) {
-  if (W < fused_seg(dtype) || W % fused_seg(dtype) != 0 || H < 1 || CI % 64 != 0 || CJ % 64 != 0) return 0;
-  int ys, rows;
-  fused_plan(N, H, W, CI, CJ, dtype, ys, rows);
-  return (long)N * (W / fused_seg(dtype)) * ys * 9 * CI * CJ * 4;
+  const int seg = fused_seg(dtype);
+  if (W < seg || W % seg != 0 || H < 1 || CI % 64 != 0 || CJ % 64 != 0) return 0;
+  const int strips = N * (W / seg), tiles = (CI / 64) * (CJ / 64);
+  return (long)strips * single_split(H, strips * tiles).ysplit * 9 * CI * CJ * 4;
 }
 
-// the input-normalising form (on top of wgrad_fused_supported): the 16x16x32 tap-split ring kernel only
-bool wgrad_fused_bnin_supported(int d, int dtype) { return dtype == UNETDC_BF16 && ring_pf(d, dtype) > 0; }
-
-// Fills the slabs (dy = w.a, x = w.b); the caller reduces `units` slabs with wgrad_reduce_kernel.
-int launch_wgrad_fused(const WgradParams& w, int dtype, int* units_out, hipStream_t stream) {
+WgradFusedPlan plan_wgrad_fused(const WgradParams& w, int dtype) {
+  WgradFusedPlan pl{};
   const int N = w.N, H = w.H, W = w.W, CI = w.CI, CJ = w.CJ, d = w.offy[8];
-  const float* in_scale = w.in_scale;
-  WgradFusedParams p{};
-  p.dy = w.a; p.x = w.b; p.part = w.part; p.N = N; p.H = H; p.W = W; p.CI = CI; p.CJ = CJ; p.lddy = w.lda; p.ldx = w.ldb;
-  p.d = d; p.in_scale = in_scale; p.in_shift = w.in_shift;
-  fused_plan(N, H, W, CI, CJ, dtype, p.ysplit, p.rows_per_unit);
-  p.itiles = CI / 64;
-  p.jtiles = CJ / 64;
-  const int units = N * (W / fused_seg(dtype)) * p.ysplit;
-  *units_out = units;
-  const long nwg = (long)units * p.itiles * p.jtiles;
-  const int pf = ring_pf(d, dtype);
-  // (the tap-split kernels run on v_mfma_f32_16x16x32_bf16: settled in round 3, profiles/r03_wgrad_m16_ab.txt; the 32x32x16
-  //  instantiations are no longer built)
-  // PAIRED FORM (round 4): 512-thread workgroups whose two halves walk the two halves of a unit's rows and meet in LDS
-  // (split_finish): half as many fp32 slabs written and reduced.  The plan is the one above at a target of 256 workgroups
-  // (one per CU: the two rings fill the LDS), i.e. every half does exactly the work a 256-thread workgroup did.
+  const bool bf16 = dtype == UNETDC_BF16;
+  const int es = bf16 ? 2 : 4, seg = fused_seg(dtype);
+  if (w.Hb != H || w.Wb != W || w.ntaps != 9 || w.stride != 1 || d < 1 || d > 8) return pl;
+  if (CI % 64 != 0 || CJ % 64 != 0 || CI > 1024 || CJ > 1024 || W % seg != 0) return pl;
+  const long P = (long)N * H * W;
+  if (P < 32L * 1024 || P * w.lda * es >= (1L << 31) || P * w.ldb * es >= (1L << 31)) return pl;
+  pl.pf = ring_pf(d, dtype);
+  pl.bnin = w.in_scale != nullptr;
+  if (pl.bnin && !(bf16 && pl.pf)) return pl;            // input normalisation: the tap-split ring kernels only
+  pl.supported = true;
+  pl.workspace = wgrad_fused_workspace_bytes(N, H, W, CI, CJ, dtype);
+
+  const int strips = N * (W / seg), tiles = (CI / 64) * (CJ / 64);
+  // 256-thread workgroups, two per CU: the ring where it fits (+ 512 bytes of normalisation constants), else the
+  // three-segment staging, double buffered
+  RowSplit rs = single_split(H, strips * tiles);
+  int target = 512;
+  pl.threads = 256;
+  pl.lds = pl.pf ? ring_lds(d, dtype, pl.pf) + (pl.bnin ? 512 : 0) : 2 * (seg * 64 * es + 3 * (seg + 16) * 64 * es);
+  pl.lds_attr = pl.pf ? (pl.bnin ? 96 : 80) * 1024 : pl.lds;
+  // PAIRED FORM (bf16, round 4): 512-thread workgroups whose two halves walk the two halves of a unit's rows and meet in LDS
+  // (split_finish): half as many fp32 slabs written and reduced.  One workgroup per CU (the two rings fill the LDS), so
+  // every half does exactly the work a 256-thread workgroup does.  Only when the two halves get the same number of rows.
   // (three-segment staging, d = 4 / 8, waits for ALL its DMAs at every step: in lock step the two halves expose that wait
   //  together -- measured 155.4 vs 157.9 us at d = 4 but 175.3 vs 166.3 us at d = 8, profiles/r04_wgrad_pair_ab.txt)
-  if (dtype == UNETDC_BF16 && (pf || d <= 4)) {
-    const int strips = N * (W / fused_seg(dtype)), tiles = p.itiles * p.jtiles;
-    int ys = 256 / (strips * tiles);
-    if (ys < 1) ys = 1;
-    if (ys > H / 16) ys = H / 16 > 0 ? H / 16 : 1;
-    const int rows = (H + ys - 1) / ys;
-    const int half_lds = pf ? ring_lds(d, dtype, pf) + (in_scale ? 512 : 0)
-                            : 2 * (fused_seg(dtype) * 128 + 3 * (fused_seg(dtype) + 16) * 128);
-    if (rows % 2 == 0 && H % rows == 0 && 2 * half_lds <= 160 * 1024) {
-      WgradFusedParams q = p;
-      q.rows_per_unit = rows;
-      q.ysplit = H / rows;
-      q.half_lds = half_lds;
-      int un = strips * q.ysplit;
-      long nwg2 = (long)un * tiles;
-      if (pf && q.ysplit == 1 && nwg2 > 256 && N > 1) {   // several images per workgroup (as in the unpaired form, target 256)
-        int ipu = (int)((nwg2 + 255) / 256);
-        if (ipu > N) ipu = N;
-        q.imgs_per_unit = ipu;
-        un = (W / fused_seg(dtype)) * ((N + ipu - 1) / ipu);
-        nwg2 = (long)un * tiles;
-      }
-      const int lds2 = 160 * 1024;                         // two rings, and 144 KB of them for the hand-over at the end
-      const void* fn2;
-      if (!pf) fn2 = reinterpret_cast<const void*>(&wgrad_fused_split_kernel<true, 2>);
-      else if (in_scale) fn2 = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_split_kernel<2, true, true, 2>)
-                                       : reinterpret_cast<const void*>(&wgrad_ring_split_kernel<1, true, true, 2>);
-      else fn2 = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_split_kernel<2, true, false, 2>)
-                         : reinterpret_cast<const void*>(&wgrad_ring_split_kernel<1, true, false, 2>);
-      if (const int rc_ = ensure_dynamic_lds(fn2, lds2, "paired wgrad kernel")) return rc_;
-      *units_out = un;
-      const dim3 g((unsigned)nwg2), b(512);
-      if (!pf) hipLaunchKernelGGL((wgrad_fused_split_kernel<true, 2>), g, b, lds2, stream, q);
-      else if (in_scale && pf == 2) hipLaunchKernelGGL((wgrad_ring_split_kernel<2, true, true, 2>), g, b, lds2, stream, q);
-      else if (in_scale) hipLaunchKernelGGL((wgrad_ring_split_kernel<1, true, true, 2>), g, b, lds2, stream, q);
-      else if (pf == 2) hipLaunchKernelGGL((wgrad_ring_split_kernel<2, true, false, 2>), g, b, lds2, stream, q);
-      else hipLaunchKernelGGL((wgrad_ring_split_kernel<1, true, false, 2>), g, b, lds2, stream, q);
-      note_kernel(!pf ? "wgrad_fused_split_kernel<16x16x32> paired"
-                      : (in_scale ? (pf == 2 ? "wgrad_ring_split_kernel<2, 16x16x32> paired bnin" : "wgrad_ring_split_kernel<1, 16x16x32> paired bnin")
-                                  : (pf == 2 ? "wgrad_ring_split_kernel<2, 16x16x32> paired" : "wgrad_ring_split_kernel<1, 16x16x32> paired")));
-      return check_launch("paired wgrad kernel");
+  if (bf16 && (pl.pf || d <= 4)) {
+    const RowSplit r2 = paired_split(H, strips * tiles);
+    if (r2.rows % 2 == 0 && H % r2.rows == 0 && 2 * pl.lds <= 160 * 1024) {
+      pl.paired = true;
+      rs = r2;
+      target = 256;
+      pl.threads = 512;
+      pl.half_lds = pl.lds;
+      pl.lds = pl.lds_attr = 160 * 1024;                 // two rings, and 144 KB of them for the hand-over at the end
     }
   }
-  if (pf && dtype == UNETDC_BF16) {
-    const int lds = ring_lds(d, dtype, pf) + (in_scale ? 512 : 0);
-    long nwg = (long)units * p.itiles * p.jtiles;
-    if (p.ysplit == 1 && nwg > 512 && N > 1) {           // more than two workgroups per CU: walk several images per workgroup
-      int ipu = (int)((nwg + 511) / 512);
-      if (ipu > N) ipu = N;
-      p.imgs_per_unit = ipu;
-      *units_out = (W / fused_seg(dtype)) * ((N + ipu - 1) / ipu);
-      nwg = (long)*units_out * p.itiles * p.jtiles;
-    }
-    const void* fn = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_split_kernel<2, true>)
-                             : reinterpret_cast<const void*>(&wgrad_ring_split_kernel<1, true>);
-    if (const int rc_ = ensure_dynamic_lds(fn, 80 * 1024, "wgrad_ring_split_kernel")) return rc_;
-    if (in_scale) {
-      const void* nfn = pf == 2 ? reinterpret_cast<const void*>(&wgrad_ring_split_kernel<2, true, true>)
-                                : reinterpret_cast<const void*>(&wgrad_ring_split_kernel<1, true, true>);
-      if (const int rc_ = ensure_dynamic_lds(nfn, 96 * 1024, "wgrad_ring_split_kernel bnin")) return rc_;
-      if (pf == 2) hipLaunchKernelGGL((wgrad_ring_split_kernel<2, true, true>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-      else hipLaunchKernelGGL((wgrad_ring_split_kernel<1, true, true>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-      note_kernel(pf == 2 ? "wgrad_ring_split_kernel<2, 16x16x32> bnin" : "wgrad_ring_split_kernel<1, 16x16x32> bnin");
-      return check_launch("wgrad_ring_split_kernel(bnin)");
-    }
-    if (pf == 2) hipLaunchKernelGGL((wgrad_ring_split_kernel<2, true>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((wgrad_ring_split_kernel<1, true>), dim3((unsigned)nwg), dim3(256), lds, stream, p);
-    note_kernel(pf == 2 ? "wgrad_ring_split_kernel<2, 16x16x32>" : "wgrad_ring_split_kernel<1, 16x16x32>");
-    return check_launch("wgrad_ring_split_kernel");
+  pl.rows_per_unit = rs.rows;
+  pl.ysplit = rs.ysplit;
+  pl.units = strips * rs.ysplit;
+  // tap-split ring kernels, more workgroups than the target although every one walks a whole image: several images per
+  // workgroup
+  if (bf16 && pl.pf && rs.ysplit == 1 && (long)pl.units * tiles > target && N > 1) {
+    int ipu = (int)(((long)pl.units * tiles + target - 1) / target);
+    if (ipu > N) ipu = N;
+    pl.imgs_per_unit = ipu;
+    pl.units = (W / seg) * ((N + ipu - 1) / ipu);
   }
-  const int es = dtype == UNETDC_BF16 ? 2 : 4;
-  const int seg = fused_seg(dtype);
-  const int lds3 = 2 * (seg * 64 * es + 3 * (seg + 16) * 64 * es);     // three-segment staging, double buffered
-  if (dtype == UNETDC_BF16) {                            // d = 4, 8: tap-split wave roles on the three-segment staging
-    if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_fused_split_kernel<true>), lds3, "wgrad_fused_split_kernel"))
-      return rc_;
-    hipLaunchKernelGGL(wgrad_fused_split_kernel<true>, dim3((unsigned)nwg), dim3(256), lds3, stream, p);
-    note_kernel("wgrad_fused_split_kernel<16x16x32>");
-    return check_launch("wgrad_fused_split_kernel");
+  pl.nwg = pl.units * tiles;
+  return pl;
+}
+
+// The kernel of a plan and the name unetdc_last_kernel() reports for it.
+struct FusedKernel {
+  void (*fn)(const WgradFusedParams);
+  const char* name;
+};
+static FusedKernel fused_kernel(const WgradFusedPlan& pl, int dtype) {
+  if (dtype != UNETDC_BF16) {                            // the quadrant kernels
+    if (!pl.pf) return {wgrad_fused_kernel, "wgrad_fused_kernel<float>"};
+    if (pl.pf == 1) return {wgrad_ring_kernel<1>, "wgrad_ring_kernel<float, 1>"};
+    return {nullptr, "wgrad_ring_kernel<float, 2>"};
   }
-  // fp32: the quadrant kernels, the ring where it fits (d = 1: one prefetch stage; a second one, or d = 2, exceeds the 80 KB
-  // of ring_lds), three-segment otherwise
-  if (pf) {
-    UNETDC_REQUIRE(pf == 1, "wgrad_ring: no fp32 form with %d prefetch stages", pf);
-    if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_ring_kernel<1>), 80 * 1024, "wgrad_ring_kernel")) return rc_;
-    hipLaunchKernelGGL((wgrad_ring_kernel<1>), dim3((unsigned)nwg), dim3(256), ring_lds(d, dtype, 1), stream, p);
-    note_kernel("wgrad_ring_kernel<float, 1>");
-    return check_launch("wgrad_ring_kernel");
+  if (!pl.pf) {
+    if (pl.paired) return {wgrad_fused_split_kernel<2>, "wgrad_fused_split_kernel<16x16x32> paired"};
+    return {wgrad_fused_split_kernel<1>, "wgrad_fused_split_kernel<16x16x32>"};
   }
-  if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&wgrad_fused_kernel), lds3, "wgrad_fused_kernel")) return rc_;
-  hipLaunchKernelGGL(wgrad_fused_kernel, dim3((unsigned)nwg), dim3(256), lds3, stream, p);
-  note_kernel("wgrad_fused_kernel<float>");
-  return check_launch("wgrad_fused_kernel");
+#define RING_SPLIT(PF, INORM, HV, SUFFIX) \
+  {wgrad_ring_split_kernel<PF, INORM, HV>, "wgrad_ring_split_kernel<" #PF ", 16x16x32>" SUFFIX}
+  static const FusedKernel ring[2][2][2] = {             // [pf - 1][paired][bnin]
+      {{RING_SPLIT(1, false, 1, ""), RING_SPLIT(1, true, 1, " bnin")},
+       {RING_SPLIT(1, false, 2, " paired"), RING_SPLIT(1, true, 2, " paired bnin")}},
+      {{RING_SPLIT(2, false, 1, ""), RING_SPLIT(2, true, 1, " bnin")},
+       {RING_SPLIT(2, false, 2, " paired"), RING_SPLIT(2, true, 2, " paired bnin")}}};
+#undef RING_SPLIT
+  return ring[pl.pf - 1][pl.paired][pl.bnin];
+}
+
+// Fills the slabs (dy = w.a, x = w.b); the caller reduces pl.units slabs with wgrad_reduce_kernel.
+int launch_wgrad_fused(const WgradParams& w, const WgradFusedPlan& pl, int dtype, hipStream_t stream) {
+  const FusedKernel k = fused_kernel(pl, dtype);
+  UNETDC_REQUIRE(pl.supported && k.fn, "wgrad_fused: no kernel for this call (%s)", k.name);
+  UNETDC_REQUIRE((long)pl.units * 9 * w.CI * w.CJ * 4 <= pl.workspace, "wgrad_fused: %d slabs exceed the workspace bound of %ld bytes",
+                 pl.units, pl.workspace);
+  WgradFusedParams p{};
+  p.dy = w.a; p.x = w.b; p.part = w.part; p.N = w.N; p.H = w.H; p.W = w.W; p.CI = w.CI; p.CJ = w.CJ; p.lddy = w.lda; p.ldx = w.ldb;
+  p.d = w.offy[8]; p.in_scale = w.in_scale; p.in_shift = w.in_shift;
+  p.ysplit = pl.ysplit; p.rows_per_unit = pl.rows_per_unit; p.itiles = w.CI / 64; p.jtiles = w.CJ / 64;
+  p.imgs_per_unit = pl.imgs_per_unit; p.half_lds = pl.half_lds;
+  if (const int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), pl.lds_attr, k.name)) return rc_;
+  hipLaunchKernelGGL(k.fn, dim3((unsigned)pl.nwg), dim3(pl.threads), pl.lds, stream, p);
+  note_kernel(k.name);
+  return check_launch(k.name);
 }
 
 }  // namespace unetdc
