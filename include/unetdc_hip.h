@@ -315,7 +315,8 @@ int unetdc_ccl_stats(const uint8_t* mask, int h, int w, int min_area, void* work
  * unetdc_rolling_ball_u8: per channel of an interleaved HWC uint8 image: background = opening with the ksize x ksize
  *   ellipse of cv2.getStructuringElement (dilate(erode(.)), pixels outside the image ignored), dst = normalize_minmax(
  *   saturate(src - background)) to 0..255 (scale/shift in double, applied in float, round half to even).  ksize <= 128,
- *   channels <= 4.  dst may not alias src.
+ *   channels <= 4.  dst may not alias src.  src, dst and the workspace must be 16-byte aligned: anything else returns
+ *   UNETDC_EINVAL before the first launch.
  * unetdc_resize_linear_u8_to_chw_f32: OpenCV's 8-bit INTER_LINEAR resize to (dh, dw), / 255, HWC -> CHW float32 (the
  *   network input layout).  xofs[dw] / yofs[dh]: source index of the first tap (x already clamped to [0, w-1]),
  *   xcoef[dw][2] / ycoef[dh][2]: the 11-bit coefficients (utils/data_loader.py:linear_tables builds them). */

@@ -4,6 +4,10 @@ rule; the strict `>` threshold.  Integer / byte work: the bar is bit-exact."""
 import numpy as np
 import pytest
 import torch
+from scipy import ndimage
+
+from tests import image_edge_fixtures as fx
+from tests.image_canaries import Canaried
 
 pytestmark = pytest.mark.gpu
 
@@ -115,3 +119,166 @@ def test_more_droplets_than_the_first_output_capacity():
     mask, area, cy, cx = mask_and_droplets(torch.from_numpy(m).cuda(), 0.5, (1024, 1024), 1)
     assert len(area) == 262144 and int(area.min()) == 1 and int(area.max()) == 1
     assert cy[0] == 0 and cx[1] == 2 and cy[512] == 2 and cx[512] == 0          # raster order
+
+
+# ---- unetdc_ccl_stats and the mask kernels through the C ABI, every output and the workspace (at exactly
+# unetdc_ccl_workspace bytes) between canaries ----------------------------------------------------------------------------------
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _ccl_canaried(m, min_area, max_out=None):
+    """-> (count, area, sum_row, sum_col, root: int64 arrays of min(count, max_out) entries).  The per-droplet outputs hold
+    exactly max_out entries, so the canary begins at entry max_out."""
+    from unet_dc_segmentation_amd import _lib
+    h, w = m.shape
+    nbytes = _lib.load().unetdc_ccl_workspace(h, w)
+    cap = h * w if max_out is None else max_out
+    mask = torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8)).cuda()
+    ws, count = Canaried(nbytes), Canaried(4)
+    area, root, sy, sx = Canaried(4 * cap), Canaried(4 * cap), Canaried(8 * cap), Canaried(8 * cap)
+    _lib.call("unetdc_ccl_stats", mask.data_ptr(), h, w, min_area, ws.ptr, nbytes, count.ptr, area.ptr, sy.ptr, sx.ptr, root.ptr,
+              cap, _stream())
+    torch.cuda.synchronize()
+    for v, what in ((ws, "workspace"), (count, "count"), (area, "areas"), (root, "roots"), (sy, "row sums"), (sx, "column sums")):
+        v.check("ccl " + what)
+    assert np.array_equal(mask.cpu().numpy(), m)
+    n = int(count.numpy(np.int32, 1)[0])
+    k = min(n, cap)
+    cols = [area.numpy(np.int32, cap), sy.numpy(np.int64, cap), sx.numpy(np.int64, cap), root.numpy(np.int32, cap)]
+    for v in cols:                                                     # entries at min(count, max_out) and above: untouched
+        assert np.all(v[k:].view(np.uint8) == 0xA5)
+    return (n,) + tuple(v[:k].astype(np.int64) for v in cols)
+
+
+def _scipy_table(m, min_area):
+    """(area, sum_row, sum_col, first raster index) per 4-connected component of at least min_area pixels, as int64, in
+    scipy.ndimage.label's order (raster order of the first pixel)."""
+    lab, n = ndimage.label(m)                                          # the default structure: 4-connectivity
+    flat = lab.ravel()
+    area = np.bincount(flat, minlength=n + 1)[1:].astype(np.int64)
+    yy, xx = np.divmod(np.arange(flat.size, dtype=np.int64), m.shape[1])
+    sy = np.bincount(flat, weights=yy, minlength=n + 1)               # float64 sums of integers below 2^53: exact
+    sx = np.bincount(flat, weights=xx, minlength=n + 1)
+    assert sy.max(initial=0) < 2.0 ** 53 and sx.max(initial=0) < 2.0 ** 53
+    sy, sx = sy.astype(np.int64), sx.astype(np.int64)
+    first = np.full(n + 1, flat.size, np.int64)
+    idx = np.flatnonzero(flat)[::-1]
+    first[flat[idx]] = idx                                             # the last write is the smallest index
+    assert np.all(np.diff(first[1:]) > 0)                              # label order IS raster order of the first pixel
+    keep = area >= min_area
+    return area[keep], sy[1:][keep], sx[1:][keep], first[1:][keep]
+
+
+def _assert_ccl_matches_scipy(m, min_area, max_out=None, want=None):
+    n, area, sy, sx, root = _ccl_canaried(m, min_area, max_out)
+    want = _scipy_table(m, min_area) if want is None else want
+    assert n == len(want[0])                                           # the full count, whatever max_out
+    k = len(area)
+    assert k == (n if max_out is None else min(n, max_out))
+    for got, w, what in zip((area, sy, sx, root), want, ("area", "row sum", "column sum", "first pixel")):
+        assert got.dtype == np.int64 and np.array_equal(got, w[:k]), what
+    return n
+
+
+CCL_SHAPES = [(1, 4097), (4097, 1), (1, 1), (700, 1), (512, 2), (341, 3), (205, 5), (33, 31), (32, 32), (25, 41), (1, 1023),
+              (1, 1024), (1025, 1), (1040, 1388), (2048, 2048)]
+
+
+@pytest.mark.parametrize("min_area", [1, 3])
+@pytest.mark.parametrize("shape", CCL_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_ccl_stats_geometry_against_scipy(shape, min_area):
+    """One-row, one-column and one-pixel masks; widths 1, 2, 3 and 5 (ccl_emit_kernel's 4 pixels per thread straddle row
+    ends); n = 1023, 1024, 1025 around the 1024-pixel scan block; 1410 and 4096 scan blocks (ccl_scan_kernel with 2 and 4
+    block sums per thread).  Random masks near the 4-connected site-percolation threshold (0.593)."""
+    h, w = shape
+    m = (np.random.default_rng(h * 3 + w).random((h, w)) < 0.58).astype(np.uint8)
+    want = _scipy_table(m, min_area)
+    n = _assert_ccl_matches_scipy(m, min_area, want=want)
+    assert n >= 1 or h * w == 1
+    if h * w >= 1023:
+        _assert_ccl_matches_scipy(m, min_area, max_out=max(n // 2, 1), want=want)
+
+
+@pytest.mark.parametrize("value", [0, 1])
+def test_ccl_stats_single_pixel(value):
+    n, area, sy, sx, root = _ccl_canaried(np.full((1, 1), value, np.uint8), 1)
+    assert n == value and list(area) == [1] * value and list(root) == [0] * value
+
+
+@pytest.mark.parametrize("min_area", [2, 5])
+def test_ccl_stats_min_area_boundary(min_area):
+    """Components of exactly min_area - 1, min_area and min_area + 1 pixels: the first are dropped, the others kept."""
+    m = fx.area_boundary_mask(min_area)
+    n, area, sy, sx, root = _ccl_canaried(m, min_area)
+    assert n == 6 and sorted(area) == [min_area] * 3 + [min_area + 1] * 3
+    _assert_ccl_matches_scipy(m, min_area)
+    _assert_ccl_matches_scipy(m, min_area, max_out=4)
+    assert _assert_ccl_matches_scipy(m, 1) == 9
+
+
+def test_ccl_stats_max_out_zero_and_workspace_too_small():
+    from unet_dc_segmentation_amd import _lib
+    m = fx.area_boundary_mask(2)
+    assert _assert_ccl_matches_scipy(m, 1, max_out=0) == 9
+    h, w = m.shape
+    nbytes = _lib.load().unetdc_ccl_workspace(h, w)
+    mask = torch.from_numpy(m).cuda()
+    ws, outs = Canaried(nbytes), [Canaried(4), Canaried(4 * 16), Canaried(8 * 16), Canaried(8 * 16), Canaried(4 * 16)]
+    rc = _lib.load().unetdc_ccl_stats(mask.data_ptr(), h, w, 1, ws.ptr, nbytes - 1, *[o.ptr for o in outs], 16, _stream())
+    torch.cuda.synchronize()
+    assert rc == -3                                                    # UNETDC_EWORKSPACE, before any launch
+    assert ws.untouched() and all(o.untouched() for o in outs)
+
+
+def _special_probs(h, w, seed):
+    p = np.random.default_rng(seed).random((h, w)).astype(np.float32)
+    flat = p.ravel()
+    for j, v in enumerate([np.nan, np.inf, -np.inf, 0.0, 1.0, -0.0, -0.5, np.nextafter(np.float32(1), np.float32(2)),
+                           np.nextafter(np.float32(0), np.float32(1)), -np.nan]):
+        flat[j::17][:max(1, flat.size // 40)] = v
+    return p
+
+
+@pytest.mark.parametrize("thresh", [0.0, 1.0, -0.5, 0.3])
+@pytest.mark.parametrize("out_hw", [(37, 53), (53, 37), (90, 11), (1, 1)])
+def test_mask_from_probs_special_values_and_thresholds(out_hw, thresh):
+    """NaN compares false, +inf true, -inf false; thresholds 0, 1 and a negative one.  Reference: p > np.float32(t) in numpy,
+    then cv2's nearest-neighbour index rule."""
+    from unet_dc_segmentation_amd import _lib
+    from unet_dc_segmentation_amd.droplets import resize_nearest_cv2
+    ph, pw = 37, 53
+    p = _special_probs(ph, pw, 3)
+    oh, ow = out_hw
+    with np.errstate(invalid="ignore"):
+        want = resize_nearest_cv2((p > np.float32(thresh)).astype(np.uint8), ow, oh)
+    out, pd = Canaried(oh * ow), torch.from_numpy(p).cuda()
+    _lib.call("unetdc_mask_from_probs", pd.data_ptr(), ph, pw, float(thresh), out.ptr, oh, ow, _stream())
+    torch.cuda.synchronize()
+    out.check("mask")
+    got = out.numpy(np.uint8, oh, ow)
+    assert np.array_equal(got, want)
+    assert 0 < int(want.sum()) < want.size or oh * ow == 1
+
+
+@pytest.mark.parametrize("p_hw,out_hw", [((1, 64), (40, 97)), ((64, 1), (97, 40)), ((1, 64), (1, 200)), ((64, 1), (200, 1)),
+                                         ((48, 64), (1, 97)), ((48, 64), (97, 1)), ((1, 1), (9, 13))])
+def test_mask_from_probs_linear_one_row_and_one_column(p_hw, out_hw):
+    """1 x W and H x 1 probability maps (and outputs): the reference's 8-bit INTER_LINEAR on the thresholded mask."""
+    from unet_dc_segmentation_amd import _lib
+    from unet_dc_segmentation_amd.preprocess import _resize_tables
+    from utils.data_loader import resize_linear_cv2_u8
+    (ph, pw), (oh, ow) = p_hw, out_hw
+    p = _special_probs(ph, pw, 5) if ph * pw > 1 else np.full((1, 1), 0.7, np.float32)
+    thresh = np.float32(0.4)
+    with np.errstate(invalid="ignore"):
+        want = resize_linear_cv2_u8((p > thresh).astype(np.uint8), ow, oh)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xo, xa = _resize_tables(pw, ow, dev, True)
+    yo, ya = _resize_tables(ph, oh, dev, False)
+    out, pd = Canaried(oh * ow), torch.from_numpy(p).cuda()
+    _lib.call("unetdc_mask_from_probs_linear", pd.data_ptr(), ph, pw, float(thresh), out.ptr, oh, ow,
+              xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr(), _stream())
+    torch.cuda.synchronize()
+    out.check("mask")
+    assert np.array_equal(out.numpy(np.uint8, oh, ow), want)

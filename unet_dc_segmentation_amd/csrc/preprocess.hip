@@ -248,6 +248,10 @@ int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int
     set_error("rolling_ball: workspace too small (%ld bytes)", workspace_bytes);
     return UNETDC_EWORKSPACE;
   }
+  // subtract_minmax_kernel's 16-byte accesses to src, dst and the background plane (workspace + a multiple of 16); checked
+  // before the first launch, so a refused call has written nothing
+  UNETDC_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && ((uintptr_t)workspace % 16 == 0),
+                 "rolling_ball: image pointers and the workspace must be 16-byte aligned");
   MorphSpans sp;
   {
     // cv::getStructuringElement(MORPH_ELLIPSE, Size(k, k))
@@ -281,8 +285,6 @@ int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int
   const long npix = (long)h * w;
   {
     const dim3 g(pp_grid(npix / 16 + 1) > 256 ? 256 : pp_grid(npix / 16 + 1));
-    UNETDC_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && ((uintptr_t)bg % 16 == 0),
-                   "rolling_ball: image pointers must be 16-byte aligned");
     if (cn == 1) hipLaunchKernelGGL(subtract_minmax_kernel<1>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
     else if (cn == 2) hipLaunchKernelGGL(subtract_minmax_kernel<2>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
     else if (cn == 3) hipLaunchKernelGGL(subtract_minmax_kernel<3>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
