@@ -456,6 +456,23 @@ int unetdc_ccl_labels(const uint8_t* mask, int h, int w, int min_area, void* wor
 int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, int64_t* out, int max_out,
                        unetdc_stream_t s);
 
+
+/* ---- overlap table of two label maps (match.hip; the definition is DESIGN.md section 12) ------------------------------------
+ * unetdc_label_overlap: label_a, label_b ([h][w] int32 each: 0 = background, objects 1..max_a and 1..max_b; any label maps,
+ *   touching labels allowed) -> the triples (a, b, n) with n > 0 = the number of pixels that carry label a on the first map
+ *   and label b on the second, in ascending order of (a, b): triple i at out_a[i], out_b[i], out_n[i].  Pixels whose label
+ *   is below 1 or above max_a (max_b) on either side contribute nothing.
+ *   *out_count = the number of triples; if there are more than max_pairs of them, *out_count = max_pairs + 1, the first
+ *   max_pairs entries of the three arrays are unspecified and nothing beyond them is written.  max_pairs = h * w always
+ *   suffices; max_pairs = 0 is allowed (the three arrays may then be NULL).  Nothing but the outputs and the workspace is
+ *   written.  Sides 1..16384; max_a, max_b, max_pairs >= 0; workspace: unetdc_label_overlap_workspace(h, w, max_pairs) bytes
+ *   (0 for arguments the call would refuse).  Integer atomics and a sort on unique keys: bitwise reproducible, order
+ *   included. */
+int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs);
+int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,
+                         int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_n,
+                         int max_pairs, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

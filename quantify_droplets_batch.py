@@ -21,6 +21,9 @@ runs on the {0,1} mask: unet_dc_segmentation_amd/droplets.py:MASK_RESIZE).
 ``--droplet_shape`` adds the shape and intensity columns of DESIGN.md section 11 to every droplet table (perimeter,
 circularity, axes, eccentricity, orientation, bounding box, touches_border, intensity of the original image): exact integers
 per droplet from csrc/shape.hip on the device or utils/droplet_shape.py on the CPU, one derivation for both.
+``--gt_dir D`` scores every image against its annotated mask D/NAME.* (DESIGN.md section 12): the overlap table of the
+predicted and the annotated label map from csrc/match.hip on the device or utils/droplet_match.py on the CPU, one derivation
+for both; adds gt_label / gt_iou / gt_covered to the droplet tables and writes gt_droplets.csv and match_per_image.csv.
 """
 import argparse
 from pathlib import Path
@@ -122,6 +125,64 @@ def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
     return add_shape_columns(df, props, bin_mask.shape, px_per_um), (labels if split_depth is not None else None)
 
 
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".tif", ".tiff")
+
+
+def find_gt_files(images, gt_dir):
+    """--gt_dir: {image path: annotation path}, checked before anything runs.  The annotation of NAME.ext is
+    gt_dir/NAME.<any image suffix>; a missing one, or one whose size differs from its image, ends the run (PIL reads the
+    sizes from the headers, nothing is decoded)."""
+    found = {}
+    for img in images:
+        cands = [q for q in sorted(Path(gt_dir).glob(img.stem + ".*")) if q.suffix.lower() in IMAGE_SUFFIXES and q.stem == img.stem]
+        if not cands:
+            raise SystemExit(f"--gt_dir: no annotated mask for {img.name} ({Path(gt_dir) / (img.stem + '.*')})")
+        with Image.open(img) as a, Image.open(cands[0]) as b:
+            if a.size != b.size:
+                raise SystemExit(f"--gt_dir: {cands[0]} is {b.size[0]} x {b.size[1]}, its image {img.name} {a.size[0]} x {a.size[1]}")
+        found[str(img)] = cands[0]
+    return found
+
+
+def decode_gt(path, as_labels):
+    """Annotation file -> uint8 {0, 1} mask (convert("L") > 0, as SegmentationDataset reads it) or, with --gt_labels, the
+    int32 label image as it is."""
+    im = Image.open(path)
+    if not as_labels:
+        return (np.array(im.convert("L")) > 0).astype(np.uint8)
+    return np.array(im if im.mode in ("1", "L", "P", "I", "I;16", "I;16B") else im.convert("I")).astype(np.int32)
+
+
+def pred_labels_cpu(bin_mask, min_area, split_depth):
+    """CPU path of --gt_dir: the int32 label map whose numbers are the rows of the droplet table."""
+    if split_depth is not None:
+        from utils.droplet_split import half_pixels, split_labels
+        return split_labels(bin_mask, half_pixels(split_depth), min_area)[0]
+    from utils.droplet_match import gt_labels_numpy
+    return gt_labels_numpy(bin_mask, min_area)
+
+
+def match_cpu(labels, area, gt_item, gt_min_area, gt_are_labels):
+    """CPU path of --gt_dir for one image: what unet_dc_segmentation_amd.evaluate.match_batch returns per image."""
+    from utils import droplet_match as dm
+    glab = gt_item if gt_are_labels else dm.gt_labels_numpy(gt_item, gt_min_area)
+    garea, gsy, gsx = dm.label_sums(glab)
+    a, b, n = dm.overlap_table_numpy(labels, glab, len(area), len(garea))
+    return {"a": a, "b": b, "n": n, "gt_area": garea, "gt_sumy": gsy, "gt_sumx": gsx,
+            "columns": dm.match_columns(area, garea, a, b, n)}
+
+
+def add_match_outputs(gt, df, res, filename):
+    """--gt_dir: the three columns behind the droplet table's own, this image's rows of gt_droplets.csv and its integers."""
+    from utils.droplet_match import gt_table
+    if not df.empty:
+        for name, col in res["columns"]["pred"].items():
+            df[name] = col
+    gt["tables"].append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], res["columns"]["gt"])))
+    gt["images"].append((filename, res["columns"]["image"]))
+    return df
+
+
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
     """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
     split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
@@ -186,7 +247,7 @@ def _density(density, dres, rgb, mask, fpath, name, writers):
 
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None, shape=None):
+              density=None, split_depth=None, shape=None, gt=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
@@ -196,6 +257,8 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
         split = {} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
         if shape is not None:                            # the grey planes go up behind the network's launches
             split.update(shape=True, gray=[torch.from_numpy(g).to(DEVICE) for g in shape["grays"]])
+        if gt is not None and split_depth is None:       # the label maps come through the shape route; its rows may go unused
+            split.update(shape=True, return_labels=True)
         if density is None:
             dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, **split)
         else:                                            # the maps count every component: the table's sums serve when min_area <= 1
@@ -204,6 +267,9 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
             # ... and when the table is not one of split droplets: the maps keep counting connected components
             dres = density_maps_batch(density["rgbs"], [o[0] for o in dev_out], sums if min_area <= 1 and not split else None,
                                       density["nb_layers"], density["kernel"])
+        if gt is not None:                               # the batch's annotations against its label maps: one more host wait
+            from unet_dc_segmentation_amd.evaluate import match_batch
+            mres = match_batch([o[4] for o in dev_out], [o[1] for o in dev_out], gt["items"], gt["min_area"], gt["labels"])
     for i in range(len(tensors)):
         fpath, (oh, ow) = meta[i]
         name = Path(fpath).stem
@@ -223,6 +289,14 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
                 df = quantify(mask, min_area, px_per_um)
             else:
                 df, labels = quantify_split(mask, min_area, px_per_um, split_depth)
+        if gt is not None:
+            if on_device:
+                res = mres[i]
+            else:
+                plab = labels if labels is not None else pred_labels_cpu(mask, min_area, split_depth)
+                res = match_cpu(plab, df["area"].to_numpy() if not df.empty else np.zeros(0, np.int64), gt["items"][i],
+                                gt["min_area"], gt["labels"])
+            df = add_match_outputs(gt, df, res, Path(fpath).name)
         df.insert(0, "filename", Path(fpath).name) if not df.empty else None
         all_props.append(df)
         per_image_rows.append({"filename": Path(fpath).name, "droplet_count": len(df),
@@ -268,6 +342,14 @@ def build_parser():
                    help="add shape and intensity columns to the droplet tables: perimeter, circularity, major / minor axis, "
                         "eccentricity, orientation, bounding box, touches_border, and mean / min / max / std of the original "
                         "image (as grey) under each droplet")
+    p.add_argument("--gt_dir", help="score the droplets against annotated masks: the mask of NAME.ext is GT_DIR/NAME.<image "
+                                    "suffix>, read as grey > 0 and labelled by 4-connected components (never split); adds "
+                                    "gt_label / gt_iou / gt_covered to the droplet tables, writes gt_droplets.csv and "
+                                    "match_per_image.csv")
+    p.add_argument("--gt_min_area", type=int, default=1, help="ignore annotated objects smaller than this (pixels^2)")
+    p.add_argument("--gt_labels", action="store_true",
+                   help="the files of --gt_dir are label images (the 16-bit NAME_labels.png of --split_touching, or any integer "
+                        "image): their values are the labels as they are, numbered 1..max (--gt_min_area does not apply)")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -283,6 +365,11 @@ def main(argv=None):
         raise SystemExit("--split_depth must be a non-negative multiple of 0.5")
     if not args.split_touching:
         split_depth = None
+    images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
+    gt = None
+    if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
+        gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels, "items": [],
+              "tables": [], "images": []}
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -299,7 +386,6 @@ def main(argv=None):
     shape = {"grays": []} if args.droplet_shape else None
     model = load_model(args.ckpt_path, args.dtype)
     tensors, meta, per_image_rows, all_props = [], [], [], []
-    images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in {".png", ".jpg", ".jpeg", ".tif", ".tiff"})
     # File decode runs ahead of the device and the per-image writes behind it, in two small thread pools (both are
     # zlib-bound and release the GIL); the order of the rows in the summary files is the order of `images` as before.
     import os
@@ -316,11 +402,12 @@ def main(argv=None):
                 nxt = next(it, None)
                 if nxt is None:
                     return
-                ahead.append((nxt, dec_pool.submit(decode_rgb, nxt)))
+                ahead.append((nxt, dec_pool.submit(decode_rgb, nxt),
+                              None if gt is None else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"])))
 
         refill()
         while ahead:
-            img, fut = ahead.popleft()
+            img, fut, gt_fut = ahead.popleft()
             refill()
             im = fut.result()
             if shape is not None:                        # the ORIGINAL image as grey, before the rolling ball
@@ -331,23 +418,33 @@ def main(argv=None):
             else:
                 t, osize, rgb = preprocess(img, args.background_radius, im, keep_rgb=True)
                 density["rgbs"].append(rgb)
+            if gt is not None:
+                gt["items"].append(gt_fut.result())
             tensors.append(t)
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
                 if shape is not None:
                     shape["grays"] = []
+                if gt is not None:
+                    gt["items"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:
         pd.DataFrame(density["rows"]).to_csv(out_dir / "density_per_image.csv", index=False)
+    if gt is not None:
+        from utils.droplet_match import pooled_row, summary_row
+        tables = [t for t in gt["tables"] if len(t)] or gt["tables"][:1]
+        pd.concat(tables, ignore_index=True).to_csv(out_dir / "gt_droplets.csv", index=False) if tables else None
+        rows = [summary_row(name, ints) for name, ints in gt["images"]] + [pooled_row([ints for _, ints in gt["images"]])]
+        pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
     summary_df = pd.DataFrame(per_image_rows)
     summary_df.to_csv(out_dir / "summary_per_image.csv", index=False)
     props = [d for d in all_props if not d.empty]

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """End-to-end throughput of the quantify_droplets_batch.py SCRIPT (file decode, preprocessing, network, droplet tables,
 mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG files:
-    python3 tools/quantify_e2e.py [N] [dtype] [--density_maps] [--split_touching] [--droplet_shape]
+    python3 tools/quantify_e2e.py [N] [dtype] [--density_maps] [--split_touching] [--droplet_shape] [--gt]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
 --split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
---droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns)."""
+--droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns).
+--gt: the matching arm (--gt_dir: annotated masks labelled and the overlap table built on the device, gt_droplets.csv and
+match_per_image.csv); the annotation of a synthetic micrograph is its own bright discs, cut out by a grey threshold."""
 import os
 import sys
 import tempfile
@@ -21,6 +23,7 @@ from models.model_2 import UNetDC
 density = "--density_maps" in sys.argv
 split = "--split_touching" in sys.argv
 shape = "--droplet_shape" in sys.argv
+gt = "--gt" in sys.argv
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 64
 dtype = pos[1] if len(pos) > 1 else "bf16"
@@ -30,6 +33,11 @@ with tempfile.TemporaryDirectory() as d:
     imgs = [bench.synthetic_micrograph(7 + i % 8) for i in range(n)]
     for i, im in enumerate(imgs):
         Image.fromarray(im).save(os.path.join(ind, f"img_{i:04d}.png"))
+    if gt:                                                # the discs are 90 grey levels above a background of 40..90
+        gtd = os.path.join(d, "gt")
+        os.makedirs(gtd)
+        for i, im in enumerate(imgs):
+            Image.fromarray((im[..., 0] > 125).astype(np.uint8) * 255).save(os.path.join(gtd, f"img_{i:04d}.png"))
     torch.manual_seed(0)
     m = UNetDC(in_channels=3, out_channels=1)
     if torch.cuda.is_available():                         # calibrate the head bias so that ~10 % of the pixels are "droplet"
@@ -47,8 +55,9 @@ with tempfile.TemporaryDirectory() as d:
     argv += ["--density_maps"] if density else []
     argv += ["--split_touching"] if split else []
     argv += ["--droplet_shape"] if shape else []
+    argv += ["--gt_dir", gtd, "--gt_min_area", "4"] if gt else []
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''})")

@@ -94,6 +94,8 @@ SIGNATURES = {
     "unetdc_ccl_labels_workspace": (L, [I, I]),
     "unetdc_ccl_labels": (I, [P, I, I, I, P, L, P, P, P, P, P, P, I, P]),
     "unetdc_label_props": (I, [P, P, I, I, P, I, P]),
+    "unetdc_label_overlap_workspace": (L, [I, I, I]),
+    "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
 }
 
 _lib = None

@@ -569,6 +569,17 @@ int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, 
   return launch_label_props(label, gray, h, w, reinterpret_cast<long long*>(out), max_out, (hipStream_t)s);
 }
 
+int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) {
+  return h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_pairs >= 0 ? label_overlap_workspace_bytes(h, w, max_pairs) : 0;
+}
+
+int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,
+                         int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_n,
+                         int max_pairs, unetdc_stream_t s) {
+  return launch_label_overlap(label_a, max_a, label_b, max_b, h, w, workspace, (long)workspace_bytes, out_count, out_a, out_b,
+                              out_n, max_pairs, (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

@@ -253,6 +253,12 @@ constexpr int SHAPE_QUANTITIES = 14;
 int launch_label_props(const int* label, const unsigned char* gray, int h, int w, long long* out, int max_out,
                        hipStream_t stream);
 
+// match.hip: the sparse contingency table of two int32 label maps, in (a, b) order
+long label_overlap_workspace_bytes(int h, int w, int max_pairs);
+int launch_label_overlap(const int* label_a, int max_a, const int* label_b, int max_b, int h, int w, void* workspace,
+                         long workspace_bytes, int* out_count, int* out_a, int* out_b, int* out_n, int max_pairs,
+                         hipStream_t stream);
+
 // split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
 long edt_workspace_bytes(int h, int w);
 int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,

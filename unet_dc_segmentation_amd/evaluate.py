@@ -1,0 +1,146 @@
+"""Predicted droplets against annotated masks on the HIP device (csrc/match.hip): the overlap table
+of two device label maps through ``unetdc_label_overlap``, and a whole batch of images enqueued back to back.
+
+Only the triples (a, b, n) and three integers per annotated droplet cross PCIe; the decisions and the float64 columns are
+``utils.droplet_match.match_columns`` on the host, the same function the CPU path uses.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def first_capacity(ka, kb):
+    """Room for the triples of the first try: droplets are compact, a handful of partners each."""
+    return 4 * (int(ka) + int(kb)) + 64
+
+
+def _check_labels(t, what):
+    if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous():
+        raise _lib.UnetdcError(f"{what} must be a contiguous int32 [h, w] tensor on the HIP device")
+
+
+def label_overlap(label_a, ka, label_b, kb, capacity=None):
+    """label_a, label_b: int32 [h, w] DEVICE label maps (objects 1..ka, 1..kb).  -> int64 arrays (a, b, n): the overlap table
+    in (a, b) order.  The first try has room for first_capacity(ka, kb) triples (or `capacity`); a table that does not fit
+    is computed again with four times the room, at most h * w, which always suffices."""
+    _check_labels(label_a, "label_a")
+    _check_labels(label_b, "label_b")
+    if label_a.shape != label_b.shape:
+        raise _lib.UnetdcError("the two label maps differ in size")
+    h, w = label_a.shape
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    dev = label_a.device
+    cap = int(min(max(first_capacity(ka, kb) if capacity is None else int(capacity), 0), h * w))
+    while True:
+        wsb = lib.unetdc_label_overlap_workspace(h, w, cap)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        out = torch.empty(1 + 3 * cap, dtype=torch.int32, device=dev)
+        rows = out[1:].view(3, cap)
+        _lib.call("unetdc_label_overlap", label_a.data_ptr(), int(ka), label_b.data_ptr(), int(kb), h, w, ws.data_ptr(), wsb,
+                  out.data_ptr(), rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), cap, s)
+        n = int(out[:1].cpu()[0])
+        if n <= cap:
+            t = rows[:, :n].cpu().numpy().astype(np.int64)
+            return t[0], t[1], t[2]
+        cap = min(4 * max(cap, 1), h * w)
+
+
+def match_batch(pred_labels, pred_areas, gts, gt_min_area=1, gt_are_labels=False, max_gt=1 << 14):
+    """pred_labels: B int32 [h, w] DEVICE label maps; pred_areas: B int64 arrays, the areas of their objects 1..Ka;
+    gts: B annotations of the same sizes, numpy arrays or DEVICE tensors -- binary masks (nonzero = droplet; labelled here by
+    4-connected components of at least gt_min_area pixels, never split) or, with gt_are_labels, integer label images whose
+    values are the labels as they are (areas by bincount on the host; gt_min_area does not apply).
+    Every launch of the batch (per image unetdc_ccl_labels, then unetdc_label_overlap) is enqueued back to back on the
+    current stream into one set of output planes; the host then waits ONCE, on the copy of the counts, and fetches the
+    filled part of the int32 and of the int64 outputs.  An image with more annotated droplets than max_gt, or more pairs
+    than its first capacity, is computed again on its own.
+    Returns per image a dict: a, b, n (the triples), gt_area, gt_sumy, gt_sumx (int64 [Kb]) and columns =
+    utils.droplet_match.match_columns(pred_area, gt_area, a, b, n)."""
+    from utils.droplet_match import label_sums, match_columns
+    B = len(pred_labels)
+    if not (len(pred_areas) == len(gts) == B):
+        raise _lib.UnetdcError("match_batch needs one area list and one annotation per label map")
+    if B == 0:
+        return []
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    dev = pred_labels[0].device
+    hws, kas = [], [len(a) for a in pred_areas]
+    for lab in pred_labels:
+        _check_labels(lab, "a predicted label map")
+        hws.append((int(lab.shape[0]), int(lab.shape[1])))
+    host_sums, gt_dev = [None] * B, []
+    for i, g in enumerate(gts):
+        if tuple(g.shape) != hws[i]:
+            raise _lib.UnetdcError(f"annotation {i} is {tuple(g.shape)}, its image {hws[i]}")
+        if gt_are_labels:
+            g_h = g.cpu().numpy() if torch.is_tensor(g) else np.asarray(g)
+            if g_h.max(initial=0) > 2 ** 31 - 1:
+                raise _lib.UnetdcError("labels above 2^31 - 1")
+            host_sums[i] = label_sums(g_h)
+            g = g if torch.is_tensor(g) and g.dtype == torch.int32 else torch.from_numpy(np.ascontiguousarray(g_h, dtype=np.int32))
+        else:
+            g = g if torch.is_tensor(g) else torch.from_numpy(np.ascontiguousarray(np.asarray(g) > 0, dtype=np.uint8))
+            g = g if g.dtype == torch.uint8 else (g != 0).to(torch.uint8)
+        gt_dev.append(g.to(dev).contiguous())
+    capb = 0 if gt_are_labels else int(min(max_gt, max(h * w for h, w in hws)))
+    # the number of annotated droplets is not known before the wait: room for as many pairs as twice the prediction suggests
+    caps = [int(min(first_capacity(ka, ka) + 1024, h * w)) for ka, (h, w) in zip(kas, hws)]
+    P = max(caps)
+    wsb = max(max(lib.unetdc_label_overlap_workspace(h, w, c) for (h, w), c in zip(hws, caps)),
+              0 if gt_are_labels else max(lib.unetdc_ccl_labels_workspace(h, w) for h, w in hws))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)           # one workspace: the launches are stream-ordered
+    counts = torch.zeros(B, 2, dtype=torch.int32, device=dev)      # annotated droplets, triples
+    W = max(capb, P, 1)
+    i32 = torch.empty(B, 4, W, dtype=torch.int32, device=dev)      # gt area, then a, b, n
+    i64 = torch.empty(B, 2, max(capb, 1), dtype=torch.int64, device=dev)
+    gt_labels = []
+    for i, (h, w) in enumerate(hws):
+        if gt_are_labels:
+            lab, kb = gt_dev[i], len(host_sums[i][0])
+        else:
+            lab, kb = torch.empty(h, w, dtype=torch.int32, device=dev), capb
+            _lib.call("unetdc_ccl_labels", gt_dev[i].data_ptr(), h, w, int(max(gt_min_area, 1)), ws.data_ptr(), wsb,
+                      counts[i, 0:].data_ptr(), i32[i, 0].data_ptr(), i64[i, 0].data_ptr(), i64[i, 1].data_ptr(), None,
+                      lab.data_ptr(), capb, s)
+        _lib.call("unetdc_label_overlap", pred_labels[i].data_ptr(), kas[i], lab.data_ptr(), kb, h, w, ws.data_ptr(), wsb,
+                  counts[i, 1:].data_ptr(), i32[i, 1].data_ptr(), i32[i, 2].data_ptr(), i32[i, 3].data_ptr(), caps[i], s)
+        gt_labels.append(lab)
+    c = counts.cpu().numpy().astype(np.int64)                      # the batch's only host wait
+    filled = int(max(min(c[:, 0].max(initial=0), capb), np.minimum(c[:, 1], caps).max(initial=0)))
+    v32 = i32[:, :, :filled].cpu().numpy().astype(np.int64)
+    v64 = i64[:, :, :int(min(c[:, 0].max(initial=0), capb))].cpu().numpy()
+    out = []
+    for i, (h, w) in enumerate(hws):
+        lab = gt_labels[i]
+        if gt_are_labels:
+            area, sy, sx = host_sums[i]
+        elif c[i, 0] > capb:                      # more annotated droplets than the outputs hold: this image again with room
+            area, sy, sx, lab = _gt_labels_again(lib, gt_dev[i], h, w, gt_min_area, int(c[i, 0]), s)
+        else:
+            area, sy, sx = v32[i, 0, :c[i, 0]], v64[i, 0, :c[i, 0]], v64[i, 1, :c[i, 0]]
+        if c[i, 1] > caps[i] or (not gt_are_labels and c[i, 0] > capb):
+            a, b, n = label_overlap(pred_labels[i], kas[i], lab, len(area))
+        else:
+            a, b, n = (v32[i, j, :c[i, 1]] for j in (1, 2, 3))
+        out.append({"a": a, "b": b, "n": n, "gt_area": area, "gt_sumy": sy, "gt_sumx": sx,
+                    "columns": match_columns(pred_areas[i], area, a, b, n)})
+    return out
+
+
+def _gt_labels_again(lib, mask, h, w, min_area, k, s):
+    dev = mask.device
+    wsb = lib.unetdc_ccl_labels_workspace(h, w)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    area = torch.empty(k, dtype=torch.int32, device=dev)
+    sums = torch.empty(2, k, dtype=torch.int64, device=dev)
+    lab = torch.empty(h, w, dtype=torch.int32, device=dev)
+    _lib.call("unetdc_ccl_labels", mask.data_ptr(), h, w, int(max(min_area, 1)), ws.data_ptr(), wsb, count.data_ptr(),
+              area.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), None, lab.data_ptr(), k, s)
+    s_h = sums.cpu().numpy()
+    return area.cpu().numpy().astype(np.int64), s_h[0], s_h[1], lab
