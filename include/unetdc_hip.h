@@ -473,6 +473,28 @@ int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label
                          int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_n,
                          int max_pairs, unetdc_stream_t s);
 
+
+/* ---- cleaning a mask before the droplet stages (clean.hip; the definition is DESIGN.md section 13) --------------------------
+ * unetdc_mask_clean: strong and weak ([h][w] uint8, nonzero = 1; weak may be NULL) -> out_mask ([h][w] uint8 in {0,1}):
+ *     hysteresis  (weak given) M = the union of the 4-connected components of weak that contain a pixel where strong and weak
+ *                 are both 1; a strong pixel outside weak is ignored.  Without weak, M = strong.
+ *     holes       (max_hole_area != 0) a hole is a 4-connected component of the background of M without a pixel on the first
+ *                 or last row or column; every hole of at most max_hole_area pixels (any size when max_hole_area < 0) is
+ *                 set to 1 (= scipy.ndimage.binary_fill_holes when there is no limit).
+ *   out_counts (DEVICE, 4 x int32, may be NULL): pixels of M not in strong, holes filled, pixels filled, holes left open
+ *   because of their size (the last three are 0 when max_hole_area == 0).
+ *   With weak == NULL and max_hole_area == 0 the call copies strong to out_mask.
+ *   Aliasing: out_mask may BE strong or weak (the same pointer: the call then works in place); an out_mask that overlaps
+ *   either only partly, and a workspace or out_counts that overlaps any other argument, return UNETDC_EINVAL.  strong and weak
+ *   may overlap each other in any way.
+ *   Sides 1..16384; workspace: unetdc_mask_clean_workspace(h, w) bytes (8 per pixel + 64; 0 for a side out of range), 4-byte
+ *   aligned.  A bad geometry, a null strong / out_mask / workspace and a workspace that is too small return UNETDC_EINVAL
+ *   before the first launch.  Launches on the given stream only; no host wait, no allocation.  Flags, integer atomics and a
+ *   union-find: the outputs depend on no order, two runs are bitwise equal. */
+int64_t unetdc_mask_clean_workspace(int h, int w);
+int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, int max_hole_area, void* workspace,
+                      int64_t workspace_bytes, uint8_t* out_mask, int32_t* out_counts, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,10 @@ per droplet from csrc/shape.hip on the device or utils/droplet_shape.py on the C
 ``--gt_dir D`` scores every image against its annotated mask D/NAME.* (DESIGN.md section 12): the overlap table of the
 predicted and the annotated label map from csrc/match.hip on the device or utils/droplet_match.py on the CPU, one derivation
 for both; adds gt_label / gt_iou / gt_covered to the droplet tables and writes gt_droplets.csv and match_per_image.csv.
+``--prob_thresh_low T`` / ``--fill_holes [N]`` clean the mask before anything reads it: hysteresis
+thresholding between T and --prob_thresh, then holes of at most N pixels (any size without N) are filled; csrc/clean.hip on the
+device, utils/droplet_clean.py on the CPU.  The cleaned mask is the one every output sees; mask_clean_per_image.csv says
+what was changed per image.
 """
 import argparse
 from pathlib import Path
@@ -247,11 +251,15 @@ def _density(density, dres, rgb, mask, fpath, name, writers):
 
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None, shape=None, gt=None):
+              density=None, split_depth=None, shape=None, gt=None, clean=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
     masks512 = None if on_device else (probs[:, 0] > thresh).to(torch.uint8).numpy()
+    weak512 = None                                       # --prob_thresh_low on the CPU path: the mask of the low threshold
+    if clean is not None and clean["low"] is not None and not on_device:
+        weak512 = (probs[:, 0] > clean["low"]).to(torch.uint8).numpy()
+    clean_counts = []
     if on_device:                                        # the whole batch enqueued back to back, ONE host wait (droplets.py)
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
         split = {} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
@@ -259,6 +267,8 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
             split.update(shape=True, gray=[torch.from_numpy(g).to(DEVICE) for g in shape["grays"]])
         if gt is not None and split_depth is None:       # the label maps come through the shape route; its rows may go unused
             split.update(shape=True, return_labels=True)
+        if clean is not None:                            # the counts ride in the copy of the droplet counts
+            split.update(thresh_low=clean["low"], max_hole_area=clean["holes"], clean_counts=clean_counts)
         if density is None:
             dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, **split)
         else:                                            # the maps count every component: the table's sums serve when min_area <= 1
@@ -283,6 +293,11 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
                 df = add_shape_columns(df, dev_out[i][-1], (oh, ow), px_per_um)
         else:
             mask = resize_mask_like_reference(masks512[i], ow, oh)
+            if clean is not None:                        # both masks under the same resize rule, then utils/droplet_clean.py
+                from utils.droplet_clean import clean_mask
+                weak = None if weak512 is None else resize_mask_like_reference(weak512[i], ow, oh)
+                mask, counts = clean_mask(mask, weak, clean["holes"])
+                clean_counts.append(counts)
             if shape is not None:
                 df, labels = quantify_shape(mask, min_area, px_per_um, split_depth, shape["grays"][i])
             elif split_depth is None:
@@ -297,6 +312,9 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
                 res = match_cpu(plab, df["area"].to_numpy() if not df.empty else np.zeros(0, np.int64), gt["items"][i],
                                 gt["min_area"], gt["labels"])
             df = add_match_outputs(gt, df, res, Path(fpath).name)
+        if clean is not None:
+            from utils.droplet_clean import COUNT_NAMES
+            clean["rows"].append({"filename": Path(fpath).name, **{k: int(v) for k, v in zip(COUNT_NAMES, clean_counts[i])}})
         df.insert(0, "filename", Path(fpath).name) if not df.empty else None
         all_props.append(df)
         per_image_rows.append({"filename": Path(fpath).name, "droplet_count": len(df),
@@ -350,9 +368,28 @@ def build_parser():
     p.add_argument("--gt_labels", action="store_true",
                    help="the files of --gt_dir are label images (the 16-bit NAME_labels.png of --split_touching, or any integer "
                         "image): their values are the labels as they are, numbered 1..max (--gt_min_area does not apply)")
+    p.add_argument("--prob_thresh_low", type=float,
+                   help="hysteresis threshold: also keep every 4-connected region above this lower threshold that contains a "
+                        "pixel above --prob_thresh (must not exceed it; equal = off)")
+    p.add_argument("--fill_holes", type=int, nargs="?", const=-1, default=0, metavar="N",
+                   help="fill the holes of the mask (background not 4-connected to the image border) before anything is "
+                        "measured: holes of at most N pixels, of any size without N; writes mask_clean_per_image.csv")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
+
+
+def clean_options(args):
+    """--prob_thresh_low / --fill_holes -> {"low": threshold or None, "holes": limit (-1 = any size), "rows": []}, None with
+    both off; a bad value ends the run before any image."""
+    low, holes = args.prob_thresh_low, args.fill_holes
+    if low is not None and not low <= args.prob_thresh:
+        raise SystemExit(f"--prob_thresh_low ({low}) must not exceed --prob_thresh ({args.prob_thresh})")
+    if holes < -1:
+        raise SystemExit("--fill_holes N: N is a number of pixels (0 = off)")
+    if low is not None and low == args.prob_thresh:
+        low = None                                       # selects what --prob_thresh selects
+    return None if low is None and holes == 0 else {"low": low, "holes": holes, "rows": []}
 
 
 def main(argv=None):
@@ -365,6 +402,7 @@ def main(argv=None):
         raise SystemExit("--split_depth must be a non-negative multiple of 0.5")
     if not args.split_touching:
         split_depth = None
+    clean = clean_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -424,7 +462,7 @@ def main(argv=None):
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
@@ -434,7 +472,7 @@ def main(argv=None):
                     gt["items"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:
@@ -445,6 +483,8 @@ def main(argv=None):
         pd.concat(tables, ignore_index=True).to_csv(out_dir / "gt_droplets.csv", index=False) if tables else None
         rows = [summary_row(name, ints) for name, ints in gt["images"]] + [pooled_row([ints for _, ints in gt["images"]])]
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
+    if clean is not None:
+        pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     summary_df = pd.DataFrame(per_image_rows)
     summary_df.to_csv(out_dir / "summary_per_image.csv", index=False)
     props = [d for d in all_props if not d.empty]

@@ -2,11 +2,14 @@
 """End-to-end throughput of the quantify_droplets_batch.py SCRIPT (file decode, preprocessing, network, droplet tables,
 mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG files:
     python3 tools/quantify_e2e.py [N] [dtype] [--density_maps] [--split_touching] [--droplet_shape] [--gt]
+                                  [--prob_thresh_low T] [--fill_holes[=N]]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
 --split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
 --droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns).
 --gt: the matching arm (--gt_dir: annotated masks labelled and the overlap table built on the device, gt_droplets.csv and
-match_per_image.csv); the annotation of a synthetic micrograph is its own bright discs, cut out by a grey threshold."""
+match_per_image.csv); the annotation of a synthetic micrograph is its own bright discs, cut out by a grey threshold.
+--prob_thresh_low T, --fill_holes or --fill_holes=N: passed through to the script (the mask-cleaning arm: hysteresis and hole
+filling on the device)."""
 import os
 import sys
 import tempfile
@@ -24,6 +27,12 @@ density = "--density_maps" in sys.argv
 split = "--split_touching" in sys.argv
 shape = "--droplet_shape" in sys.argv
 gt = "--gt" in sys.argv
+clean_argv = []
+if "--prob_thresh_low" in sys.argv:                       # the one flag here that takes a separate value
+    k = sys.argv.index("--prob_thresh_low")
+    clean_argv += sys.argv[k:k + 2]
+    del sys.argv[k:k + 2]
+clean_argv += [a for a in sys.argv[1:] if a.split("=")[0] == "--fill_holes"]
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 64
 dtype = pos[1] if len(pos) > 1 else "bf16"
@@ -56,8 +65,9 @@ with tempfile.TemporaryDirectory() as d:
     argv += ["--split_touching"] if split else []
     argv += ["--droplet_shape"] if shape else []
     argv += ["--gt_dir", gtd, "--gt_min_area", "4"] if gt else []
+    argv += clean_argv
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{', mask cleaning' if clean_argv else ''})")

@@ -96,6 +96,8 @@ SIGNATURES = {
     "unetdc_label_props": (I, [P, P, I, I, P, I, P]),
     "unetdc_label_overlap_workspace": (L, [I, I, I]),
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
+    "unetdc_mask_clean_workspace": (L, [I, I]),
+    "unetdc_mask_clean": (I, [P, P, I, I, I, P, L, P, P, P]),
 }
 
 _lib = None

@@ -580,6 +580,16 @@ int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label
                               out_n, max_pairs, (hipStream_t)s);
 }
 
+int64_t unetdc_mask_clean_workspace(int h, int w) {
+  return h > 0 && w > 0 && h <= 16384 && w <= 16384 ? mask_clean_workspace_bytes(h, w) : 0;
+}
+
+int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, int max_hole_area, void* workspace,
+                      int64_t workspace_bytes, uint8_t* out_mask, int32_t* out_counts, unetdc_stream_t s) {
+  return launch_mask_clean(strong, weak, h, w, max_hole_area, workspace, (long)workspace_bytes, out_mask, out_counts,
+                           (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

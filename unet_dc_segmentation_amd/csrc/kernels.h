@@ -268,6 +268,11 @@ int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, in
                        long workspace_bytes, int* out_count, int* out_area, long long* out_sumy, long long* out_sumx,
                        int* out_root, int* out_label, int max_out, hipStream_t stream);
 
+// clean.hip: hysteresis threshold and hole filling of a {0,1} mask (include/unetdc_hip.h)
+long mask_clean_workspace_bytes(int h, int w);
+int launch_mask_clean(const unsigned char* strong, const unsigned char* weak, int h, int w, int max_hole_area, void* workspace,
+                      long workspace_bytes, unsigned char* out_mask, int* out_counts, hipStream_t stream);
+
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).
 constexpr int AUG_HFLIP = 1, AUG_VFLIP = 2, AUG_BC = 4;
