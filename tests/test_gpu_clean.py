@@ -23,14 +23,19 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def device_clean(strong, weak, limit, counts=True, in_place=None, ws_bytes=None):
+def device_clean(strong, weak, limit, counts=True, in_place=None, ws_bytes=None, ws=None):
     """-> (mask, counts list or None).  out_mask is a plane with two canary rows above and below, out_counts has PAD canary
-    words on both sides; in_place = "strong" / "weak" makes that input the output plane."""
+    words on both sides; in_place = "strong" / "weak" makes that input the output plane;
+    ws: a prepared Canaried view (tests/image_canaries.py) to use as the workspace, its guards checked here."""
     from unet_dc_segmentation_amd import _lib
     h, w = strong.shape
     lib = _lib.load()
     nbytes = lib.unetdc_mask_clean_workspace(h, w) if ws_bytes is None else ws_bytes
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+    if ws is None:
+        wbuf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+        wptr = wbuf.data_ptr()
+    else:
+        wptr, nbytes = ws.ptr, ws.nbytes
     buf = torch.full(((h + 4) * w,), CANARY8, dtype=torch.uint8, device="cuda")
     out = buf[2 * w:(h + 2) * w]
     s = torch.from_numpy(np.ascontiguousarray(strong)).cuda()
@@ -42,8 +47,10 @@ def device_clean(strong, weak, limit, counts=True, in_place=None, ws_bytes=None)
         out.copy_(k.flatten())
         k = out
     cnt = torch.full((4 + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
-    _lib.call("unetdc_mask_clean", s.data_ptr(), None if k is None else k.data_ptr(), h, w, limit, ws.data_ptr(), nbytes,
+    _lib.call("unetdc_mask_clean", s.data_ptr(), None if k is None else k.data_ptr(), h, w, limit, wptr, nbytes,
               out.data_ptr(), cnt[PAD:].data_ptr() if counts else None, stream())
+    if ws is not None:
+        ws.check("workspace")
     b = buf.cpu().numpy()
     assert np.all(b[:2 * w] == CANARY8) and np.all(b[(h + 2) * w:] == CANARY8), "write outside the output plane"
     c = cnt.cpu().numpy()

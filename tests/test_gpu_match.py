@@ -16,27 +16,36 @@ WS_PAD = 256          # canary bytes on both sides of the workspace
 WS_CANARY = 0xA5
 
 
-def device_overlap(A, ka, B, kb, max_pairs=None):
+def device_overlap(A, ka, B, kb, max_pairs=None, ws=None):
     """-> (count, [(a, b, n)] of the first min(count, max_pairs) entries).  The count, the three arrays and the workspace sit
     between canaries; only the first min(count, max_pairs) entries of the arrays may have been written, and on overflow
-    nothing past max_pairs."""
+    nothing past max_pairs.  ws: a prepared Canaried view (tests/image_canaries.py) of exactly the queried bytes to use as the
+    workspace, its guards checked here."""
     from unet_dc_segmentation_amd import _lib
     h, w = A.shape
     lib = _lib.load()
     cap = h * w if max_pairs is None else max_pairs
     nbytes = lib.unetdc_label_overlap_workspace(h, w, cap)
     assert nbytes > 0
-    ws = torch.full((nbytes + 2 * WS_PAD,), WS_CANARY, dtype=torch.uint8, device="cuda")
+    if ws is None:
+        wbuf = torch.full((nbytes + 2 * WS_PAD,), WS_CANARY, dtype=torch.uint8, device="cuda")
+        wptr = wbuf[WS_PAD:].data_ptr()
+    else:
+        assert ws.nbytes == nbytes
+        wbuf, wptr = None, ws.ptr
     la = torch.from_numpy(np.ascontiguousarray(A, dtype=np.int32)).cuda()
     lb = torch.from_numpy(np.ascontiguousarray(B, dtype=np.int32)).cuda()
     count = torch.full((1 + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
     outs = [torch.full((cap + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda") for _ in range(3)]
-    _lib.call("unetdc_label_overlap", la.data_ptr(), ka, lb.data_ptr(), kb, h, w, ws[WS_PAD:].data_ptr(), nbytes,
+    _lib.call("unetdc_label_overlap", la.data_ptr(), ka, lb.data_ptr(), kb, h, w, wptr, nbytes,
               count[PAD:].data_ptr(), *(t[PAD:].data_ptr() for t in outs), cap, stream())
     c = count.cpu().numpy()
     assert np.all(c[:PAD] == CANARY32) and np.all(c[PAD + 1:] == CANARY32)
-    wsh = ws.cpu().numpy()
-    assert np.all(wsh[:WS_PAD] == WS_CANARY) and np.all(wsh[WS_PAD + nbytes:] == WS_CANARY), "write outside the workspace"
+    if wbuf is None:
+        ws.check("workspace")
+    else:
+        wsh = wbuf.cpu().numpy()
+        assert np.all(wsh[:WS_PAD] == WS_CANARY) and np.all(wsh[WS_PAD + nbytes:] == WS_CANARY), "write outside the workspace"
     n = int(c[PAD])
     assert 0 <= n <= cap + 1
     k = min(n, cap)

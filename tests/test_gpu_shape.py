@@ -7,7 +7,7 @@ import pytest
 import torch
 from scipy import ndimage
 
-from tests.test_gpu_split import CANARY32, PAD, device_split, plane_result, plane_with_canaries, probs_of, stream
+from tests.test_gpu_split import CANARY32, PAD, device_split, plane_result, plane_with_canaries, probs_of, stream, workspace
 from tests.test_shape_cpu import INPUTS, cc_labels, gray_plane, split_labels
 from tests.test_split_cpu import files, noise_mask, small_masks
 from utils import droplet_shape as sh
@@ -19,13 +19,12 @@ NQ = len(sh.QUANTITIES)
 CANARY64 = -0x0123456789ABCDEF
 
 
-def device_ccl_labels(mask, min_area=1, max_out=None):
+def device_ccl_labels(mask, min_area=1, max_out=None, ws=None):
     """-> (count, rows [(area, sum_row, sum_col, first_index)], label map); every output between canaries."""
     from unet_dc_segmentation_amd import _lib
     h, w = mask.shape
     lib = _lib.load()
-    nbytes = lib.unetdc_ccl_labels_workspace(h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    ws, wptr, nbytes = workspace(lib.unetdc_ccl_labels_workspace(h, w), ws)
     cap = h * w if max_out is None else max_out
     m = torch.from_numpy(np.ascontiguousarray(mask)).cuda()
     count = torch.full((1 + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
@@ -35,7 +34,9 @@ def device_ccl_labels(mask, min_area=1, max_out=None):
     sx = torch.full((cap + 2 * PAD,), CANARY32, dtype=torch.int64, device="cuda")
     lbuf, lab = plane_with_canaries(h, w)
     ptrs = [t[PAD:].data_ptr() for t in (count, area, sy, sx, root)]
-    _lib.call("unetdc_ccl_labels", m.data_ptr(), h, w, min_area, ws.data_ptr(), nbytes, *ptrs, lab.data_ptr(), cap, stream())
+    _lib.call("unetdc_ccl_labels", m.data_ptr(), h, w, min_area, wptr, nbytes, *ptrs, lab.data_ptr(), cap, stream())
+    if hasattr(ws, "check"):
+        ws.check("workspace")
     c = count.cpu().numpy()
     assert np.all(c[:PAD] == CANARY32) and np.all(c[PAD + 1:] == CANARY32)
     n = int(c[PAD])
@@ -48,8 +49,10 @@ def device_ccl_labels(mask, min_area=1, max_out=None):
     return n, [tuple(int(x) for x in r) for r in zip(*cols)], plane_result(lbuf, h, w)
 
 
-def device_props(labels, gray=None, max_out=None):
-    """unetdc_label_props -> int64 [NQ][max_out]; the output sits between canary rows that must come back intact."""
+def device_props(labels, gray=None, max_out=None, prefill=None):
+    """unetdc_label_props -> int64 [NQ][max_out]; the output sits between canary rows that must come back intact.
+    prefill: what the output rows hold before the call (a byte value, or an int64 tensor of NQ * max_out stale integers);
+    the canary pattern otherwise."""
     from unet_dc_segmentation_amd import _lib
     h, w = labels.shape
     cap = int(labels.max(initial=0)) if max_out is None else max_out
@@ -58,6 +61,10 @@ def device_props(labels, gray=None, max_out=None):
     g = None if gray is None else torch.from_numpy(np.ascontiguousarray(gray)).cuda()
     flat = buf.view(-1)
     out = flat[max(cap, 1):]
+    if isinstance(prefill, int):
+        out[:NQ * cap].view(torch.uint8).fill_(prefill)
+    elif prefill is not None:
+        out[:NQ * cap].copy_(prefill)
     _lib.call("unetdc_label_props", lab.data_ptr(), None if g is None else g.data_ptr(), h, w, out.data_ptr(), cap, stream())
     b = flat.cpu().numpy()
     lo, hi = max(cap, 1), max(cap, 1) + NQ * cap

@@ -33,27 +33,36 @@ def plane_result(buf, h, w):
     return b[2 * w:(h + 2) * w].reshape(h, w)
 
 
-def device_edt(mask):
+def workspace(nbytes, ws):
+    """-> (owner, address, bytes) of the workspace of a call: a fresh allocation of nbytes, or the Canaried view `ws` a test
+    prepared (tests/image_canaries.py; the caller of this checks its guards after the call)."""
+    if ws is None:
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+        return ws, ws.data_ptr(), nbytes
+    return ws, ws.ptr, ws.nbytes
+
+
+def device_edt(mask, ws=None):
     from unet_dc_segmentation_amd import _lib
     h, w = mask.shape
     lib = _lib.load()
-    nbytes = lib.unetdc_split_workspace(h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    ws, wptr, nbytes = workspace(lib.unetdc_split_workspace(h, w), ws)
     buf, out = plane_with_canaries(h, w)
     m = torch.from_numpy(np.ascontiguousarray(mask)).cuda()
-    _lib.call("unetdc_edt_sq", m.data_ptr(), h, w, out.data_ptr(), ws.data_ptr(), nbytes, stream())
+    _lib.call("unetdc_edt_sq", m.data_ptr(), h, w, out.data_ptr(), wptr, nbytes, stream())
+    if hasattr(ws, "check"):
+        ws.check("workspace")
     return plane_result(buf, h, w)
 
 
-def device_split(mask, h2, min_area=1, max_out=None, labels=True, call="unetdc_split_stats"):
+def device_split(mask, h2, min_area=1, max_out=None, labels=True, call="unetdc_split_stats", ws=None):
     """-> (count, rows [(area, sum_row, sum_col, first_index)], label map or None); every output sits between canaries and
     only the first min(count, max_out) entries of the per-droplet outputs may have been written."""
     from unet_dc_segmentation_amd import _lib
     h, w = mask.shape
     lib = _lib.load()
     split = call == "unetdc_split_stats"
-    nbytes = lib.unetdc_split_workspace(h, w) if split else lib.unetdc_ccl_workspace(h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    ws, wptr, nbytes = workspace(lib.unetdc_split_workspace(h, w) if split else lib.unetdc_ccl_workspace(h, w), ws)
     cap = h * w if max_out is None else max_out
     m = torch.from_numpy(np.ascontiguousarray(mask)).cuda()
     count = torch.full((1 + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
@@ -64,10 +73,12 @@ def device_split(mask, h2, min_area=1, max_out=None, labels=True, call="unetdc_s
     lbuf, lab = plane_with_canaries(h, w) if labels and split else (None, None)
     ptrs = [t[PAD:].data_ptr() for t in (count, area, sy, sx, root)]
     if split:
-        _lib.call(call, m.data_ptr(), h, w, min_area, h2, ws.data_ptr(), nbytes, *ptrs, None if lab is None else lab.data_ptr(),
+        _lib.call(call, m.data_ptr(), h, w, min_area, h2, wptr, nbytes, *ptrs, None if lab is None else lab.data_ptr(),
                   cap, stream())
     else:
-        _lib.call(call, m.data_ptr(), h, w, min_area, ws.data_ptr(), nbytes, *ptrs, cap, stream())
+        _lib.call(call, m.data_ptr(), h, w, min_area, wptr, nbytes, *ptrs, cap, stream())
+    if hasattr(ws, "check"):
+        ws.check("workspace")
     c = count.cpu().numpy()
     assert np.all(c[:PAD] == CANARY32) and np.all(c[PAD + 1:] == CANARY32)
     n = int(c[PAD])
@@ -118,6 +129,62 @@ def test_edt_without_background_and_with_one_far_background_pixel():
     m[1039, 0] = 0
     yy, xx = np.mgrid[0:1040, 0:1388]
     assert np.array_equal(device_edt(m), (yy - 1039) ** 2 + xx ** 2)
+
+
+def scipy_edt_sq(m):
+    if m.all():
+        return np.full(m.shape, 2 ** 31 - 1, np.int64)
+    d = ndimage.distance_transform_edt(m)
+    return np.rint(d * d).astype(np.int64)
+
+
+def random_mask(h, w, density, seed):
+    return (np.random.default_rng(seed).random((h, w)) < density).astype(np.uint8)
+
+
+@pytest.mark.parametrize("w", [63, 64, 65, 255, 256, 257])
+def test_edt_at_the_block_seams(w):
+    """edt_col_kernel runs 64 columns per block, edt_row_kernel strides a row by 256 threads: one column short of a block,
+    a full block, one column into the next."""
+    m = random_mask(5, w, 0.7, seed=w)
+    assert m[:, w - 1].any() and not m.all()
+    assert np.array_equal(device_edt(m), scipy_edt_sq(m))
+
+
+def test_edt_full_lds_row_and_the_longest_scan():
+    """2 x 16384, the promised maximum: the row of g fills 64 KiB of LDS, and with background at (0, 0) only the scan of the
+    last pixel runs over the whole row and ends in d^2 = 16383^2 + 1 on the second row."""
+    m = np.ones((2, 16384), np.uint8)
+    m[0, 0] = 0
+    xx = np.arange(16384, dtype=np.int64)
+    ref = np.stack([xx * xx, xx * xx + 1])
+    assert np.array_equal(scipy_edt_sq(m), ref) and ref[1, -1] == 16383 ** 2 + 1
+    assert np.array_equal(device_edt(m), ref)
+
+
+@pytest.mark.parametrize("shape", [(16384, 1), (1, 16384)], ids=["16384x1", "1x16384"])
+def test_edt_one_pixel_wide_at_the_promised_maximum(shape):
+    m = random_mask(*shape, 0.7, seed=shape[0])
+    assert not m.all()
+    assert np.array_equal(device_edt(m), scipy_edt_sq(m))
+
+
+def test_edt_without_background_at_the_promised_width():
+    assert np.all(device_edt(np.ones((3, 16384), np.uint8)) == 2 ** 31 - 1)
+
+
+@pytest.mark.parametrize("h2", [0, 4])
+@pytest.mark.parametrize("shape", [(5, 64), (5, 65), (5, 257), (3, 4097)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_split_at_the_block_seams(shape, h2):
+    """Noise at density 0.6: components that cross the 64-column seams of the distance transform, the 256-thread blocks of the
+    per-pixel kernels and the 1024-pixel blocks of the compaction (3 x 4097: one pixel into the thirteenth block)."""
+    m = random_mask(*shape, 0.6, seed=shape[1])
+    w = shape[1]
+    seams = [bool((m[:, x - 1] & m[:, x]).any()) for x in range(64, w, 64)]
+    assert not seams or sum(seams) > len(seams) // 2                       # components across most seams (5 x 64 has none inside)
+    lab, rows = host_rows(m, h2)
+    n, drows, dlab = device_split(m, h2)
+    assert n == len(rows) and drows == rows and np.array_equal(dlab, lab)
 
 
 @pytest.mark.parametrize("h2", [0, 1, 4, 7])
