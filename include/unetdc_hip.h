@@ -495,6 +495,24 @@ int64_t unetdc_mask_clean_workspace(int h, int w);
 int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, int max_hole_area, void* workspace,
                       int64_t workspace_bytes, uint8_t* out_mask, int32_t* out_counts, unetdc_stream_t s);
 
+
+/* ---- threshold sweep against an annotation (sweep.hip; the definition is DESIGN.md section 14) ------------------------------
+ * unetdc_thresh_sweep: probs ([n][ph][pw] fp32), gt ([n][oh][ow] uint8, nonzero = annotated), n >= 1 images of one geometry,
+ *   k in 1..1024 thresholds t_j = (float)j / (float)k, j = 0..k-1 (one fp32 division each).
+ *   mask_j = what unetdc_mask_from_probs (xofs, xcoef, yofs, ycoef all NULL: nearest rule) or unetdc_mask_from_probs_linear (all
+ *   four given: the tables of that call) writes for thresh = t_j: strict > in fp32, a NaN probability is never set.  Both rules
+ *   are monotone in the threshold, so every output pixel has one level = the number of j with mask_j = 1, in 0..k, and
+ *   mask_j = 1 exactly when j < level.
+ *   hist (DEVICE, [2][k + 1] int64, 8-byte aligned): hist[g][l] += the number of pixels with (gt != 0) == g and level l.  The
+ *   call ADDS; the caller zeroes hist once and may pool any number of calls in it.  Then, for every j,
+ *   tp_j = sum over l > j of hist[1][l], fp_j = the same sum over hist[0], fn_j and tn_j the rest of each row.
+ *   Nothing but hist is written; no workspace, no host wait, no allocation; launches on the given stream only.
+ *   UNETDC_EINVAL before any launch: a null probs / gt / hist, k outside 1..1024, a side outside 1..16384, n < 1, some but not
+ *   all of the four tables.  Integer atomics only: the result depends on no order, two runs are bitwise equal. */
+int unetdc_thresh_sweep(const float* probs, int n, int ph, int pw, const uint8_t* gt, int oh, int ow, const int32_t* xofs,
+                        const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int k, int64_t* hist,
+                        unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,11 @@ for both; adds gt_label / gt_iou / gt_covered to the droplet tables and writes g
 thresholding between T and --prob_thresh, then holes of at most N pixels (any size without N) are filled; csrc/clean.hip on the
 device, utils/droplet_clean.py on the CPU.  The cleaned mask is the one every output sees; mask_clean_per_image.csv says
 what was changed per image.
+``--thresh_sweep [K]`` (with ``--gt_dir``) scores the raw thresholded mask against the annotation, pixel by pixel, at the K
+thresholds k / K in one pass per image (csrc/sweep.hip on the device, utils/threshold_sweep.py on the
+CPU) and writes threshold_sweep.csv pooled over all images; ``--sweep_objects T[,T...]`` repeats the droplet stage and the
+matching of ``--gt_dir`` at the listed thresholds on the probabilities already computed and writes
+threshold_sweep_objects.csv.
 """
 import argparse
 from pathlib import Path
@@ -249,12 +254,57 @@ def _density(density, dres, rgb, mask, fpath, name, writers):
         writers[1].append(writers[0].submit(*job))
 
 
+def _cpu_mask(p2, thresh, ow, oh, clean):
+    """CPU path: probabilities [h, w] (numpy fp32) -> the mask every stage sees at one threshold (resize, then the cleaning
+    options of the run)."""
+    mask = resize_mask_like_reference((p2 > np.float32(thresh)).astype(np.uint8), ow, oh)
+    if clean is not None:
+        from utils.droplet_clean import clean_mask
+        weak = None
+        if clean["low"] is not None:
+            weak = resize_mask_like_reference((p2 > np.float32(clean["low"])).astype(np.uint8), ow, oh)
+        mask = clean_mask(mask, weak, clean["holes"])[0]
+    return mask
+
+
+def sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean):
+    """--thresh_sweep for one batch: the batch's probabilities against its annotations at every threshold of the grid, added
+    into the run's histogram (on the device: unetdc_thresh_sweep, nothing waits; on the CPU: sweep_hist_numpy).  Then, for
+    every threshold of --sweep_objects, the droplet stage with the run's own split / clean options and the matching of
+    --gt_dir once more on the same probabilities: the integers of one match_per_image.csv row per image and threshold."""
+    hws = [m[1] for m in meta]
+    if probs.is_cuda:
+        from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
+        from unet_dc_segmentation_amd.evaluate import match_batch, sweep_batch
+        sweep["hist"] = sweep_batch(probs[:, 0], gt["items"], hws, sweep["K"], hist=sweep["hist"])
+        opts = {"shape": True, "return_labels": True} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
+        if clean is not None:
+            opts.update(thresh_low=clean["low"], max_hole_area=clean["holes"])
+        for t in sweep["objects"]:
+            out = mask_and_droplets_batch(probs[:, 0], t, hws, min_area, **opts)
+            res = match_batch([o[4] for o in out], [o[1] for o in out], gt["items"], gt["min_area"], gt["labels"])
+            sweep["object_images"][t].extend(r["columns"]["image"] for r in res)
+        return
+    from utils.droplet_match import label_sums
+    from utils.threshold_sweep import sweep_hist_numpy
+    p = probs[:, 0].numpy()
+    for i, (oh, ow) in enumerate(hws):
+        h = sweep_hist_numpy(p[i], gt["items"][i], (oh, ow), sweep["K"])
+        sweep["hist"] = h if sweep["hist"] is None else sweep["hist"] + h
+        for t in sweep["objects"]:
+            plab = pred_labels_cpu(_cpu_mask(p[i], t, ow, oh, clean), min_area, split_depth)
+            res = match_cpu(plab, label_sums(plab)[0], gt["items"][i], gt["min_area"], gt["labels"])
+            sweep["object_images"][t].append(res["columns"]["image"])
+
+
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None, shape=None, gt=None, clean=None):
+              density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
     on_device = probs.is_cuda
+    if sweep is not None:                                # --thresh_sweep: the raw mask at every threshold, pooled
+        sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean)
     masks512 = None if on_device else (probs[:, 0] > thresh).to(torch.uint8).numpy()
     weak512 = None                                       # --prob_thresh_low on the CPU path: the mask of the low threshold
     if clean is not None and clean["low"] is not None and not on_device:
@@ -374,6 +424,17 @@ def build_parser():
     p.add_argument("--fill_holes", type=int, nargs="?", const=-1, default=0, metavar="N",
                    help="fill the holes of the mask (background not 4-connected to the image border) before anything is "
                         "measured: holes of at most N pixels, of any size without N; writes mask_clean_per_image.csv")
+    p.add_argument("--thresh_sweep", type=int, nargs="?", const=100, metavar="K",
+                   help="with --gt_dir: score the thresholded mask against the annotation, pixel by pixel, at the K thresholds "
+                        "k / K (K in 1..1024, 100 without K) in one pass per image, and write threshold_sweep.csv pooled over all "
+                        "images (tp, fp, fn, tn, precision, recall, dice, iou per threshold).  It describes the raw mask "
+                        "probs > threshold under the script's resize rule: --prob_thresh_low, --fill_holes, --min_area and "
+                        "--gt_min_area do not enter it (a pixel score; with --gt_labels any nonzero label is annotated)")
+    p.add_argument("--sweep_objects", metavar="T[,T...]",
+                   help="with --thresh_sweep: run the droplet stage (with this run's split and cleaning options) and the "
+                        "matching of --gt_dir again at each listed threshold, on the probabilities already computed, and write "
+                        "threshold_sweep_objects.csv: the pooled row of match_per_image.csv per threshold (none may lie below "
+                        "--prob_thresh_low)")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -392,6 +453,32 @@ def clean_options(args):
     return None if low is None and holes == 0 else {"low": low, "holes": holes, "rows": []}
 
 
+def sweep_options(args):
+    """--thresh_sweep / --sweep_objects -> {"K", "hist", "objects", "object_images"}, None without the flag; a bad value or
+    a missing --gt_dir ends the run before any image."""
+    if args.thresh_sweep is None:
+        if args.sweep_objects is not None:
+            raise SystemExit("--sweep_objects needs --thresh_sweep")
+        return None
+    if not args.gt_dir:
+        raise SystemExit("--thresh_sweep scores against annotated masks: it needs --gt_dir")
+    from utils.threshold_sweep import MAX_K
+    if not 1 <= args.thresh_sweep <= MAX_K:
+        raise SystemExit(f"--thresh_sweep K: K must be in 1..{MAX_K}")
+    objects = []
+    if args.sweep_objects is not None:
+        try:
+            objects = [float(v) for v in args.sweep_objects.split(",") if v.strip()]
+        except ValueError:
+            raise SystemExit("--sweep_objects takes thresholds separated by commas, e.g. 0.2,0.3,0.4")
+        low = args.prob_thresh_low
+        for t in objects:
+            if not t == t or (low is not None and t < low):
+                raise SystemExit(f"--sweep_objects: {t} lies below --prob_thresh_low ({low})")
+        objects = list(dict.fromkeys(objects))
+    return {"K": args.thresh_sweep, "hist": None, "objects": objects, "object_images": {t: [] for t in objects}}
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
@@ -403,6 +490,7 @@ def main(argv=None):
     if not args.split_touching:
         split_depth = None
     clean = clean_options(args)
+    sweep = sweep_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -462,7 +550,7 @@ def main(argv=None):
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
@@ -472,7 +560,7 @@ def main(argv=None):
                     gt["items"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:
@@ -485,6 +573,22 @@ def main(argv=None):
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
+    if sweep is not None and sweep["hist"] is not None:
+        from utils.threshold_sweep import summary_line, table_rows
+        hist = sweep["hist"]
+        if torch.is_tensor(hist):                        # the sweep's only copy from the device
+            from unet_dc_segmentation_amd.evaluate import sweep_result
+            hist = sweep_result(hist)
+        pd.DataFrame(table_rows(hist)).to_csv(out_dir / "threshold_sweep.csv", index=False)
+        print(summary_line(hist))
+        if sweep["objects"]:
+            from utils.droplet_match import pooled_row
+            rows = []
+            for t in sweep["objects"]:
+                row = pooled_row(sweep["object_images"][t])
+                row.pop("filename")
+                rows.append({"threshold": t, **row})
+            pd.DataFrame(rows).to_csv(out_dir / "threshold_sweep_objects.csv", index=False)
     summary_df = pd.DataFrame(per_image_rows)
     summary_df.to_csv(out_dir / "summary_per_image.csv", index=False)
     props = [d for d in all_props if not d.empty]

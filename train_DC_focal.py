@@ -52,6 +52,11 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
                    help="skip the evaluation of the best checkpoint on the held-out test split after training")
+    p.add_argument("--calibrate_thresh", type=int, nargs="?", const=100, metavar="K",
+                   help="after the final test evaluation, run the validation split once more with the weights that evaluation "
+                        "used and report the Dice-optimal probability threshold among k / K, k = 0..K-1 (K in 1..1024, 100 "
+                        "without K; csrc/sweep.hip on the HIP device).  This is Dice POOLED OVER ALL PIXELS of the split, not "
+                        "the per-batch mean Dice the epochs print")
     p.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     return p
 
@@ -103,8 +108,10 @@ def make_device_loaders(args, rank, world, device):
 
 
 class History(list):
-    """Per-epoch records of main(); ``.test`` holds the held-out-split results of the final evaluation (None if skipped)."""
+    """Per-epoch records of main(); ``.test`` holds the held-out-split results of the final evaluation (None if skipped),
+    ``.calibration`` the result of --calibrate_thresh (None without the flag)."""
     test = None
+    calibration = None
 
 
 def evaluate_test(model, loader, criterion, device):
@@ -132,8 +139,40 @@ def evaluate_test(model, loader, criterion, device):
                 precision=precision, recall=recall, f1=f1, specificity=specificity, confusion=cm.tolist())
 
 
+def calibrate_threshold(model, loader, K, device):
+    """--calibrate_thresh: the pixel confusion matrix of `probabilities > k / K` against the masks (> 0.5) of every batch of
+    `loader`, for all k at once (identity geometry, nearest rule).  On the HIP device every batch adds
+    into one device histogram (unetdc_thresh_sweep) and the host copies it once; on the CPU utils.threshold_sweep does the
+    same sums.  -> {K, best_dice_threshold, best_dice, average_precision, hist}."""
+    from utils.threshold_sweep import sweep_hist_numpy, sweep_table
+    model.eval()
+    hist = None
+    with torch.no_grad():
+        for batch in loader:
+            images, masks = batch[0].float().to(device), batch[1].float().to(device)
+            probs = model(images)[:, 0].float()
+            gts = (masks[:, 0] > 0.5).to(torch.uint8)
+            hw = tuple(gts.shape[1:])
+            if probs.is_cuda:
+                from unet_dc_segmentation_amd.evaluate import sweep_batch
+                hist = sweep_batch(probs, gts, [hw] * len(probs), K, hist=hist, linear=False)
+            else:
+                for p2, g in zip(probs.numpy(), gts.numpy()):
+                    h = sweep_hist_numpy(p2, g, hw, K, linear=False)
+                    hist = h if hist is None else hist + h
+    if torch.is_tensor(hist):
+        from unet_dc_segmentation_amd.evaluate import sweep_result
+        hist = sweep_result(hist)
+    t = sweep_table(hist)
+    k = t["best_dice_k"]
+    return dict(K=K, best_dice_threshold=float(t["threshold"][k]), best_dice=float(t["dice"][k]),
+                average_precision=t["average_precision"], hist=hist)
+
+
 def main(argv=None, parser=None):
     args = (parser or build_parser()).parse_args(argv)
+    if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
+        raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     rank, local, world = dpmod.init_from_env()
     device = torch.device(args.device if args.device != "cuda" else f"cuda:{local}")
     if args.device_data and device.type != "cuda":
@@ -295,6 +334,12 @@ def main(argv=None, parser=None):
             print(f"Precision: {t['precision']:.4f}, Recall: {t['recall']:.4f}, F1: {t['f1']:.4f}, "
                   f"Specificity: {t['specificity']:.4f}")
             print(f"Confusion matrix [[tn, fp], [fn, tp]]: {t['confusion']}")
+    if args.calibrate_thresh is not None and len(val_ds) > 0:
+        history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device)   # every rank: same weights
+        if rank == 0:
+            c = history.calibration
+            print(f"Threshold calibration on the validation split (K = {c['K']}): pooled Dice {c['best_dice']:.4f} at "
+                  f"threshold {c['best_dice_threshold']:.6g}; average precision {c['average_precision']:.4f}")
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -98,6 +98,7 @@ SIGNATURES = {
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
     "unetdc_mask_clean_workspace": (L, [I, I]),
     "unetdc_mask_clean": (I, [P, P, I, I, I, P, L, P, P, P]),
+    "unetdc_thresh_sweep": (I, [P, I, I, I, P, I, I, P, P, P, P, I, P, P]),
 }
 
 _lib = None

@@ -590,6 +590,13 @@ int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, 
                            (hipStream_t)s);
 }
 
+int unetdc_thresh_sweep(const float* probs, int n, int ph, int pw, const uint8_t* gt, int oh, int ow, const int32_t* xofs,
+                        const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int k, int64_t* hist,
+                        unetdc_stream_t s) {
+  return launch_thresh_sweep(probs, n, ph, pw, gt, oh, ow, xofs, xcoef, yofs, ycoef, k, reinterpret_cast<long long*>(hist),
+                             (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

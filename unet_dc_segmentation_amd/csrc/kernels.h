@@ -273,6 +273,11 @@ long mask_clean_workspace_bytes(int h, int w);
 int launch_mask_clean(const unsigned char* strong, const unsigned char* weak, int h, int w, int max_hole_area, void* workspace,
                       long workspace_bytes, unsigned char* out_mask, int* out_counts, hipStream_t stream);
 
+// sweep.hip: the confusion matrix of the thresholded mask against an annotation at every threshold of a grid (DESIGN.md
+// section 14; include/unetdc_hip.h)
+int launch_thresh_sweep(const float* probs, int n, int ph, int pw, const unsigned char* gt, int oh, int ow, const int* xofs,
+                        const short* xcoef, const int* yofs, const short* ycoef, int k, long long* hist, hipStream_t stream);
+
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).
 constexpr int AUG_HFLIP = 1, AUG_VFLIP = 2, AUG_BC = 4;

@@ -3,6 +3,10 @@ of two device label maps through ``unetdc_label_overlap``, and a whole batch of 
 
 Only the triples (a, b, n) and three integers per annotated droplet cross PCIe; the decisions and the float64 columns are
 ``utils.droplet_match.match_columns`` on the host, the same function the CPU path uses.
+
+``sweep_batch`` / ``sweep_result`` (csrc/sweep.hip): the pixel confusion matrix of the thresholded mask
+against the annotation at every threshold of a grid, added up in one device histogram for as many images as the caller
+likes; ``utils.threshold_sweep.sweep_table`` turns its single copy into the scores.
 """
 from __future__ import annotations
 
@@ -144,3 +148,65 @@ def _gt_labels_again(lib, mask, h, w, min_area, k, s):
               area.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), None, lab.data_ptr(), k, s)
     s_h = sums.cpu().numpy()
     return area.cpu().numpy().astype(np.int64), s_h[0], s_h[1], lab
+
+
+def _gt_run(gts, oh, ow, dev):
+    """Annotations of one size -> ONE contiguous uint8 [n, oh, ow] device tensor (nonzero = annotated)."""
+    if torch.is_tensor(gts):
+        g = gts if gts.dtype == torch.uint8 else (gts != 0).to(torch.uint8)
+    elif all(not torch.is_tensor(g) for g in gts):                 # host arrays: one upload for the run
+        hs = [np.asarray(g) for g in gts]
+        g = torch.from_numpy(np.stack([h if h.dtype == np.uint8 else (h != 0).astype(np.uint8) for h in hs]))
+    else:
+        ts = [g if torch.is_tensor(g) else torch.from_numpy(np.ascontiguousarray(g)) for g in gts]
+        g = torch.stack([(t if t.dtype == torch.uint8 else (t != 0).to(torch.uint8)).to(dev) for t in ts])
+    if tuple(g.shape[1:]) != (oh, ow):
+        raise _lib.UnetdcError(f"an annotation is {tuple(g.shape[1:])}, its image {(oh, ow)}")
+    return g.to(dev).contiguous()
+
+
+def sweep_batch(probs, gts, out_hws, K, hist=None, linear=True):
+    """probs: [B, H, W] fp32 probabilities on the HIP device; gts: B annotations (numpy arrays or tensors of the output sizes,
+    nonzero = annotated; or one [B, oh, ow] tensor); out_hws: B (oh, ow) pairs; K: thresholds k / K, k = 0..K-1.
+    One unetdc_thresh_sweep per run of consecutive images with equal output size is enqueued on the current stream; every
+    call ADDS into the int64 [2, K + 1] device tensor `hist` (a new zeroed one when None), which is returned.  Nothing waits
+    for the device: pool as many batches as you like, then sweep_result(hist) makes the one copy.
+    linear=True resizes as the droplet stage does (droplets.MASK_RESIZE: the reference's 8-bit bilinear through the cached
+    tables of preprocess.py, the identity at equal sizes); linear=False is the nearest rule."""
+    from . import droplets
+    if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
+        raise _lib.UnetdcError("sweep_batch needs a [B, H, W] fp32 tensor on the HIP device")
+    probs = probs.contiguous()
+    B, ph, pw = probs.shape
+    K = int(K)
+    out_hws = [(int(h), int(w)) for h, w in out_hws]
+    if not (len(out_hws) == len(gts) == B):
+        raise _lib.UnetdcError("sweep_batch needs one annotation and one output size per probability map")
+    dev = probs.device
+    if hist is None:
+        hist = torch.zeros(2, K + 1, dtype=torch.int64, device=dev)
+    elif not hist.is_cuda or hist.dtype != torch.int64 or tuple(hist.shape) != (2, K + 1) or not hist.is_contiguous():
+        raise _lib.UnetdcError(f"hist must be a contiguous int64 [2, {K + 1}] tensor on the HIP device")
+    s = torch.cuda.current_stream().cuda_stream
+    i = 0
+    while i < B:
+        j = i + 1
+        while j < B and out_hws[j] == out_hws[i]:
+            j += 1
+        oh, ow = out_hws[i]
+        g = _gt_run(gts[i:j], oh, ow, dev)
+        tables = [None] * 4
+        if linear and droplets.MASK_RESIZE != "nearest" and (ph, pw) != (oh, ow):
+            from .preprocess import _resize_tables
+            xo, xa = _resize_tables(pw, ow, dev, True)
+            yo, ya = _resize_tables(ph, oh, dev, False)
+            tables = [xo.data_ptr(), xa.data_ptr(), yo.data_ptr(), ya.data_ptr()]
+        _lib.call("unetdc_thresh_sweep", probs[i:j].data_ptr(), j - i, ph, pw, g.data_ptr(), oh, ow, *tables, K,
+                  hist.data_ptr(), s)
+        i = j
+    return hist
+
+
+def sweep_result(hist):
+    """The device histogram of sweep_batch -> int64 numpy [2, K + 1]: the sweep's only device-to-host copy."""
+    return hist.cpu().numpy()
