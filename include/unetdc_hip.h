@@ -513,6 +513,30 @@ int unetdc_thresh_sweep(const float* probs, int n, int ph, int pw, const uint8_t
                         const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int k, int64_t* hist,
                         unetdc_stream_t s);
 
+
+/* ---- tiled inference at native resolution (tile.hip; the definition is DESIGN.md section 15, utils/tiling.py) ------------------
+ * A plan is two ascending origin lists yo[ny], xo[nx] (DEVICE int32 arrays; utils/tiling.py:tile_plan builds them): tile number
+ * ty * nx + tx has its corner at (yo[ty], xo[tx]) and t x t pixels; t is a multiple of 16 in 16..4096 (the plan itself asks for
+ * at least 32); at most 1024 tiles per axis; image sides 1..16384.
+ * unetdc_tile_gather_u8_to_chw_f32: src_hwc ([h][w][channels] uint8, channels 1..4) -> tiles ([count][channels][t][t] fp32,
+ *   16-byte aligned) for the tile numbers t0 .. t0 + count - 1: float(v) / 255.0f (one IEEE division, the expression of
+ *   unetdc_resize_linear_u8_to_chw_f32) of the pixel at (yo[ty] + y, xo[tx] + x); a coordinate outside the image folds back by
+ *   reflect-101 with as many reflections as needed (period 2 (side - 1); a side of 1 maps to 0), so that every read lies inside
+ *   src whatever the origin arrays hold.
+ * unetdc_tile_blend_f32: tile_probs ([ny * nx][t][t] fp32) -> out ([h][w] fp32):
+ *     out[y][x] = sum(wy wx p) / sum(wy wx) over the tiles with 0 <= y - yo[ty] < t and 0 <= x - xo[tx] < t, in ascending tile
+ *     number, w(i) = min(i + 1, t - i, max(overlap, 1)) at the tile-local index i (0 <= overlap <= t / 2); both sums in fp32,
+ *     product and sum rounded separately, one IEEE division.  Only those elements of tile_probs are read: never the folded
+ *     part of a tile of an image smaller than t.  Every pixel of out is written; a pixel that no tile covers (origins that are
+ *     not a plan of h x w) gets NaN.
+ * Both: nothing but the output is written; no workspace, no allocation, no host wait, no atomics; launches on the given stream
+ * only; two runs are bitwise equal.  UNETDC_EINVAL before any launch: a null pointer, a side, channel count, tile size, overlap
+ * or tile count outside the limits above, t0 < 0, count < 1 or t0 + count > ny * nx, a misaligned tile buffer. */
+int unetdc_tile_gather_u8_to_chw_f32(const uint8_t* src_hwc, int h, int w, int channels, float* tiles, int t, const int32_t* yo,
+                                     int ny, const int32_t* xo, int nx, int t0, int count, unetdc_stream_t s);
+int unetdc_tile_blend_f32(const float* tile_probs, int t, int overlap, const int32_t* yo, int ny, const int32_t* xo, int nx,
+                          float* out, int h, int w, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

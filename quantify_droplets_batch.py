@@ -33,6 +33,11 @@ thresholds k / K in one pass per image (csrc/sweep.hip on 
 CPU) and writes threshold_sweep.csv pooled over all images; ``--sweep_objects T[,T...]`` repeats the droplet stage and the
 matching of ``--gt_dir`` at the listed thresholds on the probabilities already computed and writes
 threshold_sweep_objects.csv.
+``--tile [T]`` / ``--tile_overlap O`` run the network at the image's NATIVE resolution instead of on the 512 x 512 squash
+(DESIGN.md section 15): the rolling-ball-corrected image is cut into overlapping T x T tiles (512 without T, overlap 64), the tiles
+go through the network ``--batch`` at a time, and their probabilities are blended into one map of the image's size
+(csrc/tile.hip and unet_dc_segmentation_amd/tiling.py on the device, utils/tiling.py on the CPU, one derivation for both);
+every option above then works on that map.  Meant for checkpoints trained at the scale they are applied at.
 """
 import argparse
 from pathlib import Path
@@ -79,6 +84,22 @@ def preprocess(path, background_radius, im=None, keep_rgb=False):
     im = rolling_ball_correction_rgb(im, background_radius)
     im = resize_image(im, IMG_SIZE).astype(np.float32) / 255.0
     return torch.from_numpy(im).permute(2, 0, 1), (oh, ow)
+
+
+def predict_tiled_image(model, im, background_radius, tile, batch, keep_rgb=False):
+    """--tile: decoded image -> (probabilities [1, 1, H, W] at the image's own size, the original image for the density maps or
+    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, `batch` per forward, and the blend."""
+    if DEVICE == "cuda":
+        from unet_dc_segmentation_amd.preprocess import MAX_ELEMENT, _upload, rolling_ball_device
+        from unet_dc_segmentation_amd.tiling import predict_tiled
+        host_ball = int(background_radius) > MAX_ELEMENT     # the element does not fit the kernel's LDS tile: host operator
+        rgb = _upload(im, DEVICE) if keep_rgb or not host_ball else None
+        corrected = (_upload(rolling_ball_correction_rgb(im, int(background_radius)), DEVICE) if host_ball
+                     else rolling_ball_device(rgb, background_radius))
+        return predict_tiled(model, corrected, tile["T"], tile["O"], batch)[None, None], rgb
+    from utils.tiling import predict_tiled_cpu
+    p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, background_radius), tile["T"], tile["O"], batch)
+    return torch.from_numpy(p)[None, None], (im if keep_rgb else None)
 
 
 def _droplet_table(area, cen_row, cen_col, px_per_um):
@@ -302,6 +323,15 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
               density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None):
     batch = torch.stack(tensors).to(DEVICE)
     probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
+    finish_batch(probs, meta, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers, density,
+                 split_depth, shape, gt, clean, sweep)
+
+
+def finish_batch(probs, meta, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
+                 density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None):
+    """Everything behind the forward: probs [B, 1, ph, pw] (on the device or not) -> masks of the sizes in meta, droplet tables,
+    the optional stages and the per-image files.  run_batch feeds it the network-size maps, --tile one native-size map per image
+    (ph, pw equal to the image's size: every resize rule is then the identity)."""
     on_device = probs.is_cuda
     if sweep is not None:                                # --thresh_sweep: the raw mask at every threshold, pooled
         sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean)
@@ -330,7 +360,7 @@ def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_
         if gt is not None:                               # the batch's annotations against its label maps: one more host wait
             from unet_dc_segmentation_amd.evaluate import match_batch
             mres = match_batch([o[4] for o in dev_out], [o[1] for o in dev_out], gt["items"], gt["min_area"], gt["labels"])
-    for i in range(len(tensors)):
+    for i in range(len(meta)):
         fpath, (oh, ow) = meta[i]
         name = Path(fpath).stem
         labels = None
@@ -435,6 +465,13 @@ def build_parser():
                         "matching of --gt_dir again at each listed threshold, on the probabilities already computed, and write "
                         "threshold_sweep_objects.csv: the pooled row of match_per_image.csv per threshold (none may lie below "
                         "--prob_thresh_low)")
+    p.add_argument("--tile", type=int, nargs="?", const=512, metavar="T",
+                   help="run the network at the image's native resolution: cut the background-corrected image into overlapping "
+                        "T x T tiles (T a multiple of 16 in 32..4096, 512 without T), forward them --batch at a time and blend "
+                        "their probabilities into one map of the image's size; for checkpoints trained at that scale")
+    p.add_argument("--tile_overlap", type=int, metavar="O",
+                   help="with --tile: least overlap of neighbouring tiles in pixels, also the width of the blend ramp "
+                        "(0..T/2, default 64)")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -479,6 +516,22 @@ def sweep_options(args):
     return {"K": args.thresh_sweep, "hist": None, "objects": objects, "object_images": {t: [] for t in objects}}
 
 
+def tile_options(args):
+    """--tile / --tile_overlap -> {"T", "O"}, None without --tile; a bad value ends the run before any image."""
+    if args.tile is None:
+        if args.tile_overlap is not None:
+            raise SystemExit("--tile_overlap needs --tile")
+        return None
+    from utils.tiling import check_tile
+    try:
+        T, O = check_tile(args.tile, 64 if args.tile_overlap is None else args.tile_overlap)
+    except ValueError as e:
+        raise SystemExit(f"--tile / --tile_overlap: {e}")
+    if args.batch < 1:
+        raise SystemExit("--tile: --batch is the number of tiles per forward, at least 1")
+    return {"T": T, "O": O}
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
@@ -491,6 +544,7 @@ def main(argv=None):
         split_depth = None
     clean = clean_options(args)
     sweep = sweep_options(args)
+    tile = tile_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -539,6 +593,19 @@ def main(argv=None):
             if shape is not None:                        # the ORIGINAL image as grey, before the rolling ball
                 from utils.density import rgb_to_gray
                 shape["grays"].append(rgb_to_gray(im))
+            if tile is not None:                         # native size: one map per image, the stages on a batch of one
+                if gt is not None:
+                    gt["items"].append(gt_fut.result())
+                probs, rgb = predict_tiled_image(model, im, args.background_radius, tile, args.batch, density is not None)
+                if density is not None:
+                    density["rgbs"] = [rgb]
+                finish_batch(probs, [(str(img), im.shape[:2])], mask_dir, overlay_dir, args.prob_thresh, args.min_area,
+                             args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
+                if shape is not None:
+                    shape["grays"] = []
+                if gt is not None:
+                    gt["items"] = []
+                continue
             if density is None:
                 t, osize = preprocess(img, args.background_radius, im)
             else:

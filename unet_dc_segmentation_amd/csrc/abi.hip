@@ -597,6 +597,16 @@ int unetdc_thresh_sweep(const float* probs, int n, int ph, int pw, const uint8_t
                              (hipStream_t)s);
 }
 
+int unetdc_tile_gather_u8_to_chw_f32(const uint8_t* src_hwc, int h, int w, int channels, float* tiles, int t, const int32_t* yo,
+                                     int ny, const int32_t* xo, int nx, int t0, int count, unetdc_stream_t s) {
+  return launch_tile_gather(src_hwc, h, w, channels, tiles, t, yo, ny, xo, nx, t0, count, (hipStream_t)s);
+}
+
+int unetdc_tile_blend_f32(const float* tile_probs, int t, int overlap, const int32_t* yo, int ny, const int32_t* xo, int nx,
+                          float* out, int h, int w, unetdc_stream_t s) {
+  return launch_tile_blend(tile_probs, t, overlap, yo, ny, xo, nx, out, h, w, (hipStream_t)s);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

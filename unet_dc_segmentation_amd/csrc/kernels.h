@@ -278,6 +278,13 @@ int launch_mask_clean(const unsigned char* strong, const unsigned char* weak, in
 int launch_thresh_sweep(const float* probs, int n, int ph, int pw, const unsigned char* gt, int oh, int ow, const int* xofs,
                         const short* xcoef, const int* yofs, const short* ycoef, int k, long long* hist, hipStream_t stream);
 
+// tile.hip: overlapping network-size tiles of an image and the blend of their probabilities (DESIGN.md section 15;
+// include/unetdc_hip.h)
+int launch_tile_gather(const unsigned char* src, int h, int w, int cn, float* tiles, int t, const int* yo, int ny, const int* xo,
+                       int nx, int t0, int count, hipStream_t stream);
+int launch_tile_blend(const float* tiles, int t, int overlap, const int* yo, int ny, const int* xo, int nx, float* out, int h,
+                      int w, hipStream_t stream);
+
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).
 constexpr int AUG_HFLIP = 1, AUG_VFLIP = 2, AUG_BC = 4;
