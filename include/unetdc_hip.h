@@ -357,6 +357,38 @@ int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int
                           const unetdc_augment_params* params, int n, const float* fields, int nfields, float* out_img,
                           float* out_mask, unetdc_stream_t s);
 
+/* ---- training at native resolution: random crops of images cached at their own size (crop.hip) ----
+ * unetdc_crop_gather: out_img[i] ([channels][S][S] float32) and out_mask[i] ([1][S][S] float32) for n samples.  Sample i reads
+ *   the HWC uint8 image of params[i].h x params[i].w pixels at images_u8 + params[i].img_off and the uint8 mask of the same
+ *   size at masks_u8 + params[i].mask_off (two flat DEVICE buffers of images_bytes / masks_bytes bytes that hold every cached
+ *   image back to back).  The window is win[c][y][x] = float(img[fold(y0 + y, h)][fold(x0 + x, w)][c]) / 255.0f (one IEEE
+ *   division; fold: the reflect-101 rule of unetdc_tile_gather_u8_to_chw_f32, which only an image smaller than S along an
+ *   axis ever needs) and the mask window the mask bytes at the same pixels; the output is what unetdc_augment_gather makes of
+ *   that S x S window: hflip, vflip, np.rot90(k), clip(alpha * x + beta_max, 0, 1) (two float32 roundings, no FMA) and, when
+ *   params[i].field >= 0, the elastic warp with fields[field] ([nfields][2][S][S] float32 of unetdc_elastic_fields at S x S),
+ *   reflected at the WINDOW's border.  utils/crops.py:crop_gather_numpy is the same rule on the host, bit-equal without
+ *   elastic.  params: HOST array of n records, passed to the kernel by value: nothing but the two outputs is written, no
+ *   workspace, no allocation, no host wait, no atomics; launches on the given stream only.
+ *   UNETDC_EINVAL before any launch: a null pointer (fields may be null when no record has a field), S not a multiple of 16
+ *   in 16..1024, channels outside 1..4, a side outside 1..16384, y0 / x0 outside 0..max(side - S, 0), img_off + h * w *
+ *   channels > images_bytes or mask_off + h * w > masks_bytes (or a negative offset), k outside 0..3, unknown flags, a field
+ *   slot outside [-1, nfields).  Every coordinate is folded, so every read of an accepted record lies inside its image. */
+typedef struct unetdc_crop_params {
+  int64_t img_off;      /* byte offset of the image in images_u8 */
+  int64_t mask_off;     /* byte offset of the mask in masks_u8 */
+  int32_t h, w;         /* the image's own size */
+  int32_t y0, x0;       /* window origin */
+  int32_t flags;        /* UNETDC_AUG_* bits */
+  int32_t k;            /* 90-degree rotations, 0..3 */
+  int32_t field;        /* field slot, -1 = no elastic */
+  float alpha;          /* contrast factor, float32(alpha) */
+  float beta_max;       /* float32(beta * max of the whole cached image / 255), the product formed in double */
+  int32_t reserved;     /* pads the record to 56 bytes */
+} unetdc_crop_params;
+int unetdc_crop_gather(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes, int channels,
+                       int S, const unetdc_crop_params* records, int n, const float* fields, int nfields, float* out_img,
+                       float* out_mask, unetdc_stream_t s);
+
 
 /* ---- radial and spatial droplet density maps (the reference's quantify_pipline.py:44-142 restated; density.hip) ---------
  * unetdc_density_maps: for one image of h x w pixels (both sides >= UNETDC_DENSITY_MIN_SIDE):

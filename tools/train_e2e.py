@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """Training throughput of train_DC_focal.py on N synthetic 1040 x 1388 PNG pairs (bench.synthetic_micrograph images, masks by
-threshold), three arms, each in a fresh child process, bf16, batch 8:
+threshold), three arms (four with --crop), each in a fresh child process, bf16, batch 8:
     synthetic    --synthetic --synthetic_len N        (generated tiles: the loader is not the limit)
     device_data  --device_data                        (cache on the device, augmentation kernels per batch)
     cpu_loader   the host loader (SegmentationDataset + TrainAugment, --workers 4), capped with --steps
+    crop         --device_data --crop S               (with --crop[=S]: images cached at native size, S x S random windows cut
+                                                       and augmented per batch; S = 512 has the step shapes of device_data)
 Prints the per-epoch training img/s of every arm and one JSON line with the mean from epoch 2 on.
 
-    python tools/train_e2e.py [N] [--epochs E] [--cpu_steps S] [--only ARM]"""
+    python tools/train_e2e.py [N] [--epochs E] [--cpu_steps S] [--crop[=S]] [--only ARM [--only ARM ...]]
+
+--only may be repeated, also with one arm twice (two runs of one arm in one job give the run-to-run spread): the second run
+of an arm is reported as ARM_run2."""
 import argparse
 import json
 import os
@@ -19,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 ARMS = ("synthetic", "device_data", "cpu_loader")
+CROP_ARM = "crop"
 
 
 def write_pairs(d, n):
@@ -38,13 +44,15 @@ def write_pairs(d, n):
     return ind, md
 
 
-def run_arm(arm, n, ind, md, epochs, cpu_steps, d):
+def run_arm(arm, n, ind, md, epochs, cpu_steps, d, crop=512):
     common = ["--dtype", "bf16", "--batch", "8", "--epochs", str(epochs), "--patience", str(epochs + 1), "--no_test_eval",
               "--ckpt_path", os.path.join(d, f"{arm}.pth")]
     if arm == "synthetic":
         extra = ["--synthetic", "--synthetic_len", str(n)]
     elif arm == "device_data":
         extra = ["--image_dir", ind, "--mask_dir", md, "--device_data"]
+    elif arm == CROP_ARM:
+        extra = ["--image_dir", ind, "--mask_dir", md, "--device_data", "--crop", str(crop)]
     else:
         extra = ["--image_dir", ind, "--mask_dir", md, "--steps", str(cpu_steps), "--workers", "4"]
     cmd = [sys.executable, os.path.join(ROOT, "train_DC_focal.py"), *common, *extra]
@@ -61,15 +69,23 @@ def main():
     ap.add_argument("n", type=int, nargs="?", default=400)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--cpu_steps", type=int, default=3)
-    ap.add_argument("--only", choices=ARMS)
+    ap.add_argument("--crop", type=int, nargs="?", const=512, default=None, metavar="S",
+                    help="also run the crop arm (train_DC_focal.py --device_data --crop S; 512 without S)")
+    ap.add_argument("--only", choices=ARMS + (CROP_ARM,), action="append")
     a = ap.parse_args()
     res = {"n_pairs": a.n, "epochs": a.epochs, "batch": 8, "dtype": "bf16", "cpu_loader_steps_per_epoch": a.cpu_steps}
+    crop = 512 if a.crop is None else a.crop
+    arms = a.only or (ARMS + ((CROP_ARM,) if a.crop is not None else ()))
+    if CROP_ARM in arms:
+        res["crop"] = crop
     with tempfile.TemporaryDirectory() as d:
         ind, md = write_pairs(d, a.n)
-        for arm in ([a.only] if a.only else ARMS):
-            ips = run_arm(arm, a.n, ind, md, a.epochs, a.cpu_steps, d)
-            res[f"{arm}_img_per_s_by_epoch"] = ips
-            res[f"{arm}_img_per_s"] = sum(ips[1:]) / max(1, len(ips[1:]))
+        for j, arm in enumerate(arms):
+            ips = run_arm(arm, a.n, ind, md, a.epochs, a.cpu_steps, d, crop)
+            runs = list(arms[:j]).count(arm)
+            key = arm if not runs else f"{arm}_run{runs + 1}"
+            res[f"{key}_img_per_s_by_epoch"] = ips
+            res[f"{key}_img_per_s"] = sum(ips[1:]) / max(1, len(ips[1:]))
     if "synthetic_img_per_s" in res and "device_data_img_per_s" in res:
         res["device_data_over_synthetic"] = res["device_data_img_per_s"] / res["synthetic_img_per_s"]
     print(json.dumps(res))

@@ -9,7 +9,8 @@ New: ``--synthetic`` (seeded droplet tiles, no dataset needed), ``--dtype`` (f32
 the HIP path), ``--steps`` (cap the steps per epoch), and data-parallel training when launched with
 ``python -m torch.distributed.run --nproc-per-node N train_DC_focal.py ...`` (RCCL all-reduce
 overlapped with backward, unet_dc_segmentation_amd/dp.py), and ``--device_data`` (images preprocessed once into a cache on the
-device, each batch augmented there: unet_dc_segmentation_amd/device_data.py).  The numbers of the reference's test section (:365-402, :452-467:
+device, each batch augmented there: unet_dc_segmentation_amd/device_data.py; with ``--crop S`` the cache keeps the images at
+their own size and every batch is S x S random windows).  The numbers of the reference's test section (:365-402, :452-467:
 best checkpoint reloaded, test loss / Dice / pixel accuracy, precision / recall / F1 / specificity / confusion matrix) are
 computed and printed; its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
 """
@@ -48,6 +49,13 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--device_data", action="store_true",
                    help="decode and preprocess every image once into a cache on the HIP device and augment each batch there "
                         "(csrc/augment.hip; its own counter-based random stream); --workers is ignored")
+    p.add_argument("--crop", type=int, nargs="?", const=512, default=None, metavar="S",
+                   help="with --device_data: train at native resolution on random S x S windows of images cached at their own "
+                        "size, cut and augmented on the HIP device (csrc/crop.hip, DESIGN.md section 16); validation and test "
+                        "run on the windows of utils.crops.eval_plan.  S: a multiple of 16 in 32..1024, 512 without S; "
+                        "--img_size is not used")
+    p.add_argument("--crops_per_image", type=int, default=1, metavar="R",
+                   help="with --crop: R random windows of every training image per epoch (default 1)")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -101,10 +109,39 @@ def make_device_loaders(args, rank, world, device):
     if world > 1:
         per_rank = len(ids) // world
         ids = list(range(rank, per_rank * world, world))
+    if args.crop is not None:
+        from unet_dc_segmentation_amd.device_data import DeviceCropEvalLoader, DeviceCropTrainLoader, DeviceNativeCache
+        native = lambda names, masks: DeviceNativeCache(args.image_dir, args.mask_dir, names, device=device,  # noqa: E731
+                                                        mask_names=masks)
+        train = DeviceCropTrainLoader(native([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.crop,
+                                      args.seed, ids, args.crops_per_image)
+        return (train, DeviceCropEvalLoader(native(*va), args.batch, args.crop),
+                DeviceCropEvalLoader(native(*te), args.batch, args.crop))
     cache = lambda names, masks: DeviceImageCache(args.image_dir, args.mask_dir, names, args.img_size,  # noqa: E731
                                                   device=device, mask_names=masks)
     train = DeviceTrainLoader(cache([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.seed, ids)
     return train, DeviceEvalLoader(cache(*va), args.batch), DeviceEvalLoader(cache(*te), args.batch)
+
+
+def check_crop_flags(args):
+    """--crop / --crops_per_image: every refusal is raised here, before any file is read."""
+    if args.crop is None:
+        if args.crops_per_image != 1:
+            raise SystemExit("--crops_per_image needs --crop")
+        return
+    from utils.crops import MAX_CROP, MIN_CROP
+    if args.crop % 16 or not MIN_CROP <= args.crop <= MAX_CROP:
+        raise SystemExit(f"--crop S: S must be a multiple of 16 in {MIN_CROP}..{MAX_CROP}, not {args.crop}")
+    if args.crops_per_image < 1:
+        raise SystemExit(f"--crops_per_image R: R must be at least 1, not {args.crops_per_image}")
+    if args.synthetic:
+        raise SystemExit("--crop cuts windows out of the files of --image_dir / --mask_dir and cannot run with --synthetic")
+    if not args.device_data:
+        raise SystemExit("--crop needs --device_data: the windows are cut from a cache on the HIP device")
+    if torch.device(args.device).type != "cuda":
+        raise SystemExit(f"--crop cuts and augments its windows on the HIP device and cannot run on --device {args.device}")
+    if args.in_channels != 3:
+        raise SystemExit(f"--crop caches RGB images and cannot run with --in_channels {args.in_channels}")
 
 
 class History(list):
@@ -173,6 +210,7 @@ def main(argv=None, parser=None):
     args = (parser or build_parser()).parse_args(argv)
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
+    check_crop_flags(args)
     rank, local, world = dpmod.init_from_env()
     device = torch.device(args.device if args.device != "cuda" else f"cuda:{local}")
     if args.device_data and device.type != "cuda":
@@ -219,6 +257,9 @@ def main(argv=None, parser=None):
                                   pin_memory=pin, persistent_workers=keep)
         val_loader = DataLoader(val_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers, pin_memory=pin,
                                 persistent_workers=keep)
+    if rank == 0 and args.crop is not None:
+        print(f"--crop {args.crop}: {train_loader.samples} random {args.crop} x {args.crop} windows/rank and epoch at native "
+              f"resolution, {len(val_loader.windows)} validation windows; --img_size {args.img_size} is not used")
     if rank == 0:
         print(f"Training set: {len(train_ds)} images/rank, validation set: {len(val_ds)} images, "
               f"{world} rank(s), device {device}, compute {args.dtype}")

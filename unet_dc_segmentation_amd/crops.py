@@ -1,0 +1,66 @@
+"""Random crops at native resolution on the HIP device (csrc/crop.hip): S x S windows of images cached
+at their own size as HWC uint8, cut, scaled to [0, 1] and augmented by one kernel per batch.  The rule and its numpy path are
+``utils/crops.py``; the records reach the kernel BY VALUE in the launch arguments, so nothing here waits on the device.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+from .augment import BC, HFLIP, VFLIP
+
+# unetdc_crop_params: int64 img_off, mask_off; int32 h, w, y0, x0, flags, k, field; float32 alpha, beta_max; int32 reserved
+CROP_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("y0", "<i4"), ("x0", "<i4"),
+                       ("flags", "<i4"), ("k", "<i4"), ("field", "<i4"), ("alpha", "<f4"), ("beta_max", "<f4"),
+                       ("reserved", "<i4")])
+assert CROP_DTYPE.itemsize == 56
+
+IDENTITY = dict(hflip=False, vflip=False, k=0, bc=False, alpha=1.0, beta=0.0, elastic=False, field_seed=0)
+
+
+def pack_crops(params, img_off, mask_off, sizes, origins, img_max):
+    """[augment.draw_params dicts] + per-sample byte offsets, (h, w), (y0, x0) and whole-image maxima -> (unetdc_crop_params
+    records, field seeds): the samples that draw elastic get field slots 0, 1, ... in batch order."""
+    rec = np.zeros(len(params), dtype=CROP_DTYPE)
+    seeds = []
+    for i, p in enumerate(params):
+        r = rec[i]
+        r["img_off"], r["mask_off"] = img_off[i], mask_off[i]
+        r["h"], r["w"] = sizes[i]
+        r["y0"], r["x0"] = origins[i]
+        r["flags"] = (HFLIP if p["hflip"] else 0) | (VFLIP if p["vflip"] else 0) | (BC if p["bc"] else 0)
+        r["k"] = p["k"]
+        r["alpha"] = np.float32(p["alpha"])
+        r["beta_max"] = np.float32(p["beta"] * float(img_max[i]))         # formed in double, like beta * float(img.max())
+        r["field"] = len(seeds) if p["elastic"] else -1
+        if p["elastic"]:
+            seeds.append(p["field_seed"])
+    return rec, np.asarray(seeds, dtype=np.uint32)
+
+
+def crop_gather(images_u8, masks_u8, channels, S, rec, fields=None, out_img=None, out_mask=None):
+    """images_u8 / masks_u8: flat uint8 device tensors holding every cached image (HWC) / mask back to back; rec: CROP_DTYPE
+    records (host) -> (images [N, C, S, S], masks [N, 1, S, S]) float32 on the device."""
+    for t, what in ((images_u8, "images_u8"), (masks_u8, "masks_u8")):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
+            raise _lib.UnetdcError(f"crop_gather: {what} must be a flat contiguous uint8 tensor on the HIP device")
+    rec = np.ascontiguousarray(rec, dtype=CROP_DTYPE)
+    n, c, S = len(rec), int(channels), int(S)
+    dev = images_u8.device
+    if out_img is None:
+        out_img = torch.empty(n, c, S, S, dtype=torch.float32, device=dev)
+    if out_mask is None:
+        out_mask = torch.empty(n, 1, S, S, dtype=torch.float32, device=dev)
+    if tuple(out_img.shape) != (n, c, S, S) or tuple(out_mask.shape) != (n, 1, S, S) or out_img.dtype != torch.float32 or \
+            out_mask.dtype != torch.float32 or not (out_img.is_contiguous() and out_mask.is_contiguous()):
+        raise _lib.UnetdcError("crop_gather: outputs must be contiguous float32 [N, C, S, S] and [N, 1, S, S]")
+    nfields = 0
+    if fields is not None:
+        if tuple(fields.shape[1:]) != (2, S, S) or fields.dtype != torch.float32 or not fields.is_contiguous():
+            raise _lib.UnetdcError("crop_gather: fields must be [n, 2, S, S] float32")
+        nfields = fields.shape[0]
+    _lib.call("unetdc_crop_gather", images_u8.data_ptr(), images_u8.numel(), masks_u8.data_ptr(), masks_u8.numel(), c, S,
+              rec.ctypes.data, n, fields.data_ptr() if fields is not None else None, nfields, out_img.data_ptr(),
+              out_mask.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return out_img, out_mask

@@ -642,6 +642,20 @@ int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int
                                fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
+static_assert(sizeof(unetdc_crop_params) == 56 && sizeof(unetdc_crop_params) == sizeof(unetdc::CropRecord) &&
+                  offsetof(unetdc_crop_params, mask_off) == offsetof(unetdc::CropRecord, mask_off) &&
+                  offsetof(unetdc_crop_params, y0) == offsetof(unetdc::CropRecord, y0) &&
+                  offsetof(unetdc_crop_params, field) == offsetof(unetdc::CropRecord, field) &&
+                  offsetof(unetdc_crop_params, beta_max) == offsetof(unetdc::CropRecord, beta_max),
+              "unetdc_crop_params and CropRecord must share one layout");
+
+int unetdc_crop_gather(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes, int channels,
+                       int S, const unetdc_crop_params* records, int n, const float* fields, int nfields, float* out_img,
+                       float* out_mask, unetdc_stream_t s) {
+  return launch_crop_gather(images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
+                            reinterpret_cast<const CropRecord*>(records), n, fields, nfields, out_img, out_mask, (hipStream_t)s);
+}
+
 int64_t unetdc_density_workspace(int h, int w) { return density_workspace_bytes(h, w); }
 
 static_assert(sizeof(unetdc_density_stats) == 1088 && offsetof(unetdc_density_stats, max_ring_distance) == 40 &&

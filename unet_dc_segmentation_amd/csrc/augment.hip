@@ -20,6 +20,7 @@
 // beta * max formed in double on the host), so without elastic the output is bit-exact.  Elastic taps take their integer
 // part and fraction from the displacement alone (floor(d), d - floor(d): exact in float32), not from y + d, which would drop
 // bits of the fraction near y = 512.
+#include "gather_index.h"
 #include "kernels.h"
 
 namespace unetdc {
@@ -162,33 +163,7 @@ __global__ __launch_bounds__(256) void elastic_cols_kernel(int slot0, int H, int
     if (y0 + i < H) out[(long)(y0 + i) * W] = alpha * acc[i];
 }
 
-// scipy.ndimage mode "reflect" (half-sample symmetric, period 2n) applied to an integer tap index
-__device__ inline int aug_reflect(int i, int n) {
-  const int p = 2 * n;
-  int m = i % p;
-  m = m < 0 ? m + p : m;
-  return m < n ? m : p - 1 - m;
-}
-
-// (y, x) in the flipped + rotated image -> (sy, sx) in the source image (H x W; H == W whenever k is odd)
-__device__ inline void aug_source(int y, int x, int H, int W, int flags, int k, int& sy, int& sx) {
-  int fy = y, fx = x;
-  if (k == 1) { fy = x; fx = W - 1 - y; }
-  else if (k == 2) { fy = H - 1 - y; fx = W - 1 - x; }
-  else if (k == 3) { fy = H - 1 - x; fx = y; }
-  sy = (flags & AUG_VFLIP) ? H - 1 - fy : fy;
-  sx = (flags & AUG_HFLIP) ? W - 1 - fx : fx;
-}
-
-__device__ inline float aug_bc(float v, const AugRecord& p) {
-  if (!(p.flags & AUG_BC)) return v;
-  // two roundings, as numpy's float32 steps.  __fmul_rn / __fadd_rn are plain operators in HIP, which the backend fuses into
-  // one FMA under -ffp-contract=fast (1-ulp differences from numpy); the empty asm makes the product opaque to that fusion
-  float m = __fmul_rn(p.alpha, v);
-  asm volatile("" : "+v"(m));
-  const float t = __fadd_rn(m, p.beta_max);
-  return fminf(fmaxf(t, 0.0f), 1.0f);
-}
+// aug_reflect, aug_source and aug_bc: gather_index.h (shared with crop.hip)
 
 // grid (ceil(W / 16), ceil(H / 16), n), block 16 x 16: thread = output pixel (y, x) of sample n0 + blockIdx.z, every channel
 // plus the mask.  out_img [N][C][H][W] fp32, out_mask [N][1][H][W] fp32.

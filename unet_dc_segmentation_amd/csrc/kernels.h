@@ -302,6 +302,18 @@ int launch_augment_gather(const float* cache_img, const unsigned char* cache_mas
                           const AugRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
                           hipStream_t stream);
 
+// crop.hip: random S x S windows of images cached at their own size, cut, scaled to [0, 1] and augmented in one pass (DESIGN.md
+// section 16).  CropRecord is the layout of the public unetdc_crop_params (abi.hip asserts the two agree).
+struct CropRecord {
+  long long img_off, mask_off;
+  int h, w, y0, x0, flags, k, field;
+  float alpha, beta_max;
+  int reserved;
+};
+int launch_crop_gather(const unsigned char* images, long images_bytes, const unsigned char* masks, long masks_bytes, int c, int s,
+                       const CropRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
+                       hipStream_t stream);
+
 // preprocess.hip: rolling-ball correction + bilinear resize to the network input
 long rolling_ball_workspace_bytes(int h, int w, int cn);
 int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int w, int cn, int k, void* workspace,

@@ -14,6 +14,7 @@
 //            nothing depends on an order of arrival.
 // Both are memory-bound: the gather writes 4 * C * T * T bytes per tile against C * T * T bytes read, the blend reads 4 bytes per
 // covering tile and pixel and writes 4.
+#include "gather_index.h"
 #include "kernels.h"
 
 namespace unetdc {
@@ -24,15 +25,7 @@ constexpr int TILE_MIN_T = 16, TILE_MAX_T = 4096;   // the kernels' own limits; 
 constexpr int TILE_MAX_SIDE = 16384;
 constexpr int TILE_MAX_PER_AXIS = 1024;             // tiles per axis: tile numbers and tile offsets stay far below 2^31 / 2^63
 
-// reflect-101 of any int coordinate into 0..dim-1 (period 2 (dim - 1), dim == 1 -> 0)
-__device__ __forceinline__ int tile_fold(int i, int dim) {
-  if ((unsigned)i < (unsigned)dim) return i;
-  if (dim == 1) return 0;
-  const int p = 2 * (dim - 1);
-  int m = i % p;
-  m = m < 0 ? m + p : m;
-  return m < dim ? m : p - m;
-}
+// tile_fold (reflect-101 of any int coordinate into 0..dim-1): gather_index.h
 
 __global__ __launch_bounds__(TILE_THREADS) void tile_gather_kernel(const unsigned char* __restrict__ src, int H, int W, int cn,
                                                                    float* __restrict__ dst, int T, const int* __restrict__ yo,

@@ -6,6 +6,9 @@ resize and augmentation for every sample of every epoch on the host, which holds
 Batches have the layout of a default-collated ``SegmentationDataset``: ``(images [B, C, S, S] float32, masks [B, 1, S, S]
 float32, [orig_h tensor, orig_w tensor], [file names])``, already on the device.  The training augmentation draws a
 counter-based random stream (``augment.draw_params``, keyed by ``(seed, epoch, index)``), not TrainAugment's.
+
+``DeviceNativeCache`` / ``DeviceCropTrainLoader`` / ``DeviceCropEvalLoader`` (``--crop``) keep the images
+at their own size instead and cut S x S windows per batch (csrc/crop.hip): training at native resolution.
 """
 from __future__ import annotations
 
@@ -133,3 +136,179 @@ class DeviceTrainLoader:
         perm = np.random.default_rng([self.seed, epoch]).permutation(len(self.dataset))
         for b0 in range(0, len(perm), self.batch_size):
             yield self.batch(epoch, perm[b0:b0 + self.batch_size])
+
+
+# ---- training at native resolution: images cached at their own size, random crops cut on the device ----
+def _decode_native(image_path, mask_path):
+    """(uint8 RGB image [h, w, 3], uint8 {0, 1} mask [h, w] at the image's own size: grey > 0, not resized)."""
+    img = np.array(Image.open(image_path).convert("RGB"))
+    mask = (np.array(Image.open(mask_path).convert("L")) > 0).astype(np.uint8)
+    if mask.shape != img.shape[:2]:
+        raise ValueError(f"{mask_path}: the mask is {mask.shape[0]} x {mask.shape[1]}, its image {img.shape[0]} x {img.shape[1]}")
+    return img, mask
+
+
+class DeviceNativeCache:
+    """Rolling-ball-corrected images at their OWN size, HWC uint8, back to back in one flat device buffer (``images``), and
+    their {0, 1} masks in another (``masks``): 4 bytes per pixel against the 13 of a float32 cache.  On the host: per-image
+    byte offsets (``img_off``, ``mask_off``), ``sizes`` [(h, w)] and ``img_max`` (float32(max) / float32(255) of the corrected
+    image as a double: the maximum of the brightness / contrast step).  Images may differ in size.  Decoding runs on the thread
+    pool of DeviceImageCache; the rolling ball on the device (above radius 128 the host operator, as preprocess_device).
+    Every file is opened twice: once for its header alone, so that the memory check comes before any allocation or decode,
+    and once to decode it (a second pass over the directory, which a network file system will notice)."""
+    channels = 3
+
+    def __init__(self, image_dir, mask_dir, names, radius=50, device="cuda", mask_names=None, workers=None):
+        from .preprocess import MAX_ELEMENT, _upload, rolling_ball_device
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("DeviceNativeCache keeps the images on the HIP device: device must be a cuda device")
+        self.names = list(names)
+        mask_names = self.names if mask_names is None else list(mask_names)
+        if len(mask_names) != len(self.names):
+            raise ValueError("DeviceNativeCache: one mask per image")
+        n, self.device = len(self.names), device
+        self.sizes = []
+        for name in self.names:                                   # (the header only: PIL decodes nothing here)
+            with Image.open(os.path.join(image_dir, name)) as im:
+                self.sizes.append((int(im.size[1]), int(im.size[0])))
+        pixels = [h * w for h, w in self.sizes]
+        self.mask_off = [int(v) for v in np.concatenate([[0], np.cumsum(pixels, dtype=np.int64)])[:n]]
+        self.img_off = [self.channels * v for v in self.mask_off]
+        need = (self.channels + 1) * sum(pixels)
+        free, total = torch.cuda.mem_get_info(device)
+        if need > free:
+            raise MemoryError(f"DeviceNativeCache: {n} images at their own size need {need / 2**30:.2f} GiB on {device}, "
+                              f"{free / 2**30:.2f} GiB of {total / 2**30:.2f} GiB are free; train without --crop or on "
+                              f"fewer images")
+        self.images = torch.empty(self.channels * sum(pixels), dtype=torch.uint8, device=device)
+        self.masks = torch.empty(sum(pixels), dtype=torch.uint8, device=device)
+        self.img_max = np.zeros(n)
+        workers = workers or min(8, os.cpu_count() or 1)
+        window = 4 * workers
+        with ThreadPoolExecutor(max_workers=workers) as ex:
+            for w0 in range(0, n, window):
+                jobs = [ex.submit(_decode_native, os.path.join(image_dir, self.names[i]), os.path.join(mask_dir, mask_names[i]))
+                        for i in range(w0, min(n, w0 + window))]
+                for i, job in enumerate(jobs, start=w0):
+                    img, mask = job.result()
+                    if img.shape[:2] != self.sizes[i]:
+                        raise ValueError(f"{self.names[i]}: decoded to {img.shape[:2]}, its header says {self.sizes[i]}")
+                    if int(radius) > MAX_ELEMENT:
+                        from utils.data_loader import rolling_ball_correction_rgb
+                        rgb = _upload(rolling_ball_correction_rgb(img, int(radius)), device)
+                    else:
+                        rgb = rolling_ball_device(_upload(img, device), radius)
+                    self.image(i).copy_(rgb)
+                    self.mask(i).copy_(torch.from_numpy(mask))
+                    self.img_max[i] = float(np.float32(int(rgb.max())) / np.float32(255.0))       # (once, at build)
+        self.orig_sizes = self.sizes
+
+    def __len__(self):
+        return len(self.names)
+
+    def image(self, i):
+        """View of image i, [h, w, 3] uint8."""
+        h, w = self.sizes[i]
+        return self.images[self.img_off[i]:self.img_off[i] + h * w * self.channels].view(h, w, self.channels)
+
+    def mask(self, i):
+        h, w = self.sizes[i]
+        return self.masks[self.mask_off[i]:self.mask_off[i] + h * w].view(h, w)
+
+    def _meta(self, idx):
+        return ([torch.tensor([self.sizes[i][0] for i in idx]), torch.tensor([self.sizes[i][1] for i in idx])],
+                [self.names[i] for i in idx])
+
+    def gather(self, S, idx, origins, params, fields=None):
+        """One unetdc_crop_gather over the windows `origins` of the images `idx` with the augment.draw_params dicts `params`."""
+        from . import crops
+        rec, _ = crops.pack_crops(params, [self.img_off[i] for i in idx], [self.mask_off[i] for i in idx],
+                                  [self.sizes[i] for i in idx], origins, [self.img_max[i] for i in idx])
+        return crops.crop_gather(self.images, self.masks, self.channels, S, rec, fields)
+
+
+class DeviceCropTrainLoader:
+    """Shuffled, augmented S x S crops of a DeviceNativeCache, no drop_last: N images give N * R samples per epoch
+    (R = crops_per_image).  Epoch e visits them in the order np.random.default_rng([seed, e]).permutation(N * R); local sample
+    number j is crop rep = j % R of cached image i = j // R and draws as sample q = ids[i] * R + rep of the whole training
+    split: its window from utils.crops.draw_crop(seed, e, q, h, w, S), its augmentation from augment.draw_params(seed, e, q).
+    Per batch: at most one elastic-field launch (S x S) and one unetdc_crop_gather, parameters by value; nothing waits on the
+    device."""
+
+    def __init__(self, cache, batch_size, S, seed=0, ids=None, crops_per_image=1, sigma=augment.ELASTIC_SIGMA,
+                 alpha=augment.ELASTIC_ALPHA):
+        from utils.crops import check_crop
+        self.dataset, self.batch_size, self.S, self.seed = cache, int(batch_size), check_crop(S), int(seed)
+        self.ids = list(range(len(cache))) if ids is None else [int(i) for i in ids]
+        if len(self.ids) != len(cache):
+            raise ValueError("DeviceCropTrainLoader: one global index per cached image")
+        self.R = int(crops_per_image)
+        if self.R < 1:
+            raise ValueError("DeviceCropTrainLoader: crops_per_image must be at least 1")
+        self.sigma, self.alpha = float(sigma), float(alpha)
+        self.epoch = 0
+        s = self.S
+        self._fields = torch.empty(self.batch_size, 2, s, s, dtype=torch.float32, device=cache.device)
+        self._ws = torch.empty(augment.fields_workspace_bytes(self.batch_size, s, s, self.sigma), dtype=torch.uint8,
+                               device=cache.device)
+
+    @property
+    def samples(self):
+        return len(self.dataset) * self.R
+
+    def __len__(self):
+        return (self.samples + self.batch_size - 1) // self.batch_size
+
+    def records(self, epoch, js):
+        """(cache indices, origins, draw_params dicts) of the local sample numbers `js` in epoch `epoch`."""
+        from utils.crops import draw_crop
+        c = self.dataset
+        idx = [int(j) // self.R for j in js]
+        qs = [self.ids[i] * self.R + int(j) % self.R for i, j in zip(idx, js)]
+        origins = [draw_crop(self.seed, epoch, q, *c.sizes[i], self.S) for i, q in zip(idx, qs)]
+        return idx, origins, [augment.draw_params(self.seed, epoch, q) for q in qs]
+
+    def batch(self, epoch, js):
+        """The augmented batch of local sample numbers `js` in epoch `epoch`."""
+        c = self.dataset
+        idx, origins, params = self.records(epoch, js)
+        seeds = np.asarray([p["field_seed"] for p in params if p["elastic"]], dtype=np.uint32)
+        fields = None
+        if len(seeds):
+            fields = augment.elastic_fields(seeds, self.S, self.S, self.sigma, self.alpha, out=self._fields,
+                                            workspace=self._ws)[:len(seeds)]
+        images, masks = c.gather(self.S, idx, origins, params, fields)
+        sizes, names = c._meta(idx)
+        return images, masks, sizes, names
+
+    def __iter__(self):
+        epoch = self.epoch
+        self.epoch += 1
+        perm = np.random.default_rng([self.seed, epoch]).permutation(self.samples)
+        for b0 in range(0, len(perm), self.batch_size):
+            yield self.batch(epoch, perm[b0:b0 + self.batch_size])
+
+
+class DeviceCropEvalLoader:
+    """The utils.crops.eval_plan windows of every cached image in order (image by image, row-major), batch_size at a time,
+    through unetdc_crop_gather with identity records: validation and test at the scale the crops train at.  Where the evenly
+    spread windows of an image overlap, a pixel is counted by each window that covers it."""
+
+    def __init__(self, cache, batch_size, S):
+        from utils.crops import check_crop, eval_plan
+        self.dataset, self.batch_size, self.S = cache, int(batch_size), check_crop(S)
+        self.windows = [(i, y0, x0) for i, (h, w) in enumerate(cache.sizes) for y0, x0 in eval_plan(h, w, self.S)]
+
+    def __len__(self):
+        return (len(self.windows) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        from .crops import IDENTITY
+        c = self.dataset
+        for b0 in range(0, len(self.windows), self.batch_size):
+            win = self.windows[b0:b0 + self.batch_size]
+            idx = [i for i, _, _ in win]
+            images, masks = c.gather(self.S, idx, [(y0, x0) for _, y0, x0 in win], [IDENTITY] * len(win))
+            sizes, names = c._meta(idx)
+            yield images, masks, sizes, names
