@@ -56,7 +56,54 @@ def test_onehot_and_separable_references_match_the_gemm_forms(case):
     assert torch.equal(X.conv3x3_fwd(x, wt, d, fast=True).double(), X.conv3x3_fwd(x, wt, d))
 
 
-@pytest.mark.parametrize("case", [(2, 3, 5, 6, 4), (1, 4, 4, 3, 8)])
+# (n, h, w, ci, co, d): the shapes of tests/test_gpu_exact.py SMALL_ROUTE_CASES at a reduced channel count
+PADDED_TAP_CASES = [(1, 2, 2, 24, 16, 16), (3, 3, 3, 24, 16, 16), (2, 8, 8, 24, 16, 4)]
+
+
+@pytest.mark.parametrize("case", PADDED_TAP_CASES)
+def test_references_where_the_dilation_reaches_the_map_side(case):
+    """d >= the map side (2 x 2 and 3 x 3 under d = 16): the eight off-centre taps read only padding, so every reference form
+    -- GEMM, one-hot, separable -- reduces to the centre tap: forward and input gradient are the 1 x 1 convolution with
+    w[:, :, 1, 1], and the eight padded taps of the weight gradient are EXACTLY zero.  At 8 x 8 under d = 4 every tap has a
+    4 x 4 (or 4 x 8, 8 x 4) valid rectangle.  All against ATen in float64."""
+    n, h, w, ci, co, d = case
+    g = gen(8)
+    x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(co, ci, 3, 3, generator=g, dtype=torch.float64)
+    dy = torch.randn(n, co, h, w, generator=g, dtype=torch.float64)
+    xr, wr = x.clone().requires_grad_(True), wt.clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, None, padding=d, dilation=d)
+    gx, gw = torch.autograd.grad(y, (xr, wr), dy)
+    fwd, dg, wg = X.conv3x3_fwd(nhwc(x), wt, d), X.conv3x3_dgrad(nhwc(dy), wt, d), X.conv3x3_wgrad(nhwc(x), nhwc(dy), d)
+    torch.testing.assert_close(fwd, nhwc(y.detach()))
+    torch.testing.assert_close(dg, nhwc(gx))
+    torch.testing.assert_close(wg, gw)
+    centre = torch.zeros(3, 3, dtype=torch.bool)
+    centre[1, 1] = True
+    padded = d >= max(h, w)
+    if padded:
+        assert bool((wg[:, :, ~centre] == 0).all()) and bool((gw[:, :, ~centre] == 0).all())
+        torch.testing.assert_close(fwd, torch.einsum("nhwi,oi->nhwo", nhwc(x), wt[:, :, 1, 1]))
+        torch.testing.assert_close(dg, torch.einsum("nhwo,oi->nhwi", nhwc(dy), wt[:, :, 1, 1]))
+    else:
+        assert bool((wg.abs().amax(dim=(0, 1)) > 0).all())
+    # the integer fixtures of the GPU tests: the one-hot and separable forms equal the GEMM forms bit for bit
+    xi = X.ints((n, h, w, ci), 2, g, lo=1)
+    wo, route = X.onehot_conv3x3(co, ci)
+    assert torch.equal(X.conv3x3_fwd_onehot(xi, route, co, d).double(), X.conv3x3_fwd(xi, wo, d))
+    dyi = X.ints((n, h, w, co), 2, g)
+    assert torch.equal(X.conv3x3_dgrad_onehot(dyi, route, ci, d).double(), X.conv3x3_dgrad(dyi, wo, d))
+    a, u = X.ints((n, h, w), 2, g), X.ints((ci,), 2, g)
+    sep, dense = X.conv3x3_wgrad_separable(a, u, dyi, d), X.conv3x3_wgrad(xi, dyi, d)
+    assert torch.equal(sep, X.conv3x3_wgrad(a[..., None] * u, dyi, d))
+    if padded:
+        assert bool((sep[:, :, ~centre] == 0).all()) and bool((dense[:, :, ~centre] == 0).all())
+        tap_of = route[1]
+        off = tap_of != 4                          # output channels routed through a padded tap read nothing
+        assert bool(off.any()) and bool((X.conv3x3_fwd_onehot(xi, route, co, d)[..., off] == 0).all())
+
+
+@pytest.mark.parametrize("case", [(2, 3, 5, 6, 4), (1, 4, 4, 3, 8), (1, 2, 2, 16, 8), (3, 3, 3, 16, 8)])
 def test_conv_transpose_reference_matches_autograd(case):
     n, h, w, ci, co = case
     g = gen(3)
@@ -213,7 +260,7 @@ def test_bn_finalize_fixture_is_exact_at_any_count():
     the fp32 rounding of the fp64 reference exactly, so those cases keep bound 0 for mean, var, rstd, scale and shift."""
     from tests import test_gpu_exact_norm as N
     assert any(not N.pow2_count(count) for _, count, _ in N.ODD_FINALIZE_CASES)
-    for rows, count, c in N.FINALIZE_CASES + N.ODD_FINALIZE_CASES:
+    for rows, count, c in N.FINALIZE_CASES + N.ODD_FINALIZE_CASES + N.SMALL_FINALIZE_CASES:
         if rows * c > 1 << 20:                   # (the largest power-of-two cases: minutes of host time for nothing new)
             continue
         g = gen(31)

@@ -272,7 +272,11 @@ def test_eval_loader_returns_every_image_at_its_eval_plan(cache, host):
             assert np.array_equal(gm[j, 0], mwin.astype(np.float32)), (i, y0, x0)
 
 
-def test_crop_trains_end_to_end(data_dir, tmp_path, monkeypatch, capsys):
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_crop_trains_end_to_end(data_dir, tmp_path, monkeypatch, capsys, dtype):
+    """--crop 32 through main() in both compute types.  bf16: the same step on the small bf16 routes (a 2 x 2 bottleneck, batches
+    of 4 on four training images); val_dice > 0 stays an fp32-only assertion (two epochs from a random start in bf16 is not a
+    measured quantity)."""
     import train_DC_focal
     from unet_dc_segmentation_amd import device_data
     served = []
@@ -281,7 +285,7 @@ def test_crop_trains_end_to_end(data_dir, tmp_path, monkeypatch, capsys):
                         lambda self, epoch, js: (served.append((epoch, len(js), len(self.dataset))), batch(self, epoch, js))[1])
     h = train_DC_focal.main(["--image_dir", data_dir[0], "--mask_dir", data_dir[1], "--ckpt_path", str(tmp_path / "ck.pth"),
                              "--device_data", "--crop", "32", "--crops_per_image", "2", "--batch", "4", "--epochs", "2",
-                             "--patience", "5", "--calibrate_thresh", "10"])
+                             "--patience", "5", "--calibrate_thresh", "10"] + (["--dtype", "bf16"] if dtype == "bf16" else []))
     assert len(h) == 2
     for rec in h:
         assert all(math.isfinite(rec[k]) for k in ("train_loss", "val_loss", "train_dice", "val_dice"))
@@ -290,7 +294,9 @@ def test_crop_trains_end_to_end(data_dir, tmp_path, monkeypatch, capsys):
     for e in range(2):
         assert sum(n for ep, n, _ in served if ep == e) == 2 * n_train
     assert h.test is not None and math.isfinite(h.test["test_loss"])
-    assert max(rec["val_dice"] for rec in h) > 0 and os.path.exists(tmp_path / "ck.pth")     # every split has droplets
+    assert os.path.exists(tmp_path / "ck.pth")
+    if dtype == "f32":
+        assert max(rec["val_dice"] for rec in h) > 0                  # every split has droplets
     c = h.calibration
     assert c is not None and c["K"] == 10 and 0 <= c["best_dice_threshold"] < 1 and int(np.asarray(c["hist"]).sum()) > 0
     out = capsys.readouterr().out

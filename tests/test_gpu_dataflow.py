@@ -489,17 +489,39 @@ def test_dataflow_bf16_frozen(tracer):
     assert {"unetdc_bn_frozen_affine", "unetdc_bn_relu_bwd_frozen"} <= tr.forms
 
 
-def test_dataflow_bf16_eval_quantify(tracer):
-    """UNetDC(3, 1) eval forward under no_grad (bench.py --mode quantify): folded statistics, pool-only normalisation pass."""
+def eval_quantify(tracer, config, n=8, size=512, seed=60):
+    """One traced bf16 eval forward of UNetDC(3, 1) under no_grad on n images of size x size."""
     t0 = time.time()
     model = make_model("unetdc", 3, "bf16", perturb=True).eval()
-    tr = tracer(model, torch.bfloat16, (8, 512, 512))
-    x, _ = batch(60, 8, 3, 512)
+    tr = tracer(model, torch.bfloat16, (n, size, size))
+    x, _ = batch(seed, n, 3, size)
     with torch.no_grad():
         p = model(x)
     tr.end_step(tr.engines[tr.owner_of_probs(p.data_ptr())], trained=False)
-    report("bf16_eval", tr, t0)
+    report(config, tr, t0)
     assert {"unetdc_bn_eval_affine", "unetdc_head_fwd", "unetdc_bn_relu_apply"} <= tr.forms
+    return tr
+
+
+def test_dataflow_bf16_eval_quantify(tracer):
+    """UNetDC(3, 1) eval forward under no_grad (bench.py --mode quantify): folded statistics, pool-only normalisation pass."""
+    eval_quantify(tracer, "bf16_eval")
+
+
+def test_dataflow_bf16_eval_tile_2x48(tracer):
+    """The same eval forward at 2 x 48^2 (quantify_droplets_batch.py --tile 48 --dtype bf16, the ragged last chunk of a 4 + 2
+    tile plan): the folded-BatchNorm, affine-ReLU epilogue on the small routes -- a 3 x 3 bottleneck under dilation 16 (the
+    centre tap only), 6 x 6 maps under dilation 8, M = 18 at the bottleneck (no 16-row tile route).  Measured on MI355X, worst
+    err / bound: 0.993 (activations and up-convolutions), probabilities 0.11."""
+    tr = eval_quantify(tracer, "bf16_eval_2x48", n=2, size=48, seed=62)
+    eng = next(iter(tr.engines.values()))
+    assert eng.npix[-1] == 18 and eng.res[-1] == (3, 3), (eng.npix, eng.res)
+    at18 = {k[0]: sorted(v) for k, v in tr.calls_at.items() if (k[1], k[2]) == (3, 3) and "conv" in k[0]}
+    print(f"[bf16_eval_2x48] kernels on the 3 x 3 maps: {at18}")
+    assert {"unetdc_conv3x3_fwd", "unetdc_convT2x2_fwd"} <= set(at18), at18
+    for sym, names in at18.items():                # M % 16 != 0: plan_igemm leaves dma16; lattice and halo need whole tiles
+        for name in names:
+            assert not any(t in name for t in ("dma16", "16x16x32", "lattice", "halo")), (sym, name)
 
 
 def test_dataflow_bf16_two_live_forwards(tracer):
@@ -677,6 +699,58 @@ def test_dataflow_bf16_odd_maps(tracer):
     # odd pooled rows: enc4's 6 x 10 map pools to 3 x 5, forward and backward
     assert eng.res[3] == (6, 10) and eng.res[4] == (3, 5), eng.res
     assert ("unetdc_bn_relu_apply", 6, 10) in tr.calls_at and ("unetdc_bn_relu_bwd", 6, 10) in tr.calls_at, sorted(tr.calls_at)
+
+
+def small_crop_step(tracer, config, n, seed):
+    """UNetDC(3, 1), n x 32^2, one FusedAdam step (train_DC_focal.py --device_data --crop 32 --dtype bf16), traced and compared
+    with the production plan.  What the two planning queries say at these maps is what the engine must have planned: no stage
+    takes a normalise-on-load form (unetdc_conv3x3_bnin_supported is 0 at 32 ... 4 pixels a side: the 32 x 32 level takes the
+    lattice forward, but no input-normalising weight gradient exists below 32K pixels; the others are no lattice maps) and
+    the first layer keeps the plain weight gradient (unetdc_conv3x3_first_wgrad_bn_supported: C_in = 3).  Measured on MI355X,
+    worst err / bound over all value kinds: 0.996 at 4 x 32^2 and at 1 x 32^2 (stored bf16 activations, one rounding from the
+    reference; the BatchNorm constants stay below 3e-5 and the gradients of the parameters below 0.37)."""
+    from unet_dc_segmentation_amd import _lib
+    lib = _lib.load()
+    tr, plan, dplan = off_production(tracer, config, "unetdc", 3, (n, 32, 32), seed, adam=True)
+    eng = next(iter(tr.engines.values()))
+    print(f"[{config}] plan: {plan}")
+    assert eng.npix == [n * 1024, n * 256, n * 64, n * 16, n * 4] and eng.res[-1] == (2, 2), (eng.npix, eng.res)
+    for (block, idx), st in eng.stages.items():
+        if idx == 3 and block != "bottleneck":
+            assert lib.unetdc_conv3x3_bnin_supported(n, *st.hw, st.cout, st.cout, st.dil, 1) == 0, (block, st.hw)
+    assert lib.unetdc_conv3x3_first_wgrad_bn_supported(n, 32, 32, 3, 64, 1, 1) == 0
+    assert plan["enc1.0"] == ("first", "first", True), plan["enc1.0"]
+    assert all(v[:2] == ("plain", "plain") for k, v in plan.items() if k not in ("enc1.0", "head_fused")), plan
+    assert all(v[2] for k, v in plan.items() if k not in ("dec1.3", "head_fused")), plan       # every activation is stored
+    assert plan["head_fused"] is True
+    assert not {"bnin", "bnin_store", "unetdc_conv3x3_fwd_bnin", "unetdc_conv3x3_wgrad_bnin", "unetdc_conv3x3_first_wgrad_bn",
+                "unetdc_bn_relu_bwd_coeffs"} & tr.forms, sorted(tr.forms)
+    assert {"unetdc_conv3x3_first_wgrad", "unetdc_bn_relu_bwd_head", "unetdc_head_fwd_bn"} <= tr.forms, sorted(tr.forms)
+    # the 2 x 2 bottleneck: both stages forward, input gradient and weight gradient, and the up-convolution that reads it
+    at2 = {k[0]: sorted(v) for k, v in tr.calls_at.items() if (k[1], k[2]) == (2, 2) and "conv" in k[0]}
+    print(f"[{config}] kernels on the 2 x 2 maps: {at2}")
+    assert {"unetdc_conv3x3_fwd", "unetdc_conv3x3_wgrad", "unetdc_conv3x3_dgrad", "unetdc_conv3x3_dgrad_bnstats", "unetdc_convT2x2_fwd",
+            "unetdc_convT2x2_wgrad", "unetdc_convT2x2_dgrad_bnstats"} <= set(at2), sorted(at2)
+    for sym, names in at2.items():
+        for name in names:
+            assert "wgrad_rect_kernel" not in name, (sym, name)        # d = 16 >= 2: rect_plan finds an empty rectangle
+            if (n * 4) % 16:                                           # M = 4 N below one 16-row tile
+                assert not any(t in name for t in ("dma16", "16x16x32", "lattice", "halo")), (sym, name)
+    return tr, eng
+
+
+def test_dataflow_bf16_crop_4x32(tracer):
+    """UNetDC(3, 1), 4 x 32^2 with FusedAdam: the smallest --crop step at a full batch.  A 2 x 2 bottleneck (M = 16, exactly
+    one MFMA tile; BatchNorm statistics over 16 values), dilation >= the map side at the bottleneck, enc4 and enc3, the
+    persistent lattice kernel with 16 items at the 32 x 32 level."""
+    small_crop_step(tracer, "bf16_dc3_4x32", 4, 104)
+
+
+def test_dataflow_bf16_crop_1x32(tracer):
+    """The same at 1 x 32^2, the ragged last batch: M = 4 at the bottleneck (BatchNorm statistics over 4 values per
+    channel), 4 lattice items on a grid of 4 at the 32 x 32 level."""
+    _, eng = small_crop_step(tracer, "bf16_dc3_1x32", 1, 106)
+    assert eng.npix[-1] == 4, eng.npix
 
 
 def test_dataflow_bf16_odd_maps_three_channels_dx(tracer):

@@ -522,6 +522,45 @@ DTYPES = {"f32": 0, "bf16": 1}
 ROUTE_CASES = list(CONV_CASES) + [
     (1, 9, 13, 64, 64, 1),       # M = 117, not a multiple of 16: bf16 on the 32x32x16 DMA kernel (igemm_dma.hip)
     (1, 264, 512, 64, 64, 2)]    # bf16, d = 2, H / d = 132 not a multiple of the lattice tile: the 16x16x32 halo kernel
+# The stages of a 32^2 ... 96^2 step (train_DC_focal.py --crop, quantify_droplets_batch.py --tile) and of the 256^2 bottleneck.
+# Dilation >= the map side: the eight off-centre taps read only padding (forward and input gradient reduce to the centre tap, the
+# weight gradient writes exact zeros into eight of nine taps, rect_plan finds an empty rectangle).  M = N h w below or at one
+# 16-row MFMA tile.  The persistent lattice kernel with 4 items on a grid of 4.  SMALL_ROUTES records the kernels reached.
+SMALL_ROUTE_CASES = [
+    (1, 2, 2, 1024, 1024, 16),   # bottleneck.3 of 1 x 32^2: M = 4
+    (3, 2, 2, 512, 1024, 16),    # bottleneck.0 of 3 x 32^2: M = 12
+    (4, 2, 2, 512, 1024, 16),    # M = 16, exactly one tile
+    (3, 3, 3, 1024, 1024, 16),   # 48^2 bottleneck: M = 27, odd map
+    (1, 4, 4, 512, 512, 8),      # enc4 of 32^2, d >= side: M = 16
+    (3, 4, 4, 256, 512, 8),      # the same stage at batch 3: M = 48
+    (2, 8, 8, 256, 256, 4),      # enc3 of 32^2: the valid rectangles are 4 x 4
+    (2, 16, 16, 512, 1024, 16),  # 256^2 bottleneck: d equals the side, so the rectangles are empty
+    (1, 32, 32, 64, 64, 1),      # lattice, 4 items
+    (1, 32, 32, 128, 64, 1),     # dec1.0 of 32^2: two K chunks on 4 items
+    (1, 32, 32, 128, 128, 1),    # dec2 of 64^2: wide lattice, 4 items
+    (3, 64, 64, 64, 64, 1),      # 48 items, 3 images
+    (2, 16, 16, 64, 128, 2)]     # enc2.0 of 32^2: 8-pixel sub-lattices, not the lattice route
+# SMALL_ROUTES: the kernel every call of those cases reached on MI355X (unetdc_last_kernel(); both fixtures reach the same).
+# fp32, every case: all six forward / input-gradient calls on igemm_dma_kernel<float, 4, 2, 2> -- igemm_dma_kernel<float, 4, 1, 2>
+#   where the GEMM's N is 64 (forward of the three C_out = 64 cases, input gradient of the three C_in = 64 cases) -- and the
+#   weight gradient on wgrad_dma_kernel<float, 4> (1 at 64 x 64 and 128 -> 64 and 64 -> 128 channels, 2 at 128 x 128).
+# bf16:
+#   (1, 2, 2, 1024, 1024, 16), (3, 2, 2, 512, 1024, 16), (3, 3, 3, 1024, 1024, 16)   [M % 16 != 0]
+#       fwd store / stats / affine, dgrad plain / colsum / bnstats: igemm_dma_kernel<__bf16, 4, 2, 2>; wgrad: wgrad_dma_kernel<__bf16, 4>
+#   (4, 2, 2, 512, 1024, 16), (1, 4, 4, 512, 512, 8), (3, 4, 4, 256, 512, 8)
+#       all six: igemm_dma16_kernel<4, 2, 4> ring3; wgrad: wgrad_dma_kernel<__bf16, 4>
+#   (2, 8, 8, 256, 256, 4)       all six: igemm_dma16_kernel<4, 2, 4> ring3; wgrad: wgrad_rect_kernel
+#   (2, 16, 16, 512, 1024, 16)   all six: igemm_dma16_kernel<4, 2, 4> ring3 blocks16x16; wgrad: wgrad_dma_kernel<__bf16, 4>
+#   (1, 32, 32, 64, 64, 1), (3, 64, 64, 64, 64, 1)
+#       fwd store / stats / affine: igemm_lattice_kernel<4, 1, 4, 1, 0> / <.., 1> / <.., 2>; dgrad plain / colsum / bnstats:
+#       igemm_lattice_kernel<4, 1, 4, 1, 0> / <.., 1> / <.., 4>; wgrad: wgrad_dma_kernel<__bf16, 1>
+#   (1, 32, 32, 128, 64, 1)      fwd: as at 64 x 64 channels; dgrad plain / colsum / bnstats: igemm_lattice_kernel<4, 2, 4, 2, 0> /
+#       igemm_lattice_wide_kernel<1> / igemm_lattice_wide_kernel<4>; wgrad: wgrad_dma_kernel<__bf16, 1>
+#   (1, 32, 32, 128, 128, 1)     fwd store / stats / affine: igemm_lattice_kernel<4, 2, 4, 2, 0> / igemm_lattice_wide_kernel<1> /
+#       igemm_lattice_wide_kernel<2>; dgrad: as at 128 -> 64; wgrad: wgrad_dma_kernel<__bf16, 2>
+#   (2, 16, 16, 64, 128, 2)      fwd (all three): igemm_dma16_kernel<4, 2, 4> ring3; dgrad (all three): igemm_dma16_kernel<4, 1, 4>;
+#       wgrad: wgrad_dma_kernel<__bf16, 1>
+ROUTE_CASES += SMALL_ROUTE_CASES
 WGRAD_CASES = [(2, 512, 256, 64, 64, 1), (1, 520, 512, 128, 64, 1), (4, 256, 256, 64, 128, 2), (2, 128, 128, 256, 128, 8),
                (8, 64, 64, 128, 256, 4), (5, 64, 64, 1024, 512, 1),                      # tap-fused (wgrad_fused.hip)
                (2, 32, 32, 256, 256, 16), (1, 16, 24, 256, 512, 8), (3, 24, 40, 512, 256, 16),    # valid rectangles (bf16)
@@ -530,6 +569,14 @@ BNIN_CASES = [(2, 256, 256, 64, 64, 1), (2, 64, 256, 64, 64, 2), (2, 128, 128, 1
               (3, 64, 192, 128, 256, 1), (1, 128, 256, 256, 256, 1)]
 CONVT_CASES = [(2, 8, 12, 128, 64), (1, 16, 16, 256, 128), (1, 4, 4, 1024, 512), (2, 32, 32, 256, 128), (1, 64, 64, 128, 64),
                (2, 16, 96, 512, 256), (1, 4, 32, 128, 64), (3, 8, 32, 128, 64)]
+# up-convolutions from the 2 x 2, 3 x 3 and 6 x 6 bottlenecks of 32^2, 48^2 and 96^2 and upconv2 of 32^2: MODE_SHUFFLE with
+# Wo % 16 != 0 leaves the dma16 route (SMALL_ROUTES records the kernels reached)
+SMALL_CONVT_CASES = [(1, 2, 2, 1024, 512), (3, 3, 3, 1024, 512), (2, 6, 6, 1024, 512), (1, 8, 8, 256, 128)]
+# reached on MI355X -- fp32, every case: fwd, dgrad and dgrad_bnstats on igemm_dma_kernel<float, 4, 2, 2>, wgrad on
+# wgrad_dma_kernel<float, 4> (2 at 256 -> 128); bf16, the three 1024 -> 512 cases: fwd, dgrad and dgrad_bnstats on
+# igemm_dma_kernel<__bf16, 4, 2, 2>, wgrad on wgrad_dma_kernel<__bf16, 4>; bf16 (1, 8, 8, 256, 128): fwd on
+# igemm_dma_kernel<__bf16, 4, 2, 2>, dgrad and dgrad_bnstats on igemm_dma16_kernel<4, 2, 4> ring3, wgrad on wgrad_dma_kernel<__bf16, 2>
+CONVT_CASES += SMALL_CONVT_CASES
 FIRST_CASES = [(2, 24, 40, 1), (2, 64, 64, 2), (3, 10, 10, 1), (1, 8, 8, 1), (2, 96, 136, 1)]
 FIRST_BN_CASES = [(2, 16, 24), (1, 64, 64), (3, 40, 96)]
 ROUTE_RUN = []                  # route-case items run in this session (test_route_coverage needs all of them)
@@ -555,11 +602,35 @@ def test_exact_conv3x3_routes(case, dtype, fix):
     ROUTE_RUN.append(1)
     dense_affordable(case, fix)
     kw = kwargs(case, dtype)
-    for mode in ({"ptr:stats_part": False}, {"ptr:stats_part": True}, {"ptr:scale": True}):
-        KERNELS.add(conv_fwd(dict(kw, **mode), fix))
+    names = {}
+    for tag, mode in (("store", {"ptr:stats_part": False}), ("stats", {"ptr:stats_part": True}), ("affine", {"ptr:scale": True})):
+        names["fwd/" + tag] = conv_fwd(dict(kw, **mode), fix)
     for variant in ("plain", "colsum", "bnstats"):
-        KERNELS.add(conv_dgrad(kw, fix, variant))
-    KERNELS.add(conv_wgrad(kw, fix))
+        names["dgrad/" + variant] = conv_dgrad(kw, fix, variant)
+    names["wgrad"] = conv_wgrad(kw, fix)
+    KERNELS.update(names.values())
+    planned_routes(case, dtype, fix, names)
+
+
+def planned_routes(case, dtype, fix, names):
+    """What the planning code implies for the kernels a route case reached (names: call -> unetdc_last_kernel()):
+      - d >= a map side: a tap's valid rectangle is empty, rect_plan returns 0 (wgrad_rect.hip): never wgrad_rect_kernel;
+      - the bf16 cases of SMALL_ROUTE_CASES with d = 1 on 32 x 32 and 64 x 64 maps ((W / d) % 32 == 0, (H / d) % 8 == 0):
+        forward and input gradient on a lattice kernel (igemm_lattice_supported comes first in plan_igemm);
+      - bf16 with M % 16 != 0: no 16-row tile route (dma16 needs M % 16 == 0, the lattice and halo kernels whole tiles;
+        the 16x16x32 weight-gradient kernels need >= 32K pixels)."""
+    n, h, w, _, _, d = case
+    small = case in SMALL_ROUTE_CASES
+    if small:
+        print(f"\n[route {case} {dtype} {fix}] " + ", ".join(f"{k}: {v}" for k, v in names.items()))
+    if d >= min(h, w):
+        assert "wgrad_rect_kernel" not in names["wgrad"], (case, dtype, names)
+    if small and dtype == "bf16" and d == 1 and (h, w) in ((32, 32), (64, 64)):
+        for k, v in names.items():
+            assert k == "wgrad" or "lattice" in v, (case, k, v)
+    if dtype == "bf16" and (n * h * w) % 16:
+        for k, v in names.items():
+            assert not any(t in v for t in ("dma16", "16x16x32", "lattice", "halo")), (case, k, v)
 
 
 @pytest.mark.parametrize("fix", FIXTURES)
@@ -592,10 +663,13 @@ def test_exact_conv_transpose_routes(case, dtype, fix):
     ROUTE_RUN.append(1)
     n, h, w, cin, cout = case
     kw = dict(n=n, h=h, w=w, cin=cin, cout=cout, dtype=DTYPES[dtype])
-    KERNELS.add(convt_fwd(kw, fix))
-    KERNELS.add(convt_dgrad(kw, fix))
-    KERNELS.add(convt_dgrad(kw, fix, bnstats=True))
-    KERNELS.add(convt_wgrad(kw, fix))
+    names = dict(fwd=convt_fwd(kw, fix), dgrad=convt_dgrad(kw, fix), dgrad_bnstats=convt_dgrad(kw, fix, bnstats=True),
+                 wgrad=convt_wgrad(kw, fix))
+    KERNELS.update(names.values())
+    if case in SMALL_CONVT_CASES:
+        print(f"\n[convT {case} {dtype} {fix}] " + ", ".join(f"{k}: {v}" for k, v in names.items()))
+        if dtype == "bf16" and w % 16:                # plan_igemm: MODE_SHUFFLE with Wo % 16 != 0 (Wo = the input width) leaves dma16
+            assert "dma16" not in names["fwd"], (case, names)
 
 
 @pytest.mark.parametrize("fix", FIXTURES)
@@ -624,7 +698,8 @@ def test_exact_first_layer_wgrad_bn_on_load(case, dtype, fix):
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
 @pytest.mark.parametrize("pool", [False, True])
-@pytest.mark.parametrize("case", [(2, 16, 24, 64), (1, 8, 8, 1024), (3, 4, 4, 256), (2, 64, 96, 128)])
+@pytest.mark.parametrize("case", [(2, 16, 24, 64), (1, 8, 8, 1024), (3, 4, 4, 256), (2, 64, 96, 128),
+                                  (1, 32, 32, 64), (1, 4, 4, 512)])            # a 32^2 step: pooled to 16 x 16 and to 2 x 2
 def test_exact_bn_relu_apply(case, pool, dtype):
     n, h, w, c = case
     bn_relu_apply(dict(n=n, h=h, w=w, c=c, dtype=DTYPES[dtype], **{"ptr:pooled": pool}), "dense")
@@ -772,13 +847,74 @@ REPLAY_CONFIGS = {"bf16_8x512": cfg("bf16", 8), "f32_8x512": cfg("f32", 8),
                   "dc3_bf16_8x512_dx": cfg("bf16", 8, cin=3, dx=True), "dc3_f32_8x512_dx": cfg("f32", 8, cin=3, dx=True),
                   # train_DC_focal.py --img_size 384 --batch 5 --dtype bf16: no pixel count of the step is a power of two
                   # (5 * 9 * 2^k: 737280 ... 2880), maps of 384, 192, 96, 48 and 24 pixels a side (see the test's docstring)
-                  "dc3_bf16_5x384": cfg("bf16", 5, 384, cin=3, adam=True)}
+                  "dc3_bf16_5x384": cfg("bf16", 5, 384, cin=3, adam=True),
+                  # train_DC_focal.py --device_data --crop S: a full batch of the smallest crop in both dtypes, its ragged last
+                  # batch (a 2 x 2 bottleneck: M = 4), and crops of 64 and 96
+                  "crop_bf16_4x32": cfg("bf16", 4, 32, cin=3, adam=True), "crop_f32_4x32": cfg("f32", 4, 32, cin=3, adam=True),
+                  "crop_bf16_1x32": cfg("bf16", 1, 32, cin=3, adam=True), "crop_bf16_3x64": cfg("bf16", 3, 64, cin=3, adam=True),
+                  "crop_bf16_2x96": cfg("bf16", 2, 96, cin=3, adam=True),
+                  # quantify_droplets_batch.py --tile T: a full chunk, the ragged last chunk of a 4 + 2 tile plan
+                  # (tests/test_gpu_tiling.py), and the smallest tile
+                  "tile_bf16_4x64_eval": cfg("bf16", 4, 64, mode="eval", cin=3),
+                  "tile_bf16_2x48_eval": cfg("bf16", 2, 48, mode="eval", cin=3),
+                  "tile_f32_4x48_eval": cfg("f32", 4, 48, mode="eval", cin=3),
+                  "tile_bf16_1x32_eval": cfg("bf16", 1, 32, mode="eval", cin=3)}
 # 1024^2: the forward and weight-gradient convolution calls and every non-convolution call (the host reference of the
 # whole step is over the time budget; its input-gradient calls take the same kernels as at 512^2 with twice the items per
 # workgroup)
 REPLAY_ONLY = {"bf16_4x1024": ("fwd", "wgrad")}
 # (batch 3 and 5 x 384^2: every pixel count is 3 * 2^k or 45 * 2^k; the BatchNorm runners of tests/test_gpu_exact_norm.py take any
 # count -- sums and statistics stay exact, k2 / k3 / dbias are fp64-bounded there -- so every call of those steps is replayed)
+# The kernels each native-resolution config reached on MI355X, as test_production_step_replay prints them (sym: kernels).
+# crop_bf16_4x32   conv3x3_fwd: dma16<4, 2, 4> ring3, lattice<4, 1, 4, 1, 1>; conv3x3_dgrad: dma16<4, 1, 4>, dma16<4, 2, 4> ring3;
+#   conv3x3_dgrad_bnstats: dma16<4, 2, 4> ring3, lattice<4, 1, 4, 1, 4>; conv3x3_dgrad_colsum: dma16<4, 2, 4> ring3, lattice_wide<1>;
+#   conv3x3_wgrad: wgrad_dma<__bf16, 1 | 2 | 4>, wgrad_rect; convT2x2_fwd: dma16<4, 2, 4> ring3, igemm_dma<__bf16, 4, 2, 2>;
+#   convT2x2_dgrad_bnstats: dma16<4, 2, 4> ring3; convT2x2_wgrad: wgrad_dma<__bf16, 1 | 2 | 4>; first_fwd / first_wgrad:
+#   first_mfma_fwd_kernel<__bf16> / first_mfma_wgrad_kernel<__bf16> (so in every bf16 config below)
+# crop_f32_4x32    conv3x3_fwd, conv3x3_dgrad, conv3x3_dgrad_bnstats: igemm_dma<float, 4, 1, 2>, igemm_dma<float, 4, 2, 2>;
+#   conv3x3_dgrad_colsum, convT2x2_fwd, convT2x2_dgrad_bnstats: igemm_dma<float, 4, 2, 2>; conv3x3_wgrad, convT2x2_wgrad:
+#   wgrad_dma<float, 1 | 2 | 4>; first_mfma_fwd_kernel<float>, first_mfma_wgrad_kernel<float>
+# crop_bf16_1x32   as crop_bf16_4x32, plus igemm_dma<__bf16, 4, 2, 2> under conv3x3_fwd, conv3x3_dgrad, conv3x3_dgrad_bnstats and
+#   convT2x2_dgrad_bnstats (the 2 x 2 bottleneck: M = 4)
+# crop_bf16_3x64   conv3x3_fwd: dma16<4, 2, 4> ring3, lattice<4, 1, 4, 1, 1>, lattice_wide<1>; conv3x3_fwd_bnin: lattice_wide<1> bnin;
+#   conv3x3_dgrad: dma16<4, 1, 4>, dma16<4, 2, 4> ring3; conv3x3_dgrad_bnstats: dma16<4, 2, 4> ring3, lattice<4, 1, 4, 1, 4>,
+#   lattice_wide<4>; conv3x3_dgrad_colsum: dma16<4, 2, 4> ring3, lattice_wide<1>; conv3x3_wgrad: wgrad_dma<__bf16, 1 | 2 | 4>,
+#   wgrad_rect; convT2x2_fwd: dma16<4, 2, 4> ring3, igemm_dma<__bf16, 4, 2, 2>; convT2x2_dgrad_bnstats: dma16<4, 2, 4> ring3;
+#   convT2x2_wgrad: convt_wgrad_kernel, wgrad_dma<__bf16, 2 | 4>
+# crop_bf16_2x96   the same lists as crop_bf16_1x32 (the 6 x 6 bottleneck: M = 72)
+# tile_bf16_4x64_eval   conv3x3_fwd: dma16<4, 2, 4> ring3, lattice<4, 1, 4, 1, 2>, lattice_wide<2>; convT2x2_fwd: dma16<4, 2, 4> ring3,
+#   igemm_dma<__bf16, 4, 2, 2>
+# tile_bf16_2x48_eval   conv3x3_fwd: dma16<4, 1, 4>, dma16<4, 2, 4> ring3, igemm_dma<__bf16, 4, 2, 2>; convT2x2_fwd: igemm_dma<__bf16, 4, 2, 2>
+# tile_f32_4x48_eval    conv3x3_fwd: igemm_dma<float, 4, 1, 2>, igemm_dma<float, 4, 2, 2>; convT2x2_fwd: igemm_dma<float, 4, 2, 2>
+# tile_bf16_1x32_eval   conv3x3_fwd: dma16<4, 2, 4> ring3, igemm_dma<__bf16, 4, 2, 2>, lattice<4, 1, 4, 1, 2>; convT2x2_fwd: the call of
+#   crop_bf16_1x32 (igemm_dma<__bf16, 4, 2, 2>, dma16<4, 2, 4> ring3)
+# (dma16 = igemm_dma16_kernel, lattice = igemm_lattice_kernel, lattice_wide = igemm_lattice_wide_kernel, igemm_dma = igemm_dma_kernel,
+#  wgrad_dma = wgrad_dma_kernel, wgrad_rect = wgrad_rect_kernel)
+# kernels the native-resolution configs must reach, per symbol (test_production_step_replay's docstring says why)
+REPLAY_NAMED = {
+    # first reached by this config: wgrad_dma_kernel<__bf16, 1> under the 3x3 weight gradient, <__bf16, 1> and <__bf16, 2> under the
+    # up-convolution's; also pinned: the lattice kernels on 16 items and enc3's valid-rectangle weight gradient
+    "crop_bf16_4x32": {"unetdc_conv3x3_wgrad": ["wgrad_dma_kernel<__bf16, 1>", "wgrad_rect_kernel"],
+                       "unetdc_convT2x2_wgrad": ["wgrad_dma_kernel<__bf16, 1>", "wgrad_dma_kernel<__bf16, 2>"],
+                       "unetdc_conv3x3_fwd": ["igemm_lattice_kernel<4, 1, 4, 1, 1>"],
+                       "unetdc_conv3x3_dgrad_bnstats": ["igemm_lattice_kernel<4, 1, 4, 1, 4>"]},
+    # first reached by this config: all three pairs
+    "crop_f32_4x32": {"unetdc_conv3x3_fwd": ["igemm_dma_kernel<float, 4, 1, 2>"],
+                      "unetdc_conv3x3_dgrad_bnstats": ["igemm_dma_kernel<float, 4, 1, 2>"],
+                      "unetdc_conv3x3_wgrad": ["wgrad_dma_kernel<float, 1>"]},
+    "crop_bf16_1x32": {"unetdc_conv3x3_fwd": ["igemm_dma_kernel<__bf16, 4, 2, 2>"],
+                       "unetdc_conv3x3_dgrad_bnstats": ["igemm_dma_kernel<__bf16, 4, 2, 2>"],
+                       "unetdc_convT2x2_dgrad_bnstats": ["igemm_dma_kernel<__bf16, 4, 2, 2>"]},
+    "crop_bf16_3x64": {"unetdc_conv3x3_fwd_bnin": ["igemm_lattice_wide_kernel<1> bnin"],
+                       "unetdc_conv3x3_dgrad_bnstats": ["igemm_lattice_wide_kernel<4>"],
+                       "unetdc_convT2x2_wgrad": ["convt_wgrad_kernel"]},
+    "crop_bf16_2x96": {"unetdc_conv3x3_fwd": ["igemm_dma_kernel<__bf16, 4, 2, 2>"],
+                       "unetdc_conv3x3_dgrad": ["igemm_dma_kernel<__bf16, 4, 2, 2>"]},
+    "tile_bf16_4x64_eval": {"unetdc_conv3x3_fwd": ["igemm_lattice_kernel<4, 1, 4, 1, 2>", "igemm_lattice_wide_kernel<2>"]},
+    "tile_bf16_2x48_eval": {"unetdc_conv3x3_fwd": ["igemm_dma_kernel<__bf16, 4, 2, 2>", "igemm_dma16_kernel<4, 1, 4>"]},
+    "tile_f32_4x48_eval": {"unetdc_conv3x3_fwd": ["igemm_dma_kernel<float, 4, 1, 2>", "igemm_dma_kernel<float, 4, 2, 2>"]},
+    "tile_bf16_1x32_eval": {"unetdc_conv3x3_fwd": ["igemm_lattice_kernel<4, 1, 4, 1, 2>", "igemm_dma_kernel<__bf16, 4, 2, 2>"]},
+}
 REPLAYED = set()                # distinct calls replayed by an earlier config of this session (not replayed again)
 
 
@@ -848,7 +984,20 @@ def test_production_step_replay(config):
     3 x 512^2 bf16 step does: the first-generation DMA kernel in bf16 (igemm_dma_kernel<__bf16, 4, 2, 2>) for the
     up-convolution of the 24 x 24 bottleneck, wgrad_dma_kernel<__bf16, 4> for that up-convolution's weight gradient and
     wgrad_dma_kernel<__bf16, 2> for a 3x3 one, and igemm_dma16_kernel<4, 2, 4> ring3 under unetdc_conv3x3_dgrad_colsum (at
-    512^2 every column-sum call takes the wide lattice kernel); its BatchNorm, head and loss calls run at counts 45 * 2^k."""
+    512^2 every column-sum call takes the wide lattice kernel); its BatchNorm, head and loss calls run at counts 45 * 2^k.
+
+    The native-resolution configs (--crop, --tile), in the order above; "new" = a (symbol, kernel) pair no earlier config
+    replays, measured on MI355X.  crop_bf16_4x32 is the first to reach wgrad_dma_kernel<__bf16, 1> under unetdc_conv3x3_wgrad
+    and wgrad_dma_kernel<__bf16, 1> / <__bf16, 2> under unetdc_convT2x2_wgrad; its 32 x 32 level runs the lattice kernels on 16
+    items and enc3's 8 x 8 maps take wgrad_rect_kernel.  crop_f32_4x32 is the first to reach igemm_dma_kernel<float, 4, 1, 2>
+    under unetdc_conv3x3_fwd and unetdc_conv3x3_dgrad_bnstats and wgrad_dma_kernel<float, 1> under unetdc_conv3x3_wgrad.
+    crop_bf16_1x32 (M = 4 at the bottleneck) is the first to reach igemm_dma_kernel<__bf16, 4, 2, 2> under unetdc_conv3x3_fwd,
+    unetdc_conv3x3_dgrad, unetdc_conv3x3_dgrad_bnstats and unetdc_convT2x2_dgrad_bnstats.  crop_bf16_3x64, crop_bf16_2x96 and the
+    four eval configs reach no new pair: they replay known kernels at maps nothing replayed before -- crop_bf16_3x64 the
+    normalise-on-load forward igemm_lattice_wide_kernel<1> bnin and convt_wgrad_kernel at 3 x 32 x 32, crop_bf16_2x96 and
+    tile_bf16_2x48_eval the bottlenecks of 72 and 18 pixels (M % 16 != 0) on igemm_dma_kernel<__bf16, 4, 2, 2>,
+    tile_bf16_4x64_eval and tile_bf16_1x32_eval the affine-ReLU lattice kernels igemm_lattice_kernel<4, 1, 4, 1, 2> (and
+    igemm_lattice_wide_kernel<2>) on 16 and 4 items, tile_f32_4x48_eval the two fp32 DMA tilings.  REPLAY_NAMED asserts these."""
     c = REPLAY_CONFIGS[config]
     mode = c["mode"]
     calls = distinct_calls(record_step(**c))
@@ -895,5 +1044,12 @@ def test_production_step_replay(config):
         assert "wgrad_dma_kernel<__bf16, 4>" in reached["unetdc_convT2x2_wgrad"], reached
         assert "wgrad_dma_kernel<__bf16, 2>" in reached["unetdc_conv3x3_wgrad"], reached
         assert "igemm_dma16_kernel<4, 2, 4> ring3" in reached["unetdc_conv3x3_dgrad_colsum"], reached
+    for sym, names in REPLAY_NAMED.get(config, {}).items():
+        # the routes the docstring names.  None of these calls shows as "(replayed earlier)" in any order of the configs: the
+        # key of distinct_calls carries the batch, the map, the dtype and which optional pointers are given, so the configs
+        # that share a batch and a size (crop_bf16_4x32 / crop_f32_4x32: the dtype; crop_bf16_1x32 / tile_bf16_1x32_eval:
+        # statistics against the affine-ReLU epilogue) share no 3x3 call.  They do share unetdc_convT2x2_fwd at 1 x 32^2,
+        # which is why REPLAY_NAMED names no up-convolution forward there.
+        assert set(names) <= reached[sym], (config, sym, reached[sym])
     if c["dx"]:
         assert "unetdc_conv3x3_first_dgrad" in reached, (config, sorted(reached))

@@ -488,6 +488,9 @@ def focal_dice_loss(kw, seed=37):
 # chunk lane set ('seg' = 256 splits) in bn_bwd_kernel; pixel counts are powers of two as at every stage of a batch of 1, 2,
 # 4 or 8 square power-of-two images
 BN_CASES = [(2, 16, 32, 64), (1, 32, 32, 128), (2, 8, 16, 256), (1, 8, 8, 512), (2, 4, 4, 1024), (8, 64, 64, 64)]
+# the stages of a 32^2 step (--crop 32, --tile 32): 16 values per channel (the 2 x 2 bottleneck of a batch of 4), the first level
+# of one image (pooled to 16 x 16) and its enc4 (4 x 4, pooled to 2 x 2)
+BN_CASES += [(4, 2, 2, 1024), (1, 32, 32, 64), (1, 4, 4, 512)]
 
 
 def levels(n, h, w):
@@ -500,15 +503,20 @@ def levels(n, h, w):
 # one 256-pixel block), 5 x 24 x 40 (4800 pixels: 18 full 256-pixel blocks and a partial one, an odd number of rows) and
 # 1 x 2 x 2 (four samples per channel).
 ODD_BN_CASES = levels(3, 512, 512) + levels(3, 48, 80) + levels(2, 96, 160) + [(5, 24, 40, 128), (1, 2, 2, 1024)]
+SMALL_ODD_BN_CASES = [(1, 3, 3, 1024)]     # the 48^2 bottleneck of one image: nine samples per channel
+ODD_BN_CASES += SMALL_ODD_BN_CASES
 FINALIZE_CASES = [(1, 64, 64), (37, 1 << 12, 6), (512, 1 << 17, 64), (513, 1 << 17, 128), (8192, 1 << 21, 64),
                   (2048, 1 << 19, 1024)]
 # (rows, count, C) at counts that are not powers of two; (12, 2880, 256), (19, 4800, 128) and (386, 3 * 2^15 + 300, 64): one row
 # per 256-pixel block, the last one partial (64, 192 and 44 pixels: finalize_parts gives it the smaller share)
 ODD_FINALIZE_CASES = [(3, 768, 64), (1, 45, 1024), (1, 120, 1024), (1, 4, 1024), (513, 3 * (1 << 15) + 256, 128),
                       (3072, 3 << 18, 64), (12, 2880, 256), (19, 4800, 128), (386, 3 * (1 << 15) + 300, 64), (577, 5 * 384 * 384, 64)]
+# appended after both lists (the ids of the existing cases stay): 16 values per channel in one row (4 x 2 x 2 x 1024, 1 x 4 x 4 x 512),
+# the four rows of one 32 x 32 x 64 map, and nine values per channel (the 3 x 3 bottleneck of one 48^2 image)
+SMALL_FINALIZE_CASES = [(1, 16, 1024), (1, 16, 512), (4, 1024, 64), (1, 9, 1024)]
 
 
-@pytest.mark.parametrize("case", FINALIZE_CASES + ODD_FINALIZE_CASES)
+@pytest.mark.parametrize("case", FINALIZE_CASES + ODD_FINALIZE_CASES + SMALL_FINALIZE_CASES)
 def test_exact_bn_finalize(case):
     rows, count, c = case
     bn_finalize(dict(rows=rows, count=count, c=c, eps=0.0, momentum=0.1))
@@ -532,10 +540,11 @@ def test_exact_bn_relu_bwd(case, form, dtype):
 
 
 BN_FORMS = ["skip", "pool", "skip+pool", "frozen+skip", "frozen+pool"]
-# every form at every off-grid case, except the three pooled forms at (3, 3, 5, 1024): a 2x2 max-pool needs even H and W, and
-# the network never pools such a map (H and W are multiples of 16 and the 1/16 map is not pooled).  Nothing else is left out.
+# every form at every off-grid case, except the three pooled forms at (3, 3, 5, 1024) and at (1, 3, 3, 1024): a 2x2 max-pool needs
+# even H and W, and the network never pools such a map (H and W are multiples of 16 and the 1/16 map is not pooled).  Nothing else
+# is left out.
 ODD_BN_ITEMS = [(case, form) for case in ODD_BN_CASES for form in BN_FORMS if not ("pool" in form and (case[1] % 2 or case[2] % 2))]
-assert len(ODD_BN_ITEMS) == len(ODD_BN_CASES) * len(BN_FORMS) - 3
+assert len(ODD_BN_ITEMS) == len(ODD_BN_CASES) * len(BN_FORMS) - 6
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -555,7 +564,9 @@ PRE_CASES = [((2, 16, 32, 64), "few"), ((1, 16, 16, 512), "few"), ((8, 512, 512,
              ((8, 256, 256, 128), "few"), ((8, 256, 256, 128), "production")]
 # off the power-of-two grid.  "step": the unetdc_conv3x3_stats_rows count of that map whatever it is (3072 rows at
 # 3 x 512^2 x 64, through the fp32 pre-stage; one partial row at 45 pixels); "few": 300 rows, as above
-ODD_PRE_CASES = [(c, "step") for c in ODD_BN_CASES] + [((3, 512, 512, 64), "few"), ((3, 3, 5, 1024), "few"), ((5, 24, 40, 128), "few")]
+# (the cases of SMALL_ODD_BN_CASES go last, behind the "few" ones: that keeps the ids of the existing items and does nothing else)
+ODD_PRE_CASES = [(c, "step") for c in ODD_BN_CASES if c not in SMALL_ODD_BN_CASES] \
+    + [((3, 512, 512, 64), "few"), ((3, 3, 5, 1024), "few"), ((5, 24, 40, 128), "few")] + [(c, "step") for c in SMALL_ODD_BN_CASES]
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -580,6 +591,7 @@ def test_exact_bn_relu_bwd_pre_parts(case, rows, dtype):
 HEAD_CASES = [(2, 16, 24, 64), (1, 40, 56, 32), (3, 8, 8, 128), (8, 512, 512, 64)]
 # the head's maps of the ragged batch and of the odd geometries, a 45-pixel map (below the 64-lane width) and a 4-pixel one
 HEAD_CASES += [(3, 512, 512, 64), (3, 48, 80, 64), (2, 96, 160, 64), (5, 24, 40, 128), (3, 3, 5, 64), (1, 2, 2, 64)]
+HEAD_CASES += [(1, 32, 32, 64), (3, 48, 48, 64)]       # the head of one 32^2 crop and of three 48^2 tiles
 
 
 @pytest.mark.parametrize("dtype", list(DTYPES))
@@ -599,6 +611,7 @@ def test_exact_head(case, oc, dtype):
 
 LOSS_CASES = [(1, 1, 2.0, 1.0), (8, 1000, 2.0, 1.0), (9, 1000, 1.5, -1.75), (17, 4099, 2.0, 0.5), (8, 128 * 2048, 2.0, 1.0),
               (9, 128 * 2048 + 777, 1.5, 1.0), (2, 1 << 20, 2.0, 3.0), (17, 1, 1.5, 1.0)]
+LOSS_CASES += [(1, 32 * 32, 2.0, 1.0), (3, 48 * 48, 2.0, 1.0)]      # one 32^2 crop (half a 2048-pixel block), three 48^2 maps
 
 
 @pytest.mark.parametrize("case", LOSS_CASES)

@@ -236,6 +236,54 @@ def test_predict_tiled_against_its_own_tiles_and_the_cpu_path():
     assert np.array_equal(again.view(np.uint32), got.view(np.uint32))
 
 
+BF16_PROB_BAR_EMU, BF16_PROB_BAR_F32 = 2e-2, 3e-2    # the project's bf16 probability bars (header of tests/test_gpu_e2e.py): against
+#                                                      the bf16-storage emulation of the reference and against the fp32 reference.
+#                                                      The blend is a convex combination of tile probabilities, so a bar that
+#                                                      holds per tile pixel holds for the blended map unchanged.
+
+
+def test_predict_tiled_bf16_against_both_oracles():
+    """The geometry of the fp32 test above (80 x 112, T 48, O 16, chunks of 4 + 2 tiles) with set_compute_dtype("bf16"): what
+    quantify_droplets_batch.py --tile 48 --dtype bf16 runs.  The comparison maps are the fp64 blends of the CPU oracle's outputs
+    on the gather_numpy tiles, once with bf16 storage emulated and once in plain fp32.  Measured on MI355X: 9.1e-4 against the
+    emulation, 6.7e-4 against fp32, 5.3e-8 against the fp64 blend of the device's own tile outputs."""
+    import copy
+    from oracle import unetdc_torch_cpu as otc
+    from unet_dc_segmentation_amd.tiling import predict_tiled, tile_gather
+    h, w, T, O, batch = 80, 112, 48, 16, 4
+    img = image(h, w, 3, seed=11)
+    cpu_net = seeded_net()
+    sd = {k: v.detach().clone() for k, v in cpu_net.state_dict().items()}
+    net = copy.deepcopy(cpu_net).cuda().eval()
+    net.set_compute_dtype("bf16")
+    d = torch.from_numpy(img).cuda()
+    got = predict_tiled(net, d, T, O, batch)
+    assert got.shape == (h, w) and got.dtype == torch.float32 and got.is_cuda
+    got = got.cpu().numpy()
+    assert len(net._engines) == 2 and sum(len(v) for v in net._engines.values()) <= net.MAX_ENGINES
+    tiles = tile_gather(d, T, O)
+    assert tuple(tiles.shape) == (6, 3, T, T)
+    with torch.no_grad():                                                          # the HIP module's own bf16 outputs, same chunks
+        own = torch.cat([net(tiles[0:4])[:, 0].clone(), net(tiles[4:6])[:, 0].clone()]).cpu().numpy()
+    e_own = float(np.abs(got - tl.blend_numpy64(own, h, w, T, O)).max())
+    host_tiles = torch.from_numpy(tl.gather_numpy(img, T, O))
+    maps = {}
+    with torch.no_grad():                                                          # eval mode: a tile's output does not depend on its chunk
+        for tag, emu in (("emu", True), ("f32", False)):
+            p = otc.unet_forward(host_tiles, sd, dict(cpu_net.DILATIONS), train=False, emulate_bf16=emu)[:, 0].numpy()
+            maps[tag] = tl.blend_numpy64(p, h, w, T, O)
+    e_emu = float(np.abs(got.astype(np.float64) - maps["emu"]).max())
+    e_f32 = float(np.abs(got.astype(np.float64) - maps["f32"]).max())
+    print(f"[predict_tiled bf16] max |device - fp64 blend of its own tiles| = {e_own:.3e}, max |device - bf16-storage oracle| = "
+          f"{e_emu:.3e}, max |device - fp32 oracle| = {e_f32:.3e}")
+    assert maps["f32"].std() > 1e-3                                                # the map is not flat
+    assert e_own < 1e-6
+    assert e_emu < BF16_PROB_BAR_EMU
+    assert e_f32 < BF16_PROB_BAR_F32
+    again = predict_tiled(net, d, T, O, batch).cpu().numpy()
+    assert np.array_equal(again.view(np.uint32), got.view(np.uint32))
+
+
 # ---- script -------------------------------------------------------------------------------------------------------------------
 def test_script_tile_on_the_device(tmp_path, monkeypatch):
     """quantify_droplets_batch.main --tile on the device against the same entry point's CPU rule (predict_tiled_cpu): the masks
