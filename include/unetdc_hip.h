@@ -569,6 +569,22 @@ int unetdc_tile_gather_u8_to_chw_f32(const uint8_t* src_hwc, int h, int w, int c
 int unetdc_tile_blend_f32(const float* tile_probs, int t, int overlap, const int32_t* yo, int ny, const int32_t* xo, int nx,
                           float* out, int h, int w, unetdc_stream_t s);
 
+
+/* ---- test-time augmentation over the dihedral group (tta.hip; the definition is DESIGN.md section 17, utils/tta.py) -----------
+ * Variant v in 0..7 of a square plane P [s][s]: hflip = v & 4, k = v & 3, variant(P) = np.rot90(P[:, ::-1] if hflip else P, k)
+ * (flip first, then k counter-clockwise quarter turns: the order of unetdc_augment_gather).  nvar in {1, 2, 4, 8} stands for the
+ * ordered variant lists [0], [0, 4], [0, 4, 2, 6], [0, 1, ..., 7].  s is a multiple of 16 in 16..4096, n in 1..4096, c in 1..4.
+ * unetdc_dihedral_expand_f32: x ([n][c][s][s] fp32) -> out ([n * nvar][c][s][s] fp32): item b * nvar + i is variant list[i] of
+ *   image b, every channel alike.  A permutation: bit-exact.
+ * unetdc_dihedral_mean_f32: p ([n * nvar][s][s] fp32) -> out ([n][s][s] fp32): per pixel acc = q_0, then acc = acc + q_i in list
+ *   order, every add rounded in fp32, then one IEEE division by float(nvar); q_i is item b * nvar + i mapped back through the
+ *   inverse of variant list[i].  nvar == 1 copies the input bits.
+ * Both: nothing but out is written; no workspace, no allocation, no host wait, no atomics; launches on the given stream only;
+ * two runs are bitwise equal.  UNETDC_EINVAL before any launch: a null pointer, s, n, c or nvar outside the limits above, a
+ * buffer that is not 16-byte aligned, out overlapping the input. */
+int unetdc_dihedral_expand_f32(const float* x, int n, int c, int s, int nvar, float* out, unetdc_stream_t stream);
+int unetdc_dihedral_mean_f32(const float* p, int n, int s, int nvar, float* out, unetdc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

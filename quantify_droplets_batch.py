@@ -38,6 +38,10 @@ threshold_sweep_objects.csv.
 go through the network ``--batch`` at a time, and their probabilities are blended into one map of the image's size
 (csrc/tile.hip and unet_dc_segmentation_amd/tiling.py on the device, utils/tiling.py on the CPU, one derivation for both);
 every option above then works on that map.  Meant for checkpoints trained at the scale they are applied at.
+``--tta [N]`` averages the network over N flipped and rotated variants of every input (N in 1, 2, 4, 8; 8
+without N): the variants go through the network ``--batch`` items at a time, every output is mapped back and the mean is the
+probability map that every option above reads (csrc/tta.hip and unet_dc_segmentation_amd/tta.py on the device, utils/tta.py on
+the CPU, one derivation for both); with ``--tile`` the variants are those of every tile.
 """
 import argparse
 from pathlib import Path
@@ -86,9 +90,11 @@ def preprocess(path, background_radius, im=None, keep_rgb=False):
     return torch.from_numpy(im).permute(2, 0, 1), (oh, ow)
 
 
-def predict_tiled_image(model, im, background_radius, tile, batch, keep_rgb=False):
+def predict_tiled_image(model, im, background_radius, tile, batch, keep_rgb=False, tta=None):
     """--tile: decoded image -> (probabilities [1, 1, H, W] at the image's own size, the original image for the density maps or
-    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, `batch` per forward, and the blend."""
+    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, `batch` per forward, and the blend.
+    tta: the options of --tta, every tile's probabilities are then the mean over its variants."""
+    more = {} if tta is None else {"tta": tta["N"]}
     if DEVICE == "cuda":
         from unet_dc_segmentation_amd.preprocess import MAX_ELEMENT, _upload, rolling_ball_device
         from unet_dc_segmentation_amd.tiling import predict_tiled
@@ -96,9 +102,9 @@ def predict_tiled_image(model, im, background_radius, tile, batch, keep_rgb=Fals
         rgb = _upload(im, DEVICE) if keep_rgb or not host_ball else None
         corrected = (_upload(rolling_ball_correction_rgb(im, int(background_radius)), DEVICE) if host_ball
                      else rolling_ball_device(rgb, background_radius))
-        return predict_tiled(model, corrected, tile["T"], tile["O"], batch)[None, None], rgb
+        return predict_tiled(model, corrected, tile["T"], tile["O"], batch, **more)[None, None], rgb
     from utils.tiling import predict_tiled_cpu
-    p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, background_radius), tile["T"], tile["O"], batch)
+    p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, background_radius), tile["T"], tile["O"], batch, **more)
     return torch.from_numpy(p)[None, None], (im if keep_rgb else None)
 
 
@@ -320,9 +326,16 @@ def sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean):
 
 @torch.no_grad()
 def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None):
+              density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None, tta=None):
     batch = torch.stack(tensors).to(DEVICE)
-    probs = model(batch)                                 # sigmoid probabilities (model_2.py:80)
+    if tta is None:
+        probs = model(batch)                             # sigmoid probabilities (model_2.py:80)
+    elif batch.is_cuda:                                  # --tta: the mean over the variants, tta["batch"] items per forward
+        from unet_dc_segmentation_amd.tta import predict_tta
+        probs = predict_tta(model, batch, tta["N"], tta["batch"])
+    else:
+        from utils.tta import predict_tta_cpu
+        probs = predict_tta_cpu(model, batch, tta["N"], tta["batch"])
     finish_batch(probs, meta, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers, density,
                  split_depth, shape, gt, clean, sweep)
 
@@ -472,6 +485,11 @@ def build_parser():
     p.add_argument("--tile_overlap", type=int, metavar="O",
                    help="with --tile: least overlap of neighbouring tiles in pixels, also the width of the blend ramp "
                         "(0..T/2, default 64)")
+    p.add_argument("--tta", type=int, nargs="?", const=8, metavar="N",
+                   help="test-time augmentation: run the network on N flipped and rotated variants of every input (of every "
+                        "tile with --tile), map the outputs back and average them (N = 2: + horizontal flip, 4: the flips and "
+                        "the half turn, 8: all flips and quarter turns; 8 without N); --batch stays the number of items per "
+                        "forward")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -532,6 +550,19 @@ def tile_options(args):
     return {"T": T, "O": O}
 
 
+def tta_options(args):
+    """--tta -> {"N", "batch"}, None without the flag or with N = 1 (the identity alone: the plain forward); a bad value ends
+    the run before any image."""
+    if args.tta is None:
+        return None
+    from utils.tta import TTA_SIZES
+    if args.tta not in TTA_SIZES:
+        raise SystemExit(f"--tta N: N must be one of {', '.join(map(str, TTA_SIZES))}, not {args.tta}")
+    if args.batch < 1:
+        raise SystemExit("--tta: --batch is the number of items per forward, at least 1")
+    return None if args.tta == 1 else {"N": args.tta, "batch": args.batch}
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
@@ -545,6 +576,7 @@ def main(argv=None):
     clean = clean_options(args)
     sweep = sweep_options(args)
     tile = tile_options(args)
+    tta = tta_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -596,7 +628,7 @@ def main(argv=None):
             if tile is not None:                         # native size: one map per image, the stages on a batch of one
                 if gt is not None:
                     gt["items"].append(gt_fut.result())
-                probs, rgb = predict_tiled_image(model, im, args.background_radius, tile, args.batch, density is not None)
+                probs, rgb = predict_tiled_image(model, im, args.background_radius, tile, args.batch, density is not None, tta)
                 if density is not None:
                     density["rgbs"] = [rgb]
                 finish_batch(probs, [(str(img), im.shape[:2])], mask_dir, overlay_dir, args.prob_thresh, args.min_area,
@@ -617,7 +649,7 @@ def main(argv=None):
             meta.append((str(img), osize))
             if len(tensors) == args.batch:
                 run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
+                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep, tta)
                 tensors, meta = [], []
                 if density is not None:
                     density["rgbs"] = []
@@ -627,7 +659,7 @@ def main(argv=None):
                     gt["items"] = []
         if tensors:
             run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
+                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep, tta)
         for f in writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:

@@ -12,7 +12,8 @@ overlapped with backward, unet_dc_segmentation_amd/dp.py), and ``--device_data``
 device, each batch augmented there: unet_dc_segmentation_amd/device_data.py; with ``--crop S`` the cache keeps the images at
 their own size and every batch is S x S random windows).  The numbers of the reference's test section (:365-402, :452-467:
 best checkpoint reloaded, test loss / Dice / pixel accuracy, precision / recall / F1 / specificity / confusion matrix) are
-computed and printed; its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
+computed and printed (with ``--tta N`` on the network's mean over N flipped and rotated variants of every input, as is
+``--calibrate_thresh``: DESIGN.md section 17); its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
 """
 import argparse
 import gc
@@ -65,6 +66,10 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
                         "used and report the Dice-optimal probability threshold among k / K, k = 0..K-1 (K in 1..1024, 100 "
                         "without K; csrc/sweep.hip on the HIP device).  This is Dice POOLED OVER ALL PIXELS of the split, not "
                         "the per-batch mean Dice the epochs print")
+    p.add_argument("--tta", type=int, nargs="?", const=8, default=1, metavar="N",
+                   help="test-time augmentation in the final test evaluation and in --calibrate_thresh only: the network's mean "
+                        "over N flipped and rotated variants of every input (N in 1, 2, 4, 8; 8 without N; DESIGN.md section "
+                        "17), --batch items per forward.  The training and validation loops do not change")
     p.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     return p
 
@@ -146,15 +151,29 @@ def check_crop_flags(args):
 
 class History(list):
     """Per-epoch records of main(); ``.test`` holds the held-out-split results of the final evaluation (None if skipped),
-    ``.calibration`` the result of --calibrate_thresh (None without the flag)."""
+    ``.calibration`` the result of --calibrate_thresh (None without the flag), ``.tta`` the number of variants both were
+    computed with (--tta; 1 = the plain forward)."""
     test = None
     calibration = None
+    tta = 1
 
 
-def evaluate_test(model, loader, criterion, device):
+def predict_eval(model, images, tta, batch):
+    """The probabilities the final evaluations read: the plain forward, or with --tta N the mean over the N variants of every
+    image (unet_dc_segmentation_amd/tta.py on the HIP device, utils/tta.py on the CPU), `batch` items per forward."""
+    if tta == 1:
+        return model(images)
+    if images.is_cuda:
+        from unet_dc_segmentation_amd.tta import predict_tta
+        return predict_tta(model, images, tta, batch)
+    from utils.tta import predict_tta_cpu
+    return predict_tta_cpu(model, images, tta, batch)
+
+
+def evaluate_test(model, loader, criterion, device, tta=1, items=8):
     """The reference's final test pass (train_DC_focal.py:365-402, :452-467) without its image dumps: mean loss and Dice over
     the batches, pixel accuracy over all pixels, and calculate_metrics() on the thresholded predictions.  Sums stay on the
-    device (one read-back), like the training loop's."""
+    device (one read-back), like the training loop's.  tta, items: the number of variants of --tta and of items per forward."""
     model.eval()
     loss_t = torch.zeros((), dtype=torch.float64, device=device)
     dice_t = torch.zeros((), dtype=torch.float64, device=device)
@@ -162,7 +181,7 @@ def evaluate_test(model, loader, criterion, device):
     with torch.no_grad():
         for batch in loader:
             images, masks = batch[0].float().to(device), batch[1].float().to(device)
-            outputs = model(images)
+            outputs = predict_eval(model, images, tta, items)
             loss_t += criterion(outputs, masks).double()
             pred = (outputs > 0.3).float()
             dice_t += dice_coef(masks, pred).double()
@@ -176,18 +195,20 @@ def evaluate_test(model, loader, criterion, device):
                 precision=precision, recall=recall, f1=f1, specificity=specificity, confusion=cm.tolist())
 
 
-def calibrate_threshold(model, loader, K, device):
+def calibrate_threshold(model, loader, K, device, tta=1, items=8):
     """--calibrate_thresh: the pixel confusion matrix of `probabilities > k / K` against the masks (> 0.5) of every batch of
     `loader`, for all k at once (identity geometry, nearest rule).  On the HIP device every batch adds
     into one device histogram (unetdc_thresh_sweep) and the host copies it once; on the CPU utils.threshold_sweep does the
-    same sums.  -> {K, best_dice_threshold, best_dice, average_precision, hist}."""
+    same sums.  tta, items: the number of variants of --tta and of items per forward (a threshold calibrated without --tta is
+    not the one to apply with it).
+    -> {K, best_dice_threshold, best_dice, average_precision, hist}."""
     from utils.threshold_sweep import sweep_hist_numpy, sweep_table
     model.eval()
     hist = None
     with torch.no_grad():
         for batch in loader:
             images, masks = batch[0].float().to(device), batch[1].float().to(device)
-            probs = model(images)[:, 0].float()
+            probs = predict_eval(model, images, tta, items)[:, 0].float()
             gts = (masks[:, 0] > 0.5).to(torch.uint8)
             hw = tuple(gts.shape[1:])
             if probs.is_cuda:
@@ -211,6 +232,9 @@ def main(argv=None, parser=None):
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
+    from utils.tta import TTA_SIZES
+    if args.tta not in TTA_SIZES:
+        raise SystemExit(f"--tta N: N must be one of {', '.join(map(str, TTA_SIZES))}, not {args.tta}")
     rank, local, world = dpmod.init_from_env()
     device = torch.device(args.device if args.device != "cuda" else f"cuda:{local}")
     if args.device_data and device.type != "cuda":
@@ -267,6 +291,7 @@ def main(argv=None, parser=None):
     best_dice, patience_counter = 0.0, 0
     saved_this_run = False          # the final test evaluation only reloads a checkpoint THIS run wrote
     history = History()
+    history.tta = args.tta
     for epoch in range(args.epochs):
         model.train()
         # the per-step metrics of train_DC_focal.py:256-262 are ACCUMULATED ON THE DEVICE (fp64 / int64: the same values added in
@@ -365,10 +390,11 @@ def main(argv=None, parser=None):
         if not args.device_data:
             test_loader = DataLoader(test_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers,
                                      pin_memory=pin)
-        history.test = evaluate_test(model, test_loader, criterion, device)       # every rank: same weights, same split
+        # every rank: same weights, same split
+        history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch)
         if rank == 0:
             t = history.test
-            print("========== Test Results ==========")
+            print("========== Test Results ==========" + (f" (--tta {args.tta})" if args.tta != 1 else ""))
             print(f"Test Loss: {t['test_loss']:.4f}")
             print(f"Test Dice: {t['test_dice']:.4f}")
             print(f"Test Accuracy (pixel-wise): {t['test_acc']:.4f}")
@@ -376,10 +402,12 @@ def main(argv=None, parser=None):
                   f"Specificity: {t['specificity']:.4f}")
             print(f"Confusion matrix [[tn, fp], [fn, tp]]: {t['confusion']}")
     if args.calibrate_thresh is not None and len(val_ds) > 0:
-        history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device)   # every rank: same weights
+        history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device, args.tta,
+                                                    args.batch)             # every rank: same weights
         if rank == 0:
             c = history.calibration
-            print(f"Threshold calibration on the validation split (K = {c['K']}): pooled Dice {c['best_dice']:.4f} at "
+            with_tta = f", --tta {args.tta}" if args.tta != 1 else ""
+            print(f"Threshold calibration on the validation split (K = {c['K']}{with_tta}): pooled Dice {c['best_dice']:.4f} at "
                   f"threshold {c['best_dice_threshold']:.6g}; average precision {c['average_precision']:.4f}")
     if world > 1:
         torch.distributed.barrier()

@@ -102,6 +102,8 @@ SIGNATURES = {
     "unetdc_thresh_sweep": (I, [P, I, I, I, P, I, I, P, P, P, P, I, P, P]),
     "unetdc_tile_gather_u8_to_chw_f32": (I, [P, I, I, I, P, I, P, I, P, I, I, I, P]),
     "unetdc_tile_blend_f32": (I, [P, I, I, P, I, P, I, P, I, I, P]),
+    "unetdc_dihedral_expand_f32": (I, [P, I, I, I, I, P, P]),
+    "unetdc_dihedral_mean_f32": (I, [P, I, I, I, P, P]),
 }
 
 _lib = None

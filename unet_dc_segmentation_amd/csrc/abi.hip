@@ -607,6 +607,14 @@ int unetdc_tile_blend_f32(const float* tile_probs, int t, int overlap, const int
   return launch_tile_blend(tile_probs, t, overlap, yo, ny, xo, nx, out, h, w, (hipStream_t)s);
 }
 
+int unetdc_dihedral_expand_f32(const float* x, int n, int c, int s, int nvar, float* out, unetdc_stream_t stream) {
+  return launch_dihedral_expand(x, n, c, s, nvar, out, (hipStream_t)stream);
+}
+
+int unetdc_dihedral_mean_f32(const float* p, int n, int s, int nvar, float* out, unetdc_stream_t stream) {
+  return launch_dihedral_mean(p, n, s, nvar, out, (hipStream_t)stream);
+}
+
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }
 
 int unetdc_rolling_ball_u8(const uint8_t* src_hwc, uint8_t* dst_hwc, int h, int w, int channels, int ksize, void* workspace,

@@ -32,6 +32,16 @@ __device__ inline void aug_source(int y, int x, int H, int W, int flags, int k, 
   sx = (flags & AUG_HFLIP) ? W - 1 - fx : fx;
 }
 
+// The inverse of aug_source: (sy, sx) in the source image -> (y, x) in the flipped + rotated image
+__device__ inline void aug_dest(int sy, int sx, int H, int W, int flags, int k, int& y, int& x) {
+  const int fy = (flags & AUG_VFLIP) ? H - 1 - sy : sy;
+  const int fx = (flags & AUG_HFLIP) ? W - 1 - sx : sx;
+  y = fy; x = fx;
+  if (k == 1) { y = W - 1 - fx; x = fy; }
+  else if (k == 2) { y = H - 1 - fy; x = W - 1 - fx; }
+  else if (k == 3) { y = fx; x = H - 1 - fy; }
+}
+
 // p: an AugRecord or a CropRecord (flags, alpha, beta_max)
 template <class Record>
 __device__ inline float aug_bc(float v, const Record& p) {

@@ -285,6 +285,11 @@ int launch_tile_gather(const unsigned char* src, int h, int w, int cn, float* ti
 int launch_tile_blend(const float* tiles, int t, int overlap, const int* yo, int ny, const int* xo, int nx, float* out, int h,
                       int w, hipStream_t stream);
 
+// tta.hip: the D4 variants of a batch of square planes and the mean of the outputs mapped back (DESIGN.md section 17;
+// include/unetdc_hip.h)
+int launch_dihedral_expand(const float* x, int n, int c, int s, int nvar, float* out, hipStream_t stream);
+int launch_dihedral_mean(const float* p, int n, int s, int nvar, float* out, hipStream_t stream);
+
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).
 constexpr int AUG_HFLIP = 1, AUG_VFLIP = 2, AUG_BC = 4;

@@ -108,13 +108,19 @@ def blend_numpy64(tiles, h, w, T, O):
     return _blend(tiles, h, w, T, O, np.float64)
 
 
-def predict_tiled_cpu(model, img_u8, T, O, batch):
+def predict_tiled_cpu(model, img_u8, T, O, batch, tta=1):
     """CPU path of unet_dc_segmentation_amd.tiling.predict_tiled: img_u8 [H, W, C] uint8 (numpy) -> fp32 [H, W] probabilities
-    (numpy): the tiles of gather_numpy through `model` in chunks of `batch` under no_grad, then blend_numpy."""
+    (numpy): the tiles of gather_numpy through `model` in chunks of `batch` under no_grad, then blend_numpy.  tta > 1: every
+    tile's probabilities are the mean over its `tta` flipped and rotated variants (utils.tta.predict_tta_cpu, `batch` items per
+    forward) before the blend."""
     import torch
     img_u8 = np.asarray(img_u8)
     tiles = torch.from_numpy(gather_numpy(img_u8, T, O))
     batch = max(1, int(batch))
-    with torch.no_grad():
-        probs = torch.cat([model(tiles[i:i + batch])[:, 0] for i in range(0, len(tiles), batch)])
+    if tta != 1:
+        from utils.tta import predict_tta_cpu
+        probs = predict_tta_cpu(model, tiles, tta, batch)[:, 0]
+    else:
+        with torch.no_grad():
+            probs = torch.cat([model(tiles[i:i + batch])[:, 0] for i in range(0, len(tiles), batch)])
     return blend_numpy(probs.numpy(), img_u8.shape[0], img_u8.shape[1], T, O)
