@@ -389,6 +389,39 @@ int unetdc_crop_gather(const uint8_t* images_u8, int64_t images_bytes, const uin
                        int S, const unetdc_crop_params* records, int n, const float* fields, int nfields, float* out_img,
                        float* out_mask, unetdc_stream_t s);
 
+/* unetdc_crop_gather_scaled: unetdc_crop_gather with scale jitter.  Sample i cuts the t x t SOURCE window at (y0, x0) of its
+ *   image (the window rule above with t in place of S) and resamples it to the S x S lattice in the same pass:
+ *   - image: OpenCV's 8-bit INTER_LINEAR, as utils.data_loader.resize_linear_cv2_u8(window, S, S).  Per lattice coordinate d
+ *     the taps of linear_tables(t, S): f = (d + 0.5) * (double(t) / double(S)) - 0.5 in double (two roundings, no FMA), first
+ *     tap floor(f), coefficients rint((1.0f - float(frac)) * 2048) and rint(float(frac) * 2048).  Along x a first tap below 0
+ *     or at / above t - 1 becomes one tap of weight 2048; along y both taps are clamped to 0..t-1 and keep their weights.
+ *     Then r = p0 * a0 + p1 * a1 per source row and v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, all in
+ *     int32, and the lattice value float(v) / 255.0f.  The resize acts in the window's own orientation, before flips / rot90.
+ *   - mask: the source mask at min(floor(d * (double(t) / double(S))), t - 1) on both axes (INTER_NEAREST).
+ *   The output is what unetdc_crop_gather makes of that lattice (flips, rot90, brightness / contrast, elastic with the four
+ *   bilinear lattice taps and the nearest mask tap; a lattice tap is a scaled pixel: 4 source bytes per channel, 16 with a
+ *   field).  utils/crops.py:crop_gather_scaled_numpy is the same rule on the host, bit-equal without elastic; with t == S the
+ *   outputs are those of unetdc_crop_gather bit for bit.  Records by value, nothing but the two outputs is written, no
+ *   workspace, no allocation, no host wait, no atomics; launches on the given stream only.
+ *   UNETDC_EINVAL before any launch: everything unetdc_crop_gather refuses, with y0 / x0 taken against 0..max(side - t, 0),
+ *   and t outside S / 2 .. 2 S.  Every tap is clamped to the window and then folded into the image, so every read of an
+ *   accepted record lies inside its image. */
+typedef struct unetdc_crop_scaled_params {
+  int64_t img_off;      /* as unetdc_crop_params */
+  int64_t mask_off;
+  int32_t h, w;
+  int32_t y0, x0;       /* origin of the t x t source window */
+  int32_t flags;
+  int32_t k;
+  int32_t field;
+  float alpha;
+  float beta_max;
+  int32_t t;            /* side of the source window, S / 2 .. 2 S (where unetdc_crop_params has `reserved`) */
+} unetdc_crop_scaled_params;
+int unetdc_crop_gather_scaled(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes,
+                              int channels, int S, const unetdc_crop_scaled_params* records, int n, const float* fields,
+                              int nfields, float* out_img, float* out_mask, unetdc_stream_t s);
+
 
 /* ---- radial and spatial droplet density maps (the reference's quantify_pipline.py:44-142 restated; density.hip) ---------
  * unetdc_density_maps: for one image of h x w pixels (both sides >= UNETDC_DENSITY_MIN_SIDE):

@@ -8,7 +8,10 @@ threshold), three arms (four with --crop), each in a fresh child process, bf16, 
                                                        and augmented per batch; S = 512 has the step shapes of device_data)
 Prints the per-epoch training img/s of every arm and one JSON line with the mean from epoch 2 on.
 
-    python tools/train_e2e.py [N] [--epochs E] [--cpu_steps S] [--crop[=S]] [--only ARM [--only ARM ...]]
+    python tools/train_e2e.py [N] [--epochs E] [--cpu_steps S] [--crop[=S]] [--crop_scale LO HI] [--crop_fg P]
+                              [--only ARM [--only ARM ...]]
+
+--crop_scale / --crop_fg are passed through to every run of the crop arm (scale jitter and foreground-aware windows).
 
 --only may be repeated, also with one arm twice (two runs of one arm in one job give the run-to-run spread): the second run
 of an arm is reported as ARM_run2."""
@@ -44,7 +47,7 @@ def write_pairs(d, n):
     return ind, md
 
 
-def run_arm(arm, n, ind, md, epochs, cpu_steps, d, crop=512):
+def run_arm(arm, n, ind, md, epochs, cpu_steps, d, crop=512, crop_flags=()):
     common = ["--dtype", "bf16", "--batch", "8", "--epochs", str(epochs), "--patience", str(epochs + 1), "--no_test_eval",
               "--ckpt_path", os.path.join(d, f"{arm}.pth")]
     if arm == "synthetic":
@@ -52,7 +55,7 @@ def run_arm(arm, n, ind, md, epochs, cpu_steps, d, crop=512):
     elif arm == "device_data":
         extra = ["--image_dir", ind, "--mask_dir", md, "--device_data"]
     elif arm == CROP_ARM:
-        extra = ["--image_dir", ind, "--mask_dir", md, "--device_data", "--crop", str(crop)]
+        extra = ["--image_dir", ind, "--mask_dir", md, "--device_data", "--crop", str(crop), *crop_flags]
     else:
         extra = ["--image_dir", ind, "--mask_dir", md, "--steps", str(cpu_steps), "--workers", "4"]
     cmd = [sys.executable, os.path.join(ROOT, "train_DC_focal.py"), *common, *extra]
@@ -71,17 +74,25 @@ def main():
     ap.add_argument("--cpu_steps", type=int, default=3)
     ap.add_argument("--crop", type=int, nargs="?", const=512, default=None, metavar="S",
                     help="also run the crop arm (train_DC_focal.py --device_data --crop S; 512 without S)")
+    ap.add_argument("--crop_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="crop arm: --crop_scale LO HI")
+    ap.add_argument("--crop_fg", type=float, default=None, metavar="P", help="crop arm: --crop_fg P")
     ap.add_argument("--only", choices=ARMS + (CROP_ARM,), action="append")
     a = ap.parse_args()
     res = {"n_pairs": a.n, "epochs": a.epochs, "batch": 8, "dtype": "bf16", "cpu_loader_steps_per_epoch": a.cpu_steps}
     crop = 512 if a.crop is None else a.crop
     arms = a.only or (ARMS + ((CROP_ARM,) if a.crop is not None else ()))
+    crop_flags = []
+    if a.crop_scale is not None:
+        crop_flags += ["--crop_scale", *(repr(v) for v in a.crop_scale)]
+    if a.crop_fg is not None:
+        crop_flags += ["--crop_fg", repr(a.crop_fg)]
     if CROP_ARM in arms:
         res["crop"] = crop
+        res["crop_flags"] = crop_flags
     with tempfile.TemporaryDirectory() as d:
         ind, md = write_pairs(d, a.n)
         for j, arm in enumerate(arms):
-            ips = run_arm(arm, a.n, ind, md, a.epochs, a.cpu_steps, d, crop)
+            ips = run_arm(arm, a.n, ind, md, a.epochs, a.cpu_steps, d, crop, crop_flags)
             runs = list(arms[:j]).count(arm)
             key = arm if not runs else f"{arm}_run{runs + 1}"
             res[f"{key}_img_per_s_by_epoch"] = ips

@@ -57,6 +57,14 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
                         "--img_size is not used")
     p.add_argument("--crops_per_image", type=int, default=1, metavar="R",
                    help="with --crop: R random windows of every training image per epoch (default 1)")
+    p.add_argument("--crop_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="with --crop: scale jitter.  Every training window is cut with a source side T drawn uniformly from the "
+                        "integers ceil(LO * S) .. floor(HI * S) and resampled to S x S in the crop kernel (8-bit bilinear, masks "
+                        "nearest); 0.5 <= LO <= 1 <= HI <= 2, default off.  Validation, test and --calibrate_thresh stay at "
+                        "scale 1")
+    p.add_argument("--crop_fg", type=float, default=0.0, metavar="P",
+                   help="with --crop: with probability P a training window is placed so that it contains a uniformly chosen "
+                        "foreground pixel of its image, otherwise uniformly as without the flag; 0 <= P <= 1, default 0")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -116,10 +124,10 @@ def make_device_loaders(args, rank, world, device):
         ids = list(range(rank, per_rank * world, world))
     if args.crop is not None:
         from unet_dc_segmentation_amd.device_data import DeviceCropEvalLoader, DeviceCropTrainLoader, DeviceNativeCache
-        native = lambda names, masks: DeviceNativeCache(args.image_dir, args.mask_dir, names, device=device,  # noqa: E731
-                                                        mask_names=masks)
-        train = DeviceCropTrainLoader(native([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.crop,
-                                      args.seed, ids, args.crops_per_image)
+        native = lambda names, masks, fg=False: DeviceNativeCache(args.image_dir, args.mask_dir, names,  # noqa: E731
+                                                                  device=device, mask_names=masks, keep_foreground=fg)
+        train = DeviceCropTrainLoader(native([tr[0][i] for i in ids], [tr[1][i] for i in ids], args.crop_fg > 0), args.batch,
+                                      args.crop, args.seed, ids, args.crops_per_image, scale=args.crop_scale, p_fg=args.crop_fg)
         return (train, DeviceCropEvalLoader(native(*va), args.batch, args.crop),
                 DeviceCropEvalLoader(native(*te), args.batch, args.crop))
     cache = lambda names, masks: DeviceImageCache(args.image_dir, args.mask_dir, names, args.img_size,  # noqa: E731
@@ -129,12 +137,22 @@ def make_device_loaders(args, rank, world, device):
 
 
 def check_crop_flags(args):
-    """--crop / --crops_per_image: every refusal is raised here, before any file is read."""
+    """--crop / --crops_per_image / --crop_scale / --crop_fg: every refusal is raised here, before any file is read."""
+    from utils.crops import MAX_CROP, MAX_SCALE, MIN_CROP, MIN_SCALE
+    if args.crop_scale is not None:
+        lo, hi = args.crop_scale
+        if not (MIN_SCALE <= lo <= 1.0 <= hi <= MAX_SCALE):              # (also refuses LO > HI and a NaN)
+            raise SystemExit(f"--crop_scale LO HI: {MIN_SCALE} <= LO <= 1 <= HI <= {MAX_SCALE}, not {lo} {hi}")
+    if not 0.0 <= args.crop_fg <= 1.0:
+        raise SystemExit(f"--crop_fg P: P must be in 0..1, not {args.crop_fg}")
     if args.crop is None:
         if args.crops_per_image != 1:
             raise SystemExit("--crops_per_image needs --crop")
+        if args.crop_scale is not None:
+            raise SystemExit("--crop_scale needs --crop")
+        if args.crop_fg != 0.0:
+            raise SystemExit("--crop_fg needs --crop")
         return
-    from utils.crops import MAX_CROP, MIN_CROP
     if args.crop % 16 or not MIN_CROP <= args.crop <= MAX_CROP:
         raise SystemExit(f"--crop S: S must be a multiple of 16 in {MIN_CROP}..{MAX_CROP}, not {args.crop}")
     if args.crops_per_image < 1:
@@ -284,6 +302,12 @@ def main(argv=None, parser=None):
     if rank == 0 and args.crop is not None:
         print(f"--crop {args.crop}: {train_loader.samples} random {args.crop} x {args.crop} windows/rank and epoch at native "
               f"resolution, {len(val_loader.windows)} validation windows; --img_size {args.img_size} is not used")
+        if train_loader.scaled:
+            from utils.crops import t_range
+            tlo, thi = t_range(args.crop, args.crop_scale) if args.crop_scale is not None else (args.crop, args.crop)
+            print(f"--crop_scale / --crop_fg: source windows of side T in {tlo}..{thi} resampled to {args.crop} x {args.crop} "
+                  f"on the device, a window placed on a foreground pixel with probability P = {args.crop_fg:g}; validation "
+                  f"and test at scale 1")
     if rank == 0:
         print(f"Training set: {len(train_ds)} images/rank, validation set: {len(val_ds)} images, "
               f"{world} rank(s), device {device}, compute {args.dtype}")
@@ -352,6 +376,8 @@ def main(argv=None, parser=None):
         rec = dict(epoch=epoch + 1, train_loss=tr_loss / nb, val_loss=va_loss / nv, train_dice=tr_dice / nb,
                    val_dice=va_dice / nv, train_acc=correct / max(total, 1), val_acc=vc / max(vt, 1),
                    images_per_sec=seen * world / max(dt, 1e-9))
+        if args.crop is not None and train_loader.scaled:
+            rec["fg_windows"] = int(train_loader.fg_windows)              # (this rank's windows)
         if world > 1:
             # replicas must stay identical: one checksum per rank and epoch (compared by tests/test_dp_gloo.py)
             with torch.no_grad():
@@ -364,6 +390,8 @@ def main(argv=None, parser=None):
             print(f"Epoch {epoch + 1}/{args.epochs} | Train Loss: {rec['train_loss']:.4f}, Val Loss: {rec['val_loss']:.4f}, "
                   f"Train Dice: {rec['train_dice']:.4f}, Val Dice: {rec['val_dice']:.4f}")
             print(f"Train Acc: {rec['train_acc']:.4f}, Val Acc: {rec['val_acc']:.4f} | {rec['images_per_sec']:.1f} img/s")
+            if "fg_windows" in rec:
+                print(f"Foreground-centred windows: {rec['fg_windows']} of {seen}")
             print("-------------------------------------------------------")
         if rec["val_dice"] > best_dice:
             best_dice, patience_counter = rec["val_dice"], 0

@@ -86,6 +86,7 @@ SIGNATURES = {
     "unetdc_elastic_fields": (I, [P, I, I, I, D, F, P, P, L, P]),
     "unetdc_augment_gather": (I, [P, P, I, I, I, I, P, I, P, I, P, P, P]),
     "unetdc_crop_gather": (I, [P, L, P, L, I, I, P, I, P, I, P, P, P]),
+    "unetdc_crop_gather_scaled": (I, [P, L, P, L, I, I, P, I, P, I, P, P, P]),
     "unetdc_density_workspace": (L, [I, I]),
     "unetdc_density_maps": (I, [P, P, I, I, P, P, P, P, I, I, D, P, P, L, P, P, P, P, P, P, P, P, P]),
     "unetdc_density_sqrt": (I, [P, P, L, P]),

@@ -15,6 +15,9 @@ CROP_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("
                        ("flags", "<i4"), ("k", "<i4"), ("field", "<i4"), ("alpha", "<f4"), ("beta_max", "<f4"),
                        ("reserved", "<i4")])
 assert CROP_DTYPE.itemsize == 56
+# unetdc_crop_scaled_params: the same record with the side t of the source window where unetdc_crop_params has `reserved`
+CROP_SCALED_DTYPE = np.dtype([(n, CROP_DTYPE.fields[n][0]) for n in CROP_DTYPE.names[:-1]] + [("t", "<i4")])
+assert CROP_SCALED_DTYPE.itemsize == 56 and CROP_SCALED_DTYPE.fields["t"][1] == CROP_DTYPE.fields["reserved"][1]
 
 IDENTITY = dict(hflip=False, vflip=False, k=0, bc=False, alpha=1.0, beta=0.0, elastic=False, field_seed=0)
 
@@ -22,7 +25,19 @@ IDENTITY = dict(hflip=False, vflip=False, k=0, bc=False, alpha=1.0, beta=0.0, el
 def pack_crops(params, img_off, mask_off, sizes, origins, img_max):
     """[augment.draw_params dicts] + per-sample byte offsets, (h, w), (y0, x0) and whole-image maxima -> (unetdc_crop_params
     records, field seeds): the samples that draw elastic get field slots 0, 1, ... in batch order."""
-    rec = np.zeros(len(params), dtype=CROP_DTYPE)
+    return _pack(CROP_DTYPE, params, img_off, mask_off, sizes, origins, img_max)
+
+
+def pack_crops_scaled(params, img_off, mask_off, sizes, origins, img_max, ts):
+    """pack_crops for unetdc_crop_gather_scaled: `origins` are those of the source windows, `ts` their sides ->
+    (unetdc_crop_scaled_params records, field seeds)."""
+    rec, seeds = _pack(CROP_SCALED_DTYPE, params, img_off, mask_off, sizes, origins, img_max)
+    rec["t"] = np.asarray(ts, dtype=np.int32).reshape(len(params))
+    return rec, seeds
+
+
+def _pack(dtype, params, img_off, mask_off, sizes, origins, img_max):
+    rec = np.zeros(len(params), dtype=dtype)
     seeds = []
     for i, p in enumerate(params):
         r = rec[i]
@@ -42,10 +57,23 @@ def pack_crops(params, img_off, mask_off, sizes, origins, img_max):
 def crop_gather(images_u8, masks_u8, channels, S, rec, fields=None, out_img=None, out_mask=None):
     """images_u8 / masks_u8: flat uint8 device tensors holding every cached image (HWC) / mask back to back; rec: CROP_DTYPE
     records (host) -> (images [N, C, S, S], masks [N, 1, S, S]) float32 on the device."""
+    return _gather("unetdc_crop_gather", CROP_DTYPE, images_u8, masks_u8, channels, S, rec, fields, out_img, out_mask)
+
+
+def crop_gather_scaled(images_u8, masks_u8, channels, S, rec, fields=None, out_img=None, out_mask=None):
+    """crop_gather with CROP_SCALED_DTYPE records: every sample's rec["t"] x rec["t"] source window is resampled to S x S in
+    the same kernel pass (unetdc_crop_gather_scaled; the rule: utils.crops.window_scaled)."""
+    return _gather("unetdc_crop_gather_scaled", CROP_SCALED_DTYPE, images_u8, masks_u8, channels, S, rec, fields, out_img,
+                   out_mask)
+
+
+def _gather(symbol, dtype, images_u8, masks_u8, channels, S, rec, fields, out_img, out_mask):
     for t, what in ((images_u8, "images_u8"), (masks_u8, "masks_u8")):
         if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 1 and t.is_contiguous()):
             raise _lib.UnetdcError(f"crop_gather: {what} must be a flat contiguous uint8 tensor on the HIP device")
-    rec = np.ascontiguousarray(rec, dtype=CROP_DTYPE)
+    if getattr(rec, "dtype", dtype) != dtype:               # (a cast between the two record types would go by position)
+        raise _lib.UnetdcError(f"{symbol}: records of another type (its own has {', '.join(dtype.names)})")
+    rec = np.ascontiguousarray(rec, dtype=dtype)
     n, c, S = len(rec), int(channels), int(S)
     dev = images_u8.device
     if out_img is None:
@@ -60,7 +88,7 @@ def crop_gather(images_u8, masks_u8, channels, S, rec, fields=None, out_img=None
         if tuple(fields.shape[1:]) != (2, S, S) or fields.dtype != torch.float32 or not fields.is_contiguous():
             raise _lib.UnetdcError("crop_gather: fields must be [n, 2, S, S] float32")
         nfields = fields.shape[0]
-    _lib.call("unetdc_crop_gather", images_u8.data_ptr(), images_u8.numel(), masks_u8.data_ptr(), masks_u8.numel(), c, S,
+    _lib.call(symbol, images_u8.data_ptr(), images_u8.numel(), masks_u8.data_ptr(), masks_u8.numel(), c, S,
               rec.ctypes.data, n, fields.data_ptr() if fields is not None else None, nfields, out_img.data_ptr(),
               out_mask.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return out_img, out_mask

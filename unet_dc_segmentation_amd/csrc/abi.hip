@@ -664,6 +664,23 @@ int unetdc_crop_gather(const uint8_t* images_u8, int64_t images_bytes, const uin
                             reinterpret_cast<const CropRecord*>(records), n, fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
+static_assert(sizeof(unetdc_crop_scaled_params) == 56 && sizeof(unetdc_crop_scaled_params) == sizeof(unetdc::CropScaledRecord) &&
+                  offsetof(unetdc_crop_scaled_params, mask_off) == offsetof(unetdc::CropScaledRecord, mask_off) &&
+                  offsetof(unetdc_crop_scaled_params, y0) == offsetof(unetdc::CropScaledRecord, y0) &&
+                  offsetof(unetdc_crop_scaled_params, field) == offsetof(unetdc::CropScaledRecord, field) &&
+                  offsetof(unetdc_crop_scaled_params, beta_max) == offsetof(unetdc::CropScaledRecord, beta_max) &&
+                  offsetof(unetdc_crop_scaled_params, t) == offsetof(unetdc::CropScaledRecord, t) &&
+                  offsetof(unetdc_crop_scaled_params, t) == offsetof(unetdc_crop_params, reserved),
+              "unetdc_crop_scaled_params, CropScaledRecord and unetdc_crop_params must share one layout");
+
+int unetdc_crop_gather_scaled(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes,
+                              int channels, int S, const unetdc_crop_scaled_params* records, int n, const float* fields,
+                              int nfields, float* out_img, float* out_mask, unetdc_stream_t s) {
+  return launch_crop_gather_scaled(images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
+                                   reinterpret_cast<const CropScaledRecord*>(records), n, fields, nfields, out_img, out_mask,
+                                   (hipStream_t)s);
+}
+
 int64_t unetdc_density_workspace(int h, int w) { return density_workspace_bytes(h, w); }
 
 static_assert(sizeof(unetdc_density_stats) == 1088 && offsetof(unetdc_density_stats, max_ring_distance) == 40 &&

@@ -318,6 +318,17 @@ struct CropRecord {
 int launch_crop_gather(const unsigned char* images, long images_bytes, const unsigned char* masks, long masks_bytes, int c, int s,
                        const CropRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
                        hipStream_t stream);
+// the same with a T x T source window resampled to S x S (scale jitter): CropRecord with the source side t in place of
+// `reserved`; the layout of the public unetdc_crop_scaled_params
+struct CropScaledRecord {
+  long long img_off, mask_off;
+  int h, w, y0, x0, flags, k, field;
+  float alpha, beta_max;
+  int t;
+};
+int launch_crop_gather_scaled(const unsigned char* images, long images_bytes, const unsigned char* masks, long masks_bytes, int c,
+                              int s, const CropScaledRecord* params, int n, const float* fields, int nfields, float* out_img,
+                              float* out_mask, hipStream_t stream);
 
 // preprocess.hip: rolling-ball correction + bilinear resize to the network input
 long rolling_ball_workspace_bytes(int h, int w, int cn);
