@@ -203,6 +203,32 @@ def test_gather_elastic_across_chunks_and_long_displacements(case):
     assert slot == len(seeds) and (case != "chunks" or slot > fx.FIELDS_MAX_SEEDS)
 
 
+def test_gather_elastic_on_a_non_square_image():
+    """The elastic branch with H != W (24 x 40): the taps reflect at the border of their OWN axis.  An odd k is refused on a
+    non-square image, so k is 0 or 2; both flips and brightness / contrast are on in two records each.  sigma = 3, alpha = 40
+    (the values of the crop tests for small windows) move rows past both borders of the 24-row axis."""
+    from unet_dc_segmentation_amd.augment import pack_params
+    h, w, sigma, alpha = 24, 40, 3.0, 40.0
+    imgs, masks, ci, cm = _cache(2, h, w, seed=31)
+    ps = [dict(hflip=bool(j & 1), vflip=bool(j & 2), k=(0, 2, 2, 0)[j], bc=j in (1, 2), alpha=(1.0, 1.15, 0.85, 1.0)[j],
+               beta=(0.0, -0.1, 0.12, 0.0)[j], elastic=True, field_seed=(1, 2, 2, 1)[j]) for j in range(4)]
+    src = [0, 1, 0, 1]
+    rec, seeds = pack_params(ps, src, [float(imgs[s].max()) for s in src])
+    assert list(seeds) == [1, 2, 2, 1] and list(rec["field"]) == [0, 1, 2, 3]
+    fields = _fields_canaried(seeds, h, w, sigma, alpha)
+    oi, om = _gather_canaried(ci, cm, rec, fields)
+    fh = fields.cpu().numpy().astype(np.float64)
+    yy, xx = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    for j, p in enumerate(ps):
+        dx, dy = fh[j]
+        for c, want in enumerate(ref.fields(p["field_seed"], h, w, sigma, alpha)):
+            assert np.abs(fh[j, c] - want).max() <= 1e-5 * np.abs(want).max(), (j, c)
+        if p["field_seed"] == 1:
+            assert (yy + dy).min() < -1 and (yy + dy).max() > h and ((xx + dx).min() < -1 or (xx + dx).max() > w)
+        ei, em = _expected(imgs, masks, src[j], p, dx, dy)
+        _assert_elastic_sample(oi[j], om[j], ei, em, dx, dy, (j, p))
+
+
 def test_long_displacements_match_map_coordinates_directly():
     """The long-displacement fixture once more without flips, rotation or brightness, against a plain
     scipy.ndimage.map_coordinates call (no code of augment_ref between the kernel and SciPy)."""

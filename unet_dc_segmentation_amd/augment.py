@@ -36,21 +36,27 @@ def draw_params(seed, epoch, index):
     return p
 
 
-def pack_params(params, src, img_max):
-    """[dict from draw_params] + cache indices + per-image maxima -> (unetdc_augment_params records, field seeds): the
-    samples that draw elastic get field slots 0, 1, ... in batch order."""
-    rec = np.zeros(len(params), dtype=PARAMS_DTYPE)
+def pack_draws(rec, params, img_max):
+    """Fill flags, k, alpha, beta_max and field of the records `rec` (PARAMS_DTYPE or one of crops' record types) from the
+    draw_params dicts and per-image maxima -> field seeds: the samples that draw elastic get field slots 0, 1, ... in batch
+    order."""
     seeds = []
-    for i, (p, s, mx) in enumerate(zip(params, src, img_max)):
-        rec[i]["src"] = s
-        rec[i]["flags"] = (HFLIP if p["hflip"] else 0) | (VFLIP if p["vflip"] else 0) | (BC if p["bc"] else 0)
-        rec[i]["k"] = p["k"]
-        rec[i]["alpha"] = np.float32(p["alpha"])
-        rec[i]["beta_max"] = np.float32(p["beta"] * float(mx))            # formed in double, like beta * float(img.max())
-        rec[i]["field"] = len(seeds) if p["elastic"] else -1
+    for r, p, mx in zip(rec, params, img_max):
+        r["flags"] = (HFLIP if p["hflip"] else 0) | (VFLIP if p["vflip"] else 0) | (BC if p["bc"] else 0)
+        r["k"] = p["k"]
+        r["alpha"] = np.float32(p["alpha"])
+        r["beta_max"] = np.float32(p["beta"] * float(mx))                 # formed in double, like beta * float(img.max())
+        r["field"] = len(seeds) if p["elastic"] else -1
         if p["elastic"]:
             seeds.append(p["field_seed"])
-    return rec, np.asarray(seeds, dtype=np.uint32)
+    return np.asarray(seeds, dtype=np.uint32)
+
+
+def pack_params(params, src, img_max):
+    """[dict from draw_params] + cache indices + per-image maxima -> (unetdc_augment_params records, field seeds)."""
+    rec = np.zeros(len(params), dtype=PARAMS_DTYPE)
+    rec["src"] = np.asarray(src, dtype=np.int32).reshape(len(params))
+    return rec, pack_draws(rec, params, img_max)
 
 
 def fields_workspace_bytes(n, h, w, sigma=ELASTIC_SIGMA):

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .augment import BC, HFLIP, VFLIP
+from .augment import pack_draws
 
 # unetdc_crop_params: int64 img_off, mask_off; int32 h, w, y0, x0, flags, k, field; float32 alpha, beta_max; int32 reserved
 CROP_DTYPE = np.dtype([("img_off", "<i8"), ("mask_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("y0", "<i4"), ("x0", "<i4"),
@@ -38,20 +38,9 @@ def pack_crops_scaled(params, img_off, mask_off, sizes, origins, img_max, ts):
 
 def _pack(dtype, params, img_off, mask_off, sizes, origins, img_max):
     rec = np.zeros(len(params), dtype=dtype)
-    seeds = []
-    for i, p in enumerate(params):
-        r = rec[i]
-        r["img_off"], r["mask_off"] = img_off[i], mask_off[i]
-        r["h"], r["w"] = sizes[i]
-        r["y0"], r["x0"] = origins[i]
-        r["flags"] = (HFLIP if p["hflip"] else 0) | (VFLIP if p["vflip"] else 0) | (BC if p["bc"] else 0)
-        r["k"] = p["k"]
-        r["alpha"] = np.float32(p["alpha"])
-        r["beta_max"] = np.float32(p["beta"] * float(img_max[i]))         # formed in double, like beta * float(img.max())
-        r["field"] = len(seeds) if p["elastic"] else -1
-        if p["elastic"]:
-            seeds.append(p["field_seed"])
-    return rec, np.asarray(seeds, dtype=np.uint32)
+    for r, io, mo, (h, w), (y0, x0) in zip(rec, img_off, mask_off, sizes, origins):
+        r["img_off"], r["mask_off"], r["h"], r["w"], r["y0"], r["x0"] = io, mo, h, w, y0, x0
+    return rec, pack_draws(rec, params, img_max)
 
 
 def crop_gather(images_u8, masks_u8, channels, S, rec, fields=None, out_img=None, out_mask=None):

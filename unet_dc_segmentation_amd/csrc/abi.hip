@@ -650,35 +650,33 @@ int unetdc_augment_gather(const float* cache_img, const uint8_t* cache_mask, int
                                fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
-static_assert(sizeof(unetdc_crop_params) == 56 && sizeof(unetdc_crop_params) == sizeof(unetdc::CropRecord) &&
+// both public crop records are views of the one internal CropRecord: unetdc_crop_params names the last word `reserved`,
+// unetdc_crop_scaled_params `t`
+static_assert(sizeof(unetdc_crop_params) == 56 && sizeof(unetdc_crop_scaled_params) == 56 && sizeof(unetdc::CropRecord) == 56 &&
                   offsetof(unetdc_crop_params, mask_off) == offsetof(unetdc::CropRecord, mask_off) &&
                   offsetof(unetdc_crop_params, y0) == offsetof(unetdc::CropRecord, y0) &&
                   offsetof(unetdc_crop_params, field) == offsetof(unetdc::CropRecord, field) &&
-                  offsetof(unetdc_crop_params, beta_max) == offsetof(unetdc::CropRecord, beta_max),
-              "unetdc_crop_params and CropRecord must share one layout");
+                  offsetof(unetdc_crop_params, beta_max) == offsetof(unetdc::CropRecord, beta_max) &&
+                  offsetof(unetdc_crop_params, reserved) == offsetof(unetdc::CropRecord, t) &&
+                  offsetof(unetdc_crop_scaled_params, mask_off) == offsetof(unetdc::CropRecord, mask_off) &&
+                  offsetof(unetdc_crop_scaled_params, y0) == offsetof(unetdc::CropRecord, y0) &&
+                  offsetof(unetdc_crop_scaled_params, field) == offsetof(unetdc::CropRecord, field) &&
+                  offsetof(unetdc_crop_scaled_params, beta_max) == offsetof(unetdc::CropRecord, beta_max) &&
+                  offsetof(unetdc_crop_scaled_params, t) == offsetof(unetdc::CropRecord, t),
+              "unetdc_crop_params, unetdc_crop_scaled_params and CropRecord must share one layout");
 
 int unetdc_crop_gather(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes, int channels,
                        int S, const unetdc_crop_params* records, int n, const float* fields, int nfields, float* out_img,
                        float* out_mask, unetdc_stream_t s) {
-  return launch_crop_gather(images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
+  return launch_crop_gather("crop_gather", false, images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
                             reinterpret_cast<const CropRecord*>(records), n, fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
-
-static_assert(sizeof(unetdc_crop_scaled_params) == 56 && sizeof(unetdc_crop_scaled_params) == sizeof(unetdc::CropScaledRecord) &&
-                  offsetof(unetdc_crop_scaled_params, mask_off) == offsetof(unetdc::CropScaledRecord, mask_off) &&
-                  offsetof(unetdc_crop_scaled_params, y0) == offsetof(unetdc::CropScaledRecord, y0) &&
-                  offsetof(unetdc_crop_scaled_params, field) == offsetof(unetdc::CropScaledRecord, field) &&
-                  offsetof(unetdc_crop_scaled_params, beta_max) == offsetof(unetdc::CropScaledRecord, beta_max) &&
-                  offsetof(unetdc_crop_scaled_params, t) == offsetof(unetdc::CropScaledRecord, t) &&
-                  offsetof(unetdc_crop_scaled_params, t) == offsetof(unetdc_crop_params, reserved),
-              "unetdc_crop_scaled_params, CropScaledRecord and unetdc_crop_params must share one layout");
 
 int unetdc_crop_gather_scaled(const uint8_t* images_u8, int64_t images_bytes, const uint8_t* masks_u8, int64_t masks_bytes,
                               int channels, int S, const unetdc_crop_scaled_params* records, int n, const float* fields,
                               int nfields, float* out_img, float* out_mask, unetdc_stream_t s) {
-  return launch_crop_gather_scaled(images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
-                                   reinterpret_cast<const CropScaledRecord*>(records), n, fields, nfields, out_img, out_mask,
-                                   (hipStream_t)s);
+  return launch_crop_gather("crop_gather_scaled", true, images_u8, (long)images_bytes, masks_u8, (long)masks_bytes, channels, S,
+                            reinterpret_cast<const CropRecord*>(records), n, fields, nfields, out_img, out_mask, (hipStream_t)s);
 }
 
 int64_t unetdc_density_workspace(int h, int w) { return density_workspace_bytes(h, w); }

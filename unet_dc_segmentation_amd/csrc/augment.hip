@@ -14,7 +14,8 @@
 // come through scalar loads (uniform over the wave).  The row pass builds its noise rows in LDS straight from the hash; the
 // column pass reads the row-pass result with lanes along x (coalesced) and a window along y.
 //
-// Gather (augment_gather_kernel): one thread per output pixel, all channels and the mask.  Flips and rotation are an index
+// Gather (augment_gather_kernel: gather_pixel of gather_index.h on the cache, the body the crop kernels of crop.hip run on
+// their windows): one thread per output pixel, all channels and the mask.  Flips and rotation are an index
 // permutation; brightness / contrast is applied per source tap BEFORE interpolation (the CPU path clips, then warps) as
 // __fadd_rn(__fmul_rn(alpha32, x), b32): numpy's float32 arithmetic for `alpha * img + beta * max` (NEP 50 weak scalars,
 // beta * max formed in double on the host), so without elastic the output is bit-exact.  Elastic taps take their integer
@@ -163,7 +164,16 @@ __global__ __launch_bounds__(256) void elastic_cols_kernel(int slot0, int H, int
     if (y0 + i < H) out[(long)(y0 + i) * W] = alpha * acc[i];
 }
 
-// aug_reflect, aug_source and aug_bc: gather_index.h (shared with crop.hip)
+// The cache as a lattice of gather_pixel (gather_index.h): planar float32 images [C][H][W], one mask byte per pixel
+struct CacheLattice {
+  const float* img;
+  const unsigned char* msk;
+  long hw;
+  int W;
+  __device__ __forceinline__ long tap(int sy, int sx) const { return (long)sy * W + sx; }
+  __device__ __forceinline__ float value(long s, int c) const { return img[c * hw + s]; }
+  __device__ __forceinline__ float mask(int sy, int sx) const { return (float)msk[(long)sy * W + sx]; }
+};
 
 // grid (ceil(W / 16), ceil(H / 16), n), block 16 x 16: thread = output pixel (y, x) of sample n0 + blockIdx.z, every channel
 // plus the mask.  out_img [N][C][H][W] fp32, out_mask [N][1][H][W] fp32.
@@ -174,41 +184,9 @@ __global__ __launch_bounds__(256) void augment_gather_kernel(const float* __rest
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= W || y >= H) return;
   const AugRecord& p = b.r[blockIdx.z];
-  const long hw = (long)H * W, pix = (long)y * W + x;
-  const float* img = cache_img + (long)p.src * C * hw;
-  const unsigned char* msk = cache_mask + (long)p.src * hw;
-  const long n = n0 + blockIdx.z;
-  float* oi = out_img + n * C * hw + pix;
-  if (p.field < 0) {
-    int sy, sx;
-    aug_source(y, x, H, W, p.flags, p.k, sy, sx);
-    const long s = (long)sy * W + sx;
-    for (int c = 0; c < C; ++c) oi[c * hw] = aug_bc(img[c * hw + s], p);
-    out_mask[n * hw + pix] = (float)msk[s];
-    return;
-  }
-  const float* f = fields + (long)p.field * 2 * hw;
-  const float dx = f[pix], dy = f[hw + pix];
-  const float fx = floorf(dx), fy = floorf(dy);
-  const float tx = dx - fx, ty = dy - fy;                   // exact: the fraction of a float32
-  const int ix = x + (int)fx, iy = y + (int)fy;
-  int sy, sx;
-  long s[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    aug_source(aug_reflect(iy + (q >> 1), H), aug_reflect(ix + (q & 1), W), H, W, p.flags, p.k, sy, sx);
-    s[q] = (long)sy * W + sx;
-  }
-  const float wx0 = 1.0f - tx, wy0 = 1.0f - ty;
-  for (int c = 0; c < C; ++c) {
-    const float* ic = img + c * hw;
-    const float a00 = aug_bc(ic[s[0]], p), a01 = aug_bc(ic[s[1]], p);
-    const float a10 = aug_bc(ic[s[2]], p), a11 = aug_bc(ic[s[3]], p);
-    oi[c * hw] = wy0 * (wx0 * a00 + tx * a01) + ty * (wx0 * a10 + tx * a11);
-  }
-  // order 0: the nearest tap, round half up (ties are measure-zero for a smooth float field)
-  aug_source(aug_reflect(iy + (ty >= 0.5f), H), aug_reflect(ix + (tx >= 0.5f), W), H, W, p.flags, p.k, sy, sx);
-  out_mask[n * hw + pix] = (float)msk[(long)sy * W + sx];
+  const long hw = (long)H * W, pix = (long)y * W + x, n = n0 + blockIdx.z;
+  const CacheLattice L{cache_img + (long)p.src * C * hw, cache_mask + (long)p.src * hw, hw, W};
+  gather_pixel(L, p, C, H, W, y, x, fields, out_img + n * C * hw + pix, out_mask + n * hw + pix);
 }
 
 int aug_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
@@ -258,21 +236,13 @@ int launch_augment_gather(const float* cache_img, const unsigned char* cache_mas
     const AugRecord& p = params[i];
     UNETDC_REQUIRE(p.src >= 0 && p.src < ncache, "augment_gather: sample %d: source index %d outside the cache of %d", i,
                    p.src, ncache);
-    UNETDC_REQUIRE(p.k >= 0 && p.k <= 3, "augment_gather: sample %d: k = %d (0..3)", i, p.k);
+    if (const int rc = check_gather_record("augment_gather", i, p, fields, nfields)) return rc;
     UNETDC_REQUIRE(!(p.k & 1) || h == w, "augment_gather: sample %d: an odd k needs a square image (%d x %d)", i, h, w);
-    UNETDC_REQUIRE((p.flags & ~(AUG_HFLIP | AUG_VFLIP | AUG_BC)) == 0, "augment_gather: sample %d: bad flags 0x%x", i,
-                   p.flags);
-    UNETDC_REQUIRE(p.field >= -1 && p.field < nfields, "augment_gather: sample %d: field slot %d outside [-1, %d)", i,
-                   p.field, nfields);
-    UNETDC_REQUIRE(p.field < 0 || fields, "augment_gather: sample %d draws elastic but fields is null", i);
   }
-  for (int s0 = 0; s0 < n; s0 += AUG_MAX_BATCH) {
-    const int m = n - s0 < AUG_MAX_BATCH ? n - s0 : AUG_MAX_BATCH;
-    AugBatch b;
-    for (int i = 0; i < m; ++i) b.r[i] = params[s0 + i];
+  for_gather_batches<AugBatch>(params, n, [&](const AugBatch& b, int m, int n0) {
     hipLaunchKernelGGL(augment_gather_kernel, dim3((w + 15) / 16, (h + 15) / 16, m), dim3(256), 0, stream, cache_img,
-                       cache_mask, c, h, w, fields, b, s0, out_img, out_mask);
-  }
+                       cache_mask, c, h, w, fields, b, n0, out_img, out_mask);
+  });
   return check_launch("augment_gather_kernel");
 }
 

@@ -308,27 +308,19 @@ int launch_augment_gather(const float* cache_img, const unsigned char* cache_mas
                           hipStream_t stream);
 
 // crop.hip: random S x S windows of images cached at their own size, cut, scaled to [0, 1] and augmented in one pass (DESIGN.md
-// section 16).  CropRecord is the layout of the public unetdc_crop_params (abi.hip asserts the two agree).
+// section 16).  CropRecord is the layout of the public unetdc_crop_params and unetdc_crop_scaled_params (abi.hip asserts that
+// the three agree).  t: the side of the source window of unetdc_crop_gather_scaled, which resamples it to S x S (scale
+// jitter); unetdc_crop_gather does not read it (the public struct calls it `reserved`).
 struct CropRecord {
-  long long img_off, mask_off;
-  int h, w, y0, x0, flags, k, field;
-  float alpha, beta_max;
-  int reserved;
-};
-int launch_crop_gather(const unsigned char* images, long images_bytes, const unsigned char* masks, long masks_bytes, int c, int s,
-                       const CropRecord* params, int n, const float* fields, int nfields, float* out_img, float* out_mask,
-                       hipStream_t stream);
-// the same with a T x T source window resampled to S x S (scale jitter): CropRecord with the source side t in place of
-// `reserved`; the layout of the public unetdc_crop_scaled_params
-struct CropScaledRecord {
   long long img_off, mask_off;
   int h, w, y0, x0, flags, k, field;
   float alpha, beta_max;
   int t;
 };
-int launch_crop_gather_scaled(const unsigned char* images, long images_bytes, const unsigned char* masks, long masks_bytes, int c,
-                              int s, const CropScaledRecord* params, int n, const float* fields, int nfields, float* out_img,
-                              float* out_mask, hipStream_t stream);
+// who: the entry point's name for the messages; scaled: the source window has side params[i].t, else s
+int launch_crop_gather(const char* who, bool scaled, const unsigned char* images, long images_bytes, const unsigned char* masks,
+                       long masks_bytes, int c, int s, const CropRecord* params, int n, const float* fields, int nfields,
+                       float* out_img, float* out_mask, hipStream_t stream);
 
 // preprocess.hip: rolling-ball correction + bilinear resize to the network input
 long rolling_ball_workspace_bytes(int h, int w, int cn);

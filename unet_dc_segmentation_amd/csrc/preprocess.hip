@@ -17,6 +17,7 @@
 // LDS and takes every row span of the element as two power-of-two windows (morph_kernel); HBM traffic is one read and one
 // write per pass.
 #include "kernels.h"
+#include "linear_u8.h"
 
 namespace unetdc {
 
@@ -215,15 +216,16 @@ __global__ void resize_linear_chw_kernel(const unsigned char* __restrict__ src, 
   const long n = (long)dh * dw;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int dy = (int)(i / dw), dx = (int)(i - (long)dy * dw);
+    // (the table look-up of linear_u8_taps, written out: through that function this kernel takes 55 VGPRs instead of 51 and
+    // measured 2-3 % slower per launch)
     const int sx0 = xofs[dx], sx1 = sx0 + 1 < W ? sx0 + 1 : W - 1;
     int sy0 = yofs[dy], sy1 = sy0 + 1;
     sy0 = sy0 < 0 ? 0 : (sy0 > H - 1 ? H - 1 : sy0);
     sy1 = sy1 < 0 ? 0 : (sy1 > H - 1 ? H - 1 : sy1);
     const int a0 = xa[2 * dx], a1 = xa[2 * dx + 1], b0 = ya[2 * dy], b1 = ya[2 * dy + 1];
     for (int c = 0; c < cn; ++c) {
-      const int r0 = src[((long)sy0 * W + sx0) * cn + c] * a0 + src[((long)sy0 * W + sx1) * cn + c] * a1;   // horizontal pass
-      const int r1 = src[((long)sy1 * W + sx0) * cn + c] * a0 + src[((long)sy1 * W + sx1) * cn + c] * a1;
-      const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;                             // vertical pass
+      const int v = linear_u8_combine(src[((long)sy0 * W + sx0) * cn + c], src[((long)sy0 * W + sx1) * cn + c],
+                                      src[((long)sy1 * W + sx0) * cn + c], src[((long)sy1 * W + sx1) * cn + c], a0, a1, b0, b1);
       const unsigned char u = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
       dst[((long)c * dh + dy) * dw + dx] = (float)u / 255.0f;
     }

@@ -15,6 +15,7 @@
 //                (match by ballot, as clean_area_kernel: in a micrograph nearly every pixel is background at level 0); the
 //                nonzero bins go out as 64-bit integer atomics.  Integers only: the result depends on no order.
 #include "kernels.h"
+#include "linear_u8.h"
 
 namespace unetdc {
 
@@ -64,22 +65,17 @@ __global__ __launch_bounds__(SWEEP_THREADS) void thresh_sweep_kernel(const float
         sx = sx < pw - 1 ? sx : pw - 1;
         lev = sweep_tap_level(f32_bits(p[(long)sy * pw + sx]), grid, K);
       } else {
-        const int sx0 = xofs[x], sx1 = sx0 + 1 < pw ? sx0 + 1 : pw - 1;
-        int sy0 = yofs[y], sy1 = sy0 + 1;
-        sy0 = sy0 < 0 ? 0 : (sy0 > ph - 1 ? ph - 1 : sy0);
-        sy1 = sy1 < 0 ? 0 : (sy1 > ph - 1 ? ph - 1 : sy1);
-        const int a0 = xa[2 * x], a1 = xa[2 * x + 1], b0 = ya[2 * y], b1 = ya[2 * y + 1];
+        const LinearTaps t = linear_u8_taps(xofs, xa, yofs, ya, x, y, pw, ph);
         int l[4];
-        l[0] = sweep_tap_level(f32_bits(p[(long)sy0 * pw + sx0]), grid, K);
-        l[1] = sweep_tap_level(f32_bits(p[(long)sy0 * pw + sx1]), grid, K);
-        l[2] = sweep_tap_level(f32_bits(p[(long)sy1 * pw + sx0]), grid, K);
-        l[3] = sweep_tap_level(f32_bits(p[(long)sy1 * pw + sx1]), grid, K);
+        l[0] = sweep_tap_level(f32_bits(p[(long)t.sy0 * pw + t.sx0]), grid, K);
+        l[1] = sweep_tap_level(f32_bits(p[(long)t.sy0 * pw + t.sx1]), grid, K);
+        l[2] = sweep_tap_level(f32_bits(p[(long)t.sy1 * pw + t.sx0]), grid, K);
+        l[3] = sweep_tap_level(f32_bits(p[(long)t.sy1 * pw + t.sx1]), grid, K);
         lev = 0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {               // the mask at threshold l[c] - 1: exactly the taps of level >= l[c] are set
           const int L = l[c];
-          const int r0 = (l[0] >= L) * a0 + (l[1] >= L) * a1, r1 = (l[2] >= L) * a0 + (l[3] >= L) * a1;
-          const int v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+          const int v = linear_u8_combine(l[0] >= L, l[1] >= L, l[2] >= L, l[3] >= L, t.a0, t.a1, t.b0, t.b1);
           if (v > 0 && L > lev) lev = L;
         }
       }

@@ -229,19 +229,15 @@ class DeviceNativeCache:
         return ([torch.tensor([self.sizes[i][0] for i in idx]), torch.tensor([self.sizes[i][1] for i in idx])],
                 [self.names[i] for i in idx])
 
-    def gather(self, S, idx, origins, params, fields=None):
-        """One unetdc_crop_gather over the windows `origins` of the images `idx` with the augment.draw_params dicts `params`."""
+    def gather(self, S, idx, origins, params, fields=None, ts=None):
+        """One unetdc_crop_gather over the windows `origins` of the images `idx` with the augment.draw_params dicts `params`.
+        ts: the sides of the source windows at `origins`, resampled to S x S by one unetdc_crop_gather_scaled instead."""
         from . import crops
-        rec, _ = crops.pack_crops(params, [self.img_off[i] for i in idx], [self.mask_off[i] for i in idx],
-                                  [self.sizes[i] for i in idx], origins, [self.img_max[i] for i in idx])
-        return crops.crop_gather(self.images, self.masks, self.channels, S, rec, fields)
-
-    def gather_scaled(self, S, idx, origins, ts, params, fields=None):
-        """One unetdc_crop_gather_scaled: gather with the source windows of sides `ts` at `origins` resampled to S x S."""
-        from . import crops
-        rec, _ = crops.pack_crops_scaled(params, [self.img_off[i] for i in idx], [self.mask_off[i] for i in idx],
-                                         [self.sizes[i] for i in idx], origins, [self.img_max[i] for i in idx], ts)
-        return crops.crop_gather_scaled(self.images, self.masks, self.channels, S, rec, fields)
+        args = (params, [self.img_off[i] for i in idx], [self.mask_off[i] for i in idx], [self.sizes[i] for i in idx], origins,
+                [self.img_max[i] for i in idx])
+        if ts is None:
+            return crops.crop_gather(self.images, self.masks, self.channels, S, crops.pack_crops(*args)[0], fields)
+        return crops.crop_gather_scaled(self.images, self.masks, self.channels, S, crops.pack_crops_scaled(*args, ts)[0], fields)
 
 
 class DeviceCropTrainLoader:
@@ -291,42 +287,31 @@ class DeviceCropTrainLoader:
         return (self.samples + self.batch_size - 1) // self.batch_size
 
     def records(self, epoch, js):
-        """(cache indices, origins, draw_params dicts) of the local sample numbers `js` in epoch `epoch`."""
-        from utils.crops import draw_crop
+        """(cache indices, origins, source sides, draw_params dicts, took-the-foreground-branch flags) of the local sample
+        numbers `js` in epoch `epoch`.  Without scale and p_fg the sides are None and no flag is set."""
+        from utils import crops
         c = self.dataset
         idx = [int(j) // self.R for j in js]
         qs = [self.ids[i] * self.R + int(j) % self.R for i, j in zip(idx, js)]
-        origins = [draw_crop(self.seed, epoch, q, *c.sizes[i], self.S) for i, q in zip(idx, qs)]
-        return idx, origins, [augment.draw_params(self.seed, epoch, q) for q in qs]
-
-    def records_scaled(self, epoch, js):
-        """With scale or p_fg: (cache indices, origins, source sides, draw_params dicts, took-the-foreground-branch flags)."""
-        from utils.crops import draw_crop_fg_branch
-        c = self.dataset
-        idx = [int(j) // self.R for j in js]
-        qs = [self.ids[i] * self.R + int(j) % self.R for i, j in zip(idx, js)]
-        draws = [draw_crop_fg_branch(self.seed, epoch, q, *c.sizes[i], self.S, self.scale, self.p_fg,
-                                     c.foreground[i] if self.p_fg > 0.0 else None) for i, q in zip(idx, qs)]
-        return (idx, [(y0, x0) for y0, x0, _, _ in draws], [t for _, _, t, _ in draws],
-                [augment.draw_params(self.seed, epoch, q) for q in qs], [fg for _, _, _, fg in draws])
+        params = [augment.draw_params(self.seed, epoch, q) for q in qs]
+        if not self.scaled:
+            origins = [crops.draw_crop(self.seed, epoch, q, *c.sizes[i], self.S) for i, q in zip(idx, qs)]
+            return idx, origins, None, params, [False] * len(idx)
+        draws = [crops.draw_crop_fg_branch(self.seed, epoch, q, *c.sizes[i], self.S, self.scale, self.p_fg,
+                                           c.foreground[i] if self.p_fg > 0.0 else None) for i, q in zip(idx, qs)]
+        return (idx, [(y0, x0) for y0, x0, _, _ in draws], [t for _, _, t, _ in draws], params, [fg for _, _, _, fg in draws])
 
     def batch(self, epoch, js):
         """The augmented batch of local sample numbers `js` in epoch `epoch`."""
         c = self.dataset
-        if self.scaled:
-            idx, origins, ts, params, took = self.records_scaled(epoch, js)
-            self.fg_windows += sum(took)
-        else:
-            idx, origins, params = self.records(epoch, js)
+        idx, origins, ts, params, took = self.records(epoch, js)
+        self.fg_windows += sum(took)
         seeds = np.asarray([p["field_seed"] for p in params if p["elastic"]], dtype=np.uint32)
         fields = None
         if len(seeds):
             fields = augment.elastic_fields(seeds, self.S, self.S, self.sigma, self.alpha, out=self._fields,
                                             workspace=self._ws)[:len(seeds)]
-        if self.scaled:
-            images, masks = c.gather_scaled(self.S, idx, origins, ts, params, fields)
-        else:
-            images, masks = c.gather(self.S, idx, origins, params, fields)
+        images, masks = c.gather(self.S, idx, origins, params, fields, ts)
         sizes, names = c._meta(idx)
         return images, masks, sizes, names
 
