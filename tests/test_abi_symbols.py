@@ -91,6 +91,68 @@ def test_wgrad_workspace_and_bnin_answers_are_the_recorded_ones(lib, golden_dir)
     assert not bad, bad[:10]
 
 
+def test_partial_buffer_sizing_answers_are_the_recorded_ones(lib, golden_dir):
+    """The host-only sizing answers of the HBM-bound operators, against tests/golden/elementwise_abi_answers.json: recorded from
+    the library of the commit BEFORE each operator got its single plan (plan_bn_bwd, plan_head, plan_channel_sum) and the
+    spare-row helpers.  fp32 / bf16, n in {1, 3, 5, 8}, six image sizes from 16^2 to 1024^2: unetdc_bn_relu_bwd_workspace over
+    seven widths, pooled or not; unetdc_head_bwd_workspace over six widths and OC in {1, 2, 3}; unetdc_channel_sum_workspace,
+    unetdc_conv3x3_dgrad_colsum_workspace and unetdc_conv3x3_stats_rows over the pixel counts and widths of that grid."""
+    import json
+    t = json.load(open(os.path.join(golden_dir, "elementwise_abi_answers.json")))
+    assert t["dtypes"] == [0, 1] and t["n"] == [1, 3, 5, 8] and t["pooled"] == [0, 1] and t["oc"] == [1, 2, 3]
+    assert t["hw"] == [[16, 16], [24, 40], [64, 64], [96, 128], [512, 512], [1024, 1024]]
+    assert t["bn_c"] == [8, 64, 128, 256, 512, 1024, 2048] and t["head_c"] == [8, 16, 32, 64, 128, 256]
+    checked, bad = 0, []
+
+    def check(what, got, want, *args):
+        nonlocal checked
+        checked += 1
+        if got != want:
+            bad.append((what, *args, got, want))
+
+    for b, n in enumerate(t["n"]):
+        for c, (h, w) in enumerate(t["hw"]):
+            for a, dt in enumerate(t["dtypes"]):
+                for e, ch in enumerate(t["bn_c"]):
+                    for f, pooled in enumerate(t["pooled"]):
+                        check("bn_relu_bwd_workspace", lib.unetdc_bn_relu_bwd_workspace(n, h, w, ch, pooled, dt),
+                              t["bn_relu_bwd_workspace"][a][b][c][e][f], n, h, w, ch, pooled, dt)
+                for e, ch in enumerate(t["head_c"]):
+                    for f, oc in enumerate(t["oc"]):
+                        check("head_bwd_workspace", lib.unetdc_head_bwd_workspace(n, h, w, ch, oc, dt),
+                              t["head_bwd_workspace"][a][b][c][e][f], n, h, w, ch, oc, dt)
+            for e, ch in enumerate(t["bn_c"]):
+                check("channel_sum_workspace", lib.unetdc_channel_sum_workspace(n * h * w, ch), t["channel_sum_workspace"][b][c][e],
+                      n * h * w, ch)
+                check("dgrad_colsum_workspace", lib.unetdc_conv3x3_dgrad_colsum_workspace(n, h, w, ch),
+                      t["dgrad_colsum_workspace"][b][c][e], n, h, w, ch)
+                check("stats_rows", lib.unetdc_conv3x3_stats_rows(n * h * w, ch), t["stats_rows"][b][c][e], n * h * w, ch)
+    assert checked == 672 + 864 + 3 * 168
+    assert not bad, bad[:10]
+
+
+def test_sizing_queries_answer_zero_for_widths_the_launchers_refuse(lib):
+    """A width the launcher would refuse (no multiple of the 16-byte chunk, zero, a head width outside the powers of two up to
+    64 chunks) gets 0 bytes, like every other *_workspace query -- not a division by zero in the host process."""
+    BF16 = 1
+    assert lib.unetdc_bn_relu_bwd_workspace(1, 8, 8, 4, 0, BF16) == 0
+    assert lib.unetdc_bn_relu_bwd_workspace(1, 8, 8, 0, 0, BF16) == 0
+    assert lib.unetdc_head_bwd_workspace(1, 8, 8, 4, 1, BF16) == 0
+    assert lib.unetdc_head_bwd_workspace(1, 8, 8, 4096, 1, BF16) == 0
+    # the launchers refuse the same widths before any arithmetic on them, and before any HIP call (host memory stands in)
+    import ctypes
+    buf = ctypes.create_string_buffer(64)
+    a = ctypes.addressof(buf)
+    for c, msg in ((0, b"unsupported"), (4, b"chunk aligned")):
+        rc = lib.unetdc_bn_relu_bwd(a, c, None, 0, a, c, a, a, a, a, a, a, c, a, a, a, a, 64, None, 0, 1, 8, 8, c, BF16, None)
+        assert rc == -1 and msg in lib.unetdc_last_error(), (c, rc, lib.unetdc_last_error())
+    for c in (4, 4096):
+        rc = lib.unetdc_head_bwd(a, a, a, 8 * c, a, a, 8 * c, a, a, a, 64, 1, 8, 8, c, 1, BF16, None)
+        assert rc == -1 and b"unsupported" in lib.unetdc_last_error(), (c, rc, lib.unetdc_last_error())
+    rc = lib.unetdc_channel_sum(a, 0, a, a, 64, 16, 0, BF16, None)
+    assert rc == -1 and b"unsupported" in lib.unetdc_last_error(), (rc, lib.unetdc_last_error())
+
+
 def test_no_kernel_carries_packed_fp32(lib):
     """Build guard (widened in round 3 to EVERY kernel of the library): the packed-fp32 (SLP-vectorised) build
     of the fused BatchNorm-backward epilogue was not run-to-run deterministic on MI355X and the cause is not identified

@@ -466,7 +466,7 @@ def test_head_fwd_bwd(dtype, oc):
 def test_head_bwd_fused_bn_backward_sums(dtype, shape):
     """unetdc_head_bwd_bnstats: same da (bitwise) / dw / db as unetdc_head_bwd, and partial rows whose column sums are the
     BatchNorm-backward sums S1 = sum dyhat, S2 = sum dyhat * xhat, S3 = sum xhat of the stored gradient (fp64 restatement
-    of csrc/elementwise.hip bn_bwd_kernel on the device's own da and y)."""
+    of csrc/batchnorm.hip bn_bwd_kernel on the device's own da and y)."""
     import ctypes
     n, h, w, oc = shape
     c = 64
@@ -680,6 +680,79 @@ def test_argument_errors_are_reported():
     with pytest.raises(_lib.UnetdcError, match="workspace too small"):
         call("unetdc_conv3x3_wgrad", x.data_ptr(), 64, x.data_ptr(), 64, x.data_ptr(), x.data_ptr(), 16,
              1, 8, 8, 64, 64, 1, _lib.F32, G.stream())
+
+
+def _tight_case(name):
+    """(query bytes, NaN-prefilled outputs, run(workspace pointer, bytes)) of one workspace-taking call at a tiny shape."""
+    lib, g = _lib.load(), gen(41)
+    f32 = dict(device="cuda", dtype=torch.float32)
+    nan = lambda *shape: torch.full(shape, float("nan"), **f32)
+    if name.startswith("bn_relu_bwd"):
+        n, h, w, c, pool, dtype = (1, 4, 6, 16, True, "f32") if name.endswith("pooled") else (1, 4, 4, 8, False, "bf16")
+        yv = G.to_nhwc(torch.randn(n, c, h, w, generator=g), dtype)
+        dsv = G.to_nhwc(torch.randn(n, c, h, w, generator=g), dtype)
+        dpv = G.to_nhwc(torch.randn(n, c, h // 2, w // 2, generator=g), dtype) if pool else None
+        sc, sh, mu, rs, ga = ((torch.rand(c, generator=g) + 0.5).cuda() for _ in range(5))
+        outs = [G.empty_nhwc(n * h * w, c, dtype), nan(c), nan(c), nan(c)]
+        nbytes = lib.unetdc_bn_relu_bwd_workspace(n, h, w, c, int(pool), G.DT[dtype])
+        run = lambda ws, nb: call("unetdc_bn_relu_bwd", dsv.data_ptr(), dsv.stride(0), dpv.data_ptr() if pool else None,
+                                  dpv.stride(0) if pool else 0, yv.data_ptr(), yv.stride(0), sc.data_ptr(), sh.data_ptr(),
+                                  mu.data_ptr(), rs.data_ptr(), ga.data_ptr(), outs[0].data_ptr(), outs[0].stride(0),
+                                  outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), ws, nb, None, 0, n, h, w, c,
+                                  G.DT[dtype], G.stream())
+    elif name.startswith("head_bwd"):
+        n, h, w, c, oc, dtype = (1, 4, 4, 8, 2, "f32") if name.endswith("oc2") else (1, 4, 4, 8, 1, "bf16")
+        av = G.to_nhwc(torch.randn(n, c, h, w, generator=g), dtype)
+        probs, dp = torch.rand(n, oc, h, w, generator=g).cuda(), torch.randn(n, oc, h, w, generator=g).cuda()
+        wt = torch.randn(oc, c, generator=g).cuda()
+        outs = [G.empty_nhwc(n * h * w, c, dtype), nan(oc, c), nan(oc)]
+        nbytes = lib.unetdc_head_bwd_workspace(n, h, w, c, oc, G.DT[dtype])
+        run = lambda ws, nb: call("unetdc_head_bwd", dp.data_ptr(), probs.data_ptr(), av.data_ptr(), av.stride(0), wt.data_ptr(),
+                                  outs[0].data_ptr(), outs[0].stride(0), outs[1].data_ptr(), outs[2].data_ptr(), ws, nb, n, h, w,
+                                  c, oc, G.DT[dtype], G.stream())
+    elif name == "channel_sum":
+        npix, c, dtype = 48, 8, "f32"
+        xv = G.to_nhwc(torch.randn(1, c, 6, 8, generator=g), dtype)
+        outs = [nan(c)]
+        nbytes = lib.unetdc_channel_sum_workspace(npix, c)
+        run = lambda ws, nb: call("unetdc_channel_sum", xv.data_ptr(), xv.stride(0), outs[0].data_ptr(), ws, nb, npix, c,
+                                  G.DT[dtype], G.stream())
+    else:
+        n, h, w, cin, cout, dtype = 1, 8, 8, 64, 64, "bf16"
+        dyv = G.to_nhwc(torch.randn(n, cout, h, w, generator=g), dtype)
+        _, wd = G.pack_conv(torch.randn(cout, cin, 3, 3, generator=g) / (3 * cin ** 0.5), dtype)
+        outs = [G.empty_nhwc(n * h * w, cin, dtype), nan(cin // 2)]
+        nbytes = lib.unetdc_conv3x3_dgrad_colsum_workspace(n, h, w, cin)
+        run = lambda ws, nb: call("unetdc_conv3x3_dgrad_colsum", dyv.data_ptr(), dyv.stride(0), wd.data_ptr(), outs[0].data_ptr(),
+                                  outs[0].stride(0), outs[1].data_ptr(), 0, cin // 2, ws, nb, n, h, w, cin, cout, 1, G.DT[dtype],
+                                  G.stream())
+    return nbytes, outs, run
+
+
+@pytest.mark.parametrize("name", ["bn_relu_bwd", "bn_relu_bwd_pooled", "head_bwd", "head_bwd_oc2", "channel_sum", "dgrad_colsum"])
+def test_workspace_query_is_tight_and_a_short_workspace_is_refused(name):
+    """What a *_workspace query answers is enough and is enforced.  With exactly the queried bytes (a stale, NaN-filled workspace
+    with a guard band behind it) the outputs are bit-equal to the same call with 1 MiB, and the guard band is untouched; with one
+    byte less the call raises "workspace too small" before any launch: the NaN-prefilled outputs stay as they were."""
+    bits = lambda t: t.contiguous().view(torch.uint8).cpu()
+    nbytes, outs, run = _tight_case(name)
+    assert 0 < nbytes < (1 << 20)
+    big = torch.full((1 << 20,), 0xFF, dtype=torch.uint8, device="cuda")
+    run(big.data_ptr(), big.numel())
+    ref = [bits(o) for o in outs]
+    assert not any(bool(torch.isnan(o.float()).any()) for o in outs)
+    nbytes2, outs, run = _tight_case(name)                                  # the same seeded inputs, fresh NaN outputs
+    assert nbytes2 == nbytes
+    ws = torch.full((nbytes + 256,), 0xFF, dtype=torch.uint8, device="cuda")
+    ws[nbytes:] = 0xA5
+    run(ws.data_ptr(), nbytes)
+    assert all(torch.equal(bits(o), r) for o, r in zip(outs, ref))
+    assert bool((ws[nbytes:] == 0xA5).all()), "wrote past the queried bytes"
+    _, outs, run = _tight_case(name)
+    with pytest.raises(_lib.UnetdcError, match="workspace too small"):
+        run(ws.data_ptr(), nbytes - 1)
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(o.float()).all()) for o in outs)
 
 
 def test_pack_many_matches_per_layer_packers():

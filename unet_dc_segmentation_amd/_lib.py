@@ -110,6 +110,12 @@ SIGNATURES = {
 _lib = None
 
 
+def partial_floats(rows, row_floats):
+    """Floats of a partial-row buffer handed to the library (statistics rows, BatchNorm-backward rows): the two-stage
+    reductions leave their first-stage result in 64 spare rows behind the `rows` data rows."""
+    return (rows + 64) * row_floats
+
+
 class UnetdcError(RuntimeError):
     pass
 

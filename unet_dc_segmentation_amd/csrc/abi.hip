@@ -60,6 +60,9 @@ static void taps3x3(int d, int* offy, int* offx) {
     offx[t] = (t % 3 - 1) * d;
   }
 }
+static void taps2x2(int* offy, int* offx) {
+  for (int t = 0; t < 4; ++t) { offy[t] = t >> 1; offx[t] = t & 1; }
+}
 
 // The implicit GEMM of a dilated 3 x 3 convolution over n x h x w with cin input and cout output channels (the input
 // gradient passes them swapped), and of the input gradient of ConvTranspose2d(2, 2, stride 2): four taps of stride 2.
@@ -74,7 +77,7 @@ static IgemmParams convT2x2_dgrad_igemm(int n, int h, int w, int cin, int cout, 
   IgemmParams p{};
   p.M = n * h * w; p.Ho = h; p.Wo = w; p.Hi = 2 * h; p.Wi = 2 * w; p.Cin = cout; p.Cout = cin; p.ldx = lddup;
   p.ldo = lddx; p.ntaps = 4; p.stride = 2;
-  for (int t = 0; t < 4; ++t) { p.offy[t] = t >> 1; p.offx[t] = t & 1; }
+  taps2x2(p.offy, p.offx);
   return p;
 }
 
@@ -84,6 +87,23 @@ static WgradParams conv3x3_wgrad(int n, int h, int w, int cin, int cout, int ldx
   p.N = n; p.H = h; p.W = w; p.Hb = h; p.Wb = w; p.CI = cout; p.CJ = cin;
   p.lda = lddy; p.ldb = ldx; p.ntaps = 9; p.stride = 1;
   taps3x3(d, p.offy, p.offx);
+  return p;
+}
+
+// One filler per parameter block of the BatchNorm backward and the head.
+static BnBwdParams bn_bwd_params(const void* dskip, int ldskip, const void* dpool, int ldpool, const void* y, int ldy,
+                                 const float* scale, const float* shift, const float* mean, const float* rstd, void* dy, int lddy,
+                                 int n, int h, int w, int c) {
+  BnBwdParams p{};
+  p.dskip = dskip; p.dpool = dpool; p.y = y; p.dy = dy; p.scale = scale; p.shift = shift; p.mean = mean; p.rstd = rstd;
+  p.N = n; p.H = h; p.W = w; p.C = c; p.lds = ldskip; p.ldp = ldpool; p.ldy = ldy; p.lddy = lddy;
+  return p;
+}
+static HeadParams head_params(const void* a, int lda, const float* w, const float* probs, const float* dprobs, void* da, int ldda,
+                              int n, int h, int wd, int c, int oc) {          // forward: dprobs, da null
+  HeadParams p{};
+  p.a = a; p.w = w; p.probs = const_cast<float*>(probs); p.dprobs = dprobs; p.da = da;
+  p.N = n; p.H = h; p.W = wd; p.C = c; p.OC = oc; p.lda = lda; p.ldda = ldda;
   return p;
 }
 
@@ -196,7 +216,7 @@ int unetdc_conv3x3_dgrad(const void* dy, int lddy, const void* w_dgrad, void* dx
 
 // dgrad whose epilogue also sums the stored gradient per channel: colsum[c] = sum_pixels dx[:, c0 + c]
 int64_t unetdc_conv3x3_dgrad_colsum_workspace(int n, int h, int w, int cin) {
-  return ((int64_t)igemm_mblocks((long)n * h * w, cin) + 64) * 2 * cin * 4;
+  return partial_floats(igemm_mblocks((long)n * h * w, cin), 2L * cin) * 4;
 }
 
 int unetdc_conv3x3_dgrad_colsum(const void* dy, int lddy, const void* w_dgrad, void* dx, int lddx, float* colsum, int c0,
@@ -224,7 +244,7 @@ static int dgrad_bnstats_common(IgemmParams& p, const void* y_prev, int ldy_prev
                                 hipStream_t stream) {
   UNETDC_REQUIRE(y_prev && scale && shift && mean && rstd && parts && nparts, "dgrad_bnstats: null pointer");
   const int rows = igemm_mblocks((long)p.M, p.Cout);
-  UNETDC_REQUIRE((int64_t)(rows + 64) * 3 * c_prev <= parts_floats, "dgrad_bnstats: partial buffer too small");
+  UNETDC_REQUIRE(partial_floats(rows, 3L * c_prev) <= parts_floats, "dgrad_bnstats: partial buffer too small");
   p.mode = MODE_BNBWD;
   p.stats = parts; p.bn_y = y_prev; p.bn_ldy = ldy_prev; p.scale = scale; p.shift = shift; p.bn_mean = mean; p.bn_rstd = rstd;
   if (plan_igemm(p, dtype).route != IGEMM_FIRSTGEN) {
@@ -236,9 +256,7 @@ static int dgrad_bnstats_common(IgemmParams& p, const void* y_prev, int ldy_prev
   p.mode = MODE_STORE; p.stats = nullptr;
   const int rc = launch_igemm(p, dtype, stream);
   if (rc != UNETDC_OK) return rc;
-  BnBwdParams b{};
-  b.dskip = p.out; b.lds = p.ldo; b.y = y_prev; b.ldy = ldy_prev; b.scale = scale; b.shift = shift; b.mean = mean;
-  b.rstd = rstd; b.N = n; b.H = h; b.W = w; b.C = c_prev;
+  BnBwdParams b = bn_bwd_params(p.out, p.ldo, nullptr, 0, y_prev, ldy_prev, scale, shift, mean, rstd, nullptr, 0, n, h, w, c_prev);
   return launch_bn_bwd_reduce_only(b, parts, (long)parts_floats, nparts, dtype, stream);
 }
 
@@ -371,7 +389,7 @@ int unetdc_convT2x2_wgrad(const void* x, int ldx, const void* dup, int lddup, fl
   WgradParams p{};
   p.a = x; p.b = dup; p.N = n; p.H = h; p.W = w; p.Hb = 2 * h; p.Wb = 2 * w; p.CI = cin; p.CJ = cout;
   p.lda = ldx; p.ldb = lddup; p.ntaps = 4; p.stride = 2;
-  for (int t = 0; t < 4; ++t) { p.offy[t] = t >> 1; p.offx[t] = t & 1; }
+  taps2x2(p.offy, p.offx);
   return launch_wgrad(p, dw, workspace, (long)workspace_bytes, dtype, (hipStream_t)s);
 }
 
@@ -399,7 +417,7 @@ int unetdc_bn_relu_apply(const void* y, int ldy, const float* scale, const float
 }
 
 int64_t unetdc_bn_relu_bwd_workspace(int n, int h, int w, int c, int pooled, int dtype) {
-  return bn_bwd_workspace_bytes(n, h, w, c, pooled, dtype);
+  return plan_bn_bwd(n, h, w, c, pooled, dtype).workspace;
 }
 
 int unetdc_bn_relu_bwd(const void* dskip, int ldskip, const void* dpool, int ldpool, const void* y, int ldy,
@@ -408,11 +426,9 @@ int unetdc_bn_relu_bwd(const void* dskip, int ldskip, const void* dpool, int ldp
                        void* workspace, int64_t workspace_bytes, const float* pre_parts, int pre_nparts, int n, int h,
                        int w, int c, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
-  BnBwdParams p{};
-  p.dskip = dskip; p.dpool = dpool; p.y = y; p.dy = dy; p.scale = scale; p.shift = shift; p.mean = mean; p.rstd = rstd;
-  p.N = n; p.H = h; p.W = w; p.C = c; p.lds = ldskip; p.ldp = ldpool; p.ldy = ldy; p.lddy = lddy;
+  BnBwdParams p = bn_bwd_params(dskip, ldskip, dpool, ldpool, y, ldy, scale, shift, mean, rstd, dy, lddy, n, h, w, c);
   return launch_bn_bwd(p, gamma, dgamma, dbeta, dbias, workspace, (long)workspace_bytes, pre_parts, pre_nparts, dtype,
-                       (hipStream_t)s);
+                       (hipStream_t)s, false);
 }
 
 int unetdc_bn_relu_bwd_head(const float* dprobs, const float* probs, const float* head_w, const void* y, int ldy,
@@ -421,13 +437,11 @@ int unetdc_bn_relu_bwd_head(const float* dprobs, const float* probs, const float
                             void* workspace, int64_t workspace_bytes, const float* pre_parts, int pre_nparts, int n, int h,
                             int w, int c, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
-  BnBwdParams p{};
+  BnBwdParams p = bn_bwd_params(nullptr, 0, nullptr, 0, y, ldy, scale, shift, mean, rstd, dy, lddy, n, h, w, c);
   p.head_dprobs = dprobs; p.head_probs = probs; p.head_w = head_w;
-  p.y = y; p.dy = dy; p.scale = scale; p.shift = shift; p.mean = mean; p.rstd = rstd;
-  p.N = n; p.H = h; p.W = w; p.C = c; p.ldy = ldy; p.lddy = lddy;
   UNETDC_REQUIRE(head_w != nullptr, "bn_relu_bwd_head: null head weights");
   return launch_bn_bwd(p, gamma, dgamma, dbeta, dbias, workspace, (long)workspace_bytes, pre_parts, pre_nparts, dtype,
-                       (hipStream_t)s);
+                       (hipStream_t)s, false);
 }
 
 int unetdc_bn_frozen_affine(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
@@ -441,9 +455,7 @@ int unetdc_bn_relu_bwd_frozen(const void* dskip, int ldskip, const void* dpool, 
                               void* workspace, int64_t workspace_bytes, const float* pre_parts, int pre_nparts, int n, int h,
                               int w, int c, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, w);
-  BnBwdParams p{};
-  p.dskip = dskip; p.dpool = dpool; p.y = y; p.dy = dy; p.scale = scale; p.shift = shift; p.mean = mean; p.rstd = rstd;
-  p.N = n; p.H = h; p.W = w; p.C = c; p.lds = ldskip; p.ldp = ldpool; p.ldy = ldy; p.lddy = lddy;
+  BnBwdParams p = bn_bwd_params(dskip, ldskip, dpool, ldpool, y, ldy, scale, shift, mean, rstd, dy, lddy, n, h, w, c);
   return launch_bn_bwd(p, gamma, dgamma, dbeta, dbias, workspace, (long)workspace_bytes, pre_parts, pre_nparts, dtype,
                        (hipStream_t)s, true);
 }
@@ -451,8 +463,8 @@ int unetdc_bn_relu_bwd_frozen(const void* dskip, int ldskip, const void* dpool, 
 int unetdc_head_fwd(const void* a, int lda, const float* w, const float* b, float* probs, int n, int h, int wd,
                     int c, int oc, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, wd);
-  HeadParams p{};
-  p.a = a; p.w = w; p.b = b; p.probs = probs; p.N = n; p.H = h; p.W = wd; p.C = c; p.OC = oc; p.lda = lda;
+  HeadParams p = head_params(a, lda, w, probs, nullptr, nullptr, 0, n, h, wd, c, oc);
+  p.b = b;
   return launch_head_fwd(p, dtype, (hipStream_t)s);
 }
 
@@ -460,24 +472,21 @@ int unetdc_head_fwd_bn(const void* y, int ldy, const float* scale, const float* 
                        float* probs, int n, int h, int wd, int c, int oc, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, wd);
   UNETDC_REQUIRE(y && scale && shift, "head_fwd_bn: null pointer");
-  HeadParams p{};
-  p.a = y; p.w = w; p.b = b; p.probs = probs; p.N = n; p.H = h; p.W = wd; p.C = c; p.OC = oc; p.lda = ldy;
-  p.bn_scale = scale; p.bn_shift = shift;
+  HeadParams p = head_params(y, ldy, w, probs, nullptr, nullptr, 0, n, h, wd, c, oc);
+  p.b = b; p.bn_scale = scale; p.bn_shift = shift;
   return launch_head_fwd(p, dtype, (hipStream_t)s);
 }
 
 int64_t unetdc_head_bwd_workspace(int n, int h, int w, int c, int oc, int dtype) {
-  return head_bwd_workspace_bytes(n, h, w, c, oc, dtype);
+  return plan_head((long)n * h * w, c, oc, dtype, HEAD_BWD_MAX_ROWS).workspace;
 }
 
 int unetdc_head_bwd(const float* dprobs, const float* probs, const void* a, int lda, const float* w, void* da,
                     int ldda, float* dw, float* db, void* workspace, int64_t workspace_bytes, int n, int h, int wd,
                     int c, int oc, int dtype, unetdc_stream_t s) {
   GEOM_CHECK(n, h, wd);
-  HeadParams p{};
-  p.a = a; p.w = w; p.probs = const_cast<float*>(probs); p.dprobs = dprobs; p.da = da;
-  p.N = n; p.H = h; p.W = wd; p.C = c; p.OC = oc; p.lda = lda; p.ldda = ldda;
-  return launch_head_bwd(p, dw, db, workspace, (long)workspace_bytes, dtype, (hipStream_t)s);
+  HeadParams p = head_params(a, lda, w, probs, dprobs, da, ldda, n, h, wd, c, oc);
+  return launch_head_bwd(p, dw, db, workspace, (long)workspace_bytes, dtype, (hipStream_t)s, nullptr, 0);
 }
 
 int unetdc_head_bwd_bnstats(const float* dprobs, const float* probs, const void* a, int lda, const float* w, void* da,
@@ -487,9 +496,7 @@ int unetdc_head_bwd_bnstats(const float* dprobs, const float* probs, const void*
                             unetdc_stream_t s) {
   GEOM_CHECK(n, h, wd);
   UNETDC_REQUIRE(y_prev && scale && shift && mean && rstd && parts && nparts, "head_bwd_bnstats: null pointer");
-  HeadParams p{};
-  p.a = a; p.w = w; p.probs = const_cast<float*>(probs); p.dprobs = dprobs; p.da = da;
-  p.N = n; p.H = h; p.W = wd; p.C = c; p.OC = oc; p.lda = lda; p.ldda = ldda;
+  HeadParams p = head_params(a, lda, w, probs, dprobs, da, ldda, n, h, wd, c, oc);
   p.bn_y = y_prev; p.bn_ldy = ldy_prev; p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean; p.bn_rstd = rstd;
   p.bn_parts = parts;
   return launch_head_bwd(p, dw, db, workspace, (long)workspace_bytes, dtype, (hipStream_t)s, nparts, (long)parts_floats);
@@ -510,7 +517,8 @@ int unetdc_focal_dice_loss_bwd(const float* probs, const float* target, const fl
   return launch_loss_bwd(probs, target, coef, grad_out, dprobs, nimg, (long)hw, alpha, gamma, ratio, (hipStream_t)s);
 }
 
-int64_t unetdc_channel_sum_workspace(int64_t npixels, int c) { return channel_sum_workspace_bytes((long)npixels, c); }
+// the bytes do not depend on the dtype, and a width that bf16 takes fp32 takes too
+int64_t unetdc_channel_sum_workspace(int64_t npixels, int c) { return plan_channel_sum((long)npixels, c, UNETDC_F32).workspace; }
 
 int unetdc_channel_sum(const void* x, int ldx, float* out, void* workspace, int64_t workspace_bytes,
                        int64_t npixels, int c, int dtype, unetdc_stream_t s) {

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void first_wgrad_rows_kernel(const FirstWgradP
 #pragma unroll
         for (int i = 0; i < PB; ++i)
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {                      // bn_bwd_kernel's apply arithmetic, operation for operation
+          for (int e = 0; e < 8; ++e) {                      // the apply arithmetic of bn_bwd_terms.h, written out (see there)
             const float nrm = fmaf(yv[i][e], sc[e], sh[e]);
             const float gh = nrm > 0.f ? d[i][e] : 0.f;
             const float xh = (yv[i][e] - mu[e]) * rs[e];

@@ -1,5 +1,8 @@
 // Parameter blocks and host launchers shared between the kernel files and the C-ABI layer.
 #pragma once
+#include <algorithm>
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/unetdc_hip.h"
 
@@ -188,32 +191,61 @@ struct HeadParams {
   float* bn_parts;  // [gridDim.x][3][C]
   int bn_ldy;
 };
+// ---- the HBM-bound operators: partials.hip, batchnorm.hip, head.hip, pack.hip ----
+// Spare-row contract of the two-stage reductions (reduce_parts, partials.hip): a buffer of `rows` partial rows of L floats
+// carries SPARE_ROWS more rows behind them, where the first stage leaves its <= SPARE_ROWS reduced rows.
+constexpr int SPARE_ROWS = 64;
+inline long partial_floats(long rows, long L) { return (rows + SPARE_ROWS) * L; }    // floats of such a buffer
+inline long partial_row_cap(long floats, long L) { return floats / L - SPARE_ROWS; } // rows a caller-sized buffer takes
+inline int chunk_elems(int dtype) { return dtype == UNETDC_BF16 ? 8 : dtype == UNETDC_F32 ? 4 : 0; }   // 0: no such dtype
+inline int grid_for(long work_items, int per_block) {
+  return (int)std::min(std::max((work_items + per_block - 1) / per_block, 1L), 8192L);
+}
+// One launch line per kernel: f(TypeTag<T>{}, std::bool_constant...) for the dtype (valid: chunk_elems) and run-time flags.
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> void dispatch_flags(F&& f) { f(); }
+template <typename F, typename... B> void dispatch_flags(F&& f, bool b, B... rest) {
+  if (b) dispatch_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else dispatch_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <typename F, typename... B> void dispatch(int dtype, F&& f, B... flags) {
+  if (dtype == UNETDC_BF16) dispatch_flags([&](auto... c) { f(TypeTag<bf16_t>{}, c...); }, flags...);
+  else dispatch_flags([&](auto... c) { f(TypeTag<float>{}, c...); }, flags...);
+}
+// Host-only plans, decided once: the *_workspace query, the launcher and the reduce-only pass all read them.  ok == false
+// (and workspace == 0): a dtype or width the launcher refuses.  epc, cpp: elements per chunk, chunks per pixel.
+// seg: chunk lanes of a workgroup row; reduce grid (nb, ny) = partial rows x chunk segments; apply grid (apply_nb, ny);
+// workspace bytes: [3][C] coefficients + partial_floats(nb, 3 C)
+struct BnBwdPlan { bool ok; int epc, cpp, seg, nb, ny, apply_nb; long workspace; };
+BnBwdPlan plan_bn_bwd(int N, int H, int W, int C, int pooled, int dtype);
+// cpp = lanes per pixel: a power of two <= 64; bwd_nb = partial rows <= row_cap; workspace (backward): partial_floats(bwd_nb, OC (C + 1))
+struct HeadPlan { bool ok; int epc, cpp, fwd_nb, bwd_nb; long workspace; };
+constexpr long HEAD_BWD_MAX_ROWS = 1024;
+HeadPlan plan_head(long P, int C, int OC, int dtype, long row_cap);
+struct ChannelSumPlan { bool ok; int epc, nb, ny; long workspace; };   // workspace bytes: partial_floats(nb, C)
+ChannelSumPlan plan_channel_sum(long P, int C, int dtype);
+
 int launch_bn_finalize(const float* parts, int nparts, long count, const float* gamma, const float* beta, float eps,
                        float momentum, float* rm, float* rv, float* scale, float* shift, float* mean, float* rstd,
                        int C, hipStream_t stream);
 int launch_bn_eval_affine(const float* gamma, const float* beta, const float* rm, const float* rv,
                           const float* conv_bias, float eps, float* scale, float* shift, int C, hipStream_t stream);
 int launch_apply(ApplyParams& p, int dtype, hipStream_t stream);
-long bn_bwd_workspace_bytes(int N, int H, int W, int C, int pooled, int dtype);
 int launch_bn_bwd(BnBwdParams& p, const float* gamma, float* dgamma, float* dbeta, float* dbias, void* workspace,
-                  long workspace_bytes, const float* pre_parts, int pre_nparts, int dtype, hipStream_t stream,
-                  bool frozen = false);
+                  long workspace_bytes, const float* pre_parts, int pre_nparts, int dtype, hipStream_t stream, bool frozen);
 int launch_bn_frozen_affine(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, float* scale,
                             float* shift, float* mean, float* rstd, int C, hipStream_t stream);
-int launch_stats_colsum_rows(const float* parts, int nparts, int row_floats, int c0, int c, float* out, hipStream_t stream);
-int launch_bn_bwd_reduce_only(BnBwdParams& p, float* parts, long parts_floats, int* nparts, int dtype,
-                              hipStream_t stream);
-long head_bwd_workspace_bytes(int N, int H, int W, int C, int OC, int dtype);
+int launch_bn_bwd_reduce_only(BnBwdParams& p, float* parts, long parts_floats, int* nparts, int dtype, hipStream_t stream);
 int launch_head_fwd(HeadParams& p, int dtype, hipStream_t stream);
+// bn_nparts / bn_parts_floats: the fused BatchNorm-backward sums (HeadParams::bn_y set), else null / 0
 int launch_head_bwd(HeadParams& p, float* dw, float* db, void* workspace, long workspace_bytes, int dtype,
-                    hipStream_t stream, int* bn_nparts = nullptr, long bn_parts_floats = 0);
+                    hipStream_t stream, int* bn_nparts, long bn_parts_floats);
 int launch_pack_conv3x3(const float* w, void* wf, void* wd, int Co, int Ci, int dtype, hipStream_t stream);
 int launch_pack_convT2x2(const float* w, void* wf, void* wd, int Ci, int Co, int dtype, hipStream_t stream);
 int launch_pack_many(const void* table_dev, int n, long total, int dtype, hipStream_t stream);
 int launch_adam_step(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
                      double beta2, double eps, long step, double grad_scale, int dtype, hipStream_t stream);   // optim.hip
 int launch_stats_colsum(const float* parts, int nparts, int ctotal, int c0, int c, float* out, hipStream_t stream);
-long channel_sum_workspace_bytes(long P, int C);
 int launch_channel_sum(const void* x, int ldx, float* out, void* workspace, long workspace_bytes, long P, int C,
                        int dtype, hipStream_t stream);
 

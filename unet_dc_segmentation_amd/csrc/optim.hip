@@ -6,7 +6,7 @@
 //   m <- m + (1 - b1) (g - m);  v <- b2 v + (1 - b2) g g;  p <- p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   (the formulation of torch's _fused_adam_; g is first scaled by `gscale`, the 1/G of a SUM all-reduce)
 //
-// Work decomposition = the one of pack_many_kernel (elementwise.hip): a device-resident descriptor table; a workgroup
+// Work decomposition = the one of pack_many_kernel (pack.hip): a device-resident descriptor table; a workgroup
 // owns one 32 x 32 (out x in) channel tile of a packed tensor with all its taps -- it streams g, p, m, v of that tile in
 // the parameter's own contiguous rows, writes p, m, v back in place and the two packed images from an LDS copy of the
 // NEW p -- or 4096 consecutive elements of an unpacked tensor (biases, BatchNorm affine, first layer, head).

@@ -166,11 +166,10 @@ class _Stage:
             self.stat_rows = lib.unetdc_conv3x3_stats_rows(self.npix, cout)
             img = eng.weights.conv[(block, idx)]
             self.w_fwd, self.w_dgrad = img["w_fwd"], img["w_dgrad"]
-        self.stats = torch.empty((self.stat_rows + 64) * 2 * cout, **f32)
+        self.stats = torch.empty(_lib.partial_floats(self.stat_rows, 2 * cout), **f32)
         self.scale, self.shift = torch.empty(cout, **f32), torch.empty(cout, **f32)
         self.mean, self.rstd = torch.empty(cout, **f32), torch.empty(cout, **f32)
-        # BatchNorm-backward partial sums produced by the dgrad kernel that writes this stage's
-        # incoming gradient (fused reduction); rows = 256-pixel blocks, 64 spare rows for the 2nd stage
+        # BatchNorm-backward partial sums of the dgrad kernel that writes this stage's incoming gradient: rows = 256-pixel blocks
         self.bwd_rows = lib.unetdc_conv3x3_stats_rows(self.npix, cout)
         self.bwd_parts, self.bwd_nparts, self.bwd_coeffs = None, 0, None
         # the plan: kernel forms and the tensors they read and write
@@ -456,7 +455,7 @@ class UNetEngine:
     def _bnstats_args(self, st):
         """Arguments describing the stage whose BatchNorm-backward reduction a dgrad epilogue fuses."""
         if st.bwd_parts is None:
-            st.bwd_parts = torch.empty((st.bwd_rows + 64) * 3 * st.cout, device=self.device, dtype=torch.float32)
+            st.bwd_parts = torch.empty(_lib.partial_floats(st.bwd_rows, 3 * st.cout), device=self.device, dtype=torch.float32)
         return (st.y.data_ptr(), st.y.stride(0), st.scale.data_ptr(), st.shift.data_ptr(), st.mean.data_ptr(),
                 st.rstd.data_ptr(), st.bwd_parts.data_ptr(), st.bwd_parts.numel(), _byref(self._np))
 
