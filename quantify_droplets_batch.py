@@ -1,49 +1,29 @@
 #!/usr/bin/env python3
-"""Batch inference + droplet quantification -- drop-in for the reference's
-``quantify_droplets_batch.py`` (same CLI flags: the Tk/Qt front-ends build this argv,
-gui.py:26-39, gui_qt.py:372-400; same output files and CSV columns, outputs/all_droplets.csv:1).
+"""Batch inference + droplet quantification -- drop-in for the reference's ``quantify_droplets_batch.py`` (same CLI
+flags: the Tk/Qt front-ends build this argv, gui.py:26-39, gui_qt.py:372-400; same output files and CSV columns,
+outputs/all_droplets.csv:1).  ``--help`` describes every flag, DESIGN.md sections 10 to 17 every stage.
 
-Flow (reference lines): load_model :34-37 -> preprocess :40-46 (RGB, rolling ball, resize 512, /255)
--> run_batch :48-79 (model(batch) under no_grad, ``> thresh`` on the probabilities, nearest resize
-to the original size, mask PNG, per-image CSV) -> quantify :81-95 (4-connected components, area
-filter, area / equivalent diameter / centroid) -> summary CSV / XLSX / histogram :163-199.
-The network runs on the HIP kernels when a GPU is present (``DEVICE = "cuda"``), otherwise on
-PyTorch-CPU exactly like the reference.  On the GPU the threshold, the nearest-neighbour resize to the original
-size, the connected-component labelling and the per-droplet sums run on the device as well
-(unet_dc_segmentation_amd/droplets.py, csrc/ccl.hip): only the uint8 mask and three integers per droplet are
-copied back.  cv2 / scikit-image are optional on the CPU path: SciPy's ``ndimage.label`` with its default
-cross-shaped structure is skimage's ``label(connectivity=1)``; the resize of the mask to the original size reproduces what the
-reference's call computes (its interpolation flag sits in the positional slot of ``dst``, so OpenCV's default 8-bit bilinear
-runs on the {0,1} mask: unet_dc_segmentation_amd/droplets.py:MASK_RESIZE).
-``--split_touching`` counts a droplet per basin of the mask's distance transform instead of per connected component
-("Splitting touching droplets": csrc/split.hip on the device, utils/droplet_split.py on the CPU) and writes a
-16-bit label image next to every mask.
-``--droplet_shape`` adds the shape and intensity columns of DESIGN.md section 11 to every droplet table (perimeter,
-circularity, axes, eccentricity, orientation, bounding box, touches_border, intensity of the original image): exact integers
-per droplet from csrc/shape.hip on the device or utils/droplet_shape.py on the CPU, one derivation for both.
-``--gt_dir D`` scores every image against its annotated mask D/NAME.* (DESIGN.md section 12): the overlap table of the
-predicted and the annotated label map from csrc/match.hip on the device or utils/droplet_match.py on the CPU, one derivation
-for both; adds gt_label / gt_iou / gt_covered to the droplet tables and writes gt_droplets.csv and match_per_image.csv.
-``--prob_thresh_low T`` / ``--fill_holes [N]`` clean the mask before anything reads it: hysteresis
-thresholding between T and --prob_thresh, then holes of at most N pixels (any size without N) are filled; csrc/clean.hip on the
-device, utils/droplet_clean.py on the CPU.  The cleaned mask is the one every output sees; mask_clean_per_image.csv says
-what was changed per image.
-``--thresh_sweep [K]`` (with ``--gt_dir``) scores the raw thresholded mask against the annotation, pixel by pixel, at the K
-thresholds k / K in one pass per image (csrc/sweep.hip on the device, utils/threshold_sweep.py on the
-CPU) and writes threshold_sweep.csv pooled over all images; ``--sweep_objects T[,T...]`` repeats the droplet stage and the
-matching of ``--gt_dir`` at the listed thresholds on the probabilities already computed and writes
-threshold_sweep_objects.csv.
-``--tile [T]`` / ``--tile_overlap O`` run the network at the image's NATIVE resolution instead of on the 512 x 512 squash
-(DESIGN.md section 15): the rolling-ball-corrected image is cut into overlapping T x T tiles (512 without T, overlap 64), the tiles
-go through the network ``--batch`` at a time, and their probabilities are blended into one map of the image's size
-(csrc/tile.hip and unet_dc_segmentation_amd/tiling.py on the device, utils/tiling.py on the CPU, one derivation for both);
-every option above then works on that map.  Meant for checkpoints trained at the scale they are applied at.
-``--tta [N]`` averages the network over N flipped and rotated variants of every input (N in 1, 2, 4, 8; 8
-without N): the variants go through the network ``--batch`` items at a time, every output is mapped back and the mean is the
-probability map that every option above reads (csrc/tta.hip and unet_dc_segmentation_amd/tta.py on the device, utils/tta.py on
-the CPU, one derivation for both); with ``--tile`` the variants are those of every tile.
+main() validates the options into one Run, then per batch: decode and preprocess (rolling ball, resize to 512, /255) ->
+run_batch (the network; --tta averages it over flips and rotations; --tile runs it on native-size tiles instead and blends
+them) -> finish_batch (threshold, resize of the mask to the image's size, optional cleaning, components or split droplets,
+tables, optional shape columns, matching against annotations, threshold sweep, density maps, the per-image files) -> the
+summary files.  With a GPU (``DEVICE = "cuda"``) every stage behind the decode runs in HIP kernels and only the uint8 mask
+and a few integers per droplet come back:
+
+    preprocessing     unet_dc_segmentation_amd/preprocess.py    csrc/preprocess.hip     CPU: utils/data_loader.py
+    tiles, blend      unet_dc_segmentation_amd/tiling.py        csrc/tile.hip           CPU: utils/tiling.py
+    --tta             unet_dc_segmentation_amd/tta.py           csrc/tta.hip            CPU: utils/tta.py
+    mask, droplets    unet_dc_segmentation_amd/droplets.py      csrc/ccl.hip            CPU: droplets_cpu() here (SciPy)
+    cleaning, split   (droplets.py)                             csrc/clean.hip split.hip  CPU: utils/droplet_clean.py, droplet_split.py
+    shape columns     (droplets.py)                             csrc/shape.hip          CPU: utils/droplet_shape.py
+    --gt_dir, sweep   unet_dc_segmentation_amd/evaluate.py      csrc/match.hip sweep.hip  CPU: utils/droplet_match.py, threshold_sweep.py
+    --density_maps    unet_dc_segmentation_amd/density.py       csrc/density.hip        CPU: utils/density.py
+
+Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
+device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
 """
 import argparse
+import dataclasses
 from pathlib import Path
 
 import numpy as np
@@ -52,7 +32,7 @@ import torch
 from PIL import Image
 
 from models.model_2 import UNetDC
-from unet_dc_segmentation_amd.droplets import resize_mask_like_reference
+from unet_dc_segmentation_amd.droplets import DropletOptions, Droplets, resize_mask_like_reference
 from utils.data_loader import resize_image, rolling_ball_correction_rgb
 
 DEVICE = "cuda" if torch.cuda.is_available() else "cpu"
@@ -90,21 +70,71 @@ def preprocess(path, background_radius, im=None, keep_rgb=False):
     return torch.from_numpy(im).permute(2, 0, 1), (oh, ow)
 
 
-def predict_tiled_image(model, im, background_radius, tile, batch, keep_rgb=False, tta=None):
+@dataclasses.dataclass
+class Run:
+    """One invocation: the validated options, where the outputs go, and what accumulates over the images.  Built once in
+    main(); nothing in it belongs to a single batch."""
+    thresh: float
+    min_area: int
+    px_per_um: float | None
+    background_radius: int
+    batch_size: int
+    split_depth: float | None          # --split_touching: the depth in pixels, None without the flag
+    shape: bool                        # --droplet_shape
+    clean: dict | None                 # clean_options(); its "rows" collect mask_clean_per_image.csv
+    sweep: dict | None                 # sweep_options(); its "hist" / "object_images" collect the sweep's tables
+    tile: dict | None                  # tile_options()
+    tta: dict | None                   # tta_options()
+    density: dict | None               # --density_maps: {"nb_layers", "kernel"}
+    gt: dict | None                    # --gt_dir: {"files", "min_area", "labels"}
+    out_dir: Path
+    mask_dir: Path
+    overlay_dir: Path | None
+    writers: tuple                     # (writer pool, deque of pending writes, how many may be pending)
+    rows: list = dataclasses.field(default_factory=list)           # summary_per_image.csv
+    tables: list = dataclasses.field(default_factory=list)         # all_droplets.csv, one table per image
+    density_rows: list = dataclasses.field(default_factory=list)   # density_per_image.csv
+    gt_tables: list = dataclasses.field(default_factory=list)      # gt_droplets.csv, one table per image
+    gt_images: list = dataclasses.field(default_factory=list)      # match_per_image.csv: (filename, integers)
+
+    def droplet_options(self, labels, shape):
+        """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
+        route (unetdc_ccl_labels), so asking for labels selects that route."""
+        c = self.clean or {"low": None, "holes": 0}
+        return DropletOptions(self.split_depth, shape or (labels and self.split_depth is None), labels, c["low"], c["holes"])
+
+    def submit(self, fn, *args):
+        """PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
+        the writer pool (main() waits for them before the summary is written)."""
+        self.writers[1].append(self.writers[0].submit(fn, *args))
+
+
+@dataclasses.dataclass
+class Batch:
+    """What one forward and the stages behind it read, made fresh for every batch: entry i of every list is image i."""
+    meta: list = dataclasses.field(default_factory=list)       # (path, (oh, ow))
+    tensors: list = dataclasses.field(default_factory=list)    # network inputs (none under --tile)
+    grays: list = dataclasses.field(default_factory=list)      # --droplet_shape: the ORIGINAL image as grey, uint8 [oh, ow]
+    rgbs: list = dataclasses.field(default_factory=list)       # --density_maps: the decoded image (a device tensor on the GPU)
+    gt_items: list = dataclasses.field(default_factory=list)   # --gt_dir: the decoded annotations
+
+
+def predict_tiled_image(model, im, run):
     """--tile: decoded image -> (probabilities [1, 1, H, W] at the image's own size, the original image for the density maps or
-    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, `batch` per forward, and the blend.
-    tta: the options of --tta, every tile's probabilities are then the mean over its variants."""
-    more = {} if tta is None else {"tta": tta["N"]}
+    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, run.batch_size per forward, and the blend.
+    With --tta every tile's probabilities are the mean over its variants."""
+    more = {} if run.tta is None else {"tta": run.tta["N"]}
+    tile, radius, keep_rgb = run.tile, run.background_radius, run.density is not None
     if DEVICE == "cuda":
         from unet_dc_segmentation_amd.preprocess import MAX_ELEMENT, _upload, rolling_ball_device
         from unet_dc_segmentation_amd.tiling import predict_tiled
-        host_ball = int(background_radius) > MAX_ELEMENT     # the element does not fit the kernel's LDS tile: host operator
+        host_ball = int(radius) > MAX_ELEMENT                # the element does not fit the kernel's LDS tile: host operator
         rgb = _upload(im, DEVICE) if keep_rgb or not host_ball else None
-        corrected = (_upload(rolling_ball_correction_rgb(im, int(background_radius)), DEVICE) if host_ball
-                     else rolling_ball_device(rgb, background_radius))
-        return predict_tiled(model, corrected, tile["T"], tile["O"], batch, **more)[None, None], rgb
+        corrected = (_upload(rolling_ball_correction_rgb(im, int(radius)), DEVICE) if host_ball
+                     else rolling_ball_device(rgb, radius))
+        return predict_tiled(model, corrected, tile["T"], tile["O"], run.batch_size, **more)[None, None], rgb
     from utils.tiling import predict_tiled_cpu
-    p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, background_radius), tile["T"], tile["O"], batch, **more)
+    p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, radius), tile["T"], tile["O"], run.batch_size, **more)
     return torch.from_numpy(p)[None, None], (im if keep_rgb else None)
 
 
@@ -123,14 +153,6 @@ def _droplet_table(area, cen_row, cen_col, px_per_um):
     return df
 
 
-def quantify_split(bin_mask, min_area, px_per_um, split_depth):
-    """CPU path of --split_touching: (the per-droplet table of the split droplets, their int32 label map)."""
-    from utils.droplet_split import half_pixels, split_labels
-    labels, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
-    d = np.maximum(area, 1)
-    return _droplet_table(area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, px_per_um), labels
-
-
 def add_shape_columns(df, props, hw, px_per_um):
     """--droplet_shape: the columns of utils.droplet_shape.shape_columns behind the table's own."""
     if df.empty:
@@ -141,24 +163,50 @@ def add_shape_columns(df, props, hw, px_per_um):
     return df
 
 
-def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
-    """CPU path of --droplet_shape: (table with the shape columns, label map or None without a split depth).  Centroids are
-    the integer sums over the area, as on the device."""
+def _components(bin_mask, min_area):
+    """(area, centroid_row, centroid_col) of the 4-connected components of at least min_area pixels, in label order (SciPy:
+    ``ndimage.label`` with its default cross-shaped structure is skimage's ``label(connectivity=1)``)."""
     from scipy import ndimage
-    from utils.droplet_shape import label_props_numpy
+    lbl, n = ndimage.label(bin_mask)                     # 4-connectivity, labels in raster order of the first pixel
+    if n:
+        areas = np.bincount(lbl.ravel(), minlength=n + 1)
+        keep = areas >= min_area
+        keep[0] = False
+        lbl, n = ndimage.label(keep[lbl])
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(0), np.zeros(0)
+    area = np.bincount(lbl.ravel(), minlength=n + 1)[1:]
+    cen = np.array(ndimage.center_of_mass(np.ones_like(lbl), lbl, np.arange(1, n + 1))).reshape(n, 2)
+    return area, cen[:, 0], cen[:, 1]
+
+
+def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False):
+    """CPU path: the record that droplets.mask_and_droplets_batch returns per image, in host arrays, from the uint8 mask at
+    the image's size.  split_depth: the split droplets (utils/droplet_split.py); shape: the integers of
+    utils.droplet_shape.label_props_numpy on the label map and the grey plane, centroids then the integer sums over the
+    area as on the device; labels: the int32 label map whose numbers are the rows of the table."""
+    lab = None
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
-        labels = split_labels(bin_mask, half_pixels(split_depth), min_area)[0]
-    else:
-        labels, n = ndimage.label(bin_mask)
-        if n:
-            keep = np.bincount(labels.ravel(), minlength=n + 1) >= max(min_area, 1)
-            keep[0] = False
-            labels = ndimage.label(keep[labels])[0]
-    props = label_props_numpy(labels, gray)
-    d = np.maximum(props["area"], 1)
-    df = _droplet_table(props["area"], props["Sy"].astype(np.float64) / d, props["Sx"].astype(np.float64) / d, px_per_um)
-    return add_shape_columns(df, props, bin_mask.shape, px_per_um), (labels if split_depth is not None else None)
+        lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
+    elif shape or labels:
+        from utils.droplet_match import gt_labels_numpy
+        lab = gt_labels_numpy(bin_mask, min_area)
+    if shape:
+        from utils.droplet_shape import label_props_numpy
+        props = label_props_numpy(lab, gray)
+        area, sy, sx = props["area"], props["Sy"], props["Sx"]
+    elif split_depth is None:
+        return Droplets(bin_mask, *_components(bin_mask, min_area), labels=lab)
+    d = np.maximum(area, 1)
+    return Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None)
+
+
+def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
+    """CPU path of --droplet_shape: (table with the shape columns, label map or None without a split depth)."""
+    d = droplets_cpu(bin_mask, min_area, split_depth, True, gray)
+    df = add_shape_columns(_droplet_table(d.area, d.centroid_row, d.centroid_col, px_per_um), d.props, bin_mask.shape, px_per_um)
+    return df, (d.labels if split_depth is not None else None)
 
 
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".tif", ".tiff")
@@ -189,15 +237,6 @@ def decode_gt(path, as_labels):
     return np.array(im if im.mode in ("1", "L", "P", "I", "I;16", "I;16B") else im.convert("I")).astype(np.int32)
 
 
-def pred_labels_cpu(bin_mask, min_area, split_depth):
-    """CPU path of --gt_dir: the int32 label map whose numbers are the rows of the droplet table."""
-    if split_depth is not None:
-        from utils.droplet_split import half_pixels, split_labels
-        return split_labels(bin_mask, half_pixels(split_depth), min_area)[0]
-    from utils.droplet_match import gt_labels_numpy
-    return gt_labels_numpy(bin_mask, min_area)
-
-
 def match_cpu(labels, area, gt_item, gt_min_area, gt_are_labels):
     """CPU path of --gt_dir for one image: what unet_dc_segmentation_amd.evaluate.match_batch returns per image."""
     from utils import droplet_match as dm
@@ -208,42 +247,29 @@ def match_cpu(labels, area, gt_item, gt_min_area, gt_are_labels):
             "columns": dm.match_columns(area, garea, a, b, n)}
 
 
-def add_match_outputs(gt, df, res, filename):
+def add_match_outputs(run, df, res, filename):
     """--gt_dir: the three columns behind the droplet table's own, this image's rows of gt_droplets.csv and its integers."""
     from utils.droplet_match import gt_table
     if not df.empty:
         for name, col in res["columns"]["pred"].items():
             df[name] = col
-    gt["tables"].append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], res["columns"]["gt"])))
-    gt["images"].append((filename, res["columns"]["image"]))
+    run.gt_tables.append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], res["columns"]["gt"])))
+    run.gt_images.append((filename, res["columns"]["image"]))
     return df
 
 
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
     """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
     split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
-    if split_depth is not None:
-        return quantify_split(bin_mask, min_area, px_per_um, split_depth)[0]
-    from scipy import ndimage
-    lbl, n = ndimage.label(bin_mask)                     # 4-connectivity, labels in raster order of the first pixel
-    if n:
-        areas = np.bincount(lbl.ravel(), minlength=n + 1)
-        keep = areas >= min_area
-        keep[0] = False
-        lbl, n = ndimage.label(keep[lbl])
-    if n == 0:
-        return pd.DataFrame()
-    idx = np.arange(1, n + 1)
-    area = np.bincount(lbl.ravel(), minlength=n + 1)[1:]
-    cen = np.array(ndimage.center_of_mass(np.ones_like(lbl), lbl, idx)).reshape(n, 2)
-    return _droplet_table(area, cen[:, 0], cen[:, 1], px_per_um)
+    _, area, cy, cx = droplets_cpu(bin_mask, min_area, split_depth)
+    return _droplet_table(area, cy, cx, px_per_um)
 
 
 def quantify_device(probs2d, thresh, out_hw, min_area, px_per_um):
     """The same table from the probability map still on the HIP device; also returns the uint8 mask (host) for the PNG."""
     from unet_dc_segmentation_amd.droplets import mask_and_droplets
-    mask, area, cy, cx = mask_and_droplets(probs2d, thresh, out_hw, min_area)
-    return mask.cpu().numpy(), _droplet_table(area, cy, cx, px_per_um)
+    d = mask_and_droplets(probs2d, thresh, out_hw, min_area)
+    return d.mask.cpu().numpy(), _droplet_table(d.area, d.centroid_row, d.centroid_col, px_per_um)
 
 
 def _outline(mask):
@@ -268,163 +294,132 @@ def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels=None):
         Image.fromarray(img).save(str(overlay_dir / f"{name}_overlay.png"))
 
 
-def _density(density, dres, rgb, mask, fpath, name, writers):
+def _density(run, dres, rgb, mask, fpath):
     """--density_maps for one image: the row of density_per_image.csv, and the two heat-map PNGs (colormap gather and deflate
     in the writer pool).  dres: the device results of the batch for this image, or None on the CPU path."""
     from utils import density as hd
-    r = hd.density_maps(rgb, mask, density["nb_layers"], density["kernel"]) if dres is None else dres
-    density["rows"].append(hd.csv_row(Path(fpath).name, r, density["nb_layers"]))
-    job = (hd.write_pngs, r["radial_index"], r["spatial_index"], density["out_dir"], name)
-    if writers is None:
-        job[0](*job[1:])
-    else:
-        writers[1].append(writers[0].submit(*job))
+    nb_layers = run.density["nb_layers"]
+    r = hd.density_maps(rgb, mask, nb_layers, run.density["kernel"]) if dres is None else dres
+    run.density_rows.append(hd.csv_row(Path(fpath).name, r, nb_layers))
+    run.submit(hd.write_pngs, r["radial_index"], r["spatial_index"], run.out_dir, Path(fpath).stem)
 
 
-def _cpu_mask(p2, thresh, ow, oh, clean):
-    """CPU path: probabilities [h, w] (numpy fp32) -> the mask every stage sees at one threshold (resize, then the cleaning
-    options of the run)."""
+def _cpu_mask(p2, thresh, hw, clean):
+    """CPU path: probabilities [h, w] (numpy fp32) -> (the mask every stage sees at one threshold: resize, then the cleaning
+    options of the run; the int64 [4] counts of the cleaning, zeros without)."""
+    oh, ow = hw
     mask = resize_mask_like_reference((p2 > np.float32(thresh)).astype(np.uint8), ow, oh)
-    if clean is not None:
-        from utils.droplet_clean import clean_mask
-        weak = None
-        if clean["low"] is not None:
-            weak = resize_mask_like_reference((p2 > np.float32(clean["low"])).astype(np.uint8), ow, oh)
-        mask = clean_mask(mask, weak, clean["holes"])[0]
-    return mask
+    if clean is None:
+        return mask, np.zeros(4, np.int64)
+    from utils.droplet_clean import clean_mask
+    weak = None                                          # both masks under the same resize rule
+    if clean["low"] is not None:
+        weak = resize_mask_like_reference((p2 > np.float32(clean["low"])).astype(np.uint8), ow, oh)
+    return clean_mask(mask, weak, clean["holes"])
 
 
-def sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean):
+def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
+    """The droplet stage at one threshold, and with --gt_dir the matching of its label maps against the batch's annotations
+    -> (one Droplets per image, one match result per image or None, the density stage's device sums or None).  On the
+    device the whole batch is enqueued back to back with ONE host wait (droplets.py), and one more for the matching; on the
+    CPU the same records come from droplets_cpu and match_cpu.  sweeping: a threshold of --sweep_objects, where only the
+    matching is read: no shape columns, no grey planes."""
+    gt, hws = run.gt, [m[1] for m in batch.meta]
+    want_labels = gt is not None or run.split_depth is not None
+    shape = run.shape and not sweeping
+    if probs.is_cuda:
+        from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
+        gray = [torch.from_numpy(g).to(DEVICE) for g in batch.grays] if shape else None   # up behind the network's launches
+        out, sums = mask_and_droplets_batch(probs[:, 0], thresh, hws, run.min_area, keep_sums=True, gray=gray,
+                                            options=run.droplet_options(want_labels, shape))
+        if gt is None:
+            return out, None, sums
+        from unet_dc_segmentation_amd.evaluate import match_batch
+        return out, match_batch([d.labels for d in out], [d.area for d in out], batch.gt_items, gt["min_area"], gt["labels"]), sums
+    out, p = [], probs[:, 0].numpy()
+    for i, hw in enumerate(hws):
+        mask, counts = _cpu_mask(p[i], thresh, hw, run.clean)
+        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels)
+        d.clean_counts = np.asarray(counts, np.int64)
+        out.append(d)
+    if gt is None:
+        return out, None, None
+    return out, [match_cpu(d.labels, d.area, item, gt["min_area"], gt["labels"]) for d, item in zip(out, batch.gt_items)], None
+
+
+def sweep_step(run, batch, probs):
     """--thresh_sweep for one batch: the batch's probabilities against its annotations at every threshold of the grid, added
     into the run's histogram (on the device: unetdc_thresh_sweep, nothing waits; on the CPU: sweep_hist_numpy).  Then, for
     every threshold of --sweep_objects, the droplet stage with the run's own split / clean options and the matching of
     --gt_dir once more on the same probabilities: the integers of one match_per_image.csv row per image and threshold."""
-    hws = [m[1] for m in meta]
+    sweep, hws = run.sweep, [m[1] for m in batch.meta]
     if probs.is_cuda:
-        from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
-        from unet_dc_segmentation_amd.evaluate import match_batch, sweep_batch
-        sweep["hist"] = sweep_batch(probs[:, 0], gt["items"], hws, sweep["K"], hist=sweep["hist"])
-        opts = {"shape": True, "return_labels": True} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
-        if clean is not None:
-            opts.update(thresh_low=clean["low"], max_hole_area=clean["holes"])
-        for t in sweep["objects"]:
-            out = mask_and_droplets_batch(probs[:, 0], t, hws, min_area, **opts)
-            res = match_batch([o[4] for o in out], [o[1] for o in out], gt["items"], gt["min_area"], gt["labels"])
-            sweep["object_images"][t].extend(r["columns"]["image"] for r in res)
-        return
-    from utils.droplet_match import label_sums
-    from utils.threshold_sweep import sweep_hist_numpy
-    p = probs[:, 0].numpy()
-    for i, (oh, ow) in enumerate(hws):
-        h = sweep_hist_numpy(p[i], gt["items"][i], (oh, ow), sweep["K"])
-        sweep["hist"] = h if sweep["hist"] is None else sweep["hist"] + h
-        for t in sweep["objects"]:
-            plab = pred_labels_cpu(_cpu_mask(p[i], t, ow, oh, clean), min_area, split_depth)
-            res = match_cpu(plab, label_sums(plab)[0], gt["items"][i], gt["min_area"], gt["labels"])
-            sweep["object_images"][t].append(res["columns"]["image"])
+        from unet_dc_segmentation_amd.evaluate import sweep_batch
+        sweep["hist"] = sweep_batch(probs[:, 0], batch.gt_items, hws, sweep["K"], hist=sweep["hist"])
+    else:
+        from utils.threshold_sweep import sweep_hist_numpy
+        for p2, item, hw in zip(probs[:, 0].numpy(), batch.gt_items, hws):
+            h = sweep_hist_numpy(p2, item, hw, sweep["K"])
+            sweep["hist"] = h if sweep["hist"] is None else sweep["hist"] + h
+    for t in sweep["objects"]:
+        res = droplets_and_matches(run, batch, probs, t, sweeping=True)[1]
+        sweep["object_images"][t].extend(r["columns"]["image"] for r in res)
 
 
 @torch.no_grad()
-def run_batch(tensors, meta, model, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-              density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None, tta=None):
-    batch = torch.stack(tensors).to(DEVICE)
-    if tta is None:
-        probs = model(batch)                             # sigmoid probabilities (model_2.py:80)
-    elif batch.is_cuda:                                  # --tta: the mean over the variants, tta["batch"] items per forward
+def run_batch(run, batch, model):
+    x = torch.stack(batch.tensors).to(DEVICE)
+    if run.tta is None:
+        probs = model(x)                                 # sigmoid probabilities (model_2.py:80)
+    elif x.is_cuda:                                      # --tta: the mean over the variants, tta["batch"] items per forward
         from unet_dc_segmentation_amd.tta import predict_tta
-        probs = predict_tta(model, batch, tta["N"], tta["batch"])
+        probs = predict_tta(model, x, run.tta["N"], run.tta["batch"])
     else:
         from utils.tta import predict_tta_cpu
-        probs = predict_tta_cpu(model, batch, tta["N"], tta["batch"])
-    finish_batch(probs, meta, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers, density,
-                 split_depth, shape, gt, clean, sweep)
+        probs = predict_tta_cpu(model, x, run.tta["N"], run.tta["batch"])
+    finish_batch(run, batch, probs)
 
 
-def finish_batch(probs, meta, mask_dir, overlay_dir, thresh, min_area, px_per_um, per_image_rows, all_props, writers=None,
-                 density=None, split_depth=None, shape=None, gt=None, clean=None, sweep=None):
-    """Everything behind the forward: probs [B, 1, ph, pw] (on the device or not) -> masks of the sizes in meta, droplet tables,
-    the optional stages and the per-image files.  run_batch feeds it the network-size maps, --tile one native-size map per image
-    (ph, pw equal to the image's size: every resize rule is then the identity)."""
-    on_device = probs.is_cuda
-    if sweep is not None:                                # --thresh_sweep: the raw mask at every threshold, pooled
-        sweep_step(sweep, probs, meta, gt, min_area, split_depth, clean)
-    masks512 = None if on_device else (probs[:, 0] > thresh).to(torch.uint8).numpy()
-    weak512 = None                                       # --prob_thresh_low on the CPU path: the mask of the low threshold
-    if clean is not None and clean["low"] is not None and not on_device:
-        weak512 = (probs[:, 0] > clean["low"]).to(torch.uint8).numpy()
-    clean_counts = []
-    if on_device:                                        # the whole batch enqueued back to back, ONE host wait (droplets.py)
-        from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
-        split = {} if split_depth is None else {"split_depth": split_depth, "return_labels": True}
-        if shape is not None:                            # the grey planes go up behind the network's launches
-            split.update(shape=True, gray=[torch.from_numpy(g).to(DEVICE) for g in shape["grays"]])
-        if gt is not None and split_depth is None:       # the label maps come through the shape route; its rows may go unused
-            split.update(shape=True, return_labels=True)
-        if clean is not None:                            # the counts ride in the copy of the droplet counts
-            split.update(thresh_low=clean["low"], max_hole_area=clean["holes"], clean_counts=clean_counts)
-        if density is None:
-            dev_out = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, **split)
-        else:                                            # the maps count every component: the table's sums serve when min_area <= 1
-            from unet_dc_segmentation_amd.density import density_maps_batch
-            dev_out, sums = mask_and_droplets_batch(probs[:, 0], thresh, [m[1] for m in meta], min_area, keep_sums=True, **split)
-            # ... and when the table is not one of split droplets: the maps keep counting connected components
-            dres = density_maps_batch(density["rgbs"], [o[0] for o in dev_out], sums if min_area <= 1 and not split else None,
-                                      density["nb_layers"], density["kernel"])
-        if gt is not None:                               # the batch's annotations against its label maps: one more host wait
-            from unet_dc_segmentation_amd.evaluate import match_batch
-            mres = match_batch([o[4] for o in dev_out], [o[1] for o in dev_out], gt["items"], gt["min_area"], gt["labels"])
-    for i in range(len(meta)):
-        fpath, (oh, ow) = meta[i]
-        name = Path(fpath).stem
-        labels = None
-        if on_device:
-            mask_d, area, cy, cx = dev_out[i][:4]
-            mask, df = mask_d.cpu().numpy(), _droplet_table(area, cy, cx, px_per_um)
-            if split_depth is not None:
-                labels = dev_out[i][4].cpu().numpy()
-            if shape is not None:
-                df = add_shape_columns(df, dev_out[i][-1], (oh, ow), px_per_um)
-        else:
-            mask = resize_mask_like_reference(masks512[i], ow, oh)
-            if clean is not None:                        # both masks under the same resize rule, then utils/droplet_clean.py
-                from utils.droplet_clean import clean_mask
-                weak = None if weak512 is None else resize_mask_like_reference(weak512[i], ow, oh)
-                mask, counts = clean_mask(mask, weak, clean["holes"])
-                clean_counts.append(counts)
-            if shape is not None:
-                df, labels = quantify_shape(mask, min_area, px_per_um, split_depth, shape["grays"][i])
-            elif split_depth is None:
-                df = quantify(mask, min_area, px_per_um)
-            else:
-                df, labels = quantify_split(mask, min_area, px_per_um, split_depth)
-        if gt is not None:
-            if on_device:
-                res = mres[i]
-            else:
-                plab = labels if labels is not None else pred_labels_cpu(mask, min_area, split_depth)
-                res = match_cpu(plab, df["area"].to_numpy() if not df.empty else np.zeros(0, np.int64), gt["items"][i],
-                                gt["min_area"], gt["labels"])
-            df = add_match_outputs(gt, df, res, Path(fpath).name)
-        if clean is not None:
+def _host(x):
+    return x.cpu().numpy() if torch.is_tensor(x) else x
+
+
+def finish_batch(run, batch, probs):
+    """Everything behind the forward: probs [B, 1, ph, pw] (on the device or not) -> masks of the sizes in batch.meta, droplet
+    tables, the optional stages and the per-image files.  run_batch feeds it the network-size maps, --tile one native-size map
+    per image (ph, pw equal to the image's size: every resize rule is then the identity)."""
+    if run.sweep is not None:                            # --thresh_sweep: the raw mask at every threshold, pooled
+        sweep_step(run, batch, probs)
+    out, mres, sums = droplets_and_matches(run, batch, probs, run.thresh)
+    dres = None
+    if run.density is not None and probs.is_cuda:
+        from unet_dc_segmentation_amd.density import density_maps_batch
+        # the maps count every connected component: the table's sums serve when min_area <= 1 and no option changed the stage
+        plain = run.split_depth is None and not run.shape and run.gt is None and run.clean is None
+        dres = density_maps_batch(batch.rgbs, [d.mask for d in out], sums if run.min_area <= 1 and plain else None,
+                                  run.density["nb_layers"], run.density["kernel"])
+    for i, (d, (fpath, hw)) in enumerate(zip(out, batch.meta)):
+        filename, name = Path(fpath).name, Path(fpath).stem
+        mask = _host(d.mask)
+        labels = _host(d.labels) if run.split_depth is not None else None       # --split_touching writes them
+        df = _droplet_table(d.area, d.centroid_row, d.centroid_col, run.px_per_um)
+        if run.shape:
+            df = add_shape_columns(df, d.props, hw, run.px_per_um)
+        if mres is not None:
+            df = add_match_outputs(run, df, mres[i], filename)
+        if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
-            clean["rows"].append({"filename": Path(fpath).name, **{k: int(v) for k, v in zip(COUNT_NAMES, clean_counts[i])}})
-        df.insert(0, "filename", Path(fpath).name) if not df.empty else None
-        all_props.append(df)
-        per_image_rows.append({"filename": Path(fpath).name, "droplet_count": len(df),
-                               "total_area_px": df["area"].sum() if not df.empty else 0})
-        # PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
-        # the writer pool (same files, same contents; main() waits for them before the summary is written)
-        if writers is None:
-            _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels)
-        else:
-            writers[1].append(writers[0].submit(_write_outputs, mask, df, fpath, name, mask_dir, overlay_dir, labels))
-        if density is not None:
-            _density(density, dres[i] if on_device else None, density["rgbs"][i], mask, fpath, name, writers)
-        if writers is not None:
-            # back-pressure: at most ~4 batches of masks / tables wait for the writers; waiting on the OLDEST write also surfaces a
-            # failed write while the run is still going
-            while len(writers[1]) > writers[2]:
-                writers[1].popleft().result()
+            run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
+        df.insert(0, "filename", filename) if not df.empty else None
+        run.tables.append(df)
+        run.rows.append({"filename": filename, "droplet_count": len(df), "total_area_px": df["area"].sum() if not df.empty else 0})
+        run.submit(_write_outputs, mask, df, fpath, name, run.mask_dir, run.overlay_dir, labels)
+        if run.density is not None:
+            _density(run, None if dres is None else dres[i], batch.rgbs[i], mask, fpath)
+        # back-pressure: at most ~4 batches of masks / tables wait for the writers; waiting on the OLDEST write also surfaces a
+        # failed write while the run is still going
+        while len(run.writers[1]) > run.writers[2]:
+            run.writers[1].popleft().result()
 
 
 def build_parser():
@@ -580,8 +575,7 @@ def main(argv=None):
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
-        gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels, "items": [],
-              "tables": [], "images": []}
+        gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels}
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -594,10 +588,8 @@ def main(argv=None):
         # either path: the Gaussian radius int(4 sigma + 0.5), sigma = density_kernel / 6, is at most 128
         if not 1 <= args.nb_layers <= 255 or not 0 < args.density_kernel or int(4 * args.density_kernel / 6 + 0.5) > 128:
             raise SystemExit("--nb_layers must be in 1..255 and --density_kernel in 1..192")
-        density = {"nb_layers": args.nb_layers, "kernel": args.density_kernel, "rows": [], "rgbs": [], "out_dir": out_dir}
-    shape = {"grays": []} if args.droplet_shape else None
+        density = {"nb_layers": args.nb_layers, "kernel": args.density_kernel}
     model = load_model(args.ckpt_path, args.dtype)
-    tensors, meta, per_image_rows, all_props = [], [], [], []
     # File decode runs ahead of the device and the per-image writes behind it, in two small thread pools (both are
     # zlib-bound and release the GIL); the order of the rows in the summary files is the order of `images` as before.
     import os
@@ -605,7 +597,10 @@ def main(argv=None):
     from concurrent.futures import ThreadPoolExecutor
     nthreads = max(1, min(8, (os.cpu_count() or 2) // 2))
     with ThreadPoolExecutor(nthreads) as dec_pool, ThreadPoolExecutor(nthreads) as wr_pool:
-        writers = (wr_pool, deque(), 4 * max(1, args.batch))
+        run = Run(thresh=args.prob_thresh, min_area=args.min_area, px_per_um=args.px_per_micron,
+                  background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
+                  shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
+                  mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)))
         ahead = deque()
         it = iter(images)
 
@@ -618,57 +613,40 @@ def main(argv=None):
                               None if gt is None else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"])))
 
         refill()
+        batch = Batch()
         while ahead:
             img, fut, gt_fut = ahead.popleft()
             refill()
             im = fut.result()
-            if shape is not None:                        # the ORIGINAL image as grey, before the rolling ball
+            batch.meta.append((str(img), im.shape[:2]))
+            if run.shape:                                # the ORIGINAL image as grey, before the rolling ball
                 from utils.density import rgb_to_gray
-                shape["grays"].append(rgb_to_gray(im))
-            if tile is not None:                         # native size: one map per image, the stages on a batch of one
-                if gt is not None:
-                    gt["items"].append(gt_fut.result())
-                probs, rgb = predict_tiled_image(model, im, args.background_radius, tile, args.batch, density is not None, tta)
-                if density is not None:
-                    density["rgbs"] = [rgb]
-                finish_batch(probs, [(str(img), im.shape[:2])], mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                             args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep)
-                if shape is not None:
-                    shape["grays"] = []
-                if gt is not None:
-                    gt["items"] = []
-                continue
-            if density is None:
-                t, osize = preprocess(img, args.background_radius, im)
-            else:
-                t, osize, rgb = preprocess(img, args.background_radius, im, keep_rgb=True)
-                density["rgbs"].append(rgb)
+                batch.grays.append(rgb_to_gray(im))
             if gt is not None:
-                gt["items"].append(gt_fut.result())
-            tensors.append(t)
-            meta.append((str(img), osize))
-            if len(tensors) == args.batch:
-                run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                          args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep, tta)
-                tensors, meta = [], []
-                if density is not None:
-                    density["rgbs"] = []
-                if shape is not None:
-                    shape["grays"] = []
-                if gt is not None:
-                    gt["items"] = []
-        if tensors:
-            run_batch(tensors, meta, model, mask_dir, overlay_dir, args.prob_thresh, args.min_area,
-                      args.px_per_micron, per_image_rows, all_props, writers, density, split_depth, shape, gt, clean, sweep, tta)
-        for f in writers[1]:
+                batch.gt_items.append(gt_fut.result())
+            if tile is not None:                         # native size: one map per image, the stages on a batch of one
+                probs, rgb = predict_tiled_image(model, im, run)
+                batch.rgbs.append(rgb)
+                finish_batch(run, batch, probs)
+                batch = Batch()
+                continue
+            t, _, *rgb = preprocess(img, args.background_radius, im, keep_rgb=density is not None)
+            batch.tensors.append(t)
+            batch.rgbs += rgb
+            if len(batch.tensors) == args.batch:
+                run_batch(run, batch, model)
+                batch = Batch()
+        if batch.tensors:
+            run_batch(run, batch, model)
+        for f in run.writers[1]:
             f.result()                                   # re-raises a failed write
     if density is not None:
-        pd.DataFrame(density["rows"]).to_csv(out_dir / "density_per_image.csv", index=False)
+        pd.DataFrame(run.density_rows).to_csv(out_dir / "density_per_image.csv", index=False)
     if gt is not None:
         from utils.droplet_match import pooled_row, summary_row
-        tables = [t for t in gt["tables"] if len(t)] or gt["tables"][:1]
+        tables = [t for t in run.gt_tables if len(t)] or run.gt_tables[:1]
         pd.concat(tables, ignore_index=True).to_csv(out_dir / "gt_droplets.csv", index=False) if tables else None
-        rows = [summary_row(name, ints) for name, ints in gt["images"]] + [pooled_row([ints for _, ints in gt["images"]])]
+        rows = [summary_row(name, ints) for name, ints in run.gt_images] + [pooled_row([ints for _, ints in run.gt_images])]
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
@@ -688,9 +666,9 @@ def main(argv=None):
                 row.pop("filename")
                 rows.append({"threshold": t, **row})
             pd.DataFrame(rows).to_csv(out_dir / "threshold_sweep_objects.csv", index=False)
-    summary_df = pd.DataFrame(per_image_rows)
+    summary_df = pd.DataFrame(run.rows)
     summary_df.to_csv(out_dir / "summary_per_image.csv", index=False)
-    props = [d for d in all_props if not d.empty]
+    props = [d for d in run.tables if not d.empty]
     if props:
         combined = pd.concat(props, ignore_index=True)
         combined.to_csv(out_dir / "all_droplets.csv", index=False)

@@ -185,33 +185,30 @@ def test_batch_with_mixed_sizes_equals_single_images_and_waits_once(monkeypatch)
     def item(self):
         calls["item"] += self.is_cuda
         return real_item(self)
-    counts = []
     with monkeypatch.context() as mp:
         mp.setattr(torch.Tensor, "cpu", cpu)
         mp.setattr(torch.Tensor, "item", item)
         plain = mask_and_droplets_batch(probs, 0.5, sizes, 1)
         plain_calls = dict(calls)
         calls.update(cpu=0, item=0)
-        out = mask_and_droplets_batch(probs, 0.5, sizes, 1, split_depth=2.0, return_labels=True, thresh_low=0.3, max_hole_area=200,
-                                      clean_counts=counts)
+        out = mask_and_droplets_batch(probs, 0.5, sizes, 1, split_depth=2.0, return_labels=True, thresh_low=0.3, max_hole_area=200)
         # the host waits where it did: the clean counts ride in the copy of the droplet counts
         assert calls == plain_calls == {"cpu": 3, "item": 0}
-    assert len(counts) == len(sizes) and len(out[0]) == len(plain[0]) + 1
+    counts = [o.clean_counts for o in out]
+    assert len(out) == len(sizes) and out[0].labels is not None and plain[0].labels is None
     for i, (oh, ow) in enumerate(sizes):
-        one_counts = []
-        one = mask_and_droplets(probs[i], 0.5, (oh, ow), 1, split_depth=2.0, return_labels=True, thresh_low=0.3, max_hole_area=200,
-                                clean_counts=one_counts)
-        assert torch.equal(one[0], out[i][0]) and torch.equal(one[4], out[i][4])
-        for x, y in zip(one[1:4], out[i][1:4]):
+        one = mask_and_droplets(probs[i], 0.5, (oh, ow), 1, split_depth=2.0, return_labels=True, thresh_low=0.3, max_hole_area=200)
+        assert torch.equal(one.mask, out[i].mask) and torch.equal(one.labels, out[i].labels)
+        for x, y in zip(list(one)[1:], list(out[i])[1:]):
             assert np.array_equal(x, y)
-        assert len(one_counts) == 1 and np.array_equal(one_counts[0], counts[i])
+        assert one.clean_counts.shape == (4,) and np.array_equal(one.clean_counts, counts[i])
         # ... and equal the host path on the two resized masks
         strong = resize_mask_like_reference((p[i] > 0.5).astype(np.uint8), ow, oh)
         wk = resize_mask_like_reference((p[i] > 0.3).astype(np.uint8), ow, oh)
-        assert np.array_equal(plain[i][0].cpu().numpy(), strong)
+        assert np.array_equal(plain[i].mask.cpu().numpy(), strong)
         m, c = clean_mask(strong, wk, 200)
-        assert np.array_equal(out[i][0].cpu().numpy(), m) and np.array_equal(counts[i], c)
-        assert np.array_equal(out[i][4].cpu().numpy() > 0, m > 0)
+        assert np.array_equal(out[i].mask.cpu().numpy(), m) and np.array_equal(counts[i], c)
+        assert np.array_equal(out[i].labels.cpu().numpy() > 0, m > 0)
     total = np.sum(counts, axis=0)
     assert total[0] > 0 and total[1] > 0 and total[3] > 0           # all three did something somewhere
 
@@ -227,19 +224,19 @@ def test_options_off_launch_nothing_new_and_change_nothing(monkeypatch):
     base_one = mask_and_droplets(probs[0], 0.5, sizes[0], 2)
     names, real = [], _lib.call
     monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
-    counts = []
-    off = mask_and_droplets_batch(probs, 0.5, sizes, 2, shape=True, return_labels=True, thresh_low=None, max_hole_area=0,
-                                  clean_counts=counts)
+    off = mask_and_droplets_batch(probs, 0.5, sizes, 2, shape=True, return_labels=True, thresh_low=None, max_hole_area=0)
+    counts = [o.clean_counts for o in off]
     same = mask_and_droplets_batch(probs, 0.5, sizes, 2, shape=True, return_labels=True, thresh_low=0.5)   # equal: a no-op
     off_one = mask_and_droplets(probs[0], 0.5, sizes[0], 2, thresh_low=None, max_hole_area=0)
     assert names and "unetdc_mask_clean" not in names
     assert [c.tolist() for c in counts] == [[0, 0, 0, 0]] * 2
     for got in (off, same):
         for a, b in zip(got, base):
-            assert torch.equal(a[0], b[0]) and torch.equal(a[4], b[4])
-            assert all(np.array_equal(x, y) for x, y in zip(a[1:4], b[1:4]))
-            assert a[5].keys() == b[5].keys() and all(np.array_equal(a[5][k], b[5][k]) for k in b[5])
-    assert torch.equal(off_one[0], base_one[0]) and all(np.array_equal(x, y) for x, y in zip(off_one[1:], base_one[1:]))
+            assert torch.equal(a.mask, b.mask) and torch.equal(a.labels, b.labels)
+            assert all(np.array_equal(x, y) for x, y in zip(list(a)[1:], list(b)[1:]))
+            assert a.props.keys() == b.props.keys() and all(np.array_equal(a.props[k], b.props[k]) for k in b.props)
+    assert torch.equal(off_one.mask, base_one.mask) and all(np.array_equal(x, y) for x, y in zip(list(off_one)[1:], list(base_one)[1:]))
+    assert off_one.labels is None and off_one.props is None and base_one.labels is None and base_one.props is None
     names.clear()
     mask_and_droplets_batch(probs, 0.5, sizes, 2, max_hole_area=-1)
     assert names.count("unetdc_mask_clean") == 2
@@ -256,15 +253,15 @@ def test_more_droplets_than_the_first_capacity_with_the_options_on():
     m[0, 40, 41] = 0.4                                     # a weak bridge between two of them
     m[1, 10:20, 10:20] = 0.9
     m[1, 12:15, 12:15] = 0.1
-    counts = []
     out = mask_and_droplets_batch(torch.from_numpy(m).cuda(), 0.5, [(64, 64)] * 2, 1, max_droplets=100, thresh_low=0.3,
-                                  max_hole_area=-1, clean_counts=counts)
+                                  max_hole_area=-1)
+    counts = [o.clean_counts for o in out]
     ref = [clean_mask(m[i] > 0.5, m[i] > 0.3, -1) for i in range(2)]
     for i in range(2):
-        assert np.array_equal(out[i][0].cpu().numpy(), ref[i][0]) and np.array_equal(counts[i], ref[i][1])
+        assert np.array_equal(out[i].mask.cpu().numpy(), ref[i][0]) and np.array_equal(counts[i], ref[i][1])
     from scipy import ndimage
-    assert len(out[0][1]) == ndimage.label(ref[0][0])[1] > 1000 and counts[0].tolist() == [1, 1, 1, 0]
-    assert out[1][1].tolist() == [100] and counts[1].tolist() == [0, 1, 9, 0]
+    assert len(out[0].area) == ndimage.label(ref[0][0])[1] > 1000 and counts[0].tolist() == [1, 1, 1, 0]
+    assert out[1].area.tolist() == [100] and counts[1].tolist() == [0, 1, 9, 0]
 
 
 # ---- the script ------------------------------------------------------------------------------------------------------------

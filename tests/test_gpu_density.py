@@ -62,8 +62,8 @@ def test_batch_reuses_droplet_sums_and_matches_single_images():
     out, sums = mask_and_droplets_batch(probs, 0.5, [(96, 128)] * 2, 1, keep_sums=True)
     assert sums is not None
     rgbs = [torch.from_numpy(r).cuda() for r, _ in imgs]
-    a = density_maps_batch(rgbs, [o[0] for o in out], sums, 10, 21)
-    b = density_maps_batch(rgbs, [o[0] for o in out], None, 10, 21)
+    a = density_maps_batch(rgbs, [o.mask for o in out], sums, 10, 21)
+    b = density_maps_batch(rgbs, [o.mask for o in out], None, 10, 21)
     for x, y, (rgb, m) in zip(a, b, imgs):
         ref = hd.density_maps(rgb, m, 10, 21)
         for k in ("radial_index", "spatial_index"):

@@ -121,6 +121,81 @@ def test_more_droplets_than_the_first_output_capacity():
     assert cy[0] == 0 and cx[1] == 2 and cy[512] == 2 and cx[512] == 0          # raster order
 
 
+# ---- what droplets.py launches: one body for the batch and the single image -------------------------------------------------
+# Per image, for an output size that differs from the probabilities' (MASK_RESIZE "reference": the linear resize); at equal
+# size the mask kernel is unetdc_mask_from_probs instead.  Recorded on the commit before the two launch paths became one.
+LINEAR, CLEAN, PROPS = "unetdc_mask_from_probs_linear", "unetdc_mask_clean", "unetdc_label_props"
+LAUNCHES = {
+    "plain": (dict(), [LINEAR, "unetdc_ccl_stats"]),
+    "split": (dict(split_depth=2.0), [LINEAR, "unetdc_split_stats"]),
+    "shape": (dict(shape=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
+    "shape_gray": (dict(shape=True, gray=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
+    "labels_shape": (dict(shape=True, return_labels=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
+    "clean_low": (dict(thresh_low=0.3), [LINEAR, LINEAR, CLEAN, "unetdc_ccl_stats"]),
+    "clean_holes": (dict(max_hole_area=-1), [LINEAR, CLEAN, "unetdc_ccl_stats"]),
+    "all": (dict(split_depth=2.0, return_labels=True, shape=True, gray=True, thresh_low=0.3, max_hole_area=5),
+            [LINEAR, LINEAR, CLEAN, "unetdc_split_stats", PROPS]),
+}
+
+
+@pytest.fixture(scope="module")
+def launch_probs():
+    """Two 64 x 64 maps of discs (0.9) with skirts (0.4) and a one-pixel hole."""
+    rng = np.random.default_rng(3)
+    yy, xx = np.mgrid[0:64, 0:64]
+    p = np.full((2, 64, 64), 0.1, np.float32)
+    for i in range(2):
+        for _ in range(9):
+            cy, cx, r = rng.integers(4, 60), rng.integers(4, 60), rng.integers(2, 8)
+            d = (yy - cy) ** 2 + (xx - cx) ** 2
+            p[i][(d <= (r + 2) ** 2) & (p[i] < 0.4)] = 0.4
+            p[i][d <= r * r] = 0.9
+        p[i, 30:33, 30:33] = 0.9
+        p[i, 31, 31] = 0.1
+    return torch.from_numpy(p).cuda()
+
+
+@pytest.mark.parametrize("case", sorted(LAUNCHES))
+def test_batch_and_single_image_launch_what_they_launched(case, launch_probs, monkeypatch):
+    from unet_dc_segmentation_amd import _lib
+    from unet_dc_segmentation_amd.droplets import mask_and_droplets, mask_and_droplets_batch
+    kw, linear = LAUNCHES[case]
+    kw = dict(kw)
+    equal = [n.replace("_linear", "") for n in linear]
+    sizes = [(37, 53), (64, 96)]
+    grays = {hw: torch.zeros(hw, dtype=torch.uint8, device="cuda") for hw in sizes + [(64, 64)]} if kw.pop("gray", False) else None
+    names, real = [], _lib.call
+    calls = {"cpu": 0, "item": 0}
+    real_cpu, real_item = torch.Tensor.cpu, torch.Tensor.item
+
+    def cpu(self, *a, **k):
+        calls["cpu"] += self.is_cuda
+        return real_cpu(self, *a, **k)
+
+    def item(self):
+        calls["item"] += self.is_cuda
+        return real_item(self)
+
+    def launched(fn, probs, hws, one):
+        names.clear()
+        calls.update(cpu=0, item=0)
+        g = None if grays is None else grays[hws] if one else [grays[hw] for hw in hws]
+        return fn(probs, 0.5, hws, 1, gray=g, **kw), list(names), dict(calls)
+    monkeypatch.setattr(_lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    monkeypatch.setattr(torch.Tensor, "cpu", cpu)
+    monkeypatch.setattr(torch.Tensor, "item", item)
+    out, got, waits = launched(mask_and_droplets_batch, launch_probs, sizes, False)
+    assert got == linear + linear and waits == {"cpu": 3, "item": 0}
+    _, got, waits = launched(mask_and_droplets_batch, launch_probs[1:], [(64, 64)], False)
+    assert got == equal and waits == {"cpu": 3, "item": 0}
+    one, got, waits = launched(mask_and_droplets, launch_probs[0], sizes[0], True)
+    assert got == linear and waits == {"cpu": 3, "item": 0}
+    _, got, waits = launched(mask_and_droplets, launch_probs[1], (64, 64), True)
+    assert got == equal and waits == {"cpu": 3, "item": 0}
+    assert len(one.area) > 1 and (one.labels is not None) == kw.get("return_labels", False) and (one.props is not None) == ("shape" in kw)
+    assert torch.equal(one.mask, out[0].mask) and all(np.array_equal(x, y) for x, y in zip(list(one)[1:], list(out[0])[1:]))
+
+
 # ---- unetdc_ccl_stats and the mask kernels through the C ABI, every output and the workspace (at exactly
 # unetdc_ccl_workspace bytes) between canaries ----------------------------------------------------------------------------------
 def _stream():

@@ -171,8 +171,8 @@ def test_match_batch_with_mixed_sizes_equals_single_images_and_waits_once(monkey
         calls["item"] += self.is_cuda
         return real_item(self)
     pred = mask_and_droplets_batch(probs, 0.5, sizes, 3, shape=True, return_labels=True)
-    masks = [o[0].cpu().numpy() for o in pred]
-    labs_h = [o[4].cpu().numpy() for o in pred]
+    masks = [o.mask.cpu().numpy() for o in pred]
+    labs_h = [o.labels.cpu().numpy() for o in pred]
     if gt_are_labels:
         gts = [cc_labels(shift(m, 2, 1)) for m in masks]
     else:
@@ -181,14 +181,14 @@ def test_match_batch_with_mixed_sizes_equals_single_images_and_waits_once(monkey
     with monkeypatch.context() as mp:
         mp.setattr(torch.Tensor, "cpu", cpu)
         mp.setattr(torch.Tensor, "item", item)
-        out = match_batch([o[4] for o in pred], [o[1] for o in pred], gts, 5, gt_are_labels)
+        out = match_batch([o.labels for o in pred], [o.area for o in pred], gts, 5, gt_are_labels)
         # one wait, on the copy of the counts; then the filled part of the int32 and of the int64 outputs: the three copies
         # mask_and_droplets_batch itself makes (tests/test_gpu_shape.py), once more
         assert calls == {"cpu": 3, "item": 0}
     assert len(out) == len(sizes)
     for i in range(len(sizes)):
         assert_results_equal(out[i], host_match(labs_h[i], gts[i], 5, gt_are_labels))
-        one = match_batch([pred[i][4]], [pred[i][1]], [gts[i]], 5, gt_are_labels)[0]
+        one = match_batch([pred[i].labels], [pred[i].area], [gts[i]], 5, gt_are_labels)[0]
         assert_results_equal(one, out[i])
     assert out[3]["columns"]["image"]["tp_50"] > 50 and out[3]["columns"]["image"]["n_pred"] > 100
 

@@ -222,18 +222,18 @@ def test_batch_with_mixed_sizes_equals_single_images_and_waits_once(monkeypatch,
         assert calls == plain_calls == {"cpu": 3, "item": 0}
     nogray = mask_and_droplets_batch(probs, 0.5, sizes, 1, shape=True, **split)
     for i, (oh, ow) in enumerate(sizes):
-        mask, a, cy, cx, lab, props = out[i]
-        assert len(plain[i]) == 4 and torch.equal(mask, plain[i][0])
-        for x, y in zip(plain[i][1:], (a, cy, cx)):
+        (mask, a, cy, cx), lab, props = out[i], out[i].labels, out[i].props
+        assert plain[i].labels is None and plain[i].props is None and torch.equal(mask, plain[i].mask)
+        for x, y in zip(list(plain[i])[1:], (a, cy, cx)):
             assert np.array_equal(x, y)
         one = mask_and_droplets(probs[i], 0.5, (oh, ow), 1, shape=True, gray=grays[i], return_labels=True, **split)
-        assert torch.equal(one[0], mask) and torch.equal(one[4], lab)
-        assert_props_dicts_equal(one[5], props)
+        assert torch.equal(one.mask, mask) and torch.equal(one.labels, lab)
+        assert_props_dicts_equal(one.props, props)
         hlab, hp = host_props(mask.cpu().numpy(), grays_h[i], None if split_depth is None else 4)
         assert np.array_equal(lab.cpu().numpy(), hlab)
         assert_props_dicts_equal(props, hp)
-        assert len(nogray[i]) == 5 and "Sg" not in nogray[i][4]
-        assert_props_dicts_equal(nogray[i][4], {q: v for q, v in hp.items() if q not in sh.GRAY_QUANTITIES})
+        assert nogray[i].labels is None and "Sg" not in nogray[i].props
+        assert_props_dicts_equal(nogray[i].props, {q: v for q, v in hp.items() if q not in sh.GRAY_QUANTITIES})
 
 
 @pytest.mark.parametrize("split_depth", [None, 2.0])
@@ -247,8 +247,8 @@ def test_more_droplets_than_the_first_capacity(split_depth):
     out = mask_and_droplets_batch(torch.from_numpy(m).cuda(), 0.5, [(64, 64)] * 2, 1, max_droplets=100, shape=True, gray=g, **split)
     for i in range(2):
         hp = host_props((m[i] > 0.5).astype(np.uint8), g[i].cpu().numpy(), None if split_depth is None else 4)[1]
-        assert_props_dicts_equal(out[i][-1], hp)
-    assert len(out[0][1]) == 1024 and len(out[1][1]) == 1 and out[0][-1]["P1"].tolist() == [0] * 1024
+        assert_props_dicts_equal(out[i].props, hp)
+    assert len(out[0].area) == 1024 and len(out[1].area) == 1 and out[0].props["P1"].tolist() == [0] * 1024
 
 
 @pytest.mark.parametrize("extra", [[], ["--split_touching", "--split_depth", "1.5"]])

@@ -275,16 +275,16 @@ def test_batch_with_mixed_sizes_equals_single_images_and_waits_once(monkeypatch)
         # the host waits where it did: on the copy of the counts; then the filled part of the areas and of the sums
         assert calls == plain_calls == {"cpu": 3, "item": 0}
     for i, (oh, ow) in enumerate(sizes):
-        mask, a, cy, cx, lab = out[i]
-        assert torch.equal(mask, plain[i][0])
+        (mask, a, cy, cx), lab = out[i], out[i].labels
+        assert torch.equal(mask, plain[i].mask)
         one = mask_and_droplets(probs[i], 0.5, (oh, ow), 1, split_depth=2.0, return_labels=True)
-        assert torch.equal(one[0], mask) and torch.equal(one[4], lab)
-        for x, y in zip(one[1:4], (a, cy, cx)):
+        assert torch.equal(one.mask, mask) and torch.equal(one.labels, lab)
+        for x, y in zip(list(one)[1:], (a, cy, cx)):
             assert np.array_equal(x, y)
         hlab, ha, hsy, hsx, _ = ds.split_labels(mask.cpu().numpy(), 4, 1)
         assert np.array_equal(lab.cpu().numpy(), hlab) and np.array_equal(a, ha)
         assert np.array_equal(cy, hsy / np.maximum(ha, 1)) and np.array_equal(cx, hsx / np.maximum(ha, 1))
-        assert len(a) >= len(plain[i][1]) and int(a.sum()) == int(plain[i][1].sum())
+        assert len(a) >= len(plain[i].area) and int(a.sum()) == int(plain[i].area.sum())
 
 
 def test_more_droplets_than_the_first_capacity_with_a_split_depth():
@@ -294,7 +294,7 @@ def test_more_droplets_than_the_first_capacity_with_a_split_depth():
     m[1, 10:20, 10:20] = 1.0
     out = mask_and_droplets_batch(torch.from_numpy(m).cuda(), 0.5, [(64, 64)] * 2, 1, max_droplets=100, split_depth=2.0,
                                   return_labels=True)
-    assert len(out[0][1]) == 1024 and int(out[0][4].max()) == 1024 and len(out[1][1]) == 1
+    assert len(out[0].area) == 1024 and int(out[0].labels.max()) == 1024 and len(out[1].area) == 1
 
 
 def test_cli_split_touching_device_equals_cpu_path(tmp_path, monkeypatch):

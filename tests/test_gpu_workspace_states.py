@@ -271,19 +271,18 @@ def test_mask_and_droplets_batch_equals_single_images_in_either_order(order):
     probs = torch.from_numpy(p).cuda()
     grays = [torch.from_numpy(gray_plane(h, w, seed=70 + i)).cuda() for i, (h, w) in zip(idx, sizes)]
     opts = dict(split_depth=2.0, shape=True, return_labels=True, thresh_low=0.3, max_hole_area=200)
-    counts = []
-    out = mask_and_droplets_batch(probs, 0.5, sizes, 1, gray=grays, clean_counts=counts, **opts)
-    assert len(out) == len(counts) == len(sizes)
+    out = mask_and_droplets_batch(probs, 0.5, sizes, 1, gray=grays, **opts)
+    counts = [o.clean_counts for o in out]
+    assert len(out) == len(sizes)
     did = np.zeros(4, np.int64)
     for i, hw in enumerate(sizes):
-        one_counts = []
-        one = mask_and_droplets(probs[i], 0.5, hw, 1, gray=grays[i], clean_counts=one_counts, **opts)
-        mask, a, cy, cx, lab, props = out[i]
-        assert torch.equal(one[0], mask) and torch.equal(one[4], lab)
-        for x, y in zip(one[1:4], (a, cy, cx)):
+        one = mask_and_droplets(probs[i], 0.5, hw, 1, gray=grays[i], **opts)
+        (mask, a, cy, cx), lab, props = out[i], out[i].labels, out[i].props
+        assert torch.equal(one.mask, mask) and torch.equal(one.labels, lab)
+        for x, y in zip(list(one)[1:], (a, cy, cx)):
             assert x.dtype == y.dtype and np.array_equal(x, y)
-        assert_props_dicts_equal(one[5], props)
-        assert np.array_equal(one_counts[0], counts[i])
+        assert_props_dicts_equal(one.props, props)
+        assert one.clean_counts.shape == (4,) and np.array_equal(one.clean_counts, counts[i])
         assert len(a) > 3 and int(lab.max()) == len(a)
         did += counts[i]
     assert did[0] > 0 and did[1] > 0                           # hysteresis and hole filling both did something
