@@ -275,6 +275,35 @@ int unetdc_focal_dice_loss_bwd(const float* probs, const float* target, const fl
                                float* dprobs, int nimg, int64_t hw, float alpha, float gamma, float ratio,
                                unetdc_stream_t s);
 
+/* ---- border-weighted loss (border.hip, loss.hip; the definition is DESIGN.md section 19, utils/border_weights.py) -----------
+ * unetdc_border_weights: target ([n][h][w] fp32, foreground where > 0.5; the images are independent) ->
+ *   out_weight ([n][h][w] fp32).  With the 4-connected components of an image (the connectivity of unetdc_ccl_stats), for a
+ *   background pixel x:  D1 = the smallest squared Euclidean distance to a foreground pixel with |dy| <= radius and
+ *   |dx| <= radius, D2 = the smallest to such a pixel of another component than that one (D2 = D1 when two components tie),
+ *   UNETDC_EDT_INF where nothing qualifies; foreground pixels have D1 = D2 = 0.
+ *     out_weight = 1 + w0 * exp(-(sqrt(D1) + sqrt(D2))^2 / (2 sigma^2))   on background pixels with D2 <= radius^2
+ *                  (there D1 and D2 are the distances of the untruncated transform), exactly 1.0f everywhere else.
+ *   out_d1 / out_d2 (nullable, [n][h][w] int32): the planes D1, D2.
+ *   n 1..65535, sides 1..16384, h * w < 2^30, radius 1..64, sigma > 0, w0 >= 0 (both finite); anything else, a null target /
+ *   out_weight / workspace or a workspace that is not 4-byte aligned returns UNETDC_EINVAL before the first launch, a workspace
+ *   below unetdc_border_weights_workspace(n, h, w, radius) bytes (14 per pixel + 64; 0 for a geometry the call refuses)
+ *   UNETDC_EWORKSPACE.  Nothing but the outputs and the workspace is written, whatever the workspace held; no allocation, no
+ *   host wait; launches on the given stream only.  Integer work and a union-find up to the final expression: the planes depend
+ *   on no order, two runs are bitwise equal in all three outputs.
+ * unetdc_focal_dice_loss_w_fwd / _w_bwd: unetdc_focal_dice_loss_fwd / _bwd with weight ([nimg][hw] fp32, not differentiated)
+ *   on the pixel-wise term only:  loss = ratio * sum_j(weight_j * focal_j) / (nimg * hw) + (1 - ratio) * (1 - mean_i dice_i),
+ *   dprobs_j = g * (ratio / (nimg * hw) * weight_j * dfocal_j - (1 - ratio) / nimg * (t_j c1 - c2)).  The same kernel bodies:
+ *   a weight of 1.0f everywhere gives the bits of the unweighted calls.  Workspace: unetdc_focal_dice_loss_workspace. */
+int64_t unetdc_border_weights_workspace(int n, int h, int w, int radius);
+int unetdc_border_weights(const float* target, int n, int h, int w, float w0, float sigma, int radius, float* out_weight,
+                          int32_t* out_d1, int32_t* out_d2, void* workspace, int64_t workspace_bytes, unetdc_stream_t s);
+int unetdc_focal_dice_loss_w_fwd(const float* probs, const float* target, const float* weight, float* loss_out, float* coef,
+                                 void* workspace, int64_t workspace_bytes, int nimg, int64_t hw, float alpha, float gamma,
+                                 float ratio, float smooth, unetdc_stream_t s);
+int unetdc_focal_dice_loss_w_bwd(const float* probs, const float* target, const float* weight, const float* coef,
+                                 const float* grad_out, float* dprobs, int nimg, int64_t hw, float alpha, float gamma,
+                                 float ratio, unetdc_stream_t s);
+
 /* conv3x3_dgrad that also returns colsum[i] = sum over pixels of the STORED dx[:, c0 + i], i < c (fp32).
  * The decoder's first conv writes the gradient of torch.cat([up, enc]) (models/model_2.py:68,71,74,77); the
  * column sums of its first half are the ConvTranspose2d bias gradient (:20,23,26,29), so that gradient costs

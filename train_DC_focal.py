@@ -65,6 +65,16 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--crop_fg", type=float, default=0.0, metavar="P",
                    help="with --crop: with probability P a training window is placed so that it contains a uniformly chosen "
                         "foreground pixel of its image, otherwise uniformly as without the flag; 0 <= P <= 1, default 0")
+    p.add_argument("--border_weight", type=float, nargs="?", const=10.0, default=None, metavar="W0",
+                   help="with --loss focal_dice: weight the pixel-wise focal term of the TRAINING loss by the U-Net separation map "
+                        "1 + W0 * exp(-(d1 + d2)^2 / (2 S^2)) on the background between two droplets (d1, d2: distances to the "
+                        "nearest and second-nearest droplet), built per batch from the masks (csrc/border.hip on the HIP device, "
+                        "DESIGN.md section 19); W0 >= 0, 10 without W0, default off.  Dice, the validation and test losses, the "
+                        "metrics, early stopping and --calibrate_thresh stay unweighted")
+    p.add_argument("--border_sigma", type=float, default=None, metavar="S",
+                   help="with --border_weight: the width S of the separation term in pixels (default 5)")
+    p.add_argument("--border_radius", type=int, default=None, metavar="R",
+                   help="with --border_weight: droplets further than R pixels away do not count (1..64, default ceil(4 S))")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -167,6 +177,23 @@ def check_crop_flags(args):
         raise SystemExit(f"--crop caches RGB images and cannot run with --in_channels {args.in_channels}")
 
 
+def check_border_flags(parser, args):
+    """--border_weight / --border_sigma / --border_radius: parser errors, raised before anything else runs.
+    -> None without --border_weight, else (w0, sigma, radius)."""
+    from utils.border_weights import DEFAULT_SIGMA, check_params
+    if args.border_weight is None:
+        if args.border_sigma is not None or args.border_radius is not None:
+            parser.error("--border_sigma and --border_radius need --border_weight")
+        return None
+    if args.loss != "focal_dice":
+        parser.error(f"--border_weight weights the focal term and cannot run with --loss {args.loss}")
+    try:
+        return check_params(args.border_weight, DEFAULT_SIGMA if args.border_sigma is None else args.border_sigma,
+                            args.border_radius)
+    except ValueError as e:
+        parser.error(f"--border_weight W0 / --border_sigma S / --border_radius R: {e}")
+
+
 class History(list):
     """Per-epoch records of main(); ``.test`` holds the held-out-split results of the final evaluation (None if skipped),
     ``.calibration`` the result of --calibrate_thresh (None without the flag), ``.tta`` the number of variants both were
@@ -246,7 +273,9 @@ def calibrate_threshold(model, loader, K, device, tta=1, items=8):
 
 
 def main(argv=None, parser=None):
-    args = (parser or build_parser()).parse_args(argv)
+    parser = parser or build_parser()
+    args = parser.parse_args(argv)
+    border = check_border_flags(parser, args)
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
@@ -271,6 +300,13 @@ def main(argv=None, parser=None):
         criterion = lambda pred, tgt: focal_dice_loss(pred, tgt, alpha=1.0, gamma=2.0, ratio=0.3)  # noqa: E731
     else:
         criterion = combined_loss
+    # the training loss alone takes the separation weights; validation, test and early stopping keep `criterion`
+    train_criterion = criterion
+    if border is not None:
+        from unet_dc_segmentation_amd.border import border_weights
+
+        def train_criterion(pred, tgt):
+            return focal_dice_loss(pred, tgt, alpha=1.0, gamma=2.0, ratio=0.3, weight=border_weights(tgt, *border))
     # same update as the reference's torch.optim.Adam(lr) (train_DC_focal.py:224).  On the HIP path: one kernel that also
     # rewrites the packed weight images (unet_dc_segmentation_amd/optim.py); --optimizer torch keeps torch.optim.Adam
     if device.type == "cuda" and args.optimizer == "hip":
@@ -308,6 +344,10 @@ def main(argv=None, parser=None):
             print(f"--crop_scale / --crop_fg: source windows of side T in {tlo}..{thi} resampled to {args.crop} x {args.crop} "
                   f"on the device, a window placed on a foreground pixel with probability P = {args.crop_fg:g}; validation "
                   f"and test at scale 1")
+    if rank == 0 and border is not None:
+        print(f"--border_weight {border[0]:g}: training loss with the focal term weighted by 1 + {border[0]:g} * "
+              f"exp(-(d1 + d2)^2 / (2 * {border[1]:g}^2)) between droplets at most {border[2]} px apart, built per batch on "
+              f"{'the HIP device' if device.type == 'cuda' else 'the host'}; validation and test losses stay unweighted")
     if rank == 0:
         print(f"Training set: {len(train_ds)} images/rank, validation set: {len(val_ds)} images, "
               f"{world} rank(s), device {device}, compute {args.dtype}")
@@ -332,7 +372,7 @@ def main(argv=None, parser=None):
             images, masks = batch[0].float().to(device, non_blocking=True), batch[1].float().to(device, non_blocking=True)
             optimizer.zero_grad()
             outputs = model(images)
-            loss = criterion(outputs, masks)
+            loss = train_criterion(outputs, masks)
             loss.backward()
             if wrapper is not None and not images.is_cuda:
                 wrapper.sync_gradients()                    # ATen-CPU path: explicit all-reduce

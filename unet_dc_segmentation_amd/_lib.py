@@ -71,6 +71,10 @@ SIGNATURES = {
     "unetdc_focal_dice_loss_workspace": (L, [I, L]),
     "unetdc_focal_dice_loss_fwd": (I, [P, P, P, P, P, L, I, L, F, F, F, F, P]),
     "unetdc_focal_dice_loss_bwd": (I, [P, P, P, P, P, I, L, F, F, F, P]),
+    "unetdc_border_weights_workspace": (L, [I, I, I, I]),
+    "unetdc_border_weights": (I, [P, I, I, I, F, F, I, P, P, P, P, L, P]),
+    "unetdc_focal_dice_loss_w_fwd": (I, [P, P, P, P, P, P, L, I, L, F, F, F, F, P]),
+    "unetdc_focal_dice_loss_w_bwd": (I, [P, P, P, P, P, P, I, L, F, F, F, P]),
     "unetdc_conv3x3_dgrad_colsum_workspace": (L, [I, I, I, I]),
     "unetdc_conv3x3_dgrad_colsum": (I, [P, I, P, P, I, P, I, I, P, L, I, I, I, I, I, I, I, P]),
     "unetdc_channel_sum_workspace": (L, [L, I]),

@@ -507,14 +507,37 @@ int64_t unetdc_focal_dice_loss_workspace(int nimg, int64_t hw) { return loss_wor
 int unetdc_focal_dice_loss_fwd(const float* probs, const float* target, float* loss_out, float* coef, void* workspace,
                                int64_t workspace_bytes, int nimg, int64_t hw, float alpha, float gamma, float ratio,
                                float smooth, unetdc_stream_t s) {
-  return launch_loss_fwd(probs, target, loss_out, coef, workspace, (long)workspace_bytes, nimg, (long)hw, alpha, gamma,
+  return launch_loss_fwd(probs, target, nullptr, loss_out, coef, workspace, (long)workspace_bytes, nimg, (long)hw, alpha, gamma,
                          ratio, smooth, (hipStream_t)s);
 }
 
 int unetdc_focal_dice_loss_bwd(const float* probs, const float* target, const float* coef, const float* grad_out,
                                float* dprobs, int nimg, int64_t hw, float alpha, float gamma, float ratio,
                                unetdc_stream_t s) {
-  return launch_loss_bwd(probs, target, coef, grad_out, dprobs, nimg, (long)hw, alpha, gamma, ratio, (hipStream_t)s);
+  return launch_loss_bwd(probs, target, nullptr, coef, grad_out, dprobs, nimg, (long)hw, alpha, gamma, ratio, (hipStream_t)s);
+}
+
+int unetdc_focal_dice_loss_w_fwd(const float* probs, const float* target, const float* weight, float* loss_out, float* coef,
+                                 void* workspace, int64_t workspace_bytes, int nimg, int64_t hw, float alpha, float gamma,
+                                 float ratio, float smooth, unetdc_stream_t s) {
+  UNETDC_REQUIRE(weight, "focal_dice_loss_w: null weight");
+  return launch_loss_fwd(probs, target, weight, loss_out, coef, workspace, (long)workspace_bytes, nimg, (long)hw, alpha, gamma,
+                         ratio, smooth, (hipStream_t)s);
+}
+
+int unetdc_focal_dice_loss_w_bwd(const float* probs, const float* target, const float* weight, const float* coef,
+                                 const float* grad_out, float* dprobs, int nimg, int64_t hw, float alpha, float gamma,
+                                 float ratio, unetdc_stream_t s) {
+  UNETDC_REQUIRE(weight, "focal_dice_loss_w_bwd: null weight");
+  return launch_loss_bwd(probs, target, weight, coef, grad_out, dprobs, nimg, (long)hw, alpha, gamma, ratio, (hipStream_t)s);
+}
+
+int64_t unetdc_border_weights_workspace(int n, int h, int w, int radius) { return border_workspace_bytes(n, h, w, radius); }
+
+int unetdc_border_weights(const float* target, int n, int h, int w, float w0, float sigma, int radius, float* out_weight,
+                          int32_t* out_d1, int32_t* out_d2, void* workspace, int64_t workspace_bytes, unetdc_stream_t s) {
+  return launch_border_weights(target, n, h, w, w0, sigma, radius, out_weight, out_d1, out_d2, workspace, (long)workspace_bytes,
+                               (hipStream_t)s);
 }
 
 // the bytes do not depend on the dtype, and a width that bf16 takes fp32 takes too

@@ -373,10 +373,17 @@ int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int
                         hipStream_t stream);
 int launch_density_sqrt(const long long* x, double* out, long n, hipStream_t stream);
 
+// loss.hip: wt = the per-pixel weight of the focal term ([nimg][hw]), null = the unweighted loss
 long loss_workspace_bytes(int nimg, long hw);
-int launch_loss_fwd(const float* p, const float* t, float* loss_out, float* coef, void* workspace, long workspace_bytes,
-                    int nimg, long hw, float alpha, float gamma, float ratio, float smooth, hipStream_t stream);
-int launch_loss_bwd(const float* p, const float* t, const float* coef, const float* gout, float* dp, int nimg, long hw,
-                    float alpha, float gamma, float ratio, hipStream_t stream);
+int launch_loss_fwd(const float* p, const float* t, const float* wt, float* loss_out, float* coef, void* workspace,
+                    long workspace_bytes, int nimg, long hw, float alpha, float gamma, float ratio, float smooth,
+                    hipStream_t stream);
+int launch_loss_bwd(const float* p, const float* t, const float* wt, const float* coef, const float* gout, float* dp, int nimg,
+                    long hw, float alpha, float gamma, float ratio, hipStream_t stream);
+
+// border.hip: the separation weight map of the border-weighted loss (include/unetdc_hip.h)
+long border_workspace_bytes(int n, int h, int w, int radius);       // 0: a geometry the launcher refuses
+int launch_border_weights(const float* target, int n, int h, int w, float w0, float sigma, int radius, float* out_weight,
+                          int* out_d1, int* out_d2, void* workspace, long workspace_bytes, hipStream_t stream);
 
 }  // namespace unetdc

@@ -26,18 +26,23 @@ __device__ __forceinline__ void focal_terms(float p, float t, float alpha, float
 }
 
 // partial sums: parts[(img * nblk + blk) * 4 + {focal, p*t, p, t}]
+// WEIGHTED: the focal term of pixel j counts wt[j] times (the border-weighted loss); Dice does not.
+// The unweighted instantiation is the kernel as it was; a weight of 1.0f changes no bit of the weighted one (1 * f = f).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ p, const float* __restrict__ t,
-                                                          float* __restrict__ parts, long hw, float alpha,
-                                                          float gamma) {
+                                                          const float* __restrict__ wt, float* __restrict__ parts, long hw,
+                                                          float alpha, float gamma) {
   __shared__ float red[4][4];
   const int img = blockIdx.y, nblk = gridDim.x;
   const float* pp = p + (long)img * hw;
   const float* tt = t + (long)img * hw;
+  const float* ww = WEIGHTED ? wt + (long)img * hw : nullptr;
   float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < hw; j += (long)nblk * 256) {
     const float pv = pp[j], tv = tt[j];
     float f, df;
     focal_terms(pv, tv, alpha, gamma, f, df);
+    if (WEIGHTED) f = __fmul_rn(ww[j], f);
     s[0] += f; s[1] = fmaf(pv, tv, s[1]); s[2] += pv; s[3] += tv;
   }
 #pragma unroll
@@ -89,11 +94,12 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
   }
 }
 
-// dp_j = gout * ( ratio * dfocal_j / numel - (1-ratio)/nimg * (t_j*c1 - c2) )
+// dp_j = gout * ( ratio * w_j * dfocal_j / numel - (1-ratio)/nimg * (t_j*c1 - c2) ),  w_j = 1 unless WEIGHTED
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ p, const float* __restrict__ t,
-                                                       const float* __restrict__ coef, const float* __restrict__ gout,
-                                                       float* __restrict__ dp, long hw, int nimg, double numel,
-                                                       float alpha, float gamma, float ratio) {
+                                                       const float* __restrict__ wt, const float* __restrict__ coef,
+                                                       const float* __restrict__ gout, float* __restrict__ dp, long hw,
+                                                       int nimg, double numel, float alpha, float gamma, float ratio) {
   const int img = blockIdx.y;
   const float c1 = coef[img * 2 + 0], c2 = coef[img * 2 + 1];
   const float g = gout[0];
@@ -103,6 +109,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     const float pv = p[base + j], tv = t[base + j];
     float f, df;
     focal_terms(pv, tv, alpha, gamma, f, df);
+    if (WEIGHTED) df = __fmul_rn(wt[base + j], df);
     dp[base + j] = g * (kf * df - kd * (tv * c1 - c2));
   }
 }
@@ -116,8 +123,10 @@ static int loss_blocks(long hw) {
 
 long loss_workspace_bytes(int nimg, long hw) { return (long)nimg * loss_blocks(hw) * 4 * 4; }
 
-int launch_loss_fwd(const float* p, const float* t, float* loss_out, float* coef, void* workspace, long workspace_bytes,
-                    int nimg, long hw, float alpha, float gamma, float ratio, float smooth, hipStream_t stream) {
+// wt: null = the unweighted loss; weighted: the caller (abi.hip) has refused a null weight
+int launch_loss_fwd(const float* p, const float* t, const float* wt, float* loss_out, float* coef, void* workspace,
+                    long workspace_bytes, int nimg, long hw, float alpha, float gamma, float ratio, float smooth,
+                    hipStream_t stream) {
   UNETDC_REQUIRE(p && t && loss_out && coef && workspace, "focal_dice_loss: null pointer");
   UNETDC_REQUIRE(nimg > 0 && nimg <= 65535 && hw > 0, "focal_dice_loss: bad shape");
   const int nb = loss_blocks(hw);
@@ -126,7 +135,8 @@ int launch_loss_fwd(const float* p, const float* t, float* loss_out, float* coef
     return UNETDC_EWORKSPACE;
   }
   float* parts = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(loss_reduce_kernel, dim3(nb, nimg), dim3(256), 0, stream, p, t, parts, hw, alpha, gamma);
+  if (wt) hipLaunchKernelGGL(loss_reduce_kernel<true>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, parts, hw, alpha, gamma);
+  else hipLaunchKernelGGL(loss_reduce_kernel<false>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, parts, hw, alpha, gamma);
   int rc = check_launch("loss_reduce_kernel");
   if (rc != UNETDC_OK) return rc;
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, stream, parts, nimg, nb, (double)nimg * (double)hw,
@@ -134,13 +144,16 @@ int launch_loss_fwd(const float* p, const float* t, float* loss_out, float* coef
   return check_launch("loss_finalize_kernel");
 }
 
-int launch_loss_bwd(const float* p, const float* t, const float* coef, const float* gout, float* dp, int nimg, long hw,
-                    float alpha, float gamma, float ratio, hipStream_t stream) {
+int launch_loss_bwd(const float* p, const float* t, const float* wt, const float* coef, const float* gout, float* dp, int nimg,
+                    long hw, float alpha, float gamma, float ratio, hipStream_t stream) {
   UNETDC_REQUIRE(p && t && coef && gout && dp, "focal_dice_loss_bwd: null pointer");
   UNETDC_REQUIRE(nimg > 0 && nimg <= 65535 && hw > 0, "focal_dice_loss_bwd: bad shape");
   const int nb = loss_blocks(hw) * 4;
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(nb, nimg), dim3(256), 0, stream, p, t, coef, gout, dp, hw, nimg,
-                     (double)nimg * (double)hw, alpha, gamma, ratio);
+  const double numel = (double)nimg * (double)hw;
+  if (wt) hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, coef, gout, dp, hw, nimg, numel,
+                             alpha, gamma, ratio);
+  else hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, coef, gout, dp, hw, nimg, numel,
+                          alpha, gamma, ratio);
   return check_launch("loss_bwd_kernel");
 }
 

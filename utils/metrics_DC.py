@@ -55,17 +55,30 @@ class FocalLoss(nn.Module):
         return loss
 
 
-def focal_dice_loss(pred, target, alpha=1.0, gamma=2.0, ratio=0.3):
+def focal_dice_loss(pred, target, alpha=1.0, gamma=2.0, ratio=0.3, weight=None):
     """ratio * focal + (1 - ratio) * dice; train_DC_focal.py:222 uses (1.0, 2.0, 0.3).
 
     fp32 probability maps on a HIP device take the fused kernels of
     ``unet_dc_segmentation_amd/csrc/loss.hip`` (same arithmetic, three launches instead of ~25 ATen
-    ones)."""
+    ones).
+
+    weight (a tensor of pred's shape, e.g. ``unet_dc_segmentation_amd.border.border_weights(target, 10)``; a constant, not
+    differentiated) multiplies the pixel-wise focal term before its mean over all pixels; Dice is a region term and stays
+    unweighted.  ``weight=None`` is the code path without the argument."""
+    if weight is None:
+        if pred.is_cuda:
+            from unet_dc_segmentation_amd import loss as fused
+            if fused.supported(pred, target):
+                return fused.focal_dice_loss(pred, target, alpha, gamma, ratio)
+        fl = FocalLoss(alpha=alpha, gamma=gamma, reduction="mean")(pred, target)
+        return ratio * fl + (1 - ratio) * dice_loss(pred, target)
+    if weight.shape != pred.shape:
+        raise ValueError(f"focal_dice_loss: weight {tuple(weight.shape)} must have the shape of pred {tuple(pred.shape)}")
     if pred.is_cuda:
         from unet_dc_segmentation_amd import loss as fused
-        if fused.supported(pred, target):
-            return fused.focal_dice_loss(pred, target, alpha, gamma, ratio)
-    fl = FocalLoss(alpha=alpha, gamma=gamma, reduction="mean")(pred, target)
+        if fused.supported(pred, target) and fused.weight_supported(pred, weight):
+            return fused.focal_dice_loss(pred, target, alpha, gamma, ratio, weight=weight)
+    fl = (weight.detach() * FocalLoss(alpha=alpha, gamma=gamma, reduction="none")(pred, target)).mean()
     return ratio * fl + (1 - ratio) * dice_loss(pred, target)
 
 
