@@ -568,6 +568,31 @@ int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label
                          int max_pairs, unetdc_stream_t s);
 
 
+/* ---- droplet neighbourhoods of a label map (neighbors.hip; the definition is DESIGN.md section 20) --------------------------
+ * unetdc_label_neighbors: label ([h][w] int32: 0 = background, droplets 1..max_label; any label map, touching labels allowed;
+ *   values below 1 or above max_label are background) and radius (1..64 pixels) ->
+ *     the contact pairs (a, b, d2), a < b, d2 = the smallest squared distance between a pixel of a and a pixel of b, all with
+ *     d2 <= radius^2, in ascending order of (a, b): pair i at out_a[i], out_b[i], out_d2[i];
+ *     per label k at index k - 1 of five int32 arrays of max_label entries: out_nn_label / out_nn_d2 (the contact with the
+ *     smallest (d2, label); 0 and UNETDC_EDT_INF without one), out_degree (pairs that contain k), out_cluster (the smallest
+ *     label of k's component of the contact graph), out_cluster_size (labels with a pixel in that component; 0 for a label
+ *     without a pixel, which otherwise reads as an isolated one).
+ *   *out_count = the number of pairs; if there are more than max_pairs of them, *out_count = max_pairs + 1, the first
+ *   max_pairs entries of the three pair arrays and the five per-label arrays are unspecified and nothing beyond them is
+ *   written: repeat with more room.  max_label * (max_label - 1) / 2 always suffices (h * w does not: a label can have many
+ *   partners per pixel); the table holds at most 2^27 pairs.  max_pairs = 0 is allowed (the three pair arrays may then be
+ *   NULL), and so is max_label = 0 (the five per-label arrays may then be NULL).  Nothing but the outputs and the workspace is
+ *   written, and the workspace may hold anything on entry.  Sides 1..16384; max_label, max_pairs >= 0; workspace:
+ *   unetdc_label_neighbors_workspace(h, w, max_label, max_pairs) bytes (0 for arguments the call would refuse), 8-byte
+ *   aligned.  Launches on the given stream only; no host wait, no allocation.  Integer atomics and a sort on unique keys:
+ *   bitwise reproducible, order included. */
+int64_t unetdc_label_neighbors_workspace(int h, int w, int max_label, int max_pairs);
+int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, int radius, void* workspace,
+                           int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_d2,
+                           int max_pairs, int32_t* out_nn_label, int32_t* out_nn_d2, int32_t* out_degree, int32_t* out_cluster,
+                           int32_t* out_cluster_size, unetdc_stream_t s);
+
+
 /* ---- cleaning a mask before the droplet stages (clean.hip; the definition is DESIGN.md section 13) --------------------------
  * unetdc_mask_clean: strong and weak ([h][w] uint8, nonzero = 1; weak may be NULL) -> out_mask ([h][w] uint8 in {0,1}):
  *     hysteresis  (weak given) M = the union of the 4-connected components of weak that contain a pixel where strong and weak

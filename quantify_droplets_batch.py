@@ -18,6 +18,7 @@ and a few integers per droplet come back:
     shape columns     (droplets.py)                             csrc/shape.hip          CPU: utils/droplet_shape.py
     --gt_dir, sweep   unet_dc_segmentation_amd/evaluate.py      csrc/match.hip sweep.hip  CPU: utils/droplet_match.py, threshold_sweep.py
     --density_maps    unet_dc_segmentation_amd/density.py       csrc/density.hip        CPU: utils/density.py
+    --neighbors       (droplets.py)                             csrc/neighbors.hip      CPU: utils/droplet_neighbors.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -96,12 +97,15 @@ class Run:
     density_rows: list = dataclasses.field(default_factory=list)   # density_per_image.csv
     gt_tables: list = dataclasses.field(default_factory=list)      # gt_droplets.csv, one table per image
     gt_images: list = dataclasses.field(default_factory=list)      # match_per_image.csv: (filename, integers)
+    neighbors: int | None = None       # --neighbors: the contact radius in pixels
+    contact_tables: list = dataclasses.field(default_factory=list)  # droplet_contacts.csv, one table per image
 
     def droplet_options(self, labels, shape):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
-        route (unetdc_ccl_labels), so asking for labels selects that route."""
+        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors selects it by itself."""
         c = self.clean or {"low": None, "holes": 0}
-        return DropletOptions(self.split_depth, shape or (labels and self.split_depth is None), labels, c["low"], c["holes"])
+        return DropletOptions(self.split_depth, shape or (labels and self.split_depth is None and self.neighbors is None), labels,
+                              c["low"], c["holes"], self.neighbors)
 
     def submit(self, fn, *args):
         """PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
@@ -180,26 +184,34 @@ def _components(bin_mask, min_area):
     return area, cen[:, 0], cen[:, 1]
 
 
-def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False):
+def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None):
     """CPU path: the record that droplets.mask_and_droplets_batch returns per image, in host arrays, from the uint8 mask at
     the image's size.  split_depth: the split droplets (utils/droplet_split.py); shape: the integers of
     utils.droplet_shape.label_props_numpy on the label map and the grey plane, centroids then the integer sums over the
-    area as on the device; labels: the int32 label map whose numbers are the rows of the table."""
+    area as on the device; labels: the int32 label map whose numbers are the rows of the table; neighbors (a radius): the
+    record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well."""
     lab = None
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
         lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
-    elif shape or labels:
+    elif shape or labels or neighbors is not None:
         from utils.droplet_match import gt_labels_numpy
         lab = gt_labels_numpy(bin_mask, min_area)
     if shape:
         from utils.droplet_shape import label_props_numpy
         props = label_props_numpy(lab, gray)
         area, sy, sx = props["area"], props["Sy"], props["Sx"]
+    elif split_depth is None and neighbors is not None:
+        from utils.droplet_match import label_sums
+        area, sy, sx = label_sums(lab)
     elif split_depth is None:
         return Droplets(bin_mask, *_components(bin_mask, min_area), labels=lab)
     d = np.maximum(area, 1)
-    return Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None)
+    nb = None
+    if neighbors is not None:
+        from utils.droplet_neighbors import neighbors_numpy
+        nb = neighbors_numpy(lab, len(area), neighbors)
+    return Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None, neighbors=nb)
 
 
 def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
@@ -256,6 +268,19 @@ def add_match_outputs(run, df, res, filename):
     run.gt_tables.append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], res["columns"]["gt"])))
     run.gt_images.append((filename, res["columns"]["image"]))
     return df
+
+
+def add_neighbor_outputs(run, df, d, filename):
+    """--neighbors: the columns behind the droplet table's own, this image's rows of droplet_contacts.csv -> (the table, the
+    numbers its row of summary_per_image.csv gains)."""
+    from utils import droplet_neighbors as dn
+    rec = d.neighbors
+    pairs = tuple(rec["pairs"][q] for q in ("a", "b", "d2"))
+    if not df.empty:                                     # one concat: column by column costs six frame insertions per image
+        cols = dn.table_columns(rec, d.centroid_row, d.centroid_col, run.px_per_um)
+        df = pd.concat([df, pd.DataFrame(cols, index=df.index)], axis=1)
+    run.contact_tables.append(pd.DataFrame(dn.contact_table(filename, pairs)))
+    return df, dn.summary(pairs, rec)
 
 
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
@@ -339,7 +364,7 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
     out, p = [], probs[:, 0].numpy()
     for i, hw in enumerate(hws):
         mask, counts = _cpu_mask(p[i], thresh, hw, run.clean)
-        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels)
+        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors)
         d.clean_counts = np.asarray(counts, np.int64)
         out.append(d)
     if gt is None:
@@ -407,12 +432,15 @@ def finish_batch(run, batch, probs):
             df = add_shape_columns(df, d.props, hw, run.px_per_um)
         if mres is not None:
             df = add_match_outputs(run, df, mres[i], filename)
+        more = {}
+        if run.neighbors is not None:
+            df, more = add_neighbor_outputs(run, df, d, filename)
         if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
             run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
         df.insert(0, "filename", filename) if not df.empty else None
         run.tables.append(df)
-        run.rows.append({"filename": filename, "droplet_count": len(df), "total_area_px": df["area"].sum() if not df.empty else 0})
+        run.rows.append({"filename": filename, "droplet_count": len(df), "total_area_px": df["area"].sum() if not df.empty else 0, **more})
         run.submit(_write_outputs, mask, df, fpath, name, run.mask_dir, run.overlay_dir, labels)
         if run.density is not None:
             _density(run, None if dres is None else dres[i], batch.rgbs[i], mask, fpath)
@@ -420,6 +448,14 @@ def finish_batch(run, batch, probs):
         # failed write while the run is still going
         while len(run.writers[1]) > run.writers[2]:
             run.writers[1].popleft().result()
+
+
+def _radius_arg(text):
+    from utils.droplet_neighbors import check_radius
+    try:
+        return check_radius(int(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"G must be an integer number of pixels in 1..64, not {text!r}")
 
 
 def build_parser():
@@ -485,6 +521,13 @@ def build_parser():
                         "tile with --tile), map the outputs back and average them (N = 2: + horizontal flip, 4: the flips and "
                         "the half turn, 8: all flips and quarter turns; 8 without N); --batch stays the number of items per "
                         "forward")
+    p.add_argument("--neighbors", type=_radius_arg, nargs="?", const=5, metavar="G",
+                   help="droplet neighbourhoods: two droplets are in contact when their closest pixels are at most G pixels "
+                        "apart (pixel centres, Euclidean; G in 1..64, 5 without G -- a convention, not a measured number); adds "
+                        "nn_label, nn_dist_px, nn_centroid_dist_px, n_contacts, cluster, cluster_size (and nn_dist_micron with "
+                        "--px_per_micron) to the droplet tables, contact and cluster counts to summary_per_image.csv, and writes "
+                        "droplet_contacts.csv (filename, label_a, label_b, d2, dist_px).  With --split_touching the cut droplets "
+                        "touch (d2 = 1); components below --min_area are background")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -600,7 +643,8 @@ def main(argv=None):
         run = Run(thresh=args.prob_thresh, min_area=args.min_area, px_per_um=args.px_per_micron,
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
-                  mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)))
+                  mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
+                  neighbors=args.neighbors)
         ahead = deque()
         it = iter(images)
 
@@ -650,6 +694,8 @@ def main(argv=None):
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
+    if run.neighbors is not None and run.contact_tables:
+        pd.concat(run.contact_tables, ignore_index=True).to_csv(out_dir / "droplet_contacts.csv", index=False)
     if sweep is not None and sweep["hist"] is not None:
         from utils.threshold_sweep import summary_line, table_rows
         hist = sweep["hist"]

@@ -611,6 +611,18 @@ int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label
                               out_n, max_pairs, (hipStream_t)s);
 }
 
+int64_t unetdc_label_neighbors_workspace(int h, int w, int max_label, int max_pairs) {
+  return label_neighbors_workspace_bytes(h, w, max_label, max_pairs);
+}
+
+int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, int radius, void* workspace,
+                           int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_d2,
+                           int max_pairs, int32_t* out_nn_label, int32_t* out_nn_d2, int32_t* out_degree, int32_t* out_cluster,
+                           int32_t* out_cluster_size, unetdc_stream_t s) {
+  return launch_label_neighbors(label, max_label, h, w, radius, workspace, (long)workspace_bytes, out_count, out_a, out_b, out_d2,
+                                max_pairs, out_nn_label, out_nn_d2, out_degree, out_cluster, out_cluster_size, (hipStream_t)s);
+}
+
 int64_t unetdc_mask_clean_workspace(int h, int w) {
   return h > 0 && w > 0 && h <= 16384 && w <= 16384 ? mask_clean_workspace_bytes(h, w) : 0;
 }

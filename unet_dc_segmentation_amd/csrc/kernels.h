@@ -291,6 +291,12 @@ int launch_label_overlap(const int* label_a, int max_a, const int* label_b, int 
                          long workspace_bytes, int* out_count, int* out_a, int* out_b, int* out_n, int max_pairs,
                          hipStream_t stream);
 
+// neighbors.hip: contact pairs, nearest contact, degree and cluster of the labels of an int32 label map
+long label_neighbors_workspace_bytes(int h, int w, int max_label, int max_pairs);       // 0 for arguments the call refuses
+int launch_label_neighbors(const int* label, int max_label, int h, int w, int radius, void* workspace, long workspace_bytes,
+                           int* out_count, int* out_a, int* out_b, int* out_d2, int max_pairs, int* out_nn_label,
+                           int* out_nn_d2, int* out_degree, int* out_cluster, int* out_cluster_size, hipStream_t stream);
+
 // split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
 long edt_workspace_bytes(int h, int w);
 int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,

@@ -60,21 +60,30 @@ class DropletOptions:
     split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
     than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py).
     shape: also the per-droplet integers that utils.droplet_shape.shape_columns reads (csrc/shape.hip).
-    labels: also the int32 label map; needs a split depth or shape.
+    labels: also the int32 label map; needs a split depth, shape or neighbors.
     thresh_low (<= thresh) / max_hole_area (0 = off, negative = any size, N = holes of at most N pixels): the mask is
     cleaned first (hysteresis threshold, hole filling: csrc/clean.hip).
+    neighbors (contact radius in pixels, an integer 1..64; None = off): also the contact pairs and the per-droplet nearest
+    contact, degree and cluster (csrc/neighbors.hip, utils/droplet_neighbors.py).
     thresh / gray are not kept: the threshold the low one is checked against, and the grey planes, which need shape."""
     split_depth: float | None = None
     shape: bool = False
     labels: bool = False
     thresh_low: float | None = None
     max_hole_area: int = 0
+    neighbors: int | None = None
     thresh: dataclasses.InitVar[float | None] = None
     gray: dataclasses.InitVar[object] = None
 
     def __post_init__(self, thresh, gray):
-        if self.labels and self.split_depth is None and not self.shape:
+        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None:
             raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
+        if self.neighbors is not None:
+            from utils.droplet_neighbors import check_radius
+            try:
+                check_radius(self.neighbors)
+            except ValueError as e:
+                raise _lib.UnetdcError(str(e)) from None
         if gray is not None and not self.shape:
             raise _lib.UnetdcError("gray needs shape=True")
         if thresh is not None:
@@ -113,7 +122,8 @@ class Droplets:
     mask: uint8 [oh, ow] DEVICE tensor; area int64 [n], centroid_row / centroid_col float64 [n]: droplets in the
     reference's label order; labels: int32 [oh, ow] DEVICE label map (None unless asked for); props: the dict of
     per-droplet int64 arrays that utils.droplet_shape.shape_columns reads (None without shape); clean_counts: int64 [4],
-    the counts of utils.droplet_clean.COUNT_NAMES (zeros when cleaning is off).  The CPU path of the script fills the same
+    the counts of utils.droplet_clean.COUNT_NAMES (zeros when cleaning is off); neighbors: the record of
+    utils.droplet_neighbors.neighbors_numpy, int64 arrays (None unless asked for).  The CPU path of the script fills the same
     record with host arrays."""
     mask: object
     area: np.ndarray
@@ -122,6 +132,7 @@ class Droplets:
     labels: object = None
     props: dict | None = None
     clean_counts: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(4, np.int64))
+    neighbors: dict | None = None
 
     def __iter__(self):
         return iter((self.mask, self.area, self.centroid_row, self.centroid_col))
@@ -137,13 +148,17 @@ class _Image(NamedTuple):
     area: torch.Tensor            # int32 [cap]
     sums: torch.Tensor            # int64 [2 or 2 + NQ, cap]: sum y, sum x, then the rows of unetdc_label_props
     clean_counts: torch.Tensor | None   # int32, the four counts first
+    pair_count: torch.Tensor | None = None     # int32, the number of contact pairs first
+    pairs: torch.Tensor | None = None          # int32 [3, pair room]: a, b, d2
+    per_label: torch.Tensor | None = None      # int32 [5, cap]: the rows of utils.droplet_neighbors.COLUMN_NAMES
 
 
 def _enqueue(im, thresh, min_area, ws, opts, s):
     """One image's launches on the stream s: the mask of the threshold; unetdc_mask_clean in place on it (the weak
     mask is that of the low threshold under the same resize rule); labelling + sums + compaction by unetdc_ccl_stats,
     with a split depth unetdc_split_stats (which also fills the label map when there is one), with shape and no split
-    depth unetdc_ccl_labels; then with shape unetdc_label_props on the label map and the optional grey plane."""
+    depth unetdc_ccl_labels (so does neighbors); then with shape unetdc_label_props on the label map and the optional grey
+    plane; then with neighbors unetdc_label_neighbors on the label map, the droplet capacity as its max_label."""
     (oh, ow), cap, h2, clean = im.mask.shape, im.area.shape[0], opts.half_pixels, opts.cleaning(thresh)
     _mask_from_probs(im.probs, thresh, im.mask, s)
     if clean is not None:
@@ -159,12 +174,16 @@ def _enqueue(im, thresh, min_area, ws, opts, s):
     label = None if im.label is None else im.label.data_ptr()
     if h2 is not None:
         _lib.call("unetdc_split_stats", *head, h2, *outs, label, cap, s)
-    elif opts.shape:
+    elif opts.shape or opts.neighbors is not None:
         _lib.call("unetdc_ccl_labels", *head, *outs, label, cap, s)
     else:
         _lib.call("unetdc_ccl_stats", *head, *outs, cap, s)
     if opts.shape:
         _lib.call("unetdc_label_props", label, None if im.gray is None else im.gray.data_ptr(), oh, ow, im.sums[2].data_ptr(), cap, s)
+    if opts.neighbors is not None:
+        room = im.pairs.shape[1]
+        _lib.call("unetdc_label_neighbors", label, cap, oh, ow, int(opts.neighbors), ws.data_ptr(), ws.numel(), im.pair_count.data_ptr(),
+                  *((im.pairs[j].data_ptr() if room else None) for j in range(3)), room, *(im.per_label[j].data_ptr() for j in range(5)), s)
 
 
 def _check_gray(gray, oh, ow):
@@ -180,23 +199,39 @@ def _props_dict(area, sums, with_gray):
     return out
 
 
-def _workspace_bytes(lib, out_hws, opts, clean):
+def _neighbors_dict(pairs, per_label):
+    """The record of utils.droplet_neighbors.neighbors_numpy from the int64 copies [3, pairs] and [5, droplets]."""
+    from utils.droplet_neighbors import COLUMN_NAMES
+    return {"pairs": dict(zip(("a", "b", "d2"), pairs)), **dict(zip(COLUMN_NAMES, per_label))}
+
+
+def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room):
     query = (lib.unetdc_split_workspace if opts.split_depth is not None else
-             lib.unetdc_ccl_labels_workspace if opts.shape else lib.unetdc_ccl_workspace)
+             lib.unetdc_ccl_labels_workspace if opts.shape or opts.neighbors is not None else lib.unetdc_ccl_workspace)
     nbytes = max(query(h, w) for h, w in out_hws)
+    if opts.neighbors is not None:
+        nbytes = max(nbytes, max(lib.unetdc_label_neighbors_workspace(h, w, cap, pair_room) for h, w in out_hws))
     if clean is not None:
         nbytes = max(nbytes, max(lib.unetdc_mask_clean_workspace(h, w) for h, w in out_hws))
     return nbytes
 
 
 NQ = 14    # UNETDC_SHAPE_QUANTITIES
+PAIR_ROOM = 1 << 14    # contact pairs per image the first launch has room for; an image with more is run again with twice that
+MAX_PAIR_ROOM = 1 << 27   # the largest table of unetdc_label_neighbors
 
 
-def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts):
+def _pair_room(cap, wanted):
+    """The pair capacity for a droplet capacity: cap labels have at most cap (cap - 1) / 2 pairs."""
+    return int(min(wanted, cap * (cap - 1) // 2, MAX_PAIR_ROOM))
+
+
+def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None):
     """The one launch-and-readback body -> (B Droplets, the device outputs (count, area, sumy, sumx) or None when an image
     had more droplets than they hold).  Every launch of the batch is enqueued back to back on the current stream into ONE
     set of output planes; the host then waits ONCE: one device->host copy brings the B droplet counts (and the clean
-    counts behind them), two more the filled part of the per-droplet integers."""
+    counts and with neighbors the pair counts behind them), two more the filled part of the per-droplet integers; with
+    neighbors one more the per-droplet neighbour integers and one the filled part of the pair lists."""
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -207,35 +242,50 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts):
     if gray is not None:
         for g, (oh, ow) in zip(gray, out_hws):
             _check_gray(g, oh, ow)
-    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean), dtype=torch.uint8, device=dev)   # one: stream order
-    counts = torch.zeros(B * (1 if clean is None else 5), dtype=torch.int32, device=dev)   # droplet counts, then 4 per image
+    nb = opts.neighbors is not None
+    room = _pair_room(cap, PAIR_ROOM if pair_room is None else pair_room) if nb else 0
+    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, cap, room), dtype=torch.uint8, device=dev)   # one: stream order
+    nc = B * (1 if clean is None else 5)
+    counts = torch.zeros(nc + B * nb, dtype=torch.int32, device=dev)   # droplet counts, then 4 per image, then the pair counts
+    pairs = torch.empty(B, 3, room, dtype=torch.int32, device=dev) if nb else None
+    per_label = torch.empty(B, 5, cap, dtype=torch.int32, device=dev) if nb else None
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
     # per image: sum y, sum x, then with shape the rows of unetdc_label_props, which wants them [NQ][cap] in one piece
     sums = torch.empty(B, 2 + NQ if opts.shape else 2, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
     images = []
     for i, (oh, ow) in enumerate(out_hws):
         images.append(_Image(probs[i], torch.empty(oh, ow, dtype=torch.uint8, device=dev),
-                             torch.empty(oh, ow, dtype=torch.int32, device=dev) if opts.labels or opts.shape else None,
+                             torch.empty(oh, ow, dtype=torch.int32, device=dev) if opts.labels or opts.shape or nb else None,
                              None if gray is None else gray[i], counts[i:], area[i], sums[:, i],
-                             None if clean is None else counts[B + 4 * i:]))
+                             None if clean is None else counts[B + 4 * i:],
+                             *((counts[nc + i:], pairs[i], per_label[i]) if nb else ())))
         _enqueue(images[i], thresh, min_area, ws, opts, s)
     n = counts.cpu().numpy().astype(np.int64)                       # the batch's only host wait
-    clean_counts = n[B:].reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
-    n = n[:B]
+    clean_counts = n[B:nc].reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
+    n_pairs, n = n[nc:], n[:B]
     nmax = int(min(n.max(initial=0), cap))
     a_h = area[:, :nmax].cpu().numpy().astype(np.int64)
     s_h = sums[:, :, :nmax].cpu().numpy()
+    if nb:
+        l_h = per_label[:, :, :nmax].cpu().numpy().astype(np.int64)
+        p_h = pairs[:, :, :int(min(n_pairs.max(initial=0), room))].cpu().numpy().astype(np.int64)
     out = []
     for i, im in enumerate(images):
         if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
             out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, int(n[i]),
-                                 None if gray is None else gray[i:i + 1], opts)[0][0])
+                                 None if gray is None else gray[i:i + 1], opts, pair_room)[0][0])
+            continue
+        if nb and n_pairs[i] > room:              # more contact pairs than the pair lists hold: this image again with twice the room
+            if room >= MAX_PAIR_ROOM:
+                raise _lib.UnetdcError(f"more than {MAX_PAIR_ROOM} contact pairs in one image")
+            out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, max_droplets,
+                                 None if gray is None else gray[i:i + 1], opts, 2 * max(room, 1))[0][0])
             continue
         a, si = a_h[i, :n[i]], s_h[:, i, :n[i]]
         d = np.maximum(a, 1)
         out.append(Droplets(im.mask, a, si[0].astype(np.float64) / d, si[1].astype(np.float64) / d,
                             im.label if opts.labels else None, _props_dict(a, si, gray is not None) if opts.shape else None,
-                            clean_counts[i]))
+                            clean_counts[i], _neighbors_dict(p_h[i, :, :n_pairs[i]], l_h[i, :, :n[i]]) if nb else None))
     return out, ((counts[:B], area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
 
 
@@ -243,7 +293,7 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs -> a list of B Droplets, after
     ONE host wait for the whole batch (_droplets).  keep_sums=True returns (that list, the device outputs (count, area,
     sumy, sumx) or None when an image had more droplets than they hold) for density.density_maps_batch.
-    options: split_depth, shape, return_labels, thresh_low, max_hole_area by name, or options=DropletOptions(...); and
+    options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors by name, or options=DropletOptions(...); and
     gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none).  Every option adds its launches
     behind each image's existing ones and its integers to the copies the host already waits for; all off: no launch is added."""
     opts, gray = _options(options, thresh)
