@@ -153,6 +153,82 @@ def test_sizing_queries_answer_zero_for_widths_the_launchers_refuse(lib):
     assert rc == -1 and b"unsupported" in lib.unetdc_last_error(), (rc, lib.unetdc_last_error())
 
 
+IMAGE_SIZES = [(1, 1), (1, 64), (37, 53), (64, 64), (96, 130), (300, 401), (1040, 1388), (16384, 16384)]
+IMAGE_LIMITS = [0, 1, 33, 2 ** 14, 2 ** 27]       # max_label, max_pairs
+
+
+def image_abi_cases():
+    """{query: [argument tuple, ...]}: the geometries every image-side launcher accepts, then the refusals that
+    include/unetdc_hip.h documents (a non-positive or 16385-pixel side, h * w >= 2^30, radius 0 and 65, a negative limit)."""
+    bad_sides = [(0, 5), (5, 0), (-1, 5)]
+    too_long = [(16385, 5), (5, 16385)]
+    c = {}
+    c["unetdc_ccl_workspace"] = list(IMAGE_SIZES)
+    c["unetdc_ccl_labels_workspace"] = IMAGE_SIZES + bad_sides
+    c["unetdc_split_workspace"] = IMAGE_SIZES + bad_sides
+    c["unetdc_mask_clean_workspace"] = IMAGE_SIZES + bad_sides + too_long
+    c["unetdc_label_overlap_workspace"] = ([(h, w, mp) for h, w in IMAGE_SIZES for mp in IMAGE_LIMITS] +
+                                           [(h, w, 33) for h, w in bad_sides + too_long] + [(64, 64, -1)])
+    c["unetdc_label_neighbors_workspace"] = ([(h, w, ml, mp) for h, w in IMAGE_SIZES for ml in IMAGE_LIMITS for mp in IMAGE_LIMITS] +
+                                             [(h, w, 33, 33) for h, w in bad_sides + too_long] + [(64, 64, -1, 33), (64, 64, 33, -1)])
+    c["unetdc_border_weights_workspace"] = ([(n, h, w, r) for n in (1, 3, 8) for h, w in IMAGE_SIZES for r in (1, 64)] +
+                                            [(1, h, w, 5) for h, w in bad_sides + too_long] +
+                                            [(1, 64, 64, 0), (1, 64, 64, 65), (0, 64, 64, 5)])
+    c["unetdc_density_workspace"] = ([s for s in IMAGE_SIZES if min(s) >= 2] + [(1, 1), (1, 64)] + bad_sides +
+                                     [(32768, 32768)])
+    c["unetdc_rolling_ball_workspace"] = [(h, w, cn) for h, w in IMAGE_SIZES for cn in (1, 2, 3, 4)]
+    c["unetdc_elastic_fields_workspace"] = ([(n, h, w, s) for n in (1, 3, 8) for h, w in IMAGE_SIZES if max(h, w) <= 1024
+                                             for s in (0.5, 8.0)] +
+                                            [(-1, 64, 64, 8.0), (1, 0, 64, 8.0), (1, 64, 0, 8.0), (1, 64, 64, 0.0),
+                                             (1, 64, 64, -1.0), (1, 64, 64, 300.0)])
+    c["unetdc_focal_dice_loss_workspace"] = [(n, h * w) for n in (1, 3, 8) for h, w in IMAGE_SIZES]
+    return c
+
+
+def test_image_workspace_answers_are_the_recorded_ones(lib, golden_dir):
+    """The eleven host-only workspace queries of the image-side stages, against tests/golden/image_abi_answers.json: recorded
+    from the library of the commit BEFORE each stage got its single layout function (csrc/workspace.h), over image_abi_cases().
+    A refused geometry answers 0, for unetdc_elastic_fields_workspace -1."""
+    import json
+    t = json.load(open(os.path.join(golden_dir, "image_abi_answers.json")))
+    cases = image_abi_cases()
+    assert sorted(t) == sorted(cases) and len(cases) == 11
+    checked, bad = 0, []
+    for name, rows in cases.items():
+        assert [tuple(r[:-1]) for r in t[name]] == rows, name
+        for args, rec in zip(rows, t[name]):
+            got = getattr(lib, name)(*args)
+            checked += 1
+            if got != rec[-1]:
+                bad.append((name, args, got, rec[-1]))
+    assert checked == 8 + 11 + 11 + 13 + 46 + 207 + 56 + 12 + 32 + 42 + 24
+    assert not bad, bad[:10]
+    refused = {n: [r[-1] for r in t[n] if min(r[:2]) <= 0] for n in t if n not in ("unetdc_ccl_workspace", "unetdc_rolling_ball_workspace",
+                                                                                    "unetdc_focal_dice_loss_workspace")}
+    assert all(v and set(v) == {-1 if n == "unetdc_elastic_fields_workspace" else 0} for n, v in refused.items()), refused
+
+
+def test_ccl_stats_and_rolling_ball_refuse_a_workspace_one_byte_short(lib):
+    """Both check the workspace size before any HIP call (host memory stands in for device memory): one byte less than their
+    query names is UNETDC_EWORKSPACE, and the message names the stage."""
+    import ctypes
+    buf = ctypes.create_string_buffer(4096)
+    a = (ctypes.addressof(buf) + 63) // 64 * 64
+    need = lib.unetdc_ccl_workspace(37, 53)
+    rc = lib.unetdc_ccl_stats(a, 37, 53, 1, a, need - 1, a, a, a, a, a, 8, None)
+    err = lib.unetdc_last_error()
+    assert rc == -3 and err.startswith(b"ccl_stats") and b"workspace too small" in err, (rc, err)
+    need = lib.unetdc_rolling_ball_workspace(37, 53, 3)
+    rc = lib.unetdc_rolling_ball_u8(a, a + 64, 37, 53, 3, 50, a, need - 1, None)
+    err = lib.unetdc_last_error()
+    assert rc == -3 and err.startswith(b"rolling_ball") and b"workspace too small" in err, (rc, err)
+    # the size check comes before the 16-byte alignment check
+    rc = lib.unetdc_rolling_ball_u8(a + 1, a + 64, 37, 53, 3, 50, a, need - 1, None)
+    assert rc == -3, (rc, lib.unetdc_last_error())
+    rc = lib.unetdc_rolling_ball_u8(a + 1, a + 64, 37, 53, 3, 50, a, need, None)
+    assert rc == -1 and b"aligned" in lib.unetdc_last_error(), (rc, lib.unetdc_last_error())
+
+
 def test_no_kernel_carries_packed_fp32(lib):
     """Build guard (widened in round 3 to EVERY kernel of the library): the packed-fp32 (SLP-vectorised) build
     of the fused BatchNorm-backward epilogue was not run-to-run deterministic on MI355X and the cause is not identified

@@ -564,12 +564,12 @@ int64_t unetdc_ccl_workspace(int h, int w) { return ccl_workspace_bytes(h, w); }
 int unetdc_ccl_stats(const uint8_t* mask, int h, int w, int min_area, void* workspace, int64_t workspace_bytes,
                      int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx, int32_t* out_root,
                      int max_out, unetdc_stream_t s) {
-  return launch_ccl_stats(mask, h, w, min_area, workspace, (long)workspace_bytes, out_count, out_area,
-                          reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root, max_out,
-                          (hipStream_t)s);
+  return launch_ccl("ccl_stats", mask, h, w, min_area, workspace, (long)workspace_bytes, out_count, out_area,
+                    reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root, nullptr, max_out,
+                    (hipStream_t)s);
 }
 
-int64_t unetdc_split_workspace(int h, int w) { return h > 0 && w > 0 ? split_workspace_bytes(h, w) : 0; }
+int64_t unetdc_split_workspace(int h, int w) { return split_workspace_bytes(h, w); }
 
 int unetdc_edt_sq(const uint8_t* mask, int h, int w, int32_t* out_d2, void* workspace, int64_t workspace_bytes,
                   unetdc_stream_t s) {
@@ -584,14 +584,15 @@ int unetdc_split_stats(const uint8_t* mask, int h, int w, int min_area, int spli
                             out_label, max_out, (hipStream_t)s);
 }
 
-int64_t unetdc_ccl_labels_workspace(int h, int w) { return h > 0 && w > 0 ? ccl_labels_workspace_bytes(h, w) : 0; }
+int64_t unetdc_ccl_labels_workspace(int h, int w) { return ccl_labels_workspace_bytes(h, w); }
 
 int unetdc_ccl_labels(const uint8_t* mask, int h, int w, int min_area, void* workspace, int64_t workspace_bytes,
                       int32_t* out_count, int32_t* out_area, int64_t* out_sumy, int64_t* out_sumx, int32_t* out_root,
                       int32_t* out_label, int max_out, unetdc_stream_t s) {
-  return launch_ccl_labels(mask, h, w, min_area, workspace, (long)workspace_bytes, out_count, out_area,
-                           reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root, out_label,
-                           max_out, (hipStream_t)s);
+  UNETDC_REQUIRE(out_label, "ccl_labels: null pointer");
+  return launch_ccl("ccl_labels", mask, h, w, min_area, workspace, (long)workspace_bytes, out_count, out_area,
+                    reinterpret_cast<long long*>(out_sumy), reinterpret_cast<long long*>(out_sumx), out_root, out_label,
+                    max_out, (hipStream_t)s);
 }
 
 static_assert(UNETDC_SHAPE_QUANTITIES == SHAPE_QUANTITIES, "unetdc_label_props output rows");
@@ -600,9 +601,7 @@ int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, 
   return launch_label_props(label, gray, h, w, reinterpret_cast<long long*>(out), max_out, (hipStream_t)s);
 }
 
-int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) {
-  return h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_pairs >= 0 ? label_overlap_workspace_bytes(h, w, max_pairs) : 0;
-}
+int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) { return label_overlap_workspace_bytes(h, w, max_pairs); }
 
 int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,
                          int64_t workspace_bytes, int32_t* out_count, int32_t* out_a, int32_t* out_b, int32_t* out_n,
@@ -623,9 +622,7 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                                 max_pairs, out_nn_label, out_nn_d2, out_degree, out_cluster, out_cluster_size, (hipStream_t)s);
 }
 
-int64_t unetdc_mask_clean_workspace(int h, int w) {
-  return h > 0 && w > 0 && h <= 16384 && w <= 16384 ? mask_clean_workspace_bytes(h, w) : 0;
-}
+int64_t unetdc_mask_clean_workspace(int h, int w) { return mask_clean_workspace_bytes(h, w); }
 
 int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, int max_hole_area, void* workspace,
                       int64_t workspace_bytes, uint8_t* out_mask, int32_t* out_counts, unetdc_stream_t s) {

@@ -191,26 +191,40 @@ __global__ __launch_bounds__(256) void augment_gather_kernel(const float* __rest
 
 int aug_radius(double sigma) { return (int)(4.0 * sigma + 0.5); }
 
+static bool aug_shape_ok(int n, int h, int w) { return n >= 0 && h > 0 && w > 0; }
+// int(4 sigma + 0.5) <= AUG_MAX_RADIUS; the bound on sigma itself keeps that conversion to int defined
+static bool aug_sigma_ok(double sigma) { return sigma > 0.0 && sigma <= AUG_MAX_RADIUS && aug_radius(sigma) <= AUG_MAX_RADIUS; }
+
+// the row-pass output of every slot, then the padded Gaussian taps; no padding, no slack.  AUG_MAX_SIDE is the launcher's own
+// check (the LDS of the row pass): the layout does not depend on it, and the query names a size for any positive sides
+struct ElasticPlanes {
+  float *tmp, *wts;
+};
+static Layout<ElasticPlanes> elastic_layout(int n, int h, int w, double sigma, void* workspace) {
+  if (!(aug_shape_ok(n, h, w) && aug_sigma_ok(sigma))) return {false, 0, {}};
+  Carver c(workspace);
+  ElasticPlanes p;
+  p.tmp = c.take<float>((long)n * 2 * h * w);
+  p.wts = c.take<float>(aug_taps_padded(aug_radius(sigma)));
+  return {true, c.bytes(), p};
+}
+// -1, not 0, for a geometry the launcher refuses
 long elastic_fields_workspace_bytes(int n, int h, int w, double sigma) {
-  if (n < 0 || h <= 0 || w <= 0 || !(sigma > 0.0) || sigma > AUG_MAX_RADIUS / 4.0) return -1;
-  return 4L * ((long)n * 2 * h * w + aug_taps_padded(aug_radius(sigma)));
+  const auto lay = elastic_layout(n, h, w, sigma, nullptr);
+  return lay.ok ? lay.bytes : -1;
 }
 
 int launch_elastic_fields(const unsigned* seeds, int n, int h, int w, double sigma, float alpha, float* fields,
                           void* workspace, long workspace_bytes, hipStream_t stream) {
-  UNETDC_REQUIRE(n >= 0 && h > 0 && w > 0 && h <= AUG_MAX_SIDE && w <= AUG_MAX_SIDE,
+  UNETDC_REQUIRE(aug_shape_ok(n, h, w) && h <= AUG_MAX_SIDE && w <= AUG_MAX_SIDE,
                  "elastic_fields: bad geometry n=%d h=%d w=%d (sides up to %d)", n, h, w, AUG_MAX_SIDE);
-  UNETDC_REQUIRE(sigma > 0.0 && aug_radius(sigma) <= AUG_MAX_RADIUS, "elastic_fields: sigma must be in (0, %g]",
-                 AUG_MAX_RADIUS / 4.0);
+  UNETDC_REQUIRE(aug_sigma_ok(sigma), "elastic_fields: sigma must be in (0, %g]", AUG_MAX_RADIUS / 4.0);
   if (n == 0) return UNETDC_OK;
   UNETDC_REQUIRE(seeds && fields && workspace, "elastic_fields: null pointer");
-  if (workspace_bytes < elastic_fields_workspace_bytes(n, h, w, sigma)) {
-    set_error("elastic_fields: workspace too small (%ld bytes)", workspace_bytes);
-    return UNETDC_EWORKSPACE;
-  }
+  const auto lay = elastic_layout(n, h, w, sigma, workspace);
+  if (int rc = require_workspace("elastic_fields", workspace_bytes, lay.bytes)) return rc;
   const int r = aug_radius(sigma), taps = aug_taps_padded(r);
-  float* tmp = reinterpret_cast<float*>(workspace);
-  float* wts = tmp + (long)n * 2 * h * w;
+  const auto [tmp, wts] = lay.planes;
   hipLaunchKernelGGL(gauss_weights_kernel, dim3(1), dim3(256), 0, stream, wts, r, taps, sigma);
   const int lds = AUG_ROWS * aug_row_lds_floats(w, r) * (int)sizeof(float);       // <= 4 x (1024 + 2056) floats = 48 KB
   for (int s0 = 0; s0 < n; s0 += AUG_MAX_SEEDS) {

@@ -180,35 +180,40 @@ __global__ __launch_bounds__(256) void border_row_kernel(const int* __restrict__
   if (out_d2) out_d2[base + x] = D2;
 }
 
-static bool border_geometry_ok(int n, int h, int w, int radius) {
-  return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && h <= BORDER_MAX_SIDE && w <= BORDER_MAX_SIDE && (long)h * w < (1L << 30) &&
-         radius >= 1 && radius <= BORDER_MAX_RADIUS;
+// ids, the two candidate ids (int32 each) and the packed dy pair (uint16) of every pixel, 64 spare bytes
+struct BorderPlanes {
+  int *L, *ca, *cb;
+  unsigned short* cd;
+};
+static Layout<BorderPlanes> border_layout(int n, int h, int w, int radius, void* workspace) {
+  if (!(n >= 1 && n <= 65535 && h >= 1 && w >= 1 && h <= BORDER_MAX_SIDE && w <= BORDER_MAX_SIDE && (long)h * w < (1L << 30) &&
+        radius >= 1 && radius <= BORDER_MAX_RADIUS))
+    return {false, 0, {}};
+  const long total = (long)n * h * w;
+  Carver c(workspace);
+  BorderPlanes p;
+  p.L = c.take<int>(total);
+  p.ca = c.take<int>(total);
+  p.cb = c.take<int>(total);
+  p.cd = c.take<unsigned short>(total);
+  c.slack(64);
+  return {true, c.bytes(), p};
 }
-
-// ids, the two candidate ids (int32 each) and the packed dy pair (uint16) of every pixel
-long border_workspace_bytes(int n, int h, int w, int radius) {
-  return border_geometry_ok(n, h, w, radius) ? (long)n * h * w * 14 + 64 : 0;
-}
+long border_workspace_bytes(int n, int h, int w, int radius) { return border_layout(n, h, w, radius, nullptr).bytes; }
 
 int launch_border_weights(const float* target, int n, int h, int w, float w0, float sigma, int radius, float* out_weight,
                           int* out_d1, int* out_d2, void* workspace, long workspace_bytes, hipStream_t stream) {
   UNETDC_REQUIRE(target && out_weight && workspace, "border_weights: null pointer");
-  UNETDC_REQUIRE(border_geometry_ok(n, h, w, radius),
+  const auto lay = border_layout(n, h, w, radius, workspace);
+  UNETDC_REQUIRE(lay.ok,
                  "border_weights: bad geometry (n 1..65535, sides 1..16384, h * w < 2^30, radius 1..64)");
   UNETDC_REQUIRE(sigma > 0.f && sigma <= 3.0e38f && w0 >= 0.f && w0 <= 3.0e38f,
                  "border_weights: sigma must be positive and w0 non-negative (both finite)");
   UNETDC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "border_weights: workspace must be 4-byte aligned");
-  if (workspace_bytes < border_workspace_bytes(n, h, w, radius)) {
-    set_error("border_weights: workspace too small (%ld < %ld bytes)", workspace_bytes, border_workspace_bytes(n, h, w, radius));
-    return UNETDC_EWORKSPACE;
-  }
+  if (int rc = require_workspace("border_weights", workspace_bytes, lay.bytes)) return rc;
   const int hw = h * w;
-  const long total = (long)n * hw;
-  int* L = reinterpret_cast<int*>(workspace);
-  int* ca = L + total;
-  int* cb = ca + total;
-  unsigned short* cd = reinterpret_cast<unsigned short*>(cb + total);
-  const dim3 flat(std::min((hw + 255) / 256, 4096), n);
+  const auto [L, ca, cb, cd] = lay.planes;
+  const dim3 flat(grid_for(hw, 256, 4096), n);
   hipLaunchKernelGGL(border_init_kernel, flat, dim3(256), 0, stream, target, L, hw, w);
   hipLaunchKernelGGL(border_merge_kernel, flat, dim3(256), 0, stream, L, h, w);
   hipLaunchKernelGGL(border_flatten_kernel, flat, dim3(256), 0, stream, L, hw);

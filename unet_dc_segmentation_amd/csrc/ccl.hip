@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const unsigned char* __r
     const int i = base + k;
     if (i < n && ccl_kept(mask, L, area, i, min_area)) ++c;
   }
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) blocksum[b] = red[0] + red[1] + red[2] + red[3];
@@ -172,19 +172,12 @@ __global__ void ccl_label_kernel(const unsigned char* __restrict__ mask, const i
   }
 }
 
-static int ccl_grid(long n) {
-  long nb = (n + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
-
 int launch_mask_from_probs(const float* probs, int ph, int pw, float thresh, unsigned char* mask, int oh, int ow,
                            hipStream_t stream) {
   UNETDC_REQUIRE(probs && mask && ph > 0 && pw > 0 && oh > 0 && ow > 0, "mask_from_probs: bad arguments");
   // cv2.resize(..., INTER_NEAREST): x_ofs[x] = min(cvFloor(x * (src_w / dst_w)), src_w - 1) in double precision
-  hipLaunchKernelGGL(mask_kernel, dim3(ccl_grid((long)oh * ow)), dim3(256), 0, stream, probs, ph, pw, thresh, mask, oh, ow,
-                     (double)ph / (double)oh, (double)pw / (double)ow);
+  hipLaunchKernelGGL(mask_kernel, dim3(grid_for((long)oh * ow, 256, 4096)), dim3(256), 0, stream, probs, ph, pw, thresh, mask, oh,
+                     ow, (double)ph / (double)oh, (double)pw / (double)ow);
   return check_launch("mask_kernel");
 }
 
@@ -210,34 +203,42 @@ int launch_mask_from_probs_linear(const float* probs, int ph, int pw, float thre
                                   const int* xofs, const short* xcoef, const int* yofs, const short* ycoef, hipStream_t stream) {
   UNETDC_REQUIRE(probs && mask && xofs && xcoef && yofs && ycoef && ph > 0 && pw > 0 && oh > 0 && ow > 0,
                  "mask_from_probs_linear: bad arguments");
-  hipLaunchKernelGGL(mask_linear_kernel, dim3(ccl_grid((long)oh * ow)), dim3(256), 0, stream, probs, ph, pw, thresh, mask, oh, ow,
-                     xofs, xcoef, yofs, ycoef);
+  hipLaunchKernelGGL(mask_linear_kernel, dim3(grid_for((long)oh * ow, 256, 4096)), dim3(256), 0, stream, probs, ph, pw, thresh, mask,
+                     oh, ow, xofs, xcoef, yofs, ycoef);
   return check_launch("mask_linear_kernel");
 }
 
-long ccl_workspace_bytes(int h, int w) {
+// the two coordinate sums, the union-find, the areas, one block sum per CCL_BLK pixels (+ 16 words), one after the other
+// without padding, and 64 spare bytes; `extra` > 0: from the next multiple of 64 that many more planes, 64 spare bytes again
+Layout<CclWorkspace> ccl_layout(int h, int w, int extra, void* workspace) {
+  if (!(h > 0 && w > 0 && (long)h * w < (1L << 30))) return {false, 0, {}};
   const long n = (long)h * w, nb = (n + CCL_BLK - 1) / CCL_BLK;
-  return n * (4 + 4 + 8 + 8) + (nb + 16) * 4 + 64;
+  Carver c(workspace);
+  CclWorkspace p = {};
+  p.ccl.sy = c.take<unsigned long long>(n);
+  p.ccl.sx = c.take<unsigned long long>(n);
+  p.ccl.L = c.take<int>(n);
+  p.ccl.area = c.take<int>(n);
+  p.ccl.blocksum = c.take<int>(nb + 16);
+  c.slack(64);
+  if (extra > 0) {
+    c.align(64);
+    p.more = c.take<int>(extra * n);
+    c.slack(64);
+  }
+  return {true, c.bytes(), p};
 }
-
-CclPlanes ccl_planes(void* workspace, int n) {
-  CclPlanes p;
-  p.sy = reinterpret_cast<unsigned long long*>(workspace);
-  p.sx = p.sy + n;
-  p.L = reinterpret_cast<int*>(p.sx + n);
-  p.area = p.L + n;
-  p.blocksum = p.area + n;
-  return p;
-}
+long ccl_workspace_bytes(int h, int w) { return ccl_layout(h, w, 0, nullptr).bytes; }
+long ccl_labels_workspace_bytes(int h, int w) { return ccl_layout(h, w, 1, nullptr).bytes; }
 
 void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(ccl_init_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n);
+  hipLaunchKernelGGL(ccl_init_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n);
 }
 
 void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
                        int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
                        hipStream_t stream) {
-  const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK, g = ccl_grid(n);
+  const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK, g = grid_for(n, 256, 4096);
   hipLaunchKernelGGL(ccl_stats_kernel, dim3(g), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, h, w);
   hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, stream, mask, p.L, p.area, n, min_area, p.blocksum);
   hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, stream, p.blocksum, nb, out_count);
@@ -247,49 +248,25 @@ void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, co
 
 void launch_ccl_label(const unsigned char* mask, const CclPlanes& p, const int* rank_of_root, int min_area, int* label, int n,
                       hipStream_t stream) {
-  hipLaunchKernelGGL(ccl_label_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, p.area, rank_of_root, min_area, label,
-                     n);
+  hipLaunchKernelGGL(ccl_label_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, mask, p.L, p.area, rank_of_root, min_area,
+                     label, n);
 }
 
-int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
-                     int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
-                     hipStream_t stream) {
-  UNETDC_REQUIRE(mask && workspace && out_count && out_area && out_sumy && out_sumx, "ccl_stats: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && (long)h * w < (1L << 30) && max_out >= 0, "ccl_stats: bad geometry");
-  if (workspace_bytes < ccl_workspace_bytes(h, w)) {
-    set_error("ccl_stats: workspace too small (%ld < %ld bytes)", workspace_bytes, ccl_workspace_bytes(h, w));
-    return UNETDC_EWORKSPACE;
-  }
+int launch_ccl(const char* who, const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
+               int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
+               int max_out, hipStream_t stream) {
+  UNETDC_REQUIRE(mask && workspace && out_count && out_area && out_sumy && out_sumx, "%s: null pointer", who);
+  const auto lay = ccl_layout(h, w, out_label ? 1 : 0, workspace);     // labels: the rank of every kept component at its root
+  UNETDC_REQUIRE(lay.ok && max_out >= 0, "%s: bad geometry", who);
+  if (int rc = require_workspace(who, workspace_bytes, lay.bytes)) return rc;
   const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK;
-  UNETDC_REQUIRE(nb <= 1024 * 1024, "ccl_stats: image too large");
-  const CclPlanes p = ccl_planes(workspace, n);
+  UNETDC_REQUIRE(nb <= 1024 * 1024, "%s: image too large", who);
+  const CclPlanes& p = lay.planes.ccl;
   launch_ccl_init(mask, p, n, stream);
-  hipLaunchKernelGGL(ccl_merge_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, h, w);
-  launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, nullptr, max_out, stream);
-  return check_launch("ccl kernels");
-}
-
-// the ccl planes, then the rank of every kept component at its root pixel
-long ccl_labels_workspace_bytes(int h, int w) { return ((ccl_workspace_bytes(h, w) + 63) / 64) * 64 + (long)h * w * 4 + 64; }
-
-int launch_ccl_labels(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
-                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
-                      int max_out, hipStream_t stream) {
-  UNETDC_REQUIRE(mask && workspace && out_count && out_area && out_sumy && out_sumx && out_label, "ccl_labels: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && (long)h * w < (1L << 30) && max_out >= 0, "ccl_labels: bad geometry");
-  if (workspace_bytes < ccl_labels_workspace_bytes(h, w)) {
-    set_error("ccl_labels: workspace too small (%ld < %ld bytes)", workspace_bytes, ccl_labels_workspace_bytes(h, w));
-    return UNETDC_EWORKSPACE;
-  }
-  const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK;
-  UNETDC_REQUIRE(nb <= 1024 * 1024, "ccl_labels: image too large");
-  const CclPlanes p = ccl_planes(workspace, n);
-  int* rank = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(workspace) + ((ccl_workspace_bytes(h, w) + 63) / 64) * 64);
-  launch_ccl_init(mask, p, n, stream);
-  hipLaunchKernelGGL(ccl_merge_kernel, dim3(ccl_grid(n)), dim3(256), 0, stream, mask, p.L, h, w);
-  launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, rank, max_out, stream);
-  launch_ccl_label(mask, p, rank, min_area, out_label, n, stream);
-  return check_launch("ccl label kernels");
+  hipLaunchKernelGGL(ccl_merge_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, mask, p.L, h, w);
+  launch_ccl_finish(mask, h, w, min_area, p, out_count, out_area, out_sumy, out_sumx, out_root, lay.planes.more, max_out, stream);
+  if (out_label) launch_ccl_label(mask, p, lay.planes.more, min_area, out_label, n, stream);
+  return check_launch(out_label ? "ccl label kernels" : "ccl kernels");
 }
 
 }  // namespace unetdc

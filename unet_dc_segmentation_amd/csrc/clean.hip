@@ -23,11 +23,6 @@ struct CleanPlanes {
   int *L, *aux, *counts;
 };
 
-__device__ __forceinline__ int clean_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // L[i] = i, aux[i] = 0; the first launch of a call also clears the four counts
 __global__ void clean_init_kernel(int* __restrict__ L, int* __restrict__ aux, int n, int* __restrict__ zero_counts) {
   if (zero_counts && blockIdx.x == 0 && threadIdx.x < 4) zero_counts[threadIdx.x] = 0;
@@ -70,7 +65,7 @@ __global__ __launch_bounds__(CLEAN_THREADS) void clean_select_kernel(const unsig
     out[i] = m ? 1 : 0;
     added += m && !s;
   }
-  added = clean_wave_sum(added);
+  added = wave_sum(added);
   if ((threadIdx.x & 63) == 0 && added) atomicAdd(&counts[0], added);
 }
 
@@ -129,9 +124,9 @@ __global__ __launch_bounds__(CLEAN_THREADS) void clean_fill_kernel(const unsigne
     }
     out[i] = v;
   }
-  holes = clean_wave_sum(holes);
-  pixels = clean_wave_sum(pixels);
-  open = clean_wave_sum(open);
+  holes = wave_sum(holes);
+  pixels = wave_sum(pixels);
+  open = wave_sum(open);
   if ((threadIdx.x & 63) == 0) {
     if (holes) atomicAdd(&counts[1], holes);
     if (pixels) atomicAdd(&counts[2], pixels);
@@ -146,12 +141,17 @@ __global__ void clean_copy_kernel(const unsigned char* in, unsigned char* out, i
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = in[i];
 }
 
-static int clean_grid(long n) {
-  long nb = (n + CLEAN_THREADS - 1) / CLEAN_THREADS;
-  return (int)(nb > 4096 ? 4096 : nb < 1 ? 1 : nb);
+// L, aux, then the four count words in a 64-byte block
+static Layout<CleanPlanes> clean_layout(int h, int w, void* workspace) {
+  if (!(h > 0 && w > 0 && h <= 16384 && w <= 16384 && (long)h * w < (1L << 30))) return {false, 0, {}};
+  Carver c(workspace);
+  CleanPlanes p;
+  p.L = c.take<int>((long)h * w);
+  p.aux = c.take<int>((long)h * w);
+  p.counts = c.take<int>(4, 64);
+  return {true, c.bytes(), p};
 }
-
-long mask_clean_workspace_bytes(int h, int w) { return (long)h * w * 8 + 64; }
+long mask_clean_workspace_bytes(int h, int w) { return clean_layout(h, w, nullptr).bytes; }
 
 // [a, a + na) and [b, b + nb) share a byte
 static bool clean_overlap(const void* a, long na, const void* b, long nb) {
@@ -162,25 +162,24 @@ static bool clean_overlap(const void* a, long na, const void* b, long nb) {
 int launch_mask_clean(const unsigned char* strong, const unsigned char* weak, int h, int w, int max_hole_area, void* workspace,
                       long workspace_bytes, unsigned char* out_mask, int* out_counts, hipStream_t stream) {
   UNETDC_REQUIRE(strong && workspace && out_mask, "mask_clean: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && h <= 16384 && w <= 16384 && (long)h * w < (1L << 30), "mask_clean: bad geometry (sides 1..16384)");
-  const long wsb = mask_clean_workspace_bytes(h, w);
-  UNETDC_REQUIRE(workspace_bytes >= wsb, "mask_clean: workspace too small (%ld < %ld bytes)", workspace_bytes, wsb);
+  const auto lay = clean_layout(h, w, workspace);
+  UNETDC_REQUIRE(lay.ok, "mask_clean: bad geometry (sides 1..16384)");
+  // a short workspace is UNETDC_EINVAL here, not UNETDC_EWORKSPACE (include/unetdc_hip.h)
+  if (int rc = require_workspace("mask_clean", workspace_bytes, lay.bytes, UNETDC_EINVAL)) return rc;
   UNETDC_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 4 == 0 && reinterpret_cast<uintptr_t>(out_counts) % 4 == 0,
                  "mask_clean: workspace and out_counts must be 4-byte aligned");
   const int n = h * w;
   UNETDC_REQUIRE((out_mask == strong || !clean_overlap(out_mask, n, strong, n)) &&
                      (out_mask == weak || !clean_overlap(out_mask, n, weak, n)),
                  "mask_clean: out_mask may be strong or weak itself, but not overlap either partly");
-  UNETDC_REQUIRE(!clean_overlap(workspace, wsb, out_mask, n) && !clean_overlap(workspace, wsb, strong, n) &&
-                     !clean_overlap(workspace, wsb, weak, n) && !clean_overlap(workspace, wsb, out_counts, 16) &&
+  UNETDC_REQUIRE(!clean_overlap(workspace, lay.bytes, out_mask, n) && !clean_overlap(workspace, lay.bytes, strong, n) &&
+                     !clean_overlap(workspace, lay.bytes, weak, n) && !clean_overlap(workspace, lay.bytes, out_counts, 16) &&
                      !clean_overlap(out_counts, 16, out_mask, n) && !clean_overlap(out_counts, 16, strong, n) &&
                      !clean_overlap(out_counts, 16, weak, n),
                  "mask_clean: the workspace and out_counts may overlap nothing else");
-  CleanPlanes p;
-  p.L = reinterpret_cast<int*>(workspace);
-  p.aux = p.L + n;
-  p.counts = out_counts ? out_counts : p.aux + n;
-  const dim3 grid(clean_grid(n)), block(CLEAN_THREADS);
+  CleanPlanes p = lay.planes;
+  if (out_counts) p.counts = out_counts;
+  const dim3 grid(grid_for(n, CLEAN_THREADS, 4096)), block(CLEAN_THREADS);
   if (!weak && max_hole_area == 0) {
     hipLaunchKernelGGL(clean_copy_kernel, grid, block, 0, stream, strong, out_mask, n, p.counts);
     return check_launch("clean_copy_kernel");

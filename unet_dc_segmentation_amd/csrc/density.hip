@@ -430,47 +430,39 @@ __global__ void density_sqrt_kernel(const long long* __restrict__ x, double* __r
     out[i] = dens_sqrt((double)x[i]);
 }
 
-static int dens_grid(long n) {
-  long nb = (n + DENS_THREADS - 1) / DENS_THREADS;
-  if (nb > 4096) nb = 4096;
-  return (int)(nb < 1 ? 1 : nb);
-}
-
-// workspace layout (each part 256-byte aligned)
-struct DensLayout {
-  long scratch, rows_cnt, rows_sumx, rows_min, rows_max, bounds, blur, m1, m2, roi, ring, radial, g0m, g0r, spatial, total;
+// workspace layout: every part rounded to 256 bytes
+struct DensPlanes {
+  DensScratch* sc;
+  int* rcnt;
+  long long* rsum;
+  int *rmin, *rmax;
+  double* bounds;
+  unsigned char *blur, *m1, *m2, *roi, *ring;
+  float *radial, *g0m, *g0r, *spatial;
 };
-
-static long dens_align(long v) { return (v + 255) & ~255L; }
-
-static DensLayout dens_layout(int h, int w) {
+static Layout<DensPlanes> dens_layout(int h, int w, void* workspace) {
+  if (!(h >= DENSITY_MIN_SIDE && w >= DENSITY_MIN_SIDE && (long)h * w < (1L << 30))) return {false, 0, {}};
   const long n = (long)h * w;
-  DensLayout l;
-  long o = 0;
-  auto take = [&](long bytes) { const long at = o; o += dens_align(bytes); return at; };
-  l.scratch = take(sizeof(DensScratch));
-  l.rows_cnt = take(4L * h);
-  l.rows_sumx = take(8L * h);
-  l.rows_min = take(4L * h);
-  l.rows_max = take(4L * h);
-  l.bounds = take(8L * (DENSITY_MAX_LAYERS + 1));
-  l.blur = take(n);
-  l.m1 = take(n);
-  l.m2 = take(n);
-  l.roi = take(n);
-  l.ring = take(n);
-  l.radial = take(4 * n);
-  l.g0m = take(4 * n);
-  l.g0r = take(4 * n);
-  l.spatial = take(4 * n);
-  l.total = o;
-  return l;
+  Carver c(workspace);
+  DensPlanes p;
+  p.sc = c.take<DensScratch>(1, 256);
+  p.rcnt = c.take<int>(h, 256);
+  p.rsum = c.take<long long>(h, 256);
+  p.rmin = c.take<int>(h, 256);
+  p.rmax = c.take<int>(h, 256);
+  p.bounds = c.take<double>(DENSITY_MAX_LAYERS + 1, 256);
+  p.blur = c.take<unsigned char>(n, 256);
+  p.m1 = c.take<unsigned char>(n, 256);
+  p.m2 = c.take<unsigned char>(n, 256);
+  p.roi = c.take<unsigned char>(n, 256);
+  p.ring = c.take<unsigned char>(n, 256);
+  p.radial = c.take<float>(n, 256);
+  p.g0m = c.take<float>(n, 256);
+  p.g0r = c.take<float>(n, 256);
+  p.spatial = c.take<float>(n, 256);
+  return {true, c.bytes(), p};
 }
-
-long density_workspace_bytes(int h, int w) {
-  if (h < DENSITY_MIN_SIDE || w < DENSITY_MIN_SIDE || (long)h * w >= (1L << 30)) return 0;
-  return dens_layout(h, w).total;
-}
+long density_workspace_bytes(int h, int w) { return dens_layout(h, w, nullptr).bytes; }
 
 int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int h, int w, const int* dcount, const int* darea,
                         const long long* dsumy, const long long* dsumx, int dcap, int nb_layers, double sigma,
@@ -481,8 +473,8 @@ int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int
   UNETDC_REQUIRE(rgb && mask && dcount && darea && dsumy && dsumx && taps && workspace && stats && radial_index &&
                      spatial_index,
                  "density_maps: null pointer");
-  UNETDC_REQUIRE(h >= DENSITY_MIN_SIDE && w >= DENSITY_MIN_SIDE && (long)h * w < (1L << 30),
-                 "density_maps: bad geometry h=%d w=%d (each side >= %d, h * w < 2^30)", h, w, DENSITY_MIN_SIDE);
+  const auto lay = dens_layout(h, w, workspace);
+  UNETDC_REQUIRE(lay.ok, "density_maps: bad geometry h=%d w=%d (each side >= %d, h * w < 2^30)", h, w, DENSITY_MIN_SIDE);
   UNETDC_REQUIRE(nb_layers >= 1 && nb_layers <= DENSITY_MAX_LAYERS, "density_maps: nb_layers=%d outside 1..%d", nb_layers,
                  DENSITY_MAX_LAYERS);
   UNETDC_REQUIRE(dcap >= 0, "density_maps: bad droplet capacity %d", dcap);
@@ -492,28 +484,16 @@ int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int
   DensTaps tp;
   for (int j = 0; j <= DENSITY_MAX_RADIUS; ++j) tp.w[j] = j <= R ? taps[j] : 0.0;
   for (int j = 0; j <= R; ++j) UNETDC_REQUIRE(isfinite(tp.w[j]) && tp.w[j] >= 0.0, "density_maps: bad tap %d", j);
-  const DensLayout l = dens_layout(h, w);
-  if (workspace_bytes < l.total) {
-    set_error("density_maps: workspace too small (%ld < %ld bytes)", workspace_bytes, l.total);
-    return UNETDC_EWORKSPACE;
-  }
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  DensScratch* sc = reinterpret_cast<DensScratch*>(ws + l.scratch);
-  int* rcnt = reinterpret_cast<int*>(ws + l.rows_cnt);
-  long long* rsum = reinterpret_cast<long long*>(ws + l.rows_sumx);
-  int* rmin = reinterpret_cast<int*>(ws + l.rows_min);
-  int* rmax = reinterpret_cast<int*>(ws + l.rows_max);
-  double* bounds = reinterpret_cast<double*>(ws + l.bounds);
-  unsigned char* blur = out_blur ? out_blur : ws + l.blur;
-  unsigned char* m1 = ws + l.m1;
-  unsigned char* m2 = ws + l.m2;
-  unsigned char* roi = out_roi ? out_roi : ws + l.roi;
-  unsigned char* ring = out_ring ? out_ring : ws + l.ring;
-  float* radial = out_radial ? out_radial : reinterpret_cast<float*>(ws + l.radial);
-  float* g0m = reinterpret_cast<float*>(ws + l.g0m);
-  float* g0r = reinterpret_cast<float*>(ws + l.g0r);
-  float* spatial = out_spatial ? out_spatial : reinterpret_cast<float*>(ws + l.spatial);
+  if (int rc = require_workspace("density_maps", workspace_bytes, lay.bytes)) return rc;
+  DensPlanes p = lay.planes;                                // a plane the caller wants takes the place of the workspace's
+  if (out_blur) p.blur = out_blur;
+  if (out_roi) p.roi = out_roi;
+  if (out_ring) p.ring = out_ring;
+  if (out_radial) p.radial = out_radial;
+  if (out_spatial) p.spatial = out_spatial;
+  const auto [sc, rcnt, rsum, rmin, rmax, bounds, blur, m1, m2, roi, ring, radial, g0m, g0r, spatial] = p;
   const long n = (long)h * w;
+  const dim3 flat(grid_for(n, DENS_THREADS, 4096));
 
   hipLaunchKernelGGL(density_init_kernel, dim3(1), dim3(256), 0, stream, sc, stats);
   hipLaunchKernelGGL(density_blur_kernel, dim3((w + DENS_TW - 1) / DENS_TW, (h + DENS_TH - 1) / DENS_TH), dim3(DENS_THREADS), 0,
@@ -528,20 +508,18 @@ int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int
   hipLaunchKernelGGL(density_rows_kernel, dim3(h), dim3(DENS_THREADS), 0, stream, m2, w, sc, roi, rcnt, rsum, rmin, rmax);
   hipLaunchKernelGGL(density_rings_kernel, dim3(1), dim3(DENS_RINGS_THREADS), 0, stream, h, w, rcnt, rsum, rmin, rmax, dcount,
                      darea, dsumy, dsumx, dcap, nb_layers, bounds, sc, stats);
-  hipLaunchKernelGGL(density_radial_kernel, dim3(dens_grid(n)), dim3(DENS_THREADS), 0, stream, roi, h, w, bounds, nb_layers,
-                     stats, ring, radial);
-  hipLaunchKernelGGL(density_gauss0_kernel, dim3(dens_grid(n)), dim3(DENS_THREADS), 0, stream, mask, roi, h, w, tp, R, g0m, g0r);
-  hipLaunchKernelGGL(density_gauss1_kernel, dim3(dens_grid(n)), dim3(DENS_THREADS), 0, stream, g0m, g0r, h, w, tp, R, stats,
-                     spatial);
-  hipLaunchKernelGGL(density_index_kernel, dim3(dens_grid(n)), dim3(DENS_THREADS), 0, stream, radial, spatial, n, stats,
-                     radial_index, spatial_index);
+  hipLaunchKernelGGL(density_radial_kernel, flat, dim3(DENS_THREADS), 0, stream, roi, h, w, bounds, nb_layers, stats, ring, radial);
+  hipLaunchKernelGGL(density_gauss0_kernel, flat, dim3(DENS_THREADS), 0, stream, mask, roi, h, w, tp, R, g0m, g0r);
+  hipLaunchKernelGGL(density_gauss1_kernel, flat, dim3(DENS_THREADS), 0, stream, g0m, g0r, h, w, tp, R, stats, spatial);
+  hipLaunchKernelGGL(density_index_kernel, flat, dim3(DENS_THREADS), 0, stream, radial, spatial, n, stats, radial_index,
+                     spatial_index);
   return check_launch("density kernels");
 }
 
 int launch_density_sqrt(const long long* x, double* out, long n, hipStream_t stream) {
   UNETDC_REQUIRE(x && out && n >= 0, "density_sqrt: bad arguments");
   if (n == 0) return UNETDC_OK;
-  hipLaunchKernelGGL(density_sqrt_kernel, dim3(dens_grid(n)), dim3(DENS_THREADS), 0, stream, x, out, n);
+  hipLaunchKernelGGL(density_sqrt_kernel, dim3(grid_for(n, DENS_THREADS, 4096)), dim3(DENS_THREADS), 0, stream, x, out, n);
   return check_launch("density_sqrt_kernel");
 }
 

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "workspace.h"
 #include "../../include/unetdc_hip.h"
 
 namespace unetdc {
@@ -198,8 +199,8 @@ constexpr int SPARE_ROWS = 64;
 inline long partial_floats(long rows, long L) { return (rows + SPARE_ROWS) * L; }    // floats of such a buffer
 inline long partial_row_cap(long floats, long L) { return floats / L - SPARE_ROWS; } // rows a caller-sized buffer takes
 inline int chunk_elems(int dtype) { return dtype == UNETDC_BF16 ? 8 : dtype == UNETDC_F32 ? 4 : 0; }   // 0: no such dtype
-inline int grid_for(long work_items, int per_block) {
-  return (int)std::min(std::max((work_items + per_block - 1) / per_block, 1L), 8192L);
+inline int grid_for(long work_items, int per_block, long cap = 8192) {
+  return (int)std::min(std::max((work_items + per_block - 1) / per_block, 1L), cap);
 }
 // One launch line per kernel: f(TypeTag<T>{}, std::bool_constant...) for the dtype (valid: chunk_elems) and run-time flags.
 template <typename T> struct TypeTag { using type = T; };
@@ -254,19 +255,25 @@ int launch_mask_from_probs(const float* probs, int ph, int pw, float thresh, uns
                            hipStream_t stream);
 int launch_mask_from_probs_linear(const float* probs, int ph, int pw, float thresh, unsigned char* mask, int oh, int ow,
                                   const int* xofs, const short* xcoef, const int* yofs, const short* ycoef, hipStream_t stream);
+// out_label null: unetdc_ccl_stats, else unetdc_ccl_labels (the larger workspace); who: the entry point's name for the messages
 long ccl_workspace_bytes(int h, int w);
-int launch_ccl_stats(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
-                     int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int max_out,
-                     hipStream_t stream);
-// the stages of launch_ccl_stats around its merge kernel, for split.hip: the planes of a ccl workspace (the first
-// ccl_workspace_bytes(h, w) bytes), their initialisation (L[i] = i, sums 0), and per-class sums -> min_area filter ->
-// raster-order compaction on whatever union-find the caller left in L.  rank_of_root (nullable, [h * w]) receives the
+long ccl_labels_workspace_bytes(int h, int w);
+int launch_ccl(const char* who, const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
+               int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
+               int max_out, hipStream_t stream);
+// the stages of launch_ccl around its merge kernel, for split.hip: the layout of a ccl workspace with `extra` more int32
+// planes of h * w words behind it (more), their initialisation (L[i] = i, sums 0), and per-class sums -> min_area
+// filter -> raster-order compaction on whatever union-find the caller left in L.  rank_of_root (nullable, [h * w]) receives the
 // 1-based output rank at the root pixel of every kept class.  No checks, no check_launch: the caller does both.
 struct CclPlanes {
   unsigned long long *sy, *sx;
   int *L, *area, *blocksum;
 };
-CclPlanes ccl_planes(void* workspace, int n);
+struct CclWorkspace {
+  CclPlanes ccl;
+  int* more;
+};
+Layout<CclWorkspace> ccl_layout(int h, int w, int extra, void* workspace);
 void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipStream_t stream);
 void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
                        int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
@@ -275,10 +282,6 @@ void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, co
 // launch_ccl_finish, which compresses L and fills rank_of_root)
 void launch_ccl_label(const unsigned char* mask, const CclPlanes& p, const int* rank_of_root, int min_area, int* label, int n,
                       hipStream_t stream);
-long ccl_labels_workspace_bytes(int h, int w);
-int launch_ccl_labels(const unsigned char* mask, int h, int w, int min_area, void* workspace, long workspace_bytes,
-                      int* out_count, int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* out_label,
-                      int max_out, hipStream_t stream);
 
 // shape.hip: per-label second moments, bounding box, perimeter classes and grey statistics of an int32 label map
 constexpr int SHAPE_QUANTITIES = 14;
@@ -298,7 +301,6 @@ int launch_label_neighbors(const int* label, int max_label, int h, int w, int ra
                            int* out_nn_d2, int* out_degree, int* out_cluster, int* out_cluster_size, hipStream_t stream);
 
 // split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
-long edt_workspace_bytes(int h, int w);
 int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,
                   hipStream_t stream);
 long split_workspace_bytes(int h, int w);

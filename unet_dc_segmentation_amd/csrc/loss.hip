@@ -121,20 +121,25 @@ static int loss_blocks(long hw) {
   return (int)nb;
 }
 
-long loss_workspace_bytes(int nimg, long hw) { return (long)nimg * loss_blocks(hw) * 4 * 4; }
+// four partial sums per block of every image
+static Layout<float*> loss_layout(int nimg, long hw, void* workspace) {
+  if (!(nimg > 0 && nimg <= 65535 && hw > 0)) return {false, 0, nullptr};
+  Carver c(workspace);
+  float* parts = c.take<float>((long)nimg * loss_blocks(hw) * 4);
+  return {true, c.bytes(), parts};
+}
+long loss_workspace_bytes(int nimg, long hw) { return loss_layout(nimg, hw, nullptr).bytes; }
 
 // wt: null = the unweighted loss; weighted: the caller (abi.hip) has refused a null weight
 int launch_loss_fwd(const float* p, const float* t, const float* wt, float* loss_out, float* coef, void* workspace,
                     long workspace_bytes, int nimg, long hw, float alpha, float gamma, float ratio, float smooth,
                     hipStream_t stream) {
   UNETDC_REQUIRE(p && t && loss_out && coef && workspace, "focal_dice_loss: null pointer");
-  UNETDC_REQUIRE(nimg > 0 && nimg <= 65535 && hw > 0, "focal_dice_loss: bad shape");
+  const auto lay = loss_layout(nimg, hw, workspace);
+  UNETDC_REQUIRE(lay.ok, "focal_dice_loss: bad shape");
+  if (int rc = require_workspace("focal_dice_loss", workspace_bytes, lay.bytes)) return rc;
   const int nb = loss_blocks(hw);
-  if ((long)nimg * nb * 16 > workspace_bytes) {
-    set_error("focal_dice_loss: workspace too small");
-    return UNETDC_EWORKSPACE;
-  }
-  float* parts = reinterpret_cast<float*>(workspace);
+  float* parts = lay.planes;
   if (wt) hipLaunchKernelGGL(loss_reduce_kernel<true>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, parts, hw, alpha, gamma);
   else hipLaunchKernelGGL(loss_reduce_kernel<false>, dim3(nb, nimg), dim3(256), 0, stream, p, t, wt, parts, hw, alpha, gamma);
   int rc = check_launch("loss_reduce_kernel");

@@ -14,13 +14,14 @@
 
 namespace unetdc {
 
-// max_pairs beyond h * w buys nothing: there are at most h * w pairs
-static int match_effective_pairs(int h, int w, int max_pairs) {
-  const long n = (long)h * w;
-  return (long)max_pairs < n ? max_pairs : (int)n;
+// the pair table alone.  max_pairs beyond h * w buys nothing: there are at most h * w pairs
+static Layout<PairPlanes> match_layout(int h, int w, int max_pairs, void* workspace) {
+  if (!(h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_pairs >= 0)) return {false, 0, {}};
+  Carver c(workspace);
+  const PairPlanes p = pair_carve(c, (int)std::min((long)max_pairs, (long)h * w));
+  return {true, c.bytes(), p};
 }
-
-long label_overlap_workspace_bytes(int h, int w, int max_pairs) { return pair_table_bytes(match_effective_pairs(h, w, max_pairs)); }
+long label_overlap_workspace_bytes(int h, int w, int max_pairs) { return match_layout(h, w, max_pairs, nullptr).bytes; }
 
 __global__ __launch_bounds__(256) void match_overlap_kernel(const int* __restrict__ label_a, int max_a,
                                                             const int* __restrict__ label_b, int max_b, int h, int w,
@@ -52,16 +53,14 @@ int launch_label_overlap(const int* label_a, int max_a, const int* label_b, int 
                          hipStream_t stream) {
   UNETDC_REQUIRE(label_a && label_b && workspace && out_count && ((out_a && out_b && out_n) || max_pairs == 0),
                  "label_overlap: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_a >= 0 && max_b >= 0 && max_pairs >= 0,
+  const auto lay = match_layout(h, w, max_pairs, workspace);
+  UNETDC_REQUIRE(lay.ok && max_a >= 0 && max_b >= 0,
                  "label_overlap: bad geometry (sides 1..16384, non-negative label and pair limits)");
-  if (workspace_bytes < label_overlap_workspace_bytes(h, w, max_pairs)) {
-    set_error("label_overlap: workspace too small (%ld < %ld bytes)", workspace_bytes, label_overlap_workspace_bytes(h, w, max_pairs));
-    return UNETDC_EWORKSPACE;
-  }
-  const PairPlanes p = pair_planes(workspace, match_effective_pairs(h, w, max_pairs));
+  if (int rc = require_workspace("label_overlap", workspace_bytes, lay.bytes)) return rc;
+  const PairPlanes& p = lay.planes;
   pair_table_init<PairAdd>(p, stream);
   const long units = (long)h * ((w + 63) / 64);
-  hipLaunchKernelGGL(match_overlap_kernel, dim3(pair_grid(units, 4, 8192)), dim3(256), 0, stream, label_a, max_a, label_b, max_b,
+  hipLaunchKernelGGL(match_overlap_kernel, dim3(grid_for(units, 4, 8192)), dim3(256), 0, stream, label_a, max_a, label_b, max_b,
                      h, w, p);
   pair_table_list(p, max_pairs, out_count, out_a, out_b, out_n, stream);
   return check_launch("label overlap kernels");

@@ -46,30 +46,27 @@ static int neighbors_effective_pairs(int max_label, int max_pairs) {
   return (long)max_pairs < n ? max_pairs : (int)n;
 }
 
-static NeighborPlanes neighbor_planes(void* workspace, int h, int w, int max_label, int max_pairs) {
-  unsigned char* b = reinterpret_cast<unsigned char*>(workspace) + pair_table_bytes(neighbors_effective_pairs(max_label, max_pairs));
-  const long labels = pair_align64(((long)max_label + 1) * 4);
+// the pair table, then the per-label planes (each the int32 plane of max_label + 1 words rounded to 64 bytes; nearest twice
+// that) and the border list, rounded to 64 bytes too.  The radius is the launcher's own check: the layout does not depend on it.
+struct NeighborsWorkspace {
+  PairPlanes p;
   NeighborPlanes q;
-  q.nearest = reinterpret_cast<unsigned long long*>(b);
-  b += 2 * labels;
-  q.parent = reinterpret_cast<int*>(b);
-  b += labels;
-  q.present = reinterpret_cast<int*>(b);
-  b += labels;
-  q.size = reinterpret_cast<int*>(b);
-  b += labels;
-  q.border = reinterpret_cast<int*>(b);
-  return q;
+};
+static Layout<NeighborsWorkspace> neighbors_layout(int h, int w, int max_label, int max_pairs, void* workspace) {
+  if (!(h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_label >= 0 && max_pairs >= 0)) return {false, 0, {}};
+  const long words = align_up(((long)max_label + 1) * 4, 64) / 4;
+  Carver c(workspace);
+  NeighborsWorkspace s;
+  s.p = pair_carve(c, neighbors_effective_pairs(max_label, max_pairs));
+  s.q.nearest = c.take<unsigned long long>(words);
+  s.q.parent = c.take<int>(words);
+  s.q.present = c.take<int>(words);
+  s.q.size = c.take<int>(words);
+  s.q.border = c.take<int>((long)h * w, 64);
+  return {true, c.bytes(), s};
 }
-
-static bool neighbors_geometry_ok(int h, int w, int max_label, int max_pairs) {
-  return h > 0 && w > 0 && h <= 16384 && w <= 16384 && max_label >= 0 && max_pairs >= 0;
-}
-
 long label_neighbors_workspace_bytes(int h, int w, int max_label, int max_pairs) {
-  if (!neighbors_geometry_ok(h, w, max_label, max_pairs)) return 0;
-  return pair_table_bytes(neighbors_effective_pairs(max_label, max_pairs)) + 5 * pair_align64(((long)max_label + 1) * 4) +
-         pair_align64((long)h * w * 4);
+  return neighbors_layout(h, w, max_label, max_pairs, nullptr).bytes;
 }
 
 __global__ void neighbors_init_kernel(NeighborPlanes q, int max_label, int* __restrict__ out_degree) {
@@ -211,26 +208,23 @@ int launch_label_neighbors(const int* label, int max_label, int h, int w, int ra
   UNETDC_REQUIRE(label && workspace && out_count && ((out_a && out_b && out_d2) || max_pairs <= 0) &&
                      ((out_nn_label && out_nn_d2 && out_degree && out_cluster && out_cluster_size) || max_label <= 0),
                  "label_neighbors: null pointer");
-  UNETDC_REQUIRE(neighbors_geometry_ok(h, w, max_label, max_pairs) && radius >= 1 && radius <= 64,
+  const auto lay = neighbors_layout(h, w, max_label, max_pairs, workspace);
+  UNETDC_REQUIRE(lay.ok && radius >= 1 && radius <= 64,
                  "label_neighbors: bad geometry (sides 1..16384, radius 1..64, non-negative label and pair limits)");
   UNETDC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "label_neighbors: workspace must be 8-byte aligned");
-  const long need = label_neighbors_workspace_bytes(h, w, max_label, max_pairs);
-  if (workspace_bytes < need) {
-    set_error("label_neighbors: workspace too small (%ld < %ld bytes)", workspace_bytes, need);
-    return UNETDC_EWORKSPACE;
-  }
-  const PairPlanes p = pair_planes(workspace, neighbors_effective_pairs(max_label, max_pairs));
-  const NeighborPlanes q = neighbor_planes(workspace, h, w, max_label, max_pairs);
-  const unsigned label_grid = pair_grid((long)max_label + 1, 256, 2048);
+  if (int rc = require_workspace("label_neighbors", workspace_bytes, lay.bytes)) return rc;
+  const PairPlanes& p = lay.planes.p;
+  const NeighborPlanes& q = lay.planes.q;
+  const int label_grid = grid_for((long)max_label + 1, 256, 2048);
   pair_table_init<PairMin>(p, stream);
   hipLaunchKernelGGL(neighbors_init_kernel, dim3(label_grid), dim3(256), 0, stream, q, max_label, out_degree);
   const long units = (long)((h + NEIGHBORS_TILE_ROWS - 1) / NEIGHBORS_TILE_ROWS) * ((w + 63) / 64);
-  hipLaunchKernelGGL(neighbors_border_kernel, dim3(pair_grid(units, 4, 8192)), dim3(256), 0, stream, label, max_label, h, w, q,
+  hipLaunchKernelGGL(neighbors_border_kernel, dim3(grid_for(units, 4, 8192)), dim3(256), 0, stream, label, max_label, h, w, q,
                      p.ctl);
-  hipLaunchKernelGGL(neighbors_scan_kernel, dim3(pair_grid((long)h * w, 4, 4096)), dim3(256), 0, stream, label, max_label, h, w,
+  hipLaunchKernelGGL(neighbors_scan_kernel, dim3(grid_for((long)h * w, 4, 4096)), dim3(256), 0, stream, label, max_label, h, w,
                      radius, q, p);
   pair_table_list(p, max_pairs, out_count, out_a, out_b, out_d2, stream);
-  hipLaunchKernelGGL(neighbors_pairs_kernel, dim3(pair_grid(p.max_pairs, 256, 2048)), dim3(256), 0, stream, p, q, out_degree);
+  hipLaunchKernelGGL(neighbors_pairs_kernel, dim3(grid_for(p.max_pairs, 256, 2048)), dim3(256), 0, stream, p, q, out_degree);
   hipLaunchKernelGGL(neighbors_flatten_kernel, dim3(label_grid), dim3(256), 0, stream, q, max_label, out_nn_label, out_nn_d2,
                      out_cluster);
   hipLaunchKernelGGL(neighbors_size_kernel, dim3(label_grid), dim3(256), 0, stream, q, max_label, out_cluster, out_cluster_size);

@@ -58,31 +58,19 @@ static long pair_pow2_at_least(long v) {
   return p;
 }
 
-static long pair_align64(long v) { return (v + 63) / 64 * 64; }
-
+// the table's five planes, each rounded to 64 bytes; the owner carves its own planes behind them.
 // max_pairs: already cut to what the caller's problem can hold
-static PairPlanes pair_planes(void* workspace, int max_pairs) {
+static PairPlanes pair_carve(Carver& c, int max_pairs) {
   PairPlanes p;
   p.max_pairs = max_pairs;
   p.slots = (int)pair_pow2_at_least(p.max_pairs > 32 ? 2L * p.max_pairs : 64L);
   p.n_sort = (int)pair_pow2_at_least(p.max_pairs > 1 ? p.max_pairs : 1);
-  unsigned char* b = reinterpret_cast<unsigned char*>(workspace);
-  p.ctl = reinterpret_cast<int*>(b);
-  b += pair_align64(PAIR_CTL_WORDS * 4);
-  p.keys = reinterpret_cast<pair_key_t*>(b);
-  b += pair_align64((long)p.slots * 8);
-  p.vals = reinterpret_cast<int*>(b);
-  b += pair_align64((long)p.slots * 4);
-  p.ek = reinterpret_cast<pair_key_t*>(b);
-  b += pair_align64((long)p.n_sort * 8);
-  p.ev = reinterpret_cast<int*>(b);
+  p.ctl = c.take<int>(PAIR_CTL_WORDS, 64);
+  p.keys = c.take<pair_key_t>(p.slots, 64);
+  p.vals = c.take<int>(p.slots, 64);
+  p.ek = c.take<pair_key_t>(p.n_sort, 64);
+  p.ev = c.take<int>(p.n_sort, 64);
   return p;
-}
-
-static long pair_table_bytes(int max_pairs) {
-  const PairPlanes p = pair_planes(nullptr, max_pairs);
-  return pair_align64(PAIR_CTL_WORDS * 4) + pair_align64((long)p.slots * 8) + pair_align64((long)p.slots * 4) +
-         pair_align64((long)p.n_sort * 8) + pair_align64((long)p.n_sort * 4);
 }
 
 static __global__ void pair_init_kernel(PairPlanes p, int neutral) {
@@ -215,31 +203,26 @@ static __global__ void pair_emit_kernel(PairPlanes p, int max_pairs, int* __rest
   }
 }
 
-static unsigned pair_grid(long items, int per_block, int limit) {
-  const long g = (items + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : g > limit ? limit : g);
-}
-
 template <typename Combine>
 static void pair_table_init(const PairPlanes& p, hipStream_t stream) {
-  hipLaunchKernelGGL(pair_init_kernel, dim3(pair_grid(p.slots, 256, 2048)), dim3(256), 0, stream, p, Combine::NEUTRAL);
+  hipLaunchKernelGGL(pair_init_kernel, dim3(grid_for(p.slots, 256, 2048)), dim3(256), 0, stream, p, Combine::NEUTRAL);
 }
 
 // the filled table -> the sorted list in ek / ev (the first min(entries, max_pairs) of it in the outputs) and *out_count
 static void pair_table_list(const PairPlanes& p, int max_pairs, int* out_count, int* out_a, int* out_b, int* out_v,
                             hipStream_t stream) {
-  hipLaunchKernelGGL(pair_compact_kernel, dim3(pair_grid(p.slots, 256, 2048)), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(pair_compact_kernel, dim3(grid_for(p.slots, 256, 2048)), dim3(256), 0, stream, p);
   const int n = p.n_sort, chunk = n < PAIR_SORT_CHUNK ? n : PAIR_SORT_CHUNK;
   if (n > 1) {
     hipLaunchKernelGGL(pair_sort_local_kernel, dim3(n / chunk), dim3(1024), 0, stream, p.ctl, p.ek, p.ev, n, 2, chunk);
     for (long k = 2L * chunk; k <= n; k <<= 1) {
       for (long j = k >> 1; j >= chunk; j >>= 1)
-        hipLaunchKernelGGL(pair_sort_global_kernel, dim3(pair_grid(n / 2, 256, 4096)), dim3(256), 0, stream, p.ctl, p.ek, p.ev, n, (int)j,
+        hipLaunchKernelGGL(pair_sort_global_kernel, dim3(grid_for(n / 2, 256, 4096)), dim3(256), 0, stream, p.ctl, p.ek, p.ev, n, (int)j,
                            (int)k);
       hipLaunchKernelGGL(pair_sort_local_kernel, dim3(n / chunk), dim3(1024), 0, stream, p.ctl, p.ek, p.ev, n, (int)k, (int)k);
     }
   }
-  hipLaunchKernelGGL(pair_emit_kernel, dim3(pair_grid(p.max_pairs, 256, 2048)), dim3(256), 0, stream, p, max_pairs, out_count,
+  hipLaunchKernelGGL(pair_emit_kernel, dim3(grid_for(p.max_pairs, 256, 2048)), dim3(256), 0, stream, p, max_pairs, out_count,
                      out_a, out_b, out_v);
 }
 

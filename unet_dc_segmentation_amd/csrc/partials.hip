@@ -128,10 +128,7 @@ int launch_channel_sum(const void* x, int ldx, float* out, void* workspace, long
   UNETDC_REQUIRE(x && out && workspace && P > 0, "channel_sum: null pointer / empty");
   UNETDC_REQUIRE(C % pl.epc == 0 && ldx % pl.epc == 0, "channel_sum: C/ld not chunk aligned");
   UNETDC_REQUIRE(pl.ok, "channel_sum: C=%d unsupported", C);
-  if (pl.workspace > workspace_bytes) {
-    set_error("channel_sum: workspace too small (%ld < %ld bytes)", workspace_bytes, pl.workspace);
-    return UNETDC_EWORKSPACE;
-  }
+  if (int rc = require_workspace("channel_sum", workspace_bytes, pl.workspace)) return rc;
   float* parts = reinterpret_cast<float*>(workspace);
   dispatch(dtype, [&](auto t) {
     using T = typename decltype(t)::type;

@@ -232,24 +232,32 @@ __global__ void resize_linear_chw_kernel(const unsigned char* __restrict__ src, 
   }
 }
 
-static int pp_grid(long n) {
-  long nb = (n + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  return (int)(nb < 1 ? 1 : nb);
+// two image planes (each padded to 16 bytes: the 16-byte accesses of subtract_minmax_kernel), then a 64-byte block for the
+// per-channel min / max words (int[4] each, 16-byte aligned): never inside a plane -- for images smaller than 32 bytes a
+// scratch at the head of `eroded` would reach into `bg`, which subtract_minmax_kernel reads while the atomics write
+struct RollingBallPlanes {
+  unsigned char *eroded, *bg;
+  int *mn, *mx;
+};
+static Layout<RollingBallPlanes> rolling_ball_layout(int h, int w, int cn, void* workspace) {
+  if (!(h > 0 && w > 0 && cn >= 1 && cn <= 4)) return {false, 0, {}};
+  Carver c(workspace);
+  RollingBallPlanes p;
+  p.eroded = c.take<unsigned char>((long)h * w * cn, 16);
+  p.bg = c.take<unsigned char>((long)h * w * cn, 16);
+  p.mn = c.take<int>(4);
+  p.mx = c.take<int>(4);
+  c.slack(32);
+  return {true, c.bytes(), p};
 }
-
-// two image planes (each padded to 16 bytes: the 16-byte accesses of subtract_minmax_kernel) + 64 bytes for the min / max words
-static long pp_plane_bytes(int h, int w, int cn) { return ((long)h * w * cn + 15) & ~15L; }
-long rolling_ball_workspace_bytes(int h, int w, int cn) { return 2L * pp_plane_bytes(h, w, cn) + 64; }
+long rolling_ball_workspace_bytes(int h, int w, int cn) { return rolling_ball_layout(h, w, cn, nullptr).bytes; }
 
 int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int w, int cn, int k, void* workspace,
                         long workspace_bytes, hipStream_t stream) {
-  UNETDC_REQUIRE(src && dst && workspace && h > 0 && w > 0 && cn >= 1 && cn <= 4, "rolling_ball: bad arguments");
+  const auto lay = rolling_ball_layout(h, w, cn, workspace);
+  UNETDC_REQUIRE(src && dst && workspace && lay.ok, "rolling_ball: bad arguments");
   UNETDC_REQUIRE(k >= 1 && k <= PP_MAXK, "rolling_ball: element size must be in [1, %d]", PP_MAXK);
-  if (workspace_bytes < rolling_ball_workspace_bytes(h, w, cn)) {
-    set_error("rolling_ball: workspace too small (%ld bytes)", workspace_bytes);
-    return UNETDC_EWORKSPACE;
-  }
+  if (int rc = require_workspace("rolling_ball", workspace_bytes, lay.bytes)) return rc;
   // subtract_minmax_kernel's 16-byte accesses to src, dst and the background plane (workspace + a multiple of 16); checked
   // before the first launch, so a refused call has written nothing
   UNETDC_REQUIRE(((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && ((uintptr_t)workspace % 16 == 0),
@@ -271,28 +279,21 @@ int launch_rolling_ball(const unsigned char* src, unsigned char* dst, int h, int
       sp.j2[i] = (short)j2;
     }
   }
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  unsigned char* eroded = ws;
-  unsigned char* bg = ws + pp_plane_bytes(h, w, cn);
+  const auto [eroded, bg, mn, mx] = lay.planes;
   const dim3 grid((w + PP_TILE - 1) / PP_TILE, (h + PP_TILE - 1) / PP_TILE, cn);
   const int lds = (PP_TILE + k) * (PP_TILE + k);              // <= 192 x 192 = 36 KB
   hipLaunchKernelGGL(morph_kernel<false>, grid, dim3(PP_THREADS), lds, stream, src, eroded, h, w, cn, k, sp);
   hipLaunchKernelGGL(morph_kernel<true>, grid, dim3(PP_THREADS), lds, stream, eroded, bg, h, w, cn, k, sp);
-  // per-channel min / max (int[4] each) live in the 64 spare bytes behind the two planes (16-byte aligned): never inside a
-  // plane -- for images smaller than 32 bytes a scratch at the head of `eroded` would reach into `bg`, which
-  // subtract_minmax_kernel reads while the atomics write
-  int* mn = reinterpret_cast<int*>(ws + 2L * pp_plane_bytes(h, w, cn));
-  int* mx = mn + 4;
   hipLaunchKernelGGL(minmax_init_kernel, dim3(1), dim3(64), 0, stream, mn, mx);
   const long npix = (long)h * w;
   {
-    const dim3 g(pp_grid(npix / 16 + 1) > 256 ? 256 : pp_grid(npix / 16 + 1));
+    const dim3 g(grid_for(npix / 16 + 1, 256, 256));
     if (cn == 1) hipLaunchKernelGGL(subtract_minmax_kernel<1>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
     else if (cn == 2) hipLaunchKernelGGL(subtract_minmax_kernel<2>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
     else if (cn == 3) hipLaunchKernelGGL(subtract_minmax_kernel<3>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
     else hipLaunchKernelGGL(subtract_minmax_kernel<4>, g, dim3(256), 0, stream, src, bg, dst, npix, mn, mx);
   }
-  hipLaunchKernelGGL(normalize_kernel, dim3(pp_grid(npix)), dim3(256), 0, stream, dst, npix, cn, mn, mx);
+  hipLaunchKernelGGL(normalize_kernel, dim3(grid_for(npix, 256, 2048)), dim3(256), 0, stream, dst, npix, cn, mn, mx);
   return check_launch("rolling ball kernels");
 }
 
@@ -314,8 +315,8 @@ int launch_resize_linear_chw(const unsigned char* src, int h, int w, int cn, flo
                              const short* xa, const int* yofs, const short* ya, hipStream_t stream) {
   UNETDC_REQUIRE(src && dst && xofs && xa && yofs && ya && h > 0 && w > 0 && dh > 0 && dw > 0 && cn >= 1 && cn <= 4,
                  "resize_linear_chw: bad arguments");
-  hipLaunchKernelGGL(resize_linear_chw_kernel, dim3(pp_grid((long)dh * dw)), dim3(256), 0, stream, src, h, w, cn, dst, dh, dw,
-                     xofs, xa, yofs, ya);
+  hipLaunchKernelGGL(resize_linear_chw_kernel, dim3(grid_for((long)dh * dw, 256, 2048)), dim3(256), 0, stream, src, h, w, cn, dst, dh,
+                     dw, xofs, xa, yofs, ya);
   return check_launch("resize_linear_chw_kernel");
 }
 

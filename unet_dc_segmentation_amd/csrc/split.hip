@@ -129,17 +129,13 @@ __global__ void split_merge_kernel(const unsigned char* __restrict__ mask, const
   }
 }
 
-static int split_grid(long n) {
-  long nb = (n + 255) / 256;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  return (int)nb;
+static bool split_sides_ok(int h, int w) { return h > 0 && w > 0 && h <= SPLIT_MAX_SIDE && w <= SPLIT_MAX_SIDE; }
+
+// split_stats: the ccl workspace with two more planes, D2 and B (B holds g during the distance transform)
+static Layout<CclWorkspace> split_layout(int h, int w, void* workspace) {
+  return split_sides_ok(h, w) ? ccl_layout(h, w, 2, workspace) : Layout<CclWorkspace>{};
 }
-
-long edt_workspace_bytes(int h, int w) { return (long)h * w * 4 + 64; }
-
-// ccl planes, then D2 and B (B holds g during the distance transform)
-long split_workspace_bytes(int h, int w) { return ((ccl_workspace_bytes(h, w) + 63) / 64) * 64 + (long)h * w * 8 + 64; }
+long split_workspace_bytes(int h, int w) { return split_layout(h, w, nullptr).bytes; }
 
 static void enqueue_edt(const unsigned char* mask, int h, int w, int* d2, int* g, hipStream_t stream) {
   hipLaunchKernelGGL(edt_col_kernel, dim3((w + 63) / 64), dim3(64), 0, stream, mask, g, h, w);
@@ -149,12 +145,12 @@ static void enqueue_edt(const unsigned char* mask, int h, int w, int* d2, int* g
 int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,
                   hipStream_t stream) {
   UNETDC_REQUIRE(mask && out_d2 && workspace, "edt_sq: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && h <= SPLIT_MAX_SIDE && w <= SPLIT_MAX_SIDE, "edt_sq: bad geometry (sides 1..16384)");
-  if (workspace_bytes < edt_workspace_bytes(h, w)) {
-    set_error("edt_sq: workspace too small (%ld < %ld bytes)", workspace_bytes, edt_workspace_bytes(h, w));
-    return UNETDC_EWORKSPACE;
-  }
-  enqueue_edt(mask, h, w, out_d2, reinterpret_cast<int*>(workspace), stream);
+  UNETDC_REQUIRE(split_sides_ok(h, w), "edt_sq: bad geometry (sides 1..16384)");
+  Carver c(workspace);                                      // one plane for g, 64 spare bytes (no query of its own)
+  int* g = c.take<int>((long)h * w);
+  c.slack(64);
+  if (int rc = require_workspace("edt_sq", workspace_bytes, c.bytes())) return rc;
+  enqueue_edt(mask, h, w, out_d2, g, stream);
   return check_launch("edt kernels");
 }
 
@@ -162,17 +158,13 @@ int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, in
                        long workspace_bytes, int* out_count, int* out_area, long long* out_sumy, long long* out_sumx,
                        int* out_root, int* out_label, int max_out, hipStream_t stream) {
   UNETDC_REQUIRE(mask && workspace && out_count && out_area && out_sumy && out_sumx, "split_stats: null pointer");
-  UNETDC_REQUIRE(h > 0 && w > 0 && h <= SPLIT_MAX_SIDE && w <= SPLIT_MAX_SIDE && (long)h * w < (1L << 30) && max_out >= 0,
-                 "split_stats: bad geometry (sides 1..16384)");
+  const auto lay = split_layout(h, w, workspace);
+  UNETDC_REQUIRE(lay.ok && max_out >= 0, "split_stats: bad geometry (sides 1..16384)");
   UNETDC_REQUIRE(split_depth_half_px >= 0, "split_stats: negative split depth");
-  if (workspace_bytes < split_workspace_bytes(h, w)) {
-    set_error("split_stats: workspace too small (%ld < %ld bytes)", workspace_bytes, split_workspace_bytes(h, w));
-    return UNETDC_EWORKSPACE;
-  }
-  const int n = h * w, g = split_grid(n);
-  const CclPlanes p = ccl_planes(workspace, n);
-  int* d2 = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(workspace) + ((ccl_workspace_bytes(h, w) + 63) / 64) * 64);
-  int* B = d2 + n;
+  if (int rc = require_workspace("split_stats", workspace_bytes, lay.bytes)) return rc;
+  const int n = h * w, g = grid_for(n, 256, 4096);
+  const CclPlanes& p = lay.planes.ccl;
+  int *d2 = lay.planes.more, *B = d2 + n;
   // a depth at which every pair passes (H2 / 2 >= the largest possible sqrt(peak)) needs no more than that depth
   long long h2 = split_depth_half_px;
   if (h2 > 2ll * (h + w)) h2 = 2ll * (h + w);
