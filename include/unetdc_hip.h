@@ -593,6 +593,32 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                            int32_t* out_cluster_size, unetdc_stream_t s);
 
 
+/* ---- surface distances between two label maps (boundary.hip; the definition is DESIGN.md section 21) -----------------------
+ * unetdc_boundary_distances: label_a (the prediction), label_b (the annotation): [h][w] int32 label maps, objects 1..max_a and
+ *   1..max_b; a value below 1 or above the maximum reads as 0.  A binary mask is the label map with max = 1.
+ *   A pixel is a BOUNDARY pixel of its map when it carries a label (after that rule) and one of its 4-neighbours lies outside the
+ *   image or carries another value (after that rule): the cut between two touching objects is boundary, and so is the frame.
+ *   For every boundary pixel p of one map, d2(p) = the smallest squared Euclidean distance to a boundary pixel of the other map
+ *   (of ANY object of it, not of a matched partner): an exact integer below 2^29, UNETDC_EDT_INF when the other map has none.
+ *     hist (DEVICE, [2][radius^2 + 2] int64, 8-byte aligned): hist[0][min(d2(p), radius^2 + 1)] += 1 for every boundary pixel
+ *       of label_a, hist[1][.] likewise for label_b; bin radius^2 + 1 is "far".  The call ADDS; the caller zeroes hist once and
+ *       may pool any number of images in it.
+ *     dmax (DEVICE, [2] int32): dmax[dir] = max(dmax[dir], the largest d2 of that direction), unclamped; the caller
+ *       initialises it to -1.
+ *     out_a (nullable, [3][max_a] int64, 8-byte aligned): for object k at index k - 1, row 0 = its boundary pixels, row 1 = the
+ *       largest d2 among them (-1 without one), row 2 = the sum of their d2 (unclamped).  Every entry is initialised by the
+ *       call.  out_b ([3][max_b]): the same for label_b.  NULL: no table for that side.
+ *   Sides 1..16384, radius 1..64, max_a, max_b >= 0; anything else, a null label map / workspace / hist / dmax or a misaligned
+ *   pointer returns UNETDC_EINVAL before the first launch, a workspace below unetdc_boundary_distances_workspace(h, w) bytes
+ *   (10 per pixel + 64; 0 for a geometry the call refuses; 4-byte aligned) UNETDC_EWORKSPACE.  Nothing but hist, dmax, the two
+ *   tables and the workspace is written, and the workspace may hold anything on entry.  Launches on the given stream only; no
+ *   host wait, no allocation.  Integer atomics only: the result depends on no order, two runs are bitwise equal. */
+int64_t unetdc_boundary_distances_workspace(int h, int w);
+int unetdc_boundary_distances(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, int radius,
+                              void* workspace, int64_t workspace_bytes, int64_t* hist, int32_t* dmax, int64_t* out_a,
+                              int64_t* out_b, unetdc_stream_t s);
+
+
 /* ---- cleaning a mask before the droplet stages (clean.hip; the definition is DESIGN.md section 13) --------------------------
  * unetdc_mask_clean: strong and weak ([h][w] uint8, nonzero = 1; weak may be NULL) -> out_mask ([h][w] uint8 in {0,1}):
  *     hysteresis  (weak given) M = the union of the 4-connected components of weak that contain a pixel where strong and weak

@@ -19,6 +19,7 @@ and a few integers per droplet come back:
     --gt_dir, sweep   unet_dc_segmentation_amd/evaluate.py      csrc/match.hip sweep.hip  CPU: utils/droplet_match.py, threshold_sweep.py
     --density_maps    unet_dc_segmentation_amd/density.py       csrc/density.hip        CPU: utils/density.py
     --neighbors       (droplets.py)                             csrc/neighbors.hip      CPU: utils/droplet_neighbors.py
+    --boundary        unet_dc_segmentation_amd/evaluate.py      csrc/boundary.hip       CPU: utils/droplet_boundary.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -99,6 +100,7 @@ class Run:
     gt_images: list = dataclasses.field(default_factory=list)      # match_per_image.csv: (filename, integers)
     neighbors: int | None = None       # --neighbors: the contact radius in pixels
     contact_tables: list = dataclasses.field(default_factory=list)  # droplet_contacts.csv, one table per image
+    boundary: dict | None = None       # boundary_options(); its "records" collect boundary_per_image.csv
 
     def droplet_options(self, labels, shape):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
@@ -249,23 +251,36 @@ def decode_gt(path, as_labels):
     return np.array(im if im.mode in ("1", "L", "P", "I", "I;16", "I;16B") else im.convert("I")).astype(np.int32)
 
 
-def match_cpu(labels, area, gt_item, gt_min_area, gt_are_labels):
-    """CPU path of --gt_dir for one image: what unet_dc_segmentation_amd.evaluate.match_batch returns per image."""
+def match_cpu(labels, area, gt_item, gt_min_area, gt_are_labels, boundary=None):
+    """CPU path of --gt_dir for one image: what unet_dc_segmentation_amd.evaluate.match_batch returns per image; with
+    boundary (a radius) also the record of utils.droplet_boundary.boundary_record_numpy under "boundary"."""
     from utils import droplet_match as dm
     glab = gt_item if gt_are_labels else dm.gt_labels_numpy(gt_item, gt_min_area)
     garea, gsy, gsx = dm.label_sums(glab)
     a, b, n = dm.overlap_table_numpy(labels, glab, len(area), len(garea))
-    return {"a": a, "b": b, "n": n, "gt_area": garea, "gt_sumy": gsy, "gt_sumx": gsx,
-            "columns": dm.match_columns(area, garea, a, b, n)}
+    res = {"a": a, "b": b, "n": n, "gt_area": garea, "gt_sumy": gsy, "gt_sumx": gsx,
+           "columns": dm.match_columns(area, garea, a, b, n)}
+    if boundary is not None:
+        from utils.droplet_boundary import boundary_record_numpy
+        res["boundary"] = boundary_record_numpy(labels, len(area), glab, len(garea), boundary)
+    return res
 
 
 def add_match_outputs(run, df, res, filename):
-    """--gt_dir: the three columns behind the droplet table's own, this image's rows of gt_droplets.csv and its integers."""
+    """--gt_dir: the three columns behind the droplet table's own, this image's rows of gt_droplets.csv and its integers; with
+    --boundary the per-object boundary columns and this image's record as well."""
     from utils.droplet_match import gt_table
+    pred_cols, gt_cols = dict(res["columns"]["pred"]), dict(res["columns"]["gt"])
+    if run.boundary is not None:                         # --boundary: bd_px, bd_rms, bd_max behind them, on both tables
+        from utils.droplet_boundary import object_columns
+        rec = res["boundary"]
+        pred_cols.update(object_columns(rec["a"]))
+        gt_cols.update(object_columns(rec["b"]))
+        run.boundary["records"].append((filename, rec["hist"], rec["dmax"]))
     if not df.empty:
-        for name, col in res["columns"]["pred"].items():
+        for name, col in pred_cols.items():
             df[name] = col
-    run.gt_tables.append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], res["columns"]["gt"])))
+    run.gt_tables.append(pd.DataFrame(gt_table(filename, res["gt_area"], res["gt_sumy"], res["gt_sumx"], gt_cols)))
     run.gt_images.append((filename, res["columns"]["image"]))
     return df
 
@@ -348,8 +363,10 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
     -> (one Droplets per image, one match result per image or None, the density stage's device sums or None).  On the
     device the whole batch is enqueued back to back with ONE host wait (droplets.py), and one more for the matching; on the
     CPU the same records come from droplets_cpu and match_cpu.  sweeping: a threshold of --sweep_objects, where only the
-    matching is read: no shape columns, no grey planes."""
+    matching is read: no shape columns, no grey planes, no boundary distances.  With --boundary every match result carries the
+    record of DESIGN.md section 21 under "boundary" (device: one more batch of launches and one more wait, evaluate.boundary_batch)."""
     gt, hws = run.gt, [m[1] for m in batch.meta]
+    radius = run.boundary["R"] if run.boundary is not None and not sweeping else None
     want_labels = gt is not None or run.split_depth is not None
     shape = run.shape and not sweeping
     if probs.is_cuda:
@@ -359,8 +376,16 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
                                             options=run.droplet_options(want_labels, shape))
         if gt is None:
             return out, None, sums
-        from unet_dc_segmentation_amd.evaluate import match_batch
-        return out, match_batch([d.labels for d in out], [d.area for d in out], batch.gt_items, gt["min_area"], gt["labels"]), sums
+        from unet_dc_segmentation_amd.evaluate import boundary_batch, match_batch
+        labs, areas = [d.labels for d in out], [d.area for d in out]
+        if radius is None:
+            return out, match_batch(labs, areas, batch.gt_items, gt["min_area"], gt["labels"]), sums
+        mres = match_batch(labs, areas, batch.gt_items, gt["min_area"], gt["labels"], keep_labels=True)
+        recs = boundary_batch(labs, [len(a) for a in areas], [r.pop("gt_labels") for r in mres], [len(r["gt_area"]) for r in mres],
+                              radius)
+        for r, rec in zip(mres, recs):
+            r["boundary"] = rec
+        return out, mres, sums
     out, p = [], probs[:, 0].numpy()
     for i, hw in enumerate(hws):
         mask, counts = _cpu_mask(p[i], thresh, hw, run.clean)
@@ -369,7 +394,7 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
         out.append(d)
     if gt is None:
         return out, None, None
-    return out, [match_cpu(d.labels, d.area, item, gt["min_area"], gt["labels"]) for d, item in zip(out, batch.gt_items)], None
+    return out, [match_cpu(d.labels, d.area, item, gt["min_area"], gt["labels"], radius) for d, item in zip(out, batch.gt_items)], None
 
 
 def sweep_step(run, batch, probs):
@@ -528,6 +553,16 @@ def build_parser():
                         "--px_per_micron) to the droplet tables, contact and cluster counts to summary_per_image.csv, and writes "
                         "droplet_contacts.csv (filename, label_a, label_b, d2, dist_px).  With --split_touching the cut droplets "
                         "touch (d2 = 1); components below --min_area are background")
+    p.add_argument("--boundary", type=int, nargs="?", const=64, metavar="R",
+                   help="with --gt_dir: boundary accuracy against the annotation -- for every boundary pixel of the predicted "
+                        "label map (the cuts of --split_touching and the image frame included) the distance to the nearest "
+                        "boundary pixel of the annotated one, and back; distances beyond R pixels (1..64, 64 without R) count as "
+                        "far.  Adds bd_px, bd_rms, bd_max to the droplet tables and to gt_droplets.csv (distances to the nearest "
+                        "boundary of ANY object of the other map, not of the matched partner) and writes boundary_per_image.csv: "
+                        "Hausdorff distance, HD95, average symmetric surface distance, and per tolerance boundary precision, "
+                        "recall, F and surface Dice (nsd), one row per image and the pooled row ALL")
+    p.add_argument("--boundary_tol", metavar="T[,T...]",
+                   help="with --boundary: the integer pixel tolerances of the surface Dice columns (0..R, default 1,2,3)")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -570,6 +605,25 @@ def sweep_options(args):
                 raise SystemExit(f"--sweep_objects: {t} lies below --prob_thresh_low ({low})")
         objects = list(dict.fromkeys(objects))
     return {"K": args.thresh_sweep, "hist": None, "objects": objects, "object_images": {t: [] for t in objects}}
+
+
+def boundary_options(args):
+    """--boundary / --boundary_tol -> {"R", "tols", "records"}, None without the flag; a bad value or a missing --gt_dir ends
+    the run before any image."""
+    if args.boundary is None:
+        if args.boundary_tol is not None:
+            raise SystemExit("--boundary_tol needs --boundary")
+        return None
+    if not args.gt_dir:
+        raise SystemExit("--boundary measures against annotated masks: it needs --gt_dir")
+    from utils.droplet_boundary import DEFAULT_TOLS, check_radius, check_tols
+    try:
+        R = check_radius(args.boundary)
+        tols = DEFAULT_TOLS if args.boundary_tol is None else [int(v) for v in args.boundary_tol.split(",") if v.strip()]
+        tols = check_tols([t for t in tols if args.boundary_tol is not None or t <= R], R)
+    except ValueError as e:
+        raise SystemExit(f"--boundary R / --boundary_tol: {e}")
+    return {"R": R, "tols": tols, "records": []}
 
 
 def tile_options(args):
@@ -615,6 +669,7 @@ def main(argv=None):
     sweep = sweep_options(args)
     tile = tile_options(args)
     tta = tta_options(args)
+    boundary = boundary_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -644,7 +699,7 @@ def main(argv=None):
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
-                  neighbors=args.neighbors)
+                  neighbors=args.neighbors, boundary=boundary)
         ahead = deque()
         it = iter(images)
 
@@ -692,6 +747,12 @@ def main(argv=None):
         pd.concat(tables, ignore_index=True).to_csv(out_dir / "gt_droplets.csv", index=False) if tables else None
         rows = [summary_row(name, ints) for name, ints in run.gt_images] + [pooled_row([ints for _, ints in run.gt_images])]
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
+    if boundary is not None:
+        from utils import droplet_boundary as db
+        recs = boundary["records"]
+        rows = [db.summary_row(name, h, d, boundary["R"], boundary["tols"]) for name, h, d in recs]
+        rows.append(db.pooled_row([(h, d) for _, h, d in recs], boundary["R"], boundary["tols"]))
+        pd.DataFrame(rows, columns=db.column_names(boundary["tols"])).to_csv(out_dir / "boundary_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     if run.neighbors is not None and run.contact_tables:

@@ -75,6 +75,10 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
                    help="with --border_weight: the width S of the separation term in pixels (default 5)")
     p.add_argument("--border_radius", type=int, default=None, metavar="R",
                    help="with --border_weight: droplets further than R pixels away do not count (1..64, default ceil(4 S))")
+    p.add_argument("--boundary", type=int, nargs="?", const=64, default=None, metavar="R",
+                   help="the final test evaluation also reports boundary accuracy: pooled HD95, average symmetric surface "
+                        "distance, surface Dice (nsd) and boundary F at 1, 2, 3 pixels of the thresholded predictions against "
+                        "the masks (both binary; distances beyond R pixels, 1..64, 64 without R, count as far)")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -215,14 +219,51 @@ def predict_eval(model, images, tta, batch):
     return predict_tta_cpu(model, images, tta, batch)
 
 
-def evaluate_test(model, loader, criterion, device, tta=1, items=8):
+def pool_boundary(yp, yt, radius, state=None):
+    """--boundary: adds the surface distances between the binary predictions yp and masks yt (bool
+    [N, 1, H, W], a label map with K = 1 on either side) into state = (hist, dmax), which it returns (a new one from None).  On
+    the HIP device the pair are device tensors and every image adds into them (unetdc_boundary_distances, nothing waits); on the
+    CPU they are numpy arrays and utils.droplet_boundary does the same sums."""
+    n = len(yp)
+    if yp.is_cuda:
+        from unet_dc_segmentation_amd.evaluate import boundary_batch
+        if state is None:
+            state = (torch.zeros(2, radius * radius + 2, dtype=torch.int64, device=yp.device),
+                     torch.full((2,), -1, dtype=torch.int32, device=yp.device))
+        a, b = yp[:, 0].to(torch.int32).contiguous(), yt[:, 0].to(torch.int32).contiguous()
+        boundary_batch(list(a), [1] * n, list(b), [1] * n, radius, hist=state[0], dmax=state[1], objects=False)
+        return state
+    import numpy as np
+    from utils.droplet_boundary import boundary_record_numpy
+    if state is None:
+        state = (np.zeros((2, radius * radius + 2), np.int64), np.full(2, -1, np.int64))
+    for a, b in zip(yp[:, 0].numpy(), yt[:, 0].numpy()):
+        rec = boundary_record_numpy(a.astype(np.int32), 1, b.astype(np.int32), 1, radius, objects=False)
+        state = (state[0] + rec["hist"], np.maximum(state[1], rec["dmax"]))
+    return state
+
+
+def boundary_report(state, radius):
+    """The pooled planes of pool_boundary -> {"R", "hist", "dmax", and the columns of utils.droplet_boundary.boundary_columns}."""
+    from utils.droplet_boundary import DEFAULT_TOLS, boundary_columns
+    hist, dmax = state
+    if torch.is_tensor(hist):
+        from unet_dc_segmentation_amd.evaluate import boundary_result
+        hist, dmax = boundary_result(hist, dmax)
+    tols = tuple(t for t in DEFAULT_TOLS if t <= radius)
+    return {"R": radius, "hist": hist, "dmax": dmax, **boundary_columns(hist, dmax, radius, tols)}
+
+
+def evaluate_test(model, loader, criterion, device, tta=1, items=8, boundary=None):
     """The reference's final test pass (train_DC_focal.py:365-402, :452-467) without its image dumps: mean loss and Dice over
     the batches, pixel accuracy over all pixels, and calculate_metrics() on the thresholded predictions.  Sums stay on the
-    device (one read-back), like the training loop's.  tta, items: the number of variants of --tta and of items per forward."""
+    device (one read-back), like the training loop's.  tta, items: the number of variants of --tta and of items per forward.
+    boundary (a radius): also "boundary", the pooled boundary_report of the thresholded predictions against the masks."""
     model.eval()
     loss_t = torch.zeros((), dtype=torch.float64, device=device)
     dice_t = torch.zeros((), dtype=torch.float64, device=device)
     cm_t = torch.zeros(4, dtype=torch.int64, device=device)           # tn, fp, fn, tp
+    bstate = None
     with torch.no_grad():
         for batch in loader:
             images, masks = batch[0].float().to(device), batch[1].float().to(device)
@@ -232,12 +273,17 @@ def evaluate_test(model, loader, criterion, device, tta=1, items=8):
             dice_t += dice_coef(masks, pred).double()
             yt, yp = masks > 0.5, pred > 0.5
             cm_t += torch.stack([(~yp & ~yt).sum(), (yp & ~yt).sum(), (~yp & yt).sum(), (yp & yt).sum()])
+            if boundary is not None:
+                bstate = pool_boundary(yp, yt, boundary, bstate)
     nb = max(1, len(loader))
     tn, fp, fn, tp = (int(v) for v in cm_t.tolist())
     precision, recall, f1, specificity, cm = metrics_from_counts(tn, fp, fn, tp)     # = calculate_metrics() on the label arrays
     total = max(1, tn + fp + fn + tp)
-    return dict(test_loss=float(loss_t.item()) / nb, test_dice=float(dice_t.item()) / nb, test_acc=(tn + tp) / total,
-                precision=precision, recall=recall, f1=f1, specificity=specificity, confusion=cm.tolist())
+    out = dict(test_loss=float(loss_t.item()) / nb, test_dice=float(dice_t.item()) / nb, test_acc=(tn + tp) / total,
+               precision=precision, recall=recall, f1=f1, specificity=specificity, confusion=cm.tolist())
+    if bstate is not None:
+        out["boundary"] = boundary_report(bstate, boundary)
+    return out
 
 
 def calibrate_threshold(model, loader, K, device, tta=1, items=8):
@@ -279,6 +325,8 @@ def main(argv=None, parser=None):
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
+    if args.boundary is not None and not 1 <= args.boundary <= 64:
+        raise SystemExit("--boundary R: R must be in 1..64")
     from utils.tta import TTA_SIZES
     if args.tta not in TTA_SIZES:
         raise SystemExit(f"--tta N: N must be one of {', '.join(map(str, TTA_SIZES))}, not {args.tta}")
@@ -459,7 +507,7 @@ def main(argv=None, parser=None):
             test_loader = DataLoader(test_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers,
                                      pin_memory=pin)
         # every rank: same weights, same split
-        history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch)
+        history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch, args.boundary)
         if rank == 0:
             t = history.test
             print("========== Test Results ==========" + (f" (--tta {args.tta})" if args.tta != 1 else ""))
@@ -469,6 +517,10 @@ def main(argv=None, parser=None):
             print(f"Precision: {t['precision']:.4f}, Recall: {t['recall']:.4f}, F1: {t['f1']:.4f}, "
                   f"Specificity: {t['specificity']:.4f}")
             print(f"Confusion matrix [[tn, fp], [fn, tp]]: {t['confusion']}")
+            if "boundary" in t:
+                b = t["boundary"]
+                per_tol = ", ".join(f"nsd_{q} {b[f'nsd_{q}']:.4f}, bf_{q} {b[f'bf_{q}']:.4f}" for q in (1, 2, 3) if f"nsd_{q}" in b)
+                print(f"Boundary (--boundary {b['R']}, pooled): HD95 {b['hd95']:.3f} px, ASSD {b['assd']:.3f} px, {per_tol}")
     if args.calibrate_thresh is not None and len(val_ds) > 0:
         history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device, args.tta,
                                                     args.batch)             # every rank: same weights

@@ -102,6 +102,8 @@ SIGNATURES = {
     "unetdc_label_props": (I, [P, P, I, I, P, I, P]),
     "unetdc_label_overlap_workspace": (L, [I, I, I]),
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
+    "unetdc_boundary_distances_workspace": (L, [I, I]),
+    "unetdc_boundary_distances": (I, [P, I, P, I, I, I, I, P, L, P, P, P, P, P]),
     "unetdc_label_neighbors_workspace": (L, [I, I, I, I]),
     "unetdc_label_neighbors": (I, [P, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P]),
     "unetdc_mask_clean_workspace": (L, [I, I]),

@@ -622,6 +622,16 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                                 max_pairs, out_nn_label, out_nn_d2, out_degree, out_cluster, out_cluster_size, (hipStream_t)s);
 }
 
+int64_t unetdc_boundary_distances_workspace(int h, int w) { return boundary_distances_workspace_bytes(h, w); }
+
+int unetdc_boundary_distances(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, int radius,
+                              void* workspace, int64_t workspace_bytes, int64_t* hist, int32_t* dmax, int64_t* out_a,
+                              int64_t* out_b, unetdc_stream_t s) {
+  return launch_boundary_distances(label_a, max_a, label_b, max_b, h, w, radius, workspace, (long)workspace_bytes,
+                                   reinterpret_cast<long long*>(hist), dmax, reinterpret_cast<long long*>(out_a),
+                                   reinterpret_cast<long long*>(out_b), (hipStream_t)s);
+}
+
 int64_t unetdc_mask_clean_workspace(int h, int w) { return mask_clean_workspace_bytes(h, w); }
 
 int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, int max_hole_area, void* workspace,

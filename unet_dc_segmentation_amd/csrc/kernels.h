@@ -300,9 +300,18 @@ int launch_label_neighbors(const int* label, int max_label, int h, int w, int ra
                            int* out_count, int* out_a, int* out_b, int* out_d2, int max_pairs, int* out_nn_label,
                            int* out_nn_d2, int* out_degree, int* out_cluster, int* out_cluster_size, hipStream_t stream);
 
+// boundary.hip: surface distances between the boundary pixels of two int32 label maps
+long boundary_distances_workspace_bytes(int h, int w);      // 0 for a geometry the call refuses
+int launch_boundary_distances(const int* label_a, int max_a, const int* label_b, int max_b, int h, int w, int radius,
+                              void* workspace, long workspace_bytes, long long* hist, int* dmax, long long* out_a,
+                              long long* out_b, hipStream_t stream);
+
 // split.hip: exact squared Euclidean distance transform and the split of touching droplets (include/unetdc_hip.h)
 int launch_edt_sq(const unsigned char* mask, int h, int w, int* out_d2, void* workspace, long workspace_bytes,
                   hipStream_t stream);
+// the column pass alone, for boundary.hip: g[y][x] = the distance to the nearest zero pixel of column x, 0x7fffffff without one.
+// No checks, no check_launch: the caller does both.
+void launch_edt_col(const unsigned char* mask, int* g, int h, int w, hipStream_t stream);
 long split_workspace_bytes(int h, int w);
 int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, int split_depth_half_px, void* workspace,
                        long workspace_bytes, int* out_count, int* out_area, long long* out_sumy, long long* out_sumx,

@@ -137,8 +137,12 @@ static Layout<CclWorkspace> split_layout(int h, int w, void* workspace) {
 }
 long split_workspace_bytes(int h, int w) { return split_layout(h, w, nullptr).bytes; }
 
-static void enqueue_edt(const unsigned char* mask, int h, int w, int* d2, int* g, hipStream_t stream) {
+void launch_edt_col(const unsigned char* mask, int* g, int h, int w, hipStream_t stream) {
   hipLaunchKernelGGL(edt_col_kernel, dim3((w + 63) / 64), dim3(64), 0, stream, mask, g, h, w);
+}
+
+static void enqueue_edt(const unsigned char* mask, int h, int w, int* d2, int* g, hipStream_t stream) {
+  launch_edt_col(mask, g, h, w, stream);
   hipLaunchKernelGGL(edt_row_kernel, dim3(h), dim3(256), (size_t)w * 4, stream, g, d2, w);
 }
 

@@ -7,6 +7,10 @@ Only the triples (a, b, n) and three integers per annotated droplet cross PCIe; 
 ``sweep_batch`` / ``sweep_result`` (csrc/sweep.hip): the pixel confusion matrix of the thresholded mask
 against the annotation at every threshold of a grid, added up in one device histogram for as many images as the caller
 likes; ``utils.threshold_sweep.sweep_table`` turns its single copy into the scores.
+
+``boundary_batch`` / ``boundary_result`` (csrc/boundary.hip): the surface distances between the boundary
+pixels of predicted and annotated label maps, a batch enqueued back to back; ``utils.droplet_boundary.boundary_columns`` turns
+the integers into HD, HD95, ASSD and surface Dice.
 """
 from __future__ import annotations
 
@@ -53,7 +57,7 @@ def label_overlap(label_a, ka, label_b, kb, capacity=None):
         cap = min(4 * max(cap, 1), h * w)
 
 
-def match_batch(pred_labels, pred_areas, gts, gt_min_area=1, gt_are_labels=False, max_gt=1 << 14):
+def match_batch(pred_labels, pred_areas, gts, gt_min_area=1, gt_are_labels=False, max_gt=1 << 14, keep_labels=False):
     """pred_labels: B int32 [h, w] DEVICE label maps; pred_areas: B int64 arrays, the areas of their objects 1..Ka;
     gts: B annotations of the same sizes, numpy arrays or DEVICE tensors -- binary masks (nonzero = droplet; labelled here by
     4-connected components of at least gt_min_area pixels, never split) or, with gt_are_labels, integer label images whose
@@ -63,7 +67,8 @@ def match_batch(pred_labels, pred_areas, gts, gt_min_area=1, gt_are_labels=False
     filled part of the int32 and of the int64 outputs.  An image with more annotated droplets than max_gt, or more pairs
     than its first capacity, is computed again on its own.
     Returns per image a dict: a, b, n (the triples), gt_area, gt_sumy, gt_sumx (int64 [Kb]) and columns =
-    utils.droplet_match.match_columns(pred_area, gt_area, a, b, n)."""
+    utils.droplet_match.match_columns(pred_area, gt_area, a, b, n); with keep_labels also gt_labels, the annotation's int32
+    DEVICE label map (objects 1..len(gt_area)), for boundary_batch."""
     from utils.droplet_match import label_sums, match_columns
     B = len(pred_labels)
     if not (len(pred_areas) == len(gts) == B):
@@ -133,6 +138,8 @@ def match_batch(pred_labels, pred_areas, gts, gt_min_area=1, gt_are_labels=False
             a, b, n = (v32[i, j, :c[i, 1]] for j in (1, 2, 3))
         out.append({"a": a, "b": b, "n": n, "gt_area": area, "gt_sumy": sy, "gt_sumx": sx,
                     "columns": match_columns(pred_areas[i], area, a, b, n)})
+        if keep_labels:
+            out[-1]["gt_labels"] = lab
     return out
 
 
@@ -210,3 +217,77 @@ def sweep_batch(probs, gts, out_hws, K, hist=None, linear=True):
 def sweep_result(hist):
     """The device histogram of sweep_batch -> int64 numpy [2, K + 1]: the sweep's only device-to-host copy."""
     return hist.cpu().numpy()
+
+
+def boundary_batch(pred_labels, kas, gt_labels, kbs, radius, hist=None, dmax=None, objects=True):
+    """pred_labels, gt_labels: B int32 [h, w] DEVICE label maps each (image i of both lists has one size; the sizes may differ
+    between images); kas, kbs: B label limits (objects 1..ka, 1..kb; a binary mask is a label map with k = 1); radius: 1..64.
+    One unetdc_boundary_distances per image is enqueued back to back on the current stream into ONE workspace and ONE int64
+    output plane (histograms, tables and the two maxima); the host then waits ONCE, on the copy of that plane.
+    hist (int64 [2, radius^2 + 2]) and dmax (int32 [2], initialised to -1) given, both on the device: every image ADDS into them
+    (pool as many batches as you like, then boundary_result(hist, dmax) makes the copy) and nothing is fetched for them; with
+    objects False as well nothing waits for the device at all.
+    Returns per image the record of utils.droplet_boundary.boundary_record_numpy as int64 arrays: hist, dmax (None when
+    pooled), a, b (None without objects)."""
+    from utils.droplet_boundary import check_radius
+    B, R = len(pred_labels), check_radius(radius)
+    if not (len(kas) == len(gt_labels) == len(kbs) == B):
+        raise _lib.UnetdcError("boundary_batch needs one label limit per map and one annotation per prediction")
+    if (hist is None) != (dmax is None):
+        raise _lib.UnetdcError("hist and dmax come together or not at all")
+    nb = R * R + 2
+    if B == 0:
+        return []
+    dev = pred_labels[0].device
+    if hist is not None:
+        if not (hist.is_cuda and hist.dtype == torch.int64 and tuple(hist.shape) == (2, nb) and hist.is_contiguous()):
+            raise _lib.UnetdcError(f"hist must be a contiguous int64 [2, {nb}] tensor on the HIP device")
+        if not (dmax.is_cuda and dmax.dtype == torch.int32 and tuple(dmax.shape) == (2,) and dmax.is_contiguous()):
+            raise _lib.UnetdcError("dmax must be a contiguous int32 [2] tensor on the HIP device")
+    hws, kas, kbs = [], [int(k) for k in kas], [int(k) for k in kbs]
+    for a, b in zip(pred_labels, gt_labels):
+        _check_labels(a, "a predicted label map")
+        _check_labels(b, "an annotated label map")
+        if a.shape != b.shape:
+            raise _lib.UnetdcError("the two label maps differ in size")
+        hws.append((int(a.shape[0]), int(a.shape[1])))
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    wsb = max(lib.unetdc_boundary_distances_workspace(h, w) for h, w in hws)
+    if min(lib.unetdc_boundary_distances_workspace(h, w) for h, w in hws) <= 0 or min(kas + kbs) < 0:
+        raise _lib.UnetdcError("boundary_batch: sides 1..16384, non-negative label limits")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)           # one workspace: the launches are stream-ordered
+    pooled = hist is not None
+    # one int64 plane: per image [2, nb] histogram (unless pooled), then the tables [3, ka], [3, kb], then B words = [B, 2] int32
+    n_hist = 0 if pooled else B * 2 * nb
+    offs, at = [], n_hist
+    for ka, kb in zip(kas, kbs):
+        offs.append((at, at + 3 * ka))
+        at += (3 * ka + 3 * kb) if objects else 0
+    n_dmax = 0 if pooled else B
+    plane = torch.zeros(max(at + n_dmax, 1), dtype=torch.int64, device=dev)
+    if n_dmax:
+        plane[at:].fill_(-1)                                       # both int32 halves of every word are -1
+        dm = plane[at:].view(torch.int32).view(B, 2)
+    for i, (h, w) in enumerate(hws):
+        oa, ob = offs[i]
+        _lib.call("unetdc_boundary_distances", pred_labels[i].data_ptr(), kas[i], gt_labels[i].data_ptr(), kbs[i], h, w, R,
+                  ws.data_ptr(), wsb, hist.data_ptr() if pooled else plane[i * 2 * nb:].data_ptr(),
+                  dmax.data_ptr() if pooled else dm[i].data_ptr(),
+                  plane[oa:].data_ptr() if objects and kas[i] else None, plane[ob:].data_ptr() if objects and kbs[i] else None, s)
+    if pooled and not objects:
+        return [{"hist": None, "dmax": None, "a": None, "b": None} for _ in range(B)]
+    host = plane.cpu().numpy()                                     # the batch's only host wait
+    out = []
+    for i, (ka, kb) in enumerate(zip(kas, kbs)):
+        oa, ob = offs[i]
+        out.append({"hist": None if pooled else host[i * 2 * nb:(i + 1) * 2 * nb].reshape(2, nb).copy(),
+                    "dmax": None if pooled else host[at + i:at + i + 1].view(np.int32).astype(np.int64),
+                    "a": host[oa:oa + 3 * ka].reshape(3, ka).copy() if objects else None,
+                    "b": host[ob:ob + 3 * kb].reshape(3, kb).copy() if objects else None})
+    return out
+
+
+def boundary_result(hist, dmax):
+    """The pooled device planes of boundary_batch -> (int64 numpy [2, R^2 + 2], int64 numpy [2])."""
+    return hist.cpu().numpy(), dmax.cpu().numpy().astype(np.int64)
