@@ -1,4 +1,5 @@
-"""Inputs of tests/test_gpu_grid_caps.py and of the C-ABI density tests (tests/test_gpu_density.py), and the host-side rules
+"""Inputs of tests/test_gpu_grid_caps.py, of the long-list tests of tests/test_gpu_match.py (pair_count_labels,
+unique_pair_labels) and of the C-ABI density tests (tests/test_gpu_density.py), and the host-side rules
 they are checked with; tests/test_droplet_edges_cpu.py pins what each of them is for."""
 import functools
 
@@ -52,6 +53,59 @@ def cap_labels(shape):
     moved[h - 3:, w - 3:] = 1
     s = ndimage.generate_binary_structure(2, 1)
     return ndimage.label(m, s)[0].astype(np.int32), ndimage.label(moved, s)[0].astype(np.int32)
+
+
+PAIR_SORT_CHUNK = 4096            # pair_table.h: the entries one workgroup sorts in LDS; a longer list takes the global passes
+PAIR_GRID_PER_TRIP = 2048 * 256   # pair_init / pair_compact / pair_emit, neighbors_pairs and the per-label kernels of neighbors.hip
+PAIR_SHAPE = (96, 256)
+PAIR_B_LABELS = 61                # labels of the second map of pair_count_labels
+PAIR_B_PER_A = 5                  # partners of one label of the first map
+
+
+def pair_count_pairs(E):
+    """The construction of pair_count_labels -> int64 (a, b, pixels) of pair p = 0..E-1, in (a, b) order.  Label a = p // 5 + 1
+    has the five partners b = ((p % 5) * 12 + 7 (a - 1)) % 61 + 1, distinct because 12 j < 61 for j < 5; a label b meets many a.
+    Every third pair has a second pixel, every eleventh one more."""
+    p = np.arange(int(E), dtype=np.int64)
+    a = p // PAIR_B_PER_A + 1
+    b = ((p % PAIR_B_PER_A) * 12 + 7 * (a - 1)) % PAIR_B_LABELS + 1
+    n = 1 + (p % 3 == 0) + (p % 11 == 0)
+    order = np.lexsort((b, a))
+    return a[order], b[order], n[order].astype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_count_labels(E, shape=PAIR_SHAPE):
+    """-> (A, B): int32 label maps of `shape` with exactly E distinct overlapping (a, b) pairs, those of pair_count_pairs(E), at
+    pixel positions shuffled with a fixed seed (the pixels of one pair lie apart: the combine step of the insert runs, not
+    only the run length).  Of the pixels left over a third carries a label on the first map only, a third on the second only."""
+    h, w = shape
+    a, b, n = pair_count_pairs(E)
+    total = int(n.sum())
+    assert total <= h * w
+    pos = np.random.default_rng(1000 + int(E)).permutation(h * w)
+    A, B = np.zeros(h * w, np.int32), np.zeros(h * w, np.int32)
+    A[pos[:total]] = np.repeat(a, n)
+    B[pos[:total]] = np.repeat(b, n)
+    rest = pos[total:]
+    A[rest[0::3]] = 1 + rest[0::3] % int(a.max())              # a label over background of the other map: no pair
+    B[rest[1::3]] = 1 + rest[1::3] % PAIR_B_LABELS
+    A, B = A.reshape(h, w), B.reshape(h, w)
+    A.setflags(write=False)
+    B.setflags(write=False)
+    return A, B
+
+
+@functools.lru_cache(maxsize=None)
+def unique_pair_labels(shape):
+    """-> (A, B): A a seeded permutation of 1..h*w, B = (i % 5) + 1 at linear index i.  Every pixel is a pair of its own: the
+    list is h * w long."""
+    h, w = shape
+    A = (1 + np.random.default_rng(h + w).permutation(h * w)).astype(np.int32).reshape(h, w)
+    B = (np.arange(h * w) % 5 + 1).astype(np.int32).reshape(h, w)
+    A.setflags(write=False)
+    B.setflags(write=False)
+    return A, B
 
 
 def few_dozen_labels():

@@ -131,3 +131,79 @@ def touching_map(h=97, w=131, seed=3, cells=9):
     lab = np.ascontiguousarray(lab)
     lab.setflags(write=False)
     return lab, 39
+
+
+# (h, w, step, G, labels, pairs): lattices of single-pixel droplets whose pair lists pass one, two and four sort chunks of 4096
+LATTICES = ((64, 65, 1, 1, 4160, 8191), (129, 129, 2, 2, 4225, 8320), (129, 129, 2, 3, 4225, 16512), (91, 91, 1, 2, 8281, 48778))
+CAP_LATTICE = (1500, 1500, 2, 2, 562500, 1123500)              # past the 2048 x 256 grids of the per-label and per-pair kernels
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_map(h, w, step, seed=1):
+    """-> (int32 map, k): single-pixel droplets every `step` pixels from (0, 0), labelled by a seeded permutation of 1..k, so
+    label order is unrelated to raster order.  The nearest neighbours of a droplet all lie `step` away: the smaller label
+    decides nn_label."""
+    lab = np.zeros((h, w), np.int32)
+    rows, cols = len(range(0, h, step)), len(range(0, w, step))
+    k = rows * cols
+    lab[::step, ::step] = (1 + np.random.default_rng(seed).permutation(k)).astype(np.int32).reshape(rows, cols)
+    lab.setflags(write=False)
+    return lab, k
+
+
+def offset_pairs(lab, k, G):
+    """A map of single-pixel droplets -> int64 (a, b, d2) in (a, b) order: for every offset (dy, dx) of the half plane with
+    dy^2 + dx^2 <= G^2 the pixel pairs (p, p + offset) with two different labels in 1..k, keyed (smaller, larger), the minimum
+    per key.  Plain shifted views; shares nothing with utils/droplet_neighbors.py."""
+    lab = np.asarray(lab).astype(np.int64)
+    lab = np.where((lab >= 1) & (lab <= int(k)), lab, 0)
+    h, w = lab.shape
+    keys, dist = [], []
+    for dy in range(0, G + 1):
+        for dx in range(-G, G + 1):
+            if (dy == 0 and dx <= 0) or dy * dy + dx * dx > G * G or dy >= h or abs(dx) >= w:
+                continue
+            p = lab[:h - dy, max(-dx, 0):w - max(dx, 0)]
+            q = lab[dy:, max(dx, 0):w - max(-dx, 0)]
+            hit = (p > 0) & (q > 0) & (p != q)
+            lo, hi = np.minimum(p[hit], q[hit]), np.maximum(p[hit], q[hit])
+            keys.append((lo << 32) | hi)
+            dist.append(np.full(lo.size, dy * dy + dx * dx, np.int64))
+    if not keys:
+        return tuple(np.zeros(0, np.int64) for _ in range(3))
+    keys, dist = np.concatenate(keys), np.concatenate(dist)
+    uniq, inverse = np.unique(keys, return_inverse=True)
+    d2 = np.full(uniq.size, INF, np.int64)
+    np.minimum.at(d2, inverse, dist)
+    return uniq >> 32, uniq & 0xFFFFFFFF, d2
+
+
+PATCH_SIZES = ((1, 1), (1, 2), (2, 2), (2, 3), (3, 3), (3, 1), (1, 3))       # droplets per patch: rows x columns
+PATCH_G = 2
+PATCH_MISSING = 7                                                             # labels of 1..K without a pixel
+
+
+@functools.lru_cache(maxsize=None)
+def patch_map(h=512, w=520, seed=4):
+    """-> (int32 map, K, cluster [K], cluster_size [K]) for radius PATCH_G: one step-2 lattice patch of a seeded choice of
+    PATCH_SIZES in the corner of every 8 x 8 cell (a patch spans at most 5 x 5 pixels: 3 > G pixels between two patches), labels a
+    seeded permutation of 1..K of which the last PATCH_MISSING stay unused.  A patch is one cluster: its root is its smallest
+    label, its size the patch's droplets; a label without a pixel is its own cluster of size 0."""
+    g = np.random.default_rng(seed)
+    cells = [(y, x) for y in range(0, h - 7, 8) for x in range(0, w - 7, 8)]
+    sizes = [PATCH_SIZES[i] for i in g.integers(0, len(PATCH_SIZES), len(cells))]
+    K = sum(r * c for r, c in sizes) + PATCH_MISSING
+    labels = (1 + g.permutation(K)).astype(np.int64)
+    lab = np.zeros((h, w), np.int32)
+    cluster, size = np.arange(1, K + 1, dtype=np.int64), np.zeros(K, np.int64)
+    at = 0
+    for (y, x), (r, c) in zip(cells, sizes):
+        mine = labels[at:at + r * c]
+        at += r * c
+        lab[y:y + 2 * r:2, x:x + 2 * c:2] = mine.reshape(r, c)
+        cluster[mine - 1] = mine.min()
+        size[mine - 1] = r * c
+    assert at == K - PATCH_MISSING
+    for v in (lab, cluster, size):
+        v.setflags(write=False)
+    return lab, K, cluster, size

@@ -83,6 +83,60 @@ def test_cap_label_maps_hold_what_they_are_for(shape):
     assert table == overlap_table_ref(A.tolist(), B.tolist(), kmax(A), kmax(B))  # the vectorised host path and the plain loops
 
 
+PAIR_COUNTS = (4095, 4096, 4097, 8191, 8192, 8193, 12289)     # around one, two and three sort chunks
+
+
+def pow2_at_least(v):
+    return 1 << max(int(v) - 1, 0).bit_length()
+
+
+@pytest.mark.parametrize("E", PAIR_COUNTS)
+def test_pair_count_labels_hold_exactly_that_many_pairs(E):
+    assert fx.PAIR_SORT_CHUNK == 4096 and fx.PAIR_SHAPE == (96, 256)
+    a, b, n = fx.pair_count_pairs(E)
+    assert len(a) == E and len(set(zip(a.tolist(), b.tolist()))) == E            # the construction: E distinct keys
+    assert np.bincount(a)[1:-1].min() == fx.PAIR_B_PER_A                          # several b per a (the last a may have fewer)
+    assert np.bincount(b, minlength=fx.PAIR_B_LABELS + 1)[1:].min() >= 50         # ... and many a per b: both halves of the key order
+    assert (n == 2).sum() > E // 4 and (n == 3).sum() > E // 40 and n.min() == 1
+    for shape in (fx.PAIR_SHAPE, (512, 512)):
+        A, B = fx.pair_count_labels(E, shape)
+        assert A.dtype == B.dtype == np.int32 and A.shape == B.shape == shape
+        got = dm.overlap_table_numpy(A, B, kmax(A), kmax(B))
+        assert all(np.array_equal(x, y) for x, y in zip(got, (a, b, n)))          # the host path finds what was put there
+        assert kmax(A) == (E - 1) // fx.PAIR_B_PER_A + 1 and kmax(B) == fx.PAIR_B_LABELS
+        assert ((A > 0) & (B == 0)).sum() > 100 and ((A == 0) & (B > 0)).sum() > 100      # labels that meet background only
+        # the pixels of a pair with several lie apart: in different 64-pixel units, so each is an insert of its own
+        key = (A.astype(np.int64) << 32 | B)[(A > 0) & (B > 0)]
+        yy, xx = np.nonzero((A > 0) & (B > 0))
+        units = np.unique(np.stack([key, fx.unit_of(yy, xx, shape[1])]), axis=1)
+        assert (np.unique(units[0], return_counts=True)[1] >= 2).sum() > E // 4
+    assert 512 * 512 >= 1 << 18                                                   # a capacity of 2^18 is not cut to h * w there
+    h, w = fx.PAIR_SHAPE
+    # the network of a tight capacity: one chunk, two, four
+    assert pow2_at_least(E) == {4095: 4096, 4096: 4096, 4097: 8192, 8191: 8192, 8192: 8192, 8193: 16384, 12289: 16384}[E]
+    assert E - 1 <= h * w and pow2_at_least(h * w) == 32768
+
+
+def test_the_pair_counts_sit_on_both_sides_of_every_chunk_multiple():
+    c = fx.PAIR_SORT_CHUNK
+    assert [E for E in PAIR_COUNTS if E <= c] == [4095, 4096] and [E for E in PAIR_COUNTS if c < E <= 2 * c] == [4097, 8191, 8192]
+    assert [E for E in PAIR_COUNTS if 2 * c < E <= 4 * c] == [8193, 12289] and 12289 == 3 * c + 1
+    from unet_dc_segmentation_amd import droplets
+    assert droplets.PAIR_ROOM == 4 * c                                            # what production launches with: four chunks
+
+
+@pytest.mark.parametrize("shape", fx.CAP_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_unique_pair_labels_make_every_pixel_a_pair(shape):
+    h, w = shape
+    A, B = fx.unique_pair_labels(shape)
+    assert A.dtype == B.dtype == np.int32 and np.array_equal(np.sort(A.ravel()), np.arange(1, h * w + 1))
+    assert not np.array_equal(A.ravel(), np.arange(1, h * w + 1)) and np.array_equal(B.ravel(), np.arange(h * w) % 5 + 1)
+    a, b, n = dm.overlap_table_numpy(A, B, h * w, 5)
+    assert len(a) == h * w > 1 << 21 and pow2_at_least(h * w) == 1 << 22          # 2^21 compare-exchanges a pass: 4096 x 256 twice
+    assert h * w > fx.PAIR_GRID_PER_TRIP == 524288 and (n == 1).all()
+    assert np.array_equal(a, np.arange(1, h * w + 1)) and np.array_equal(b[A.ravel() - 1], B.ravel())
+
+
 def test_expected_rows_layout_for_a_large_capacity():
     from tests.test_gpu_shape import NQ, expected_rows
     lab = fx.few_dozen_labels()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import droplet_edge_fixtures as fx
 from tests.test_gpu_split import CANARY32, PAD, device_split, probs_of, stream
 from tests.test_match_cpu import BIG_PAIRS, areas, big_pair, cc_labels, kmax, shift, small_pairs
 from tests.test_split_cpu import files, noise_mask
@@ -16,11 +17,11 @@ WS_PAD = 256          # canary bytes on both sides of the workspace
 WS_CANARY = 0xA5
 
 
-def device_overlap(A, ka, B, kb, max_pairs=None, ws=None):
-    """-> (count, [(a, b, n)] of the first min(count, max_pairs) entries).  The count, the three arrays and the workspace sit
-    between canaries; only the first min(count, max_pairs) entries of the arrays may have been written, and on overflow
-    nothing past max_pairs.  ws: a prepared Canaried view (tests/image_canaries.py) of exactly the queried bytes to use as the
-    workspace, its guards checked here."""
+def device_overlap_arrays(A, ka, B, kb, max_pairs=None, ws=None):
+    """-> (count, int64 arrays (a, b, n) of the first min(count, max_pairs) entries).  The count, the three arrays and the
+    workspace sit between canaries; only the first min(count, max_pairs) entries of the arrays may have been written, and on
+    overflow nothing past max_pairs.  ws: a prepared Canaried view (tests/image_canaries.py) of exactly the queried bytes to use
+    as the workspace, its guards checked here."""
     from unet_dc_segmentation_amd import _lib
     h, w = A.shape
     lib = _lib.load()
@@ -33,8 +34,8 @@ def device_overlap(A, ka, B, kb, max_pairs=None, ws=None):
     else:
         assert ws.nbytes == nbytes
         wbuf, wptr = None, ws.ptr
-    la = torch.from_numpy(np.ascontiguousarray(A, dtype=np.int32)).cuda()
-    lb = torch.from_numpy(np.ascontiguousarray(B, dtype=np.int32)).cuda()
+    la = torch.from_numpy(np.array(A, dtype=np.int32, order="C")).cuda()        # a copy: the fixtures may be read-only
+    lb = torch.from_numpy(np.array(B, dtype=np.int32, order="C")).cuda()
     count = torch.full((1 + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda")
     outs = [torch.full((cap + 2 * PAD,), CANARY32, dtype=torch.int32, device="cuda") for _ in range(3)]
     _lib.call("unetdc_label_overlap", la.data_ptr(), ka, lb.data_ptr(), kb, h, w, wptr, nbytes,
@@ -54,7 +55,13 @@ def device_overlap(A, ka, B, kb, max_pairs=None, ws=None):
         v = t.cpu().numpy()
         assert np.all(v[:PAD] == CANARY32) and np.all(v[PAD + k:] == CANARY32), "write outside the first min(count, max_pairs)"
         cols.append(v[PAD:PAD + k].astype(np.int64))
-    assert torch.equal(la.cpu(), torch.from_numpy(np.ascontiguousarray(A, dtype=np.int32)))      # the inputs are read only
+    assert np.array_equal(la.cpu().numpy(), A) and np.array_equal(lb.cpu().numpy(), B)          # the inputs are read only
+    return n, tuple(cols)
+
+
+def device_overlap(A, ka, B, kb, max_pairs=None, ws=None):
+    """device_overlap_arrays with the entries as a list of (a, b, n) tuples."""
+    n, cols = device_overlap_arrays(A, ka, B, kb, max_pairs, ws)
     return n, list(zip(*(v.tolist() for v in cols)))
 
 
@@ -106,6 +113,59 @@ def test_capacity():
         assert n == cap + 1
     z = np.zeros_like(A)
     assert device_overlap(A, ka, z, 0, max_pairs=0) == (0, [])
+
+
+def assert_arrays_equal_host_path(A, B, max_pairs=None):
+    """The long lists: arrays, not tuples.  -> (the host table, the device's arrays)."""
+    ka, kb = kmax(A), kmax(B)
+    ref = dm.overlap_table_numpy(A, B, ka, kb)
+    n, got = device_overlap_arrays(A, ka, B, kb, max_pairs)
+    assert n == len(ref[0])
+    for q, x, y in zip("abn", got, ref):
+        assert np.array_equal(x, y), (q, max_pairs, np.flatnonzero(x != y)[:5])
+    return ref, got
+
+
+@pytest.mark.parametrize("E", [4095, 4096, 4097, 8191, 8192, 8193, 12289])
+def test_list_lengths_around_the_sort_chunks(E):
+    """Lists of one, two and four LDS chunks of 4096 entries (csrc/pair_table.h): past 4096 the global compare-exchange passes
+    and the merge tails of the blocks behind block 0 run.  Tight: the network is the power of two that holds E.  Roomy and
+    h * w: the launches of a larger capacity run the list's shorter network, the blocks behind it leave at once.  E - 1:
+    overflow, nothing written from the capacity on (the canary check inside device_overlap_arrays)."""
+    A, B = fx.pair_count_labels(E)
+    want = fx.pair_count_pairs(E)
+    ref, _ = assert_arrays_equal_host_path(A, B, max_pairs=E)
+    assert len(ref[0]) == E and all(np.array_equal(x, y) for x, y in zip(ref, want))
+    assert_arrays_equal_host_path(A, B)                                  # h * w = 24 576: launched for a network of 32 768
+    assert_arrays_equal_host_path(A, B, max_pairs=1 << 18)               # outputs of 2^18; the table is cut to h * w
+    roomy_A, roomy_B = fx.pair_count_labels(E, (512, 512))               # h * w = 2^18: the capacity is not cut
+    roomy, _ = assert_arrays_equal_host_path(roomy_A, roomy_B, max_pairs=1 << 18)
+    assert all(np.array_equal(x, y) for x, y in zip(roomy, want))
+    n, _ = device_overlap_arrays(A, kmax(A), B, kmax(B), max_pairs=E - 1)
+    assert n == E
+
+
+def test_two_runs_of_a_four_chunk_list_give_equal_bytes():
+    A, B = fx.pair_count_labels(12289)
+    for cap in (12289, None):
+        _, one = assert_arrays_equal_host_path(A, B, max_pairs=cap)
+        _, two = assert_arrays_equal_host_path(A, B, max_pairs=cap)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(one, two))
+
+
+def test_label_overlap_recovers_on_a_table_of_more_than_three_chunks():
+    """evaluate.label_overlap with 12 289 overlaps: its first capacity 4 (ka + kb) + 64 = 10 140 overflows and the second is
+    h * w; from capacity 3 the seventh try has room for 12 288, one short."""
+    from unet_dc_segmentation_amd.evaluate import first_capacity, label_overlap
+    A, B = fx.pair_count_labels(12289)
+    ka, kb = kmax(A), kmax(B)
+    assert first_capacity(ka, kb) == 10140 < 12289 and 3 * 4 ** 6 == 12288
+    ref = dm.overlap_table_numpy(A, B, ka, kb)
+    a_d, b_d = torch.from_numpy(np.array(A)).cuda(), torch.from_numpy(np.array(B)).cuda()
+    for capacity in (None, 3):
+        got = label_overlap(a_d, ka, b_d, kb, capacity=capacity)
+        for x, y in zip(got, ref):
+            assert x.dtype == np.int64 and np.array_equal(x, y)
 
 
 def test_labels_out_of_range_are_skipped():

@@ -17,9 +17,9 @@ pytestmark = pytest.mark.gpu
 RADII = (1, 2, 5, 32, 64)
 
 
-def device_neighbors(lab, k, G, max_pairs=None, ws=None):
-    """-> (count, [(a, b, d2)] of the first min(count, max_pairs) entries, {column: list of k}, the workspace view).  The count,
-    the three pair arrays, the five per-label arrays and the workspace sit between canaries; only the first
+def device_neighbors_arrays(lab, k, G, max_pairs=None, ws=None):
+    """-> (count, int64 arrays (a, b, d2) of the first min(count, max_pairs) entries, {column: int64 [k]}, the workspace view).
+    The count, the three pair arrays, the five per-label arrays and the workspace sit between canaries; only the first
     min(count, max_pairs) entries of the pair arrays may have been written.  ws: a prepared Canaried view of exactly the
     queried bytes to use as the workspace."""
     from unet_dc_segmentation_amd import _lib
@@ -48,14 +48,20 @@ def device_neighbors(lab, k, G, max_pairs=None, ws=None):
     for t in pairs:
         v = t.cpu().numpy()
         assert np.all(v[:PAD] == CANARY32) and np.all(v[PAD + m:] == CANARY32), "write outside the first min(count, max_pairs)"
-        got.append(v[PAD:PAD + m].astype(np.int64).tolist())
+        got.append(v[PAD:PAD + m].astype(np.int64))
     out = {}
     for q, t in zip(dn.COLUMN_NAMES, cols):
         v = t.cpu().numpy()
         assert np.all(v[:PAD] == CANARY32) and np.all(v[PAD + k:] == CANARY32), "write outside a per-label output"
-        out[q] = v[PAD:PAD + k].astype(np.int64).tolist()
+        out[q] = v[PAD:PAD + k].astype(np.int64)
     assert np.array_equal(dl.cpu().numpy(), lab)               # the input is read only
-    return n, list(zip(*got)), out, ws
+    return n, tuple(got), out, ws
+
+
+def device_neighbors(lab, k, G, max_pairs=None, ws=None):
+    """device_neighbors_arrays with the pairs as a list of (a, b, d2) tuples and the columns as lists."""
+    n, got, out, ws = device_neighbors_arrays(lab, k, G, max_pairs, ws)
+    return n, list(zip(*(v.tolist() for v in got))), {q: v.tolist() for q, v in out.items()}, ws
 
 
 def host_record(lab, k, G):
@@ -174,6 +180,66 @@ def test_capacity():
         assert device_neighbors(lab, n, 5, max_pairs=cap)[0] == cap + 1
     assert device_neighbors(np.zeros_like(lab), n, 5, max_pairs=0)[:2] == (0, [])
     assert device_neighbors(lab, 0, 5, max_pairs=0)[:3] == (0, [], {q: [] for q in dn.COLUMN_NAMES})
+
+
+def assert_arrays_equal_reference(lab, k, G, max_pairs, pairs=None):
+    """The long lists: the device's arrays against offset_pairs (tests/neighbors_ref.py, pinned to the host path on the CPU)
+    and the host columns of that list, twice: two runs give equal bytes, pair order included.  -> the device's record."""
+    pairs = ref.offset_pairs(lab, k, G) if pairs is None else pairs
+    cols = dn.neighbor_columns(pairs, k, dn.present_labels(lab, k))
+    runs = [device_neighbors_arrays(lab, k, G, max_pairs)[:3] for _ in range(2)]
+    n, got, gcols = runs[0]
+    assert n == len(pairs[0])
+    for q, x, y in zip(("a", "b", "d2"), got, pairs):
+        assert np.array_equal(x, y), (q, G, max_pairs, np.flatnonzero(x != y)[:5])
+    for q in dn.COLUMN_NAMES:
+        assert np.array_equal(gcols[q], cols[q]), (q, G, max_pairs, np.flatnonzero(gcols[q] != cols[q])[:5])
+    assert runs[1][0] == n and all(x.tobytes() == y.tobytes() for x, y in zip(got, runs[1][1]))
+    assert all(gcols[q].tobytes() == runs[1][2][q].tobytes() for q in dn.COLUMN_NAMES)
+    return n, got, gcols
+
+
+@pytest.mark.parametrize("lattice", ref.LATTICES, ids=lambda v: "{}x{}_step{}_G{}".format(*v[:4]))
+def test_lattices_of_more_pairs_than_a_sort_chunk(lattice):
+    """Two, four and sixteen LDS chunks of pairs (csrc/pair_table.h) in this file's copy of the sort: the global passes, the
+    merge tails behind block 0, and thousands of labels for the union and the 64-bit minimum, whose ties the smaller label
+    wins.  max_pairs is always given: the helper's default k (k - 1) / 2 would be a table of gigabytes."""
+    h, w, step, G, k, n = lattice
+    lab, _ = ref.lattice_map(h, w, step)
+    pairs = ref.offset_pairs(lab, k, G)
+    assert len(pairs[0]) == n > 4096
+    assert_arrays_equal_reference(lab, k, G, n, pairs)                   # exact
+    _, _, cols = assert_arrays_equal_reference(lab, k, G, 1 << 16, pairs)
+    assert (cols["cluster"] == 1).all() and (cols["cluster_size"] == k).all() and (cols["nn_d2"] == step * step).all()
+    assert device_neighbors_arrays(lab, k, G, n - 1)[0] == n             # overflow: the canaries from n - 1 on are checked inside
+    half = ref.offset_pairs(lab, k // 2, G)                              # half the labels are background
+    assert 0 < len(half[0]) < n // 2
+    assert_arrays_equal_reference(lab, k // 2, G, len(half[0]), half)
+    assert_arrays_equal_reference(lab, k // 2, G, 1 << 16, half)
+
+
+def test_patches_of_known_cluster_sizes():
+    """Thousands of clusters of one to nine droplets and a few labels without a pixel, over three sort chunks of pairs."""
+    lab, K, cluster, size = ref.patch_map()
+    for cap in (1 << 14, 1 << 16):
+        n, _, cols = assert_arrays_equal_reference(lab, K, ref.PATCH_G, cap)
+        assert 3 * 4096 < n <= 1 << 14
+        assert np.array_equal(cols["cluster"], cluster) and np.array_equal(cols["cluster_size"], size)
+
+
+def test_batch_at_the_production_pair_room():
+    """260 x 260 with a droplet every second pixel: 16 900 droplets and 33 540 pairs, more than PAIR_ROOM = 2^14.  The first launch
+    overflows at the capacity production uses, the retries double it."""
+    from unet_dc_segmentation_amd import droplets as D
+    m = np.zeros((260, 260), np.uint8)
+    m[::2, ::2] = 1
+    probs = torch.from_numpy(probs_of(m)[None]).cuda()
+    assert D.PAIR_ROOM == 1 << 14 and 2 * D.PAIR_ROOM < 33540
+    out = D.mask_and_droplets_batch(probs, 0.5, [m.shape], 1, max_droplets=1 << 15, return_labels=True, neighbors=2)[0]
+    assert len(out.area) == 16900 and (out.area == 1).all()
+    assert assert_record_equals_host(out, 2) == 33540
+    lab = out.labels.cpu().numpy()
+    assert all(np.array_equal(out.neighbors["pairs"][q], v) for q, v in zip(("a", "b", "d2"), ref.offset_pairs(lab, 16900, 2)))
 
 
 @pytest.mark.parametrize("state", ["ones", "stale"])

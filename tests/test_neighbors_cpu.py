@@ -85,6 +85,76 @@ def test_random_maps_equal_the_brute_force(G):
         assert sum(1 for _, _, d in tp if d == 1) > 20
 
 
+def arrays_equal(x, y):
+    return len(x) == len(y) and all(u.dtype == np.int64 and np.array_equal(u, v) for u, v in zip(x, y))
+
+
+def test_offset_pairs_equal_the_brute_force_and_the_host_path():
+    """The plain reference of the long-list GPU tests, on maps of single-pixel droplets small enough for the brute force."""
+    for (h, w, step), radii in (((9, 11, 1), (1, 2, 3)), ((12, 13, 2), (2, 3, 5)), ((10, 14, 3), (3, 5, 9)), ((1, 9, 1), (1, 4))):
+        lab, k = ref.lattice_map(h, w, step, seed=h)
+        assert np.array_equal(np.sort(lab[lab > 0]), np.arange(1, k + 1)) and (lab[::step, ::step] > 0).all()
+        for G in radii:
+            for kk in (k, k // 2, 0):
+                got = ref.offset_pairs(lab, kk, G)
+                assert list(zip(*(v.tolist() for v in got))) == ref.brute_pairs(lab, kk, G), (h, w, step, G, kk)
+                assert arrays_equal(got, dn.neighbor_pairs_numpy(lab, kk, G))
+    lab, k, G, want = ref.hand_fixtures()["chain_and_islands"]
+    assert list(zip(*(v.tolist() for v in ref.offset_pairs(lab, k, G)))) == want
+    messy, k = ref.edge_maps()["out_of_range_values"]
+    assert arrays_equal(ref.offset_pairs(messy, k, 2), dn.neighbor_pairs_numpy(messy, k, 2))
+
+
+@pytest.mark.parametrize("lattice", ref.LATTICES, ids=lambda v: "{}x{}_step{}_G{}".format(*v[:4]))
+def test_lattices_pass_the_sort_chunks_they_are_for(lattice):
+    h, w, step, G, k, n = lattice
+    lab, got_k = ref.lattice_map(h, w, step)
+    assert got_k == k > 4096 and np.array_equal(np.sort(lab[lab > 0]), np.arange(1, k + 1))
+    assert not np.array_equal(lab[lab > 0], np.arange(1, k + 1))                  # label order is not raster order
+    pairs = ref.offset_pairs(lab, k, G)
+    assert arrays_equal(pairs, dn.neighbor_pairs_numpy(lab, k, G)) and len(pairs[0]) == n
+    assert {8191: 4096 < n < 8192, 8320: 8192 < n < 16384, 16512: 16384 < n, 48778: 2 * 16384 < n < 1 << 16}[n]
+    cols = dn.neighbor_columns(pairs, k)
+    assert (cols["nn_d2"] == step * step).all() and cols["degree"].min() >= 2     # every droplet has a partner at the lattice step
+    a, b, d2 = pairs
+    ties = np.bincount(np.concatenate([a, b])[np.concatenate([d2, d2]) == step * step], minlength=k + 1)[1:]
+    assert ties.min() >= 2                                                         # ... at least two of them: the smaller label wins
+    assert (cols["cluster"] == 1).all() and (cols["cluster_size"] == k).all()
+    half = ref.offset_pairs(lab, k // 2, G)
+    assert arrays_equal(half, dn.neighbor_pairs_numpy(lab, k // 2, G)) and 0 < len(half[0]) < n // 2
+    assert len(np.unique(dn.neighbor_columns(half, k // 2, dn.present_labels(lab, k // 2))["cluster"])) > 1     # no longer one cluster
+
+
+def test_the_cap_lattice_passes_the_grids_of_the_per_label_and_per_pair_kernels():
+    h, w, step, G, k, n = ref.CAP_LATTICE
+    lab, got_k = ref.lattice_map(h, w, step)
+    a, b, d2 = ref.offset_pairs(lab, k, G)
+    assert got_k == k > 2048 * 256 and len(a) == n > 2048 * 256 and n <= 1 << 21 and (d2 == 4).all()
+    assert len(np.unique((a << 32) | b)) == n and (a < b).all()
+    # the same pairs by position: each droplet with its right and its lower neighbour
+    grid = lab[::step, ::step].astype(np.int64)
+    by_hand = np.concatenate([(np.minimum(p, q) << 32 | np.maximum(p, q)).ravel()
+                              for p, q in ((grid[:, :-1], grid[:, 1:]), (grid[:-1], grid[1:]))])
+    assert np.array_equal(np.sort(by_hand), (a << 32) | b)
+
+
+def test_patch_map_has_thousands_of_clusters_of_known_sizes():
+    lab, K, cluster, size = ref.patch_map()
+    G = ref.PATCH_G
+    pairs = ref.offset_pairs(lab, K, G)
+    assert arrays_equal(pairs, dn.neighbor_pairs_numpy(lab, K, G)) and len(pairs[0]) > 3 * 4096
+    present = dn.present_labels(lab, K)
+    assert (~present).sum() == ref.PATCH_MISSING and K > 4096
+    cols = dn.neighbor_columns(pairs, K, present)
+    assert np.array_equal(cols["cluster"], cluster) and np.array_equal(cols["cluster_size"], size)
+    assert len(np.unique(cluster[present])) == (512 // 8) * (520 // 8) == 4160
+    assert sorted(set(size.tolist())) == [0, 1, 2, 3, 4, 6, 9] and (size[~present] == 0).all()
+    assert set(cols["degree"].tolist()) == {0, 1, 2, 3, 4} and (cols["nn_label"][size == 1] == 0).all()
+    # no pair joins two patches: more than G pixels of background between any two
+    fg = lab > 0
+    assert not fg[5::8].any() and not fg[6::8].any() and not fg[7::8].any() and not fg[:, 5::8].any() and not fg[:, 6::8].any() and not fg[:, 7::8].any()
+
+
 def test_check_radius_and_helpers():
     assert dn.check_radius(1) == 1 and dn.check_radius(np.int64(64)) == 64 and dn.DEFAULT_RADIUS == 5
     for bad in (0, 65, -1, 2.0, "3", None, True):
