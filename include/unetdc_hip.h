@@ -85,10 +85,51 @@ typedef struct unetdc_adam_desc {
   int64_t g_off, begin, numel;
   int32_t a, b;                   /* kind 0: (cout, cin); kind 1: (cin, cout); kind 2: unused */
   int32_t kind;                   /* 0 conv3x3 (packed), 1 convT2x2 (packed), 2 plain */
-  int32_t pad;
+  int32_t flags;                  /* bit 0: weight decay applies (unetdc_adam_step_ex; unetdc_adam_step ignores the word) */
 } unetdc_adam_desc;
 int unetdc_adam_step(const unetdc_adam_desc* table_dev, int n, int64_t total_blocks, const float* flat_grad, double lr,
                      double beta1, double beta2, double eps, int64_t step, double grad_scale, int dtype, unetdc_stream_t s);
+
+/* ---- optimizer recipe: global-norm clipping, non-finite guard, decoupled weight decay, EMA -----
+ * unetdc_step_ctl: the DEVICE-resident record unetdc_grad_norm writes and unetdc_adam_step_ex reads; the host never has to
+ *   read it between the two.  The caller zeroes it once (steps, clipped, skipped and norm_sum accumulate over the calls;
+ *   sumsq, norm, gscale_eff and skip are rewritten by every call, nothing of the previous step survives).
+ * unetdc_grad_norm: sumsq = grad_scale^2 * sum_i flat_grad[i]^2 over i in [0, n), norm = sqrt(sumsq): the global L2 norm of
+ *   grad_scale * flat_grad.  Two launches: at most 2048 fp64 partials (one per workgroup, 4096 elements per trip), then a
+ *   one-workgroup finaliser.  Every product is formed as (double)g * (double)g, which is exact, and summed in fp64 in a fixed
+ *   order: no atomics, no hand-off between workgroups, bitwise reproducible, and the relative error of sumsq is below
+ *   (n + 2) 2^-53.  16-byte loads with a scalar tail: n need not be a multiple of 4.  Then
+ *     skip = 1 when sumsq is not finite (an inf or NaN gradient anywhere), else 0;
+ *     coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), 1 when max_norm <= 0 (no clipping);
+ *     gscale_eff = (float)(grad_scale * coef), formed in double and rounded once (0 when skip is set);
+ *     steps += 1; skipped += skip; on a finite step norm_sum += norm and clipped += (coef < 1).
+ *   Nothing but the workspace (unetdc_grad_norm_workspace(n) bytes, 8-byte aligned; 0 for n <= 0) and the record is written.
+ *   UNETDC_EINVAL before any HIP call: a null pointer, a flat_grad that is not 16-byte aligned, a ctl_dev or workspace that
+ *   is not 8-byte aligned, n <= 0, a non-finite grad_scale, a NaN max_norm; UNETDC_EWORKSPACE for a workspace too small.
+ * unetdc_adam_step_ex: unetdc_adam_step (same table, same work decomposition, the other instantiation of the same kernel) with
+ *     ctl_dev (nullable): every workgroup reads the record once; with skip set it returns before touching anything (p, m, v,
+ *       both images and the EMA stay bit for bit), else gscale_eff replaces (float)grad_scale;
+ *     weight_decay: p <- p * (float)(1 - lr * weight_decay) before the Adam update, one extra rounding (torch.optim.AdamW),
+ *       for the descriptors with bit 0 of `flags` set only;
+ *     ema_base (nullable), m_base, ema_decay: the moving average of tensor i lives at ema_base + (table[i].m - m_base), i.e.
+ *       in the flat layout of the moments; e <- e + (float)(1 - ema_decay) * (p_new - e), two roundings.
+ *   The images are written from the new p.  With ctl_dev == NULL (or a record with gscale_eff == (float)grad_scale),
+ *   weight_decay == 0 and ema_base == NULL the results equal unetdc_adam_step's bit for bit.  Refuses what unetdc_adam_step
+ *   refuses, a weight_decay outside [0, 1 / lr), an ema_decay outside [0, 1], an ema_base without m_base. */
+typedef struct unetdc_step_ctl {
+  double sumsq, norm;
+  float gscale_eff;
+  int32_t skip;
+  int64_t steps, clipped, skipped;
+  double norm_sum;
+} unetdc_step_ctl;
+int64_t unetdc_grad_norm_workspace(int64_t n);
+int unetdc_grad_norm(const float* flat_grad, int64_t n, double grad_scale, double max_norm, unetdc_step_ctl* ctl_dev,
+                     void* workspace, int64_t workspace_bytes, unetdc_stream_t s);
+int unetdc_adam_step_ex(const unetdc_adam_desc* table_dev, int n, int64_t total_blocks, const float* flat_grad, double lr,
+                        double beta1, double beta2, double eps, int64_t step, double grad_scale, int dtype,
+                        const unetdc_step_ctl* ctl_dev, double weight_decay, float* ema_base, const float* m_base,
+                        double ema_decay, unetdc_stream_t s);
 
 /* ---- dilated 3x3 convolution, padding = dilation: nn.Conv2d at models/model_2.py:41-44,48-51 ---
  * y = conv(x) + bias                                  (scale == NULL; training: raw pre-BN output)

@@ -13,9 +13,11 @@ device, each batch augmented there: unet_dc_segmentation_amd/device_data.py; wit
 their own size and every batch is S x S random windows).  The numbers of the reference's test section (:365-402, :452-467:
 best checkpoint reloaded, test loss / Dice / pixel accuracy, precision / recall / F1 / specificity / confusion matrix) are
 computed and printed (with ``--tta N`` on the network's mean over N flipped and rotated variants of every input, as is
-``--calibrate_thresh``: DESIGN.md section 17); its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
+``--calibrate_thresh``: DESIGN.md section 17); ``--weight_decay``, ``--clip_grad``, ``--ema`` and ``--lr_schedule`` add the usual
+fine-tuning recipe to the fused optimizer step (without them the run is the reference's Adam(lr)); its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
 """
 import argparse
+import contextlib
 import gc
 import os
 import time
@@ -46,6 +48,24 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--steps", type=int, default=0, help="max training steps per epoch (0 = all)")
     p.add_argument("--optimizer", default="hip", choices=["hip", "torch"],
                    help="Adam implementation on a GPU: hip = fused step + weight re-pack kernel, torch = torch.optim.Adam")
+    p.add_argument("--weight_decay", type=float, default=0.0, metavar="WD",
+                   help="decoupled weight decay (torch.optim.AdamW's rule) in the fused step, on the conv, transposed-conv and "
+                        "head weights; biases and the BatchNorm affine are left alone (DESIGN.md section 22); default 0")
+    p.add_argument("--decay_all", action="store_true", help="with --weight_decay: decay every parameter (torch's one-group AdamW)")
+    p.add_argument("--clip_grad", type=float, default=None, metavar="N",
+                   help="clip the global L2 norm of the gradient to N (torch.nn.utils.clip_grad_norm_'s rule; the norm stays on "
+                        "the device) and drop a step whose gradient holds an inf or a NaN; the epoch records gain "
+                        "grad_norm_mean, clipped_steps and skipped_steps")
+    p.add_argument("--ema", type=float, default=None, metavar="D",
+                   help="keep an exponential moving average of the weights with decay D (warm-up min(D, (1 + t) / (10 + t))); "
+                        "validation, early stopping, the saved checkpoint, the final test and --calibrate_thresh use the "
+                        "averaged weights")
+    p.add_argument("--lr_schedule", default="constant", choices=["constant", "cosine", "plateau"],
+                   help="cosine: per optimizer step over the planned steps of the run, down to --lr_min; plateau: "
+                        "ReduceLROnPlateau(mode='min', factor=0.5, patience=5) on the epoch's validation loss (the scheduler the "
+                        "reference declares); the epoch records gain lr")
+    p.add_argument("--warmup_steps", type=int, default=0, metavar="N", help="linear learning-rate warm-up over the first N steps")
+    p.add_argument("--lr_min", type=float, default=0.0, help="with --lr_schedule cosine / plateau: the floor of the rate")
     p.add_argument("--workers", type=int, default=4)
     p.add_argument("--device_data", action="store_true",
                    help="decode and preprocess every image once into a cache on the HIP device and augment each batch there "
@@ -198,6 +218,32 @@ def check_border_flags(parser, args):
         parser.error(f"--border_weight W0 / --border_sigma S / --border_radius R: {e}")
 
 
+def check_optim_flags(args):
+    """--weight_decay / --decay_all / --clip_grad / --ema / --lr_schedule / --warmup_steps / --lr_min: every refusal is raised
+    here, before any file is read.  -> True when one of the three optimizer flags is given (the recipe of FusedAdam)."""
+    recipe = [f for f, on in (("--weight_decay", args.weight_decay != 0.0), ("--clip_grad", args.clip_grad is not None),
+                              ("--ema", args.ema is not None)) if on]
+    if not args.weight_decay >= 0.0:
+        raise SystemExit(f"--weight_decay WD: WD must be >= 0, not {args.weight_decay}")
+    if args.decay_all and not args.weight_decay:
+        raise SystemExit("--decay_all needs --weight_decay")
+    if args.clip_grad is not None and not args.clip_grad > 0.0:
+        raise SystemExit(f"--clip_grad N: N must be > 0, not {args.clip_grad}")
+    if args.ema is not None and not 0.0 <= args.ema < 1.0:
+        raise SystemExit(f"--ema D: D must be in [0, 1), not {args.ema}")
+    if args.warmup_steps < 0:
+        raise SystemExit(f"--warmup_steps N: N must be >= 0, not {args.warmup_steps}")
+    if not 0.0 <= args.lr_min <= args.lr:
+        raise SystemExit(f"--lr_min: must be in 0..--lr, not {args.lr_min}")
+    if args.lr_min and args.lr_schedule == "constant":
+        raise SystemExit("--lr_min needs --lr_schedule cosine or plateau")
+    if recipe and args.optimizer == "torch":
+        raise SystemExit(f"{', '.join(recipe)}: weight decay, clipping and the EMA live in the fused optimizer step "
+                         "(unet_dc_segmentation_amd/optim.py) and cannot run with --optimizer torch; drop that flag "
+                         "(--optimizer hip is the default; on --device cpu it runs the same rules in PyTorch)")
+    return bool(recipe)
+
+
 class History(list):
     """Per-epoch records of main(); ``.test`` holds the held-out-split results of the final evaluation (None if skipped),
     ``.calibration`` the result of --calibrate_thresh (None without the flag), ``.tta`` the number of variants both were
@@ -325,6 +371,7 @@ def main(argv=None, parser=None):
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
+    recipe = check_optim_flags(args)
     if args.boundary is not None and not 1 <= args.boundary <= 64:
         raise SystemExit("--boundary R: R must be in 1..64")
     from utils.tta import TTA_SIZES
@@ -357,7 +404,13 @@ def main(argv=None, parser=None):
             return focal_dice_loss(pred, tgt, alpha=1.0, gamma=2.0, ratio=0.3, weight=border_weights(tgt, *border))
     # same update as the reference's torch.optim.Adam(lr) (train_DC_focal.py:224).  On the HIP path: one kernel that also
     # rewrites the packed weight images (unet_dc_segmentation_amd/optim.py); --optimizer torch keeps torch.optim.Adam
-    if device.type == "cuda" and args.optimizer == "hip":
+    if recipe:
+        # --weight_decay / --clip_grad / --ema: the recipe of the fused step; on CPU tensors the same
+        # class runs the same rules in PyTorch
+        from unet_dc_segmentation_amd.optim import FusedAdam
+        optimizer = FusedAdam(model, lr=args.lr, weight_decay=args.weight_decay, decay="all" if args.decay_all else "weights",
+                              clip_norm=args.clip_grad, ema_decay=args.ema)
+    elif device.type == "cuda" and args.optimizer == "hip":
         from unet_dc_segmentation_amd.optim import FusedAdam
         optimizer = FusedAdam(model, lr=args.lr)
     else:
@@ -400,6 +453,20 @@ def main(argv=None, parser=None):
         print(f"Training set: {len(train_ds)} images/rank, validation set: {len(val_ds)} images, "
               f"{world} rank(s), device {device}, compute {args.dtype}")
 
+    # learning-rate schedule: a host number set on the group before every step (the step kernel takes lr by value); None = the
+    # constant rate of the reference, nothing is touched
+    schedule, opt_step = None, 0
+    if args.lr_schedule != "constant" or args.warmup_steps:
+        from utils.lr_schedule import LRSchedule
+        per_epoch = min(len(train_loader), args.steps or len(train_loader))
+        try:
+            schedule = LRSchedule(args.lr_schedule, args.lr, args.epochs * per_epoch, args.warmup_steps, args.lr_min)
+        except ValueError as e:
+            raise SystemExit(f"--lr_schedule {args.lr_schedule}: {e}")
+    # --ema: validation, the checkpoint and the final evaluations read the averaged weights
+    ema_weights = optimizer.ema_weights if args.ema is not None else contextlib.nullcontext
+    stats_prev = dict(steps=0, clipped=0, skipped=0, norm_sum=0.0)
+
     best_dice, patience_counter = 0.0, 0
     saved_this_run = False          # the final test evaluation only reloads a checkpoint THIS run wrote
     history = History()
@@ -424,6 +491,9 @@ def main(argv=None, parser=None):
             loss.backward()
             if wrapper is not None and not images.is_cuda:
                 wrapper.sync_gradients()                    # ATen-CPU path: explicit all-reduce
+            if schedule is not None:
+                optimizer.param_groups[0]["lr"] = schedule.lr_at(opt_step)
+                opt_step += 1
             optimizer.step()
             with torch.no_grad():
                 tr_loss_t += loss.detach().double()
@@ -442,6 +512,15 @@ def main(argv=None, parser=None):
         nb = max(1, min(len(train_loader), args.steps or len(train_loader)))
         tr_loss, tr_dice, correct = float(tr_loss_t.item()), float(tr_dice_t.item()), int(correct_t.item())   # (waits for the epoch's work)
         dt = time.time() - t0
+        clip_rec = {}
+        if args.clip_grad is not None:
+            # one read of the optimizer's device record per epoch, next to the read-back above (the queue is drained anyway)
+            s = optimizer.recipe_stats()
+            s["norm_sum"] = (s["grad_norm_mean"] or 0.0) * (s["steps"] - s["skipped"])
+            done = (s["steps"] - s["skipped"]) - (stats_prev["steps"] - stats_prev["skipped"])
+            clip_rec = dict(grad_norm_mean=(s["norm_sum"] - stats_prev["norm_sum"]) / done if done else 0.0,
+                            clipped_steps=s["clipped"] - stats_prev["clipped"], skipped_steps=s["skipped"] - stats_prev["skipped"])
+            stats_prev = s
         # -------- validation --------
         if wrapper is not None:
             wrapper.broadcast_buffers()                     # rank 0's BatchNorm running statistics everywhere
@@ -450,7 +529,7 @@ def main(argv=None, parser=None):
         va_dice_t = torch.zeros((), dtype=torch.float64, device=device)
         vc_t = torch.zeros((), dtype=torch.int64, device=device)
         vt = 0
-        with torch.no_grad():
+        with torch.no_grad(), ema_weights():
             for batch in val_loader:
                 images, masks = batch[0].float().to(device), batch[1].float().to(device)
                 outputs = model(images)
@@ -466,6 +545,11 @@ def main(argv=None, parser=None):
                    images_per_sec=seen * world / max(dt, 1e-9))
         if args.crop is not None and train_loader.scaled:
             rec["fg_windows"] = int(train_loader.fg_windows)              # (this rank's windows)
+        if schedule is not None:
+            rec["lr"] = float(optimizer.param_groups[0]["lr"])            # the rate of the epoch's last step
+            # plateau: every rank steps on rank 0's validation loss, so all ranks keep the same rate
+            schedule.epoch_end(dpmod.broadcast_scalar(rec["val_loss"], device) if world > 1 else rec["val_loss"])
+        rec.update(clip_rec)
         if world > 1:
             # replicas must stay identical: one checksum per rank and epoch (compared by tests/test_dp_gloo.py)
             with torch.no_grad():
@@ -480,12 +564,18 @@ def main(argv=None, parser=None):
             print(f"Train Acc: {rec['train_acc']:.4f}, Val Acc: {rec['val_acc']:.4f} | {rec['images_per_sec']:.1f} img/s")
             if "fg_windows" in rec:
                 print(f"Foreground-centred windows: {rec['fg_windows']} of {seen}")
+            if "lr" in rec:
+                print(f"Learning rate: {rec['lr']:.3e}")
+            if "grad_norm_mean" in rec:
+                print(f"Gradient norm (mean): {rec['grad_norm_mean']:.4g}, clipped steps: {rec['clipped_steps']}, "
+                      f"skipped steps: {rec['skipped_steps']}")
             print("-------------------------------------------------------")
         if rec["val_dice"] > best_dice:
             best_dice, patience_counter = rec["val_dice"], 0
             saved_this_run = True       # (decided from rank 0's broadcast Dice: the same on every rank)
             if rank == 0:
-                torch.save(model.state_dict(), args.ckpt_path)
+                with ema_weights():                         # (--ema: the checkpoint holds the averaged weights)
+                    torch.save(model.state_dict(), args.ckpt_path)
                 print("Model saved!")
         else:
             patience_counter += 1
@@ -499,6 +589,7 @@ def main(argv=None, parser=None):
     if args.test_eval and len(test_ds) > 0:
         if saved_this_run and os.path.exists(args.ckpt_path):
             model.load_state_dict(torch.load(args.ckpt_path, map_location=device, weights_only=True))
+            ema_weights = contextlib.nullcontext            # (--ema: the checkpoint IS the averaged weights of the best epoch)
         elif rank == 0:
             # validation Dice never rose above 0: nothing was written by THIS run, and a file of that name left by an earlier
             # run (possibly another architecture) is not this run's result
@@ -507,7 +598,8 @@ def main(argv=None, parser=None):
             test_loader = DataLoader(test_ds, batch_size=args.batch, shuffle=False, num_workers=args.workers,
                                      pin_memory=pin)
         # every rank: same weights, same split
-        history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch, args.boundary)
+        with ema_weights():
+            history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch, args.boundary)
         if rank == 0:
             t = history.test
             print("========== Test Results ==========" + (f" (--tta {args.tta})" if args.tta != 1 else ""))
@@ -522,8 +614,9 @@ def main(argv=None, parser=None):
                 per_tol = ", ".join(f"nsd_{q} {b[f'nsd_{q}']:.4f}, bf_{q} {b[f'bf_{q}']:.4f}" for q in (1, 2, 3) if f"nsd_{q}" in b)
                 print(f"Boundary (--boundary {b['R']}, pooled): HD95 {b['hd95']:.3f} px, ASSD {b['assd']:.3f} px, {per_tol}")
     if args.calibrate_thresh is not None and len(val_ds) > 0:
-        history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device, args.tta,
-                                                    args.batch)             # every rank: same weights
+        with ema_weights():                                 # the weights the test evaluation used
+            history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device, args.tta,
+                                                        args.batch)         # every rank: same weights
         if rank == 0:
             c = history.calibration
             with_tta = f", --tta {args.tta}" if args.tta != 1 else ""

@@ -33,6 +33,9 @@ SIGNATURES = {
     "unetdc_pack_convT2x2": (I, [P, P, P, I, I, I, P]),
     "unetdc_pack_many": (I, [P, I, L, I, P]),
     "unetdc_adam_step": (I, [P, I, L, P, D, D, D, D, L, D, I, P]),
+    "unetdc_grad_norm_workspace": (L, [L]),
+    "unetdc_grad_norm": (I, [P, L, D, D, P, P, L, P]),
+    "unetdc_adam_step_ex": (I, [P, I, L, P, D, D, D, D, L, D, I, P, D, P, P, D, P]),
     "unetdc_conv3x3_stats_rows": (I, [L, I]),
     "unetdc_conv3x3_fwd": (I, [P, I, P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, P]),
     "unetdc_conv3x3_bnin_supported": (I, [I, I, I, I, I, I, I]),

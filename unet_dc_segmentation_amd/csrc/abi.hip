@@ -142,6 +142,23 @@ int unetdc_adam_step(const unetdc_adam_desc* table_dev, int n, int64_t total_blo
                           (hipStream_t)s);
 }
 
+int64_t unetdc_grad_norm_workspace(int64_t n) { return grad_norm_workspace_bytes((long)n); }
+
+int unetdc_grad_norm(const float* flat_grad, int64_t n, double grad_scale, double max_norm, unetdc_step_ctl* ctl_dev,
+                     void* workspace, int64_t workspace_bytes, unetdc_stream_t s) {
+  static_assert(sizeof(unetdc_step_ctl) == 56 && offsetof(unetdc_step_ctl, gscale_eff) == 16 &&
+                offsetof(unetdc_step_ctl, steps) == 24, "unetdc_step_ctl layout (mirrored by unet_dc_segmentation_amd/optim.py)");
+  return launch_grad_norm(flat_grad, (long)n, grad_scale, max_norm, ctl_dev, workspace, (long)workspace_bytes, (hipStream_t)s);
+}
+
+int unetdc_adam_step_ex(const unetdc_adam_desc* table_dev, int n, int64_t total_blocks, const float* flat_grad, double lr,
+                        double beta1, double beta2, double eps, int64_t step, double grad_scale, int dtype,
+                        const unetdc_step_ctl* ctl_dev, double weight_decay, float* ema_base, const float* m_base,
+                        double ema_decay, unetdc_stream_t s) {
+  return launch_adam_step_ex(table_dev, n, (long)total_blocks, flat_grad, lr, beta1, beta2, eps, (long)step, grad_scale, dtype,
+                             ctl_dev, weight_decay, ema_base, m_base, ema_decay, (hipStream_t)s);
+}
+
 int unetdc_conv3x3_stats_rows(int64_t npixels, int cout) { return igemm_mblocks((long)npixels, cout); }
 
 int unetdc_conv3x3_fwd(const void* x, int ldx, const void* w_fwd, const float* bias, const float* scale,

@@ -246,6 +246,13 @@ int launch_pack_convT2x2(const float* w, void* wf, void* wd, int Ci, int Co, int
 int launch_pack_many(const void* table_dev, int n, long total, int dtype, hipStream_t stream);
 int launch_adam_step(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
                      double beta2, double eps, long step, double grad_scale, int dtype, hipStream_t stream);   // optim.hip
+// the optimizer recipe: global gradient norm -> unetdc_step_ctl, and the step that reads it
+long grad_norm_workspace_bytes(long n);                     // 0 for n <= 0
+int launch_grad_norm(const float* flat_grad, long n, double grad_scale, double max_norm, void* ctl_dev, void* workspace,
+                     long workspace_bytes, hipStream_t stream);
+int launch_adam_step_ex(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
+                        double beta2, double eps, long step, double grad_scale, int dtype, const void* ctl_dev,
+                        double weight_decay, float* ema_base, const float* m_base, double ema_decay, hipStream_t stream);
 int launch_stats_colsum(const float* parts, int nparts, int ctotal, int c0, int c, float* out, hipStream_t stream);
 int launch_channel_sum(const void* x, int ldx, float* out, void* workspace, long workspace_bytes, long P, int C,
                        int dtype, hipStream_t stream);

@@ -11,6 +11,12 @@
 // the parameter's own contiguous rows, writes p, m, v back in place and the two packed images from an LDS copy of the
 // NEW p -- or 4096 consecutive elements of an unpacked tensor (biases, BatchNorm affine, first layer, head).
 // HBM-bound: 28 bytes per parameter + 4 (bf16) / 8 (fp32) for the images; nothing else reads the parameters per step.
+//
+// The recipe around it: unetdc_grad_norm takes the global L2 norm of the flat gradient buffer in two
+// launches (fp64 partials in a fixed order, then a one-workgroup finaliser) and leaves the clipping coefficient, the
+// non-finite guard and the running counters in a device-resident record (unetdc_step_ctl); unetdc_adam_step_ex is the
+// EX = true instantiation of the step kernel: it reads that record (a skipped step touches nothing), applies decoupled
+// weight decay to the flagged descriptors and keeps an exponential moving average of the new parameters.
 #include "kernels.h"
 
 namespace unetdc {
@@ -26,12 +32,22 @@ struct AdamDesc {
   long numel;
   int a, b;            // conv3x3: (Cout, Cin); convT: (Cin, Cout); plain: unused
   int kind;            // 0 conv3x3 packed, 1 convT2x2 packed, 2 plain
-  int pad;
+  int flags;           // bit 0: decoupled weight decay applies (unetdc_adam_step_ex only; unetdc_adam_step ignores the word)
 };
 static_assert(sizeof(AdamDesc) == 80, "AdamDesc layout (mirrored by unet_dc_segmentation_amd/optim.py)");
 
 struct AdamHyper {
   float b2, omb1, omb2, eps, step_size, inv_bc2_sqrt, gscale;   // omb = 1 - beta, formed in double on the host like torch does
+};
+
+// unetdc_adam_step_ex: the plain hyper-parameters (gscale replaced by the record's gscale_eff when ctl is set) and the recipe
+struct AdamHyperEx {
+  AdamHyper h;
+  const unetdc_step_ctl* ctl;   // nullable: no norm pass ran, gscale stands
+  float decay;                  // 1 - lr * weight_decay, formed in double on the host
+  float omd;                    // 1 - ema_decay, likewise
+  float* ema_base;              // nullable; the EMA of a tensor lives at ema_base + (d.m - m_base)
+  const float* m_base;
 };
 
 __device__ __forceinline__ float adam_update(float& p, float& m, float& v, float g, const AdamHyper& h) {
@@ -43,12 +59,40 @@ __device__ __forceinline__ float adam_update(float& p, float& m, float& v, float
   return p;
 }
 
-template <typename T>
+// One element: p, m, v read, updated and written back in place; the new p is returned.  EX: the decay factor first (its own
+// rounding, never contracted into the update), the moving average e <- e + (1 - d)(p_new - e) last.
+template <bool EX, typename H>
+__device__ __forceinline__ float adam_elem(const AdamDesc& d, float* e, long i, float g, const AdamHyper& hh, const H& h,
+                                           bool decay) {
+  float p = d.p[i], m = d.m[i], v = d.v[i];
+  if constexpr (EX) {
+    if (decay) p = __fmul_rn(p, h.decay);
+  }
+  adam_update(p, m, v, g, hh);
+  d.p[i] = p; d.m[i] = m; d.v[i] = v;
+  if constexpr (EX) {
+    if (e) { const float e0 = e[i]; e[i] = fmaf(h.omd, p - e0, e0); }
+  }
+  return p;
+}
+
+template <typename T, bool EX>
 __global__ __launch_bounds__(256) void adam_pack_kernel(const AdamDesc* __restrict__ table, int n,
-                                                        const float* __restrict__ flat_grad, const AdamHyper h) {
+                                                        const float* __restrict__ flat_grad,
+                                                        const std::conditional_t<EX, AdamHyperEx, AdamHyper> h) {
   __shared__ float tile[32 * 289];
   const int tid = threadIdx.x;
   const long tix = blockIdx.x;
+  AdamHyper hh;
+  if constexpr (EX) {
+    hh = h.h;
+    if (h.ctl) {                                 // every workgroup reads the record once; a skipped step touches nothing
+      if (h.ctl->skip) return;
+      hh.gscale = h.ctl->gscale_eff;
+    }
+  } else {
+    hh = h;
+  }
   int lo = 0, hi = n - 1;                      // last descriptor with begin <= tix
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -57,16 +101,18 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(const AdamDesc* __restri
   const AdamDesc d = table[lo];
   const long local = tix - d.begin;
   const float* g = flat_grad + d.g_off;
+  float* e = nullptr;
+  bool decay = false;
+  if constexpr (EX) {
+    if (h.ema_base) e = h.ema_base + (d.m - h.m_base);
+    decay = (d.flags & 1) != 0;
+  }
   if (d.kind == 2) {
     const long i0 = local * 4096;
 #pragma unroll 4
     for (int k = 0; k < 16; ++k) {
       const long i = i0 + k * 256 + tid;
-      if (i < d.numel) {
-        float p = d.p[i], m = d.m[i], v = d.v[i];
-        adam_update(p, m, v, g[i], h);
-        d.p[i] = p; d.m[i] = m; d.v[i] = v;
-      }
+      if (i < d.numel) adam_elem<EX>(d, e, i, g[i], hh, h, decay);
     }
     return;
   }
@@ -78,9 +124,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(const AdamDesc* __restri
     for (int i = tid; i < 32 * 288; i += 256) {            // w[co][ci0 .. ci0+31][9]: 288 contiguous floats
       const int co = i / 288, rem = i - co * 288;
       const long gi = ((long)(co0 + co) * Ci + ci0) * 9 + rem;
-      float p = d.p[gi], m = d.m[gi], v = d.v[gi];
-      tile[co * 289 + rem] = adam_update(p, m, v, g[gi], h);
-      d.p[gi] = p; d.m[gi] = m; d.v[gi] = v;
+      tile[co * 289 + rem] = adam_elem<EX>(d, e, gi, g[gi], hh, h, decay);
     }
     if (!wf) return;
     __syncthreads();
@@ -95,9 +139,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(const AdamDesc* __restri
     for (int i = tid; i < 32 * 128; i += 256) {            // w[ci][co0 .. co0+31][4]: 128 contiguous floats
       const int ci = i >> 7, rem = i & 127;
       const long gi = ((long)(ci0 + ci) * Co + co0) * 4 + rem;
-      float p = d.p[gi], m = d.m[gi], v = d.v[gi];
-      tile[ci * 129 + rem] = adam_update(p, m, v, g[gi], h);
-      d.p[gi] = p; d.m[gi] = m; d.v[gi] = v;
+      tile[ci * 129 + rem] = adam_elem<EX>(d, e, gi, g[gi], hh, h, decay);
     }
     if (!wf) return;
     __syncthreads();
@@ -109,25 +151,153 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(const AdamDesc* __restri
   }
 }
 
-int launch_adam_step(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
-                     double beta2, double eps, long step, double grad_scale, int dtype, hipStream_t stream) {
+// ---- global gradient norm -> step-control record ----------------------------------------------------------------------
+// First stage: a workgroup covers GN_BLOCK consecutive elements per trip (256 threads x GN_UNROLL 16-byte loads) and walks
+// the buffer with the stride of the grid, which is capped at GN_MAX_PARTS: the finaliser reads every partial itself.  Every
+// product (double)g * (double)g is exact; the sums are fp64 in a fixed order (thread, then the wave's shuffle tree, then the
+// four waves in order), so the record is bitwise reproducible.  The <= 3 elements behind the last full vector go to
+// workgroup 0.  An inf or NaN anywhere makes the sum non-finite: that IS the guard.
+constexpr int GN_UNROLL = 4, GN_BLOCK = 256 * 4 * GN_UNROLL, GN_MAX_PARTS = 2048;
+
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ parts) {
+  __shared__ double red[4];
+  const long nvec = n >> 2;
+  double s = 0.0;
+  for (long v0 = (long)blockIdx.x * (GN_BLOCK / 4); v0 < nvec; v0 += (long)gridDim.x * (GN_BLOCK / 4)) {
+    f32x4 t[GN_UNROLL];
+#pragma unroll
+    for (int k = 0; k < GN_UNROLL; ++k) {
+      const long vi = v0 + k * 256 + threadIdx.x;
+      t[k] = vi < nvec ? *reinterpret_cast<const f32x4*>(g + 4 * vi) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < GN_UNROLL; ++k)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const double x = (double)t[k][c];
+        s += x * x;
+      }
+  }
+  if (blockIdx.x == 0) {
+    const long i = 4 * nvec + threadIdx.x;
+    if (i < n) {
+      const double x = (double)g[i];
+      s += x * x;
+    }
+  }
+  s = block_sum_f64(s, red);
+  if (threadIdx.x == 0) parts[blockIdx.x] = s;
+}
+
+// One workgroup: thread t takes partials t, t + 256, ...; then the rules of unetdc_step_ctl (include/unetdc_hip.h), in fp64.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double* __restrict__ parts, int nparts, double grad_scale,
+                                                                 double max_norm, unetdc_step_ctl* ctl) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += parts[i];
+  s = block_sum_f64(s, red);
+  if (threadIdx.x != 0) return;
+  const double sumsq = (s * grad_scale) * grad_scale;
+  const double norm = sqrt(sumsq);
+  // a class test, not `sumsq - sumsq == 0`: hipcc contracts that difference with the product above into one fma, which
+  // yields the product's rounding error instead of zero
+  const bool finite = __builtin_isfinite(sumsq);
+  double coef = 1.0;
+  if (finite && max_norm > 0.0) coef = fmin(1.0, max_norm / (norm + 1e-6));
+  ctl->sumsq = sumsq;
+  ctl->norm = norm;
+  ctl->gscale_eff = finite ? (float)(grad_scale * coef) : 0.f;
+  ctl->skip = finite ? 0 : 1;
+  ctl->steps += 1;
+  if (finite) {
+    ctl->norm_sum += norm;
+    if (coef < 1.0) ctl->clipped += 1;
+  } else {
+    ctl->skipped += 1;
+  }
+}
+
+long grad_norm_workspace_bytes(long n) {
+  if (n <= 0) return 0;
+  return 8 * std::min((n + GN_BLOCK - 1) / GN_BLOCK, (long)GN_MAX_PARTS);
+}
+
+int launch_grad_norm(const float* flat_grad, long n, double grad_scale, double max_norm, void* ctl_dev, void* workspace,
+                     long workspace_bytes, hipStream_t stream) {
+  UNETDC_REQUIRE(flat_grad && ctl_dev && workspace, "grad_norm: null pointer");
+  UNETDC_REQUIRE((reinterpret_cast<uintptr_t>(flat_grad) & 15) == 0, "grad_norm: flat_grad is not 16-byte aligned");
+  UNETDC_REQUIRE(((reinterpret_cast<uintptr_t>(ctl_dev) | reinterpret_cast<uintptr_t>(workspace)) & 7) == 0,
+                 "grad_norm: ctl_dev / workspace are not 8-byte aligned");
+  UNETDC_REQUIRE(n > 0, "grad_norm: n = %ld, nothing to sum", n);
+  UNETDC_REQUIRE(__builtin_isfinite(grad_scale) && max_norm == max_norm, "grad_norm: grad_scale / max_norm not finite");
+  const long need = grad_norm_workspace_bytes(n);
+  if (int rc = require_workspace("grad_norm", workspace_bytes, need)) return rc;
+  const int nparts = (int)(need / 8);
+  double* parts = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nparts), dim3(256), 0, stream, flat_grad, n, parts);
+  int rc = check_launch("grad_sumsq_kernel");
+  if (rc != UNETDC_OK) return rc;
+  hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, stream, parts, nparts, grad_scale, max_norm,
+                     reinterpret_cast<unetdc_step_ctl*>(ctl_dev));
+  return check_launch("grad_norm_finalize_kernel");
+}
+
+// ---- the step ---------------------------------------------------------------------------------------------------------
+static int adam_hyper(AdamHyper& h, const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr,
+                      double beta1, double beta2, double eps, long step, double grad_scale, int dtype) {
   UNETDC_REQUIRE(table_dev && flat_grad && n > 0 && total_blocks > 0 && total_blocks < (1L << 31), "adam_step: empty table");
   UNETDC_REQUIRE(dtype == UNETDC_F32 || dtype == UNETDC_BF16, "adam_step: bad dtype %d", dtype);
   UNETDC_REQUIRE(step >= 1 && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0.,
                  "adam_step: bad hyper-parameters");
   // bias corrections in double like torch (1 - beta ** step), then rounded once
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  AdamHyper h;
   h.b2 = (float)beta2; h.omb1 = (float)(1.0 - beta1); h.omb2 = (float)(1.0 - beta2); h.eps = (float)eps;
   h.gscale = (float)grad_scale;
   h.step_size = (float)(lr / bc1);
   h.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  return UNETDC_OK;
+}
+
+int launch_adam_step(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
+                     double beta2, double eps, long step, double grad_scale, int dtype, hipStream_t stream) {
+  AdamHyper h;
+  if (int rc = adam_hyper(h, table_dev, n, total_blocks, flat_grad, lr, beta1, beta2, eps, step, grad_scale, dtype)) return rc;
   const AdamDesc* t = reinterpret_cast<const AdamDesc*>(table_dev);
   if (dtype == UNETDC_BF16)
-    hipLaunchKernelGGL(adam_pack_kernel<bf16_t>, dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, h);
+    hipLaunchKernelGGL((adam_pack_kernel<bf16_t, false>), dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, h);
   else
-    hipLaunchKernelGGL(adam_pack_kernel<float>, dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, h);
+    hipLaunchKernelGGL((adam_pack_kernel<float, false>), dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, h);
   return check_launch("adam_pack_kernel");
+}
+
+int launch_adam_step_ex(const void* table_dev, int n, long total_blocks, const float* flat_grad, double lr, double beta1,
+                        double beta2, double eps, long step, double grad_scale, int dtype, const void* ctl_dev,
+                        double weight_decay, float* ema_base, const float* m_base, double ema_decay, hipStream_t stream) {
+  AdamHyperEx x;
+  if (int rc = adam_hyper(x.h, table_dev, n, total_blocks, flat_grad, lr, beta1, beta2, eps, step, grad_scale, dtype)) return rc;
+  UNETDC_REQUIRE((reinterpret_cast<uintptr_t>(ctl_dev) & 7) == 0, "adam_step_ex: ctl_dev is not 8-byte aligned");
+  UNETDC_REQUIRE(weight_decay >= 0. && lr * weight_decay < 1., "adam_step_ex: weight_decay must be in [0, 1 / lr)");
+  UNETDC_REQUIRE(!ema_base || (m_base && ema_decay >= 0. && ema_decay <= 1.),
+                 "adam_step_ex: the EMA needs m_base and a decay in [0, 1]");
+  x.ctl = reinterpret_cast<const unetdc_step_ctl*>(ctl_dev);
+  x.decay = (float)(1.0 - lr * weight_decay);          // torch.optim.AdamW: param.mul_(1 - lr * weight_decay)
+  x.omd = ema_base ? (float)(1.0 - ema_decay) : 0.f;
+  x.ema_base = ema_base;
+  x.m_base = m_base;
+  const AdamDesc* t = reinterpret_cast<const AdamDesc*>(table_dev);
+  if (dtype == UNETDC_BF16)
+    hipLaunchKernelGGL((adam_pack_kernel<bf16_t, true>), dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, x);
+  else
+    hipLaunchKernelGGL((adam_pack_kernel<float, true>), dim3((unsigned)total_blocks), dim3(256), 0, stream, t, n, flat_grad, x);
+  return check_launch("adam_pack_kernel<ex>");
 }
 
 }  // namespace unetdc
