@@ -592,6 +592,35 @@ int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, 
                        unetdc_stream_t s);
 
 
+/* ---- per-droplet confidence and TTA disagreement (confidence.hip; the definition is DESIGN.md section 23) -------------------
+ * unetdc_label_confidence: label ([h][w] int32: 0 = background, droplets 1..max_out; any label map, touching labels allowed),
+ *   probs ([ph][pw] fp32) and optionally the envelope lo, hi ([ph][pw] fp32 each: the per-pixel minimum and maximum over the
+ *   variants of unetdc_dihedral_mean_env_f32; both NULL or both given).  Pixel (y, x) reads the planes at
+ *   (min(floor(y * ph / h), ph - 1), min(floor(x * pw / w), pw - 1)), the index rule of unetdc_mask_from_probs.  Per pixel:
+ *     q = rint(clamp(p, 0, 1) * 65535), the product in fp32, ties to even, a NaN gives 0; H = entropy_table[q] (uint16 [65536],
+ *     utils.droplet_confidence.entropy_table: rint(65535 * binary entropy in bits)); uncertain = |q - q(thresh)| <= q(band);
+ *     spread = q(hi) - q(lo); unstable = !(lo > thresh) && hi > thresh.
+ *   -> out[UNETDC_CONF_QUANTITIES][max_out] int64, row j of droplet k at out[j * max_out + k - 1]:
+ *     0 n, 1 Sq, 2 Sqq (sums of 1, q, q^2), 3 min_q, 4 max_q, 5 n_band (uncertain pixels), 6 Sh (sum of H),
+ *     7 Sspread, 8 max_spread, 9 n_unstable
+ *   Every row is initialised for all max_out droplets: sums and counts 0, minima INT64_MAX, maxima -1; that is what a number
+ *   without pixels keeps, and what rows 7..9 keep without an envelope.  Labels below 1 or above max_out are skipped there.
+ *   -> out_image[UNETDC_CONF_IMAGE_QUANTITIES] int64 (required): 0 n_px (= h * w), 1 n_fg (label > 0, whatever max_out),
+ *     2 Sh_all, 3 Sh_fg (H over all / foreground pixels), 4 n_band_all, 5 n_band_fg, 6 n_unstable_all, 7 Sspread_all (6 and 7
+ *     stay 0 without an envelope).
+ *   -> out_entropy_u8, out_spread_u8 ([h][w] uint8, each nullable): H >> 8 and spread >> 8; the spread map needs an envelope.
+ *   out may be NULL when max_out == 0.  Sides 1..16384 with h * w < 2^30; ph, pw >= 1; 0 <= band <= 0.5.  No workspace; nothing
+ *   but the outputs is written, and they may hold anything on entry.  Integer atomics only: bitwise reproducible.
+ *   UNETDC_EINVAL before any launch: a null pointer, one of lo / hi alone, a spread map without an envelope, a side or band
+ *   outside the limits. */
+#define UNETDC_CONF_QUANTITIES 10
+#define UNETDC_CONF_IMAGE_QUANTITIES 8
+int unetdc_label_confidence(const int32_t* label, int max_out, int h, int w, const float* probs, const float* lo,
+                            const float* hi, int ph, int pw, float thresh, float band, const uint16_t* entropy_table,
+                            int64_t* out, int64_t* out_image, uint8_t* out_entropy_u8, uint8_t* out_spread_u8,
+                            unetdc_stream_t s);
+
+
 /* ---- overlap table of two label maps (match.hip; the definition is DESIGN.md section 12) ------------------------------------
  * unetdc_label_overlap: label_a, label_b ([h][w] int32 each: 0 = background, objects 1..max_a and 1..max_b; any label maps,
  *   touching labels allowed) -> the triples (a, b, n) with n > 0 = the number of pixels that carry label a on the first map
@@ -733,11 +762,17 @@ int unetdc_tile_blend_f32(const float* tile_probs, int t, int overlap, const int
  * unetdc_dihedral_mean_f32: p ([n * nvar][s][s] fp32) -> out ([n][s][s] fp32): per pixel acc = q_0, then acc = acc + q_i in list
  *   order, every add rounded in fp32, then one IEEE division by float(nvar); q_i is item b * nvar + i mapped back through the
  *   inverse of variant list[i].  nvar == 1 copies the input bits.
- * Both: nothing but out is written; no workspace, no allocation, no host wait, no atomics; launches on the given stream only;
+ * unetdc_dihedral_mean_env_f32: the same mean into out_mean, bit for bit, and from the same pass out_lo / out_hi ([n][s][s] fp32
+ *   each): the minimum / maximum of the q_i (fminf / fmaxf: numpy's minimum / maximum on inputs without a NaN).  lo <= hi holds;
+ *   lo <= mean <= hi does not (the rounded fp32 mean of equal values may miss them).  Every buffer 16-byte aligned; no output
+ *   may overlap the input or another output.
+ * All: nothing but the outputs is written; no workspace, no allocation, no host wait, no atomics; launches on the given stream only;
  * two runs are bitwise equal.  UNETDC_EINVAL before any launch: a null pointer, s, n, c or nvar outside the limits above, a
  * buffer that is not 16-byte aligned, out overlapping the input. */
 int unetdc_dihedral_expand_f32(const float* x, int n, int c, int s, int nvar, float* out, unetdc_stream_t stream);
 int unetdc_dihedral_mean_f32(const float* p, int n, int s, int nvar, float* out, unetdc_stream_t stream);
+int unetdc_dihedral_mean_env_f32(const float* p, int n, int s, int nvar, float* out_mean, float* out_lo, float* out_hi,
+                                 unetdc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ and a few integers per droplet come back:
     --density_maps    unet_dc_segmentation_amd/density.py       csrc/density.hip        CPU: utils/density.py
     --neighbors       (droplets.py)                             csrc/neighbors.hip      CPU: utils/droplet_neighbors.py
     --boundary        unet_dc_segmentation_amd/evaluate.py      csrc/boundary.hip       CPU: utils/droplet_boundary.py
+    --confidence      (droplets.py, tta.py)                     csrc/confidence.hip tta.hip  CPU: utils/droplet_confidence.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -101,13 +102,22 @@ class Run:
     neighbors: int | None = None       # --neighbors: the contact radius in pixels
     contact_tables: list = dataclasses.field(default_factory=list)  # droplet_contacts.csv, one table per image
     boundary: dict | None = None       # boundary_options(); its "records" collect boundary_per_image.csv
+    confidence: dict | None = None     # confidence_options(); its "rows" collect confidence_per_image.csv
 
-    def droplet_options(self, labels, shape):
+    @property
+    def envelope(self):
+        """Whether the forward also keeps the minimum and maximum over the variants: only with both --tta and --confidence."""
+        return self.tta is not None and self.confidence is not None
+
+    def droplet_options(self, labels, shape, confidence=False):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
-        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors selects it by itself."""
+        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors and --confidence select it by
+        themselves."""
         c = self.clean or {"low": None, "holes": 0}
-        return DropletOptions(self.split_depth, shape or (labels and self.split_depth is None and self.neighbors is None), labels,
-                              c["low"], c["holes"], self.neighbors)
+        conf = self.confidence if confidence else None
+        route = self.split_depth is None and self.neighbors is None and conf is None
+        return DropletOptions(self.split_depth, shape or (labels and route), labels, c["low"], c["holes"], self.neighbors,
+                              None if conf is None else conf["band"], conf is not None and conf["maps"])
 
     def submit(self, fn, *args):
         """PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
@@ -127,9 +137,10 @@ class Batch:
 
 def predict_tiled_image(model, im, run):
     """--tile: decoded image -> (probabilities [1, 1, H, W] at the image's own size, the original image for the density maps or
-    None).  Preprocessing is the rolling ball alone, at native size; then the tiles, run.batch_size per forward, and the blend.
-    With --tta every tile's probabilities are the mean over its variants."""
-    more = {} if run.tta is None else {"tta": run.tta["N"]}
+    None); with --tta and --confidence the probabilities are the triple (mean, lo, hi) of that shape.  Preprocessing is the
+    rolling ball alone, at native size; then the tiles, run.batch_size per forward, and the blend.  With --tta every tile's
+    probabilities are the mean over its variants."""
+    more = {} if run.tta is None else {"tta": run.tta["N"], "envelope": True} if run.envelope else {"tta": run.tta["N"]}
     tile, radius, keep_rgb = run.tile, run.background_radius, run.density is not None
     if DEVICE == "cuda":
         from unet_dc_segmentation_amd.preprocess import MAX_ELEMENT, _upload, rolling_ball_device
@@ -138,10 +149,11 @@ def predict_tiled_image(model, im, run):
         rgb = _upload(im, DEVICE) if keep_rgb or not host_ball else None
         corrected = (_upload(rolling_ball_correction_rgb(im, int(radius)), DEVICE) if host_ball
                      else rolling_ball_device(rgb, radius))
-        return predict_tiled(model, corrected, tile["T"], tile["O"], run.batch_size, **more)[None, None], rgb
+        p = predict_tiled(model, corrected, tile["T"], tile["O"], run.batch_size, **more)
+        return (tuple(q[None, None] for q in p) if run.envelope else p[None, None]), rgb
     from utils.tiling import predict_tiled_cpu
     p = predict_tiled_cpu(model, rolling_ball_correction_rgb(im, radius), tile["T"], tile["O"], run.batch_size, **more)
-    return torch.from_numpy(p)[None, None], (im if keep_rgb else None)
+    return (tuple(torch.from_numpy(q)[None, None] for q in p) if run.envelope else torch.from_numpy(p)[None, None]), (im if keep_rgb else None)
 
 
 def _droplet_table(area, cen_row, cen_col, px_per_um):
@@ -186,34 +198,40 @@ def _components(bin_mask, min_area):
     return area, cen[:, 0], cen[:, 1]
 
 
-def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None):
+def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None, confidence=None):
     """CPU path: the record that droplets.mask_and_droplets_batch returns per image, in host arrays, from the uint8 mask at
     the image's size.  split_depth: the split droplets (utils/droplet_split.py); shape: the integers of
     utils.droplet_shape.label_props_numpy on the label map and the grey plane, centroids then the integer sums over the
     area as on the device; labels: the int32 label map whose numbers are the rows of the table; neighbors (a radius): the
-    record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well."""
+    record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well; confidence
+    (the keywords probs, thresh, band, lo, hi, maps of utils.droplet_confidence.confidence_numpy): its record on the label map."""
     lab = None
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
         lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
-    elif shape or labels or neighbors is not None:
+    elif shape or labels or neighbors is not None or confidence is not None:
         from utils.droplet_match import gt_labels_numpy
         lab = gt_labels_numpy(bin_mask, min_area)
     if shape:
         from utils.droplet_shape import label_props_numpy
         props = label_props_numpy(lab, gray)
         area, sy, sx = props["area"], props["Sy"], props["Sx"]
-    elif split_depth is None and neighbors is not None:
+    elif split_depth is None and (neighbors is not None or confidence is not None):
         from utils.droplet_match import label_sums
         area, sy, sx = label_sums(lab)
     elif split_depth is None:
         return Droplets(bin_mask, *_components(bin_mask, min_area), labels=lab)
     d = np.maximum(area, 1)
-    nb = None
+    nb = conf = None
     if neighbors is not None:
         from utils.droplet_neighbors import neighbors_numpy
         nb = neighbors_numpy(lab, len(area), neighbors)
-    return Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None, neighbors=nb)
+    if confidence is not None:
+        from utils.droplet_confidence import confidence_numpy
+        conf = confidence_numpy(lab, max_out=len(area), **confidence)
+    out = Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None, neighbors=nb)
+    out.confidence = conf
+    return out
 
 
 def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
@@ -298,6 +316,24 @@ def add_neighbor_outputs(run, df, d, filename):
     return df, dn.summary(pairs, rec)
 
 
+def add_confidence_outputs(run, df, d, filename, name):
+    """--confidence: the columns of utils.droplet_confidence.confidence_columns behind the droplet table's own, this image's row
+    of confidence_per_image.csv, and with --confidence_maps the two map PNGs through the writer pool."""
+    from utils import droplet_confidence as dc
+    rec = d.confidence
+    if not df.empty:
+        df = pd.concat([df, pd.DataFrame(dc.confidence_columns(rec), index=df.index)], axis=1)
+    run.confidence["rows"].append({"filename": filename, **dc.image_columns(rec)})
+    for key, suffix in (("entropy_u8", "entropy"), ("spread_u8", "spread")):
+        if rec.get(key) is not None:
+            run.submit(_write_map, _host(rec[key]), run.out_dir / f"{name}_{suffix}.png")
+    return df
+
+
+def _write_map(plane, path):
+    Image.fromarray(plane).save(str(path))
+
+
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
     """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
     split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
@@ -358,22 +394,26 @@ def _cpu_mask(p2, thresh, hw, clean):
     return clean_mask(mask, weak, clean["holes"])
 
 
-def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
+def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=None):
     """The droplet stage at one threshold, and with --gt_dir the matching of its label maps against the batch's annotations
     -> (one Droplets per image, one match result per image or None, the density stage's device sums or None).  On the
     device the whole batch is enqueued back to back with ONE host wait (droplets.py), and one more for the matching; on the
     CPU the same records come from droplets_cpu and match_cpu.  sweeping: a threshold of --sweep_objects, where only the
     matching is read: no shape columns, no grey planes, no boundary distances.  With --boundary every match result carries the
-    record of DESIGN.md section 21 under "boundary" (device: one more batch of launches and one more wait, evaluate.boundary_batch)."""
+    record of DESIGN.md section 21 under "boundary" (device: one more batch of launches and one more wait, evaluate.boundary_batch).
+    With --confidence (never while sweeping) every Droplets carries the record of DESIGN.md section 23; envelope: the (lo, hi) maps
+    of --tta, shaped like probs."""
     gt, hws = run.gt, [m[1] for m in batch.meta]
     radius = run.boundary["R"] if run.boundary is not None and not sweeping else None
     want_labels = gt is not None or run.split_depth is not None
     shape = run.shape and not sweeping
+    conf = run.confidence if not sweeping else None
     if probs.is_cuda:
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
         gray = [torch.from_numpy(g).to(DEVICE) for g in batch.grays] if shape else None   # up behind the network's launches
+        more = {} if conf is None or envelope is None else {"envelope": tuple(e[:, 0] for e in envelope)}
         out, sums = mask_and_droplets_batch(probs[:, 0], thresh, hws, run.min_area, keep_sums=True, gray=gray,
-                                            options=run.droplet_options(want_labels, shape))
+                                            options=run.droplet_options(want_labels, shape, conf is not None), **more)
         if gt is None:
             return out, None, sums
         from unet_dc_segmentation_amd.evaluate import boundary_batch, match_batch
@@ -389,7 +429,11 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False):
     out, p = [], probs[:, 0].numpy()
     for i, hw in enumerate(hws):
         mask, counts = _cpu_mask(p[i], thresh, hw, run.clean)
-        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors)
+        ckw = None
+        if conf is not None:
+            lo, hi = (None, None) if envelope is None else (e[i, 0].numpy() for e in envelope)
+            ckw = {"probs": p[i], "thresh": thresh, "band": conf["band"], "lo": lo, "hi": hi, "maps": conf["maps"]}
+        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors, ckw)
         d.clean_counts = np.asarray(counts, np.int64)
         out.append(d)
     if gt is None:
@@ -419,14 +463,15 @@ def sweep_step(run, batch, probs):
 @torch.no_grad()
 def run_batch(run, batch, model):
     x = torch.stack(batch.tensors).to(DEVICE)
+    more = {"envelope": True} if run.envelope else {}    # --tta with --confidence: (mean, lo, hi) from the same launch
     if run.tta is None:
         probs = model(x)                                 # sigmoid probabilities (model_2.py:80)
     elif x.is_cuda:                                      # --tta: the mean over the variants, tta["batch"] items per forward
         from unet_dc_segmentation_amd.tta import predict_tta
-        probs = predict_tta(model, x, run.tta["N"], run.tta["batch"])
+        probs = predict_tta(model, x, run.tta["N"], run.tta["batch"], **more)
     else:
         from utils.tta import predict_tta_cpu
-        probs = predict_tta_cpu(model, x, run.tta["N"], run.tta["batch"])
+        probs = predict_tta_cpu(model, x, run.tta["N"], run.tta["batch"], **more)
     finish_batch(run, batch, probs)
 
 
@@ -437,10 +482,14 @@ def _host(x):
 def finish_batch(run, batch, probs):
     """Everything behind the forward: probs [B, 1, ph, pw] (on the device or not) -> masks of the sizes in batch.meta, droplet
     tables, the optional stages and the per-image files.  run_batch feeds it the network-size maps, --tile one native-size map
-    per image (ph, pw equal to the image's size: every resize rule is then the identity)."""
+    per image (ph, pw equal to the image's size: every resize rule is then the identity).  probs may be the triple (mean, lo,
+    hi) of --tta with --confidence: every stage reads the mean, the confidence stage the envelope as well."""
+    envelope = None
+    if isinstance(probs, tuple):
+        probs, envelope = probs[0], probs[1:]
     if run.sweep is not None:                            # --thresh_sweep: the raw mask at every threshold, pooled
         sweep_step(run, batch, probs)
-    out, mres, sums = droplets_and_matches(run, batch, probs, run.thresh)
+    out, mres, sums = droplets_and_matches(run, batch, probs, run.thresh, envelope=envelope)
     dres = None
     if run.density is not None and probs.is_cuda:
         from unet_dc_segmentation_amd.density import density_maps_batch
@@ -460,6 +509,8 @@ def finish_batch(run, batch, probs):
         more = {}
         if run.neighbors is not None:
             df, more = add_neighbor_outputs(run, df, d, filename)
+        if run.confidence is not None:
+            df = add_confidence_outputs(run, df, d, filename, name)
         if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
             run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
@@ -563,6 +614,17 @@ def build_parser():
                         "recall, F and surface Dice (nsd), one row per image and the pooled row ALL")
     p.add_argument("--boundary_tol", metavar="T[,T...]",
                    help="with --boundary: the integer pixel tolerances of the surface Dice columns (0..R, default 1,2,3)")
+    p.add_argument("--confidence", type=float, nargs="?", const=0.1, metavar="BAND",
+                   help="per-droplet confidence: adds prob_mean, prob_std, prob_min, prob_max, entropy_mean (bits) and "
+                        "uncertain_frac (pixels whose probability lies within BAND of --prob_thresh; BAND in 0..0.5, 0.1 without "
+                        "BAND -- a convention, not a measured number) to the droplet tables, and with --tta the disagreement of "
+                        "the variants: tta_spread_mean, tta_spread_max, unstable_frac (pixels some variants put above the "
+                        "threshold and some not).  Writes confidence_per_image.csv: mean entropy over the image and over its "
+                        "background, uncertain pixels in all and on the background (the missed-droplet indicator), unstable pixels, "
+                        "mean spread, droplets and their lowest prob_mean -- which images to look at, or annotate, next.  "
+                        "Probabilities are read at the nearest source pixel of each mask pixel and quantised to 16 bits")
+    p.add_argument("--confidence_maps", action="store_true",
+                   help="with --confidence: also write NAME_entropy.png and, with --tta, NAME_spread.png (8-bit maps)")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -626,6 +688,21 @@ def boundary_options(args):
     return {"R": R, "tols": tols, "records": []}
 
 
+def confidence_options(args):
+    """--confidence / --confidence_maps -> {"band", "maps", "rows"}, None without the flag; a bad value ends the run before any
+    image."""
+    if args.confidence is None:
+        if args.confidence_maps:
+            raise SystemExit("--confidence_maps needs --confidence")
+        return None
+    from utils.droplet_confidence import check_band
+    try:
+        band = check_band(args.confidence)
+    except ValueError as e:
+        raise SystemExit(f"--confidence BAND: {e}")
+    return {"band": band, "maps": bool(args.confidence_maps), "rows": []}
+
+
 def tile_options(args):
     """--tile / --tile_overlap -> {"T", "O"}, None without --tile; a bad value ends the run before any image."""
     if args.tile is None:
@@ -670,6 +747,7 @@ def main(argv=None):
     tile = tile_options(args)
     tta = tta_options(args)
     boundary = boundary_options(args)
+    confidence = confidence_options(args)
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -699,7 +777,7 @@ def main(argv=None):
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
-                  neighbors=args.neighbors, boundary=boundary)
+                  neighbors=args.neighbors, boundary=boundary, confidence=confidence)
         ahead = deque()
         it = iter(images)
 
@@ -753,6 +831,9 @@ def main(argv=None):
         rows = [db.summary_row(name, h, d, boundary["R"], boundary["tols"]) for name, h, d in recs]
         rows.append(db.pooled_row([(h, d) for _, h, d in recs], boundary["R"], boundary["tols"]))
         pd.DataFrame(rows, columns=db.column_names(boundary["tols"])).to_csv(out_dir / "boundary_per_image.csv", index=False)
+    if confidence is not None:
+        from utils.droplet_confidence import IMAGE_COLUMNS
+        pd.DataFrame(confidence["rows"], columns=("filename",) + IMAGE_COLUMNS).to_csv(out_dir / "confidence_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     if run.neighbors is not None and run.contact_tables:

@@ -103,6 +103,7 @@ SIGNATURES = {
     "unetdc_ccl_labels_workspace": (L, [I, I]),
     "unetdc_ccl_labels": (I, [P, I, I, I, P, L, P, P, P, P, P, P, I, P]),
     "unetdc_label_props": (I, [P, P, I, I, P, I, P]),
+    "unetdc_label_confidence": (I, [P, I, I, I, P, P, P, I, I, F, F, P, P, P, P, P, P]),
     "unetdc_label_overlap_workspace": (L, [I, I, I]),
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
     "unetdc_boundary_distances_workspace": (L, [I, I]),
@@ -116,6 +117,7 @@ SIGNATURES = {
     "unetdc_tile_blend_f32": (I, [P, I, I, P, I, P, I, P, I, I, P]),
     "unetdc_dihedral_expand_f32": (I, [P, I, I, I, I, P, P]),
     "unetdc_dihedral_mean_f32": (I, [P, I, I, I, P, P]),
+    "unetdc_dihedral_mean_env_f32": (I, [P, I, I, I, P, P, P, P]),
 }
 
 _lib = None

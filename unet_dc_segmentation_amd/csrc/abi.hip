@@ -618,6 +618,17 @@ int unetdc_label_props(const int32_t* label, const uint8_t* gray, int h, int w, 
   return launch_label_props(label, gray, h, w, reinterpret_cast<long long*>(out), max_out, (hipStream_t)s);
 }
 
+static_assert(UNETDC_CONF_QUANTITIES == CONF_QUANTITIES && UNETDC_CONF_IMAGE_QUANTITIES == CONF_IMAGE_QUANTITIES,
+              "unetdc_label_confidence output rows");
+
+int unetdc_label_confidence(const int32_t* label, int max_out, int h, int w, const float* probs, const float* lo, const float* hi,
+                            int ph, int pw, float thresh, float band, const uint16_t* entropy_table, int64_t* out,
+                            int64_t* out_image, uint8_t* out_entropy_u8, uint8_t* out_spread_u8, unetdc_stream_t s) {
+  return launch_label_confidence(label, max_out, h, w, probs, lo, hi, ph, pw, thresh, band, entropy_table,
+                                 reinterpret_cast<long long*>(out), reinterpret_cast<long long*>(out_image), out_entropy_u8,
+                                 out_spread_u8, (hipStream_t)s);
+}
+
 int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) { return label_overlap_workspace_bytes(h, w, max_pairs); }
 
 int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,
@@ -680,6 +691,11 @@ int unetdc_dihedral_expand_f32(const float* x, int n, int c, int s, int nvar, fl
 
 int unetdc_dihedral_mean_f32(const float* p, int n, int s, int nvar, float* out, unetdc_stream_t stream) {
   return launch_dihedral_mean(p, n, s, nvar, out, (hipStream_t)stream);
+}
+
+int unetdc_dihedral_mean_env_f32(const float* p, int n, int s, int nvar, float* out_mean, float* out_lo, float* out_hi,
+                                 unetdc_stream_t stream) {
+  return launch_dihedral_mean_env(p, n, s, nvar, out_mean, out_lo, out_hi, (hipStream_t)stream);
 }
 
 int64_t unetdc_rolling_ball_workspace(int h, int w, int channels) { return rolling_ball_workspace_bytes(h, w, channels); }

@@ -295,6 +295,13 @@ constexpr int SHAPE_QUANTITIES = 14;
 int launch_label_props(const int* label, const unsigned char* gray, int h, int w, long long* out, int max_out,
                        hipStream_t stream);
 
+// confidence.hip: per-label and per-image integers of the quantised probability, its entropy and the TTA envelope under an
+// int32 label map
+constexpr int CONF_QUANTITIES = 10, CONF_IMAGE_QUANTITIES = 8;
+int launch_label_confidence(const int* label, int max_out, int h, int w, const float* probs, const float* lo, const float* hi,
+                            int ph, int pw, float thresh, float band, const unsigned short* table, long long* out,
+                            long long* out_image, unsigned char* out_entropy, unsigned char* out_spread, hipStream_t stream);
+
 // match.hip: the sparse contingency table of two int32 label maps, in (a, b) order
 long label_overlap_workspace_bytes(int h, int w, int max_pairs);
 int launch_label_overlap(const int* label_a, int max_a, const int* label_b, int max_b, int h, int w, void* workspace,
@@ -345,6 +352,8 @@ int launch_tile_blend(const float* tiles, int t, int overlap, const int* yo, int
 // include/unetdc_hip.h)
 int launch_dihedral_expand(const float* x, int n, int c, int s, int nvar, float* out, hipStream_t stream);
 int launch_dihedral_mean(const float* p, int n, int s, int nvar, float* out, hipStream_t stream);
+int launch_dihedral_mean_env(const float* p, int n, int s, int nvar, float* out_mean, float* out_lo, float* out_hi,
+                             hipStream_t stream);
 
 // augment.hip: elastic displacement fields + the per-batch augmentation gather.  AugRecord is the layout of the public
 // unetdc_augment_params (include/unetdc_hip.h; abi.hip asserts the two agree).

@@ -13,6 +13,8 @@
 // 64-byte run), park it in LDS, pick their four destination pixels from the permuted positions and write the destination block by
 // rows, 16 bytes each -- for the odd k too, where a per-thread gather would walk down columns.  Both kernels are memory-bound:
 // the expand moves 4 bytes in and 4 out per output element, the mean 4 * nvar in and 4 out per output pixel.
+//   mean_env the mean, and from the same LDS tile in the same trip lo / hi = the minimum / maximum over the mapped-back items
+//            (DESIGN.md section 23): 4 * nvar bytes in and 12 out per pixel, where a separate pass would read the items twice.
 #include "gather_index.h"
 #include "kernels.h"
 
@@ -63,10 +65,12 @@ __global__ __launch_bounds__(TTA_THREADS) void dihedral_expand_kernel(const floa
   }
 }
 
-template <int NVAR>
-__global__ __launch_bounds__(TTA_THREADS) void dihedral_mean_kernel(const float* __restrict__ p, int S, float* __restrict__ out,
-                                                                    long nblocks) {
-  __shared__ __attribute__((aligned(16))) unsigned int tile[TTA_WAVES][NVAR][16 * TTA_ROW];
+// The body of both mean kernels: the NVAR mapped-back items of a block through LDS, their mean in list order, and with ENV the
+// per-pixel minimum and maximum of the same LDS tile (fminf / fmaxf), each output written with the same 16-byte row stores.
+template <int NVAR, bool ENV>
+__device__ __forceinline__ void dihedral_mean_body(unsigned int (&tile)[TTA_WAVES][NVAR][16 * TTA_ROW], const float* __restrict__ p,
+                                                   int S, float* __restrict__ out, float* __restrict__ out_lo,
+                                                   float* __restrict__ out_hi, long nblocks) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane >> 2, q4 = (lane & 3) * 4;
   const int nb = S / 16;
   const long plane = (long)S * S, ntrips = (nblocks + TTA_WAVES - 1) / TTA_WAVES;
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(TTA_THREADS) void dihedral_mean_kernel(const float*
     }
     __syncthreads();
     if (live) {
-      float acc[4];
+      float acc[4], lo[4], hi[4];
 #pragma unroll
       for (int i = 0; i < NVAR; ++i) {
         const int v = tta_variant(NVAR, i);
@@ -97,15 +101,43 @@ __global__ __launch_bounds__(TTA_THREADS) void dihedral_mean_kernel(const float*
           aug_dest(r, q4 + e, 16, 16, (v & 4) ? AUG_HFLIP : 0, v & 3, ly, lx);
           const float qv = bits_f32(tile[wave][i][ly * TTA_ROW + lx]);
           acc[e] = i == 0 ? qv : acc[e] + qv;                             // list order, every add rounded
+          if (ENV) {
+            lo[e] = i == 0 ? qv : fminf(lo[e], qv);
+            hi[e] = i == 0 ? qv : fmaxf(hi[e], qv);
+          }
         }
       }
+      const long at = b * plane + (long)(16 * by + r) * S + 16 * bx + q4;
       u32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = f32_bits(acc[e] / (float)NVAR);
-      st16(out + b * plane + (long)(16 * by + r) * S + 16 * bx + q4, o);
+      st16(out + at, o);
+      if (ENV) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = f32_bits(lo[e]);
+        st16(out_lo + at, o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = f32_bits(hi[e]);
+        st16(out_hi + at, o);
+      }
     }
     __syncthreads();
   }
+}
+
+template <int NVAR>
+__global__ __launch_bounds__(TTA_THREADS) void dihedral_mean_kernel(const float* __restrict__ p, int S, float* __restrict__ out,
+                                                                    long nblocks) {
+  __shared__ __attribute__((aligned(16))) unsigned int tile[TTA_WAVES][NVAR][16 * TTA_ROW];
+  dihedral_mean_body<NVAR, false>(tile, p, S, out, nullptr, nullptr, nblocks);
+}
+
+template <int NVAR>
+__global__ __launch_bounds__(TTA_THREADS) void dihedral_mean_env_kernel(const float* __restrict__ p, int S, float* __restrict__ out,
+                                                                        float* __restrict__ out_lo, float* __restrict__ out_hi,
+                                                                        long nblocks) {
+  __shared__ __attribute__((aligned(16))) unsigned int tile[TTA_WAVES][NVAR][16 * TTA_ROW];
+  dihedral_mean_body<NVAR, true>(tile, p, S, out, out_lo, out_hi, nblocks);
 }
 
 static int tta_groups(long nblocks) {
@@ -153,6 +185,30 @@ int launch_dihedral_mean(const float* p, int n, int s, int nvar, float* out, hip
     default: hipLaunchKernelGGL(dihedral_mean_kernel<8>, grid, block, 0, stream, p, s, out, nblocks); break;
   }
   return check_launch("dihedral_mean_kernel");
+}
+
+int launch_dihedral_mean_env(const float* p, int n, int s, int nvar, float* out_mean, float* out_lo, float* out_hi,
+                             hipStream_t stream) {
+  if (int rc = tta_check("dihedral_mean_env", p, out_mean, n, 1, s, nvar)) return rc;
+  UNETDC_REQUIRE(out_lo && out_hi, "dihedral_mean_env: null pointer");
+  UNETDC_REQUIRE(reinterpret_cast<uintptr_t>(out_lo) % 16 == 0 && reinterpret_cast<uintptr_t>(out_hi) % 16 == 0,
+                 "dihedral_mean_env: every buffer must be 16-byte aligned");
+  const long out_elems = (long)n * s * s;
+  float* const outs[3] = {out_mean, out_lo, out_hi};
+  for (int a = 0; a < 3; ++a) {
+    UNETDC_REQUIRE(!tta_overlap(p, out_elems * nvar * 4, outs[a], out_elems * 4), "dihedral_mean_env: no output may overlap the input");
+    for (int b = a + 1; b < 3; ++b)
+      UNETDC_REQUIRE(!tta_overlap(outs[a], out_elems * 4, outs[b], out_elems * 4), "dihedral_mean_env: the outputs must not overlap");
+  }
+  const long nblocks = out_elems / 256;
+  const dim3 grid(tta_groups(nblocks)), block(TTA_THREADS);
+  switch (nvar) {
+    case 1: hipLaunchKernelGGL(dihedral_mean_env_kernel<1>, grid, block, 0, stream, p, s, out_mean, out_lo, out_hi, nblocks); break;
+    case 2: hipLaunchKernelGGL(dihedral_mean_env_kernel<2>, grid, block, 0, stream, p, s, out_mean, out_lo, out_hi, nblocks); break;
+    case 4: hipLaunchKernelGGL(dihedral_mean_env_kernel<4>, grid, block, 0, stream, p, s, out_mean, out_lo, out_hi, nblocks); break;
+    default: hipLaunchKernelGGL(dihedral_mean_env_kernel<8>, grid, block, 0, stream, p, s, out_mean, out_lo, out_hi, nblocks); break;
+  }
+  return check_launch("dihedral_mean_env_kernel");
 }
 
 }  // namespace unetdc

@@ -60,11 +60,14 @@ class DropletOptions:
     split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
     than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py).
     shape: also the per-droplet integers that utils.droplet_shape.shape_columns reads (csrc/shape.hip).
-    labels: also the int32 label map; needs a split depth, shape or neighbors.
+    labels: also the int32 label map; needs a split depth, shape, neighbors or confidence.
     thresh_low (<= thresh) / max_hole_area (0 = off, negative = any size, N = holes of at most N pixels): the mask is
     cleaned first (hysteresis threshold, hole filling: csrc/clean.hip).
     neighbors (contact radius in pixels, an integer 1..64; None = off): also the contact pairs and the per-droplet nearest
     contact, degree and cluster (csrc/neighbors.hip, utils/droplet_neighbors.py).
+    confidence (the uncertainty band, 0..0.5; None = off): also the per-droplet and per-image integers of the quantised
+    probability, its entropy and, given envelope=(lo, hi), the disagreement of the TTA variants (csrc/confidence.hip,
+    utils/droplet_confidence.py); confidence_maps: also the uint8 entropy and spread maps, on the device.
     thresh / gray are not kept: the threshold the low one is checked against, and the grey planes, which need shape."""
     split_depth: float | None = None
     shape: bool = False
@@ -72,11 +75,13 @@ class DropletOptions:
     thresh_low: float | None = None
     max_hole_area: int = 0
     neighbors: int | None = None
+    confidence: float | None = None
+    confidence_maps: bool = False
     thresh: dataclasses.InitVar[float | None] = None
     gray: dataclasses.InitVar[object] = None
 
     def __post_init__(self, thresh, gray):
-        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None:
+        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None and self.confidence is None:
             raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
         if self.neighbors is not None:
             from utils.droplet_neighbors import check_radius
@@ -84,10 +89,23 @@ class DropletOptions:
                 check_radius(self.neighbors)
             except ValueError as e:
                 raise _lib.UnetdcError(str(e)) from None
+        if self.confidence is not None:
+            from utils.droplet_confidence import check_band
+            try:
+                check_band(self.confidence)
+            except ValueError as e:
+                raise _lib.UnetdcError(str(e)) from None
+        elif self.confidence_maps:
+            raise _lib.UnetdcError("confidence_maps needs confidence (the band)")
         if gray is not None and not self.shape:
             raise _lib.UnetdcError("gray needs shape=True")
         if thresh is not None:
             self.cleaning(thresh)
+
+    @property
+    def label_map(self):
+        """Whether a stage reads the int32 label map (without a split depth that selects unetdc_ccl_labels)."""
+        return self.shape or self.neighbors is not None or self.confidence is not None
 
     @property
     def half_pixels(self):
@@ -110,10 +128,13 @@ def _options(keywords, thresh):
     """The option keywords of the public functions -> (the record, validated against this call's threshold and grey planes;
     gray).  options=DropletOptions(...), or its fields by name (labels also under its earlier name return_labels)."""
     kw = dict(keywords)
-    gray, base = kw.pop("gray", None), kw.pop("options", None) or DropletOptions()
+    gray, base, envelope = kw.pop("gray", None), kw.pop("options", None) or DropletOptions(), kw.pop("envelope", None)
     if "return_labels" in kw:
         kw["labels"] = kw.pop("return_labels")
-    return dataclasses.replace(base, **kw, thresh=thresh, gray=gray), gray
+    opts = dataclasses.replace(base, **kw, thresh=thresh, gray=gray)
+    if envelope is not None and opts.confidence is None:
+        raise _lib.UnetdcError("envelope needs confidence (the band)")
+    return opts, gray, envelope
 
 
 @dataclasses.dataclass(eq=False)
@@ -123,8 +144,9 @@ class Droplets:
     reference's label order; labels: int32 [oh, ow] DEVICE label map (None unless asked for); props: the dict of
     per-droplet int64 arrays that utils.droplet_shape.shape_columns reads (None without shape); clean_counts: int64 [4],
     the counts of utils.droplet_clean.COUNT_NAMES (zeros when cleaning is off); neighbors: the record of
-    utils.droplet_neighbors.neighbors_numpy, int64 arrays (None unless asked for).  The CPU path of the script fills the same
-    record with host arrays."""
+    utils.droplet_neighbors.neighbors_numpy, int64 arrays (None unless asked for); confidence: the record of
+    utils.droplet_confidence.confidence_numpy (None unless asked for), its two maps DEVICE tensors.  The CPU path of the script
+    fills the same record with host arrays."""
     mask: object
     area: np.ndarray
     centroid_row: np.ndarray
@@ -133,6 +155,7 @@ class Droplets:
     props: dict | None = None
     clean_counts: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(4, np.int64))
     neighbors: dict | None = None
+    confidence = None             # set by name after construction: the constructor's fields stay those of the stages before
 
     def __iter__(self):
         return iter((self.mask, self.area, self.centroid_row, self.centroid_col))
@@ -151,6 +174,7 @@ class _Image(NamedTuple):
     pair_count: torch.Tensor | None = None     # int32, the number of contact pairs first
     pairs: torch.Tensor | None = None          # int32 [3, pair room]: a, b, d2
     per_label: torch.Tensor | None = None      # int32 [5, cap]: the rows of utils.droplet_neighbors.COLUMN_NAMES
+    conf: tuple | None = None                  # confidence: (lo, hi fp32 [ph, pw] or None, int64 [8] image totals, the two uint8 maps or None)
 
 
 def _enqueue(im, thresh, min_area, ws, opts, s):
@@ -158,7 +182,9 @@ def _enqueue(im, thresh, min_area, ws, opts, s):
     mask is that of the low threshold under the same resize rule); labelling + sums + compaction by unetdc_ccl_stats,
     with a split depth unetdc_split_stats (which also fills the label map when there is one), with shape and no split
     depth unetdc_ccl_labels (so does neighbors); then with shape unetdc_label_props on the label map and the optional grey
-    plane; then with neighbors unetdc_label_neighbors on the label map, the droplet capacity as its max_label."""
+    plane; then with neighbors unetdc_label_neighbors on the label map, the droplet capacity as its max_label; then with
+    confidence unetdc_label_confidence on the label map and the probabilities (and the envelope), the capacity as its max_out,
+    into the rows of `sums` behind those of shape."""
     (oh, ow), cap, h2, clean = im.mask.shape, im.area.shape[0], opts.half_pixels, opts.cleaning(thresh)
     _mask_from_probs(im.probs, thresh, im.mask, s)
     if clean is not None:
@@ -174,7 +200,7 @@ def _enqueue(im, thresh, min_area, ws, opts, s):
     label = None if im.label is None else im.label.data_ptr()
     if h2 is not None:
         _lib.call("unetdc_split_stats", *head, h2, *outs, label, cap, s)
-    elif opts.shape or opts.neighbors is not None:
+    elif opts.label_map:
         _lib.call("unetdc_ccl_labels", *head, *outs, label, cap, s)
     else:
         _lib.call("unetdc_ccl_stats", *head, *outs, cap, s)
@@ -184,6 +210,24 @@ def _enqueue(im, thresh, min_area, ws, opts, s):
         room = im.pairs.shape[1]
         _lib.call("unetdc_label_neighbors", label, cap, oh, ow, int(opts.neighbors), ws.data_ptr(), ws.numel(), im.pair_count.data_ptr(),
                   *((im.pairs[j].data_ptr() if room else None) for j in range(3)), room, *(im.per_label[j].data_ptr() for j in range(5)), s)
+    if opts.confidence is not None:
+        lo, hi, totals, emap, smap = im.conf
+        ph, pw = im.probs.shape
+        _lib.call("unetdc_label_confidence", label, cap, oh, ow, im.probs.data_ptr(), *(None if t is None else t.data_ptr() for t in (lo, hi)),
+                  ph, pw, float(thresh), float(opts.confidence), _entropy_table(im.probs.device).data_ptr(),
+                  im.sums[2 + NQ * opts.shape].data_ptr(), totals.data_ptr(), *(None if t is None else t.data_ptr() for t in (emap, smap)), s)
+
+
+_tables = {}
+
+
+def _entropy_table(device):
+    """utils.droplet_confidence.entropy_table on the device, uploaded once per device (128 KB; int16 holds the uint16 bits)."""
+    key = str(device)
+    if key not in _tables:
+        from utils.droplet_confidence import entropy_table
+        _tables[key] = torch.from_numpy(entropy_table().view(np.int16).copy()).to(device)
+    return _tables[key]
 
 
 def _check_gray(gray, oh, ow):
@@ -205,9 +249,15 @@ def _neighbors_dict(pairs, per_label):
     return {"pairs": dict(zip(("a", "b", "d2"), pairs)), **dict(zip(COLUMN_NAMES, per_label))}
 
 
+def _confidence_dict(rows, totals, envelope, maps):
+    """The record of utils.droplet_confidence.confidence_numpy from the int64 copies [NC, droplets] and [8]."""
+    from utils.droplet_confidence import CONF_QUANTITIES
+    return {**dict(zip(CONF_QUANTITIES, rows)), "image": totals, "envelope": envelope, "entropy_u8": maps[0], "spread_u8": maps[1]}
+
+
 def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room):
     query = (lib.unetdc_split_workspace if opts.split_depth is not None else
-             lib.unetdc_ccl_labels_workspace if opts.shape or opts.neighbors is not None else lib.unetdc_ccl_workspace)
+             lib.unetdc_ccl_labels_workspace if opts.label_map else lib.unetdc_ccl_workspace)
     nbytes = max(query(h, w) for h, w in out_hws)
     if opts.neighbors is not None:
         nbytes = max(nbytes, max(lib.unetdc_label_neighbors_workspace(h, w, cap, pair_room) for h, w in out_hws))
@@ -217,6 +267,7 @@ def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room):
 
 
 NQ = 14    # UNETDC_SHAPE_QUANTITIES
+NC = 10    # UNETDC_CONF_QUANTITIES
 PAIR_ROOM = 1 << 14    # contact pairs per image the first launch has room for; an image with more is run again with twice that
 MAX_PAIR_ROOM = 1 << 27   # the largest table of unetdc_label_neighbors
 
@@ -226,15 +277,21 @@ def _pair_room(cap, wanted):
     return int(min(wanted, cap * (cap - 1) // 2, MAX_PAIR_ROOM))
 
 
-def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None):
+def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None, envelope=None):
     """The one launch-and-readback body -> (B Droplets, the device outputs (count, area, sumy, sumx) or None when an image
     had more droplets than they hold).  Every launch of the batch is enqueued back to back on the current stream into ONE
     set of output planes; the host then waits ONCE: one device->host copy brings the B droplet counts (and the clean
     counts and with neighbors the pair counts behind them), two more the filled part of the per-droplet integers; with
-    neighbors one more the per-droplet neighbour integers and one the filled part of the pair lists."""
+    neighbors one more the per-droplet neighbour integers and one the filled part of the pair lists.  The integers of confidence
+    add no copy: the per-droplet rows lie behind the sums, the per-image totals (int64) behind the counts."""
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
+    if envelope is not None:
+        if len(envelope) != 2 or any(not torch.is_tensor(t) or t.dtype != torch.float32 or t.shape != probs.shape or t.device != probs.device
+                                     for t in envelope):
+            raise _lib.UnetdcError("envelope is (lo, hi): two fp32 tensors shaped like probs, on its device")
+        envelope = tuple(t.contiguous() for t in envelope)
     B, dev, s = probs.shape[0], probs.device, torch.cuda.current_stream().cuda_stream
     clean = opts.cleaning(thresh)
     out_hws = [(int(h), int(w)) for h, w in out_hws]
@@ -245,22 +302,34 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
     nb = opts.neighbors is not None
     room = _pair_room(cap, PAIR_ROOM if pair_room is None else pair_room) if nb else 0
     ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, cap, room), dtype=torch.uint8, device=dev)   # one: stream order
-    nc = B * (1 if clean is None else 5)
-    counts = torch.zeros(nc + B * nb, dtype=torch.int32, device=dev)   # droplet counts, then 4 per image, then the pair counts
+    nc, cf = B * (1 if clean is None else 5), opts.confidence is not None
+    n32 = nc + B * nb
+    at64 = (n32 + 1) // 2 * 2                                          # the int64 totals start on an 8-byte boundary
+    # droplet counts, then 4 per image, then the pair counts; then with confidence 8 int64 per image (16 int32 slots)
+    counts = torch.zeros(at64 + 16 * B if cf else n32, dtype=torch.int32, device=dev)
+    totals = counts[at64:].view(torch.int64) if cf else None
     pairs = torch.empty(B, 3, room, dtype=torch.int32, device=dev) if nb else None
     per_label = torch.empty(B, 5, cap, dtype=torch.int32, device=dev) if nb else None
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
     # per image: sum y, sum x, then with shape the rows of unetdc_label_props, which wants them [NQ][cap] in one piece
-    sums = torch.empty(B, 2 + NQ if opts.shape else 2, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
+    # and with confidence behind them the rows of unetdc_label_confidence, [NC][cap] in one piece as well
+    r0 = 2 + NQ * opts.shape
+    sums = torch.empty(B, r0 + NC * cf, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
     images = []
     for i, (oh, ow) in enumerate(out_hws):
         images.append(_Image(probs[i], torch.empty(oh, ow, dtype=torch.uint8, device=dev),
-                             torch.empty(oh, ow, dtype=torch.int32, device=dev) if opts.labels or opts.shape or nb else None,
+                             torch.empty(oh, ow, dtype=torch.int32, device=dev) if opts.labels or opts.label_map else None,
                              None if gray is None else gray[i], counts[i:], area[i], sums[:, i],
                              None if clean is None else counts[B + 4 * i:],
-                             *((counts[nc + i:], pairs[i], per_label[i]) if nb else ())))
+                             *((counts[nc + i:], pairs[i], per_label[i]) if nb else (None, None, None)),
+                             (*((envelope[0][i], envelope[1][i]) if envelope is not None else (None, None)), totals[8 * i:],
+                              torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps else None,
+                              torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps and envelope is not None else None)
+                             if cf else None))
         _enqueue(images[i], thresh, min_area, ws, opts, s)
-    n = counts.cpu().numpy().astype(np.int64)                       # the batch's only host wait
+    raw = counts.cpu().numpy()                                      # the batch's only host wait
+    t_h = raw[at64:].view(np.int64).reshape(B, 8) if cf else None
+    n = raw[:n32].astype(np.int64)
     clean_counts = n[B:nc].reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
     n_pairs, n = n[nc:], n[:B]
     nmax = int(min(n.max(initial=0), cap))
@@ -273,19 +342,23 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
     for i, im in enumerate(images):
         if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
             out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, int(n[i]),
-                                 None if gray is None else gray[i:i + 1], opts, pair_room)[0][0])
+                                 None if gray is None else gray[i:i + 1], opts, pair_room,
+                                 None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
             continue
         if nb and n_pairs[i] > room:              # more contact pairs than the pair lists hold: this image again with twice the room
             if room >= MAX_PAIR_ROOM:
                 raise _lib.UnetdcError(f"more than {MAX_PAIR_ROOM} contact pairs in one image")
             out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, max_droplets,
-                                 None if gray is None else gray[i:i + 1], opts, 2 * max(room, 1))[0][0])
+                                 None if gray is None else gray[i:i + 1], opts, 2 * max(room, 1),
+                                 None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
             continue
         a, si = a_h[i, :n[i]], s_h[:, i, :n[i]]
         d = np.maximum(a, 1)
         out.append(Droplets(im.mask, a, si[0].astype(np.float64) / d, si[1].astype(np.float64) / d,
                             im.label if opts.labels else None, _props_dict(a, si, gray is not None) if opts.shape else None,
                             clean_counts[i], _neighbors_dict(p_h[i, :, :n_pairs[i]], l_h[i, :, :n[i]]) if nb else None))
+        if cf:
+            out[-1].confidence = _confidence_dict(si[r0:r0 + NC], t_h[i], envelope is not None, im.conf[3:])
     return out, ((counts[:B], area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
 
 
@@ -293,16 +366,19 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs -> a list of B Droplets, after
     ONE host wait for the whole batch (_droplets).  keep_sums=True returns (that list, the device outputs (count, area,
     sumy, sumx) or None when an image had more droplets than they hold) for density.density_maps_batch.
-    options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors by name, or options=DropletOptions(...); and
-    gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none).  Every option adds its launches
+    options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors, confidence, confidence_maps by name, or
+    options=DropletOptions(...); gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none); and
+    envelope=(lo, hi), two fp32 DEVICE tensors shaped like probs (tta.predict_tta(..., envelope=True)), for the disagreement
+    integers of confidence (None: those keep their initial values).  Every option adds its launches
     behind each image's existing ones and its integers to the copies the host already waits for; all off: no launch is added."""
-    opts, gray = _options(options, thresh)
-    out, sums = _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts)
+    opts, gray, envelope = _options(options, thresh)
+    out, sums = _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, envelope=envelope)
     return (out, sums) if keep_sums else out
 
 
 def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, **options):
     """probs2d: [H, W] fp32 probabilities on the HIP device -> its Droplets: the batch of one.  options as in
-    mask_and_droplets_batch; gray: one uint8 [oh, ow] DEVICE tensor."""
-    opts, gray = _options(options, thresh)
-    return _droplets(probs2d[None], thresh, [out_hw], min_area, max_droplets, None if gray is None else [gray], opts)[0][0]
+    mask_and_droplets_batch; gray: one uint8 [oh, ow] DEVICE tensor; envelope: two fp32 [H, W] DEVICE tensors."""
+    opts, gray, envelope = _options(options, thresh)
+    return _droplets(probs2d[None], thresh, [out_hw], min_area, max_droplets, None if gray is None else [gray], opts,
+                     envelope=None if envelope is None else tuple(t[None] for t in envelope))[0][0]

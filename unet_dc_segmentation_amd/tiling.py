@@ -66,17 +66,31 @@ def tile_blend(tile_probs, h, w, T, O):
 
 
 @torch.no_grad()
-def predict_tiled(model, img_u8, T, O, batch, tta=1):
+def predict_tiled(model, img_u8, T, O, batch, tta=1, envelope=False):
     """img_u8: [H, W, C] uint8 on the HIP device (background-corrected) -> [H, W] fp32 probabilities on the device.
     The tiles are gathered and forwarded `batch` at a time (a ragged last chunk is a second engine shape), every chunk's output
     is copied into its slice of one [n_tiles, T, T] buffer, and ONE blend launch makes the map.  Nothing waits for the device.
     tta > 1 (DESIGN.md section 17): the tiles go in groups of max(1, batch // tta), and a group's slice of the buffer is the mean
-    over the `tta` flipped and rotated variants of its tiles (tta.group_mean, `batch` items per forward)."""
+    over the `tta` flipped and rotated variants of its tiles (tta.group_mean, `batch` items per forward).
+    envelope: -> (mean, lo, hi), three [H, W] maps: every group's one launch also leaves the per-tile minimum and maximum over the
+    variants (tta.dihedral_mean_env), and lo and hi go through the same blend -- they are the blend of the per-tile envelopes,
+    not the envelope of blended maps."""
     img_u8 = _image(img_u8)
     h, w, _ = img_u8.shape
     yo, xo = _plan(h, w, T, O, img_u8.device)
     n, batch = len(yo) * len(xo), max(1, int(batch))
-    probs = torch.empty(n, T, T, dtype=torch.float32, device=img_u8.device)
+    probs = torch.empty(3 if envelope else 1, n, T, T, dtype=torch.float32, device=img_u8.device)
+    if envelope:
+        from utils.tta import check_tta, groups
+        from .tta import group_mean
+        try:
+            tta = check_tta(tta)
+        except (ValueError, TypeError) as e:
+            raise _lib.UnetdcError(f"predict_tiled: {e}")
+        for t0, cnt in groups(n, tta, batch):
+            group_mean(model, tile_gather(img_u8, T, O, t0, cnt), tta, batch, tuple(p[t0:t0 + cnt] for p in probs), True)
+        return tuple(tile_blend(p, h, w, T, O) for p in probs)
+    probs = probs[0]
     if tta != 1:
         from utils.tta import check_tta, groups
         from .tta import group_mean

@@ -60,25 +60,45 @@ def dihedral_mean(p, N, out=None):
     return out
 
 
-def group_mean(model, x, N, batch, out):
+def dihedral_mean_env(p, N, out=None):
+    """p as for dihedral_mean -> (mean, lo, hi), [n, S, S] each, from ONE pass over the items: the mean of dihedral_mean bit for
+    bit, and the per-pixel minimum and maximum over the mapped-back items (utils.tta.mean_env_numpy).  out: the three tensors to
+    write into.  Only lo <= hi holds; the rounded mean may lie outside them."""
+    p, N = _check(p, 3, N, "dihedral_mean_env")
+    if p.shape[0] % N:
+        raise _lib.UnetdcError(f"dihedral_mean_env: {p.shape[0]} items are no multiple of {N} variants")
+    n, s = p.shape[0] // N, p.shape[-1]
+    if out is not None and len(out) != 3:
+        raise _lib.UnetdcError("dihedral_mean_env: out is the three tensors (mean, lo, hi)")
+    outs = tuple(_out(None if out is None else o, (n, s, s), p, "dihedral_mean_env") for o in (out or (None,) * 3))
+    _lib.call("unetdc_dihedral_mean_env_f32", p.data_ptr(), n, s, N, *(o.data_ptr() for o in outs),
+              torch.cuda.current_stream().cuda_stream)
+    return outs
+
+
+def group_mean(model, x, N, batch, out, envelope=False):
     """One group of the chunk rule: x [g, C, S, S] is expanded once, its g * N items go through `model` in slices of `batch` into
-    one buffer, and one mean writes out [g, S, S]."""
+    one buffer, and one mean writes out [g, S, S].  envelope: out is the three tensors (mean, lo, hi) and the one launch is
+    dihedral_mean_env."""
     items = dihedral_expand(x, N)
     p = torch.empty(items.shape[0], items.shape[2], items.shape[3], dtype=torch.float32, device=x.device)
     for i in range(0, len(items), batch):
         p[i:i + batch].copy_(model(items[i:i + batch])[:, 0])
-    return dihedral_mean(p, N, out=out)
+    return dihedral_mean_env(p, N, out=out) if envelope else dihedral_mean(p, N, out=out)
 
 
 @torch.no_grad()
-def predict_tta(model, x, N, batch):
+def predict_tta(model, x, N, batch, envelope=False):
     """x: [n, C, S, S] fp32 on the HIP device -> [n, 1, S, S] fp32 probabilities on the device: the mean of `model` over the N
     variants of every image.  The images go in groups of max(1, batch // N) (utils.tta.groups: at most two engine shapes);
-    nothing waits for the device."""
+    nothing waits for the device.  envelope: -> (mean, lo, hi), three tensors of that shape (dihedral_mean_env)."""
     from utils.tta import groups
     x, N = _check(x, 4, N, "predict_tta")
     batch = max(1, int(batch))
-    out = torch.empty(x.shape[0], 1, x.shape[2], x.shape[3], dtype=torch.float32, device=x.device)
+    out = torch.empty(3 if envelope else 1, x.shape[0], 1, x.shape[2], x.shape[3], dtype=torch.float32, device=x.device)
     for b0, g in groups(x.shape[0], N, batch):
-        group_mean(model, x[b0:b0 + g], N, batch, out[b0:b0 + g, 0])
-    return out
+        if envelope:
+            group_mean(model, x[b0:b0 + g], N, batch, tuple(o[b0:b0 + g, 0] for o in out), True)
+        else:
+            group_mean(model, x[b0:b0 + g], N, batch, out[0, b0:b0 + g, 0])
+    return tuple(out) if envelope else out[0]

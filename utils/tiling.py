@@ -108,15 +108,20 @@ def blend_numpy64(tiles, h, w, T, O):
     return _blend(tiles, h, w, T, O, np.float64)
 
 
-def predict_tiled_cpu(model, img_u8, T, O, batch, tta=1):
+def predict_tiled_cpu(model, img_u8, T, O, batch, tta=1, envelope=False):
     """CPU path of unet_dc_segmentation_amd.tiling.predict_tiled: img_u8 [H, W, C] uint8 (numpy) -> fp32 [H, W] probabilities
     (numpy): the tiles of gather_numpy through `model` in chunks of `batch` under no_grad, then blend_numpy.  tta > 1: every
     tile's probabilities are the mean over its `tta` flipped and rotated variants (utils.tta.predict_tta_cpu, `batch` items per
-    forward) before the blend."""
+    forward) before the blend.  envelope: -> (mean, lo, hi), three maps: lo and hi are the blend of the per-tile envelopes
+    (utils.tta.mean_env_numpy per tile, each through the same blend_numpy)."""
     import torch
     img_u8 = np.asarray(img_u8)
     tiles = torch.from_numpy(gather_numpy(img_u8, T, O))
     batch = max(1, int(batch))
+    if envelope:
+        from utils.tta import predict_tta_cpu
+        return tuple(blend_numpy(p[:, 0].numpy(), img_u8.shape[0], img_u8.shape[1], T, O)
+                     for p in predict_tta_cpu(model, tiles, tta, batch, envelope=True))
     if tta != 1:
         from utils.tta import predict_tta_cpu
         probs = predict_tta_cpu(model, tiles, tta, batch)[:, 0]

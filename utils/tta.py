@@ -70,6 +70,19 @@ def mean_numpy(p, N):
     return _mean(np.asarray(p, np.float32), N, np.float32)
 
 
+def mean_env_numpy(p, N):
+    """p as for mean_numpy -> (mean, lo, hi), fp32 [n, S, S] each: mean_numpy bit for bit, and the per-pixel minimum and maximum
+    over the mapped-back items (np.minimum / np.maximum: the envelope of unetdc_dihedral_mean_env_f32).  Only lo <= hi holds: the
+    rounded fp32 mean of equal values may miss them, so nothing may assume lo <= mean <= hi."""
+    p, vs = _square(np.asarray(p, np.float32), 3, "mean"), variants(N)
+    mean = mean_numpy(p, N)
+    lo = hi = variant_inverse(p[0::len(vs)], vs[0])
+    for i, v in enumerate(vs[1:], 1):
+        q = variant_inverse(p[i::len(vs)], v)
+        lo, hi = np.minimum(lo, q), np.maximum(hi, q)
+    return mean, np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+
+
 def mean_numpy64(p, N):
     """The same rule in fp64 (the yardstick of the tests)."""
     return _mean(p, N, np.float64)
@@ -82,16 +95,20 @@ def groups(n, N, batch):
     return [(b0, min(G, n - b0)) for b0 in range(0, n, G)]
 
 
-def predict_tta_cpu(model, x, N, batch):
+def predict_tta_cpu(model, x, N, batch, envelope=False):
     """CPU path of unet_dc_segmentation_amd.tta.predict_tta: x [n, C, S, S] fp32 (torch, on the CPU) -> [n, 1, S, S] fp32
-    probabilities: expand_numpy of every group, its items through `model` in slices of `batch` under no_grad, mean_numpy."""
+    probabilities: expand_numpy of every group, its items through `model` in slices of `batch` under no_grad, mean_numpy.
+    envelope: -> (mean, lo, hi) of mean_env_numpy instead, three tensors of that shape."""
     import torch
     N, batch = check_tta(N), max(1, int(batch))
     xn = _square(x.detach().numpy(), 4, "predict_tta_cpu")
-    out = np.empty((xn.shape[0], 1) + xn.shape[2:], np.float32)
+    out = np.empty((3 if envelope else 1, xn.shape[0], 1) + xn.shape[2:], np.float32)
     with torch.no_grad():
         for b0, g in groups(xn.shape[0], N, batch):
             items = torch.from_numpy(expand_numpy(xn[b0:b0 + g], N))
             p = torch.cat([model(items[i:i + batch])[:, 0].float() for i in range(0, g * N, batch)])
-            out[b0:b0 + g, 0] = mean_numpy(p.numpy(), N)
-    return torch.from_numpy(out)
+            if envelope:
+                out[:, b0:b0 + g, 0] = mean_env_numpy(p.numpy(), N)
+            else:
+                out[0, b0:b0 + g, 0] = mean_numpy(p.numpy(), N)
+    return tuple(torch.from_numpy(o) for o in out) if envelope else torch.from_numpy(out[0])
