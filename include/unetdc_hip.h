@@ -621,6 +621,35 @@ int unetdc_label_confidence(const int32_t* label, int max_out, int h, int w, con
                             unetdc_stream_t s);
 
 
+/* ---- convex hull, solidity and Feret integers per droplet (hull.hip; the definition is DESIGN.md section 24) -----------------
+ * unetdc_label_hull: label ([h][w] int32: 0 = background, droplets 1..max_out; any label map: labels may touch and need not be
+ *   connected; values below 1 or above max_out are skipped).  The point set of label k is the union of the closed unit squares
+ *   [x, x + 1] x [y, y + 1] of its pixels (y, x); its convex hull has lattice vertices in 0..w x 0..h and is taken without
+ *   collinear points, so a label with a pixel has at least 4 vertices and area >= 1.
+ *   -> out[UNETDC_HULL_QUANTITIES][max_out] int64, row j of droplet k at out[j * max_out + k - 1]:
+ *     0 H2   twice the hull's area (shoelace sum)
+ *     1 F2   the largest squared distance between two hull vertices (Feret maximum squared)
+ *     2 Wc   of the minimising edge e = (p -> q): max over vertices v of |e x (v - p)|
+ *     3 Wl   that edge's squared length |e|^2
+ *     4 nv   number of hull vertices
+ *   The minimising edge is the one with the smallest Wc^2 / Wl (the squared caliper width across it), compared exactly by
+ *   cross-multiplication in 128 bits; among equal ratios the one with the smallest Wl, which makes (Wc, Wl) unique.  A number
+ *   without pixels keeps 0 in all five rows.
+ *   *out_rows = the number of row-extent slots needed: the sum over the labels with pixels of max_y - min_y + 1.  If that
+ *   exceeds max_rows, *out_rows = max_rows + 1 and out is unspecified (nothing outside it is written): repeat with more room.
+ *   max_rows = h * w suffices for connected labels (every row between a connected label's first and last holds one of its
+ *   pixels); it need not for scattered ones, whose rows in between count without holding a pixel.  max_rows <= 2^28.
+ *   max_out = 0 is allowed (out may then be NULL).  Nothing but the outputs and the workspace is written, and the workspace may
+ *   hold anything on entry.  Sides 1..16384; max_out, max_rows >= 0; workspace: unetdc_label_hull_workspace(h, w, max_out,
+ *   max_rows) bytes (0 for arguments the call would refuse), 4-byte aligned.  UNETDC_EINVAL before any launch for a null pointer
+ *   or a refused geometry.  Launches on the given stream only; no host wait, no allocation.  Integer atomic minima and maxima
+ *   and sequential integer chains: bitwise reproducible. */
+#define UNETDC_HULL_QUANTITIES 5
+int64_t unetdc_label_hull_workspace(int h, int w, int max_out, int max_rows);
+int unetdc_label_hull(const int32_t* label, int max_out, int h, int w, void* workspace, int64_t workspace_bytes, int64_t* out,
+                      int32_t* out_rows, int max_rows, unetdc_stream_t s);
+
+
 /* ---- overlap table of two label maps (match.hip; the definition is DESIGN.md section 12) ------------------------------------
  * unetdc_label_overlap: label_a, label_b ([h][w] int32 each: 0 = background, objects 1..max_a and 1..max_b; any label maps,
  *   touching labels allowed) -> the triples (a, b, n) with n > 0 = the number of pixels that carry label a on the first map

@@ -21,6 +21,7 @@ and a few integers per droplet come back:
     --neighbors       (droplets.py)                             csrc/neighbors.hip      CPU: utils/droplet_neighbors.py
     --boundary        unet_dc_segmentation_amd/evaluate.py      csrc/boundary.hip       CPU: utils/droplet_boundary.py
     --confidence      (droplets.py, tta.py)                     csrc/confidence.hip tta.hip  CPU: utils/droplet_confidence.py
+    --droplet_hull    (droplets.py)                             csrc/hull.hip           CPU: utils/droplet_hull.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -103,21 +104,22 @@ class Run:
     contact_tables: list = dataclasses.field(default_factory=list)  # droplet_contacts.csv, one table per image
     boundary: dict | None = None       # boundary_options(); its "records" collect boundary_per_image.csv
     confidence: dict | None = None     # confidence_options(); its "rows" collect confidence_per_image.csv
+    hull: float | None = None          # --droplet_hull: the solidity below which a droplet is flagged, None without the flag
 
     @property
     def envelope(self):
         """Whether the forward also keeps the minimum and maximum over the variants: only with both --tta and --confidence."""
         return self.tta is not None and self.confidence is not None
 
-    def droplet_options(self, labels, shape, confidence=False):
+    def droplet_options(self, labels, shape, confidence=False, hull=False):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
-        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors and --confidence select it by
-        themselves."""
+        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors, --confidence and --droplet_hull
+        select it by themselves."""
         c = self.clean or {"low": None, "holes": 0}
         conf = self.confidence if confidence else None
-        route = self.split_depth is None and self.neighbors is None and conf is None
+        route = self.split_depth is None and self.neighbors is None and conf is None and not hull
         return DropletOptions(self.split_depth, shape or (labels and route), labels, c["low"], c["holes"], self.neighbors,
-                              None if conf is None else conf["band"], conf is not None and conf["maps"])
+                              None if conf is None else conf["band"], conf is not None and conf["maps"], hull)
 
     def submit(self, fn, *args):
         """PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
@@ -198,25 +200,26 @@ def _components(bin_mask, min_area):
     return area, cen[:, 0], cen[:, 1]
 
 
-def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None, confidence=None):
+def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None, confidence=None, hull=False):
     """CPU path: the record that droplets.mask_and_droplets_batch returns per image, in host arrays, from the uint8 mask at
     the image's size.  split_depth: the split droplets (utils/droplet_split.py); shape: the integers of
     utils.droplet_shape.label_props_numpy on the label map and the grey plane, centroids then the integer sums over the
     area as on the device; labels: the int32 label map whose numbers are the rows of the table; neighbors (a radius): the
     record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well; confidence
-    (the keywords probs, thresh, band, lo, hi, maps of utils.droplet_confidence.confidence_numpy): its record on the label map."""
+    (the keywords probs, thresh, band, lo, hi, maps of utils.droplet_confidence.confidence_numpy): its record on the label map;
+    hull: the integers of utils.droplet_hull.label_hull_numpy on the label map."""
     lab = None
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
         lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
-    elif shape or labels or neighbors is not None or confidence is not None:
+    elif shape or labels or neighbors is not None or confidence is not None or hull:
         from utils.droplet_match import gt_labels_numpy
         lab = gt_labels_numpy(bin_mask, min_area)
     if shape:
         from utils.droplet_shape import label_props_numpy
         props = label_props_numpy(lab, gray)
         area, sy, sx = props["area"], props["Sy"], props["Sx"]
-    elif split_depth is None and (neighbors is not None or confidence is not None):
+    elif split_depth is None and (neighbors is not None or confidence is not None or hull):
         from utils.droplet_match import label_sums
         area, sy, sx = label_sums(lab)
     elif split_depth is None:
@@ -231,6 +234,9 @@ def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, l
         conf = confidence_numpy(lab, max_out=len(area), **confidence)
     out = Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None, neighbors=nb)
     out.confidence = conf
+    if hull:
+        from utils.droplet_hull import label_hull_numpy
+        out.hull = label_hull_numpy(lab, len(area))
     return out
 
 
@@ -330,6 +336,16 @@ def add_confidence_outputs(run, df, d, filename, name):
     return df
 
 
+def add_hull_outputs(run, df, d):
+    """--droplet_hull: the columns of utils.droplet_hull.hull_columns behind the droplet table's own -> (the table, the numbers
+    its row of summary_per_image.csv gains)."""
+    from utils import droplet_hull as dh
+    cols = dh.hull_columns(d.hull, d.area, run.hull, run.px_per_um)
+    if not df.empty:
+        df = pd.concat([df, pd.DataFrame(cols, index=df.index)], axis=1)
+    return df, dh.hull_summary(cols)
+
+
 def _write_map(plane, path):
     Image.fromarray(plane).save(str(path))
 
@@ -401,6 +417,7 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
     CPU the same records come from droplets_cpu and match_cpu.  sweeping: a threshold of --sweep_objects, where only the
     matching is read: no shape columns, no grey planes, no boundary distances.  With --boundary every match result carries the
     record of DESIGN.md section 21 under "boundary" (device: one more batch of launches and one more wait, evaluate.boundary_batch).
+    With --droplet_hull (never while sweeping) every Droplets carries the integers of DESIGN.md section 24.
     With --confidence (never while sweeping) every Droplets carries the record of DESIGN.md section 23; envelope: the (lo, hi) maps
     of --tta, shaped like probs."""
     gt, hws = run.gt, [m[1] for m in batch.meta]
@@ -408,12 +425,13 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
     want_labels = gt is not None or run.split_depth is not None
     shape = run.shape and not sweeping
     conf = run.confidence if not sweeping else None
+    hull = run.hull is not None and not sweeping
     if probs.is_cuda:
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
         gray = [torch.from_numpy(g).to(DEVICE) for g in batch.grays] if shape else None   # up behind the network's launches
         more = {} if conf is None or envelope is None else {"envelope": tuple(e[:, 0] for e in envelope)}
         out, sums = mask_and_droplets_batch(probs[:, 0], thresh, hws, run.min_area, keep_sums=True, gray=gray,
-                                            options=run.droplet_options(want_labels, shape, conf is not None), **more)
+                                            options=run.droplet_options(want_labels, shape, conf is not None, hull), **more)
         if gt is None:
             return out, None, sums
         from unet_dc_segmentation_amd.evaluate import boundary_batch, match_batch
@@ -433,7 +451,7 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
         if conf is not None:
             lo, hi = (None, None) if envelope is None else (e[i, 0].numpy() for e in envelope)
             ckw = {"probs": p[i], "thresh": thresh, "band": conf["band"], "lo": lo, "hi": hi, "maps": conf["maps"]}
-        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors, ckw)
+        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors, ckw, hull)
         d.clean_counts = np.asarray(counts, np.int64)
         out.append(d)
     if gt is None:
@@ -511,6 +529,9 @@ def finish_batch(run, batch, probs):
             df, more = add_neighbor_outputs(run, df, d, filename)
         if run.confidence is not None:
             df = add_confidence_outputs(run, df, d, filename, name)
+        if run.hull is not None:
+            df, hull_more = add_hull_outputs(run, df, d)
+            more = {**more, **hull_more}
         if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
             run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
@@ -625,6 +646,13 @@ def build_parser():
                         "Probabilities are read at the nearest source pixel of each mask pixel and quantised to 16 bits")
     p.add_argument("--confidence_maps", action="store_true",
                    help="with --confidence: also write NAME_entropy.png and, with --tta, NAME_spread.png (8-bit maps)")
+    p.add_argument("--droplet_hull", type=float, nargs="?", const=0.9, metavar="S",
+                   help="per-droplet convex hull of the pixel squares: adds area_convex, solidity (area / area_convex: a single "
+                        "droplet is convex and near 1, two fused ones are not), feret_diameter_max and feret_diameter_min (the "
+                        "largest and smallest caliper width), feret_ratio, hull_vertices and low_solidity (solidity < S; S in "
+                        "(0, 1], 0.9 without S -- a convention, not a measured number) to the droplet tables, with "
+                        "--px_per_micron also feret_max_micron, feret_min_micron, area_convex_sqmicron; summary_per_image.csv "
+                        "gains solidity_median, feret_max_median and n_low_solidity")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -748,6 +776,13 @@ def main(argv=None):
     tta = tta_options(args)
     boundary = boundary_options(args)
     confidence = confidence_options(args)
+    hull = None
+    if args.droplet_hull is not None:
+        from utils.droplet_hull import check_solidity
+        try:
+            hull = check_solidity(args.droplet_hull)
+        except ValueError as e:
+            raise SystemExit(f"--droplet_hull S: {e}")
     images = sorted(p for p in in_dir.iterdir() if p.suffix.lower() in IMAGE_SUFFIXES)
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
@@ -777,7 +812,7 @@ def main(argv=None):
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
-                  neighbors=args.neighbors, boundary=boundary, confidence=confidence)
+                  neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull)
         ahead = deque()
         it = iter(images)
 

@@ -629,6 +629,16 @@ int unetdc_label_confidence(const int32_t* label, int max_out, int h, int w, con
                                  out_spread_u8, (hipStream_t)s);
 }
 
+static_assert(UNETDC_HULL_QUANTITIES == HULL_QUANTITIES, "unetdc_label_hull output rows");
+
+int64_t unetdc_label_hull_workspace(int h, int w, int max_out, int max_rows) { return label_hull_workspace_bytes(h, w, max_out, max_rows); }
+
+int unetdc_label_hull(const int32_t* label, int max_out, int h, int w, void* workspace, int64_t workspace_bytes, int64_t* out,
+                      int32_t* out_rows, int max_rows, unetdc_stream_t s) {
+  return launch_label_hull(label, max_out, h, w, workspace, (long)workspace_bytes, reinterpret_cast<long long*>(out), out_rows,
+                           max_rows, (hipStream_t)s);
+}
+
 int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) { return label_overlap_workspace_bytes(h, w, max_pairs); }
 
 int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,

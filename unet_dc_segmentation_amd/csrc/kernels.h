@@ -308,6 +308,13 @@ int launch_label_overlap(const int* label_a, int max_a, const int* label_b, int 
                          long workspace_bytes, int* out_count, int* out_a, int* out_b, int* out_n, int max_pairs,
                          hipStream_t stream);
 
+// hull.hip: twice the hull area, the largest squared vertex distance, the minimum-width edge's (Wc, Wl) and the vertex count of
+// the convex hull of the pixel squares of every label of an int32 label map
+constexpr int HULL_QUANTITIES = 5;
+long label_hull_workspace_bytes(int h, int w, int max_out, int max_rows);               // 0 for arguments the call refuses
+int launch_label_hull(const int* label, int max_out, int h, int w, void* workspace, long workspace_bytes, long long* out,
+                      int* out_rows, int max_rows, hipStream_t stream);
+
 // neighbors.hip: contact pairs, nearest contact, degree and cluster of the labels of an int32 label map
 long label_neighbors_workspace_bytes(int h, int w, int max_label, int max_pairs);       // 0 for arguments the call refuses
 int launch_label_neighbors(const int* label, int max_label, int h, int w, int radius, void* workspace, long workspace_bytes,

@@ -60,7 +60,7 @@ class DropletOptions:
     split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
     than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py).
     shape: also the per-droplet integers that utils.droplet_shape.shape_columns reads (csrc/shape.hip).
-    labels: also the int32 label map; needs a split depth, shape, neighbors or confidence.
+    labels: also the int32 label map; needs a split depth, shape, neighbors, confidence or hull.
     thresh_low (<= thresh) / max_hole_area (0 = off, negative = any size, N = holes of at most N pixels): the mask is
     cleaned first (hysteresis threshold, hole filling: csrc/clean.hip).
     neighbors (contact radius in pixels, an integer 1..64; None = off): also the contact pairs and the per-droplet nearest
@@ -68,6 +68,8 @@ class DropletOptions:
     confidence (the uncertainty band, 0..0.5; None = off): also the per-droplet and per-image integers of the quantised
     probability, its entropy and, given envelope=(lo, hi), the disagreement of the TTA variants (csrc/confidence.hip,
     utils/droplet_confidence.py); confidence_maps: also the uint8 entropy and spread maps, on the device.
+    hull: also the per-droplet integers of the convex hull that utils.droplet_hull.hull_columns reads (csrc/hull.hip, DESIGN.md
+    section 24).
     thresh / gray are not kept: the threshold the low one is checked against, and the grey planes, which need shape."""
     split_depth: float | None = None
     shape: bool = False
@@ -77,11 +79,12 @@ class DropletOptions:
     neighbors: int | None = None
     confidence: float | None = None
     confidence_maps: bool = False
+    hull: bool = False
     thresh: dataclasses.InitVar[float | None] = None
     gray: dataclasses.InitVar[object] = None
 
     def __post_init__(self, thresh, gray):
-        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None and self.confidence is None:
+        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None and self.confidence is None and not self.hull:
             raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
         if self.neighbors is not None:
             from utils.droplet_neighbors import check_radius
@@ -105,7 +108,7 @@ class DropletOptions:
     @property
     def label_map(self):
         """Whether a stage reads the int32 label map (without a split depth that selects unetdc_ccl_labels)."""
-        return self.shape or self.neighbors is not None or self.confidence is not None
+        return self.shape or self.neighbors is not None or self.confidence is not None or self.hull
 
     @property
     def half_pixels(self):
@@ -145,8 +148,9 @@ class Droplets:
     per-droplet int64 arrays that utils.droplet_shape.shape_columns reads (None without shape); clean_counts: int64 [4],
     the counts of utils.droplet_clean.COUNT_NAMES (zeros when cleaning is off); neighbors: the record of
     utils.droplet_neighbors.neighbors_numpy, int64 arrays (None unless asked for); confidence: the record of
-    utils.droplet_confidence.confidence_numpy (None unless asked for), its two maps DEVICE tensors.  The CPU path of the script
-    fills the same record with host arrays."""
+    utils.droplet_confidence.confidence_numpy (None unless asked for), its two maps DEVICE tensors; hull: the dict of five int64
+    arrays that utils.droplet_hull.hull_columns reads (None unless asked for).  The CPU path of the script fills the same record
+    with host arrays."""
     mask: object
     area: np.ndarray
     centroid_row: np.ndarray
@@ -156,6 +160,7 @@ class Droplets:
     clean_counts: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(4, np.int64))
     neighbors: dict | None = None
     confidence = None             # set by name after construction: the constructor's fields stay those of the stages before
+    hull = None                   # likewise
 
     def __iter__(self):
         return iter((self.mask, self.area, self.centroid_row, self.centroid_col))
@@ -175,16 +180,18 @@ class _Image(NamedTuple):
     pairs: torch.Tensor | None = None          # int32 [3, pair room]: a, b, d2
     per_label: torch.Tensor | None = None      # int32 [5, cap]: the rows of utils.droplet_neighbors.COLUMN_NAMES
     conf: tuple | None = None                  # confidence: (lo, hi fp32 [ph, pw] or None, int64 [8] image totals, the two uint8 maps or None)
+    hull_rows: torch.Tensor | None = None      # int32, the row-extent slots unetdc_label_hull needed first
 
 
-def _enqueue(im, thresh, min_area, ws, opts, s):
+def _enqueue(im, thresh, min_area, ws, opts, s, row_room=0):
     """One image's launches on the stream s: the mask of the threshold; unetdc_mask_clean in place on it (the weak
     mask is that of the low threshold under the same resize rule); labelling + sums + compaction by unetdc_ccl_stats,
     with a split depth unetdc_split_stats (which also fills the label map when there is one), with shape and no split
     depth unetdc_ccl_labels (so does neighbors); then with shape unetdc_label_props on the label map and the optional grey
     plane; then with neighbors unetdc_label_neighbors on the label map, the droplet capacity as its max_label; then with
     confidence unetdc_label_confidence on the label map and the probabilities (and the envelope), the capacity as its max_out,
-    into the rows of `sums` behind those of shape."""
+    into the rows of `sums` behind those of shape; then with hull unetdc_label_hull on the label map, the capacity as its max_out
+    and `row_room` row-extent slots, into the rows of `sums` behind those."""
     (oh, ow), cap, h2, clean = im.mask.shape, im.area.shape[0], opts.half_pixels, opts.cleaning(thresh)
     _mask_from_probs(im.probs, thresh, im.mask, s)
     if clean is not None:
@@ -216,6 +223,9 @@ def _enqueue(im, thresh, min_area, ws, opts, s):
         _lib.call("unetdc_label_confidence", label, cap, oh, ow, im.probs.data_ptr(), *(None if t is None else t.data_ptr() for t in (lo, hi)),
                   ph, pw, float(thresh), float(opts.confidence), _entropy_table(im.probs.device).data_ptr(),
                   im.sums[2 + NQ * opts.shape].data_ptr(), totals.data_ptr(), *(None if t is None else t.data_ptr() for t in (emap, smap)), s)
+    if opts.hull:
+        _lib.call("unetdc_label_hull", label, cap, oh, ow, ws.data_ptr(), ws.numel(),
+                  im.sums[2 + NQ * opts.shape + NC * (opts.confidence is not None)].data_ptr(), im.hull_rows.data_ptr(), row_room, s)
 
 
 _tables = {}
@@ -255,7 +265,7 @@ def _confidence_dict(rows, totals, envelope, maps):
     return {**dict(zip(CONF_QUANTITIES, rows)), "image": totals, "envelope": envelope, "entropy_u8": maps[0], "spread_u8": maps[1]}
 
 
-def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room):
+def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room, row_room=0):
     query = (lib.unetdc_split_workspace if opts.split_depth is not None else
              lib.unetdc_ccl_labels_workspace if opts.label_map else lib.unetdc_ccl_workspace)
     nbytes = max(query(h, w) for h, w in out_hws)
@@ -263,11 +273,21 @@ def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room):
         nbytes = max(nbytes, max(lib.unetdc_label_neighbors_workspace(h, w, cap, pair_room) for h, w in out_hws))
     if clean is not None:
         nbytes = max(nbytes, max(lib.unetdc_mask_clean_workspace(h, w) for h, w in out_hws))
+    if opts.hull:
+        nbytes = max(nbytes, max(lib.unetdc_label_hull_workspace(h, w, cap, row_room) for h, w in out_hws))
     return nbytes
 
 
+HULL_QUANTITIES = ("H2", "F2", "Wc", "Wl", "nv")    # the rows of unetdc_label_hull, as utils.droplet_hull.QUANTITIES names them
 NQ = 14    # UNETDC_SHAPE_QUANTITIES
 NC = 10    # UNETDC_CONF_QUANTITIES
+NH = 5     # UNETDC_HULL_QUANTITIES
+# Row-extent slots per droplet of the capacity that the first launch of unetdc_label_hull has room for.  The slots needed are the
+# sum of the droplets' heights.  The droplets of the flow are connected, so that sum is at most h * w, and the room is capped
+# there: then it always suffices.  Below the cap, 64 rows per droplet is three times the about 20 rows of a median droplet of a
+# 1040 x 1388 micrograph and 512 KB of workspace per 1024 droplets; an image of taller droplets than that is run again with
+# twice the room, like one with more contact pairs than the pair lists hold.
+ROWS_PER_DROPLET = 64
 PAIR_ROOM = 1 << 14    # contact pairs per image the first launch has room for; an image with more is run again with twice that
 MAX_PAIR_ROOM = 1 << 27   # the largest table of unetdc_label_neighbors
 
@@ -277,13 +297,20 @@ def _pair_room(cap, wanted):
     return int(min(wanted, cap * (cap - 1) // 2, MAX_PAIR_ROOM))
 
 
-def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None, envelope=None):
+def _row_room(cap, out_hws, wanted=None):
+    """The row-extent room of unetdc_label_hull: `wanted` slots (default ROWS_PER_DROPLET per droplet of the capacity), at most
+    h * w of the largest image -- the sum of the heights of connected droplets cannot pass that."""
+    return int(min(ROWS_PER_DROPLET * cap if wanted is None else wanted, max(h * w for h, w in out_hws)))
+
+
+def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None, envelope=None, row_room=None):
     """The one launch-and-readback body -> (B Droplets, the device outputs (count, area, sumy, sumx) or None when an image
     had more droplets than they hold).  Every launch of the batch is enqueued back to back on the current stream into ONE
     set of output planes; the host then waits ONCE: one device->host copy brings the B droplet counts (and the clean
     counts and with neighbors the pair counts behind them), two more the filled part of the per-droplet integers; with
     neighbors one more the per-droplet neighbour integers and one the filled part of the pair lists.  The integers of confidence
-    add no copy: the per-droplet rows lie behind the sums, the per-image totals (int64) behind the counts."""
+    add no copy: the per-droplet rows lie behind the sums, the per-image totals (int64) behind the counts.  Nor do those of hull:
+    its rows lie behind those of confidence, the row-extent slots each image needed behind the pair counts."""
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -301,20 +328,24 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
             _check_gray(g, oh, ow)
     nb = opts.neighbors is not None
     room = _pair_room(cap, PAIR_ROOM if pair_room is None else pair_room) if nb else 0
-    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, cap, room), dtype=torch.uint8, device=dev)   # one: stream order
-    nc, cf = B * (1 if clean is None else 5), opts.confidence is not None
-    n32 = nc + B * nb
+    rows = _row_room(cap, out_hws, row_room) if opts.hull else 0
+    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, cap, room, rows), dtype=torch.uint8, device=dev)   # one: stream order
+    nc, cf, hl = B * (1 if clean is None else 5), opts.confidence is not None, bool(opts.hull)
+    n32 = nc + B * nb + B * hl
     at64 = (n32 + 1) // 2 * 2                                          # the int64 totals start on an 8-byte boundary
-    # droplet counts, then 4 per image, then the pair counts; then with confidence 8 int64 per image (16 int32 slots)
+    # droplet counts, then 4 per image, then the pair counts, then the hull's row counts; then with confidence 8 int64 per image
+    # (16 int32 slots)
     counts = torch.zeros(at64 + 16 * B if cf else n32, dtype=torch.int32, device=dev)
     totals = counts[at64:].view(torch.int64) if cf else None
     pairs = torch.empty(B, 3, room, dtype=torch.int32, device=dev) if nb else None
     per_label = torch.empty(B, 5, cap, dtype=torch.int32, device=dev) if nb else None
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
     # per image: sum y, sum x, then with shape the rows of unetdc_label_props, which wants them [NQ][cap] in one piece
-    # and with confidence behind them the rows of unetdc_label_confidence, [NC][cap] in one piece as well
+    # and with confidence behind them the rows of unetdc_label_confidence, [NC][cap] in one piece as well, then those of
+    # unetdc_label_hull, [NH][cap]
     r0 = 2 + NQ * opts.shape
-    sums = torch.empty(B, r0 + NC * cf, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
+    rh = r0 + NC * cf
+    sums = torch.empty(B, rh + NH * hl, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
     images = []
     for i, (oh, ow) in enumerate(out_hws):
         images.append(_Image(probs[i], torch.empty(oh, ow, dtype=torch.uint8, device=dev),
@@ -325,13 +356,13 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
                              (*((envelope[0][i], envelope[1][i]) if envelope is not None else (None, None)), totals[8 * i:],
                               torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps else None,
                               torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps and envelope is not None else None)
-                             if cf else None))
-        _enqueue(images[i], thresh, min_area, ws, opts, s)
+                             if cf else None, counts[nc + B * nb + i:] if hl else None))
+        _enqueue(images[i], thresh, min_area, ws, opts, s, rows)
     raw = counts.cpu().numpy()                                      # the batch's only host wait
     t_h = raw[at64:].view(np.int64).reshape(B, 8) if cf else None
     n = raw[:n32].astype(np.int64)
     clean_counts = n[B:nc].reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
-    n_pairs, n = n[nc:], n[:B]
+    n_pairs, n_rows, n = n[nc:nc + B * nb], n[nc + B * nb:], n[:B]
     nmax = int(min(n.max(initial=0), cap))
     a_h = area[:, :nmax].cpu().numpy().astype(np.int64)
     s_h = sums[:, :, :nmax].cpu().numpy()
@@ -339,18 +370,23 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
         l_h = per_label[:, :, :nmax].cpu().numpy().astype(np.int64)
         p_h = pairs[:, :, :int(min(n_pairs.max(initial=0), room))].cpu().numpy().astype(np.int64)
     out = []
+    def again(i, max_droplets, pair_room, row_room):
+        return _droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, max_droplets, None if gray is None else gray[i:i + 1], opts,
+                         pair_room, None if envelope is None else tuple(t[i:i + 1] for t in envelope), row_room)[0][0]
+
     for i, im in enumerate(images):
         if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
-            out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, int(n[i]),
-                                 None if gray is None else gray[i:i + 1], opts, pair_room,
-                                 None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
+            out.append(again(i, int(n[i]), pair_room, row_room))
             continue
         if nb and n_pairs[i] > room:              # more contact pairs than the pair lists hold: this image again with twice the room
             if room >= MAX_PAIR_ROOM:
                 raise _lib.UnetdcError(f"more than {MAX_PAIR_ROOM} contact pairs in one image")
-            out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, max_droplets,
-                                 None if gray is None else gray[i:i + 1], opts, 2 * max(room, 1),
-                                 None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
+            out.append(again(i, max_droplets, 2 * max(room, 1), row_room))
+            continue
+        if hl and n_rows[i] > rows:               # taller droplets than the row room holds: this image again with twice the room
+            if rows >= out_hws[i][0] * out_hws[i][1]:
+                raise _lib.UnetdcError("unetdc_label_hull: connected droplets need more row room than the image has pixels")
+            out.append(again(i, max_droplets, pair_room, 2 * max(rows, 1)))
             continue
         a, si = a_h[i, :n[i]], s_h[:, i, :n[i]]
         d = np.maximum(a, 1)
@@ -359,6 +395,8 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
                             clean_counts[i], _neighbors_dict(p_h[i, :, :n_pairs[i]], l_h[i, :, :n[i]]) if nb else None))
         if cf:
             out[-1].confidence = _confidence_dict(si[r0:r0 + NC], t_h[i], envelope is not None, im.conf[3:])
+        if hl:
+            out[-1].hull = dict(zip(HULL_QUANTITIES, si[rh:rh + NH]))
     return out, ((counts[:B], area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
 
 
@@ -366,7 +404,7 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     """probs: [B, H, W] fp32 probabilities on the HIP device; out_hws: B (oh, ow) pairs -> a list of B Droplets, after
     ONE host wait for the whole batch (_droplets).  keep_sums=True returns (that list, the device outputs (count, area,
     sumy, sumx) or None when an image had more droplets than they hold) for density.density_maps_batch.
-    options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors, confidence, confidence_maps by name, or
+    options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors, confidence, confidence_maps, hull by name, or
     options=DropletOptions(...); gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none); and
     envelope=(lo, hi), two fp32 DEVICE tensors shaped like probs (tta.predict_tta(..., envelope=True)), for the disagreement
     integers of confidence (None: those keep their initial values).  Every option adds its launches
