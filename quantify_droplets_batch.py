@@ -113,13 +113,15 @@ class Run:
 
     def droplet_options(self, labels, shape, confidence=False, hull=False):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
-        route (unetdc_ccl_labels), so asking for labels selects that route; --neighbors, --confidence and --droplet_hull
-        select it by themselves."""
+        route (unetdc_ccl_labels), so asking for labels selects that route, unless a stage that reads the label map
+        (DropletOptions.label_map) has selected it already."""
         c = self.clean or {"low": None, "holes": 0}
         conf = self.confidence if confidence else None
-        route = self.split_depth is None and self.neighbors is None and conf is None and not hull
-        return DropletOptions(self.split_depth, shape or (labels and route), labels, c["low"], c["holes"], self.neighbors,
-                              None if conf is None else conf["band"], conf is not None and conf["maps"], hull)
+        opts = DropletOptions(split_depth=self.split_depth, shape=shape, thresh_low=c["low"], max_hole_area=c["holes"],
+                              neighbors=self.neighbors, confidence=None if conf is None else conf["band"],
+                              confidence_maps=conf is not None and conf["maps"], hull=hull)
+        route = labels and self.split_depth is None and not opts.label_map
+        return dataclasses.replace(opts, labels=labels, shape=shape or route)
 
     def submit(self, fn, *args):
         """PNG deflate and CSV formatting are the slowest part of an image once the network runs on the device: they go to
@@ -208,36 +210,35 @@ def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, l
     record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well; confidence
     (the keywords probs, thresh, band, lo, hi, maps of utils.droplet_confidence.confidence_numpy): its record on the label map;
     hull: the integers of utils.droplet_hull.label_hull_numpy on the label map."""
-    lab = None
+    lab, rec = None, {}
+    label_map = shape or neighbors is not None or confidence is not None or hull      # a stage reads it, as DropletOptions.label_map
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
         lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
-    elif shape or labels or neighbors is not None or confidence is not None or hull:
-        from utils.droplet_match import gt_labels_numpy
+    elif label_map or labels:
+        from utils.droplet_match import gt_labels_numpy, label_sums
         lab = gt_labels_numpy(bin_mask, min_area)
-    if shape:
-        from utils.droplet_shape import label_props_numpy
-        props = label_props_numpy(lab, gray)
-        area, sy, sx = props["area"], props["Sy"], props["Sx"]
-    elif split_depth is None and (neighbors is not None or confidence is not None or hull):
-        from utils.droplet_match import label_sums
-        area, sy, sx = label_sums(lab)
-    elif split_depth is None:
-        return Droplets(bin_mask, *_components(bin_mask, min_area), labels=lab)
-    d = np.maximum(area, 1)
-    nb = conf = None
-    if neighbors is not None:
-        from utils.droplet_neighbors import neighbors_numpy
-        nb = neighbors_numpy(lab, len(area), neighbors)
-    if confidence is not None:
-        from utils.droplet_confidence import confidence_numpy
-        conf = confidence_numpy(lab, max_out=len(area), **confidence)
-    out = Droplets(bin_mask, area, sy.astype(np.float64) / d, sx.astype(np.float64) / d, lab, props if shape else None, neighbors=nb)
-    out.confidence = conf
-    if hull:
-        from utils.droplet_hull import label_hull_numpy
-        out.hull = label_hull_numpy(lab, len(area))
-    return out
+        if label_map and not shape:                      # shape brings its own
+            area, sy, sx = label_sums(lab)
+    if split_depth is None and not label_map:
+        area, cen_row, cen_col = _components(bin_mask, min_area)
+    else:                                                # then the stages, in the order of the device's
+        if shape:
+            from utils.droplet_shape import label_props_numpy
+            rec["props"] = label_props_numpy(lab, gray)
+            area, sy, sx = (rec["props"][q] for q in ("area", "Sy", "Sx"))
+        if neighbors is not None:
+            from utils.droplet_neighbors import neighbors_numpy
+            rec["neighbors"] = neighbors_numpy(lab, len(area), neighbors)
+        if confidence is not None:
+            from utils.droplet_confidence import confidence_numpy
+            rec["confidence"] = confidence_numpy(lab, max_out=len(area), **confidence)
+        if hull:
+            from utils.droplet_hull import label_hull_numpy
+            rec["hull"] = label_hull_numpy(lab, len(area))
+        d = np.maximum(area, 1)
+        cen_row, cen_col = sy.astype(np.float64) / d, sx.astype(np.float64) / d
+    return Droplets(bin_mask, area, cen_row, cen_col, labels=lab, **rec)
 
 
 def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):

@@ -125,26 +125,34 @@ def test_more_droplets_than_the_first_output_capacity():
 # Per image, for an output size that differs from the probabilities' (MASK_RESIZE "reference": the linear resize); at equal
 # size the mask kernel is unetdc_mask_from_probs instead.  Recorded on the commit before the two launch paths became one.
 LINEAR, CLEAN, PROPS = "unetdc_mask_from_probs_linear", "unetdc_mask_clean", "unetdc_label_props"
+NEIGHBORS, CONFIDENCE, HULL = "unetdc_label_neighbors", "unetdc_label_confidence", "unetdc_label_hull"
+# case: (options, the launches of one image, the device->host copies of one batch)
 LAUNCHES = {
-    "plain": (dict(), [LINEAR, "unetdc_ccl_stats"]),
-    "split": (dict(split_depth=2.0), [LINEAR, "unetdc_split_stats"]),
-    "shape": (dict(shape=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
-    "shape_gray": (dict(shape=True, gray=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
-    "labels_shape": (dict(shape=True, return_labels=True), [LINEAR, "unetdc_ccl_labels", PROPS]),
-    "clean_low": (dict(thresh_low=0.3), [LINEAR, LINEAR, CLEAN, "unetdc_ccl_stats"]),
-    "clean_holes": (dict(max_hole_area=-1), [LINEAR, CLEAN, "unetdc_ccl_stats"]),
+    "plain": (dict(), [LINEAR, "unetdc_ccl_stats"], 3),
+    "split": (dict(split_depth=2.0), [LINEAR, "unetdc_split_stats"], 3),
+    "shape": (dict(shape=True), [LINEAR, "unetdc_ccl_labels", PROPS], 3),
+    "shape_gray": (dict(shape=True, gray=True), [LINEAR, "unetdc_ccl_labels", PROPS], 3),
+    "labels_shape": (dict(shape=True, return_labels=True), [LINEAR, "unetdc_ccl_labels", PROPS], 3),
+    "clean_low": (dict(thresh_low=0.3), [LINEAR, LINEAR, CLEAN, "unetdc_ccl_stats"], 3),
+    "clean_holes": (dict(max_hole_area=-1), [LINEAR, CLEAN, "unetdc_ccl_stats"], 3),
     "all": (dict(split_depth=2.0, return_labels=True, shape=True, gray=True, thresh_low=0.3, max_hole_area=5),
-            [LINEAR, LINEAR, CLEAN, "unetdc_split_stats", PROPS]),
+            [LINEAR, LINEAR, CLEAN, "unetdc_split_stats", PROPS], 3),
+    # the stages added since: recorded on the commit before they moved into the stage table
+    "neighbors": (dict(neighbors=3), [LINEAR, "unetdc_ccl_labels", NEIGHBORS], 5),
+    "confidence": (dict(confidence=0.1), [LINEAR, "unetdc_ccl_labels", CONFIDENCE], 3),
+    "hull": (dict(hull=True), [LINEAR, "unetdc_ccl_labels", HULL], 3),
+    "everything": (dict(split_depth=2.0, return_labels=True, shape=True, gray=True, thresh_low=0.3, max_hole_area=5, neighbors=3,
+                        confidence=0.1, confidence_maps=True, hull=True),
+                   [LINEAR, LINEAR, CLEAN, "unetdc_split_stats", PROPS, NEIGHBORS, CONFIDENCE, HULL], 5),
 }
 
 
-@pytest.fixture(scope="module")
-def launch_probs():
-    """Two 64 x 64 maps of discs (0.9) with skirts (0.4) and a one-pixel hole."""
+def disc_maps(n):
+    """n 64 x 64 maps of discs (0.9) with skirts (0.4) and a one-pixel hole."""
     rng = np.random.default_rng(3)
     yy, xx = np.mgrid[0:64, 0:64]
-    p = np.full((2, 64, 64), 0.1, np.float32)
-    for i in range(2):
+    p = np.full((n, 64, 64), 0.1, np.float32)
+    for i in range(n):
         for _ in range(9):
             cy, cx, r = rng.integers(4, 60), rng.integers(4, 60), rng.integers(2, 8)
             d = (yy - cy) ** 2 + (xx - cx) ** 2
@@ -152,15 +160,20 @@ def launch_probs():
             p[i][d <= r * r] = 0.9
         p[i, 30:33, 30:33] = 0.9
         p[i, 31, 31] = 0.1
-    return torch.from_numpy(p).cuda()
+    return p
+
+
+@pytest.fixture(scope="module")
+def launch_probs():
+    return torch.from_numpy(disc_maps(2)).cuda()
 
 
 @pytest.mark.parametrize("case", sorted(LAUNCHES))
 def test_batch_and_single_image_launch_what_they_launched(case, launch_probs, monkeypatch):
     from unet_dc_segmentation_amd import _lib
     from unet_dc_segmentation_amd.droplets import mask_and_droplets, mask_and_droplets_batch
-    kw, linear = LAUNCHES[case]
-    kw = dict(kw)
+    kw, linear, copies = LAUNCHES[case]
+    kw, want = dict(kw), {"cpu": copies, "item": 0}
     equal = [n.replace("_linear", "") for n in linear]
     sizes = [(37, 53), (64, 96)]
     grays = {hw: torch.zeros(hw, dtype=torch.uint8, device="cuda") for hw in sizes + [(64, 64)]} if kw.pop("gray", False) else None
@@ -185,15 +198,90 @@ def test_batch_and_single_image_launch_what_they_launched(case, launch_probs, mo
     monkeypatch.setattr(torch.Tensor, "cpu", cpu)
     monkeypatch.setattr(torch.Tensor, "item", item)
     out, got, waits = launched(mask_and_droplets_batch, launch_probs, sizes, False)
-    assert got == linear + linear and waits == {"cpu": 3, "item": 0}
+    assert got == linear + linear and waits == want
     _, got, waits = launched(mask_and_droplets_batch, launch_probs[1:], [(64, 64)], False)
-    assert got == equal and waits == {"cpu": 3, "item": 0}
+    assert got == equal and waits == want
     one, got, waits = launched(mask_and_droplets, launch_probs[0], sizes[0], True)
-    assert got == linear and waits == {"cpu": 3, "item": 0}
+    assert got == linear and waits == want
     _, got, waits = launched(mask_and_droplets, launch_probs[1], (64, 64), True)
-    assert got == equal and waits == {"cpu": 3, "item": 0}
+    assert got == equal and waits == want
     assert len(one.area) > 1 and (one.labels is not None) == kw.get("return_labels", False) and (one.props is not None) == ("shape" in kw)
     assert torch.equal(one.mask, out[0].mask) and all(np.array_equal(x, y) for x, y in zip(list(one)[1:], list(out[0])[1:]))
+
+
+# ---- the optional stages share one int32 and one int64 allocation per batch: none may move another's numbers -------------------
+STAGES = {"props": dict(shape=True), "neighbors": dict(neighbors=3), "confidence": dict(confidence=0.1), "hull": dict(hull=True)}
+
+
+def same(a, b):
+    if isinstance(a, dict):
+        return isinstance(b, dict) and list(a) == list(b) and all(same(a[k], b[k]) for k in a)
+    if torch.is_tensor(a):
+        return torch.is_tensor(b) and torch.equal(a, b)
+    return type(a) is type(b) and np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("clean", [dict(), dict(thresh_low=0.3, max_hole_area=5)], ids=["raw", "clean"])
+@pytest.mark.parametrize("split", [dict(), dict(split_depth=1.0)], ids=["ccl", "split"])
+@pytest.mark.parametrize("B", [3, 2])
+def test_every_subset_of_stages_leaves_each_stage_its_own_numbers(B, split, clean):
+    """Every subset of the four stages that measure on the label map, with and without a split depth and cleaning, on batches
+    of 3 and 2 images (both parities of the int32 region, so both states of the pad before the int64 totals): each stage's
+    record equals, array by array, its record when it is the only stage on; mask, labels, areas, centroids and clean counts
+    equal those runs' too.  Integer work, one device, the same kernels: no tolerance."""
+    import itertools
+    from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
+    rng = np.random.default_rng(11)
+    p = disc_maps(3)[:B]
+    lo, hi = (p - rng.random(p.shape, dtype=np.float32) * np.float32(0.2), p + rng.random(p.shape, dtype=np.float32) * np.float32(0.2))
+    probs, env = torch.from_numpy(p).cuda(), tuple(torch.from_numpy(e.astype(np.float32)).cuda() for e in (lo, hi))
+    hws = [(37, 53), (64, 96), (64, 64)][:B]
+
+    def run(fields):
+        kw = dict(split, **clean)
+        for f in fields:
+            kw.update(STAGES[f])
+        if "confidence" in fields:
+            kw["envelope"] = env
+        return mask_and_droplets_batch(probs, 0.5, hws, 1, return_labels=bool(fields or split), **kw)
+    base = run(())
+    alone = {f: run((f,)) for f in STAGES}
+    assert min(len(d.area) for d in base) > 1
+    for k in range(len(STAGES) + 1):
+        for fields in itertools.combinations(STAGES, k):
+            for i, d in enumerate(run(fields)):
+                for f in STAGES:
+                    got = getattr(d, f)
+                    assert (got is None) if f not in fields else same(got, getattr(alone[f][i], f)), (fields, i, f)
+                ref = alone[fields[0]][i] if fields else base[i]
+                assert torch.equal(d.mask, ref.mask) and torch.equal(d.mask, base[i].mask), (fields, i)
+                assert (d.labels is None and ref.labels is None) or torch.equal(d.labels, ref.labels), (fields, i)
+                for name in ("area", "centroid_row", "centroid_col", "clean_counts"):
+                    assert np.array_equal(getattr(d, name), getattr(ref, name)), (fields, i, name)
+                    assert np.array_equal(getattr(d, name), getattr(base[i], name)), (fields, i, name)
+            assert bool(clean) == bool(base[0].clean_counts.any())
+
+
+def test_an_image_that_overflows_two_rooms_at_once_is_run_again_until_all_hold(monkeypatch):
+    """Room for 4 droplets, 2 contact pairs and one row-extent slot per droplet: every image overflows the droplet capacity,
+    then the pair lists and the row room, and comes out as with the default rooms."""
+    from tests.test_gpu_hull import batch_inputs
+    from unet_dc_segmentation_amd import droplets as D
+    hws, p = batch_inputs()
+    probs = torch.from_numpy(p).cuda()
+    kw = dict(neighbors=3, hull=True, return_labels=True)
+    want = D.mask_and_droplets_batch(probs, 0.5, hws, 2, **kw)
+    names, real = [], D._lib.call
+    monkeypatch.setattr(D, "PAIR_ROOM", 2)
+    monkeypatch.setattr(D, "ROWS_PER_DROPLET", 1)
+    monkeypatch.setattr(D._lib, "call", lambda name, *a: (names.append(name), real(name, *a))[1])
+    got = D.mask_and_droplets_batch(probs, 0.5, hws, 2, max_droplets=4, **kw)
+    assert names.count(NEIGHBORS) >= 2 * len(hws) and names.count(HULL) >= 2 * len(hws)
+    assert max(len(w.neighbors["pairs"]["a"]) for w in want) > 2         # the last image: 7 pairs, so room for 2, 4, then 8
+    for d, w in zip(got, want):
+        assert len(w.area) > 4 and int(w.hull["nv"].max()) >= 3           # a droplet spans rows: more row slots than droplets
+        assert same(d.neighbors, w.neighbors) and same(d.hull, w.hull) and torch.equal(d.labels, w.labels)
+        assert np.array_equal(d.area, w.area)
 
 
 # ---- unetdc_ccl_stats and the mask kernels through the C ABI, every output and the workspace (at exactly

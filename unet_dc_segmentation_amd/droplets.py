@@ -3,14 +3,21 @@ components -> the per-droplet table of the reference's ``quantify()`` (/root/ref
 
 Only the uint8 mask (needed for the PNG the script writes) and three integers per droplet cross PCIe; the reference
 copies every fp32 probability map to the host, labels it twice with scikit-image and walks ``np.unique`` in Python.
+
+Shape: DropletOptions in, one Droplets per image out, one launch-and-readback body (_droplets).  What runs before a label
+map exists (mask, cleaning, the choice of labelling kernel) is the explicit head of _enqueue; every optional stage that measures
+on the label map is one entry of _STAGES, and one _Layout per batch owns every offset into the batch's two shared buffers.
+DESIGN.md section 13 describes both.
 """
 from __future__ import annotations
 
+import collections
 import dataclasses
 from typing import NamedTuple
 
 import numpy as np
 import torch
+from utils import droplet_confidence, droplet_hull, droplet_neighbors, droplet_shape
 
 from . import _lib
 
@@ -60,7 +67,7 @@ class DropletOptions:
     split_depth (pixels, a multiple of 0.5; None = off): touching droplets are cut where the distance transform dips more
     than that below the lower of two peaks (csrc/split.hip, utils/droplet_split.py).
     shape: also the per-droplet integers that utils.droplet_shape.shape_columns reads (csrc/shape.hip).
-    labels: also the int32 label map; needs a split depth, shape, neighbors, confidence or hull.
+    labels: also the int32 label map; needs a split depth or a stage that reads the label map (label_map).
     thresh_low (<= thresh) / max_hole_area (0 = off, negative = any size, N = holes of at most N pixels): the mask is
     cleaned first (hysteresis threshold, hole filling: csrc/clean.hip).
     neighbors (contact radius in pixels, an integer 1..64; None = off): also the contact pairs and the per-droplet nearest
@@ -84,21 +91,16 @@ class DropletOptions:
     gray: dataclasses.InitVar[object] = None
 
     def __post_init__(self, thresh, gray):
-        if self.labels and self.split_depth is None and not self.shape and self.neighbors is None and self.confidence is None and not self.hull:
-            raise _lib.UnetdcError("return_labels needs a split_depth or shape=True")
-        if self.neighbors is not None:
-            from utils.droplet_neighbors import check_radius
-            try:
-                check_radius(self.neighbors)
-            except ValueError as e:
-                raise _lib.UnetdcError(str(e)) from None
-        if self.confidence is not None:
-            from utils.droplet_confidence import check_band
-            try:
-                check_band(self.confidence)
-            except ValueError as e:
-                raise _lib.UnetdcError(str(e)) from None
-        elif self.confidence_maps:
+        if self.labels and self.split_depth is None and not self.label_map:
+            raise _lib.UnetdcError("return_labels needs a split_depth or a stage on the label map: " + ", ".join(S.option for S in _STAGES))
+        try:
+            if self.neighbors is not None:
+                droplet_neighbors.check_radius(self.neighbors)
+            if self.confidence is not None:
+                droplet_confidence.check_band(self.confidence)
+        except ValueError as e:
+            raise _lib.UnetdcError(str(e)) from None
+        if self.confidence_maps and self.confidence is None:
             raise _lib.UnetdcError("confidence_maps needs confidence (the band)")
         if gray is not None and not self.shape:
             raise _lib.UnetdcError("gray needs shape=True")
@@ -107,8 +109,8 @@ class DropletOptions:
 
     @property
     def label_map(self):
-        """Whether a stage reads the int32 label map (without a split depth that selects unetdc_ccl_labels)."""
-        return self.shape or self.neighbors is not None or self.confidence is not None or self.hull
+        """Whether a stage of _STAGES reads the int32 label map (without a split depth that selects unetdc_ccl_labels)."""
+        return any(S.on(self) for S in _STAGES)
 
     @property
     def half_pixels(self):
@@ -159,8 +161,8 @@ class Droplets:
     props: dict | None = None
     clean_counts: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(4, np.int64))
     neighbors: dict | None = None
-    confidence = None             # set by name after construction: the constructor's fields stay those of the stages before
-    hull = None                   # likewise
+    confidence: dict | None = None
+    hull: dict | None = None
 
     def __iter__(self):
         return iter((self.mask, self.area, self.centroid_row, self.centroid_col))
@@ -174,58 +176,136 @@ class _Image(NamedTuple):
     gray: torch.Tensor | None     # uint8 [oh, ow]
     count: torch.Tensor           # int32, the droplet count first
     area: torch.Tensor            # int32 [cap]
-    sums: torch.Tensor            # int64 [2 or 2 + NQ, cap]: sum y, sum x, then the rows of unetdc_label_props
-    clean_counts: torch.Tensor | None   # int32, the four counts first
-    pair_count: torch.Tensor | None = None     # int32, the number of contact pairs first
-    pairs: torch.Tensor | None = None          # int32 [3, pair room]: a, b, d2
-    per_label: torch.Tensor | None = None      # int32 [5, cap]: the rows of utils.droplet_neighbors.COLUMN_NAMES
-    conf: tuple | None = None                  # confidence: (lo, hi fp32 [ph, pw] or None, int64 [8] image totals, the two uint8 maps or None)
-    hull_rows: torch.Tensor | None = None      # int32, the row-extent slots unetdc_label_hull needed first
+    sums: torch.Tensor            # int64 [layout.n_rows, cap]: sum y, sum x, then the rows of the stages
+    clean_counts: torch.Tensor | None   # int32, the four counts
+    stage: dict                   # by the field of each stage that is on: its views of this image (_Stage.views and _droplets)
 
 
-def _enqueue(im, thresh, min_area, ws, opts, s, row_room=0):
-    """One image's launches on the stream s: the mask of the threshold; unetdc_mask_clean in place on it (the weak
-    mask is that of the low threshold under the same resize rule); labelling + sums + compaction by unetdc_ccl_stats,
-    with a split depth unetdc_split_stats (which also fills the label map when there is one), with shape and no split
-    depth unetdc_ccl_labels (so does neighbors); then with shape unetdc_label_props on the label map and the optional grey
-    plane; then with neighbors unetdc_label_neighbors on the label map, the droplet capacity as its max_label; then with
-    confidence unetdc_label_confidence on the label map and the probabilities (and the envelope), the capacity as its max_out,
-    into the rows of `sums` behind those of shape; then with hull unetdc_label_hull on the label map, the capacity as its max_out
-    and `row_room` row-extent slots, into the rows of `sums` behind those."""
-    (oh, ow), cap, h2, clean = im.mask.shape, im.area.shape[0], opts.half_pixels, opts.cleaning(thresh)
-    _mask_from_probs(im.probs, thresh, im.mask, s)
-    if clean is not None:
-        low, holes = clean
-        weak = None
-        if low is not None:
-            weak = torch.empty_like(im.mask)
-            _mask_from_probs(im.probs, low, weak, s)
-        _lib.call("unetdc_mask_clean", im.mask.data_ptr(), None if weak is None else weak.data_ptr(), oh, ow, holes, ws.data_ptr(),
-                  ws.numel(), im.mask.data_ptr(), im.clean_counts.data_ptr(), s)
-    head = (im.mask.data_ptr(), oh, ow, int(max(min_area, 1)))
-    outs = (ws.data_ptr(), ws.numel(), im.count.data_ptr(), im.area.data_ptr(), im.sums[0].data_ptr(), im.sums[1].data_ptr(), None)
-    label = None if im.label is None else im.label.data_ptr()
-    if h2 is not None:
-        _lib.call("unetdc_split_stats", *head, h2, *outs, label, cap, s)
-    elif opts.label_map:
-        _lib.call("unetdc_ccl_labels", *head, *outs, label, cap, s)
-    else:
-        _lib.call("unetdc_ccl_stats", *head, *outs, cap, s)
-    if opts.shape:
-        _lib.call("unetdc_label_props", label, None if im.gray is None else im.gray.data_ptr(), oh, ow, im.sums[2].data_ptr(), cap, s)
-    if opts.neighbors is not None:
-        room = im.pairs.shape[1]
-        _lib.call("unetdc_label_neighbors", label, cap, oh, ow, int(opts.neighbors), ws.data_ptr(), ws.numel(), im.pair_count.data_ptr(),
-                  *((im.pairs[j].data_ptr() if room else None) for j in range(3)), room, *(im.per_label[j].data_ptr() for j in range(5)), s)
-    if opts.confidence is not None:
-        lo, hi, totals, emap, smap = im.conf
-        ph, pw = im.probs.shape
-        _lib.call("unetdc_label_confidence", label, cap, oh, ow, im.probs.data_ptr(), *(None if t is None else t.data_ptr() for t in (lo, hi)),
-                  ph, pw, float(thresh), float(opts.confidence), _entropy_table(im.probs.device).data_ptr(),
-                  im.sums[2 + NQ * opts.shape].data_ptr(), totals.data_ptr(), *(None if t is None else t.data_ptr() for t in (emap, smap)), s)
-    if opts.hull:
-        _lib.call("unetdc_label_hull", label, cap, oh, ow, ws.data_ptr(), ws.numel(),
-                  im.sums[2 + NQ * opts.shape + NC * (opts.confidence is not None)].data_ptr(), im.hull_rows.data_ptr(), row_room, s)
+# What the launches of one batch share.  ws: the one workspace, uint8, used in stream order; cap: the droplets per image that the
+# outputs hold; rooms: by _Stage.room, the slots per image of each growable room; envelope: (lo, hi) fp32 [B, ph, pw] or None.
+_Batch = collections.namedtuple("_Batch", "opts thresh min_area stream ws cap rooms layout counts envelope")
+
+
+class _Layout:
+    """Where everything lies in the two buffers that a batch shares, computed once from (B, the stages that are on, whether
+    the mask is cleaned); the launches and the readback both index through it.
+    counts, int32, zeroed: B droplet counts, 4 clean counts per image, then each stage's slots32 per image in stage order;
+    from `tail`, the next even index (an 8-byte boundary), as int64: each stage's slots64 per image.
+    sums, int64 [n_rows, B, cap]: sum y, sum x, then each stage's rows, in one piece as its kernel wants them."""
+
+    def __init__(self, B, stages, clean):
+        self.B, self.at32, self.at64, self.at_row, n, m, r = B, {}, {}, {}, 0, 0, 2
+        for name, per in [("count", 1), ("clean", 4 * bool(clean))] + [(S.field, S.slots32) for S in stages]:
+            self.at32[name], n = (n, per), n + per * B
+        for S in stages:
+            self.at64[S.field], m = (m, S.slots64), m + S.slots64 * B
+            self.at_row[S.field], r = (r, S.rows), r + S.rows
+        self.n32, self.tail, self.n_rows = n, (n + 1) // 2 * 2, r
+        self.n_counts = self.tail + 2 * m if m else n
+
+    def int32(self, counts, name, i=None):
+        """The int32 slots of `name` in counts (device or host): image i's, or the whole batch's."""
+        at, per = self.at32[name]
+        return counts[at:at + per * self.B] if i is None else counts[at + per * i:at + per * (i + 1)]
+
+    def int64(self, counts, name, i):
+        """Image i's int64 slots of the stage `name` in the tail of counts (device or host)."""
+        at, per = self.at64[name]
+        return counts[self.tail:].view(torch.int64 if torch.is_tensor(counts) else np.int64)[at + per * i:at + per * (i + 1)]
+
+    def rows(self, sums, name):
+        """The rows of the stage `name` in one image's sums [n_rows, ...] (device or host)."""
+        at, k = self.at_row[name]
+        return sums[at:at + k]
+
+    def views(self, counts, sums, S, i):
+        """Image i's part of the stage S on the device, by name: "rows" of its sums, "needed" (slots32) and "totals" (slots64)."""
+        v = {"rows": self.rows(sums, S.field)} if S.rows else {}
+        if S.slots32:
+            v["needed"] = self.int32(counts, S.field, i)
+        if S.slots64:
+            v["totals"] = self.int64(counts, S.field, i)
+        return v
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class _Stage:
+    """An optional stage that measures on the label map: what it needs of the batch's buffers, its launch(b, im, v) behind
+    the labelling (v: im.stage[field], with "needed" = its slots32, "totals" = its slots64 and "rows" = its rows of im.sums)
+    and record(b, i, im, area, sums, raw) from the host copies.  One instance per batch; _STAGES below holds the subclasses
+    in launch order, and nothing else names a stage."""
+    option = field = None         # the DropletOptions field that switches it on (None / False: off), the Droplets field it fills
+    slots32 = slots64 = rows = 0  # per image: int32 slots in counts, int64 slots in its tail; per droplet: int64 rows in sums
+    room = None                   # the name of its growable room; slots32[0] is then what the image needed of it, and
+    #                               capacity(cap, out_hws, wanted) -> the slots it gets, limit(hw) -> (the most there can be, the error)
+    workspace = staticmethod(lambda lib, h, w, cap, rooms: 0)
+
+    def __init__(self, b):
+        pass
+
+    @classmethod
+    def on(cls, opts):
+        v = getattr(opts, cls.option)
+        return v is not None and v is not False
+
+    def views(self, b, i, hw):
+        """Image i's device tensors beyond those of the layout, by name."""
+        return {}
+
+    def fetch(self, b, ints, nmax):
+        """Further device->host copies, once the counts are on the host (ints: their int32 part as int64)."""
+
+
+class _Props(_Stage):
+    """csrc/shape.hip: the integers utils.droplet_shape.shape_columns reads, under the names of label_props_numpy."""
+    option, field, rows = "shape", "props", len(droplet_shape.QUANTITIES)
+
+    def launch(self, b, im, v):
+        _lib.call("unetdc_label_props", im.label.data_ptr(), _ptr(im.gray), *im.mask.shape, v["rows"][0].data_ptr(), b.cap, b.stream)
+
+    def record(self, b, i, im, area, sums, raw):
+        rows = zip(droplet_shape.QUANTITIES, b.layout.rows(sums, self.field))
+        return {"area": area, "Sy": sums[0], "Sx": sums[1],
+                **{q: r for q, r in rows if im.gray is not None or q not in droplet_shape.GRAY_QUANTITIES}}
+
+
+PAIR_ROOM = 1 << 14    # contact pairs per image the first launch has room for; an image with more is run again with twice that
+MAX_PAIR_ROOM = 1 << 27   # the largest table of unetdc_label_neighbors
+
+
+class _Neighbors(_Stage):
+    """csrc/neighbors.hip: the record of utils.droplet_neighbors.neighbors_numpy; the capacity is the kernel's max_label.  Its
+    integers are int32 planes of its own, [3, pair room] (a, b, d2) and [5, cap] (COLUMN_NAMES) per image: two more copies."""
+    option, field, slots32, room = "neighbors", "neighbors", 1, "pairs"
+    # cap labels have at most cap (cap - 1) / 2 pairs
+    capacity = staticmethod(lambda cap, out_hws, wanted: int(min(PAIR_ROOM if wanted is None else wanted, cap * (cap - 1) // 2, MAX_PAIR_ROOM)))
+    limit = staticmethod(lambda hw: (MAX_PAIR_ROOM, f"more than {MAX_PAIR_ROOM} contact pairs in one image"))
+    workspace = staticmethod(lambda lib, h, w, cap, rooms: lib.unetdc_label_neighbors_workspace(h, w, cap, rooms["pairs"]))
+
+    def __init__(self, b):
+        self.pairs = torch.empty(b.layout.B, 3, b.rooms["pairs"], dtype=torch.int32, device=b.counts.device)
+        self.per_label = torch.empty(b.layout.B, 5, b.cap, dtype=torch.int32, device=b.counts.device)
+
+    def views(self, b, i, hw):
+        return {"pairs": self.pairs[i], "per_label": self.per_label[i]}
+
+    def launch(self, b, im, v):
+        room = b.rooms["pairs"]
+        _lib.call("unetdc_label_neighbors", im.label.data_ptr(), b.cap, *im.mask.shape, int(b.opts.neighbors), b.ws.data_ptr(), b.ws.numel(),
+                  v["needed"].data_ptr(), *((v["pairs"][j].data_ptr() if room else None) for j in range(3)), room,
+                  *(v["per_label"][j].data_ptr() for j in range(5)), b.stream)
+
+    def fetch(self, b, ints, nmax):
+        self.n_pairs = b.layout.int32(ints, self.field)
+        self.per_label_h = self.per_label[:, :, :nmax].cpu().numpy().astype(np.int64)
+        self.pairs_h = self.pairs[:, :, :int(min(self.n_pairs.max(initial=0), b.rooms["pairs"]))].cpu().numpy().astype(np.int64)
+
+    def record(self, b, i, im, area, sums, raw):
+        return {"pairs": dict(zip(("a", "b", "d2"), self.pairs_h[i, :, :self.n_pairs[i]])),
+                **dict(zip(droplet_neighbors.COLUMN_NAMES, self.per_label_h[i, :, :len(area)]))}
 
 
 _tables = {}
@@ -235,82 +315,103 @@ def _entropy_table(device):
     """utils.droplet_confidence.entropy_table on the device, uploaded once per device (128 KB; int16 holds the uint16 bits)."""
     key = str(device)
     if key not in _tables:
-        from utils.droplet_confidence import entropy_table
-        _tables[key] = torch.from_numpy(entropy_table().view(np.int16).copy()).to(device)
+        _tables[key] = torch.from_numpy(droplet_confidence.entropy_table().view(np.int16).copy()).to(device)
     return _tables[key]
 
 
-def _check_gray(gray, oh, ow):
-    if not gray.is_cuda or gray.dtype != torch.uint8 or tuple(gray.shape) != (oh, ow) or not gray.is_contiguous():
-        raise _lib.UnetdcError("gray must be a contiguous uint8 [oh, ow] tensor on the HIP device")
+class _Confidence(_Stage):
+    """csrc/confidence.hip: the record of utils.droplet_confidence.confidence_numpy; the capacity is the kernel's max_out.  Its
+    slots64 are the per-image totals (IMAGE_QUANTITIES); its two uint8 maps stay on the device."""
+    option, field = "confidence", "confidence"
+    slots64, rows = len(droplet_confidence.IMAGE_QUANTITIES), len(droplet_confidence.CONF_QUANTITIES)
+
+    def views(self, b, i, hw):
+        lo, hi = (None, None) if b.envelope is None else (t[i] for t in b.envelope)
+        maps = [torch.empty(hw, dtype=torch.uint8, device=b.counts.device) if b.opts.confidence_maps and read else None
+                for read in (True, lo is not None)]               # the spread map only with an envelope
+        return {"lo": lo, "hi": hi, "entropy_u8": maps[0], "spread_u8": maps[1]}
+
+    def launch(self, b, im, v):
+        _lib.call("unetdc_label_confidence", im.label.data_ptr(), b.cap, *im.mask.shape, im.probs.data_ptr(), _ptr(v["lo"]), _ptr(v["hi"]),
+                  *im.probs.shape, float(b.thresh), float(b.opts.confidence), _entropy_table(im.probs.device).data_ptr(),
+                  v["rows"][0].data_ptr(), v["totals"].data_ptr(), _ptr(v["entropy_u8"]), _ptr(v["spread_u8"]), b.stream)
+
+    def record(self, b, i, im, area, sums, raw):
+        v = im.stage[self.field]
+        return {**dict(zip(droplet_confidence.CONF_QUANTITIES, b.layout.rows(sums, self.field))), "image": b.layout.int64(raw, self.field, i),
+                "envelope": b.envelope is not None, "entropy_u8": v["entropy_u8"], "spread_u8": v["spread_u8"]}
 
 
-def _props_dict(area, sums, with_gray):
-    """The integers utils.droplet_shape.shape_columns reads, under the names of label_props_numpy."""
-    from utils.droplet_shape import GRAY_QUANTITIES, QUANTITIES
-    out = {"area": area, "Sy": sums[0], "Sx": sums[1]}
-    out.update((q, sums[2 + j]) for j, q in enumerate(QUANTITIES) if with_gray or q not in GRAY_QUANTITIES)
-    return out
-
-
-def _neighbors_dict(pairs, per_label):
-    """The record of utils.droplet_neighbors.neighbors_numpy from the int64 copies [3, pairs] and [5, droplets]."""
-    from utils.droplet_neighbors import COLUMN_NAMES
-    return {"pairs": dict(zip(("a", "b", "d2"), pairs)), **dict(zip(COLUMN_NAMES, per_label))}
-
-
-def _confidence_dict(rows, totals, envelope, maps):
-    """The record of utils.droplet_confidence.confidence_numpy from the int64 copies [NC, droplets] and [8]."""
-    from utils.droplet_confidence import CONF_QUANTITIES
-    return {**dict(zip(CONF_QUANTITIES, rows)), "image": totals, "envelope": envelope, "entropy_u8": maps[0], "spread_u8": maps[1]}
-
-
-def _workspace_bytes(lib, out_hws, opts, clean, cap, pair_room, row_room=0):
-    query = (lib.unetdc_split_workspace if opts.split_depth is not None else
-             lib.unetdc_ccl_labels_workspace if opts.label_map else lib.unetdc_ccl_workspace)
-    nbytes = max(query(h, w) for h, w in out_hws)
-    if opts.neighbors is not None:
-        nbytes = max(nbytes, max(lib.unetdc_label_neighbors_workspace(h, w, cap, pair_room) for h, w in out_hws))
-    if clean is not None:
-        nbytes = max(nbytes, max(lib.unetdc_mask_clean_workspace(h, w) for h, w in out_hws))
-    if opts.hull:
-        nbytes = max(nbytes, max(lib.unetdc_label_hull_workspace(h, w, cap, row_room) for h, w in out_hws))
-    return nbytes
-
-
-HULL_QUANTITIES = ("H2", "F2", "Wc", "Wl", "nv")    # the rows of unetdc_label_hull, as utils.droplet_hull.QUANTITIES names them
-NQ = 14    # UNETDC_SHAPE_QUANTITIES
-NC = 10    # UNETDC_CONF_QUANTITIES
-NH = 5     # UNETDC_HULL_QUANTITIES
 # Row-extent slots per droplet of the capacity that the first launch of unetdc_label_hull has room for.  The slots needed are the
 # sum of the droplets' heights.  The droplets of the flow are connected, so that sum is at most h * w, and the room is capped
 # there: then it always suffices.  Below the cap, 64 rows per droplet is three times the about 20 rows of a median droplet of a
 # 1040 x 1388 micrograph and 512 KB of workspace per 1024 droplets; an image of taller droplets than that is run again with
 # twice the room, like one with more contact pairs than the pair lists hold.
 ROWS_PER_DROPLET = 64
-PAIR_ROOM = 1 << 14    # contact pairs per image the first launch has room for; an image with more is run again with twice that
-MAX_PAIR_ROOM = 1 << 27   # the largest table of unetdc_label_neighbors
 
 
-def _pair_room(cap, wanted):
-    """The pair capacity for a droplet capacity: cap labels have at most cap (cap - 1) / 2 pairs."""
-    return int(min(wanted, cap * (cap - 1) // 2, MAX_PAIR_ROOM))
+class _Hull(_Stage):
+    """csrc/hull.hip: the integers utils.droplet_hull.hull_columns reads; the capacity is the kernel's max_out."""
+    option, field, slots32, room, rows = "hull", "hull", 1, "rows", len(droplet_hull.QUANTITIES)
+    capacity = staticmethod(lambda cap, out_hws, wanted: int(min(ROWS_PER_DROPLET * cap if wanted is None else wanted, max(h * w for h, w in out_hws))))
+    limit = staticmethod(lambda hw: (hw[0] * hw[1], "unetdc_label_hull: connected droplets need more row room than the image has pixels"))
+    workspace = staticmethod(lambda lib, h, w, cap, rooms: lib.unetdc_label_hull_workspace(h, w, cap, rooms["rows"]))
+
+    def launch(self, b, im, v):
+        _lib.call("unetdc_label_hull", im.label.data_ptr(), b.cap, *im.mask.shape, b.ws.data_ptr(), b.ws.numel(), v["rows"][0].data_ptr(),
+                  v["needed"].data_ptr(), b.rooms["rows"], b.stream)
+
+    def record(self, b, i, im, area, sums, raw):
+        return dict(zip(droplet_hull.QUANTITIES, b.layout.rows(sums, self.field)))
 
 
-def _row_room(cap, out_hws, wanted=None):
-    """The row-extent room of unetdc_label_hull: `wanted` slots (default ROWS_PER_DROPLET per droplet of the capacity), at most
-    h * w of the largest image -- the sum of the heights of connected droplets cannot pass that."""
-    return int(min(ROWS_PER_DROPLET * cap if wanted is None else wanted, max(h * w for h, w in out_hws)))
+_STAGES = (_Props, _Neighbors, _Confidence, _Hull)     # in launch order, which is the order of their slots and rows
 
 
-def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_room=None, envelope=None, row_room=None):
+def _enqueue(im, b, stages):
+    """One image's launches on the batch's stream: the mask of the threshold; unetdc_mask_clean in place on it (the weak
+    mask is that of the low threshold under the same resize rule); labelling + sums + compaction by unetdc_ccl_stats,
+    with a split depth unetdc_split_stats (which also fills the label map when there is one), with a stage and no split
+    depth unetdc_ccl_labels; then every stage that is on, on the label map, the droplet capacity as its max_label / max_out."""
+    (oh, ow), opts, ws, s = im.mask.shape, b.opts, b.ws, b.stream
+    h2, clean = opts.half_pixels, opts.cleaning(b.thresh)
+    _mask_from_probs(im.probs, b.thresh, im.mask, s)
+    if clean is not None:
+        low, holes = clean
+        weak = None
+        if low is not None:
+            weak = torch.empty_like(im.mask)
+            _mask_from_probs(im.probs, low, weak, s)
+        _lib.call("unetdc_mask_clean", im.mask.data_ptr(), _ptr(weak), oh, ow, holes, ws.data_ptr(), ws.numel(), im.mask.data_ptr(),
+                  im.clean_counts.data_ptr(), s)
+    head = (im.mask.data_ptr(), oh, ow, int(max(b.min_area, 1)))
+    outs = (ws.data_ptr(), ws.numel(), im.count.data_ptr(), im.area.data_ptr(), im.sums[0].data_ptr(), im.sums[1].data_ptr(), None)
+    if h2 is not None:
+        _lib.call("unetdc_split_stats", *head, h2, *outs, _ptr(im.label), b.cap, s)
+    elif stages:
+        _lib.call("unetdc_ccl_labels", *head, *outs, _ptr(im.label), b.cap, s)
+    else:
+        _lib.call("unetdc_ccl_stats", *head, *outs, b.cap, s)
+    for st in stages:
+        st.launch(b, im, im.stage[st.field])
+
+
+def _workspace_bytes(lib, out_hws, opts, clean, stages, cap, rooms):
+    """The one workspace holds the largest need of any launch of any image."""
+    head = (lib.unetdc_split_workspace if opts.split_depth is not None else
+            lib.unetdc_ccl_labels_workspace if opts.label_map else lib.unetdc_ccl_workspace)
+    return max(max(head(h, w), lib.unetdc_mask_clean_workspace(h, w) if clean is not None else 0,
+                   *(S.workspace(lib, h, w, cap, rooms) for S in stages)) for h, w in out_hws)
+
+
+def _droplets(probs, thresh, out_hws, min_area, wanted, gray, opts, envelope=None):
     """The one launch-and-readback body -> (B Droplets, the device outputs (count, area, sumy, sumx) or None when an image
-    had more droplets than they hold).  Every launch of the batch is enqueued back to back on the current stream into ONE
-    set of output planes; the host then waits ONCE: one device->host copy brings the B droplet counts (and the clean
-    counts and with neighbors the pair counts behind them), two more the filled part of the per-droplet integers; with
-    neighbors one more the per-droplet neighbour integers and one the filled part of the pair lists.  The integers of confidence
-    add no copy: the per-droplet rows lie behind the sums, the per-image totals (int64) behind the counts.  Nor do those of hull:
-    its rows lie behind those of confidence, the row-extent slots each image needed behind the pair counts."""
+    had more droplets than they hold).  wanted: the rooms asked for by name, "droplets" (the capacity) and optionally those of
+    the stages (_Stage.room; their defaults otherwise).  Every launch of the batch is enqueued back to back on the current
+    stream into ONE int32 and ONE int64 buffer (_Layout); the host then waits ONCE: one device->host copy brings every count
+    and per-image total, two more the filled part of the per-droplet integers, and a stage may add copies of planes of its
+    own (_Stage.fetch).  An image that needed more of a room than there was is run again alone with that room enlarged:
+    droplets to the exact count, a stage's to twice what it had, up to the stage's limit."""
     if not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
         raise _lib.UnetdcError("mask_and_droplets_batch needs a [B, H, W] fp32 tensor on the HIP device")
     probs = probs.contiguous()
@@ -319,85 +420,62 @@ def _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, pair_r
                                      for t in envelope):
             raise _lib.UnetdcError("envelope is (lo, hi): two fp32 tensors shaped like probs, on its device")
         envelope = tuple(t.contiguous() for t in envelope)
-    B, dev, s = probs.shape[0], probs.device, torch.cuda.current_stream().cuda_stream
-    clean = opts.cleaning(thresh)
+    B, dev, clean = probs.shape[0], probs.device, opts.cleaning(thresh)
     out_hws = [(int(h), int(w)) for h, w in out_hws]
-    cap = int(min(max_droplets, max(h * w for h, w in out_hws)))
-    if gray is not None:
-        for g, (oh, ow) in zip(gray, out_hws):
-            _check_gray(g, oh, ow)
-    nb = opts.neighbors is not None
-    room = _pair_room(cap, PAIR_ROOM if pair_room is None else pair_room) if nb else 0
-    rows = _row_room(cap, out_hws, row_room) if opts.hull else 0
-    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, cap, room, rows), dtype=torch.uint8, device=dev)   # one: stream order
-    nc, cf, hl = B * (1 if clean is None else 5), opts.confidence is not None, bool(opts.hull)
-    n32 = nc + B * nb + B * hl
-    at64 = (n32 + 1) // 2 * 2                                          # the int64 totals start on an 8-byte boundary
-    # droplet counts, then 4 per image, then the pair counts, then the hull's row counts; then with confidence 8 int64 per image
-    # (16 int32 slots)
-    counts = torch.zeros(at64 + 16 * B if cf else n32, dtype=torch.int32, device=dev)
-    totals = counts[at64:].view(torch.int64) if cf else None
-    pairs = torch.empty(B, 3, room, dtype=torch.int32, device=dev) if nb else None
-    per_label = torch.empty(B, 5, cap, dtype=torch.int32, device=dev) if nb else None
+    cap = int(min(wanted["droplets"], max(h * w for h, w in out_hws)))
+    for g, hw in zip(() if gray is None else gray, out_hws):
+        if not g.is_cuda or g.dtype != torch.uint8 or tuple(g.shape) != hw or not g.is_contiguous():
+            raise _lib.UnetdcError("gray must be a contiguous uint8 [oh, ow] tensor on the HIP device")
+    on = [S for S in _STAGES if S.on(opts)]
+    rooms = {S.room: S.capacity(cap, out_hws, wanted.get(S.room)) for S in on if S.room}
+    lay = _Layout(B, on, clean is not None)
+    ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, on, cap, rooms), dtype=torch.uint8, device=dev)   # one: stream order
+    counts = torch.zeros(lay.n_counts, dtype=torch.int32, device=dev)
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    # per image: sum y, sum x, then with shape the rows of unetdc_label_props, which wants them [NQ][cap] in one piece
-    # and with confidence behind them the rows of unetdc_label_confidence, [NC][cap] in one piece as well, then those of
-    # unetdc_label_hull, [NH][cap]
-    r0 = 2 + NQ * opts.shape
-    rh = r0 + NC * cf
-    sums = torch.empty(B, rh + NH * hl, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
-    images = []
-    for i, (oh, ow) in enumerate(out_hws):
-        images.append(_Image(probs[i], torch.empty(oh, ow, dtype=torch.uint8, device=dev),
-                             torch.empty(oh, ow, dtype=torch.int32, device=dev) if opts.labels or opts.label_map else None,
-                             None if gray is None else gray[i], counts[i:], area[i], sums[:, i],
-                             None if clean is None else counts[B + 4 * i:],
-                             *((counts[nc + i:], pairs[i], per_label[i]) if nb else (None, None, None)),
-                             (*((envelope[0][i], envelope[1][i]) if envelope is not None else (None, None)), totals[8 * i:],
-                              torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps else None,
-                              torch.empty(oh, ow, dtype=torch.uint8, device=dev) if opts.confidence_maps and envelope is not None else None)
-                             if cf else None, counts[nc + B * nb + i:] if hl else None))
-        _enqueue(images[i], thresh, min_area, ws, opts, s, rows)
+    sums = torch.empty(B, lay.n_rows, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
+    b = _Batch(opts, thresh, min_area, torch.cuda.current_stream().cuda_stream, ws, cap, rooms, lay, counts, envelope)
+    stages, images = [S(b) for S in on], []
+    for i, hw in enumerate(out_hws):
+        view = sums[:, i]
+        images.append(_Image(probs=probs[i], mask=torch.empty(hw, dtype=torch.uint8, device=dev),
+                             label=torch.empty(hw, dtype=torch.int32, device=dev) if opts.labels or on else None,
+                             gray=None if gray is None else gray[i], count=lay.int32(counts, "count", i), area=area[i], sums=view,
+                             clean_counts=None if clean is None else lay.int32(counts, "clean", i),
+                             stage={st.field: {**st.views(b, i, hw), **lay.views(counts, view, st, i)} for st in stages}))
+        _enqueue(images[i], b, stages)
     raw = counts.cpu().numpy()                                      # the batch's only host wait
-    t_h = raw[at64:].view(np.int64).reshape(B, 8) if cf else None
-    n = raw[:n32].astype(np.int64)
-    clean_counts = n[B:nc].reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
-    n_pairs, n_rows, n = n[nc:nc + B * nb], n[nc + B * nb:], n[:B]
+    ints = raw[:lay.n32].astype(np.int64)
+    n = lay.int32(ints, "count")
+    clean_counts = lay.int32(ints, "clean").reshape(B, 4) if clean is not None else np.zeros((B, 4), np.int64)
     nmax = int(min(n.max(initial=0), cap))
     a_h = area[:, :nmax].cpu().numpy().astype(np.int64)
     s_h = sums[:, :, :nmax].cpu().numpy()
-    if nb:
-        l_h = per_label[:, :, :nmax].cpu().numpy().astype(np.int64)
-        p_h = pairs[:, :, :int(min(n_pairs.max(initial=0), room))].cpu().numpy().astype(np.int64)
-    out = []
-    def again(i, max_droplets, pair_room, row_room):
-        return _droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, max_droplets, None if gray is None else gray[i:i + 1], opts,
-                         pair_room, None if envelope is None else tuple(t[i:i + 1] for t in envelope), row_room)[0][0]
+    for st in stages:
+        st.fetch(b, ints, nmax)
 
+    def overflowed(i):
+        """The room that image i needed more of than there was, enlarged (droplets first, then the stages' in their order)."""
+        if n[i] > cap:
+            return {"droplets": int(n[i])}
+        for st in stages:
+            if st.room and lay.int32(ints, st.field, i)[0] > rooms[st.room]:
+                most, error = st.limit(out_hws[i])
+                if rooms[st.room] >= most:
+                    raise _lib.UnetdcError(error)
+                return {st.room: 2 * max(rooms[st.room], 1)}
+
+    out = []
     for i, im in enumerate(images):
-        if n[i] > cap:                            # more droplets than the output capacity: this image again with room for all
-            out.append(again(i, int(n[i]), pair_room, row_room))
-            continue
-        if nb and n_pairs[i] > room:              # more contact pairs than the pair lists hold: this image again with twice the room
-            if room >= MAX_PAIR_ROOM:
-                raise _lib.UnetdcError(f"more than {MAX_PAIR_ROOM} contact pairs in one image")
-            out.append(again(i, max_droplets, 2 * max(room, 1), row_room))
-            continue
-        if hl and n_rows[i] > rows:               # taller droplets than the row room holds: this image again with twice the room
-            if rows >= out_hws[i][0] * out_hws[i][1]:
-                raise _lib.UnetdcError("unetdc_label_hull: connected droplets need more row room than the image has pixels")
-            out.append(again(i, max_droplets, pair_room, 2 * max(rows, 1)))
+        more = overflowed(i)
+        if more:                                  # this image again, alone
+            out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, {**wanted, **more}, None if gray is None else gray[i:i + 1],
+                                 opts, None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
             continue
         a, si = a_h[i, :n[i]], s_h[:, i, :n[i]]
         d = np.maximum(a, 1)
-        out.append(Droplets(im.mask, a, si[0].astype(np.float64) / d, si[1].astype(np.float64) / d,
-                            im.label if opts.labels else None, _props_dict(a, si, gray is not None) if opts.shape else None,
-                            clean_counts[i], _neighbors_dict(p_h[i, :, :n_pairs[i]], l_h[i, :, :n[i]]) if nb else None))
-        if cf:
-            out[-1].confidence = _confidence_dict(si[r0:r0 + NC], t_h[i], envelope is not None, im.conf[3:])
-        if hl:
-            out[-1].hull = dict(zip(HULL_QUANTITIES, si[rh:rh + NH]))
-    return out, ((counts[:B], area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
+        out.append(Droplets(im.mask, a, si[0].astype(np.float64) / d, si[1].astype(np.float64) / d, labels=im.label if opts.labels else None,
+                            clean_counts=clean_counts[i], **{st.field: st.record(b, i, im, a, si, raw) for st in stages}))
+    return out, ((lay.int32(counts, "count"), area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
 
 
 def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 14, keep_sums=False, **options):
@@ -410,7 +488,7 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     integers of confidence (None: those keep their initial values).  Every option adds its launches
     behind each image's existing ones and its integers to the copies the host already waits for; all off: no launch is added."""
     opts, gray, envelope = _options(options, thresh)
-    out, sums = _droplets(probs, thresh, out_hws, min_area, max_droplets, gray, opts, envelope=envelope)
+    out, sums = _droplets(probs, thresh, out_hws, min_area, {"droplets": max_droplets}, gray, opts, envelope)
     return (out, sums) if keep_sums else out
 
 
@@ -418,5 +496,6 @@ def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, *
     """probs2d: [H, W] fp32 probabilities on the HIP device -> its Droplets: the batch of one.  options as in
     mask_and_droplets_batch; gray: one uint8 [oh, ow] DEVICE tensor; envelope: two fp32 [H, W] DEVICE tensors."""
     opts, gray, envelope = _options(options, thresh)
-    return _droplets(probs2d[None], thresh, [out_hw], min_area, max_droplets, None if gray is None else [gray], opts,
-                     envelope=None if envelope is None else tuple(t[None] for t in envelope))[0][0]
+    return _droplets(probs2d[None], thresh, [out_hw], min_area, {"droplets": max_droplets}, None if gray is None else [gray], opts,
+                     None if envelope is None else tuple(t[None] for t in envelope))[0][0]
+
