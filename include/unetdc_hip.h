@@ -740,6 +740,40 @@ int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, 
                       int64_t workspace_bytes, uint8_t* out_mask, int32_t* out_counts, unetdc_stream_t s);
 
 
+/* ---- difference map against an annotation and its regions (diffmap.hip; the definition is DESIGN.md section 25) --------------
+ * pred, gt ([h][w] uint8 each, nonzero = 1) give the class plane c = pred | gt << 1 and its colours, the reference's:
+ *     0 black (0, 0, 0): neither (TN)        1 green (0, 255, 0): only predicted (FP)
+ *     2 red (255, 0, 0): only annotated (FN) 3 yellow (255, 255, 0): both (TP)
+ * unetdc_diff_regions: a REGION is a maximal 8-connected set of pixels of equal c; all four classes count, black included.
+ *     out_image (DEVICE, int64 [12], 8-byte aligned): pixels[4] (the pixel count of each class), regions[4] (every region of
+ *       each class), kept[4] (the regions of each class with area >= min_area).
+ *     The table: one row per region of class 1..3 with area >= min_area, in raster order of the region's first pixel, the
+ *       classes interleaved: row i at out_class[i], out_area[i] (int32), out_sumy[i], out_sumx[i] (int64: the sums of the row
+ *       and column coordinates of its pixels), out_neighbors[i] (int32: bit k is set when some pixel of the region has an
+ *       8-neighbour of class k != class; the image border sets no bit).
+ *     *out_count = the number of rows that exist; it may exceed max_out, rows past max_out are not written.  max_out = 0 is
+ *       allowed (the five table arrays may then be NULL).
+ *   Sides 1..16384 with h * w < 2^30, min_area >= 1, max_out >= 0; anything else, a null pred / gt / workspace / out_image /
+ *   out_count, a null table with max_out > 0 or a misaligned pointer (workspace, out_image, out_sumy, out_sumx: 8 bytes; the
+ *   int32 outputs: 4) returns UNETDC_EINVAL before the first launch, a workspace below unetdc_diff_regions_workspace(h, w)
+ *   bytes UNETDC_EWORKSPACE.  The query answers 29 n + 4 ceil(n / 1024) + 128 bytes for n = h * w pixels (two int64 and three
+ *   int32 planes, one word per 1024 pixels and 16 more, one byte plane, 64 spare bytes) and 0 for a geometry the call refuses.
+ *   pred and gt are only read; nothing but the outputs and the workspace is written, and the workspace may hold anything on
+ *   entry.  Launches on the given stream only; no host wait, no allocation.  Integer atomics and a union-find whose root is the
+ *   region's smallest linear index: the outputs depend on no order, two runs are bitwise equal.
+ * unetdc_diff_paint: out_diff ([h][w][3] uint8, nullable): the colour of c at every pixel.  out_overlay ([h][w][3] uint8,
+ *   nullable): rgb ([h][w][3] uint8, required with out_overlay, else ignored and nullable) with every pixel of c != 0 replaced
+ *   by its colour.  At least one output must be given; no output may overlap an input or the other output.  Same limits on the
+ *   sides; UNETDC_EINVAL before the launch otherwise.  No alignment is required: planes that are all 4-byte aligned move as
+ *   whole dwords, any other set byte by byte, with equal results.  No workspace, no atomics, one launch on the given stream. */
+int64_t unetdc_diff_regions_workspace(int h, int w);
+int unetdc_diff_regions(const uint8_t* pred, const uint8_t* gt, int h, int w, int min_area, void* workspace,
+                        int64_t workspace_bytes, int64_t* out_image, int32_t* out_count, int32_t* out_class, int32_t* out_area,
+                        int64_t* out_sumy, int64_t* out_sumx, int32_t* out_neighbors, int max_out, unetdc_stream_t s);
+int unetdc_diff_paint(const uint8_t* pred, const uint8_t* gt, const uint8_t* rgb, int h, int w, uint8_t* out_diff,
+                      uint8_t* out_overlay, unetdc_stream_t s);
+
+
 /* ---- threshold sweep against an annotation (sweep.hip; the definition is DESIGN.md section 14) ------------------------------
  * unetdc_thresh_sweep: probs ([n][ph][pw] fp32), gt ([n][oh][ow] uint8, nonzero = annotated), n >= 1 images of one geometry,
  *   k in 1..1024 thresholds t_j = (float)j / (float)k, j = 0..k-1 (one fp32 division each).

@@ -22,6 +22,7 @@ and a few integers per droplet come back:
     --boundary        unet_dc_segmentation_amd/evaluate.py      csrc/boundary.hip       CPU: utils/droplet_boundary.py
     --confidence      (droplets.py, tta.py)                     csrc/confidence.hip tta.hip  CPU: utils/droplet_confidence.py
     --droplet_hull    (droplets.py)                             csrc/hull.hip           CPU: utils/droplet_hull.py
+    --diff_maps       unet_dc_segmentation_amd/evaluate.py      csrc/diffmap.hip        CPU: utils/difference_map.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -105,6 +106,12 @@ class Run:
     boundary: dict | None = None       # boundary_options(); its "records" collect boundary_per_image.csv
     confidence: dict | None = None     # confidence_options(); its "rows" collect confidence_per_image.csv
     hull: float | None = None          # --droplet_hull: the solidity below which a droplet is flagged, None without the flag
+    diff: dict | None = None           # diff_options(); its "tables" / "rows" collect diff_regions.csv and diff_regions_per_image.csv
+
+    @property
+    def keep_rgb(self):
+        """Whether the batch keeps the decoded original image: the density maps read it, the difference overlays are painted on it."""
+        return self.density is not None or self.diff is not None
 
     @property
     def envelope(self):
@@ -135,7 +142,7 @@ class Batch:
     meta: list = dataclasses.field(default_factory=list)       # (path, (oh, ow))
     tensors: list = dataclasses.field(default_factory=list)    # network inputs (none under --tile)
     grays: list = dataclasses.field(default_factory=list)      # --droplet_shape: the ORIGINAL image as grey, uint8 [oh, ow]
-    rgbs: list = dataclasses.field(default_factory=list)       # --density_maps: the decoded image (a device tensor on the GPU)
+    rgbs: list = dataclasses.field(default_factory=list)       # --density_maps, --diff_maps: the decoded image (a device tensor on the GPU)
     gt_items: list = dataclasses.field(default_factory=list)   # --gt_dir: the decoded annotations
 
 
@@ -145,7 +152,7 @@ def predict_tiled_image(model, im, run):
     rolling ball alone, at native size; then the tiles, run.batch_size per forward, and the blend.  With --tta every tile's
     probabilities are the mean over its variants."""
     more = {} if run.tta is None else {"tta": run.tta["N"], "envelope": True} if run.envelope else {"tta": run.tta["N"]}
-    tile, radius, keep_rgb = run.tile, run.background_radius, run.density is not None
+    tile, radius, keep_rgb = run.tile, run.background_radius, run.keep_rgb
     if DEVICE == "cuda":
         from unet_dc_segmentation_amd.preprocess import MAX_ELEMENT, _upload, rolling_ball_device
         from unet_dc_segmentation_amd.tiling import predict_tiled
@@ -351,6 +358,38 @@ def _write_map(plane, path):
     Image.fromarray(plane).save(str(path))
 
 
+def _write_picture(rgb, path):
+    """A full-size RGB PNG of --diff_maps.  zlib level 1: on a 1040 x 1388 overlay PIL's default level 6 takes 3.4 times as
+    long for a file 5 % smaller, and the two pictures are most of what the flag costs per image."""
+    Image.fromarray(rgb).save(str(path), compress_level=1)
+
+
+def add_diff_outputs(run, batch, out):
+    """--diff_maps for one batch: the difference map of every measured mask (after cleaning, at the image's size) against its
+    annotation (> 0, labels included), the overlay on the decoded image, this image's rows of diff_regions.csv and its row of
+    diff_regions_per_image.csv.  On the device the batch is enqueued back to back with one host wait
+    (evaluate.diff_regions_batch) and reads the images already uploaded; the PNGs go through the writer pool."""
+    from utils import difference_map as dmap
+    diff = run.diff
+    gts = [np.ascontiguousarray(np.asarray(g) > 0, dtype=np.uint8) for g in batch.gt_items]
+    if torch.is_tensor(out[0].mask) and out[0].mask.is_cuda:
+        from unet_dc_segmentation_amd.evaluate import diff_regions_batch
+        recs = diff_regions_batch([d.mask.contiguous() for d in out], [torch.from_numpy(g).to(DEVICE) for g in gts],
+                                  diff["min_area"], batch.rgbs, paint=True)
+    else:
+        recs = []
+        for d, g, rgb in zip(out, gts, batch.rgbs):
+            mask = _host(d.mask)
+            recs.append({**dmap.diff_regions_numpy(mask, g, diff["min_area"]), "diff": dmap.difference_map_rgb(mask, g),
+                         "overlay": dmap.overlay_difference(_host(rgb), mask, g)})
+    for rec, (fpath, _) in zip(recs, batch.meta):
+        filename, name = Path(fpath).name, Path(fpath).stem
+        diff["tables"].append(pd.DataFrame(dmap.region_table(filename, rec, run.px_per_um)))
+        diff["rows"].append({"filename": filename, **dmap.image_columns(rec)})
+        run.submit(_write_picture, _host(rec["diff"]), diff["map_dir"] / f"{name}_diffmap.png")
+        run.submit(_write_picture, _host(rec["overlay"]), diff["overlay_dir"] / f"{name}_overlay.png")
+
+
 def quantify(bin_mask, min_area, px_per_um, split_depth=None):
     """Per-droplet table: label, area, equivalent_diameter, centroid-0/1 (+ micron columns) -- CPU path (SciPy).
     split_depth (pixels): the table of the split droplets instead (utils/droplet_split.py)."""
@@ -516,6 +555,8 @@ def finish_batch(run, batch, probs):
         plain = run.split_depth is None and not run.shape and run.gt is None and run.clean is None
         dres = density_maps_batch(batch.rgbs, [d.mask for d in out], sums if run.min_area <= 1 and plain else None,
                                   run.density["nb_layers"], run.density["kernel"])
+    if run.diff is not None:
+        add_diff_outputs(run, batch, out)
     for i, (d, (fpath, hw)) in enumerate(zip(out, batch.meta)):
         filename, name = Path(fpath).name, Path(fpath).stem
         mask = _host(d.mask)
@@ -654,6 +695,16 @@ def build_parser():
                         "(0, 1], 0.9 without S -- a convention, not a measured number) to the droplet tables, with "
                         "--px_per_micron also feret_max_micron, feret_min_micron, area_convex_sqmicron; summary_per_image.csv "
                         "gains solidity_median, feret_max_median and n_low_solidity")
+    p.add_argument("--diff_maps", type=int, nargs="?", const=1, metavar="MIN_AREA",
+                   help="with --gt_dir: where the prediction fails -- writes difference_maps/NAME_diffmap.png (yellow: predicted "
+                        "and annotated, red: only annotated, green: only predicted, black: neither) and "
+                        "diff_overlays/NAME_overlay.png (that map over the original image), diff_regions.csv (one row per "
+                        "8-connected red, green or yellow region of at least MIN_AREA pixels, 1 without MIN_AREA: class, area, "
+                        "centroid, touches_common = it borders a yellow region, isolated = a red or green one that does not: a "
+                        "droplet missed entirely, or a spurious one) and diff_regions_per_image.csv (yellow / red / green / black "
+                        "regions = region-level TP / FN / FP / TN, their pixels, the regions kept, missed_droplets, "
+                        "spurious_droplets).  The prediction is the mask the droplet stage measured (after --prob_thresh_low / "
+                        "--fill_holes), the annotation is grey > 0, with --gt_labels label > 0; --gt_min_area does not apply here")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -762,7 +813,12 @@ def tta_options(args):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.diff_maps is not None and not args.gt_dir:
+        parser.error("--diff_maps compares against annotated masks: it needs --gt_dir")
+    if args.diff_maps is not None and args.diff_maps < 1:
+        parser.error("--diff_maps MIN_AREA: MIN_AREA is a number of pixels, at least 1")
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
     from utils.droplet_split import half_pixels
     try:                                                 # checked before any image, and before any output directory exists
@@ -801,6 +857,12 @@ def main(argv=None):
         if not 1 <= args.nb_layers <= 255 or not 0 < args.density_kernel or int(4 * args.density_kernel / 6 + 0.5) > 128:
             raise SystemExit("--nb_layers must be in 1..255 and --density_kernel in 1..192")
         density = {"nb_layers": args.nb_layers, "kernel": args.density_kernel}
+    diff = None
+    if args.diff_maps is not None:
+        diff = {"min_area": args.diff_maps, "map_dir": out_dir / "difference_maps", "overlay_dir": out_dir / "diff_overlays",
+                "tables": [], "rows": []}
+        diff["map_dir"].mkdir(exist_ok=True)
+        diff["overlay_dir"].mkdir(exist_ok=True)
     model = load_model(args.ckpt_path, args.dtype)
     # File decode runs ahead of the device and the per-image writes behind it, in two small thread pools (both are
     # zlib-bound and release the GIL); the order of the rows in the summary files is the order of `images` as before.
@@ -813,7 +875,7 @@ def main(argv=None):
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
-                  neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull)
+                  neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff)
         ahead = deque()
         it = iter(images)
 
@@ -843,7 +905,7 @@ def main(argv=None):
                 finish_batch(run, batch, probs)
                 batch = Batch()
                 continue
-            t, _, *rgb = preprocess(img, args.background_radius, im, keep_rgb=density is not None)
+            t, _, *rgb = preprocess(img, args.background_radius, im, keep_rgb=run.keep_rgb)
             batch.tensors.append(t)
             batch.rgbs += rgb
             if len(batch.tensors) == args.batch:
@@ -870,6 +932,11 @@ def main(argv=None):
     if confidence is not None:
         from utils.droplet_confidence import IMAGE_COLUMNS
         pd.DataFrame(confidence["rows"], columns=("filename",) + IMAGE_COLUMNS).to_csv(out_dir / "confidence_per_image.csv", index=False)
+    if diff is not None:
+        from utils import difference_map as dmap
+        tables = [t for t in diff["tables"] if len(t)] or diff["tables"][:1]
+        pd.concat(tables, ignore_index=True).to_csv(out_dir / "diff_regions.csv", index=False) if tables else None
+        pd.DataFrame(diff["rows"], columns=("filename",) + dmap.IMAGE_COLUMNS).to_csv(out_dir / "diff_regions_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     if run.neighbors is not None and run.contact_tables:

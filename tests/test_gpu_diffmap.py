@@ -1,0 +1,233 @@
+"""GPU: the difference map and its 8-connected regions (unetdc_diff_regions, unetdc_diff_paint, csrc/diffmap.hip) through the
+C ABI against the host path of the same definition (utils/difference_map.py, itself pinned to the plain loops of
+tests/diffmap_ref.py on the CPU); then evaluate.diff_regions_batch, the CLI flag and the training script's dumps.  Integer
+work: bit-exact.  Every buffer sits between canaries and the tables start as canary bytes."""
+import functools
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+from tests import diffmap_ref as R
+from tests import workspace_states as wstates
+from tests.image_canaries import CANARY, Canaried, canaried_like
+from tests.test_gpu_split import stream
+from utils import difference_map as D
+
+pytestmark = pytest.mark.gpu
+
+KEYS = ("image",) + D.TABLE_KEYS
+GRID_CAP_PIXELS = 4096 * 256            # DIFF_GRID_CAP workgroups of 256 pixels; DIFF_BLOCK_GRID_CAP * DIFF_BLK is as many
+PAST_THE_CAP = (1024, 1025)             # 1 049 600 pixels: the first image width past it at 1024 rows
+
+
+def workspace_formula(h, w):
+    n = h * w
+    return 29 * n + 4 * ((n + 1023) // 1024) + 128
+
+
+def device_regions(pred, gt, min_area=1, max_out=None, ws=None, keep_ws=False):
+    """-> the record as int64 numpy arrays, "count" = *out_count, "written" = the rows the tables hold.  Inputs, workspace,
+    out_image, out_count and the five tables each sit between canaries; a table row the call did not write keeps them."""
+    from unet_dc_segmentation_amd import _lib
+    pred, gt = np.ascontiguousarray(pred, np.uint8), np.ascontiguousarray(gt, np.uint8)
+    h, w = pred.shape
+    lib = _lib.load()
+    nbytes = lib.unetdc_diff_regions_workspace(h, w)
+    assert nbytes == workspace_formula(h, w)
+    ws = Canaried(nbytes) if ws is None else ws
+    assert ws.nbytes == nbytes
+    max_out = h * w if max_out is None else max_out
+    dp, dg = canaried_like(pred), canaried_like(gt)
+    image, count = Canaried(12 * 8), Canaried(4)
+    t32 = [Canaried(4 * max_out) for _ in range(3)] if max_out else [None] * 3
+    t64 = [Canaried(8 * max_out) for _ in range(2)] if max_out else [None] * 2
+    ptr = lambda c: c.ptr if c is not None else None
+    _lib.call("unetdc_diff_regions", dp.ptr, dg.ptr, h, w, min_area, ws.ptr, nbytes, image.ptr, count.ptr, ptr(t32[0]),
+              ptr(t32[1]), ptr(t64[0]), ptr(t64[1]), ptr(t32[2]), max_out, stream())
+    for v in [dp, dg, ws, image, count] + t32 + t64:
+        if v is not None:
+            v.check()
+    assert np.array_equal(dp.numpy(np.uint8, h, w), pred) and np.array_equal(dg.numpy(np.uint8, h, w), gt)    # read only
+    n = int(count.numpy(np.int32, 1)[0])
+    k = min(n, max_out)
+    rec = {"image": image.numpy(np.int64, 12).copy(), "count": n, "written": k}
+    for key, c, dt in zip(("class", "area", "neighbors", "sumy", "sumx"), t32 + t64, (np.int32,) * 3 + (np.int64,) * 2):
+        full = c.numpy(dt, max_out) if c is not None else np.zeros(0, dt)
+        rec[key] = full[:k].astype(np.int64)
+        assert np.all(full[k:].view(np.uint8) == CANARY), f"{key}: a row past the count was written"
+    if keep_ws:
+        rec["ws"] = ws
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
+def host_record(name, min_area=1):
+    pred, gt = R.full_case() if name == "full" else R.small_cases()[name]
+    return D.diff_regions_numpy(pred, gt, min_area)
+
+
+def assert_same(got, want, what="", rows=None):
+    assert np.array_equal(got["image"], want["image"]), (what, got["image"], want["image"])
+    n = len(want["class"])
+    assert got["count"] == n, (what, got["count"], n)
+    rows = n if rows is None else rows
+    for q in D.TABLE_KEYS:
+        assert got[q].shape == (rows,) and np.array_equal(got[q], want[q][:rows]), (what, q, got[q][:8], want[q][:8])
+
+
+@pytest.mark.parametrize("name", sorted(R.small_cases()))
+def test_regions_equal_the_host_path(name):
+    pred, gt = R.small_cases()[name]
+    for min_area in ((1, 5) if name.startswith(("realistic", "random/37", "random/96")) else (1,)):
+        assert_same(device_regions(pred, gt, min_area), host_record(name, min_area), (name, min_area))
+
+
+def test_fixtures_hold_what_they_are_for():
+    """What a 4-connected implementation gets wrong, what fills the table, what makes long union-find chains."""
+    for name, want in (("checkerboard03/37x53", {0: 1, 3: 1}), ("checkerboard12/96x130", {1: 1, 2: 1}), ("crossing01", {0: 1, 1: 1}),
+                       ("anti_diagonal2", {2: 1}), ("serpentine", {0: 1, 3: 1}), ("all0/37x53", {0: 1}), ("all3/37x53", {3: 1})):
+        im = host_record(name)["image"]
+        for k, n in want.items():
+            assert im[4 + k] == n, (name, k, im)
+    four = host_record("four_classes")
+    assert four["image"].tolist() == [1024] * 12 and len(four["class"]) == 3072
+    for kind in ("moved", "dilated", "unrelated"):
+        rec = host_record(f"realistic_{kind}/96x130")
+        assert len(set(rec["neighbors"].tolist())) > 1 and len(rec["class"]) > 5, kind
+        assert host_record(f"realistic_{kind}/96x130", 5)["image"][8:].sum() < rec["image"][8:].sum()
+
+
+@pytest.mark.parametrize("max_out", [3072, 100, 0])
+def test_four_classes_at_once_with_room_or_without(max_out):
+    pred, gt = R.small_cases()["four_classes"]
+    got = device_regions(pred, gt, 1, max_out)
+    assert got["count"] == 3072 and got["written"] == max_out
+    assert_same(got, host_record("four_classes"), max_out, rows=max_out)
+
+
+@pytest.fixture(scope="module")
+def full_runs():
+    """The one 1040 x 1388 case: two runs of the device, the second on the workspace the first left."""
+    pred, gt = R.full_case()
+    first = device_regions(pred, gt, 1, keep_ws=True)
+    second = device_regions(pred, gt, 1, ws=first.pop("ws"))
+    return first, second
+
+
+def test_full_size_equals_the_host_path_and_two_runs_are_bitwise_equal(full_runs):
+    first, second = full_runs
+    assert 1040 * 1388 > GRID_CAP_PIXELS
+    assert_same(first, host_record("full"), "full")
+    for q in KEYS:
+        assert np.array_equal(first[q], second[q]), q
+
+
+def test_past_the_grid_caps():
+    """The largest caps are 1 048 576 pixels a trip (per-pixel kernels: 4096 workgroups of 256; count and emit: 1024 workgroups
+    of 1024 pixels; the stats kernel, at 1024 workgroups of 256, is on its fifth trip): at 1024 x 1025 the last 1024 pixels are
+    every kernel's trip past its cap, and regions span the seam."""
+    h, w = PAST_THE_CAP
+    assert h * w > GRID_CAP_PIXELS and h * (w - 1) <= GRID_CAP_PIXELS
+    pred, gt = R.realistic(h, w, "moved", seed=9)
+    want = D.diff_regions_numpy(pred, gt, 5)
+    assert (want["sumy"] // np.maximum(want["area"], 1)).max() >= h - 2        # rows of the table lie on the second trip
+    assert_same(device_regions(pred, gt, 5), want, "past the cap")
+
+
+@pytest.mark.parametrize("state", wstates.STATES)
+def test_stale_workspace(state):
+    """Whatever the workspace holds on entry (the three patterns, and the bytes a call at another geometry left there, as
+    diff_regions_batch reuses one buffer), the record is the same."""
+    from unet_dc_segmentation_amd import _lib
+    name = "realistic_unrelated/96x130"
+    pred, gt = R.small_cases()[name]
+    stale = None
+    if state == "stale":
+        other = device_regions(*R.small_cases()["random/300x401"], keep_ws=True)
+        stale = other["ws"].u8.clone()
+    ws = wstates.prepare(Canaried(_lib.load().unetdc_diff_regions_workspace(*pred.shape)), state, stale)
+    assert_same(device_regions(pred, gt, 1, ws=ws), host_record(name), state)
+
+
+def device_paint(pred, gt, rgb, want_diff, want_overlay, skew=0):
+    from unet_dc_segmentation_amd import _lib
+    h, w = pred.shape
+    dp, dg = canaried_like(pred, skew=skew), canaried_like(gt, skew=skew)
+    di = canaried_like(rgb, skew=skew) if rgb is not None else None
+    diff = Canaried(3 * h * w, skew=skew) if want_diff else None
+    over = Canaried(3 * h * w, skew=skew) if want_overlay else None
+    _lib.call("unetdc_diff_paint", dp.ptr, dg.ptr, di.ptr if di else None, h, w, diff.ptr if diff else None,
+              over.ptr if over else None, stream())
+    for v in (dp, dg, di, diff, over):
+        if v is not None:
+            v.check()
+    assert np.array_equal(dp.numpy(np.uint8, h, w), pred) and np.array_equal(dg.numpy(np.uint8, h, w), gt)
+    if di is not None:
+        assert np.array_equal(di.numpy(np.uint8, h, w, 3), rgb)
+    return (diff.numpy(np.uint8, h, w, 3) if diff else None), (over.numpy(np.uint8, h, w, 3) if over else None)
+
+
+@pytest.mark.parametrize("skew", [0, 1], ids=["aligned", "skewed"])
+@pytest.mark.parametrize("shape", [(1, 1), (3, 5), (37, 53), (96, 130)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_paint_equals_numpy(shape, skew):
+    """The odd pixel counts end in a bytewise tail; a plane one byte past a multiple of 4 takes the bytewise kernel."""
+    h, w = shape
+    rng = np.random.default_rng(h * w)
+    pred, gt = R.from_classes(rng.integers(0, 4, shape))
+    pred, gt = pred * 255, gt * 7                                      # any nonzero counts as 1
+    rgb = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
+    want_d, want_o = D.difference_map_rgb(pred, gt), D.overlay_difference(rgb, pred, gt)
+    c = D.class_plane(pred, gt)
+    assert np.array_equal(want_o[c == 0], rgb[c == 0])
+    for d, o in ((True, False), (False, True), (True, True)):
+        got_d, got_o = device_paint(pred, gt, rgb if o else None, d, o, skew)
+        if d:
+            assert np.array_equal(got_d, want_d), (shape, skew, d, o)
+        if o:
+            assert np.array_equal(got_o, want_o), (shape, skew, d, o)
+            assert np.array_equal(got_o[c == 0], rgb[c == 0])
+
+
+def test_diff_regions_batch_of_three_sizes_with_a_rerun():
+    from unet_dc_segmentation_amd.evaluate import diff_regions_batch
+    names = ["realistic_moved/96x130", "four_classes", "random/37x53"]
+    pairs = [R.small_cases()[n] for n in names]
+    rng = np.random.default_rng(1)
+    rgbs = [rng.integers(0, 256, p.shape + (3,)).astype(np.uint8) for p, _ in pairs]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    assert len(host_record("four_classes")["class"]) > 2000 > len(host_record(names[0])["class"])      # only it takes the rerun
+    out = diff_regions_batch([dev(p) for p, _ in pairs], [dev(g) for _, g in pairs], 1, [dev(i) for i in rgbs], paint=True,
+                             max_regions=2000)
+    for name, (p, g), rgb, rec in zip(names, pairs, rgbs, out):
+        want = host_record(name)
+        for q in KEYS:
+            assert rec[q].dtype == np.int64 and np.array_equal(rec[q], want[q]), (name, q)
+        assert np.array_equal(rec["diff"].cpu().numpy(), D.difference_map_rgb(p, g))
+        assert np.array_equal(rec["overlay"].cpu().numpy(), D.overlay_difference(rgb, p, g))
+    plain = diff_regions_batch([dev(pairs[0][0])], [dev(pairs[0][1])], 5)
+    assert "diff" not in plain[0] and np.array_equal(plain[0]["area"], host_record(names[0], 5)["area"])
+
+
+def test_cli_diff_maps_on_the_device_equals_the_cpu_path(tmp_path, monkeypatch):
+    from tests.test_diffmap_cpu import DIFF_FILES, cli_gt_dir
+    from tests.test_split_cpu import files, run_cli
+    gt_dir = cli_gt_dir(tmp_path)
+    args = ["--gt_dir", str(gt_dir), "--diff_maps", "3", "--px_per_micron", "2.0"]
+    cpu = run_cli(tmp_path, monkeypatch, "cpu", args)
+    for tag, extra in (("gpu", []), ("gpu_density", ["--density_maps"])):
+        gpu = run_cli(tmp_path, monkeypatch, tag, args + extra, device="cuda")
+        assert set(DIFF_FILES) <= set(files(gpu))
+        for f in DIFF_FILES:
+            assert (gpu / f).read_bytes() == (cpu / f).read_bytes(), (tag, f)
+    assert len(pd.read_csv(cpu / "diff_regions.csv")) > 3
+
+
+def test_evaluate_test_diff_maps_on_the_device_equals_the_cpu_path(tmp_path):
+    from tests.test_diffmap_cpu import evaluate_fixed
+    cpu = evaluate_fixed(tmp_path / "cpu", "cpu")
+    gpu = evaluate_fixed(tmp_path / "gpu", "cuda")
+    assert cpu["record"]["diff_regions"] == gpu["record"]["diff_regions"] and cpu["files"] == gpu["files"] and len(cpu["files"]) == 6
+    for f in cpu["files"]:
+        assert (tmp_path / "cpu" / f).read_bytes() == (tmp_path / "gpu" / f).read_bytes(), f

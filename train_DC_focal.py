@@ -14,7 +14,7 @@ their own size and every batch is S x S random windows).  
 best checkpoint reloaded, test loss / Dice / pixel accuracy, precision / recall / F1 / specificity / confusion matrix) are
 computed and printed (with ``--tta N`` on the network's mean over N flipped and rotated variants of every input, as is
 ``--calibrate_thresh``: DESIGN.md section 17); ``--weight_decay``, ``--clip_grad``, ``--ema`` and ``--lr_schedule`` add the usual
-fine-tuning recipe to the fused optimizer step (without them the run is the reference's Adam(lr)); its PNG dumps and plots (:404-450, :468-611) are visualisation and out of scope.
+fine-tuning recipe to the fused optimizer step (without them the run is the reference's Adam(lr)); ``--diff_maps`` writes its difference-map and overlay dumps (:404-449); its plots (:468-611) are visualisation and out of scope.
 """
 import argparse
 import contextlib
@@ -99,6 +99,12 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
                    help="the final test evaluation also reports boundary accuracy: pooled HD95, average symmetric surface "
                         "distance, surface Dice (nsd) and boundary F at 1, 2, 3 pixels of the thresholded predictions against "
                         "the masks (both binary; distances beyond R pixels, 1..64, 64 without R, count as far)")
+    p.add_argument("--diff_maps", nargs="?", const=".", default=None, metavar="DIR",
+                   help="the final test evaluation also writes, per test image at the network's resolution, "
+                        "DIR/differences_map_test/NAME_diffmap.png (yellow: predicted and annotated, red: only annotated, green: "
+                        "only predicted) and DIR/overlay_diff_test/NAME_overlay.png (that map over the network's input), and "
+                        "reports the 8-connected yellow / red / green / black regions summed over the test set (region-level "
+                        "TP / FN / FP / TN; DESIGN.md section 25); DIR is the working directory without DIR")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--ckpt_path", default=ckpt)
     p.add_argument("--no_test_eval", dest="test_eval", action="store_false",
@@ -300,16 +306,48 @@ def boundary_report(state, radius):
     return {"R": radius, "hist": hist, "dmax": dmax, **boundary_columns(hist, dmax, radius, tols)}
 
 
-def evaluate_test(model, loader, criterion, device, tta=1, items=8, boundary=None):
-    """The reference's final test pass (train_DC_focal.py:365-402, :452-467) without its image dumps: mean loss and Dice over
-    the batches, pixel accuracy over all pixels, and calculate_metrics() on the thresholded predictions.  Sums stay on the
-    device (one read-back), like the training loop's.  tta, items: the number of variants of --tta and of items per forward.
-    boundary (a radius): also "boundary", the pooled boundary_report of the thresholded predictions against the masks."""
+def dump_diff_maps(images, yp, yt, names, out_dir):
+    """--diff_maps for one test batch: per image the difference map of the thresholded prediction against the mask (DESIGN.md
+    section 25) as out_dir/differences_map_test/NAME_diffmap.png and, painted on (image * 255) truncated to uint8 (reference
+    :439-440), out_dir/overlay_diff_test/NAME_overlay.png, both at the network's resolution.  On the HIP device the regions and
+    both pictures come from unetdc_diff_regions / unetdc_diff_paint (one wait per batch), on the CPU from
+    utils/difference_map.py.  -> the utils.difference_map.image_columns of every image."""
+    from PIL import Image
+    from utils import difference_map as dmap
+    preds, gts = yp[:, 0].to(torch.uint8).contiguous(), yt[:, 0].to(torch.uint8).contiguous()
+    rgbs = (images * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    if images.is_cuda:
+        from unet_dc_segmentation_amd.evaluate import diff_regions_batch
+        recs = diff_regions_batch(list(preds), list(gts), 1, list(rgbs), paint=True)
+        for r in recs:
+            r["diff"], r["overlay"] = r["diff"].cpu().numpy(), r["overlay"].cpu().numpy()
+    else:
+        recs = []
+        for p, g, rgb in zip(preds.numpy(), gts.numpy(), rgbs.numpy()):
+            recs.append({**dmap.diff_regions_numpy(p, g, 1), "diff": dmap.difference_map_rgb(p, g),
+                         "overlay": dmap.overlay_difference(rgb, p, g)})
+    for name, r in zip(names, recs):
+        Image.fromarray(r["diff"]).save(os.path.join(out_dir, "differences_map_test", f"{name}_diffmap.png"))
+        Image.fromarray(r["overlay"]).save(os.path.join(out_dir, "overlay_diff_test", f"{name}_overlay.png"))
+    return [dmap.image_columns(r) for r in recs]
+
+
+def evaluate_test(model, loader, criterion, device, tta=1, items=8, boundary=None, diff_maps=None):
+    """The reference's final test pass (train_DC_focal.py:365-402, :452-467): mean loss and Dice over the batches, pixel accuracy
+    over all pixels, and calculate_metrics() on the thresholded predictions.  Sums stay on the device (one read-back), like the
+    training loop's.  tta, items: the number of variants of --tta and of items per forward.
+    boundary (a radius): also "boundary", the pooled boundary_report of the thresholded predictions against the masks.
+    diff_maps (a directory): the reference's difference-map and overlay dumps (:404-449) under it, at the network's resolution,
+    named after the loader's file names (test_%05d where it yields none), and "diff_regions", the image_columns of
+    utils/difference_map.py summed over the test set (its *_blobs are the reference's count_color_regions_in_memory)."""
     model.eval()
     loss_t = torch.zeros((), dtype=torch.float64, device=device)
     dice_t = torch.zeros((), dtype=torch.float64, device=device)
     cm_t = torch.zeros(4, dtype=torch.int64, device=device)           # tn, fp, fn, tp
-    bstate = None
+    bstate, diff_rows, seen = None, [], 0
+    if diff_maps is not None:
+        for sub in ("differences_map_test", "overlay_diff_test"):
+            os.makedirs(os.path.join(diff_maps, sub), exist_ok=True)
     with torch.no_grad():
         for batch in loader:
             images, masks = batch[0].float().to(device), batch[1].float().to(device)
@@ -321,6 +359,12 @@ def evaluate_test(model, loader, criterion, device, tta=1, items=8, boundary=Non
             cm_t += torch.stack([(~yp & ~yt).sum(), (yp & ~yt).sum(), (~yp & yt).sum(), (yp & yt).sum()])
             if boundary is not None:
                 bstate = pool_boundary(yp, yt, boundary, bstate)
+            if diff_maps is not None:
+                names = batch[-1] if len(batch) > 2 and isinstance(batch[-1], (list, tuple)) and \
+                    all(isinstance(q, str) for q in batch[-1]) else None
+                names = [os.path.splitext(q)[0] for q in names] if names else [f"test_{seen + j:05d}" for j in range(len(images))]
+                diff_rows += dump_diff_maps(images, yp, yt, names, diff_maps)
+                seen += len(images)
     nb = max(1, len(loader))
     tn, fp, fn, tp = (int(v) for v in cm_t.tolist())
     precision, recall, f1, specificity, cm = metrics_from_counts(tn, fp, fn, tp)     # = calculate_metrics() on the label arrays
@@ -329,6 +373,9 @@ def evaluate_test(model, loader, criterion, device, tta=1, items=8, boundary=Non
                precision=precision, recall=recall, f1=f1, specificity=specificity, confusion=cm.tolist())
     if bstate is not None:
         out["boundary"] = boundary_report(bstate, boundary)
+    if diff_maps is not None:
+        from utils.difference_map import sum_image_columns
+        out["diff_regions"] = sum_image_columns(diff_rows)
     return out
 
 
@@ -374,6 +421,8 @@ def main(argv=None, parser=None):
     recipe = check_optim_flags(args)
     if args.boundary is not None and not 1 <= args.boundary <= 64:
         raise SystemExit("--boundary R: R must be in 1..64")
+    if args.diff_maps is not None and args.in_channels != 3:
+        raise SystemExit(f"--diff_maps paints on RGB inputs and cannot run with --in_channels {args.in_channels}")
     from utils.tta import TTA_SIZES
     if args.tta not in TTA_SIZES:
         raise SystemExit(f"--tta N: N must be one of {', '.join(map(str, TTA_SIZES))}, not {args.tta}")
@@ -599,7 +648,8 @@ def main(argv=None, parser=None):
                                      pin_memory=pin)
         # every rank: same weights, same split
         with ema_weights():
-            history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch, args.boundary)
+            history.test = evaluate_test(model, test_loader, criterion, device, args.tta, args.batch, args.boundary,
+                                         args.diff_maps if rank == 0 else None)
         if rank == 0:
             t = history.test
             print("========== Test Results ==========" + (f" (--tta {args.tta})" if args.tta != 1 else ""))
@@ -613,6 +663,11 @@ def main(argv=None, parser=None):
                 b = t["boundary"]
                 per_tol = ", ".join(f"nsd_{q} {b[f'nsd_{q}']:.4f}, bf_{q} {b[f'bf_{q}']:.4f}" for q in (1, 2, 3) if f"nsd_{q}" in b)
                 print(f"Boundary (--boundary {b['R']}, pooled): HD95 {b['hd95']:.3f} px, ASSD {b['assd']:.3f} px, {per_tol}")
+            if "diff_regions" in t:
+                d = t["diff_regions"]
+                print(f"Difference maps under {args.diff_maps}: regions yellow {d['yellow_blobs']}, red {d['red_blobs']}, green "
+                      f"{d['green_blobs']}, black {d['black_blobs']}; missed droplets {d['missed_droplets']}, spurious "
+                      f"{d['spurious_droplets']}")
     if args.calibrate_thresh is not None and len(val_ds) > 0:
         with ema_weights():                                 # the weights the test evaluation used
             history.calibration = calibrate_threshold(model, val_loader, args.calibrate_thresh, device, args.tta,

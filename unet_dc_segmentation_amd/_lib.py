@@ -114,6 +114,9 @@ SIGNATURES = {
     "unetdc_label_neighbors": (I, [P, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P]),
     "unetdc_mask_clean_workspace": (L, [I, I]),
     "unetdc_mask_clean": (I, [P, P, I, I, I, P, L, P, P, P]),
+    "unetdc_diff_regions_workspace": (L, [I, I]),
+    "unetdc_diff_regions": (I, [P, P, I, I, I, P, L, P, P, P, P, P, P, P, I, P]),
+    "unetdc_diff_paint": (I, [P, P, P, I, I, P, P, P]),
     "unetdc_thresh_sweep": (I, [P, I, I, I, P, I, I, P, P, P, P, I, P, P]),
     "unetdc_tile_gather_u8_to_chw_f32": (I, [P, I, I, I, P, I, P, I, P, I, I, I, P]),
     "unetdc_tile_blend_f32": (I, [P, I, I, P, I, P, I, P, I, I, P]),

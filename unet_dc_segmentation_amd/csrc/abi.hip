@@ -678,6 +678,21 @@ int unetdc_mask_clean(const uint8_t* strong, const uint8_t* weak, int h, int w, 
                            (hipStream_t)s);
 }
 
+int64_t unetdc_diff_regions_workspace(int h, int w) { return diff_regions_workspace_bytes(h, w); }
+
+int unetdc_diff_regions(const uint8_t* pred, const uint8_t* gt, int h, int w, int min_area, void* workspace,
+                        int64_t workspace_bytes, int64_t* out_image, int32_t* out_count, int32_t* out_class, int32_t* out_area,
+                        int64_t* out_sumy, int64_t* out_sumx, int32_t* out_neighbors, int max_out, unetdc_stream_t s) {
+  return launch_diff_regions(pred, gt, h, w, min_area, workspace, (long)workspace_bytes, reinterpret_cast<long long*>(out_image),
+                             out_count, out_class, out_area, reinterpret_cast<long long*>(out_sumy),
+                             reinterpret_cast<long long*>(out_sumx), out_neighbors, max_out, (hipStream_t)s);
+}
+
+int unetdc_diff_paint(const uint8_t* pred, const uint8_t* gt, const uint8_t* rgb, int h, int w, uint8_t* out_diff,
+                      uint8_t* out_overlay, unetdc_stream_t s) {
+  return launch_diff_paint(pred, gt, rgb, h, w, out_diff, out_overlay, (hipStream_t)s);
+}
+
 int unetdc_thresh_sweep(const float* probs, int n, int ph, int pw, const uint8_t* gt, int oh, int ow, const int32_t* xofs,
                         const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int k, int64_t* hist,
                         unetdc_stream_t s) {

@@ -235,13 +235,17 @@ void launch_ccl_init(const unsigned char* mask, const CclPlanes& p, int n, hipSt
   hipLaunchKernelGGL(ccl_init_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n);
 }
 
+void launch_ccl_scan(int* blocksum, int nblocks, int* total, hipStream_t stream) {
+  hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, stream, blocksum, nblocks, total);
+}
+
 void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, const CclPlanes& p, int* out_count,
                        int* out_area, long long* out_sumy, long long* out_sumx, int* out_root, int* rank_of_root, int max_out,
                        hipStream_t stream) {
   const int n = h * w, nb = (n + CCL_BLK - 1) / CCL_BLK, g = grid_for(n, 256, 4096);
   hipLaunchKernelGGL(ccl_stats_kernel, dim3(g), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, h, w);
   hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, stream, mask, p.L, p.area, n, min_area, p.blocksum);
-  hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, stream, p.blocksum, nb, out_count);
+  launch_ccl_scan(p.blocksum, nb, out_count, stream);
   hipLaunchKernelGGL(ccl_emit_kernel, dim3(nb), dim3(256), 0, stream, mask, p.L, p.area, p.sy, p.sx, n, min_area, p.blocksum,
                      max_out, out_area, out_sumy, out_sumx, out_root, rank_of_root);
 }

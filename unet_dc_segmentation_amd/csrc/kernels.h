@@ -289,6 +289,9 @@ void launch_ccl_finish(const unsigned char* mask, int h, int w, int min_area, co
 // launch_ccl_finish, which compresses L and fills rank_of_root)
 void launch_ccl_label(const unsigned char* mask, const CclPlanes& p, const int* rank_of_root, int min_area, int* label, int n,
                       hipStream_t stream);
+// the scan of launch_ccl_finish alone, for diffmap.hip: blocksum[0 .. nblocks) (nblocks <= 2^20) -> its exclusive prefix sums
+// in place, *total = the sum
+void launch_ccl_scan(int* blocksum, int nblocks, int* total, hipStream_t stream);
 
 // shape.hip: per-label second moments, bounding box, perimeter classes and grey statistics of an int32 label map
 constexpr int SHAPE_QUANTITIES = 14;
@@ -342,6 +345,15 @@ int launch_split_stats(const unsigned char* mask, int h, int w, int min_area, in
 long mask_clean_workspace_bytes(int h, int w);
 int launch_mask_clean(const unsigned char* strong, const unsigned char* weak, int h, int w, int max_hole_area, void* workspace,
                       long workspace_bytes, unsigned char* out_mask, int* out_counts, hipStream_t stream);
+
+// diffmap.hip: the difference map of a predicted mask against an annotated one, and its 8-connected regions of equal class
+// (include/unetdc_hip.h)
+long diff_regions_workspace_bytes(int h, int w);            // 0 for a geometry the call refuses
+int launch_diff_regions(const unsigned char* pred, const unsigned char* gt, int h, int w, int min_area, void* workspace,
+                        long workspace_bytes, long long* out_image, int* out_count, int* out_class, int* out_area,
+                        long long* out_sumy, long long* out_sumx, int* out_neighbors, int max_out, hipStream_t stream);
+int launch_diff_paint(const unsigned char* pred, const unsigned char* gt, const unsigned char* rgb, int h, int w,
+                      unsigned char* out_diff, unsigned char* out_overlay, hipStream_t stream);
 
 // sweep.hip: the confusion matrix of the thresholded mask against an annotation at every threshold of a grid (DESIGN.md
 // section 14; include/unetdc_hip.h)

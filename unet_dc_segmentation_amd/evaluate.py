@@ -288,6 +288,101 @@ def boundary_batch(pred_labels, kas, gt_labels, kbs, radius, hist=None, dmax=Non
     return out
 
 
+def _check_plane(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_contiguous():
+        raise _lib.UnetdcError(f"{what} must be a contiguous uint8 [h, w] tensor on the HIP device")
+
+
+def _diff_tables(v32, v64, n):
+    """Row j of the int32 planes (class, area, neighbors) and of the int64 planes (sumy, sumx) -> the table of n rows."""
+    return {"class": v32[0, :n].astype(np.int64), "area": v32[1, :n].astype(np.int64), "sumy": v64[0, :n].copy(),
+            "sumx": v64[1, :n].copy(), "neighbors": v32[2, :n].astype(np.int64)}
+
+
+def diff_regions_batch(preds, gts, min_area=1, images=None, paint=False, max_regions=1 << 14):
+    """preds, gts: B uint8 [h, w] DEVICE planes each (nonzero = set; image i of both lists has one size, the sizes may differ
+    between images); images: optionally B uint8 [h, w, 3] DEVICE tensors, the pictures the overlays are painted on.
+    Per image unetdc_diff_regions (and with paint unetdc_diff_paint) is enqueued back to back on the current stream into ONE
+    workspace and one set of output planes; the host then waits ONCE, on the copy of the twelve image integers and the row
+    counts, and fetches the filled part of the tables.  An image with more rows than max_regions is run again alone with room.
+    Returns per image the record of utils.difference_map.diff_regions_numpy: image (int64 [12]), class, area, sumy, sumx,
+    neighbors (int64 arrays); with paint also diff (uint8 [h, w, 3] DEVICE tensor) and overlay (the same on images[i]; None
+    without images)."""
+    B = len(preds)
+    if len(gts) != B or (images is not None and len(images) != B):
+        raise _lib.UnetdcError("diff_regions_batch needs one annotation (and one image, if any) per prediction")
+    if B == 0:
+        return []
+    min_area, max_regions = int(min_area), int(max_regions)
+    if min_area < 1 or max_regions < 0:
+        raise _lib.UnetdcError("diff_regions_batch: min_area >= 1, max_regions >= 0")
+    lib = _lib.load()
+    hws = []
+    for i, (p, g) in enumerate(zip(preds, gts)):
+        _check_plane(p, "a prediction")
+        _check_plane(g, "an annotation")
+        if p.shape != g.shape:
+            raise _lib.UnetdcError(f"annotation {i} is {tuple(g.shape)}, its prediction {tuple(p.shape)}")
+        hws.append((int(p.shape[0]), int(p.shape[1])))
+        if images is not None:
+            im = images[i]
+            if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and tuple(im.shape) == hws[i] + (3,) and
+                    im.is_contiguous()):
+                raise _lib.UnetdcError(f"image {i} must be a contiguous uint8 {hws[i] + (3,)} tensor on the HIP device")
+    sizes = [lib.unetdc_diff_regions_workspace(h, w) for h, w in hws]
+    if min(sizes) <= 0:
+        raise _lib.UnetdcError("diff_regions_batch: sides 1..16384, h * w < 2^30")
+    s = torch.cuda.current_stream().cuda_stream
+    dev = preds[0].device
+    wsb = max(sizes)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)           # one workspace: the launches are stream-ordered
+    cap = int(min(max_regions, max(h * w for h, w in hws)))
+    head = torch.zeros(B, 13, dtype=torch.int64, device=dev)       # the twelve image integers, then the row count (int32)
+    i32 = torch.empty(B, 3, max(cap, 1), dtype=torch.int32, device=dev)     # class, area, neighbors
+    i64 = torch.empty(B, 2, max(cap, 1), dtype=torch.int64, device=dev)     # sumy, sumx
+    pics = []
+    for i, (h, w) in enumerate(hws):
+        tables = [i32[i, 0], i32[i, 1], i64[i, 0], i64[i, 1], i32[i, 2]] if cap else [None] * 5
+        _lib.call("unetdc_diff_regions", preds[i].data_ptr(), gts[i].data_ptr(), h, w, min_area, ws.data_ptr(), wsb,
+                  head[i].data_ptr(), head[i, 12:].data_ptr(), *(t.data_ptr() if t is not None else None for t in tables), cap, s)
+        if paint:
+            diff = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+            over = torch.empty(h, w, 3, dtype=torch.uint8, device=dev) if images is not None else None
+            _lib.call("unetdc_diff_paint", preds[i].data_ptr(), gts[i].data_ptr(),
+                      images[i].data_ptr() if images is not None else None, h, w, diff.data_ptr(),
+                      over.data_ptr() if over is not None else None, s)
+            pics.append((diff, over))
+    host = head.cpu().numpy()                                      # the batch's only host wait
+    counts = host[:, 12] & 0xFFFFFFFF                              # the int32 the call wrote into the zeroed word
+    filled = int(np.minimum(counts, cap).max(initial=0))
+    v32 = i32[:, :, :filled].cpu().numpy()
+    v64 = i64[:, :, :filled].cpu().numpy()
+    out = []
+    for i, (h, w) in enumerate(hws):
+        n = int(counts[i])
+        if n > cap:                                                # more rows than the planes hold: this image again with room
+            rec = _diff_regions_again(preds[i], gts[i], h, w, min_area, n, s)
+        else:
+            rec = {"image": host[i, :12].copy(), **_diff_tables(v32[i], v64[i], n)}
+        if paint:
+            rec["diff"], rec["overlay"] = pics[i]
+        out.append(rec)
+    return out
+
+
+def _diff_regions_again(pred, gt, h, w, min_area, n, s):
+    lib, dev = _lib.load(), pred.device
+    wsb = lib.unetdc_diff_regions_workspace(h, w)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    head = torch.zeros(13, dtype=torch.int64, device=dev)
+    i32 = torch.empty(3, n, dtype=torch.int32, device=dev)
+    i64 = torch.empty(2, n, dtype=torch.int64, device=dev)
+    _lib.call("unetdc_diff_regions", pred.data_ptr(), gt.data_ptr(), h, w, min_area, ws.data_ptr(), wsb, head.data_ptr(),
+              head[12:].data_ptr(), i32[0].data_ptr(), i32[1].data_ptr(), i64[0].data_ptr(), i64[1].data_ptr(), i32[2].data_ptr(),
+              n, s)
+    return {"image": head[:12].cpu().numpy(), **_diff_tables(i32.cpu().numpy(), i64.cpu().numpy(), n)}
+
+
 def boundary_result(hist, dmax):
     """The pooled device planes of boundary_batch -> (int64 numpy [2, R^2 + 2], int64 numpy [2])."""
     return hist.cpu().numpy(), dmax.cpu().numpy().astype(np.int64)
