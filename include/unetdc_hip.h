@@ -692,6 +692,33 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                            int32_t* out_cluster_size, unetdc_stream_t s);
 
 
+/* ---- Ripley's K of the droplet centroids with simulated patterns (spatial.hip; the definition is DESIGN.md section 26) --------
+ * unetdc_droplet_points: the droplet table of unetdc_ccl_stats (*count droplets: area, sum of rows, sum of columns; device
+ *   memory) -> the centroid pixels y = (2 sum_y + area) div (2 area), x likewise, of the droplets whose pixel lies in the
+ *   window (uint8 [h][w], nonzero = inside; NULL: every pixel), in table order: out_py / out_px (int32 [max_points]).
+ *   out_info (int32 [4]): N (the points written), n_dropped, A (the pixels of the window) and a flags word; bit 0 of the
+ *   flags: *count exceeds max_points, the other outputs are then unspecified and nothing beyond max_points entries is
+ *   written: repeat with more room.  Sides 1..16384, max_points 1..2^20.
+ * unetdc_ripley_counts: N = *n_points points (py, px: int32, inside the image and the window; N is cut to max_points) -> for
+ *   r = 0..rmax and the point sets 0 (the given points) and s + 1 (simulation s of n_sim: N pixels of the window drawn with
+ *   replacement by a counter hash of (seed, s, k)):
+ *     out_n [(1 + n_sim)][rmax + 1] int32: the points whose distance to the border of the window and of the image exceeds r;
+ *     out_pairs, out_pairs_all (int64, same shape): the ordered pairs (i, j), i != j, at most r apart (the distance rounded
+ *     up to an integer), out_pairs only those whose i counts in out_n at r.
+ *   The simulation rows are zero without a point or without a window pixel.  rmax 1..256, n_sim 0..999, max_points 1..2^20,
+ *   sides 1..16384; workspace: unetdc_ripley_workspace(h, w, max_points, rmax, n_sim) bytes (0 for arguments the call would
+ *   refuse), 8-byte aligned; it may hold anything on entry.  Nothing but the outputs and the workspace is written.
+ * Both launch on the given stream only: no host wait, no allocation.  Integer work and integer atomics: bitwise
+ * reproducible. */
+int64_t unetdc_ripley_workspace(int h, int w, int max_points, int rmax, int n_sim);
+int unetdc_droplet_points(const int32_t* count, const int32_t* area, const int64_t* sum_y, const int64_t* sum_x, int max_points,
+                          const uint8_t* window, int h, int w, int32_t* out_py, int32_t* out_px, int32_t* out_info,
+                          unetdc_stream_t s);
+int unetdc_ripley_counts(const int32_t* py, const int32_t* px, const int32_t* n_points, int max_points, const uint8_t* window,
+                         int h, int w, int rmax, int n_sim, uint32_t seed, void* workspace, int64_t workspace_bytes,
+                         int32_t* out_n, int64_t* out_pairs, int64_t* out_pairs_all, unetdc_stream_t s);
+
+
 /* ---- surface distances between two label maps (boundary.hip; the definition is DESIGN.md section 21) -----------------------
  * unetdc_boundary_distances: label_a (the prediction), label_b (the annotation): [h][w] int32 label maps, objects 1..max_a and
  *   1..max_b; a value below 1 or above the maximum reads as 0.  A binary mask is the label map with max = 1.

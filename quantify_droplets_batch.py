@@ -23,6 +23,7 @@ and a few integers per droplet come back:
     --confidence      (droplets.py, tta.py)                     csrc/confidence.hip tta.hip  CPU: utils/droplet_confidence.py
     --droplet_hull    (droplets.py)                             csrc/hull.hip           CPU: utils/droplet_hull.py
     --diff_maps       unet_dc_segmentation_amd/evaluate.py      csrc/diffmap.hip        CPU: utils/difference_map.py
+    --spatial_stats   unet_dc_segmentation_amd/spatial.py       csrc/spatial.hip        CPU: utils/spatial_stats.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -107,6 +108,7 @@ class Run:
     confidence: dict | None = None     # confidence_options(); its "rows" collect confidence_per_image.csv
     hull: float | None = None          # --droplet_hull: the solidity below which a droplet is flagged, None without the flag
     diff: dict | None = None           # diff_options(); its "tables" / "rows" collect diff_regions.csv and diff_regions_per_image.csv
+    spatial: dict | None = None        # spatial_options(); its "table" / "rows" collect spatial_stats.csv and spatial_per_image.csv
 
     @property
     def keep_rgb(self):
@@ -144,6 +146,7 @@ class Batch:
     grays: list = dataclasses.field(default_factory=list)      # --droplet_shape: the ORIGINAL image as grey, uint8 [oh, ow]
     rgbs: list = dataclasses.field(default_factory=list)       # --density_maps, --diff_maps: the decoded image (a device tensor on the GPU)
     gt_items: list = dataclasses.field(default_factory=list)   # --gt_dir: the decoded annotations
+    windows: list = dataclasses.field(default_factory=list)    # --spatial_window_dir: the decoded windows, uint8 {0, 1}
 
 
 def predict_tiled_image(model, im, run):
@@ -258,18 +261,18 @@ def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".tif", ".tiff")
 
 
-def find_gt_files(images, gt_dir):
+def find_gt_files(images, gt_dir, flag="--gt_dir", what="annotated mask"):
     """--gt_dir: {image path: annotation path}, checked before anything runs.  The annotation of NAME.ext is
     gt_dir/NAME.<any image suffix>; a missing one, or one whose size differs from its image, ends the run (PIL reads the
-    sizes from the headers, nothing is decoded)."""
+    sizes from the headers, nothing is decoded).  --spatial_window_dir finds its windows by the same rule."""
     found = {}
     for img in images:
         cands = [q for q in sorted(Path(gt_dir).glob(img.stem + ".*")) if q.suffix.lower() in IMAGE_SUFFIXES and q.stem == img.stem]
         if not cands:
-            raise SystemExit(f"--gt_dir: no annotated mask for {img.name} ({Path(gt_dir) / (img.stem + '.*')})")
+            raise SystemExit(f"{flag}: no {what} for {img.name} ({Path(gt_dir) / (img.stem + '.*')})")
         with Image.open(img) as a, Image.open(cands[0]) as b:
             if a.size != b.size:
-                raise SystemExit(f"--gt_dir: {cands[0]} is {b.size[0]} x {b.size[1]}, its image {img.name} {a.size[0]} x {a.size[1]}")
+                raise SystemExit(f"{flag}: {cands[0]} is {b.size[0]} x {b.size[1]}, its image {img.name} {a.size[0]} x {a.size[1]}")
         found[str(img)] = cands[0]
     return found
 
@@ -352,6 +355,30 @@ def add_hull_outputs(run, df, d):
     if not df.empty:
         df = pd.concat([df, pd.DataFrame(cols, index=df.index)], axis=1)
     return df, dh.hull_summary(cols)
+
+
+def add_spatial_outputs(run, batch, out, sums, on_device):
+    """--spatial_stats for one batch: the counts of DESIGN.md section 26 from the droplet table alone (on the device from the
+    sums the droplet stage left there, one more batch of launches and one more wait; on the CPU from the label map's sums),
+    then the rows of spatial_stats.csv and spatial_per_image.csv, which utils.spatial_stats derives on both paths."""
+    from utils import spatial_stats as ss
+    sp, hws = run.spatial, [m[1] for m in batch.meta]
+    windows = batch.windows or [None] * len(hws)
+    if on_device:
+        from unet_dc_segmentation_amd.spatial import spatial_stats_batch
+        wins = [None if win is None else torch.from_numpy(win).to(DEVICE) for win in windows]
+        recs = spatial_stats_batch(sums, hws, sp["R"], sp["S"], sp["seed"], wins, masks=[d.mask for d in out])
+    else:
+        from utils.droplet_match import gt_labels_numpy, label_sums
+        recs = []
+        for d, hw, win in zip(out, hws, windows):
+            lab = d.labels if d.labels is not None else gt_labels_numpy(d.mask, run.min_area)
+            recs.append(ss.spatial_record(*label_sums(lab), *hw, sp["R"], sp["S"], sp["seed"], win))
+    for rec, (fpath, _) in zip(recs, batch.meta):
+        filename = Path(fpath).name
+        res = ss.analyse(rec["n"], rec["pairs"], rec["pairs_all"], rec["A"], rec["N"])
+        sp["rows"].append(ss.summary_row(filename, rec, res))
+        sp["table"].extend(ss.table_rows(filename, (rec["n"], rec["pairs"], rec["pairs_all"]), res, run.px_per_um))
 
 
 def _write_map(plane, path):
@@ -557,6 +584,8 @@ def finish_batch(run, batch, probs):
                                   run.density["nb_layers"], run.density["kernel"])
     if run.diff is not None:
         add_diff_outputs(run, batch, out)
+    if run.spatial is not None:
+        add_spatial_outputs(run, batch, out, sums, probs.is_cuda)
     for i, (d, (fpath, hw)) in enumerate(zip(out, batch.meta)):
         filename, name = Path(fpath).name, Path(fpath).stem
         mask = _host(d.mask)
@@ -595,6 +624,14 @@ def _radius_arg(text):
         return check_radius(int(text))
     except ValueError:
         raise argparse.ArgumentTypeError(f"G must be an integer number of pixels in 1..64, not {text!r}")
+
+
+def _spatial_radius_arg(text):
+    from utils.spatial_stats import check_radius
+    try:
+        return check_radius(int(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"R must be an integer number of pixels in 1..256, not {text!r}")
 
 
 def build_parser():
@@ -705,6 +742,16 @@ def build_parser():
                         "regions = region-level TP / FN / FP / TN, their pixels, the regions kept, missed_droplets, "
                         "spurious_droplets).  The prediction is the mask the droplet stage measured (after --prob_thresh_low / "
                         "--fill_holes), the annotation is grey > 0, with --gt_labels label > 0; --gt_min_area does not apply here")
+    p.add_argument("--spatial_stats", type=_spatial_radius_arg, nargs="?", const=64, metavar="R",
+                   help="Ripley's K(r), L(r) - r and g(r) of the droplet centroids for r = 1..R pixels (default 64, at most 256), "
+                        "border-corrected, with the envelope of --spatial_sims patterns of complete spatial randomness in the "
+                        "same window: spatial_stats.csv (one row per image and r) and spatial_per_image.csv (csr_p, pattern)")
+    p.add_argument("--spatial_sims", type=int, default=99, metavar="S",
+                   help="simulated patterns behind the envelope and csr_p of --spatial_stats, 0..999 (0: no envelope)")
+    p.add_argument("--spatial_seed", type=int, default=0, help="32-bit seed of the simulated patterns of --spatial_stats")
+    p.add_argument("--spatial_window_dir", metavar="D",
+                   help="observation windows of --spatial_stats: the window of NAME.ext is D/NAME.<image suffix>, nonzero = "
+                        "inside, of its image's size; without it the window is the whole image")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -783,6 +830,26 @@ def confidence_options(args):
     return {"band": band, "maps": bool(args.confidence_maps), "rows": []}
 
 
+def spatial_options(args, images):
+    """--spatial_stats -> {"R", "S", "seed", "files" ({image path: window path} or None), "table", "rows"} or None; every window
+    is there and of its image's size, or nothing runs."""
+    if args.spatial_stats is None:
+        if args.spatial_window_dir:
+            raise SystemExit("--spatial_window_dir belongs to --spatial_stats")
+        return None
+    from utils.spatial_stats import check_sims
+    try:
+        sims = check_sims(args.spatial_sims)
+    except ValueError as e:
+        raise SystemExit(f"--spatial_sims S: {e}")
+    if not 0 <= args.spatial_seed < 2 ** 32:
+        raise SystemExit("--spatial_seed must be in 0..2^32 - 1")
+    files = None
+    if args.spatial_window_dir:
+        files = find_gt_files(images, args.spatial_window_dir, "--spatial_window_dir", "window")
+    return {"R": args.spatial_stats, "S": sims, "seed": args.spatial_seed, "files": files, "table": [], "rows": []}
+
+
 def tile_options(args):
     """--tile / --tile_overlap -> {"T", "O"}, None without --tile; a bad value ends the run before any image."""
     if args.tile is None:
@@ -844,6 +911,7 @@ def main(argv=None):
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
         gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels}
+    spatial = spatial_options(args, images)
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -875,7 +943,8 @@ def main(argv=None):
                   background_radius=args.background_radius, batch_size=args.batch, split_depth=split_depth,
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
-                  neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff)
+                  neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff,
+                  spatial=spatial)
         ahead = deque()
         it = iter(images)
 
@@ -885,12 +954,14 @@ def main(argv=None):
                 if nxt is None:
                     return
                 ahead.append((nxt, dec_pool.submit(decode_rgb, nxt),
-                              None if gt is None else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"])))
+                              None if gt is None else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"]),
+                              None if spatial is None or spatial["files"] is None
+                              else dec_pool.submit(decode_gt, spatial["files"][str(nxt)], False)))
 
         refill()
         batch = Batch()
         while ahead:
-            img, fut, gt_fut = ahead.popleft()
+            img, fut, gt_fut, win_fut = ahead.popleft()
             refill()
             im = fut.result()
             batch.meta.append((str(img), im.shape[:2]))
@@ -899,6 +970,8 @@ def main(argv=None):
                 batch.grays.append(rgb_to_gray(im))
             if gt is not None:
                 batch.gt_items.append(gt_fut.result())
+            if win_fut is not None:
+                batch.windows.append(win_fut.result())
             if tile is not None:                         # native size: one map per image, the stages on a batch of one
                 probs, rgb = predict_tiled_image(model, im, run)
                 batch.rgbs.append(rgb)
@@ -937,6 +1010,10 @@ def main(argv=None):
         tables = [t for t in diff["tables"] if len(t)] or diff["tables"][:1]
         pd.concat(tables, ignore_index=True).to_csv(out_dir / "diff_regions.csv", index=False) if tables else None
         pd.DataFrame(diff["rows"], columns=("filename",) + dmap.IMAGE_COLUMNS).to_csv(out_dir / "diff_regions_per_image.csv", index=False)
+    if spatial is not None:
+        from utils import spatial_stats as ss
+        pd.DataFrame(spatial["table"], columns=ss.table_columns(run.px_per_um)).to_csv(out_dir / "spatial_stats.csv", index=False)
+        pd.DataFrame(spatial["rows"], columns=ss.IMAGE_COLUMNS).to_csv(out_dir / "spatial_per_image.csv", index=False)
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     if run.neighbors is not None and run.contact_tables:

@@ -2,7 +2,7 @@
 """Registers / scratch / LDS of every kernel in libunetdc_hip.so, from the code objects' metadata notes (no GPU needed).
 
     python tools/kernel_resources.py [substring ...]      e.g.  python tools/kernel_resources.py lattice convt
-A non-zero scratch size means spills: in the kernels with hand-counted vmcnt waits a scratch reload drains the VM queue."""
+lds is the static group segment (dynamic LDS is sized at the launch).  A non-zero scratch size means spills: in the kernels with hand-counted vmcnt waits a scratch reload drains the VM queue."""
 import os
 import re
 import subprocess
@@ -21,7 +21,7 @@ def kernels(so_path=B.OUT):
             f.write(elf)
             f.flush()
             txt = subprocess.run([readelf, "--notes", f.name], capture_output=True, text=True).stdout
-        for blk in re.split(r"\n\s+- ", txt):
+        for blk in re.split(r"\n  - ", txt):                    # one block per kernel (argument entries sit deeper)
             m = re.search(r"\.name:\s+(\S+)", blk)
             if not m or ".vgpr_count" not in blk:
                 continue
@@ -38,5 +38,5 @@ if __name__ == "__main__":
     for k, d in zip(kernels(), dem):
         if pats and not any(p in d for p in pats):
             continue
-        print(f"{d[:110]:110s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} sgpr {k['sgpr']:3d} scratch {k['scratch']:4d} "
+        print(f"{d[:110]:110s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} sgpr {k['sgpr']:3d} lds {k['lds']:5d} scratch {k['scratch']:4d} "
               f"spill v/s {k['spill_v']}/{k['spill_s']}")

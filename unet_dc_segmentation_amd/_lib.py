@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_void_p
 
 import torch  # noqa: F401  (must be imported before the CDLL below -- see module docstring)
 
@@ -18,7 +18,7 @@ EDT_INF = 2 ** 31 - 1      # UNETDC_EDT_INF: the squared distance of every pixel
 LIB_NAME = "libunetdc_hip.so"
 LIB_PATH = os.environ.get("UNETDC_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
-P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
+P, I, L, F, D, U = c_void_p, c_int, c_int64, c_float, c_double, c_uint32
 
 # UNETDC_ABI_VERSION of include/unetdc_hip.h that SIGNATURES describes.  load() refuses a library reporting another version
 # (e.g. a UNETDC_LIB base build of an older revision), which would otherwise be called with shifted arguments.
@@ -112,6 +112,9 @@ SIGNATURES = {
     "unetdc_boundary_distances": (I, [P, I, P, I, I, I, I, P, L, P, P, P, P, P]),
     "unetdc_label_neighbors_workspace": (L, [I, I, I, I]),
     "unetdc_label_neighbors": (I, [P, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P]),
+    "unetdc_ripley_workspace": (L, [I, I, I, I, I]),
+    "unetdc_droplet_points": (I, [P, P, P, P, I, P, I, I, P, P, P, P]),
+    "unetdc_ripley_counts": (I, [P, P, P, I, P, I, I, I, I, U, P, L, P, P, P, P]),
     "unetdc_mask_clean_workspace": (L, [I, I]),
     "unetdc_mask_clean": (I, [P, P, I, I, I, P, L, P, P, P]),
     "unetdc_diff_regions_workspace": (L, [I, I]),

@@ -660,6 +660,25 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                                 max_pairs, out_nn_label, out_nn_d2, out_degree, out_cluster, out_cluster_size, (hipStream_t)s);
 }
 
+int64_t unetdc_ripley_workspace(int h, int w, int max_points, int rmax, int n_sim) {
+  return ripley_workspace_bytes(h, w, max_points, rmax, n_sim);
+}
+
+int unetdc_droplet_points(const int32_t* count, const int32_t* area, const int64_t* sum_y, const int64_t* sum_x, int max_points,
+                          const uint8_t* window, int h, int w, int32_t* out_py, int32_t* out_px, int32_t* out_info,
+                          unetdc_stream_t s) {
+  return launch_droplet_points(count, area, reinterpret_cast<const long long*>(sum_y), reinterpret_cast<const long long*>(sum_x),
+                               max_points, window, h, w, out_py, out_px, out_info, (hipStream_t)s);
+}
+
+int unetdc_ripley_counts(const int32_t* py, const int32_t* px, const int32_t* n_points, int max_points, const uint8_t* window,
+                         int h, int w, int rmax, int n_sim, uint32_t seed, void* workspace, int64_t workspace_bytes,
+                         int32_t* out_n, int64_t* out_pairs, int64_t* out_pairs_all, unetdc_stream_t s) {
+  return launch_ripley_counts(py, px, n_points, max_points, window, h, w, rmax, n_sim, seed, workspace, (long)workspace_bytes,
+                              out_n, reinterpret_cast<long long*>(out_pairs), reinterpret_cast<long long*>(out_pairs_all),
+                              (hipStream_t)s);
+}
+
 int64_t unetdc_boundary_distances_workspace(int h, int w) { return boundary_distances_workspace_bytes(h, w); }
 
 int unetdc_boundary_distances(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, int radius,

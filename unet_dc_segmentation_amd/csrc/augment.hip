@@ -22,6 +22,7 @@
 // part and fraction from the displacement alone (floor(d), d - floor(d): exact in float32), not from y + d, which would drop
 // bits of the fraction near y = 512.
 #include "gather_index.h"
+#include "hash32.h"
 #include "kernels.h"
 
 namespace unetdc {
@@ -38,15 +39,6 @@ struct AugSeeds {
 struct AugBatch {
   AugRecord r[AUG_MAX_BATCH];
 };
-
-__host__ __device__ inline unsigned aug_fmix32(unsigned h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 
 // hash of (seed, component, y) -- the per-row part of the noise counter
 __device__ inline unsigned aug_row_key(unsigned seed, int comp, int y) {

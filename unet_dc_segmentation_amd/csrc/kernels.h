@@ -324,6 +324,16 @@ int launch_label_neighbors(const int* label, int max_label, int h, int w, int ra
                            int* out_count, int* out_a, int* out_b, int* out_d2, int max_pairs, int* out_nn_label,
                            int* out_nn_d2, int* out_degree, int* out_cluster, int* out_cluster_size, hipStream_t stream);
 
+// spatial.hip: centroid pixels of a droplet table; Ripley counts of the observed pattern and of simulated ones (DESIGN.md
+// section 26)
+long ripley_workspace_bytes(int h, int w, int max_points, int rmax, int n_sim);         // 0 for arguments the call refuses
+int launch_droplet_points(const int* count, const int* area, const long long* sum_y, const long long* sum_x, int max_points,
+                          const unsigned char* window, int h, int w, int* out_py, int* out_px, int* out_info,
+                          hipStream_t stream);
+int launch_ripley_counts(const int* py, const int* px, const int* n_points, int max_points, const unsigned char* window, int h,
+                         int w, int rmax, int n_sim, unsigned seed, void* workspace, long workspace_bytes, int* out_n,
+                         long long* out_pairs, long long* out_pairs_all, hipStream_t stream);
+
 // boundary.hip: surface distances between the boundary pixels of two int32 label maps
 long boundary_distances_workspace_bytes(int h, int w);      // 0 for a geometry the call refuses
 int launch_boundary_distances(const int* label_a, int max_a, const int* label_b, int max_b, int h, int w, int radius,
