@@ -10,6 +10,18 @@ from utils import density as hd
 
 WAVE_UNITS_PER_TRIP = 8192 * 4    # label_props_kernel / match_overlap_kernel: 8192 blocks of 4 waves, one 64-pixel unit per wave
 CAP_SHAPES = ((8200, 257), (600, 3521))
+# Mirrors of the caps of hull.hip, spatial.hip and border.hip; tests/test_droplet_edges_cpu.py reads the constexpr values and the
+# launch lines from the sources and checks every one of them.  The fixtures that pass them are in tests/cap_fixtures.py.
+HULL_MAX_GROUPS = 4096            # hull_caliper_kernel: workgroups of 4 waves, one label per wave
+HULL_MAX_CHAINS = 1 << 15         # hull_chain_kernel: one-wave workgroups, one per (label, side)
+HULL_LDS_POINTS = 2048            # levels, and chunk vertices, of one side that a chain pass holds in LDS
+HULL_LABELS_PER_TRIP = min(HULL_MAX_CHAINS // 2, HULL_MAX_GROUPS * 4)     # label k and label k + 16 384 share a wave
+HULL_WORDS_PER_TRIP = 1024 * 256  # hull_init_kernel (words of the output) and hull_fill_kernel (used slots)
+RIPLEY_TILE = 2048                # spatial_pairs_kernel: packed points per LDS tile
+RIPLEY_PAIR_GROUPS = 4096         # ... its grid: max(1, 4096 // (1 + S)) workgroups of 4 waves per point set, one i per wave
+RIPLEY_SET_POINTS_PER_TRIP = 4096 * 256    # spatial_sets_kernel: one thread per point of every set
+RIPLEY_TABLE_CHUNK = 256          # spatial_points_kernel: droplets per step of its one workgroup
+BORDER_PIXELS_PER_TRIP = 4096 * 256        # border_init / border_merge / border_flatten, per image
 
 
 def unit_of(y, x, w):

@@ -1,18 +1,26 @@
 """CPU: what the inputs and host-side rules of the workspace-state, grid-cap and C-ABI density tests are for
 (tests/workspace_states.py, tests/droplet_edge_fixtures.py), checked without a device."""
+import pathlib
+import re
+
 import numpy as np
 import pytest
 import torch
 
+from tests import cap_fixtures as cf
 from tests import droplet_edge_fixtures as fx
+from tests import hull_ref, spatial_ref
 from tests import workspace_states as wss
 from tests.image_canaries import CANARY, Canaried
 from tests.match_ref import overlap_table_ref
 from tests.test_density_cpu import cell_image
+from tests.test_hull_cpu import known_shapes
 from tests.test_match_cpu import kmax
 from utils import density as hd
+from utils import droplet_hull as dh
 from utils import droplet_match as dm
 from utils import droplet_shape as sh
+from utils import spatial_stats as ss
 
 
 @pytest.fixture(scope="module")
@@ -185,6 +193,142 @@ def test_bound_case_puts_droplets_on_exact_ring_bounds():
     assert hd.ring_of(bounds, d).tolist() == rings                               # lower ring on a bound, none at d = 0
     assert rings.count(-1) == 1 and np.array_equal(r["ring_counts"], counts) and counts.tolist() == [1, 1, 1, 1, 1, 0, 0, 1, 0, 1]
     assert r["roi"][60, 80] == 1 and r["ring"][60, 80] == 0 and r["ring"][60, 90] == 1 and r["ring"][60, 91] == 2 and r["ring"][0, 0] == 10
+
+
+# ---- the caps of hull.hip, spatial.hip and border.hip, and the fixtures of tests/cap_fixtures.py that pass them ---------------------
+
+CSRC = pathlib.Path(__file__).resolve().parent.parent / "unet_dc_segmentation_amd" / "csrc"
+
+
+def constexpr_int(source, name):
+    """The value of `constexpr int NAME = <integer expression>;` in a source text (digits, shifts, + - * / and brackets only)."""
+    m = re.search(r"constexpr\s+int\s+(?:\w+\s*=\s*[^,;]+,\s*)*" + name + r"\s*=\s*([0-9()<>+\-*/ ]+)[,;]", source)
+    assert m, name
+    return int(eval(m.group(1).replace("/", "//"), {"__builtins__": {}}))
+
+
+def test_cap_mirrors_equal_the_sources():
+    hull, spatial, border = ((CSRC / f).read_text() for f in ("hull.hip", "spatial.hip", "border.hip"))
+    for name in ("HULL_MAX_GROUPS", "HULL_MAX_CHAINS", "HULL_LDS_POINTS"):
+        assert constexpr_int(hull, name) == getattr(fx, name), name
+    assert constexpr_int(spatial, "RIPLEY_TILE") == fx.RIPLEY_TILE == 2048
+    assert (fx.HULL_MAX_GROUPS, fx.HULL_MAX_CHAINS, fx.HULL_LDS_POINTS, fx.HULL_LABELS_PER_TRIP) == (4096, 32768, 2048, 16384)
+    assert (constexpr_int(spatial, "RIPLEY_MAX_R"), constexpr_int(spatial, "RIPLEY_MAX_SIMS")) == (ss.MAX_RADIUS, ss.MAX_SIMS)
+    # the caps that are literals of the launch lines
+    kernels_h = (CSRC / "kernels.h").read_text()
+    assert "inline int grid_for(long work_items, int per_block, long cap = 8192)" in kernels_h and fx.WAVE_UNITS_PER_TRIP == 8192 * 4
+    for line in ("grid_for((long)HULL_QUANTITIES * max_out, 256, 1024)", "grid_for(p.slots, 256, 1024)", "grid_for((long)h * ((w + 63) / 64), 4)",
+                 "grid_for(2L * max_out, 1, HULL_MAX_CHAINS)", "grid_for(max_out, 4, HULL_MAX_GROUPS)"):
+        assert line in hull, line
+    assert fx.HULL_WORDS_PER_TRIP == 256 * 1024
+    for line in ("grid_for(max_points, 4, std::max(1, 4096 / sets))", "grid_for((long)sets * max_points, 256, 4096)",
+                 "for (int base = 0; base < n; base += 256)"):
+        assert line in spatial, line
+    assert (fx.RIPLEY_PAIR_GROUPS, fx.RIPLEY_SET_POINTS_PER_TRIP, fx.RIPLEY_TABLE_CHUNK) == (4096, 256 * 4096, 256)
+    assert "const dim3 flat(grid_for(hw, 256, 4096), n);" in border and fx.BORDER_PIXELS_PER_TRIP == 256 * 4096
+    assert constexpr_int("constexpr int A = 3, B = (1 << 4) / 2 + 1;", "B") == 9                 # the reader itself
+
+
+def test_hull_sparse_fixture_reaches_four_trips():
+    compact, high, numbers = cf.hull_sparse_maps()
+    max_out = cf.HULL_SPARSE_MAX_OUT
+    assert max_out == 65536 and high.shape == (96, 130) and len(numbers) == len(set(numbers.tolist())) == 14
+    cf.assert_hull_sparse_premise(high, max_out)
+    with pytest.raises(AssertionError):                      # at one trip's worth of labels the premise does not hold
+        cf.assert_hull_sparse_premise(np.where(high <= 16384, high, 0), 16384)
+    with pytest.raises(AssertionError):
+        cf.assert_hull_sparse_premise(compact, max_out)
+    # the expected rows: the compact map's by the plain loops, scattered; the host path on the high numbers gives the same
+    ref = hull_ref.label_hull_ref(compact, len(numbers))
+    want = cf.scatter_rows(ref, numbers, max_out)
+    host = dh.label_hull_numpy(high, max_out)
+    assert all(np.array_equal(want[j], host[q]) for j, q in enumerate(dh.QUANTITIES))
+    assert np.count_nonzero(want[4]) == 14 and want[4].max() >= 8
+    assert cf.rows_needed(high, max_out) == sum(rows for _, _, rows, _ in cf.HULL_SPARSE_SPEC)
+
+
+def test_hull_columns_fixture_uses_more_slots_than_one_trip():
+    lab = cf.hull_columns_map()
+    cf.assert_hull_columns_premise(lab)
+    assert cf.slots_used(lab, cf.HULL_COLUMNS) == 268928 and lab.shape == (2100, 130)
+    with pytest.raises(AssertionError):
+        cf.assert_hull_columns_premise(lab[:2000])
+    host = dh.label_hull_numpy(lab, cf.HULL_COLUMNS)
+    assert all(tuple(int(host[q][k]) for q in dh.QUANTITIES) == cf.rect_integers(2100, 1) for k in range(cf.HULL_COLUMNS))
+    assert cf.rect_integers(7, 3) == known_shapes()["rectangle"][2]
+
+
+def test_hull_limit_fixtures_reach_the_last_column_and_row():
+    for name, (lab, hand) in cf.hull_limit_maps().items():
+        h, w = lab.shape
+        host = dh.label_hull_numpy(lab, 2)
+        for k, ints in hand.items():
+            assert tuple(int(host[q][k - 1]) for q in dh.QUANTITIES) == ints, (name, k)
+        pts = hull_ref.hull_corner_points(lab, 1)
+        assert max(p[0] for p in pts) == w if name == "wide" else max(p[1] for p in pts) == h == 16384
+    assert dh.label_hull_numpy(cf.hull_limit_maps()["tall"][0], 2)["nv"].tolist() == [4, 6]
+    lab = cf.hull_tall_parabolas()
+    c, kept = cf.chunk_chain_points(cf.left_candidates(lab, 1), 1)
+    assert (c, kept) == (257, 2160) and kept > fx.HULL_LDS_POINTS and cf.rows_needed(lab, 1) == 16384
+    small = np.zeros((9, 12), np.int32)
+    small[[0, 1, 2, 8], [4, 1, 0, 9]] = 1
+    assert cf.left_candidates(small, 1) == [4, 1, 0, 0, None, None, None, None, 9, 9]
+    assert cf.label_heights(small, 1) == {1: (0, 9)} and cf.slots_used(small, 1) == 10
+
+
+def test_ripley_fixtures_reach_the_tiles_trips_and_chunks():
+    assert cf.RIPLEY_TILE_COUNTS == (2049, 4100)
+    for N in cf.RIPLEY_TILE_COUNTS:
+        for windowed in (False, True):
+            py, px, win = cf.ripley_tile_points(N, windowed)
+            cf.assert_ripley_tiles_premise(N, py, px)
+            assert (win is None) != windowed and (win is None or win[py, px].all())
+    with pytest.raises(AssertionError):                      # one full tile is not enough
+        py, px, _ = cf.ripley_tile_points(2049, False)
+        cf.assert_ripley_tiles_premise(2048, py[:2048], px[:2048])
+    assert cf.assert_second_i_trip(165, 99) == (40, 2) and cf.assert_second_i_trip(70, 999) == (4, 5)
+    for N, S in ((160, 99), (65, 99), (1025, 3)):            # what tests/test_gpu_spatial.py runs: one trip
+        with pytest.raises(AssertionError):
+            cf.assert_second_i_trip(N, S)
+    assert cf.pair_grid(1025, 3) == 257 and cf.pair_grid(65, 99) == 17 and cf.pair_grid(16384, 3) == 1024
+    c = cf.RIPLEY_SETS_CASE
+    cf.assert_ripley_sets_premise(c["S"], c["N"])
+    for S, N in ((999, 1048), (998, 1049)):
+        with pytest.raises(AssertionError):
+            cf.assert_ripley_sets_premise(S, N)
+    for k, cap in ((257, 257), (600, 600), (600, 300), (600, cf.RIPLEY_CAPACITY)):
+        area, sy, sx, window = cf.long_table(k)
+        assert len(area) == k
+        cf.assert_table_chunks_premise(area, sy, sx, 96, 130, window, cap)
+    with pytest.raises(AssertionError):
+        cf.assert_table_chunks_premise(*cf.long_table(257)[:3], 96, 130, cf.long_table(257)[3], 256)
+    for h, w in ((16384, 2), (2, 16384)):
+        py, px = cf.ripley_limit_points(h, w)
+        assert len(set(zip(py, px))) == len(py) == 10 and max(py) == h - 1 and max(px) == w - 1
+
+
+def test_ripley_plain_loops_on_the_small_cap_fixtures():
+    """The host path that the device is compared with, against the plain loops of tests/spatial_ref.py, where those are quick."""
+    h, w = 96, 130
+    win = cf.ripley_holes_window(h, w)
+    py, px = ss.simulated_points(50 + 165, 0, 165, h, w, win)
+    got = ss.ripley_counts_numpy(py, px, h, w, 16, 2, 4321, win)
+    want = spatial_ref.ripley_counts(list(zip(py.tolist(), px.tolist())), h, w, 16, 2, 4321, win)
+    assert all(np.array_equal(g, np.array(v)) for g, v in zip(got, want))
+    area, sy, sx, window = cf.long_table(600)
+    pts, dropped = spatial_ref.points_of_table(area.tolist(), sy.tolist(), sx.tolist(), h, w, window)[:2]
+    qy, qx, info = ss.droplet_points(area, sy, sx, h, w, window)
+    assert [tuple(p) for p in pts] == list(zip(qy.tolist(), qx.tolist())) and info["n_dropped"] == 600 - len(pts)
+
+
+def test_border_fixture_crosses_the_second_trip():
+    masks = cf.border_masks()
+    assert masks.shape == (2, 1100, 960) and cf.assert_border_premise(masks) == 1056000 > fx.BORDER_PIXELS_PER_TRIP
+    assert divmod(fx.BORDER_PIXELS_PER_TRIP, 960) == (1092, 256)
+    with pytest.raises(AssertionError):                      # an image of at most 1 048 576 pixels has no second trip
+        cf.assert_border_premise(cf.border_masks((1092, 960)))
+    with pytest.raises(AssertionError):
+        cf.assert_border_premise(np.stack([masks[0], masks[0]]))
 
 
 def test_workspace_queries_cover_the_planes_the_launchers_lay_out(lib):

@@ -42,6 +42,57 @@
                                         1040 x 1388 test of tests/test_gpu_split.py, test_gpu_clean.py, test_gpu_shape.py and
                                         test_gpu_density.py.
 
+  hull.hip.  Label k and label k + 16 384 share one wave of the chain and of the caliper kernel, and with it s_count, s_pts, s_lvl.
+    hull_init_kernel                    1024 x 256 = 262 144 words over 5 max_out: max_out > 52 428.  max_out = 65 536 (what
+                                        mask_and_droplets passes): test_hull_sparse_high_label_numbers, where 65 522 numbers without
+                                        pixels keep the zeros, before and after a 0xFF prefill.
+    hull_extent_kernel, hull_rows_kernel   8192 x 4 waves = 32 768 units, the frame of label_props_kernel: 41 000 and 33 600 units in
+                                        test_label_hull_past_the_grid_cap.
+    hull_scan_kernel                    one workgroup, tiles of 4096 labels: 16 tiles at max_out = 65 536 (the sparse test), 2 at the
+                                        6240 labels of tests/test_gpu_hull.py.
+    hull_fill_kernel                    1024 x 256 = 262 144 used slots (a label of height H takes H + 1): 128 x 2101 = 268 928 in
+                                        test_hull_more_slots_than_one_trip_of_the_fill, in all four workspace states, with exact
+                                        row room and with h * w; the four labels past the boundary are mostly empty levels.
+    hull_chain_kernel                   HULL_MAX_CHAINS = 32 768 one-wave workgroups over 2 max_out: max_out > 16 384.  Four trips
+                                        in test_hull_sparse_high_label_numbers, on one wave in consecutive trips: LDS path then
+                                        register path, the reverse, LDS then a shorter LDS label, pixels then none, none then pixels.
+                                        Its memory paths: 2101 levels (the fill test), 16 385 levels (test_hull_coordinate_limits
+                                        [tall]); both passes in memory at 16 385 levels: test_hull_memory_passes_at_the_largest_height.
+    hull_caliper_kernel                 HULL_MAX_GROUPS = 4096 x 4 waves = 16 384 labels: the same four trips.
+    hull_pack (y << 15 | x)             x = 16384 and y = 16384: test_hull_coordinate_limits, also against hand-derived rectangles.
+  spatial.hip.
+    spatial_points_kernel               one workgroup, 256 droplets a step, `kept` carried: tables of 257 and 600, cut at 300, and
+                                        with a capacity of 16 384: test_droplet_tables_longer_than_one_chunk.
+    spatial_window_count_kernel         sized for 16 steps a thread, 1024 x 256 pixels a step: every window of more than 4096 pixels
+                                        takes several steps (tests/test_gpu_spatial.py); past 4 194 304 pixels only their number
+                                        grows.  Deliberately not reached.
+    spatial_window_rows_kernel          4096 x 4 waves = 16 384 rows a trip, and h <= 16 384: no second trip exists.  h = 16 384:
+                                        test_ripley_coordinate_limits (also the 64 rows a thread of spatial_window_scan_kernel).
+    spatial_sets_kernel                 4096 x 256 = 1 048 576 points of all sets: (1 + 999) x 1049 = 1 049 000 in
+                                        test_ripley_sets_kernel_second_trip; the last simulation holds the boundary.
+    spatial_eligible_kernel             one workgroup per set, 256 points a step: N = 1025 (tests/test_gpu_spatial.py), 4100 here.
+    spatial_pairs_kernel                tiles of RIPLEY_TILE = 2048 points: N = 2049 and 4100 (second and third tile, the last of
+                                        four points, coincident points across tiles) in test_ripley_second_and_third_lds_tile.  Grid
+                                        max(1, 4096 // (1 + S)) workgroups of 4 i: ceil(N / 4) > 4096 // (1 + S) at N = 165, S = 99
+                                        (2 trips) and N = 70, S = 999 (5 trips): test_ripley_later_trips_of_the_i_loop.  The set
+                                        stride is max_points, not N: max_points = 16 384 over N = 0, 65, 300 in
+                                        test_ripley_capacity_far_above_the_point_count and
+                                        test_ripley_points_from_a_table_shorter_than_its_capacity.  Scan chunks of 64 bins:
+                                        R = 63, 65, 127, 128, 255 in test_ripley_radii_around_the_scan_chunks.  Sides of 16 384:
+                                        test_ripley_coordinate_limits.
+  border.hip.
+    border_init_kernel, border_merge_kernel, border_flatten_kernel   4096 x 256 = 1 048 576 pixels per image: n = 2 at 1100 x 960
+                                        (1 056 000), a component across pixel 1 048 576 in both:
+                                        test_border_planes_on_the_second_trip_of_two_images, and the weights bit for bit in
+                                        test_border_weights_on_the_second_trip_of_two_images.
+    border_col_kernel, border_row_kernel   one workgroup per tile, no loop over the grid.
+
+The fixtures of the hull, Ripley and border tests are in tests/cap_fixtures.py, each with a premise that fails when it stops
+reaching its loop; tests/test_droplet_edges_cpu.py runs the premises, and checks the mirrored caps against the sources, without a
+device.  Timed once (host reference and device together, on the GPU machine): the sparse hull 0.24 s, the fill test 0.2 s per
+state, the hull at the cap shapes 0.14 s, Ripley at N = 4100 0.24 s, S = 999 0.07 s, the two border tests 1.5 s together (most of it
+border_weights_numpy, about 5 s on a slow host); everything else below 0.1 s.
+
 The label maps (tests/droplet_edge_fixtures.py:cap_labels) are the components of a blob mask: a few hundred droplets that
 cross the 64-pixel seams, some of them the row where the second trip starts, and one in the last rows and columns.  Host
 references at these shapes, timed on the CPU: label_props_numpy 0.25 s, overlap_table_numpy 0.03 s (0.2 s on
@@ -50,16 +101,26 @@ unique_pair_labels), the plain loops of tests/match_ref.py 0.5 s, offset_pairs a
 import numpy as np
 import pytest
 
+from tests import cap_fixtures as cf
 from tests import droplet_edge_fixtures as fx
-from tests import neighbors_ref
+from tests import hull_ref, neighbors_ref
+from tests import spatial_ref
 from tests.match_ref import overlap_table_ref
+from tests.test_gpu_border import SIGMA, W0
+from tests.test_gpu_border import run as border_run
+from tests.test_gpu_hull import device_hull
 from tests.test_gpu_match import assert_arrays_equal_host_path, device_overlap, host_table
 from tests.test_gpu_neighbors import device_neighbors_arrays
 from tests.test_gpu_shape import NQ, assert_props_equal
+from tests.test_gpu_spatial import assert_counts_equal_host, device_counts, device_points
 from tests.test_match_cpu import kmax
 from tests.test_shape_cpu import gray_plane
+from tests.workspace_states import STATES, holds
+from utils import droplet_hull as dh
 from utils import droplet_neighbors as dn
 from utils import droplet_shape as sh
+from utils import spatial_stats as ss
+from utils.border_weights import border_weights_numpy
 
 pytestmark = pytest.mark.gpu
 
@@ -145,3 +206,251 @@ def test_neighbors_past_the_label_and_pair_grids():
         assert np.array_equal(gcols[q], cols[q]), (q, np.flatnonzero(gcols[q] != cols[q])[:5])
     assert (gcols["cluster"] == 1).all() and (gcols["cluster_size"] == k).all() and (gcols["nn_d2"] == 4).all()
     assert gcols["degree"].min() == 2 and gcols["degree"].max() == 4 and (gcols["nn_label"] >= 1).all()
+
+
+# ---- hull.hip ----------------------------------------------------------------------------------------------------------------------
+
+def assert_hull_rows(rows, want):
+    """rows, want: int64 [5, max_out]."""
+    for j, q in enumerate(dh.QUANTITIES):
+        assert np.array_equal(rows[j], want[j]), (q, np.flatnonzero(rows[j] != want[j])[:5].tolist())
+
+
+def host_rows(lab, max_out):
+    ref = dh.label_hull_numpy(lab, max_out)
+    return np.stack([ref[q] for q in dh.QUANTITIES])
+
+
+def test_hull_sparse_high_label_numbers():
+    """max_out = 65 536 on a 96 x 130 map whose fourteen labels carry numbers in all four trips of hull_chain_kernel and
+    hull_caliper_kernel.  The hull depends on the pixel set alone: the expected rows are those of the same map numbered 1..14 (plain
+    loops), at the high numbers; every other number keeps the zeros of hull_init_kernel, whose 327 680 words take a second trip."""
+    compact, high, numbers = cf.hull_sparse_maps()
+    max_out = cf.HULL_SPARSE_MAX_OUT
+    cf.assert_hull_sparse_premise(high, max_out)
+    want = cf.scatter_rows(hull_ref.label_hull_ref(compact, len(numbers)), numbers, max_out)
+    assert (want[4, numbers - 1] >= 4).all() and np.count_nonzero(want[4]) == len(numbers)
+    need = cf.rows_needed(high, max_out)
+    rows, n_rows, _ = device_hull(high, max_out, max_rows=need)
+    assert n_rows == need
+    assert_hull_rows(rows, want)
+    again, n_rows, _ = device_hull(high, max_out, max_rows=need, prefill=0xFF, state="ones")
+    assert n_rows == need and again.tobytes() == rows.tobytes()
+
+
+_columns = {}
+
+
+def columns_rows():
+    if not _columns:
+        _columns["rows"] = host_rows(cf.hull_columns_map(), cf.HULL_COLUMNS)
+        _columns["rows"].setflags(write=False)
+    return _columns["rows"]
+
+
+@pytest.mark.parametrize("state", STATES)
+def test_hull_more_slots_than_one_trip_of_the_fill(state):
+    """128 labels of 2101 corner levels: 268 928 used slots, so hull_fill_kernel comes round again; the last four labels lie
+    beyond slot 262 144 and are mostly levels without a pixel, which the chains skip only where the fill reached them."""
+    lab = cf.hull_columns_map()
+    cf.assert_hull_columns_premise(lab)
+    h, w = lab.shape
+    want = columns_rows()
+    assert all(tuple(want[:, k]) == cf.rect_integers(h, 1) for k in range(cf.HULL_COLUMNS))       # every hull is the 2100 x 1 rectangle
+    stale = None
+    if state == "stale":                                     # what the stage left at another geometry and capacity
+        _, high, _ = cf.hull_sparse_maps()
+        stale = device_hull(high, cf.HULL_SPARSE_MAX_OUT, max_rows=cf.rows_needed(high, cf.HULL_SPARSE_MAX_OUT))[2].u8.clone()
+    exact = cf.HULL_COLUMNS * h
+    for max_rows in (exact, h * w):
+        rows, n_rows, ws = device_hull(lab, cf.HULL_COLUMNS, max_rows=max_rows, state=state, stale=stale)
+        assert n_rows == exact and not holds(ws, state, stale)
+        assert_hull_rows(rows, want)
+
+
+@pytest.mark.parametrize("shape", fx.CAP_SHAPES, ids=IDS)
+def test_label_hull_past_the_grid_cap(shape):
+    """hull_extent_kernel and hull_rows_kernel share the frame of label_props_kernel: 8192 x 4 units a trip."""
+    lab = fx.cap_labels(shape)[0]
+    assert_reaches_the_second_trip(lab)
+    k = kmax(lab)
+    need = cf.rows_needed(lab, k)
+    rows, n_rows, _ = device_hull(lab, k, max_rows=need, state="ones")
+    assert n_rows == need
+    assert_hull_rows(rows, host_rows(lab, k))
+
+
+@pytest.mark.parametrize("name", ["wide", "tall"])
+def test_hull_coordinate_limits(name):
+    """A vertex at x = 16384 and one at y = 16384: the largest values hull_pack holds, and the largest products of the calipers."""
+    lab, hand = cf.hull_limit_maps()[name]
+    h, w = lab.shape
+    assert max(h, w) == 16384 and (lab[:, w - 1] > 0).any() and (lab[h - 1] > 0).any()
+    if name == "tall":
+        assert (lab[:, 0] == 1).all() and h + 1 > fx.HULL_LDS_POINTS        # 16 385 levels: the first chain pass in memory
+    need = cf.rows_needed(lab, 2)
+    rows, n_rows, _ = device_hull(lab, 2, max_rows=need, state="ones")
+    assert n_rows == need
+    assert_hull_rows(rows, host_rows(lab, 2))
+    for k, ints in hand.items():
+        assert tuple(int(v) for v in rows[:, k - 1]) == ints, k
+
+
+def test_hull_memory_passes_at_the_largest_height():
+    """16 385 levels with 2160 chunk vertices on the left side: both chain passes run in memory, up to y = 16384."""
+    lab = cf.hull_tall_parabolas()
+    c, kept = cf.chunk_chain_points(cf.left_candidates(lab, 1), 1)
+    assert lab.shape[0] == 16384 and c == 257 and kept > fx.HULL_LDS_POINTS
+    rows, n_rows, _ = device_hull(lab, 1, max_rows=16384, state="ones")
+    assert n_rows == 16384
+    assert_hull_rows(rows, host_rows(lab, 1))
+
+
+# ---- spatial.hip -----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("windowed", [False, True], ids=["null", "holes"])
+@pytest.mark.parametrize("N", cf.RIPLEY_TILE_COUNTS)
+def test_ripley_second_and_third_lds_tile(N, windowed):
+    py, px, win = cf.ripley_tile_points(N, windowed)
+    cf.assert_ripley_tiles_premise(N, py, px)
+    n, pairs, pairs_all = assert_counts_equal_host(py, px, *cf.RIPLEY_SHAPE, 64, 1, 17, win)
+    assert pairs_all[0][0] >= 2 * len(cf.coincident_pairs(N)) and pairs_all[0][64] > N       # c = 0 pairs: only t0 + j != i tells i from j
+
+
+@pytest.mark.parametrize("N,S,trips", [(165, 99, 2), (70, 999, 5)])
+def test_ripley_later_trips_of_the_i_loop(N, S, trips):
+    """165 points at the flow's S = 99: 40 workgroups, and a second trip in which workgroup 1 has one active wave.  70 points at
+    S = 999, the most the ABI takes: 4 workgroups, five trips, the last of 6 i."""
+    groups, got = cf.assert_second_i_trip(N, S)
+    assert (groups, got) == ({99: 40, 999: 4}[S], trips) and N % 4 != 0
+    h, w = 96, 130
+    win = cf.ripley_holes_window(h, w)
+    py, px = ss.simulated_points(50 + N, 0, N, h, w, win)
+    n, pairs, pairs_all = assert_counts_equal_host(py, px, h, w, 16, S, 4321, win)
+    assert len({tuple(r) for r in pairs_all[1:].tolist()}) > S // 2
+
+
+@pytest.mark.parametrize("N", [0, 65, 300])
+def test_ripley_capacity_far_above_the_point_count(N):
+    """max_points = 16 384 as in the flow: the set stride is the capacity, not N, and most workgroups start past N."""
+    h, w = 96, 130
+    cap = cf.RIPLEY_CAPACITY
+    assert cap >= 16384 > 4 * N and cf.pair_grid(cap, 3) * 4 > N
+    for win in (None, cf.ripley_holes_window(h, w)):
+        py, px = ss.simulated_points(60 + N, 0, N, h, w, win)
+        want = ss.ripley_counts_numpy(py, px, h, w, 16, 3, 9, win)
+        got = device_counts(py, px, h, w, 16, 3, 9, win, max_points=cap)[:3]
+        for name, g, v in zip(("n", "pairs", "pairs_all"), got, want):
+            assert np.array_equal(g, v), (name, np.argwhere(g != v)[:5].tolist())
+        assert N == 0 or (want[2][1:, 16] > 0).all()
+
+
+def test_ripley_points_from_a_table_shorter_than_its_capacity():
+    h, w, cap = 96, 130, cf.RIPLEY_CAPACITY
+    area, sy, sx, window = spatial_ref.random_case(h, w, 70, "holes", seed=5)
+    want_py, want_px, info = ss.droplet_points(area, sy, sx, h, w, window)
+    py, px, got = device_points(area, sy, sx, h, w, window, max_points=cap)
+    assert np.array_equal(py, want_py) and np.array_equal(px, want_px)
+    assert got.tolist() == [info["N"], info["n_dropped"], info["A"], 0] and 0 < info["n_dropped"] < 70
+    want = ss.ripley_counts_numpy(py, px, h, w, 16, 3, 9, window)
+    got = device_counts(py, px, h, w, 16, 3, 9, window, max_points=cap)[:3]
+    assert all(np.array_equal(g, v) for g, v in zip(got, want))
+
+
+@pytest.mark.parametrize("k,cap", [(257, 257), (600, 600), (600, 300), (600, cf.RIPLEY_CAPACITY)])
+def test_droplet_tables_longer_than_one_chunk(k, cap):
+    """spatial_points_kernel walks the table 256 droplets at a time and carries the number kept so far; max_points = 300 cuts the
+    table inside its second chunk (the canaries past entry 300 are checked in device_points)."""
+    h, w = 96, 130
+    area, sy, sx, window = cf.long_table(k)
+    cf.assert_table_chunks_premise(area, sy, sx, h, w, window, cap)
+    n = min(k, cap)
+    want_py, want_px, info = ss.droplet_points(area[:n], sy[:n], sx[:n], h, w, window)
+    py, px, got = device_points(area, sy, sx, h, w, window, max_points=cap)
+    assert np.array_equal(py, want_py) and np.array_equal(px, want_px)                   # table order
+    assert got.tolist() == [info["N"], info["n_dropped"], info["A"], int(k > cap)]
+    assert info["N"] + info["n_dropped"] == n and info["n_dropped"] > 0
+
+
+@pytest.mark.parametrize("R", [63, 65, 127, 128, 255])
+def test_ripley_radii_around_the_scan_chunks(R):
+    """The scan of a wave's bins runs in chunks of 64 and stops at the first chunk that starts past R."""
+    h, w = cf.RIPLEY_SHAPE
+    assert (R + 1) % 64 in (0, 1, 2) and R not in (64, 256)
+    win = cf.ripley_holes_window(h, w)
+    py, px = ss.simulated_points(70 + R, 0, 65, h, w, win)
+    n, pairs, pairs_all = assert_counts_equal_host(py, px, h, w, R, 1, 5, win)
+    assert pairs_all[:, R].sum() > pairs_all[:, R - 1].sum() > pairs_all[:, R // 2].sum() > 0         # the last bin is in use
+
+
+def test_ripley_sets_kernel_second_trip():
+    """S = 999 and N = 1049: 1 049 000 points for spatial_sets_kernel against 1 048 576 a trip; the points across that index are
+    those of the last simulation from its point 625 on.  The full host reference takes a quarter of a minute, so the observed
+    pattern, the first two and the last three simulations are compared, each a host call of its own on simulated_points."""
+    c = cf.RIPLEY_SETS_CASE
+    S, N, R, h, w, seed = (c[q] for q in ("S", "N", "R", "h", "w", "seed"))
+    cf.assert_ripley_sets_premise(S, N)
+    py, px = ss.simulated_points(77, 0, N, h, w)
+    n, pairs, pairs_all, _ = device_counts(py, px, h, w, R, S, seed)
+    for s in (-1,) + cf.RIPLEY_SETS_CHECKED:
+        qy, qx = (py, px) if s < 0 else ss.simulated_points(seed, s, N, h, w)
+        want = ss.ripley_counts_numpy(qy, qx, h, w, R, 0, seed)
+        for name, g, v in zip(("n", "pairs", "pairs_all"), (n, pairs, pairs_all), want):
+            assert np.array_equal(g[s + 1], v[0]), (s, name, g[s + 1].tolist(), v[0].tolist())
+    assert (n[:, 0] == N).all() and (pairs_all[:, R] > 0).all() and (pairs_all[:, R] >= pairs[:, R]).all()
+
+
+@pytest.mark.parametrize("hw", [(16384, 2), (2, 16384)], ids=lambda v: "{}x{}".format(*v))
+def test_ripley_coordinate_limits(hw):
+    """The largest sides: packed coordinates of 16 383, squared differences of 16 383^2, m * m at the frame."""
+    h, w = hw
+    py, px = cf.ripley_limit_points(h, w)
+    assert max(py) == h - 1 and max(px) == w - 1 and min(py) == min(px) == 0 and max(h, w) == 16384
+    for win in (None, np.ones((h, w), np.uint8)):
+        n, pairs, pairs_all = assert_counts_equal_host(py, px, h, w, 16, 3, 11, win)
+        assert pairs_all[0][16] >= 8 and pairs_all[0][0] == 0
+
+
+# ---- border.hip ------------------------------------------------------------------------------------------------------------------
+
+_border = {}
+
+
+def border_reference():
+    if not _border:
+        out = border_weights_numpy(cf.border_masks(), W0, SIGMA, cf.BORDER_RADIUS, planes=True)
+        for v in out:
+            v.setflags(write=False)
+        _border["ref"] = out
+    return _border["ref"]
+
+
+def border_device():
+    if not _border.get("dev"):
+        _border["dev"] = border_run(cf.border_masks().copy(), cf.BORDER_RADIUS, state="ones")[:3]
+    return _border["dev"]
+
+
+def test_border_planes_on_the_second_trip_of_two_images():
+    """n = 2 at 1100 x 960: border_init / merge / flatten come round again from pixel 1 048 576 (row 1092, column 256), where
+    each mask holds a component on both sides; the second image tells a trip that forgot its image's base."""
+    masks = cf.border_masks()
+    assert cf.assert_border_premise(masks) == 1056000
+    _, n1, n2 = border_reference()
+    _, d1, d2 = border_device()                              # outputs and workspace between canaries (border_run)
+    for i in range(2):
+        assert np.array_equal(d1[i], n1[i]), (i, np.argwhere(d1[i] != n1[i])[:5].tolist())
+        assert np.array_equal(d2[i], n2[i]), (i, np.argwhere(d2[i] != n2[i])[:5].tolist())
+    y, x = divmod(fx.BORDER_PIXELS_PER_TRIP, masks.shape[2])
+    assert (n2[:, y - 8:y + 9, x - 16:x + 17] <= cf.BORDER_RADIUS ** 2).any(axis=(1, 2)).all()   # border terms around the boundary
+
+
+def test_border_weights_on_the_second_trip_of_two_images():
+    masks = cf.border_masks()
+    cf.assert_border_premise(masks)
+    nw, _, _ = border_reference()
+    wt, _, _ = border_device()
+    diff = wt.view(np.uint32) != nw.view(np.uint32)
+    print(f"\n border weights, 2 x 1100 x 960 at R {cf.BORDER_RADIUS}: {int(diff.sum())} of {int((nw > 1).sum())} weights above 1 differ from "
+          f"the host path; largest gap {float(np.abs(wt.astype(np.float64) - nw).max()):.3e}")
+    assert not diff.any(), np.argwhere(diff)[:5].tolist()

@@ -2,9 +2,12 @@
 against the host path of the same definition (utils/spatial_stats.py, itself pinned to the plain loops of tests/spatial_ref.py
 on the CPU); then spatial.spatial_stats_batch and the CLI flag.  Integer work: bit-exact.
 
-The shapes are the smallest at which a kernel can go wrong: N around one wave (63, 64, 65) and past one LDS tile and one wave's
-worth of i (1 025 > 4 x 256), R at both ends and across the 64-bin chunks of the scan (64, 256), widths across a 64-pixel block
-(130, 401), every kind of window."""
+The shapes are the smallest at which a kernel can go wrong: N around one wave (63, 64, 65) and 1 025 = 4 x 256 + 1 (a fifth pass, of
+one point, of the 256 threads that stage the tile; still inside ONE LDS tile of RIPLEY_TILE = 2048 points and one trip of the i loop),
+R at both ends and across the 64-bin chunks of the scan (64, 256), widths across a 64-pixel block (130, 401), every kind of
+window.  The second and third LDS tile, the later trips of the i loop, a capacity above the point count, tables longer than one
+chunk of 256, the other chunk edges of R, the second trip of spatial_sets_kernel and the largest sides are in
+tests/test_gpu_grid_caps.py."""
 import ctypes
 
 import numpy as np

@@ -129,7 +129,7 @@ __device__ __forceinline__ void border_insert(int d, int l, int& d1, int& l1, in
 __global__ __launch_bounds__(256) void border_row_kernel(const int* __restrict__ ca, const int* __restrict__ cb,
                                                          const unsigned short* __restrict__ cd, float* __restrict__ out_w,
                                                          int* __restrict__ out_d1, int* __restrict__ out_d2, int h, int w, int R,
-                                                         float w0, float inv_two_sigma_sq) {
+                                                         double w0, double two_sigma_sq) {
   __shared__ int sa[BORDER_RH][BORDER_RW + 2 * BORDER_MAX_RADIUS], sb[BORDER_RH][BORDER_RW + 2 * BORDER_MAX_RADIUS];
   __shared__ unsigned short sd[BORDER_RH][BORDER_RW + 2 * BORDER_MAX_RADIUS];
   const int tx = threadIdx.x & (BORDER_RW - 1), ty = threadIdx.x >> 7;
@@ -172,8 +172,10 @@ __global__ __launch_bounds__(256) void border_row_kernel(const int* __restrict__
   }
   float wv = 1.f;
   if (D1 > 0 && D2 <= R * R) {
-    const float s = sqrtf((float)D1) + sqrtf((float)D2);
-    wv = 1.f + w0 * expf(-(s * s) * inv_two_sigma_sq);
+    // the arithmetic of the definition (utils/border_weights.py:weights_from_planes): fp64, every operation rounded on its own
+    // (no contraction into an FMA), the weight rounded to fp32 once
+    const double s = __dadd_rn(sqrt((double)D1), sqrt((double)D2));
+    wv = (float)__dadd_rn(1.0, __dmul_rn(w0, exp(-__dmul_rn(s, s) / two_sigma_sq)));
   }
   out_w[base + x] = wv;
   if (out_d1) out_d1[base + x] = D1;
@@ -220,8 +222,8 @@ int launch_border_weights(const float* target, int n, int h, int w, float w0, fl
   hipLaunchKernelGGL(border_col_kernel, dim3((w + BORDER_CT - 1) / BORDER_CT, (h + BORDER_CH - 1) / BORDER_CH, n), dim3(256),
                      (size_t)(BORDER_CH + 2 * radius) * BORDER_CT * 4, stream, L, ca, cb, cd, h, w, radius);
   hipLaunchKernelGGL(border_row_kernel, dim3((w + BORDER_RW - 1) / BORDER_RW, (h + BORDER_RH - 1) / BORDER_RH, n), dim3(256), 0,
-                     stream, ca, cb, cd, out_weight, out_d1, out_d2, h, w, radius, w0,
-                     (float)(1.0 / (2.0 * (double)sigma * (double)sigma)));
+                     stream, ca, cb, cd, out_weight, out_d1, out_d2, h, w, radius, (double)w0,
+                     2.0 * ((double)sigma * (double)sigma));
   return check_launch("border kernels");
 }
 
