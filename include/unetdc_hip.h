@@ -650,6 +650,45 @@ int unetdc_label_hull(const int32_t* label, int max_out, int h, int w, void* wor
                       int32_t* out_rows, int max_rows, unetdc_stream_t s);
 
 
+/* ---- ordered outlines per droplet: crack-following contours (outlines.hip; the definition is DESIGN.md section 27) -----------
+ * unetdc_label_outlines: label ([h][w] int32: 0 = background, droplets 1..max_out; any label map: labels may touch and need not
+ *   be connected; values below 1 or above max_out are skipped, and are "not k" to every droplet like the background).  Pixel
+ *   (r, c) is the square [c, c + 1] x [r, r + 1]; corners are (x, y), x in 0..w, y in 0..h.  A crack of label k is a unit edge
+ *   between a pixel of k and one that is not k (or the outside), directed with the k-pixel on its right on the screen (top: E,
+ *   right: S, bottom: W, left: N); its id is (y_tail * (w + 1) + x_tail) * 4 + d, d = 0 E, 1 S, 2 W, 3 N.  Its successor, at
+ *   its head facing d: ahead-right not k: turn right; else ahead-left not k: straight; else turn left.  The cracks of a label
+ *   fall into cycles, its contours; a contour starts at its crack of smallest id, its vertices are the heads of the cracks whose
+ *   successor has another direction, listed from the start's tail in walking order (nv >= 4, no three on a line), its length is
+ *   its number of cracks and S2 = sum (x_tail * y_head - x_head * y_tail) is > 0 for an outer contour (clockwise on the screen),
+ *   < 0 for a hole.  Contours are listed in ascending start id.
+ *   -> out[UNETDC_OUTLINE_QUANTITIES][max_out] int64, row j of droplet k at out[j * max_out + k - 1]:
+ *     0 E    number of cracks              3 nv   vertices over all its contours
+ *     1 no   outer contours                4 F2   sum of S2 over the outer contours (twice the filled area)
+ *     2 nh   hole contours                 5 S2   sum of S2 over all contours (twice the pixel count)
+ *   A number without pixels keeps 0 in all six rows.
+ *   -> contours[UNETDC_CONTOUR_FIELDS][max_contours] int64, field f of contour i at contours[f * max_contours + i]: label,
+ *     first (index of its first vertex in vx / vy), nv, length, S2;  vx, vy[max_vertices] int32.
+ *   -> needed[4] int32: the cracks, contours and vertices of the image, and too_long.
+ *   Rooms: if needed[0] > max_cracks nothing else is computed: out is zero, needed[1..3] are 0 and only needed[0] means anything
+ *   (it is cut at 2^31 - 1).  Otherwise out is always complete; contours and vertices are written where they fit their rooms
+ *   (contour i if i < max_contours, a vertex if its index < max_vertices), and needed[1], needed[2] say how many there are.
+ *   max_len bounds the length of a contour: the list ranking runs ceil(log2(max_len)) rounds.  If a contour is longer,
+ *   needed[3] = 1, needed[1] = needed[2] = 0, out is zero and no contour or vertex is written: repeat with a larger max_len
+ *   (max_len = needed[0] always suffices).  A 4-connected label of A pixels has at most 2 A + 2 cracks.
+ *   max_out = 0 and rooms of 0 are allowed (out, contours, vx / vy may then be NULL).  Nothing but the outputs and the
+ *   workspace is written, and the workspace may hold anything on entry.  Sides 1..16384, h * w < 2^30; max_out, max_len,
+ *   max_contours, max_vertices >= 0; max_cracks 0..2^30; workspace: unetdc_label_outlines_workspace(h, w, max_out, max_cracks)
+ *   bytes (0 for arguments the call would refuse), 8-byte aligned.  UNETDC_EINVAL before any launch for a null pointer, a
+ *   refused geometry or a negative limit, UNETDC_EWORKSPACE for a workspace too small.  Launches on the given stream only; no
+ *   host wait, no allocation.  Integer atomic adds and fixed-order scans: bitwise reproducible. */
+#define UNETDC_OUTLINE_QUANTITIES 6
+#define UNETDC_CONTOUR_FIELDS 5      /* label, first vertex, nv, length, S2 */
+int64_t unetdc_label_outlines_workspace(int h, int w, int max_out, int max_cracks);
+int unetdc_label_outlines(const int32_t* label, int max_out, int h, int w, int max_len, void* workspace, int64_t workspace_bytes,
+                          int64_t* out, int64_t* contours, int max_contours, int32_t* vx, int32_t* vy, int max_vertices,
+                          int max_cracks, int32_t* needed, unetdc_stream_t s);
+
+
 /* ---- overlap table of two label maps (match.hip; the definition is DESIGN.md section 12) ------------------------------------
  * unetdc_label_overlap: label_a, label_b ([h][w] int32 each: 0 = background, objects 1..max_a and 1..max_b; any label maps,
  *   touching labels allowed) -> the triples (a, b, n) with n > 0 = the number of pixels that carry label a on the first map

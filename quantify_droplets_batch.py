@@ -23,6 +23,7 @@ and a few integers per droplet come back:
     --confidence      (droplets.py, tta.py)                     csrc/confidence.hip tta.hip  CPU: utils/droplet_confidence.py
     --droplet_hull    (droplets.py)                             csrc/hull.hip           CPU: utils/droplet_hull.py
     --diff_maps       unet_dc_segmentation_amd/evaluate.py      csrc/diffmap.hip        CPU: utils/difference_map.py
+    --outlines        unet_dc_segmentation_amd/outlines.py      csrc/outlines.hip       CPU: utils/droplet_outlines.py
     --spatial_stats   unet_dc_segmentation_amd/spatial.py       csrc/spatial.hip        CPU: utils/spatial_stats.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
@@ -109,6 +110,7 @@ class Run:
     hull: float | None = None          # --droplet_hull: the solidity below which a droplet is flagged, None without the flag
     diff: dict | None = None           # diff_options(); its "tables" / "rows" collect diff_regions.csv and diff_regions_per_image.csv
     spatial: dict | None = None        # spatial_options(); its "table" / "rows" collect spatial_stats.csv and spatial_per_image.csv
+    outlines: dict | None = None       # --outlines: {"dir", "images", "jobs"}: outlines/NAME.geojson and what outlines_coco.json collects
 
     @property
     def keep_rgb(self):
@@ -357,6 +359,42 @@ def add_hull_outputs(run, df, d):
     return df, dh.hull_summary(cols)
 
 
+def outline_records(run, out, on_device):
+    """--outlines for one batch: the record of DESIGN.md section 27 per image from the label map of the droplet stage (the split
+    one with --split_touching).  On the device the batch is enqueued back to back behind the droplets with one more wait
+    (outlines.label_outlines_batch); the rooms come from the areas the table already holds.  Split droplets are basins of the
+    watershed and need not be 4-connected: their rooms are the ones of any label."""
+    if on_device:
+        from unet_dc_segmentation_amd.outlines import label_outlines_batch
+        return label_outlines_batch([d.labels for d in out], [d.area for d in out], connected=run.split_depth is None)
+    from utils import droplet_outlines as do
+    return [do.outlines_numpy(d.labels, len(d.area)) for d in out]
+
+
+def _write_outlines(rec, path, name, image_id, px_per_um):
+    """Writer pool: outlines/NAME.geojson, and the image's COCO annotations for main() to number and write."""
+    import json
+    from utils import droplet_outlines as do
+    with open(path, "w") as f:                           # dumps, not dump: one pass of the C encoder instead of Python chunks
+        groups = do.rings(rec)
+        f.write(json.dumps(do.geojson(rec, name, px_per_um, groups), separators=(",", ":")))
+    return do.coco_annotation(rec, image_id=image_id, groups=groups)
+
+
+def add_outline_outputs(run, df, d, rec, filename, name, hw):
+    """--outlines: the columns of utils.droplet_outlines.outline_columns behind the droplet table's own, the image's GeoJSON file
+    and COCO annotations (writer pool) -> (the table, the numbers its row of summary_per_image.csv gains)."""
+    from utils import droplet_outlines as do
+    cols = do.outline_columns(rec, d.area, run.px_per_um)
+    if not df.empty:
+        df = pd.concat([df, pd.DataFrame(cols, index=df.index)], axis=1)
+    o = run.outlines
+    o["images"].append({"id": len(o["images"]) + 1, "file_name": filename, "height": int(hw[0]), "width": int(hw[1])})
+    run.submit(_write_outlines, rec, o["dir"] / f"{name}.geojson", name, len(o["images"]), run.px_per_um)
+    o["jobs"].append(run.writers[1][-1])
+    return df, do.outline_summary(cols)
+
+
 def add_spatial_outputs(run, batch, out, sums, on_device):
     """--spatial_stats for one batch: the counts of DESIGN.md section 26 from the droplet table alone (on the device from the
     sums the droplet stage left there, one more batch of launches and one more wait; on the CPU from the label map's sums),
@@ -485,11 +523,12 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
     matching is read: no shape columns, no grey planes, no boundary distances.  With --boundary every match result carries the
     record of DESIGN.md section 21 under "boundary" (device: one more batch of launches and one more wait, evaluate.boundary_batch).
     With --droplet_hull (never while sweeping) every Droplets carries the integers of DESIGN.md section 24.
+    With --outlines (never while sweeping) every Droplets carries its label map, which finish_batch hands to the outline stage.
     With --confidence (never while sweeping) every Droplets carries the record of DESIGN.md section 23; envelope: the (lo, hi) maps
     of --tta, shaped like probs."""
     gt, hws = run.gt, [m[1] for m in batch.meta]
     radius = run.boundary["R"] if run.boundary is not None and not sweeping else None
-    want_labels = gt is not None or run.split_depth is not None
+    want_labels = gt is not None or run.split_depth is not None or (run.outlines is not None and not sweeping)
     shape = run.shape and not sweeping
     conf = run.confidence if not sweeping else None
     hull = run.hull is not None and not sweeping
@@ -586,6 +625,7 @@ def finish_batch(run, batch, probs):
         add_diff_outputs(run, batch, out)
     if run.spatial is not None:
         add_spatial_outputs(run, batch, out, sums, probs.is_cuda)
+    orecs = outline_records(run, out, probs.is_cuda) if run.outlines is not None else None
     for i, (d, (fpath, hw)) in enumerate(zip(out, batch.meta)):
         filename, name = Path(fpath).name, Path(fpath).stem
         mask = _host(d.mask)
@@ -603,6 +643,9 @@ def finish_batch(run, batch, probs):
         if run.hull is not None:
             df, hull_more = add_hull_outputs(run, df, d)
             more = {**more, **hull_more}
+        if orecs is not None:
+            df, outline_more = add_outline_outputs(run, df, d, orecs[i], filename, name, hw)
+            more = {**more, **outline_more}
         if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
             run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
@@ -742,6 +785,12 @@ def build_parser():
                         "regions = region-level TP / FN / FP / TN, their pixels, the regions kept, missed_droplets, "
                         "spurious_droplets).  The prediction is the mask the droplet stage measured (after --prob_thresh_low / "
                         "--fill_holes), the annotation is grey > 0, with --gt_labels label > 0; --gt_min_area does not apply here")
+    p.add_argument("--outlines", action="store_true",
+                   help="per-droplet outlines as polygons (crack-following contours of the label map, holes as inner rings): adds "
+                        "perimeter_crack (boundary length in pixel edges, a city-block length), n_holes, euler_number, area_filled, "
+                        "hole_area and outline_vertices to the droplet tables, n_with_holes and hole_area_total to "
+                        "summary_per_image.csv, and writes outlines/NAME.geojson per image and one outlines_coco.json (outer rings "
+                        "only) for annotation tools; with --split_touching the outlines follow the cuts")
     p.add_argument("--spatial_stats", type=_spatial_radius_arg, nargs="?", const=64, metavar="R",
                    help="Ripley's K(r), L(r) - r and g(r) of the droplet centroids for r = 1..R pixels (default 64, at most 256), "
                         "border-corrected, with the envelope of --spatial_sims patterns of complete spatial randomness in the "
@@ -931,6 +980,10 @@ def main(argv=None):
                 "tables": [], "rows": []}
         diff["map_dir"].mkdir(exist_ok=True)
         diff["overlay_dir"].mkdir(exist_ok=True)
+    outlines = None
+    if args.outlines:
+        outlines = {"dir": out_dir / "outlines", "images": [], "jobs": []}
+        outlines["dir"].mkdir(exist_ok=True)
     model = load_model(args.ckpt_path, args.dtype)
     # File decode runs ahead of the device and the per-image writes behind it, in two small thread pools (both are
     # zlib-bound and release the GIL); the order of the rows in the summary files is the order of `images` as before.
@@ -944,7 +997,7 @@ def main(argv=None):
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
                   neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff,
-                  spatial=spatial)
+                  spatial=spatial, outlines=outlines)
         ahead = deque()
         it = iter(images)
 
@@ -1014,6 +1067,14 @@ def main(argv=None):
         from utils import spatial_stats as ss
         pd.DataFrame(spatial["table"], columns=ss.table_columns(run.px_per_um)).to_csv(out_dir / "spatial_stats.csv", index=False)
         pd.DataFrame(spatial["rows"], columns=ss.IMAGE_COLUMNS).to_csv(out_dir / "spatial_per_image.csv", index=False)
+    if outlines is not None:                             # one COCO file for the run: annotation ids count through the images
+        import json
+        anns = [a for job in outlines["jobs"] for a in job.result()]
+        for i, a in enumerate(anns, start=1):
+            a["id"] = i
+        with open(out_dir / "outlines_coco.json", "w") as f:
+            f.write(json.dumps({"images": outlines["images"], "annotations": anns, "categories": [{"id": 1, "name": "droplet"}]},
+                               separators=(",", ":")))
     if clean is not None:
         pd.DataFrame(clean["rows"]).to_csv(out_dir / "mask_clean_per_image.csv", index=False)
     if run.neighbors is not None and run.contact_tables:

@@ -6,6 +6,7 @@ mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG fil
                                   [--tile[=T]] [--tile_overlap=O] [--batch=B] [--tta[=N]] [--neighbors[=G]]
                                   [--boundary[=R]] [--boundary_tol=T,T...] [--confidence[=BAND]] [--confidence_maps]
                                   [--droplet_hull[=S]] [--diff_maps[=MIN_AREA]] [--spatial_stats[=R]] [--spatial_sims=S]
+                                  [--outlines]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
 --split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
 --droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns).
@@ -30,7 +31,9 @@ integers on the device, the extra CSV columns).
 --diff_maps or --diff_maps=MIN_AREA: passed through to the script, implies --gt (the difference-map arm: 8-connected regions of the
 class plane and both pictures on the device, two more PNGs per image, diff_regions.csv and diff_regions_per_image.csv).
 --spatial_stats or --spatial_stats=R, --spatial_sims=S, --spatial_seed=N: passed through to the script (the spatial-statistics arm:
-Ripley counts of the droplet centroids and of the simulated patterns on the device, spatial_stats.csv and spatial_per_image.csv)."""
+Ripley counts of the droplet centroids and of the simulated patterns on the device, spatial_stats.csv and spatial_per_image.csv).
+--outlines: passed through to the script (the outline arm: crack-following contours of the label map on the device, the extra CSV
+columns, one GeoJSON file per image and outlines_coco.json)."""
 import os
 import sys
 import tempfile
@@ -66,6 +69,7 @@ hl_argv = [a for a in sys.argv[1:] if a.split("=")[0] == "--droplet_hull"]
 df_argv = [a for a in sys.argv[1:] if a.split("=")[0] == "--diff_maps"]
 gt = gt or bool(df_argv)
 sp_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--spatial_stats", "--spatial_sims", "--spatial_seed")]
+ol_argv = [a for a in sys.argv[1:] if a == "--outlines"]
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 64
 dtype = pos[1] if len(pos) > 1 else "bf16"
@@ -98,9 +102,9 @@ with tempfile.TemporaryDirectory() as d:
     argv += ["--split_touching"] if split else []
     argv += ["--droplet_shape"] if shape else []
     argv += ["--gt_dir", gtd, "--gt_min_area", "4"] if gt else []
-    argv += clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv
+    argv += clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv + ol_argv
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''})")

@@ -106,6 +106,8 @@ SIGNATURES = {
     "unetdc_label_confidence": (I, [P, I, I, I, P, P, P, I, I, F, F, P, P, P, P, P, P]),
     "unetdc_label_hull_workspace": (L, [I, I, I, I]),
     "unetdc_label_hull": (I, [P, I, I, I, P, L, P, P, I, P]),
+    "unetdc_label_outlines_workspace": (L, [I, I, I, I]),
+    "unetdc_label_outlines": (I, [P, I, I, I, I, P, L, P, P, I, P, P, I, I, P, P]),
     "unetdc_label_overlap_workspace": (L, [I, I, I]),
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
     "unetdc_boundary_distances_workspace": (L, [I, I]),

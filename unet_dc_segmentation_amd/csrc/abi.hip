@@ -639,6 +639,17 @@ int unetdc_label_hull(const int32_t* label, int max_out, int h, int w, void* wor
                            max_rows, (hipStream_t)s);
 }
 
+static_assert(UNETDC_OUTLINE_QUANTITIES == OUTLINE_QUANTITIES && UNETDC_CONTOUR_FIELDS == CONTOUR_FIELDS, "unetdc_label_outlines output rows");
+
+int64_t unetdc_label_outlines_workspace(int h, int w, int max_out, int max_cracks) { return label_outlines_workspace_bytes(h, w, max_out, max_cracks); }
+
+int unetdc_label_outlines(const int32_t* label, int max_out, int h, int w, int max_len, void* workspace, int64_t workspace_bytes, int64_t* out,
+                          int64_t* contours, int max_contours, int32_t* vx, int32_t* vy, int max_vertices, int max_cracks, int32_t* needed,
+                          unetdc_stream_t s) {
+  return launch_label_outlines(label, max_out, h, w, max_len, workspace, (long)workspace_bytes, reinterpret_cast<long long*>(out),
+                               reinterpret_cast<long long*>(contours), max_contours, vx, vy, max_vertices, max_cracks, needed, (hipStream_t)s);
+}
+
 int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) { return label_overlap_workspace_bytes(h, w, max_pairs); }
 
 int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,

@@ -318,6 +318,15 @@ long label_hull_workspace_bytes(int h, int w, int max_out, int max_rows);       
 int launch_label_hull(const int* label, int max_out, int h, int w, void* workspace, long workspace_bytes, long long* out,
                       int* out_rows, int max_rows, hipStream_t stream);
 
+// outlines.hip: the ordered contours (crack following as list ranking) of every label of an int32 label map, six integers per
+// label, the contour table and the vertex lists
+constexpr int OUTLINE_QUANTITIES = 6;
+constexpr int CONTOUR_FIELDS = 5;
+long label_outlines_workspace_bytes(int h, int w, int max_out, int max_cracks);        // 0 for arguments the call refuses
+int launch_label_outlines(const int* label, int max_out, int h, int w, int max_len, void* workspace, long workspace_bytes, long long* out,
+                          long long* contours, int max_contours, int* vx, int* vy, int max_vertices, int max_cracks, int* needed,
+                          hipStream_t stream);
+
 // neighbors.hip: contact pairs, nearest contact, degree and cluster of the labels of an int32 label map
 long label_neighbors_workspace_bytes(int h, int w, int max_label, int max_pairs);       // 0 for arguments the call refuses
 int launch_label_neighbors(const int* label, int max_label, int h, int w, int radius, void* workspace, long workspace_bytes,
