@@ -1,4 +1,4 @@
-"""Inputs of the hull, Ripley and border tests of tests/test_gpu_grid_caps.py, each with the premise that says what it is for: an
+"""Inputs of the hull, Ripley, border and outline tests of tests/test_gpu_grid_caps.py, each with the premise that says what it is for: an
 assert that fails when the fixture stops reaching the loop, the tile or the limit it was built to reach.  Host code only;
 tests/test_droplet_edges_cpu.py runs every premise without a device."""
 import functools
@@ -344,3 +344,169 @@ def assert_border_premise(masks):
         part = np.flatnonzero(flat == flat[P])
         assert part[0] < P - w and part[-1] >= P + w         # ... of a component with rows above and below
     return h * w
+
+
+# ---- outlines ------------------------------------------------------------------------------------------------------------------
+
+def outline_rounds(max_len):
+    """The leader and the rank rounds of launch_label_outlines: the smallest r, at most 31, with 2^r >= max_len."""
+    r = 0
+    while r < 31 and (1 << r) < max_len:
+        r += 1
+    return r
+
+
+def crack_census(lab, n=None):
+    """(ids, label) of every crack in ascending id, as the first lines of utils.droplet_outlines.outlines_numpy find them: the
+    position of a crack in this list is the index ol_base_kernel gives it, and ids >> 2 is the corner it leaves."""
+    lab = np.asarray(lab)
+    h, w = lab.shape
+    n = int(lab.max(initial=0)) if n is None else int(n)
+    pad = np.zeros((h + 2, w + 2), np.int32)
+    pad[1:-1, 1:-1] = np.where((lab >= 1) & (lab <= n), lab, 0)
+    nw, ne, sw, se = pad[:-1, :-1], pad[:-1, 1:], pad[1:, :-1], pad[1:, 1:]
+    own, left = np.stack((se, sw, nw, ne), axis=-1).ravel(), np.stack((ne, se, sw, nw), axis=-1).ravel()
+    ids = np.flatnonzero((own > 0) & (own != left))
+    return ids, own[ids]
+
+
+def tiles(n, per=fx.OUTLINE_TILE):
+    return -(-int(n) // per)
+
+
+@functools.lru_cache(maxsize=None)
+def outline_long_serpentine(shape=(1100, 960)):
+    """One label, the rule of tests/test_gpu_outlines.py:serpentine: every other row full, joined alternately at the right and the
+    left end.  One contour of 2 A + 2 cracks."""
+    h, w = shape
+    lab = np.zeros((h, w), np.int32)
+    lab[0::2] = 1
+    lab[1::4, w - 1] = 1
+    lab[3::4, 0] = 1
+    lab.setflags(write=False)
+    return lab
+
+
+@functools.lru_cache(maxsize=None)
+def outline_checkerboard(side=728):
+    """Every other pixel a contour of its own (4 cracks, 4 vertices), in bands of 100 rows labelled 1, 2, 3, 1, ..."""
+    r, c = np.mgrid[:side, :side]
+    lab = (((r + c) % 2 == 0) * (1 + (r // 100) % 3)).astype(np.int32)
+    lab.setflags(write=False)
+    return lab
+
+
+OUTLINE_BAR = (2 * 16384 + 2, 1, 0, 4, 2 * 16384, 2 * 16384)       # (E, no, nh, nv, F2, S2) of a 16384 x 1 bar
+
+
+@functools.lru_cache(maxsize=None)
+def outline_limit_maps():
+    """{name: (label map, {label: hand-derived (E, no, nh, nv, F2, S2)})}, sides of 16384.
+    tall   16384 x 2: label 1 column 0 over the full height (a vertex at y = 16384), label 2 in column 1 at the far end.
+    wide   2 x 16384: label 1 row 0 over the full width (a vertex at x = 16384), label 2 in row 1 at the far end.
+    Beside the bar one line of pixels is left, where neither a one-pixel hole nor a notch fits: label 2 is two pixels, a gap, and
+    the last pixel: two contours that touch the bar and the last corner (16384, 2) or (2, 16384).  The bar: 2 A + 2 cracks, one
+    outer contour, four vertices, twice its area."""
+    tall = np.zeros((16384, 2), np.int32)
+    tall[:, 0] = 1
+    tall[[16380, 16381, 16383], 1] = 2
+    wide = np.ascontiguousarray(tall.T)
+    for v in (tall, wide):
+        v.setflags(write=False)
+    two = (6 + 4, 2, 0, 8, 4 + 2, 4 + 2)                     # a 2 x 1 piece and a pixel
+    return {"tall": (tall, {1: OUTLINE_BAR, 2: two}), "wide": (wide, {1: OUTLINE_BAR, 2: two})}
+
+
+OUTLINE_BLOB_SHAPE, OUTLINE_BLOB_SEED = (1040, 1388), 3
+
+
+@functools.lru_cache(maxsize=None)
+def outline_blob_labels():
+    """A label map of the flow's full image size: the components of a blob mask, numbered as cap_labels numbers its own."""
+    lab = fx.components(fx.blob_mask(*OUTLINE_BLOB_SHAPE, seed=OUTLINE_BLOB_SEED))
+    lab.setflags(write=False)
+    return lab
+
+
+OUTLINE_MAPS = {"serpentine": outline_long_serpentine, "checkerboard": outline_checkerboard,
+                "tall": lambda: outline_limit_maps()["tall"][0], "wide": lambda: outline_limit_maps()["wide"][0],
+                "blobs": outline_blob_labels, **{f"{h}x{w}": (lambda s=(h, w): fx.cap_labels(s)[0]) for h, w in fx.CAP_SHAPES}}
+
+
+@functools.lru_cache(maxsize=None)
+def outline_ref(name):
+    """(label map, the follower's record for its labels 1..max) of OUTLINE_MAPS[name]: computed once, shared, read-only."""
+    from utils.droplet_outlines import outlines_numpy
+    lab = OUTLINE_MAPS[name]()
+    ref = outlines_numpy(lab, int(lab.max()))
+    for v in (*ref["rows"].values(), *ref["contours"].values(), ref["x"], ref["y"]):
+        v.setflags(write=False)
+    return lab, ref
+
+
+def outline_counts(lab, ref):
+    """(corners, cracks, contours, vertices, longest contour) of a map and its follower's record."""
+    h, w = lab.shape
+    c = ref["contours"]
+    return (h + 1) * (w + 1), int(c["length"].sum()), len(c["label"]), len(ref["x"]), int(c["length"].max(initial=0))
+
+
+def assert_outline_serpentine_premise(lab, ref):
+    """One contour longer than one trip of the crack-side loops, so that pointer jumping crosses the trip boundary; more corner
+    tiles than one trip of the crack scan; a round count the small fixtures do not reach."""
+    corners, cracks, contours, vertices, longest = outline_counts(lab, ref)
+    A = int(lab.sum())
+    assert set(np.unique(lab).tolist()) == {0, 1} and contours == 1 and longest == cracks == 2 * A + 2
+    assert cracks == len(crack_census(lab)[0]) > fx.OUTLINE_CRACKS_PER_TRIP
+    assert tiles(corners) > fx.OUTLINE_SCAN_TILES_PER_TRIP and corners <= fx.OUTLINE_CORNERS_PER_TRIP
+    assert outline_rounds(longest) > 15 and outline_rounds(fx.OUTLINE_CRACKS_PER_TRIP) == outline_rounds(longest) - 1
+    return corners, tiles(corners), cracks, contours, vertices, outline_rounds(longest)
+
+
+def assert_outline_checkerboard_premise(lab, ref):
+    """More cracks, contours and crack tiles than one trip holds while the corners stay within one trip of every corner-side
+    loop; contours that start on the second trip; more than one label on the first, and a band that holds the boundary."""
+    corners, cracks, contours, vertices, longest = outline_counts(lab, ref)
+    P = fx.OUTLINE_CRACKS_PER_TRIP
+    assert tiles(corners) <= fx.OUTLINE_SCAN_TILES_PER_TRIP and corners <= fx.OUTLINE_CORNERS_PER_TRIP
+    assert cracks > P and tiles(cracks) > fx.OUTLINE_SCAN_TILES_PER_TRIP and vertices > P and contours > P // 4
+    ids, own = crack_census(lab)
+    assert len(ids) == cracks
+    h, w = lab.shape
+    c = ref["contours"]
+    start = (ref["y"][c["first"]].astype(np.int64) * (w + 1) + ref["x"][c["first"]]) * 4         # the E crack of the start's tail
+    index = np.searchsorted(ids, start)
+    assert np.array_equal(ids[index], start) and (np.diff(index) > 0).all()
+    late = index >= P
+    assert late.any() and not late.all() and index[late].min() - P < 4                           # a contour across the boundary, or next to it
+    assert len(np.unique(own[:P])) > 1                       # a label band changes before the boundary ...
+    assert own[P - 1] == own[P] and (own[:P] == own[P]).sum() > w                                # ... and the one across it began well before
+    return corners, cracks, contours, vertices, tiles(cracks), int(late.sum())
+
+
+def assert_outline_corner_grid_premise(lab, ref):
+    """More corners than one trip of ol_successor_kernel, three trips of the crack scan, and a label with cracks that leave
+    corners on both sides of corner 2 097 152: from the crack census, not from the pixels.  -> (corners, corner tiles, labels,
+    cracks, contours, holes, labels with a crack past the boundary, those of them with a crack before it)."""
+    corners, cracks, contours, vertices, longest = outline_counts(lab, ref)
+    P = fx.OUTLINE_CORNERS_PER_TRIP
+    assert corners > P and tiles(corners) > 2 * fx.OUTLINE_SCAN_TILES_PER_TRIP
+    ids, own = crack_census(lab)
+    assert len(ids) == cracks <= fx.OUTLINE_CRACKS_PER_TRIP
+    past = np.unique(own[(ids >> 2) >= P])
+    both = np.intersect1d(past, np.unique(own[(ids >> 2) < P]))
+    assert len(both) >= 1
+    return corners, tiles(corners), int(lab.max()), cracks, contours, int((ref["contours"]["S2"] < 0).sum()), len(past), len(both)
+
+
+def assert_outline_limit_premise(name, lab, ref, hand):
+    """A side of 16384 with a vertex on its last lattice line, and label 2 at the far corner."""
+    h, w = lab.shape
+    assert (h, w) == ((16384, 2) if name == "tall" else (2, 16384)) and int(lab.max()) == 2
+    far = ref["y"] if name == "tall" else ref["x"]
+    c = ref["contours"]
+    owner = np.repeat(c["label"], c["nv"])
+    assert far[owner == 1].max() == 16384 and far[owner == 2].max() == 16384 and far[owner == 1].min() == 0
+    assert (ref["x"].max(), ref["y"].max()) == (w, h)
+    for k, ints in hand.items():
+        assert tuple(int(ref["rows"][q][k - 1]) for q in ("E", "no", "nh", "nv", "F2", "S2")) == ints, (name, k)

@@ -22,6 +22,12 @@ RIPLEY_PAIR_GROUPS = 4096         # ... its grid: max(1, 4096 // (1 + S)) workgr
 RIPLEY_SET_POINTS_PER_TRIP = 4096 * 256    # spatial_sets_kernel: one thread per point of every set
 RIPLEY_TABLE_CHUNK = 256          # spatial_points_kernel: droplets per step of its one workgroup
 BORDER_PIXELS_PER_TRIP = 4096 * 256        # border_init / border_merge / border_flatten, per image
+# ... and of outlines.hip
+OUTLINE_TILE = 1024               # OL_THREADS * OL_ITEMS: corners of a census tile, cracks of a contour tile
+OUTLINE_SCAN_TILES_PER_TRIP = 1024         # ol_scan_plane: one workgroup of 1024, one tile count per thread and trip
+OUTLINE_CRACKS_PER_TRIP = 4096 * 256       # ol_leader / ol_cut / ol_rank / ol_vertices: OL_MAX_GRID blocks of 256 threads
+OUTLINE_CORNERS_PER_TRIP = 8192 * 256      # ol_successor_kernel
+OUTLINE_INIT_WORDS_PER_TRIP = 1024 * 256   # ol_init_kernel: words of the 6 output rows
 
 
 def unit_of(y, x, w):
@@ -54,6 +60,11 @@ def blob_mask(h, w, seed, sigma=12.0, frac=0.2):
     return m
 
 
+def components(mask):
+    """The 4-connected components of a mask as an int32 label map, numbered in raster order."""
+    return ndimage.label(mask, ndimage.generate_binary_structure(2, 1))[0].astype(np.int32)
+
+
 @functools.lru_cache(maxsize=None)
 def cap_labels(shape):
     """-> (A, B): the 4-connected components of a blob mask of `shape` and of the same mask moved down 2 and right 1, both
@@ -63,8 +74,7 @@ def cap_labels(shape):
     moved = np.zeros_like(m)
     moved[2:, 1:] = m[:h - 2, :w - 1]
     moved[h - 3:, w - 3:] = 1
-    s = ndimage.generate_binary_structure(2, 1)
-    return ndimage.label(m, s)[0].astype(np.int32), ndimage.label(moved, s)[0].astype(np.int32)
+    return components(m), components(moved)
 
 
 PAIR_SORT_CHUNK = 4096            # pair_table.h: the entries one workgroup sorts in LDS; a longer list takes the global passes

@@ -19,6 +19,7 @@ from tests.test_match_cpu import kmax
 from utils import density as hd
 from utils import droplet_hull as dh
 from utils import droplet_match as dm
+from utils import droplet_outlines as do
 from utils import droplet_shape as sh
 from utils import spatial_stats as ss
 
@@ -226,6 +227,19 @@ def test_cap_mirrors_equal_the_sources():
         assert line in spatial, line
     assert (fx.RIPLEY_PAIR_GROUPS, fx.RIPLEY_SET_POINTS_PER_TRIP, fx.RIPLEY_TABLE_CHUNK) == (4096, 256 * 4096, 256)
     assert "const dim3 flat(grid_for(hw, 256, 4096), n);" in border and fx.BORDER_PIXELS_PER_TRIP == 256 * 4096
+    outlines = (CSRC / "outlines.hip").read_text()
+    assert constexpr_int(outlines, "OL_THREADS") * constexpr_int(outlines, "OL_ITEMS") == fx.OUTLINE_TILE == 1024
+    assert "OL_TILE = OL_THREADS * OL_ITEMS;" in outlines and constexpr_int(outlines, "OL_THREADS") == 256
+    assert constexpr_int(outlines, "OL_MAX_GRID") * 256 == fx.OUTLINE_CRACKS_PER_TRIP == 1 << 20
+    for line in ("const int crack_grid = grid_for(max_cracks, OL_THREADS, OL_MAX_GRID);", "grid_for(p.corners, OL_THREADS, 8192)",
+                 "grid_for((long)OUTLINE_QUANTITIES * max_out, 256, 1024)), dim3(256)", "for (int base = 0; base < n; base += 1024)",
+                 "hipLaunchKernelGGL(ol_scan_cracks_kernel, dim3(1), dim3(1024)", "hipLaunchKernelGGL(ol_scan_contours_kernel, dim3(1), dim3(1024)",
+                 "const dim3 block(OL_THREADS);"):
+        assert line in outlines, line
+    for kernel in ("ol_leader_kernel", "ol_cut_kernel", "ol_rank_kernel"):                      # the loops of one trip of 4096 x 256
+        assert f"hipLaunchKernelGGL({kernel}, dim3(crack_grid), block" in outlines, kernel
+    assert "hipLaunchKernelGGL(ol_vertices_kernel, dim3(crack_grid), block" in outlines
+    assert (fx.OUTLINE_SCAN_TILES_PER_TRIP, fx.OUTLINE_CORNERS_PER_TRIP, fx.OUTLINE_INIT_WORDS_PER_TRIP) == (1024, 8192 * 256, 1024 * 256)
     assert constexpr_int("constexpr int A = 3, B = (1 << 4) / 2 + 1;", "B") == 9                 # the reader itself
 
 
@@ -329,6 +343,69 @@ def test_border_fixture_crosses_the_second_trip():
         cf.assert_border_premise(cf.border_masks((1092, 960)))
     with pytest.raises(AssertionError):
         cf.assert_border_premise(np.stack([masks[0], masks[0]]))
+
+
+# ---- outlines.hip ----------------------------------------------------------------------------------------------------------------
+
+def test_outline_serpentine_is_one_contour_longer_than_a_trip():
+    lab, ref = cf.outline_ref("serpentine")
+    assert lab.shape == (1100, 960)
+    assert cf.assert_outline_serpentine_premise(lab, ref) == (1058061, 1034, 1057102, 1, 2202, 21)
+    from tests.test_gpu_outlines import serpentine
+    assert np.array_equal(cf.outline_long_serpentine((96, 130)), serpentine())                # the same rule
+    small = cf.outline_long_serpentine((96, 130))            # what tests/test_gpu_outlines.py reaches: one trip, 14 rounds
+    rec = do.outlines_numpy(small, 1)
+    assert cf.outline_counts(small, rec) == (12707, 12578, 1, 194, 12578) and cf.outline_rounds(12578) == 14
+    with pytest.raises(AssertionError):
+        cf.assert_outline_serpentine_premise(small, rec)
+    assert [cf.outline_rounds(v) for v in (0, 1, 2, 3, 1 << 20, (1 << 20) + 1, 1 << 30, (1 << 30) + 1, 2 ** 31 - 1)] == [0, 0, 1, 2, 20, 21, 30, 31, 31]
+
+
+def test_outline_checkerboard_has_more_contours_than_a_trip():
+    lab, ref = cf.outline_ref("checkerboard")
+    assert lab.shape == (728, 728)
+    assert cf.assert_outline_checkerboard_premise(lab, ref)[:5] == (531441, 1059968, 264992, 1059968, 1036)
+    assert (ref["contours"]["length"] == 4).all() and sorted(np.unique(lab).tolist()) == [0, 1, 2, 3]
+    small = cf.outline_checkerboard(96)
+    with pytest.raises(AssertionError):
+        cf.assert_outline_checkerboard_premise(small, do.outlines_numpy(small, 3))
+
+
+@pytest.mark.parametrize("shape,counts", zip(fx.CAP_SHAPES, ((2115858, 2067, 338, 59248, 344, 6, 4, 1), (2116722, 2068, 315, 58496, 316, 1, 34, 31))),
+                         ids=[f"{s[0]}x{s[1]}" for s in fx.CAP_SHAPES])
+def test_cap_label_maps_pass_the_corner_grid_of_the_outlines(shape, counts):
+    lab, ref = cf.outline_ref("{}x{}".format(*shape))
+    assert lab is fx.cap_labels(shape)[0]
+    assert cf.assert_outline_corner_grid_premise(lab, ref) == counts
+    h = fx.OUTLINE_CORNERS_PER_TRIP // (shape[1] + 1)        # cut where the second trip would start: no corner past it
+    cut = lab[:h - 1]
+    with pytest.raises(AssertionError):
+        cf.assert_outline_corner_grid_premise(cut, do.outlines_numpy(cut, int(lab.max())))
+
+
+def test_outline_limit_fixtures_reach_the_last_lattice_lines():
+    maps = cf.outline_limit_maps()
+    assert sorted(maps) == ["tall", "wide"]
+    for name, (lab, hand) in maps.items():
+        cf.assert_outline_limit_premise(name, lab, cf.outline_ref(name)[1], hand)
+        assert hand[1] == (32770, 1, 0, 4, 32768, 32768)
+    with pytest.raises(AssertionError):
+        lab = maps["tall"][0][:16383]
+        cf.assert_outline_limit_premise("tall", lab, do.outlines_numpy(lab, 2), maps["tall"][1])
+
+
+def test_outline_blob_map_asks_for_more_room_than_a_trip():
+    from unet_dc_segmentation_amd.outlines import rooms_for
+    lab = cf.outline_blob_labels()
+    area = np.bincount(lab.ravel())[1:]
+    rooms = rooms_for(area, connected=False)
+    assert lab.shape == (1040, 1388) and rooms["max_cracks"] == rooms["max_len"] == 4 * int((lab > 0).sum()) == 1154852
+    assert rooms["max_cracks"] > fx.OUTLINE_CRACKS_PER_TRIP and cf.outline_rounds(rooms["max_len"]) == 21
+    assert cf.tiles(1041 * 1389) > fx.OUTLINE_SCAN_TILES_PER_TRIP                              # the crack scan's second trip
+    for shape, cracks in zip(fx.CAP_SHAPES, (1685856, 1690116)):                                # what the flow asks for on the cap maps
+        a = np.bincount(fx.cap_labels(shape)[0].ravel())[1:]
+        assert rooms_for(a, connected=False)["max_cracks"] == cracks and cf.tiles(cracks) > fx.OUTLINE_SCAN_TILES_PER_TRIP
+    assert fx.OUTLINE_INIT_WORDS_PER_TRIP < 6 * 65536 and 6 * 43690 <= fx.OUTLINE_INIT_WORDS_PER_TRIP < 6 * 43691
 
 
 def test_workspace_queries_cover_the_planes_the_launchers_lay_out(lib):

@@ -86,12 +86,52 @@
                                         test_border_planes_on_the_second_trip_of_two_images, and the weights bit for bit in
                                         test_border_weights_on_the_second_trip_of_two_images.
     border_col_kernel, border_row_kernel   one workgroup per tile, no loop over the grid.
+  outlines.hip.  tests/test_gpu_outlines.py stops at 12 707 corners (13 tiles), 12 578 cracks (13 tiles) and 14 rounds.
+    ol_init_kernel                      1024 x 256 = 262 144 words over 6 max_out: max_out > 43 690.  max_out = 65 536 (what the
+                                        flow passes) over a canary-filled output: test_outlines_past_the_corner_grid.
+    ol_census_kernel, ol_base_kernel    one workgroup per tile of 1024 corners, no loop over the grid: a second trip does not
+                                        exist.  Tiles past 1024 and 2048 read tile_base entries of a later scan trip: the same tests
+                                        as the crack scan.
+    ol_scan_cracks_kernel (ol_scan_plane over the corner tiles)   1024 tiles = 1 048 576 corners a trip, `run` carried.  1034 tiles
+                                        with ONE contour through all of them (1100 x 960):
+                                        test_outlines_one_contour_longer_than_a_trip; 2067 and 2068 tiles, three trips:
+                                        test_outlines_past_the_corner_grid; 1413 tiles at 1040 x 1388:
+                                        test_label_outlines_batch_at_full_size.
+    ol_successor_kernel                 8192 x 256 = 2 097 152 corners: 2 115 858 and 2 116 722 at 8200 x 257 and 600 x 3521, a
+                                        label with cracks on both sides of that corner: test_outlines_past_the_corner_grid.
+    ol_leader_kernel, ol_cut_kernel, ol_rank_kernel, ol_vertices_kernel   OL_MAX_GRID = 4096 x 256 = 1 048 576 cracks.  One contour
+                                        of 1 057 102 cracks, so every jump of the later rounds crosses the trip boundary, 21 rounds;
+                                        max_len = 2^20 (20 rounds) leaves the cycle longer than the windows, and the disagreement
+                                        is the cut kernel's to find, with cracks on its second trip; max_len = length - 1 is the
+                                        OL_LEN path at 21 rounds: test_outlines_one_contour_longer_than_a_trip.  264 992 contours
+                                        of 4 cracks, 2665 of them on the second trip: test_outlines_more_contours_than_a_trip.
+                                        Round counts 5 .. 30 on one small map, both parities of lead / rank / fin, jumps that
+                                        wrap every cycle many times: test_outlines_every_round_count.
+    ol_contour_count_kernel, ol_contours_kernel   one workgroup per tile of 1024 cracks of ROOM, no loop over the grid.  Their tile
+                                        counts are what the contour scans read: below.
+    ol_scan_contours_kernel (ol_scan_plane over the crack tiles, twice) and tile_at[0 / 1] read back   1024 tiles = 1 048 576
+                                        cracks of room.  1036 tiles, all in use, rooms cut inside the second trip (262 147
+                                        contours, 1 048 578 vertices: mid-contour): test_outlines_more_contours_than_a_trip.
+                                        1647 and 1651 tiles of room over 58 tiles of cracks (rooms_for(area, connected=False), as
+                                        the flow asks): the second trip sums tiles past n, which ol_contour_count_kernel must have
+                                        written as zero over a workspace of ones and a stale one:
+                                        test_outlines_rooms_far_above_the_counts, and behind label_outlines_batch at 1040 x 1388
+                                        (1128 tiles) with the shared workspace stale from the larger image before:
+                                        test_label_outlines_batch_at_full_size.
+    corner / (w + 1), the shoelace terms   sides of 16 384, a vertex at x = 16384 and one at y = 16384, also against hand-derived
+                                        integers: test_outline_coordinate_limits.
+    Deliberately not reached: corners near 2^29 (the most `where` packs beside its 3 low bits) need a label map of two gigabytes;
+    a prefix past 2^31 in ol_scan_plane needs as many cracks.
 
-The fixtures of the hull, Ripley and border tests are in tests/cap_fixtures.py, each with a premise that fails when it stops
+The fixtures of the hull, Ripley, border and outline tests are in tests/cap_fixtures.py, each with a premise that fails when it stops
 reaching its loop; tests/test_droplet_edges_cpu.py runs the premises, and checks the mirrored caps against the sources, without a
 device.  Timed once (host reference and device together, on the GPU machine): the sparse hull 0.24 s, the fill test 0.2 s per
 state, the hull at the cap shapes 0.14 s, Ripley at N = 4100 0.24 s, S = 999 0.07 s, the two border tests 1.5 s together (most of it
-border_weights_numpy, about 5 s on a slow host); everything else below 0.1 s.
+border_weights_numpy, about 5 s on a slow host); everything else below 0.1 s.  The outline tests: one contour longer than a
+trip 1.9 s (six runs on canaried buffers of 60 MB, and the followers of the serpentine and of the checkerboard, 0.4 s and
+0.75 s, which every later test shares), past the corner grid 0.26 s and 0.22 s (their followers 0.2 s each), the batch at full
+size 0.16 s, more contours than a trip 0.08 s, rooms far above the counts 0.05 s, every round count (28 runs) and the
+coordinate limits 0.02 s each.
 
 The label maps (tests/droplet_edge_fixtures.py:cap_labels) are the components of a blob mask: a few hundred droplets that
 cross the 64-pixel seams, some of them the row where the second trip starts, and one in the last rows and columns.  Host
@@ -111,6 +151,9 @@ from tests.test_gpu_border import run as border_run
 from tests.test_gpu_hull import device_hull
 from tests.test_gpu_match import assert_arrays_equal_host_path, device_overlap, host_table
 from tests.test_gpu_neighbors import device_neighbors_arrays
+from tests.test_gpu_outlines import FIXTURES as OUTLINE_FIXTURES
+from tests.test_gpu_outlines import assert_equal as assert_outlines_equal
+from tests.test_gpu_outlines import device_outlines, exact_rooms, ref_of
 from tests.test_gpu_shape import NQ, assert_props_equal
 from tests.test_gpu_spatial import assert_counts_equal_host, device_counts, device_points
 from tests.test_match_cpu import kmax
@@ -118,6 +161,7 @@ from tests.test_shape_cpu import gray_plane
 from tests.workspace_states import STATES, holds
 from utils import droplet_hull as dh
 from utils import droplet_neighbors as dn
+from utils import droplet_outlines as do
 from utils import droplet_shape as sh
 from utils import spatial_stats as ss
 from utils.border_weights import border_weights_numpy
@@ -454,3 +498,188 @@ def test_border_weights_on_the_second_trip_of_two_images():
     print(f"\n border weights, 2 x 1100 x 960 at R {cf.BORDER_RADIUS}: {int(diff.sum())} of {int((nw > 1).sum())} weights above 1 differ from "
           f"the host path; largest gap {float(np.abs(wt.astype(np.float64) - nw).max()):.3e}")
     assert not diff.any(), np.argwhere(diff)[:5].tolist()
+
+
+# ---- outlines.hip ----------------------------------------------------------------------------------------------------------------
+# Every comparison is integer for integer and vertex for vertex against the sequential follower (cf.outline_ref: once per fixture,
+# read-only); device_outlines puts the label map, every output and the workspace between canaries.
+
+OQ, OF = do.QUANTITIES, do.CONTOUR_FIELDS
+
+
+def outline_bytes(rec):
+    return b"".join(rec[part][k].tobytes() for part in ("rows", "contours") for k in rec[part]) + rec["x"].tobytes() + rec["y"].tobytes()
+
+
+def outline_counts_of(ref):
+    r = exact_rooms(ref)
+    return [r["max_cracks"], r["max_contours"], r["max_vertices"], 0]
+
+
+def assert_nothing_listed(rec, cont, vx, vy):
+    assert cont.untouched() and vx.untouched() and vy.untouched() and not any(rec["rows"][q].any() for q in OQ)
+
+
+def assert_prefix_listed(rec, ref, nc, nv):
+    """The per-label rows are complete; the table and the vertex lists hold what the follower lists first."""
+    for q in OQ:
+        assert np.array_equal(rec["rows"][q], ref["rows"][q]), q
+    assert (len(rec["contours"]["label"]), len(rec["x"]), len(rec["y"])) == (nc, nv, nv)
+    for f in OF:
+        assert np.array_equal(rec["contours"][f], ref["contours"][f][:nc]), f
+    assert np.array_equal(rec["x"], ref["x"][:nv]) and np.array_equal(rec["y"], ref["y"][:nv])
+
+
+def test_outlines_one_contour_longer_than_a_trip():
+    """1100 x 960, one contour of 1 057 102 cracks through 1034 corner tiles: the crack scan's second trip, and 21 leader and 21
+    rank rounds whose jumps cross crack 1 048 576 in both directions.  The stale workspace is what the checkerboard left."""
+    lab, ref = cf.outline_ref("serpentine")
+    assert cf.assert_outline_serpentine_premise(lab, ref) == (1058061, 1034, 1057102, 1, 2202, 21)
+    rooms, A = exact_rooms(ref), int(lab.sum())
+    board, board_ref = cf.outline_ref("checkerboard")
+    stale = device_outlines(board, 3, exact_rooms(board_ref))[2][0].u8.clone()
+    runs = []
+    for state in ("ones", "stale"):
+        rec, needed, (ws, *_) = device_outlines(lab, 1, rooms, state=state, stale=stale)
+        assert needed.tolist() == [1057102, 1, 2202, 0] and not holds(ws, state, stale)
+        assert_outlines_equal(rec, ref)
+        assert rec["contours"]["length"].tolist() == [2 * A + 2] and rec["contours"]["S2"].tolist() == [2 * A]
+        runs.append(outline_bytes(rec))
+    assert runs[0] == runs[1]
+    # 2^20: 20 rounds, the cycle is longer than the windows (ol_cut_kernel finds it); length - 1: 21 rounds, the OL_LEN path
+    for short, rounds in ((1 << 20, 20), (rooms["max_len"] - 1, 21)):
+        assert cf.outline_rounds(short) == rounds and short < rooms["max_len"]
+        rec, needed, (_, cont, vx, vy) = device_outlines(lab, 1, {**rooms, "max_len": short}, state="ones")
+        assert needed.tolist() == [1057102, 0, 0, 1], short
+        assert_nothing_listed(rec, cont, vx, vy)
+    rec, needed, (_, cont, vx, vy) = device_outlines(lab, 1, {**rooms, "max_cracks": 1 << 20}, state="ones")      # one trip of room
+    assert needed.tolist() == [1057102, 0, 0, 0]
+    assert_nothing_listed(rec, cont, vx, vy)
+
+
+def test_outlines_more_contours_than_a_trip():
+    """728 x 728, 264 992 one-pixel contours in 1036 crack tiles and one trip of corners: the crack-side loops and both contour
+    scans on their second trip, alone."""
+    lab, ref = cf.outline_ref("checkerboard")
+    assert cf.assert_outline_checkerboard_premise(lab, ref)[:5] == (531441, 1059968, 264992, 1059968, 1036)
+    rooms = exact_rooms(ref)
+    rec, needed, _ = device_outlines(lab, 3, rooms, state="ones")
+    assert needed.tolist() == [1059968, 264992, 1059968, 0]
+    assert_outlines_equal(rec, ref)
+    c = rec["contours"]                                      # without the follower: pixel by pixel in raster order
+    rr, cc = np.nonzero(lab)
+    assert (c["length"] == 4).all() and (c["nv"] == 4).all() and (c["S2"] == 2).all() and np.array_equal(c["first"], 4 * np.arange(264992))
+    assert np.array_equal(c["label"], 1 + (rr // 100) % 3)
+    assert np.array_equal(rec["x"].reshape(-1, 4), cc[:, None] + np.array([0, 1, 1, 0])) and np.array_equal(rec["y"].reshape(-1, 4), rr[:, None] + np.array([0, 0, 1, 1]))
+    area = np.bincount(lab.ravel(), minlength=4)[1:]
+    assert np.array_equal(rec["rows"]["E"], 4 * area) and np.array_equal(rec["rows"]["no"], area) and not rec["rows"]["nh"].any()
+    cut = {**rooms, "max_contours": (1 << 18) + 3, "max_vertices": (1 << 20) + 2}        # inside the second trip, mid-contour
+    assert cut["max_vertices"] % 4 == 2 and cut["max_vertices"] < 4 * cut["max_contours"]
+    rec, needed, _ = device_outlines(lab, 3, cut, state="ones")                          # the canaries held
+    assert needed.tolist() == [1059968, 264992, 1059968, 0]
+    assert_prefix_listed(rec, ref, cut["max_contours"], cut["max_vertices"])
+
+
+@pytest.mark.parametrize("shape", fx.CAP_SHAPES, ids=IDS)
+def test_outlines_past_the_corner_grid(shape):
+    """More than 8192 x 256 corners, three trips of the crack scan; then max_out = 65 536 as the flow passes it: 393 216 output
+    words, the second trip of ol_init_kernel, over an output that held the canary pattern."""
+    lab, ref = cf.outline_ref("{}x{}".format(*shape))
+    cf.assert_outline_corner_grid_premise(lab, ref)
+    k, rooms = kmax(lab), exact_rooms(ref)
+    rec, needed, _ = device_outlines(lab, k, rooms, state="ones")
+    assert needed.tolist() == outline_counts_of(ref)
+    assert_outlines_equal(rec, ref)
+    big = 65536
+    assert len(OQ) * big > fx.OUTLINE_INIT_WORDS_PER_TRIP
+    rec, needed, _ = device_outlines(lab, big, rooms, state="ones")
+    assert needed.tolist() == outline_counts_of(ref)
+    assert all(rec["rows"][q].shape == (big,) and not rec["rows"][q][k:].any() for q in OQ)      # zeros, not the canary
+    rec["rows"] = {q: rec["rows"][q][:k] for q in OQ}
+    assert_outlines_equal(rec, ref)
+
+
+@pytest.mark.parametrize("shape", fx.CAP_SHAPES, ids=IDS)
+def test_outlines_rooms_far_above_the_counts(shape):
+    """rooms_for(area, connected=False), as the flow asks: about 1.69 M cracks of room over 58 tiles of cracks, so the contour
+    scans take a second trip over tiles past n, and 21 rounds run over contours of at most 1354 cracks."""
+    from unet_dc_segmentation_amd.outlines import rooms_for
+    lab, ref = cf.outline_ref("{}x{}".format(*shape))
+    k = kmax(lab)
+    rooms = rooms_for(np.bincount(lab.ravel(), minlength=k + 1)[1:], connected=False)
+    counts = outline_counts_of(ref)
+    assert cf.tiles(rooms["max_cracks"]) > fx.OUTLINE_SCAN_TILES_PER_TRIP > cf.tiles(counts[0])
+    assert cf.outline_rounds(rooms["max_len"]) == 21 and exact_rooms(ref)["max_len"] <= 1354
+    other = fx.CAP_SHAPES[1 - fx.CAP_SHAPES.index(shape)]    # stale: what the stage left at the other shape with exact rooms
+    other_lab, other_ref = cf.outline_ref("{}x{}".format(*other))
+    stale = device_outlines(other_lab, kmax(other_lab), exact_rooms(other_ref))[2][0].u8.clone()
+    runs = []
+    for state in ("ones", "stale"):
+        rec, needed, (ws, *_) = device_outlines(lab, k, rooms, state=state, stale=stale)
+        assert needed.tolist() == counts and not holds(ws, state, stale)
+        assert_outlines_equal(rec, ref)
+        runs.append(outline_bytes(rec))
+    assert runs[0] == runs[1]
+
+
+def test_outlines_every_round_count():
+    """max_len = 2^r for every r from the fewest rounds that hold the longest contour to 30, then 2^29 + 1 and 2^30: both parities
+    of lead / rank / fin, jumps that wrap every cycle many times.  One record, the same bytes, at every count."""
+    name = "37x53 random"
+    lab, ref = OUTLINE_FIXTURES[name], ref_of(name)
+    rooms = exact_rooms(ref)
+    L = rooms["max_len"]
+    r0 = cf.outline_rounds(L)
+    assert 1 << r0 >= L > 1 << (r0 - 1) and 4 < r0 < 15
+    lens = [1 << r for r in range(r0, 31)] + [(1 << 29) + 1, 1 << 30]
+    assert [cf.outline_rounds(v) for v in lens] == list(range(r0, 31)) + [30, 30]
+    first = None
+    for max_len in lens:
+        rec, needed, _ = device_outlines(lab, 3, {**rooms, "max_len": max_len}, state="a5")
+        assert needed.tolist() == outline_counts_of(ref), max_len
+        assert_outlines_equal(rec, ref)
+        first = outline_bytes(rec) if first is None else first
+        assert outline_bytes(rec) == first, max_len
+
+
+@pytest.mark.parametrize("name", ["tall", "wide"])
+def test_outline_coordinate_limits(name):
+    """Sides of 16 384: a bar with a vertex on the last lattice line, two small contours at the far corner."""
+    lab, hand = cf.outline_limit_maps()[name]
+    ref = cf.outline_ref(name)[1]
+    cf.assert_outline_limit_premise(name, lab, ref, hand)
+    rec, needed, _ = device_outlines(lab, 2, exact_rooms(ref), state="ones")
+    assert needed.tolist() == outline_counts_of(ref)
+    assert_outlines_equal(rec, ref)
+    for k, ints in hand.items():
+        assert tuple(int(rec["rows"][q][k - 1]) for q in OQ) == ints, k
+    assert int(rec["y" if name == "tall" else "x"].max()) == 16384
+
+
+def test_label_outlines_batch_at_full_size():
+    """label_outlines_batch with the rooms it computes itself (connected=False) on a 1040 x 1388 blob map (1 154 852 cracks of
+    room: second trips of the crack scan and of both contour scans, 21 rounds), the 96 x 130 serpentine in the workspace the larger
+    image left, and 600 x 3521: three launches, no retry."""
+    import torch
+    from unet_dc_segmentation_amd import _lib
+    from unet_dc_segmentation_amd.outlines import label_outlines_batch, rooms_for
+    small = "96x130 serpentine"
+    cases = [cf.outline_ref("blobs"), (OUTLINE_FIXTURES[small], ref_of(small)), cf.outline_ref("600x3521")]
+    areas = [np.bincount(lab.ravel(), minlength=kmax(lab) + 1)[1:] for lab, _ in cases]
+    rooms = [rooms_for(a, connected=False) for a in areas]
+    assert rooms[0]["max_cracks"] == 4 * int((cases[0][0] > 0).sum()) == 1154852 > fx.OUTLINE_CRACKS_PER_TRIP
+    need = [_lib.load().unetdc_label_outlines_workspace(*lab.shape, len(a), r["max_cracks"]) for (lab, _), a, r in zip(cases, areas, rooms)]
+    assert need[0] > need[1] > 0 and need[2] > need[0]       # the small image runs in a workspace stale from a larger one
+    labs = [torch.from_numpy(lab.copy()).cuda() for lab, _ in cases]
+    calls = []
+    real = _lib.call
+    try:
+        _lib.call = lambda name, *a: (calls.append(name), real(name, *a))[1]
+        recs = label_outlines_batch(labs, areas, connected=False)
+    finally:
+        _lib.call = real
+    assert calls == ["unetdc_label_outlines"] * 3            # no image ran again
+    for rec, (lab, ref), area in zip(recs, cases, areas):
+        assert_outlines_equal(rec, ref)
+        cols, want = do.outline_columns(rec, area), do.outline_columns(ref, area)
+        assert list(cols) == list(want) and all(cols[q].tobytes() == want[q].tobytes() for q in want)
