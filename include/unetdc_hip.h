@@ -689,6 +689,35 @@ int unetdc_label_outlines(const int32_t* label, int max_out, int h, int w, int m
                           int max_cracks, int32_t* needed, unetdc_stream_t s);
 
 
+/* ---- polygons back into a label map: exact even-odd fill (polyfill.hip; the definition is DESIGN.md section 28) --------------
+ * unetdc_polygon_fill: verts ([n_verts][2] int32: x, y in sub-pixels, 256 per pixel, |v| <= 2^28), ring_first ([n_rings + 1]:
+ *   ring j owns verts[ring_first[j] .. ring_first[j + 1])), poly_first_ring ([n_polys + 1]: polygon p owns the rings
+ *   poly_first_ring[p] .. poly_first_ring[p + 1] - 1), poly_label ([n_polys], > 0; a polygon whose label is not is skipped), all
+ *   on the device -> labels_out ([h][w] int32).  Pixel (r, c) is the square [c, c + 1] x [r, r + 1]; its centre is
+ *   (X, Y) = (256 c + 128, 256 r + 128).  It is inside a polygon iff an odd number of the polygon's edges (x0, y0) -> (x1, y1),
+ *   over all its rings, have (y0 <= Y) != (y1 <= Y) and, ordered so that y0 < y1, (X - x0)(y1 - y0) > (Y - y0)(x1 - x0):
+ *   horizontal edges never count, a centre on an edge is not right of it, ring orientation does not matter.  labels_out is the
+ *   largest label among the polygons that contain the pixel, 0 where none does; every pixel is written.  Vertices outside
+ *   the image are legal.  Index ranges read from ring_first and poly_first_ring are clamped to the arrays.
+ *   Limits: sides 1..16384, h * w < 2^30; n_verts 0..2^24; 3 n_rings <= n_verts; n_polys <= n_rings, n_polys <= 2^22; items
+ *   (polygon, row) < 2^31, checked as n_polys * h < 2^31.  n_polys = 0 is allowed (verts and poly_label may then be NULL).
+ *   workspace: unetdc_polygon_fill_workspace(h, w, n_polys, n_rings, n_verts) bytes (negative for arguments the call would
+ *   refuse), 16-byte aligned; it may hold anything on entry.  UNETDC_EINVAL before any launch for a null pointer or a refused
+ *   geometry, UNETDC_EWORKSPACE for a workspace too small.
+ * unetdc_label_census: label ([h][w] int32) -> area[n_labels] int64: area[k - 1] = the pixels of value k, k = 1..n_labels (all
+ *   n_labels entries are written; other values are not counted).  No workspace.
+ * unetdc_label_relabel: label[i] = lut[label[i] - 1] for every pixel whose value lies in 1..n_lut, in place; lut int32 on the
+ *   device.  Other pixels are not written.  No workspace.
+ *   All three launch on the given stream only; no host wait, no allocation.  Integer atomic maxima and adds only: bitwise
+ *   reproducible. */
+int64_t unetdc_polygon_fill_workspace(int h, int w, int n_polys, int n_rings, int n_verts);
+int unetdc_polygon_fill(const int32_t* verts, const int32_t* ring_first, const int32_t* poly_first_ring, const int32_t* poly_label,
+                        int n_polys, int n_rings, int n_verts, int h, int w, int32_t* labels_out, void* workspace,
+                        int64_t workspace_bytes, unetdc_stream_t s);
+int unetdc_label_census(const int32_t* label, int h, int w, int n_labels, int64_t* area, unetdc_stream_t s);
+int unetdc_label_relabel(int32_t* label, int h, int w, const int32_t* lut, int n_lut, unetdc_stream_t s);
+
+
 /* ---- overlap table of two label maps (match.hip; the definition is DESIGN.md section 12) ------------------------------------
  * unetdc_label_overlap: label_a, label_b ([h][w] int32 each: 0 = background, objects 1..max_a and 1..max_b; any label maps,
  *   touching labels allowed) -> the triples (a, b, n) with n > 0 = the number of pixels that carry label a on the first map

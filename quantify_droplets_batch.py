@@ -25,6 +25,7 @@ and a few integers per droplet come back:
     --diff_maps       unet_dc_segmentation_amd/evaluate.py      csrc/diffmap.hip        CPU: utils/difference_map.py
     --outlines        unet_dc_segmentation_amd/outlines.py      csrc/outlines.hip       CPU: utils/droplet_outlines.py
     --spatial_stats   unet_dc_segmentation_amd/spatial.py       csrc/spatial.hip        CPU: utils/spatial_stats.py
+    --gt_polygons     unet_dc_segmentation_amd/polygons.py      csrc/polyfill.hip       CPU: utils/polygon_masks.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -93,7 +94,7 @@ class Run:
     tile: dict | None                  # tile_options()
     tta: dict | None                   # tta_options()
     density: dict | None               # --density_maps: {"nb_layers", "kernel"}
-    gt: dict | None                    # --gt_dir: {"files", "min_area", "labels"}
+    gt: dict | None                    # --gt_dir: {"files", "min_area", "labels"}; --gt_polygons: "polygons" in place of "files"
     out_dir: Path
     mask_dir: Path
     overlay_dir: Path | None
@@ -279,6 +280,43 @@ def find_gt_files(images, gt_dir, flag="--gt_dir", what="annotated mask"):
     return found
 
 
+def find_gt_polygons(images, path):
+    """--gt_polygons: {image path: load}, checked before anything runs (utils/polygon_masks.py).  A
+    directory holds NAME.geojson per image; a .json file is COCO, its images matched by the stem of file_name.  A missing
+    annotation or a COCO size that differs from the image ends the run here; the files are read and packed by
+    decode_gt_polygons on the decode pool, ahead of the device like the files of --gt_dir."""
+    from utils import polygon_masks as pm
+    try:
+        return pm.find_polygons(path, images)
+    except pm.PolygonError as e:
+        raise SystemExit(f"--gt_polygons: {e}")
+
+
+def decode_gt_polygons(load):
+    """One image's polygons -> (packed record, number of features); what the reader or pack refuses ends the run."""
+    from utils.polygon_masks import PolygonError
+    try:
+        return load()
+    except PolygonError as e:
+        raise SystemExit(f"--gt_polygons: {e}")
+
+
+def rasterize_gt(run, batch, on_device):
+    """--gt_polygons: the packed polygons of the batch -> label maps of the images' sizes, numbered 1..K (what --gt_dir with
+    --gt_labels decodes from files): DEVICE tensors through polygons.rasterize_batch when the run is on the device, else
+    rasterize_numpy.  Features that own no pixel are dropped and counted."""
+    gt, hws = run.gt, [m[1] for m in batch.meta]
+    if on_device:
+        from unet_dc_segmentation_amd.polygons import rasterize_batch
+        recs = rasterize_batch([p for p, _ in batch.gt_items], hws, compact=True, device=DEVICE)
+    else:
+        from utils.polygon_masks import rasterize_numpy
+        recs = [rasterize_numpy(p, *hw, compact=True) for (p, _), hw in zip(batch.gt_items, hws)]
+    gt["features"] += sum(n for _, n in batch.gt_items)
+    gt["dropped"] += sum(n - len(r["kept"]) for (_, n), r in zip(batch.gt_items, recs))
+    batch.gt_items = [r["labels"] for r in recs]
+
+
 def decode_gt(path, as_labels):
     """Annotation file -> uint8 {0, 1} mask (convert("L") > 0, as SegmentationDataset reads it) or, with --gt_labels, the
     int32 label image as it is."""
@@ -436,7 +474,7 @@ def add_diff_outputs(run, batch, out):
     (evaluate.diff_regions_batch) and reads the images already uploaded; the PNGs go through the writer pool."""
     from utils import difference_map as dmap
     diff = run.diff
-    gts = [np.ascontiguousarray(np.asarray(g) > 0, dtype=np.uint8) for g in batch.gt_items]
+    gts = [np.ascontiguousarray(np.asarray(_host(g)) > 0, dtype=np.uint8) for g in batch.gt_items]
     if torch.is_tensor(out[0].mask) and out[0].mask.is_cuda:
         from unet_dc_segmentation_amd.evaluate import diff_regions_batch
         recs = diff_regions_batch([d.mask.contiguous() for d in out], [torch.from_numpy(g).to(DEVICE) for g in gts],
@@ -611,7 +649,9 @@ def finish_batch(run, batch, probs):
     envelope = None
     if isinstance(probs, tuple):
         probs, envelope = probs[0], probs[1:]
-    if run.sweep is not None:                            # --thresh_sweep: the raw mask at every threshold, pooled
+    if run.gt is not None and run.gt.get("polygons") is not None:
+        rasterize_gt(run, batch, probs.is_cuda)           # --gt_polygons: label maps from here on, as --gt_labels decodes them
+    if run.sweep is not None:                           # --thresh_sweep: the raw mask at every threshold, pooled
         sweep_step(run, batch, probs)
     out, mres, sums = droplets_and_matches(run, batch, probs, run.thresh, envelope=envelope)
     dres = None
@@ -711,6 +751,11 @@ def build_parser():
     p.add_argument("--gt_labels", action="store_true",
                    help="the files of --gt_dir are label images (the 16-bit NAME_labels.png of --split_touching, or any integer "
                         "image): their values are the labels as they are, numbered 1..max (--gt_min_area does not apply)")
+    p.add_argument("--gt_polygons", metavar="PATH",
+                   help="score against polygon annotations instead of --gt_dir: a directory with NAME.geojson per image (as "
+                        "--outlines writes them), or a COCO .json file whose images are matched by the stem of file_name.  The "
+                        "polygons are filled by the exact rule of DESIGN.md section 28 (on the device where the run is) and "
+                        "behave as --gt_dir with --gt_labels from then on; --gt_min_area does not apply")
     p.add_argument("--prob_thresh_low", type=float,
                    help="hysteresis threshold: also keep every 4-connected region above this lower threshold that contains a "
                         "pixel above --prob_thresh (must not exceed it; equal = off)")
@@ -826,7 +871,7 @@ def sweep_options(args):
         if args.sweep_objects is not None:
             raise SystemExit("--sweep_objects needs --thresh_sweep")
         return None
-    if not args.gt_dir:
+    if not (args.gt_dir or args.gt_polygons):
         raise SystemExit("--thresh_sweep scores against annotated masks: it needs --gt_dir")
     from utils.threshold_sweep import MAX_K
     if not 1 <= args.thresh_sweep <= MAX_K:
@@ -852,7 +897,7 @@ def boundary_options(args):
         if args.boundary_tol is not None:
             raise SystemExit("--boundary_tol needs --boundary")
         return None
-    if not args.gt_dir:
+    if not (args.gt_dir or args.gt_polygons):
         raise SystemExit("--boundary measures against annotated masks: it needs --gt_dir")
     from utils.droplet_boundary import DEFAULT_TOLS, check_radius, check_tols
     try:
@@ -931,7 +976,9 @@ def tta_options(args):
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
-    if args.diff_maps is not None and not args.gt_dir:
+    if args.gt_dir and args.gt_polygons:
+        parser.error("--gt_polygons and --gt_dir are two sources of the same annotation: give one")
+    if args.diff_maps is not None and not (args.gt_dir or args.gt_polygons):
         parser.error("--diff_maps compares against annotated masks: it needs --gt_dir")
     if args.diff_maps is not None and args.diff_maps < 1:
         parser.error("--diff_maps MIN_AREA: MIN_AREA is a number of pixels, at least 1")
@@ -960,6 +1007,8 @@ def main(argv=None):
     gt = None
     if args.gt_dir:                                      # every annotation is there and of its image's size, or nothing runs
         gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels}
+    elif args.gt_polygons:                               # every polygon file is there (COCO: read, and of its image's size), or nothing runs
+        gt = {"polygons": find_gt_polygons(images, args.gt_polygons), "min_area": 1, "labels": True, "features": 0, "dropped": 0}
     spatial = spatial_options(args, images)
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
@@ -1007,7 +1056,8 @@ def main(argv=None):
                 if nxt is None:
                     return
                 ahead.append((nxt, dec_pool.submit(decode_rgb, nxt),
-                              None if gt is None else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"]),
+                              None if gt is None else dec_pool.submit(decode_gt_polygons, gt["polygons"][str(nxt)]) if "polygons" in gt
+                              else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"]),
                               None if spatial is None or spatial["files"] is None
                               else dec_pool.submit(decode_gt, spatial["files"][str(nxt)], False)))
 
@@ -1049,6 +1099,8 @@ def main(argv=None):
         pd.concat(tables, ignore_index=True).to_csv(out_dir / "gt_droplets.csv", index=False) if tables else None
         rows = [summary_row(name, ints) for name, ints in run.gt_images] + [pooled_row([ints for _, ints in run.gt_images])]
         pd.DataFrame(rows).to_csv(out_dir / "match_per_image.csv", index=False)
+        if "polygons" in gt:
+            print(f"--gt_polygons: {gt['dropped']} of {gt['features']} features own no pixel centre and were dropped")
     if boundary is not None:
         from utils import droplet_boundary as db
         recs = boundary["records"]

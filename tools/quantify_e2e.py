@@ -33,7 +33,10 @@ class plane and both pictures on the device, two more PNGs per image, diff_regio
 --spatial_stats or --spatial_stats=R, --spatial_sims=S, --spatial_seed=N: passed through to the script (the spatial-statistics arm:
 Ripley counts of the droplet centroids and of the simulated patterns on the device, spatial_stats.csv and spatial_per_image.csv).
 --outlines: passed through to the script (the outline arm: crack-following contours of the label map on the device, the extra CSV
-columns, one GeoJSON file per image and outlines_coco.json)."""
+columns, one GeoJSON file per image and outlines_coco.json).
+--gt_polygons: the matching arm on polygon annotations (--gt_polygons DIR: the discs' outlines as one GeoJSON file per image,
+filled on the device); --gt_labels: its yardstick, the same annotations as the 16-bit label images those polygons fill to
+(--gt_dir DIR --gt_labels).  Both imply --gt."""
 import os
 import sys
 import tempfile
@@ -70,6 +73,8 @@ df_argv = [a for a in sys.argv[1:] if a.split("=")[0] == "--diff_maps"]
 gt = gt or bool(df_argv)
 sp_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--spatial_stats", "--spatial_sims", "--spatial_seed")]
 ol_argv = [a for a in sys.argv[1:] if a == "--outlines"]
+gt_polygons, gt_label_files = "--gt_polygons" in sys.argv, "--gt_labels" in sys.argv
+gt = gt or gt_polygons or gt_label_files
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 64
 dtype = pos[1] if len(pos) > 1 else "bf16"
@@ -79,11 +84,33 @@ with tempfile.TemporaryDirectory() as d:
     imgs = [bench.synthetic_micrograph(7 + i % 8) for i in range(n)]
     for i, im in enumerate(imgs):
         Image.fromarray(im).save(os.path.join(ind, f"img_{i:04d}.png"))
-    if gt:                                                # the discs are 90 grey levels above a background of 40..90
+    gt_argv = []
+    if gt and (gt_polygons or gt_label_files):            # the same discs as polygons, or as the label images they fill to
+        import json
+        from utils import droplet_outlines as do
+        from utils import polygon_masks as pm
+        from utils.droplet_match import gt_labels_numpy
+        gtd = os.path.join(d, "gt")
+        os.makedirs(gtd)
+        docs = {}
+        for i, im in enumerate(imgs):
+            if 7 + i % 8 not in docs:
+                lab = gt_labels_numpy(im[..., 0] > 125, 4)
+                doc = do.geojson(do.outlines_numpy(lab), "gt")
+                docs[7 + i % 8] = (json.dumps(doc), pm.rasterize_numpy(pm.pack(pm.features_of_geojson(doc)), *lab.shape, compact=True)["labels"])
+            text, filled = docs[7 + i % 8]
+            if gt_polygons:
+                with open(os.path.join(gtd, f"img_{i:04d}.geojson"), "w") as fh:
+                    fh.write(text)
+            else:
+                Image.fromarray(filled.astype(np.uint16)).save(os.path.join(gtd, f"img_{i:04d}.png"))
+        gt_argv = ["--gt_polygons", gtd] if gt_polygons else ["--gt_dir", gtd, "--gt_labels"]
+    elif gt:                                              # the discs are 90 grey levels above a background of 40..90
         gtd = os.path.join(d, "gt")
         os.makedirs(gtd)
         for i, im in enumerate(imgs):
             Image.fromarray((im[..., 0] > 125).astype(np.uint8) * 255).save(os.path.join(gtd, f"img_{i:04d}.png"))
+        gt_argv = ["--gt_dir", gtd, "--gt_min_area", "4"]
     torch.manual_seed(0)
     m = UNetDC(in_channels=3, out_channels=1)
     if torch.cuda.is_available():                         # calibrate the head bias so that ~10 % of the pixels are "droplet"
@@ -101,10 +128,9 @@ with tempfile.TemporaryDirectory() as d:
     argv += ["--density_maps"] if density else []
     argv += ["--split_touching"] if split else []
     argv += ["--droplet_shape"] if shape else []
-    argv += ["--gt_dir", gtd, "--gt_min_area", "4"] if gt else []
-    argv += clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv + ol_argv
+    argv += gt_argv + clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv + ol_argv
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{' --gt_polygons' if gt_polygons else ' --gt_labels' if gt_label_files else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''})")

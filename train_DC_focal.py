@@ -34,6 +34,11 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p = argparse.ArgumentParser("Train the U-Net(-DC) segmentation model")
     p.add_argument("--image_dir")
     p.add_argument("--mask_dir")
+    p.add_argument("--mask_polygons", metavar="PATH",
+                   help="with --device_data, instead of --mask_dir: polygon annotations -- a directory with NAME.geojson per "
+                        "image, or a COCO .json file matched by the stem of file_name.  The mask of an image is its filled "
+                        "polygons (labels > 0; the exact rule of DESIGN.md section 28, filled on the HIP device at the image's "
+                        "own size), and is cached like a mask file from there")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic droplet tiles instead of a dataset")
     p.add_argument("--synthetic_len", type=int, default=64)
     p.add_argument("--arch", default=arch, choices=["unetdc", "unet"])
@@ -138,11 +143,12 @@ def make_datasets(args):
 
 def split_files(args):
     """(image names, mask names) of the train, validation and test splits of --image_dir / --mask_dir."""
-    if not args.image_dir or not args.mask_dir:
+    if not args.image_dir or not (args.mask_dir or args.mask_polygons):
         raise SystemExit("--image_dir and --mask_dir are required unless --synthetic is given")
     exts = (".png", ".jpg", ".jpeg", ".tif")
     imgs = sorted(f for f in os.listdir(args.image_dir) if f.lower().endswith(exts))
-    masks = sorted(f for f in os.listdir(args.mask_dir) if f.lower().endswith(exts))
+    # --mask_polygons: the annotation of an image is found by the image's own name
+    masks = list(imgs) if args.mask_polygons else sorted(f for f in os.listdir(args.mask_dir) if f.lower().endswith(exts))
     assert len(imgs) == len(masks), "Mismatch between the number of images and masks!"
     idx = torch.randperm(len(imgs), generator=torch.Generator().manual_seed(args.seed)).tolist()
     n_test = max(1, len(imgs) // 5)
@@ -158,6 +164,14 @@ def make_device_loaders(args, rank, world, device):
     if args.synthetic:
         raise SystemExit("--device_data caches the files of --image_dir / --mask_dir; --synthetic tiles need no cache")
     tr, va, te = split_files(args)
+    polygons = None
+    if args.mask_polygons:                               # every annotation read, checked and packed before any cache is built
+        from utils import polygon_masks as pm
+        try:
+            found = pm.find_polygons(args.mask_polygons, [os.path.join(args.image_dir, n) for n in tr[0] + va[0] + te[0]])
+            polygons = {os.path.basename(k): load()[0] for k, load in found.items()}
+        except pm.PolygonError as e:
+            raise SystemExit(f"--mask_polygons: {e}")
     ids = list(range(len(tr[0])))
     if world > 1:
         per_rank = len(ids) // world
@@ -165,13 +179,14 @@ def make_device_loaders(args, rank, world, device):
     if args.crop is not None:
         from unet_dc_segmentation_amd.device_data import DeviceCropEvalLoader, DeviceCropTrainLoader, DeviceNativeCache
         native = lambda names, masks, fg=False: DeviceNativeCache(args.image_dir, args.mask_dir, names,  # noqa: E731
-                                                                  device=device, mask_names=masks, keep_foreground=fg)
+                                                                  device=device, mask_names=masks, keep_foreground=fg,
+                                                                  mask_polygons=polygons)
         train = DeviceCropTrainLoader(native([tr[0][i] for i in ids], [tr[1][i] for i in ids], args.crop_fg > 0), args.batch,
                                       args.crop, args.seed, ids, args.crops_per_image, scale=args.crop_scale, p_fg=args.crop_fg)
         return (train, DeviceCropEvalLoader(native(*va), args.batch, args.crop),
                 DeviceCropEvalLoader(native(*te), args.batch, args.crop))
     cache = lambda names, masks: DeviceImageCache(args.image_dir, args.mask_dir, names, args.img_size,  # noqa: E731
-                                                  device=device, mask_names=masks)
+                                                  device=device, mask_names=masks, mask_polygons=polygons)
     train = DeviceTrainLoader(cache([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.seed, ids)
     return train, DeviceEvalLoader(cache(*va), args.batch), DeviceEvalLoader(cache(*te), args.batch)
 
@@ -418,6 +433,11 @@ def main(argv=None, parser=None):
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
+    if args.mask_polygons and args.mask_dir:
+        raise SystemExit("--mask_polygons and --mask_dir are two sources of the same masks: give one")
+    if args.mask_polygons and not args.device_data:
+        raise SystemExit("--mask_polygons needs --device_data: the polygons are filled on the HIP device into its cache "
+                         "(the host loader reads mask files only)")
     recipe = check_optim_flags(args)
     if args.boundary is not None and not 1 <= args.boundary <= 64:
         raise SystemExit("--boundary R: R must be in 1..64")

@@ -108,6 +108,10 @@ SIGNATURES = {
     "unetdc_label_hull": (I, [P, I, I, I, P, L, P, P, I, P]),
     "unetdc_label_outlines_workspace": (L, [I, I, I, I]),
     "unetdc_label_outlines": (I, [P, I, I, I, I, P, L, P, P, I, P, P, I, I, P, P]),
+    "unetdc_polygon_fill_workspace": (L, [I, I, I, I, I]),
+    "unetdc_polygon_fill": (I, [P, P, P, P, I, I, I, I, I, P, P, L, P]),
+    "unetdc_label_census": (I, [P, I, I, I, P, P]),
+    "unetdc_label_relabel": (I, [P, I, I, P, I, P]),
     "unetdc_label_overlap_workspace": (L, [I, I, I]),
     "unetdc_label_overlap": (I, [P, I, P, I, I, I, P, L, P, P, P, P, I, P]),
     "unetdc_boundary_distances_workspace": (L, [I, I]),

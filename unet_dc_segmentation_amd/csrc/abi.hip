@@ -650,6 +650,25 @@ int unetdc_label_outlines(const int32_t* label, int max_out, int h, int w, int m
                                reinterpret_cast<long long*>(contours), max_contours, vx, vy, max_vertices, max_cracks, needed, (hipStream_t)s);
 }
 
+int64_t unetdc_polygon_fill_workspace(int h, int w, int n_polys, int n_rings, int n_verts) {
+  return polygon_fill_workspace_bytes(h, w, n_polys, n_rings, n_verts);
+}
+
+int unetdc_polygon_fill(const int32_t* verts, const int32_t* ring_first, const int32_t* poly_first_ring, const int32_t* poly_label,
+                        int n_polys, int n_rings, int n_verts, int h, int w, int32_t* labels_out, void* workspace,
+                        int64_t workspace_bytes, unetdc_stream_t s) {
+  return launch_polygon_fill(verts, ring_first, poly_first_ring, poly_label, n_polys, n_rings, n_verts, h, w, labels_out, workspace,
+                             (long)workspace_bytes, (hipStream_t)s);
+}
+
+int unetdc_label_census(const int32_t* label, int h, int w, int n_labels, int64_t* area, unetdc_stream_t s) {
+  return launch_label_census(label, h, w, n_labels, reinterpret_cast<long long*>(area), (hipStream_t)s);
+}
+
+int unetdc_label_relabel(int32_t* label, int h, int w, const int32_t* lut, int n_lut, unetdc_stream_t s) {
+  return launch_label_relabel(label, h, w, lut, n_lut, (hipStream_t)s);
+}
+
 int64_t unetdc_label_overlap_workspace(int h, int w, int max_pairs) { return label_overlap_workspace_bytes(h, w, max_pairs); }
 
 int unetdc_label_overlap(const int32_t* label_a, int max_a, const int32_t* label_b, int max_b, int h, int w, void* workspace,

@@ -327,6 +327,15 @@ int launch_label_outlines(const int* label, int max_out, int h, int w, int max_l
                           long long* contours, int max_contours, int* vx, int* vy, int max_vertices, int max_cracks, int* needed,
                           hipStream_t stream);
 
+// polyfill.hip: polygons -> int32 label map by the exact even-odd rule at pixel centres, the census of a label map's values and
+// a lookup applied in place
+long polygon_fill_workspace_bytes(int h, int w, int n_polys, int n_rings, int n_verts);       // -1 for arguments the call refuses
+int launch_polygon_fill(const int* verts, const int* ring_first, const int* poly_first_ring, const int* poly_label, int n_polys,
+                        int n_rings, int n_verts, int h, int w, int* labels_out, void* workspace, long workspace_bytes,
+                        hipStream_t stream);
+int launch_label_census(const int* label, int h, int w, int n_labels, long long* area, hipStream_t stream);
+int launch_label_relabel(int* label, int h, int w, const int* lut, int n_lut, hipStream_t stream);
+
 // neighbors.hip: contact pairs, nearest contact, degree and cluster of the labels of an int32 label map
 long label_neighbors_workspace_bytes(int h, int w, int max_label, int max_pairs);       // 0 for arguments the call refuses
 int launch_label_neighbors(const int* label, int max_label, int h, int w, int radius, void* workspace, long workspace_bytes,

@@ -27,17 +27,33 @@ def _decode_pair(image_path, mask_path, size):
     """(uint8 RGB image, its (h, w), uint8 {0, 1} mask nearest-resized to size x size) -- SegmentationDataset's host steps."""
     from utils.data_loader import resize_image
     img = np.array(Image.open(image_path).convert("RGB"))
+    if mask_path is None:                                         # mask_polygons: the mask comes from the rasteriser
+        return img, img.shape[:2], None
     mask = (np.array(Image.open(mask_path).convert("L")) > 0).astype(np.uint8)
     return img, img.shape[:2], resize_image(mask, size, nearest=True)
+
+
+def _polygon_masks(mask_polygons, names, hws, device):
+    """mask_polygons ({image name: packed record of utils.polygon_masks.pack}) -> per image the uint8 {0, 1} DEVICE mask
+    [h, w] at the image's own size: labels > 0 of polygons.rasterize_batch, one batch per call."""
+    from .polygons import rasterize_batch
+    missing = [n for n in names if n not in mask_polygons]
+    if missing:
+        raise ValueError(f"mask_polygons: no polygons for {missing[0]}")
+    recs = rasterize_batch([mask_polygons[n] for n in names], hws, compact=False, device=device)
+    return [(r["labels"] > 0).to(torch.uint8) for r in recs]
 
 
 class DeviceImageCache:
     """Preprocessed images [N, 3, size, size] float32 and masks [N, size, size] uint8 on `device`, bit-identical to
     ``SegmentationDataset(image_dir, mask_dir, names, mask_names, size=size, radius=radius)[i][:2]`` before its transform;
     ``img_max[i]`` is the image's maximum (the ``img.max()`` of the brightness / contrast step).  Files are decoded on a small
-    thread pool (PIL releases the GIL while it inflates), in windows so that at most a few dozen decoded images are held."""
+    thread pool (PIL releases the GIL while it inflates), in windows so that at most a few dozen decoded images are held.
+    mask_polygons ({image name: packed polygons}): the mask is the rasterised annotation (labels > 0 at the image's own size,
+    filled on the device) instead of a file of mask_dir, and takes the same nearest resize from there."""
 
-    def __init__(self, image_dir, mask_dir, names, size=512, radius=50, device="cuda", mask_names=None, workers=None):
+    def __init__(self, image_dir, mask_dir, names, size=512, radius=50, device="cuda", mask_names=None, workers=None,
+                 mask_polygons=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("DeviceImageCache keeps the images on the HIP device: device must be a cuda device")
@@ -59,10 +75,15 @@ class DeviceImageCache:
         window = 4 * workers
         with ThreadPoolExecutor(max_workers=workers) as ex:
             for w0 in range(0, n, window):
-                jobs = [ex.submit(_decode_pair, os.path.join(image_dir, self.names[i]), os.path.join(mask_dir, mask_names[i]),
-                                  size) for i in range(w0, min(n, w0 + window))]
-                for i, job in enumerate(jobs, start=w0):
-                    img, hw, mask = job.result()
+                jobs = [ex.submit(_decode_pair, os.path.join(image_dir, self.names[i]),
+                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]), size)
+                        for i in range(w0, min(n, w0 + window))]
+                done = [job.result() for job in jobs]
+                if mask_polygons is not None:
+                    from utils.data_loader import resize_image
+                    filled = _polygon_masks(mask_polygons, self.names[w0:w0 + len(done)], [d[1] for d in done], device)
+                    done = [(img, hw, resize_image(m.cpu().numpy(), size, nearest=True)) for (img, hw, _), m in zip(done, filled)]
+                for i, (img, hw, mask) in enumerate(done, start=w0):
                     self.orig_sizes.append(tuple(int(v) for v in hw))
                     self.images[i].copy_(preprocess_device(img, radius, size, device))
                     self.masks[i].copy_(torch.from_numpy(mask))
@@ -142,6 +163,8 @@ class DeviceTrainLoader:
 def _decode_native(image_path, mask_path):
     """(uint8 RGB image [h, w, 3], uint8 {0, 1} mask [h, w] at the image's own size: grey > 0, not resized)."""
     img = np.array(Image.open(image_path).convert("RGB"))
+    if mask_path is None:                                         # mask_polygons: the mask comes from the rasteriser
+        return img, None
     mask = (np.array(Image.open(mask_path).convert("L")) > 0).astype(np.uint8)
     if mask.shape != img.shape[:2]:
         raise ValueError(f"{mask_path}: the mask is {mask.shape[0]} x {mask.shape[1]}, its image {img.shape[0]} x {img.shape[1]}")
@@ -160,11 +183,14 @@ class DeviceNativeCache:
     keep_foreground: also keep, on the HOST, ``foreground[i] = np.flatnonzero(mask).astype(np.int32)`` of every image, taken
     from the mask as it is decoded (the mask itself is still not kept): the pixels utils.crops.draw_crop_fg places a
     foreground-aware window on.  4 bytes per foreground pixel: about 0.6 MB for a 1040 x 1388 image that is 10 % covered
-    (144 000 pixels), 5.8 MB for a fully covered one."""
+    (144 000 pixels), 5.8 MB for a fully covered one.
+
+    mask_polygons ({image name: packed polygons}): the mask is the rasterised annotation (labels > 0, filled on the device at the
+    image's size) instead of a file of mask_dir; it never visits the host unless keep_foreground asks for its pixels."""
     channels = 3
 
     def __init__(self, image_dir, mask_dir, names, radius=50, device="cuda", mask_names=None, workers=None,
-                 keep_foreground=False):
+                 keep_foreground=False, mask_polygons=None):
         from .preprocess import MAX_ELEMENT, _upload, rolling_ball_device
         device = torch.device(device)
         if device.type != "cuda":
@@ -195,10 +221,14 @@ class DeviceNativeCache:
         window = 4 * workers
         with ThreadPoolExecutor(max_workers=workers) as ex:
             for w0 in range(0, n, window):
-                jobs = [ex.submit(_decode_native, os.path.join(image_dir, self.names[i]), os.path.join(mask_dir, mask_names[i]))
+                jobs = [ex.submit(_decode_native, os.path.join(image_dir, self.names[i]),
+                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]))
                         for i in range(w0, min(n, w0 + window))]
-                for i, job in enumerate(jobs, start=w0):
-                    img, mask = job.result()
+                done = [job.result() for job in jobs]
+                if mask_polygons is not None:
+                    filled = _polygon_masks(mask_polygons, self.names[w0:w0 + len(done)], [d[0].shape[:2] for d in done], device)
+                    done = [(img, m) for (img, _), m in zip(done, filled)]
+                for i, (img, mask) in enumerate(done, start=w0):
                     if img.shape[:2] != self.sizes[i]:
                         raise ValueError(f"{self.names[i]}: decoded to {img.shape[:2]}, its header says {self.sizes[i]}")
                     if int(radius) > MAX_ELEMENT:
@@ -207,9 +237,9 @@ class DeviceNativeCache:
                     else:
                         rgb = rolling_ball_device(_upload(img, device), radius)
                     self.image(i).copy_(rgb)
-                    self.mask(i).copy_(torch.from_numpy(mask))
+                    self.mask(i).copy_(mask if torch.is_tensor(mask) else torch.from_numpy(mask))
                     if keep_foreground:
-                        self.foreground[i] = np.flatnonzero(mask).astype(np.int32)
+                        self.foreground[i] = np.flatnonzero(mask.cpu().numpy() if torch.is_tensor(mask) else mask).astype(np.int32)
                     self.img_max[i] = float(np.float32(int(rgb.max())) / np.float32(255.0))       # (once, at build)
         self.orig_sizes = self.sizes
 
