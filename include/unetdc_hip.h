@@ -932,6 +932,29 @@ int unetdc_dihedral_mean_f32(const float* p, int n, int s, int nvar, float* out,
 int unetdc_dihedral_mean_env_f32(const float* p, int n, int s, int nvar, float* out_mean, float* out_lo, float* out_hi,
                                  unetdc_stream_t stream);
 
+/* ---- deep (16-bit) images -> the 8-bit image the flow takes (window.hip; the definition is DESIGN.md section 29,
+ * utils/intensity_window.py) -------------------------------------------------------------------------------------------------
+ * src is uint16, interleaved [h][w][c], c in 1..4, sides 1..16384, h * w < 2^30; n = h * w values per channel.
+ * unetdc_u16_ranks: nq in 1..8 requests ppm[j] in 0..1000000 (HOST array, read before the call returns; any order, repeats
+ *   allowed).  k_j = max(1, ceil(ppm[j] * n / 10^6)) in int64; out_value[ch][j] = the k_j-th smallest value of channel ch
+ *   (nearest rank: 0 asks for the minimum, 10^6 for the maximum), out_below = the number of values < value, out_equal the number
+ *   == value (DEVICE int32 [c][nq] each, 4-byte aligned).  The workspace (unetdc_u16_ranks_workspace bytes; 0 for a refused
+ *   geometry) may hold anything: the call zeroes the counters it uses.
+ * unetdc_window_u16_to_u8: levels (DEVICE int32 [c][2], lo then hi per channel, clamped to 0..65535 when read): d = hi - lo;
+ *   for d > 0: t = min(max(v, lo), hi) - lo and dst = (510 t + d) / (2 d) by integer division (255 t / d rounded half up); for
+ *   d <= 0: dst = 0.  dst is uint8 [h][w][dc], dc == c, or dc == 3 with c == 1 (the grey value three times).
+ * unetdc_planes_max_u16: src ([planes][h][w] uint16, planes in 1..256) -> dst ([h][w] uint16): the maximum over the planes.
+ * All: nothing but the outputs and the workspace is written; no allocation, no host wait, no copy to the host; launches on the
+ *   given stream only; integer atomics only, so two runs are bitwise equal.  Before any launch: UNETDC_EINVAL for a null
+ *   pointer, a geometry, channel, rank or plane count outside the limits above, a request outside 0..10^6; UNETDC_EWORKSPACE for
+ *   a workspace smaller than the query's answer; then UNETDC_EINVAL for an image or a workspace that is not 16-byte aligned. */
+int64_t unetdc_u16_ranks_workspace(int h, int w, int c, int nq);
+int unetdc_u16_ranks(const uint16_t* src, int h, int w, int c, const int32_t* ppm, int nq, void* workspace, int64_t workspace_bytes,
+                     int32_t* out_value, int32_t* out_below, int32_t* out_equal, unetdc_stream_t s);
+int unetdc_window_u16_to_u8(const uint16_t* src, int h, int w, int c, const int32_t* levels, uint8_t* dst, int dc,
+                            unetdc_stream_t s);
+int unetdc_planes_max_u16(const uint16_t* src, int planes, int h, int w, uint16_t* dst, unetdc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

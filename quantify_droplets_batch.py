@@ -26,6 +26,8 @@ and a few integers per droplet come back:
     --outlines        unet_dc_segmentation_amd/outlines.py      csrc/outlines.hip       CPU: utils/droplet_outlines.py
     --spatial_stats   unet_dc_segmentation_amd/spatial.py       csrc/spatial.hip        CPU: utils/spatial_stats.py
     --gt_polygons     unet_dc_segmentation_amd/polygons.py      csrc/polyfill.hip       CPU: utils/polygon_masks.py
+    --intensity_window, --intensity_levels (in front of the preprocessing)
+                      unet_dc_segmentation_amd/window.py        csrc/window.hip         CPU: utils/intensity_window.py
 
 Without a GPU the network runs on PyTorch-CPU like the reference, and every stage has one derivation shared with the
 device.  The mask's resize reproduces what the reference's call computes (droplets.py:MASK_RESIZE).
@@ -41,6 +43,7 @@ from PIL import Image
 
 from models.model_2 import UNetDC
 from unet_dc_segmentation_amd.droplets import DropletOptions, Droplets, resize_mask_like_reference
+from utils import intensity_window as iw
 from utils.data_loader import resize_image, rolling_ball_correction_rgb
 
 DEVICE = "cuda" if torch.cuda.is_available() else "cpu"
@@ -55,8 +58,30 @@ def load_model(ckpt, dtype="f32"):
 
 
 def decode_rgb(path):
-    """File -> uint8 RGB array (runs in the decode pool: PIL releases the GIL while it inflates)."""
-    return np.array(Image.open(path).convert("RGB"))
+    """File -> uint8 RGB array (runs in the decode pool: PIL releases the GIL while it inflates).  A deep image is clipped at
+    255 by convert("RGB"): the first one of a run is reported, with the flag that windows it instead."""
+    return iw.decode_rgb_clipped(path)
+
+
+def decode_image(path, intensity=None):
+    """The decode pool's job: the RGB array, or with a window flag (uint16 [h, w, c], the file's mode) for window_image."""
+    if intensity is None:
+        return decode_rgb(path)
+    return iw.decode_deep_info(path, intensity["spec"].page)
+
+
+def window_image(run, path, arr, mode):
+    """--intensity_window / --intensity_levels: decoded uint16 image -> the 8-bit RGB image every later stage takes as 'the
+    original' (a device tensor on the GPU path, where nothing comes back before the summary), and its record for
+    intensity_per_image.csv."""
+    spec = run.intensity["spec"]
+    if DEVICE == "cuda":
+        from unet_dc_segmentation_amd.window import deep_to_u8_device
+        u8, rec = deep_to_u8_device(arr, spec, DEVICE)
+    else:
+        u8, rec = iw.deep_to_u8_numpy(arr, spec)
+    run.intensity["records"].append((Path(path).name, mode, arr.shape[0] * arr.shape[1], rec))
+    return u8
 
 
 def preprocess(path, background_radius, im=None, keep_rgb=False):
@@ -65,7 +90,10 @@ def preprocess(path, background_radius, im=None, keep_rgb=False):
     im = decode_rgb(path) if im is None else im
     oh, ow = im.shape[:2]
     if DEVICE == "cuda":                                 # rolling ball + resize + /255 + CHW on the GPU (csrc/preprocess.hip)
-        from unet_dc_segmentation_amd.preprocess import preprocess_device
+        from unet_dc_segmentation_amd.preprocess import preprocess_device, preprocess_device_u8
+        if torch.is_tensor(im):                          # the windowed image is on the device already
+            x = preprocess_device_u8(im, background_radius, IMG_SIZE, return_rgb=keep_rgb)
+            return (x[0], (oh, ow), x[1]) if keep_rgb else (x, (oh, ow))
         if keep_rgb:
             x, rgb = preprocess_device(im, background_radius, IMG_SIZE, DEVICE, return_rgb=True)
             return x, (oh, ow), rgb
@@ -112,11 +140,12 @@ class Run:
     diff: dict | None = None           # diff_options(); its "tables" / "rows" collect diff_regions.csv and diff_regions_per_image.csv
     spatial: dict | None = None        # spatial_options(); its "table" / "rows" collect spatial_stats.csv and spatial_per_image.csv
     outlines: dict | None = None       # --outlines: {"dir", "images", "jobs"}: outlines/NAME.geojson and what outlines_coco.json collects
+    intensity: dict | None = None      # --intensity_window / --intensity_levels: {"spec", "records"}: intensity_per_image.csv
 
     @property
     def keep_rgb(self):
         """Whether the batch keeps the decoded original image: the density maps read it, the difference overlays are painted on it."""
-        return self.density is not None or self.diff is not None
+        return self.density is not None or self.diff is not None or (self.intensity is not None and self.overlay_dir is not None)
 
     @property
     def envelope(self):
@@ -512,16 +541,17 @@ def _outline(mask):
     return mask.astype(bool) & ~ndimage.binary_erosion(mask.astype(bool), iterations=2)
 
 
-def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels=None):
+def _write_outputs(mask, df, fpath, name, mask_dir, overlay_dir, labels=None, img=None):
     """The per-image files of run_batch (reference :66-79): mask PNG, droplet CSV, optional overlay; with --split_touching
-    (labels given) the 16-bit label image as well, and the overlay's outline follows the cuts."""
+    (labels given) the 16-bit label image as well, and the overlay's outline follows the cuts.  img: the windowed 8-bit image
+    of a run with a window flag, which the overlay is painted on in place of the file's clipped pixels."""
     Image.fromarray(mask * 255).save(str(mask_dir / f"{name}_pred.png"))
     df.to_csv(mask_dir.parent / f"{name}_droplets.csv", index=False)
     if labels is not None:
         from utils.droplet_split import labels_u16
         Image.fromarray(labels_u16(labels)).save(str(mask_dir / f"{name}_labels.png"))
     if overlay_dir is not None:
-        img = np.array(Image.open(fpath).convert("RGB"))
+        img = np.array(Image.open(fpath).convert("RGB")) if img is None else np.array(img)
         img[_outline(mask)] = (0, 255, 0)
         if labels is not None:
             from utils.droplet_split import label_boundaries
@@ -692,7 +722,8 @@ def finish_batch(run, batch, probs):
         df.insert(0, "filename", filename) if not df.empty else None
         run.tables.append(df)
         run.rows.append({"filename": filename, "droplet_count": len(df), "total_area_px": df["area"].sum() if not df.empty else 0, **more})
-        run.submit(_write_outputs, mask, df, fpath, name, run.mask_dir, run.overlay_dir, labels)
+        windowed = _host(batch.rgbs[i]) if run.intensity is not None and run.overlay_dir is not None else None
+        run.submit(_write_outputs, mask, df, fpath, name, run.mask_dir, run.overlay_dir, labels, windowed)
         if run.density is not None:
             _density(run, None if dres is None else dres[i], batch.rgbs[i], mask, fpath)
         # back-pressure: at most ~4 batches of masks / tables wait for the writers; waiting on the OLDEST write also surfaces a
@@ -830,6 +861,7 @@ def build_parser():
                         "regions = region-level TP / FN / FP / TN, their pixels, the regions kept, missed_droplets, "
                         "spurious_droplets).  The prediction is the mask the droplet stage measured (after --prob_thresh_low / "
                         "--fill_holes), the annotation is grey > 0, with --gt_labels label > 0; --gt_min_area does not apply here")
+    iw.add_flags(p)
     p.add_argument("--outlines", action="store_true",
                    help="per-droplet outlines as polygons (crack-following contours of the label map, holes as inner rings): adds "
                         "perimeter_crack (boundary length in pixel edges, a city-block length), n_holes, euler_number, area_filled, "
@@ -983,6 +1015,12 @@ def main(argv=None):
     if args.diff_maps is not None and args.diff_maps < 1:
         parser.error("--diff_maps MIN_AREA: MIN_AREA is a number of pixels, at least 1")
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
+    try:                                                 # checked before any image, and before any output directory exists
+        spec = iw.spec_from_flags(args.intensity_window, args.intensity_levels, args.page)
+    except ValueError as e:
+        parser.error(str(e))
+    intensity = None if spec is None else {"spec": spec, "records": []}
+    iw.clip_warner.done = False
     from utils.droplet_split import half_pixels
     try:                                                 # checked before any image, and before any output directory exists
         split_depth = half_pixels(args.split_depth) / 2.0
@@ -1046,7 +1084,7 @@ def main(argv=None):
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
                   neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff,
-                  spatial=spatial, outlines=outlines)
+                  spatial=spatial, outlines=outlines, intensity=intensity)
         ahead = deque()
         it = iter(images)
 
@@ -1055,7 +1093,7 @@ def main(argv=None):
                 nxt = next(it, None)
                 if nxt is None:
                     return
-                ahead.append((nxt, dec_pool.submit(decode_rgb, nxt),
+                ahead.append((nxt, dec_pool.submit(decode_image, nxt, intensity),
                               None if gt is None else dec_pool.submit(decode_gt_polygons, gt["polygons"][str(nxt)]) if "polygons" in gt
                               else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"]),
                               None if spatial is None or spatial["files"] is None
@@ -1067,16 +1105,18 @@ def main(argv=None):
             img, fut, gt_fut, win_fut = ahead.popleft()
             refill()
             im = fut.result()
-            batch.meta.append((str(img), im.shape[:2]))
+            if intensity is not None:                    # the windowed 8-bit image stands for the original from here on
+                im = window_image(run, img, *im)
+            batch.meta.append((str(img), tuple(int(v) for v in im.shape[:2])))
             if run.shape:                                # the ORIGINAL image as grey, before the rolling ball
                 from utils.density import rgb_to_gray
-                batch.grays.append(rgb_to_gray(im))
+                batch.grays.append(rgb_to_gray(_host(im)))
             if gt is not None:
                 batch.gt_items.append(gt_fut.result())
             if win_fut is not None:
                 batch.windows.append(win_fut.result())
             if tile is not None:                         # native size: one map per image, the stages on a batch of one
-                probs, rgb = predict_tiled_image(model, im, run)
+                probs, rgb = predict_tiled_image(model, _host(im), run)
                 batch.rgbs.append(rgb)
                 finish_batch(run, batch, probs)
                 batch = Batch()
@@ -1091,6 +1131,9 @@ def main(argv=None):
             run_batch(run, batch, model)
         for f in run.writers[1]:
             f.result()                                   # re-raises a failed write
+    if intensity is not None:
+        rows = [iw.record_row(name, mode, spec, n, {k: _host(v) for k, v in rec.items()}) for name, mode, n, rec in intensity["records"]]
+        pd.DataFrame(rows).to_csv(out_dir / "intensity_per_image.csv", index=False)
     if density is not None:
         pd.DataFrame(run.density_rows).to_csv(out_dir / "density_per_image.csv", index=False)
     if gt is not None:

@@ -6,7 +6,7 @@ mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG fil
                                   [--tile[=T]] [--tile_overlap=O] [--batch=B] [--tta[=N]] [--neighbors[=G]]
                                   [--boundary[=R]] [--boundary_tol=T,T...] [--confidence[=BAND]] [--confidence_maps]
                                   [--droplet_hull[=S]] [--diff_maps[=MIN_AREA]] [--spatial_stats[=R]] [--spatial_sims=S]
-                                  [--outlines]
+                                  [--outlines] [--deep] [--intensity_window[=PLO,PHI]] [--intensity_levels=LO,HI]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
 --split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
 --droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns).
@@ -36,7 +36,10 @@ Ripley counts of the droplet centroids and of the simulated patterns on the devi
 columns, one GeoJSON file per image and outlines_coco.json).
 --gt_polygons: the matching arm on polygon annotations (--gt_polygons DIR: the discs' outlines as one GeoJSON file per image,
 filled on the device); --gt_labels: its yardstick, the same annotations as the 16-bit label images those polygons fill to
-(--gt_dir DIR --gt_labels).  Both imply --gt."""
+(--gt_dir DIR --gt_labels).  Both imply --gt.
+--deep: the files are 16-bit grey PNGs (the micrograph's grey x 16 plus four bits of noise, a 12-bit camera's range);
+--intensity_window or --intensity_window=PLO,PHI, --intensity_levels=LO,HI: passed through to the script (the window arm: ranks
+and the window to 8 bits on the device, intensity_per_image.csv).  --deep without a window flag is the clipped decode."""
 import os
 import sys
 import tempfile
@@ -73,6 +76,8 @@ df_argv = [a for a in sys.argv[1:] if a.split("=")[0] == "--diff_maps"]
 gt = gt or bool(df_argv)
 sp_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--spatial_stats", "--spatial_sims", "--spatial_seed")]
 ol_argv = [a for a in sys.argv[1:] if a == "--outlines"]
+iw_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--intensity_window", "--intensity_levels")]
+deep = "--deep" in sys.argv
 gt_polygons, gt_label_files = "--gt_polygons" in sys.argv, "--gt_labels" in sys.argv
 gt = gt or gt_polygons or gt_label_files
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -83,7 +88,11 @@ with tempfile.TemporaryDirectory() as d:
     os.makedirs(ind)
     imgs = [bench.synthetic_micrograph(7 + i % 8) for i in range(n)]
     for i, im in enumerate(imgs):
-        Image.fromarray(im).save(os.path.join(ind, f"img_{i:04d}.png"))
+        if deep:
+            g = im[..., 0].astype(np.uint16) * 16 + np.random.default_rng(i).integers(0, 16, im.shape[:2]).astype(np.uint16)
+            Image.fromarray(g).save(os.path.join(ind, f"img_{i:04d}.png"))
+        else:
+            Image.fromarray(im).save(os.path.join(ind, f"img_{i:04d}.png"))
     gt_argv = []
     if gt and (gt_polygons or gt_label_files):            # the same discs as polygons, or as the label images they fill to
         import json
@@ -128,9 +137,9 @@ with tempfile.TemporaryDirectory() as d:
     argv += ["--density_maps"] if density else []
     argv += ["--split_touching"] if split else []
     argv += ["--droplet_shape"] if shape else []
-    argv += gt_argv + clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv + ol_argv
+    argv += gt_argv + clean_argv + sweep_argv + tile_argv + tta_argv + nb_argv + bd_argv + cf_argv + hl_argv + df_argv + sp_argv + ol_argv + iw_argv
     qdb.main(argv)                                        # warm-up (library load, engine construction)
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{' --gt_polygons' if gt_polygons else ' --gt_labels' if gt_label_files else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{' --gt_polygons' if gt_polygons else ' --gt_labels' if gt_label_files else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''}{', 16-bit files' if deep else ''}{', ' + ' '.join(iw_argv) if iw_argv else ''})")

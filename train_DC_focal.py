@@ -72,6 +72,8 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     p.add_argument("--warmup_steps", type=int, default=0, metavar="N", help="linear learning-rate warm-up over the first N steps")
     p.add_argument("--lr_min", type=float, default=0.0, help="with --lr_schedule cosine / plateau: the floor of the rate")
     p.add_argument("--workers", type=int, default=4)
+    from utils.intensity_window import add_flags
+    add_flags(p)
     p.add_argument("--device_data", action="store_true",
                    help="decode and preprocess every image once into a cache on the HIP device and augment each batch there "
                         "(csrc/augment.hip; its own counter-based random stream); --workers is ignored")
@@ -127,6 +129,16 @@ def build_parser(arch="unetdc", epochs=15, ckpt="best_UNetDC_focal_model.pth", l
     return p
 
 
+def intensity_spec(args):
+    """--intensity_window / --intensity_levels / --page -> utils.intensity_window.WindowSpec, or None without a window flag (DESIGN.md
+    section 29): deep images are then windowed to 8 bits in front of the rolling ball, on the device with --device_data."""
+    from utils import intensity_window as iw
+    try:
+        return iw.spec_from_flags(args.intensity_window, args.intensity_levels, args.page)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
 def make_datasets(args):
     if args.synthetic:
         full = SyntheticDropletDataset(args.synthetic_len, args.img_size, args.in_channels, seed=args.seed)
@@ -137,7 +149,7 @@ def make_datasets(args):
                 Subset(full, idx[:n_test]))
     tr, va, te = split_files(args)
     mk = lambda pair, tf: SegmentationDataset(args.image_dir, args.mask_dir, pair[0], pair[1], transform=tf,  # noqa: E731
-                                              size=args.img_size)
+                                              size=args.img_size, intensity=intensity_spec(args))
     return mk(tr, TrainAugment(args.seed)), mk(va, None), mk(te, None)
 
 
@@ -180,13 +192,14 @@ def make_device_loaders(args, rank, world, device):
         from unet_dc_segmentation_amd.device_data import DeviceCropEvalLoader, DeviceCropTrainLoader, DeviceNativeCache
         native = lambda names, masks, fg=False: DeviceNativeCache(args.image_dir, args.mask_dir, names,  # noqa: E731
                                                                   device=device, mask_names=masks, keep_foreground=fg,
-                                                                  mask_polygons=polygons)
+                                                                  mask_polygons=polygons, intensity=intensity_spec(args))
         train = DeviceCropTrainLoader(native([tr[0][i] for i in ids], [tr[1][i] for i in ids], args.crop_fg > 0), args.batch,
                                       args.crop, args.seed, ids, args.crops_per_image, scale=args.crop_scale, p_fg=args.crop_fg)
         return (train, DeviceCropEvalLoader(native(*va), args.batch, args.crop),
                 DeviceCropEvalLoader(native(*te), args.batch, args.crop))
     cache = lambda names, masks: DeviceImageCache(args.image_dir, args.mask_dir, names, args.img_size,  # noqa: E731
-                                                  device=device, mask_names=masks, mask_polygons=polygons)
+                                                  device=device, mask_names=masks, mask_polygons=polygons,
+                                                  intensity=intensity_spec(args))
     train = DeviceTrainLoader(cache([tr[0][i] for i in ids], [tr[1][i] for i in ids]), args.batch, args.seed, ids)
     return train, DeviceEvalLoader(cache(*va), args.batch), DeviceEvalLoader(cache(*te), args.batch)
 
@@ -433,6 +446,7 @@ def main(argv=None, parser=None):
     if args.calibrate_thresh is not None and not 1 <= args.calibrate_thresh <= 1024:
         raise SystemExit("--calibrate_thresh K: K must be in 1..1024")
     check_crop_flags(args)
+    intensity_spec(args)                                 # checked before anything is read
     if args.mask_polygons and args.mask_dir:
         raise SystemExit("--mask_polygons and --mask_dir are two sources of the same masks: give one")
     if args.mask_polygons and not args.device_data:

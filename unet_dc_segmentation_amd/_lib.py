@@ -132,6 +132,10 @@ SIGNATURES = {
     "unetdc_dihedral_expand_f32": (I, [P, I, I, I, I, P, P]),
     "unetdc_dihedral_mean_f32": (I, [P, I, I, I, P, P]),
     "unetdc_dihedral_mean_env_f32": (I, [P, I, I, I, P, P, P, P]),
+    "unetdc_u16_ranks_workspace": (L, [I, I, I, I]),
+    "unetdc_u16_ranks": (I, [P, I, I, I, P, I, P, L, P, P, P, P]),
+    "unetdc_window_u16_to_u8": (I, [P, I, I, I, P, P, I, P]),
+    "unetdc_planes_max_u16": (I, [P, I, I, I, P, P]),
 }
 
 _lib = None

@@ -859,4 +859,20 @@ int unetdc_density_sqrt(const int64_t* x, double* out, int64_t n, unetdc_stream_
   return launch_density_sqrt(reinterpret_cast<const long long*>(x), out, (long)n, (hipStream_t)s);
 }
 
+int64_t unetdc_u16_ranks_workspace(int h, int w, int c, int nq) { return u16_ranks_workspace_bytes(h, w, c, nq); }
+
+int unetdc_u16_ranks(const uint16_t* src, int h, int w, int c, const int32_t* ppm, int nq, void* workspace, int64_t workspace_bytes,
+                     int32_t* out_value, int32_t* out_below, int32_t* out_equal, unetdc_stream_t s) {
+  return launch_u16_ranks(src, h, w, c, ppm, nq, workspace, (long)workspace_bytes, out_value, out_below, out_equal, (hipStream_t)s);
+}
+
+int unetdc_window_u16_to_u8(const uint16_t* src, int h, int w, int c, const int32_t* levels, uint8_t* dst, int dc,
+                            unetdc_stream_t s) {
+  return launch_window_u16_to_u8(src, h, w, c, levels, dst, dc, (hipStream_t)s);
+}
+
+int unetdc_planes_max_u16(const uint16_t* src, int planes, int h, int w, uint16_t* dst, unetdc_stream_t s) {
+  return launch_planes_max_u16(src, planes, h, w, dst, (hipStream_t)s);
+}
+
 }  // extern "C"

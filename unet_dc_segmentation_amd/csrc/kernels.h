@@ -443,6 +443,15 @@ int launch_resize_linear_chw(const unsigned char* src, int h, int w, int cn, flo
 // erosion (is_max false) / dilation of a single-channel plane by the k x k rectangle (morph_kernel, outside pixels ignored)
 int launch_morph_rect(const unsigned char* src, unsigned char* dst, int h, int w, int k, bool is_max, hipStream_t stream);
 
+// window.hip: order statistics of a deep image by radix select, the integer window to 8 bits, the maximum over planes (DESIGN.md
+// section 29; include/unetdc_hip.h)
+long u16_ranks_workspace_bytes(int h, int w, int c, int nq);        // 0 for arguments the call refuses
+int launch_u16_ranks(const unsigned short* src, int h, int w, int c, const int* ppm, int nq, void* workspace, long workspace_bytes,
+                     int* out_value, int* out_below, int* out_equal, hipStream_t stream);
+int launch_window_u16_to_u8(const unsigned short* src, int h, int w, int c, const int* levels, unsigned char* dst, int dc,
+                            hipStream_t stream);
+int launch_planes_max_u16(const unsigned short* src, int planes, int h, int w, unsigned short* dst, hipStream_t stream);
+
 // density.hip: ROI, radial and spatial droplet density maps (include/unetdc_hip.h, unetdc_density_maps)
 long density_workspace_bytes(int h, int w);
 int launch_density_maps(const unsigned char* rgb, const unsigned char* mask, int h, int w, const int* dcount, const int* darea,

@@ -20,13 +20,29 @@ import torch
 from PIL import Image
 
 from . import augment
-from .preprocess import preprocess_device
+from .preprocess import preprocess_device, preprocess_device_u8
 
 
-def _decode_pair(image_path, mask_path, size):
+def _decode_image(image_path, intensity):
+    """uint8 RGB as before (a deep file clipped at 255, reported once), or with a window (utils.intensity_window.WindowSpec)
+    the uint16 image of decode_deep, which _windowed() takes to 8 bits on the device."""
+    from utils import intensity_window as iw
+    return iw.decode_rgb_clipped(image_path) if intensity is None else iw.decode_deep(image_path, intensity.page)
+
+
+def _windowed(img, intensity, device):
+    """Decoded image -> what the preprocessing takes: the host array as it is, or with a window the [h, w, 3] uint8 DEVICE
+    tensor of window.deep_to_u8_device."""
+    if intensity is None:
+        return img
+    from .window import deep_to_u8_device
+    return deep_to_u8_device(img, intensity, device)[0]
+
+
+def _decode_pair(image_path, mask_path, size, intensity=None):
     """(uint8 RGB image, its (h, w), uint8 {0, 1} mask nearest-resized to size x size) -- SegmentationDataset's host steps."""
     from utils.data_loader import resize_image
-    img = np.array(Image.open(image_path).convert("RGB"))
+    img = _decode_image(image_path, intensity)
     if mask_path is None:                                         # mask_polygons: the mask comes from the rasteriser
         return img, img.shape[:2], None
     mask = (np.array(Image.open(mask_path).convert("L")) > 0).astype(np.uint8)
@@ -53,7 +69,7 @@ class DeviceImageCache:
     filled on the device) instead of a file of mask_dir, and takes the same nearest resize from there."""
 
     def __init__(self, image_dir, mask_dir, names, size=512, radius=50, device="cuda", mask_names=None, workers=None,
-                 mask_polygons=None):
+                 mask_polygons=None, intensity=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("DeviceImageCache keeps the images on the HIP device: device must be a cuda device")
@@ -76,7 +92,7 @@ class DeviceImageCache:
         with ThreadPoolExecutor(max_workers=workers) as ex:
             for w0 in range(0, n, window):
                 jobs = [ex.submit(_decode_pair, os.path.join(image_dir, self.names[i]),
-                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]), size)
+                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]), size, intensity)
                         for i in range(w0, min(n, w0 + window))]
                 done = [job.result() for job in jobs]
                 if mask_polygons is not None:
@@ -85,7 +101,10 @@ class DeviceImageCache:
                     done = [(img, hw, resize_image(m.cpu().numpy(), size, nearest=True)) for (img, hw, _), m in zip(done, filled)]
                 for i, (img, hw, mask) in enumerate(done, start=w0):
                     self.orig_sizes.append(tuple(int(v) for v in hw))
-                    self.images[i].copy_(preprocess_device(img, radius, size, device))
+                    if intensity is None:
+                        self.images[i].copy_(preprocess_device(img, radius, size, device))
+                    else:                                         # deep image: windowed to 8 bits on the device first
+                        self.images[i].copy_(preprocess_device_u8(_windowed(img, intensity, device), radius, size))
                     self.masks[i].copy_(torch.from_numpy(mask))
         self.img_max = self.images.amax(dim=(1, 2, 3)).double().cpu().numpy() if n else np.zeros(0)   # (once, at build)
 
@@ -160,9 +179,9 @@ class DeviceTrainLoader:
 
 
 # ---- training at native resolution: images cached at their own size, random crops cut on the device ----
-def _decode_native(image_path, mask_path):
+def _decode_native(image_path, mask_path, intensity=None):
     """(uint8 RGB image [h, w, 3], uint8 {0, 1} mask [h, w] at the image's own size: grey > 0, not resized)."""
-    img = np.array(Image.open(image_path).convert("RGB"))
+    img = _decode_image(image_path, intensity)
     if mask_path is None:                                         # mask_polygons: the mask comes from the rasteriser
         return img, None
     mask = (np.array(Image.open(mask_path).convert("L")) > 0).astype(np.uint8)
@@ -190,7 +209,7 @@ class DeviceNativeCache:
     channels = 3
 
     def __init__(self, image_dir, mask_dir, names, radius=50, device="cuda", mask_names=None, workers=None,
-                 keep_foreground=False, mask_polygons=None):
+                 keep_foreground=False, mask_polygons=None, intensity=None):
         from .preprocess import MAX_ELEMENT, _upload, rolling_ball_device
         device = torch.device(device)
         if device.type != "cuda":
@@ -222,7 +241,7 @@ class DeviceNativeCache:
         with ThreadPoolExecutor(max_workers=workers) as ex:
             for w0 in range(0, n, window):
                 jobs = [ex.submit(_decode_native, os.path.join(image_dir, self.names[i]),
-                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]))
+                                  None if mask_polygons is not None else os.path.join(mask_dir, mask_names[i]), intensity)
                         for i in range(w0, min(n, w0 + window))]
                 done = [job.result() for job in jobs]
                 if mask_polygons is not None:
@@ -231,11 +250,13 @@ class DeviceNativeCache:
                 for i, (img, mask) in enumerate(done, start=w0):
                     if img.shape[:2] != self.sizes[i]:
                         raise ValueError(f"{self.names[i]}: decoded to {img.shape[:2]}, its header says {self.sizes[i]}")
+                    img = _windowed(img, intensity, device)           # deep image: windowed to 8 bits on the device first
                     if int(radius) > MAX_ELEMENT:
                         from utils.data_loader import rolling_ball_correction_rgb
-                        rgb = _upload(rolling_ball_correction_rgb(img, int(radius)), device)
+                        host = img.cpu().numpy() if torch.is_tensor(img) else img
+                        rgb = _upload(rolling_ball_correction_rgb(host, int(radius)), device)
                     else:
-                        rgb = rolling_ball_device(_upload(img, device), radius)
+                        rgb = rolling_ball_device(img if torch.is_tensor(img) else _upload(img, device), radius)
                     self.image(i).copy_(rgb)
                     self.mask(i).copy_(mask if torch.is_tensor(mask) else torch.from_numpy(mask))
                     if keep_foreground:

@@ -79,3 +79,18 @@ def preprocess_device(img_u8_host, radius, size, device="cuda", return_rgb=False
     rgb = _upload(img_u8_host, device)
     x = resize_to_input_device(rolling_ball_device(rgb, radius), size)
     return (x, rgb) if return_rgb else x
+
+
+def preprocess_device_u8(rgb_u8, radius, size, return_rgb=False):
+    """preprocess_device for an image that is on the device already: [H, W, 3] uint8 device tensor (the windowed 8-bit image of
+    unet_dc_segmentation_amd/window.py) -> network input [3, size, size] float32.  The same kernels in the same order; with a
+    structuring element beyond MAX_ELEMENT the rolling ball takes the host operator, as there, on a copy fetched for it."""
+    if not rgb_u8.is_cuda or rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3:
+        raise _lib.UnetdcError("preprocess_device_u8 needs an [H, W, C] uint8 tensor on the HIP device")
+    if int(radius) > MAX_ELEMENT:
+        from utils.data_loader import rolling_ball_correction_rgb
+        corrected = _upload(rolling_ball_correction_rgb(rgb_u8.cpu().numpy(), int(radius)), rgb_u8.device)
+    else:
+        corrected = rolling_ball_device(rgb_u8, radius)
+    x = resize_to_input_device(corrected, size)
+    return (x, rgb_u8) if return_rgb else x

@@ -163,10 +163,13 @@ def resize_image(arr, size, nearest=False):
 
 class SegmentationDataset(Dataset):
     """(image, mask[, (orig_h, orig_w)][, filename]) with the reference's preprocessing:
-    RGB -> rolling ball (r=50) -> resize 512 -> /255; mask binarised and resized (nearest)."""
+    RGB -> rolling ball (r=50) -> resize 512 -> /255; mask binarised and resized (nearest).  intensity (a
+    utils.intensity_window.WindowSpec): the image is decoded at its own depth and windowed to 8 bits first (DESIGN.md section
+    29); without it a deep file is clipped at 255 as before, and the first one is reported."""
 
     def __init__(self, image_dir, mask_dir, image_list, mask_list, transform=None, return_filename=True,
-                 return_orig_size=True, size=512, radius=50):
+                 return_orig_size=True, size=512, radius=50, intensity=None):
+        self.intensity = intensity
         self.image_dir, self.mask_dir = image_dir, mask_dir
         self.image_list, self.mask_list = list(image_list), list(mask_list)
         self.transform = transform
@@ -177,7 +180,12 @@ class SegmentationDataset(Dataset):
         return len(self.image_list)
 
     def __getitem__(self, idx):
-        img = np.array(Image.open(os.path.join(self.image_dir, self.image_list[idx])).convert("RGB"))
+        from utils import intensity_window as iw
+        path = os.path.join(self.image_dir, self.image_list[idx])
+        if self.intensity is None:
+            img = iw.decode_rgb_clipped(path)
+        else:
+            img = iw.deep_to_u8_numpy(iw.decode_deep(path, self.intensity.page), self.intensity)[0]
         oh, ow = img.shape[:2]
         img = rolling_ball_correction_rgb(img, radius=self.radius)
         mask = np.array(Image.open(os.path.join(self.mask_dir, self.mask_list[idx])).convert("L"))
