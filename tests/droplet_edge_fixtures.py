@@ -24,7 +24,7 @@ RIPLEY_TABLE_CHUNK = 256          # spatial_points_kernel: droplets per step of 
 BORDER_PIXELS_PER_TRIP = 4096 * 256        # border_init / border_merge / border_flatten, per image
 # ... and of outlines.hip
 OUTLINE_TILE = 1024               # OL_THREADS * OL_ITEMS: corners of a census tile, cracks of a contour tile
-OUTLINE_SCAN_TILES_PER_TRIP = 1024         # ol_scan_plane: one workgroup of 1024, one tile count per thread and trip
+OUTLINE_SCAN_TILES_PER_TRIP = 1024         # scan_plane (wave_ops.h): one workgroup of 1024, one tile count per thread and trip
 OUTLINE_CRACKS_PER_TRIP = 4096 * 256       # ol_leader / ol_cut / ol_rank / ol_vertices: OL_MAX_GRID blocks of 256 threads
 OUTLINE_CORNERS_PER_TRIP = 8192 * 256      # ol_successor_kernel
 OUTLINE_INIT_WORDS_PER_TRIP = 1024 * 256   # ol_init_kernel: words of the 6 output rows
@@ -128,6 +128,38 @@ def unique_pair_labels(shape):
     A.setflags(write=False)
     B.setflags(write=False)
     return A, B
+
+
+RUN_EDGE_MAX_OUT = 13             # the labels of run_edge_labels that count; RUN_EDGE_SKIPPED lies above it
+RUN_EDGE_SKIPPED = 20
+
+
+def run_edge_labels():
+    """A 6 x 130 map (two full 64-lane chunks and a chunk with 2 live lanes) for the run helpers of csrc/wave_ops.h, which every
+    per-row stage shares.  Row 0: one label over the whole row (runs of 64, 64 and 2: a run mask of all 64 lanes).  Row 1: a new
+    label at every pixel (64 heads in a wave).  Row 2: the label changes exactly at x = 63|64 and 127|128, and one label lives
+    at x = 129 only.  Row 3: background but for x = 0, x = 63 and x = 64.  Row 4: a label above RUN_EDGE_MAX_OUT inside a run of
+    a valid one, which it splits.  Row 5: background.  tests/test_droplet_edges_cpu.py checks each of these."""
+    lab = np.zeros((6, 130), np.int32)
+    lab[0] = 1
+    lab[1] = 2 + np.arange(130) % 5                             # 2..6
+    lab[2, :64], lab[2, 64:128], lab[2, 128], lab[2, 129] = 7, 8, 9, 10
+    lab[3, 0], lab[3, 63:65] = 11, 12
+    lab[4, 40:120] = 13
+    lab[4, 70] = RUN_EDGE_SKIPPED
+    lab.setflags(write=False)
+    return lab
+
+
+def moved_one_pixel(lab):
+    """The map one pixel to the right (one pixel down where it is one column wide), zeros moving in: the second map of the
+    overlap and boundary cases, whose runs end one lane after the first map's."""
+    out = np.zeros_like(lab)
+    if lab.shape[1] > 1:
+        out[:, 1:] = lab[:, :-1]
+    else:
+        out[1:] = lab[:-1]
+    return out
 
 
 def few_dozen_labels():

@@ -232,15 +232,45 @@ def test_cap_mirrors_equal_the_sources():
     assert "OL_TILE = OL_THREADS * OL_ITEMS;" in outlines and constexpr_int(outlines, "OL_THREADS") == 256
     assert constexpr_int(outlines, "OL_MAX_GRID") * 256 == fx.OUTLINE_CRACKS_PER_TRIP == 1 << 20
     for line in ("const int crack_grid = grid_for(max_cracks, OL_THREADS, OL_MAX_GRID);", "grid_for(p.corners, OL_THREADS, 8192)",
-                 "grid_for((long)OUTLINE_QUANTITIES * max_out, 256, 1024)), dim3(256)", "for (int base = 0; base < n; base += 1024)",
+                 "grid_for((long)OUTLINE_QUANTITIES * max_out, 256, 1024)), dim3(256)",
                  "hipLaunchKernelGGL(ol_scan_cracks_kernel, dim3(1), dim3(1024)", "hipLaunchKernelGGL(ol_scan_contours_kernel, dim3(1), dim3(1024)",
                  "const dim3 block(OL_THREADS);"):
         assert line in outlines, line
+    # the scan loop of the two one-workgroup kernels is scan_plane's: a trip is its THREADS, 1024 unless a caller says otherwise
+    wave_ops = (CSRC / "wave_ops.h").read_text()
+    for line in ("template <int THREADS = 1024>\n__device__ __forceinline__ long long scan_plane(",
+                 "for (int base = 0; base < n; base += THREADS)"):
+        assert line in wave_ops, line
+    assert outlines.count("scan_plane(p.tile_") == 3 and "scan_plane<" not in outlines
     for kernel in ("ol_leader_kernel", "ol_cut_kernel", "ol_rank_kernel"):                      # the loops of one trip of 4096 x 256
         assert f"hipLaunchKernelGGL({kernel}, dim3(crack_grid), block" in outlines, kernel
     assert "hipLaunchKernelGGL(ol_vertices_kernel, dim3(crack_grid), block" in outlines
     assert (fx.OUTLINE_SCAN_TILES_PER_TRIP, fx.OUTLINE_CORNERS_PER_TRIP, fx.OUTLINE_INIT_WORDS_PER_TRIP) == (1024, 8192 * 256, 1024 * 256)
     assert constexpr_int("constexpr int A = 3, B = (1 << 4) / 2 + 1;", "B") == 9                 # the reader itself
+
+
+def test_run_edge_labels_hold_what_they_are_for():
+    lab = fx.run_edge_labels()
+    K, big = fx.RUN_EDGE_MAX_OUT, fx.RUN_EDGE_SKIPPED
+    assert lab.shape == (6, 130) and lab.dtype == np.int32 and 130 == 2 * 64 + 2
+    heads = np.ones_like(lab, bool)                             # lane 0 of a chunk, or a label other than the one before
+    heads[:, 1:] = lab[:, 1:] != lab[:, :-1]
+    heads[:, [0, 64, 128]] = True
+    per_chunk = [[int(heads[y, c:c + 64].sum()) for c in (0, 64, 128)] for y in range(6)]
+    assert (lab[0] == 1).all() and per_chunk[0] == [1, 1, 1]                            # runs of 64, 64 and 2
+    assert per_chunk[1] == [64, 64, 2] and lab[1].min() >= 1 and lab[1].max() <= K      # every lane a head
+    changes = np.flatnonzero(lab[2, 1:] != lab[2, :-1]) + 1
+    assert changes.tolist() == [64, 128, 129] and (lab == lab[2, 129]).sum() == 1       # 63|64, 127|128, and a label at 129 only
+    assert np.flatnonzero(lab[3]).tolist() == [0, 63, 64] and lab[3, 63] == lab[3, 64] != lab[3, 0]
+    at = np.flatnonzero(lab[4] == big)
+    assert big > K and at.tolist() == [70] and lab[4, 69] == lab[4, 71] and 1 <= lab[4, 69] <= K
+    assert lab[4, 63] == lab[4, 64] == lab[4, 69]                                       # ... a run that also crosses a chunk seam
+    assert not lab[5].any()
+    assert sorted(set(lab.ravel().tolist()) - {0, big}) == list(range(1, K + 1))
+    moved = fx.moved_one_pixel(lab)
+    assert np.array_equal(moved[:, 1:], lab[:, :-1]) and not moved[:, 0].any()
+    col = fx.moved_one_pixel(lab[:, :1])
+    assert col.shape == (6, 1) and np.array_equal(col[1:], lab[:-1, :1]) and col[0, 0] == 0
 
 
 def test_hull_sparse_fixture_reaches_four_trips():

@@ -99,6 +99,28 @@ def test_fixtures_hold_what_they_are_for():
         assert host_record(f"realistic_{kind}/96x130", 5)["image"][8:].sum() < rec["image"][8:].sum()
 
 
+@pytest.mark.parametrize("case", ["seams", "cycle"])
+def test_emit_ranks_at_the_thread_and_block_seams(case):
+    """diff_emit_kernel ranks the table rows by a workgroup scan of 256 per-thread counts, four pixels a thread, 1024 a block, on
+    a 1 x 2048 pair.  seams: one coloured pixel each at 0, 3, 4, 1023, 1024 and 2047, neighbours of different classes -- the
+    first and the last pixel of thread 0, the first of thread 1, the last of block 0, the first and the last of block 1: a
+    thread holds 0, 1 or 2 rows.  cycle: the classes 1, 2, 3 in turn, every pixel a region: 4 rows in every thread."""
+    c = np.zeros((1, 2048), np.int64)
+    if case == "seams":
+        roots = [0, 3, 4, 255 * 4 + 3, 1024, 2047]
+        c[0, roots] = [1, 2, 3, 1, 2, 3]
+    else:
+        roots = list(range(2048))
+        c[0] = 1 + np.arange(2048) % 3
+    pred, gt = R.from_classes(c)
+    want = D.diff_regions_numpy(pred, gt, 1)
+    assert want["class"].tolist() == c[0, roots].tolist() and want["sumx"].tolist() == roots      # every one a row, in raster order
+    assert_same(device_regions(pred, gt, 1), want, case)
+    got = device_regions(pred, gt, 1, max_out=5)
+    assert got["written"] == 5
+    assert_same(got, want, case, rows=5)
+
+
 @pytest.mark.parametrize("max_out", [3072, 100, 0])
 def test_four_classes_at_once_with_room_or_without(max_out):
     pred, gt = R.small_cases()["four_classes"]

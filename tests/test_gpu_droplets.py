@@ -353,7 +353,7 @@ CCL_SHAPES = [(1, 4097), (4097, 1), (1, 1), (700, 1), (512, 2), (341, 3), (205, 
 def test_ccl_stats_geometry_against_scipy(shape, min_area):
     """One-row, one-column and one-pixel masks; widths 1, 2, 3 and 5 (ccl_emit_kernel's 4 pixels per thread straddle row
     ends); n = 1023, 1024, 1025 around the 1024-pixel scan block; 1410 and 4096 scan blocks (ccl_scan_kernel with 2 and 4
-    block sums per thread).  Random masks near the 4-connected site-percolation threshold (0.593)."""
+    trips of 1024 block sums).  Random masks near the 4-connected site-percolation threshold (0.593)."""
     h, w = shape
     m = (np.random.default_rng(h * 3 + w).random((h, w)) < 0.58).astype(np.uint8)
     want = _scipy_table(m, min_area)
@@ -361,6 +361,27 @@ def test_ccl_stats_geometry_against_scipy(shape, min_area):
     assert n >= 1 or h * w == 1
     if h * w >= 1023:
         _assert_ccl_matches_scipy(m, min_area, max_out=max(n // 2, 1), want=want)
+
+
+EMIT_ROOTS = (0, 3, 4, 255 * 4 + 3, 1024, 2047)
+
+
+@pytest.mark.parametrize("shape", [(1, 2048), (1024, 2)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_ccl_emit_ranks_at_the_thread_and_block_seams(shape):
+    """ccl_emit_kernel ranks the kept roots by a workgroup scan of 256 per-thread counts, four pixels a thread, 1024 a block.
+    Pixels 0, 3, 4, 1023, 1024 and 2047 set: the first and the last pixel of thread 0, the first of thread 1, the last of block
+    0, the first and the last of block 1.  As 1024 x 2 no two of them are 4-neighbours and each is a root (a thread holds 0, 1
+    or 2 roots, the most a 4-connected mask allows); as 1 x 2048 the pairs 3|4 and 1023|1024 unite into objects of two
+    pixels.  The chessboard (every pixel a root, two a thread) is test_ccl_table_matches_scipy[checker]."""
+    m = np.zeros(2048, np.uint8)
+    m[list(EMIT_ROOTS)] = 1
+    m = m.reshape(shape)
+    want = _scipy_table(m, 1)
+    assert want[3].tolist() == (list(EMIT_ROOTS) if shape[1] == 2 else [0, 3, 1023, 2047])
+    assert _assert_ccl_matches_scipy(m, 1, want=want) == len(want[3])
+    _assert_ccl_matches_scipy(m, 1, max_out=3, want=want)
+    if shape[1] != 2:
+        assert _assert_ccl_matches_scipy(m, 2) == 2
 
 
 @pytest.mark.parametrize("value", [0, 1])

@@ -67,7 +67,7 @@
                                         takes several steps (tests/test_gpu_spatial.py); past 4 194 304 pixels only their number
                                         grows.  Deliberately not reached.
     spatial_window_rows_kernel          4096 x 4 waves = 16 384 rows a trip, and h <= 16 384: no second trip exists.  h = 16 384:
-                                        test_ripley_coordinate_limits (also the 64 rows a thread of spatial_window_scan_kernel).
+                                        test_ripley_coordinate_limits (also the 64 trips of 256 rows of spatial_window_scan_kernel).
     spatial_sets_kernel                 4096 x 256 = 1 048 576 points of all sets: (1 + 999) x 1049 = 1 049 000 in
                                         test_ripley_sets_kernel_second_trip; the last simulation holds the boundary.
     spatial_eligible_kernel             one workgroup per set, 256 points a step: N = 1025 (tests/test_gpu_spatial.py), 4100 here.
@@ -92,7 +92,7 @@
     ol_census_kernel, ol_base_kernel    one workgroup per tile of 1024 corners, no loop over the grid: a second trip does not
                                         exist.  Tiles past 1024 and 2048 read tile_base entries of a later scan trip: the same tests
                                         as the crack scan.
-    ol_scan_cracks_kernel (ol_scan_plane over the corner tiles)   1024 tiles = 1 048 576 corners a trip, `run` carried.  1034 tiles
+    ol_scan_cracks_kernel (scan_plane, wave_ops.h, over the corner tiles)   1024 tiles = 1 048 576 corners a trip, `run` carried.  1034 tiles
                                         with ONE contour through all of them (1100 x 960):
                                         test_outlines_one_contour_longer_than_a_trip; 2067 and 2068 tiles, three trips:
                                         test_outlines_past_the_corner_grid; 1413 tiles at 1040 x 1388:
@@ -109,7 +109,7 @@
                                         wrap every cycle many times: test_outlines_every_round_count.
     ol_contour_count_kernel, ol_contours_kernel   one workgroup per tile of 1024 cracks of ROOM, no loop over the grid.  Their tile
                                         counts are what the contour scans read: below.
-    ol_scan_contours_kernel (ol_scan_plane over the crack tiles, twice) and tile_at[0 / 1] read back   1024 tiles = 1 048 576
+    ol_scan_contours_kernel (scan_plane over the crack tiles, twice) and tile_at[0 / 1] read back   1024 tiles = 1 048 576
                                         cracks of room.  1036 tiles, all in use, rooms cut inside the second trip (262 147
                                         contours, 1 048 578 vertices: mid-contour): test_outlines_more_contours_than_a_trip.
                                         1647 and 1651 tiles of room over 58 tiles of cracks (rooms_for(area, connected=False), as
@@ -121,7 +121,7 @@
     corner / (w + 1), the shoelace terms   sides of 16 384, a vertex at x = 16384 and one at y = 16384, also against hand-derived
                                         integers: test_outline_coordinate_limits.
     Deliberately not reached: corners near 2^29 (the most `where` packs beside its 3 low bits) need a label map of two gigabytes;
-    a prefix past 2^31 in ol_scan_plane needs as many cracks.
+    a prefix past 2^31 in scan_plane needs as many cracks.
 
 The fixtures of the hull, Ripley, border and outline tests are in tests/cap_fixtures.py, each with a premise that fails when it stops
 reaching its loop; tests/test_droplet_edges_cpu.py runs the premises, and checks the mirrored caps against the sources, without a

@@ -20,6 +20,7 @@
 //                         and one atomicMax per wave; the per-object rows take one atomic triple per run of equal labels in
 //                         a wave's part of the list (a one-label map would put every pixel on three addresses).
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -140,34 +141,20 @@ __global__ __launch_bounds__(256) void boundary_row_kernel(BoundarySide s0, Boun
       if (s.table) {                                        // uniform
         // One atomic triple per run of equal labels among the wave's 64 list entries (the list keeps the order of the row
         // within 64 pixels, so the two or three boundary pixels where a row crosses an outline sit next to each other, and a
-        // one-label map is one run): heads from a ballot as in match_overlap_kernel, then a segmented suffix reduction, after
-        // whose step o a lane holds max and sum of the lanes from itself to the end of its run or to lane + 2 o - 1.
+        // one-label map is one run): wave_runs, then the run's maximum and sum (wave_ops.h).
         const int k = live ? s.label[base + x] : 0;         // a query's label is in range; the dead lanes form the last run
-        const int prev = __shfl_up(k, 1, 64);
-        const unsigned long long heads = __ballot(lane == 0 || k != prev);
-        const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);      // bit i: lane + 1 + i starts a run
-        int m = live ? d2 : -1;
-        long long t = live ? (long long)d2 : 0ll;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int m2 = __shfl_down(m, o, 64);
-          const long long t2 = __shfl_down(t, o, 64);
-          if (lane + o < 64 && (after & ((1ull << o) - 1ull)) == 0ull) {             // lane + o lies in this lane's run
-            m = max(m, m2);
-            t += t2;
-          }
-        }
-        if (k != 0 && ((heads >> lane) & 1ull)) {
-          const int len = after ? __ffsll((long long)after) : 64 - lane;
-          atomicAdd(reinterpret_cast<unsigned long long*>(s.table + k - 1), (unsigned long long)len);
+        const WaveRuns runs = wave_runs(k, lane);
+        const int m = run_max(live ? d2 : -1, runs, lane);
+        const long long t = run_sum(live ? (long long)d2 : 0ll, runs, lane);
+        if (k != 0 && runs.head) {
+          atomic_add64(s.table + k - 1, runs.len);
           atomicMax(s.table + s.k + k - 1, (long long)m);
-          atomicAdd(reinterpret_cast<unsigned long long*>(s.table + 2l * s.k + k - 1), (unsigned long long)t);
+          atomic_add64(s.table + 2l * s.k + k - 1, t);
         }
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best_max = max(best_max, __shfl_xor(best_max, o, 64));
+  best_max = wave_max(best_max);
   if (lane == 0 && best_max >= 0) atomicMax(&dmax[dir], best_max);
   __syncthreads();
   for (int b = threadIdx.x; b < nbins; b += 256) {

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "ccl_uf.h"
 #include "linear_u8.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -87,34 +88,15 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const unsigned char* __r
     const int i = base + k;
     if (i < n && ccl_kept(mask, L, area, i, min_area)) ++c;
   }
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) blocksum[b] = red[0] + red[1] + red[2] + red[3];
+  c = block_sum<256>(c, red);
+  if (threadIdx.x == 0) blocksum[b] = c;
 }
 
-__global__ __launch_bounds__(1024) void ccl_scan_kernel(int* __restrict__ blocksum, int nblocks, int* __restrict__ total) {
-  // one workgroup: exclusive scan of up to 1024 * items_per_thread block sums (serial per thread, then across threads)
-  __shared__ int part[1024];
-  const int per = (nblocks + 1023) / 1024;
-  const int t = threadIdx.x, lo = t * per, hi = min(lo + per, nblocks);
-  int s = 0;
-  for (int i = lo; i < hi; ++i) s += blocksum[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {                      // Hillis-Steele inclusive scan
-    const int v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int run = part[t] - s;                                    // exclusive prefix of this thread's range
-  for (int i = lo; i < hi; ++i) {
-    const int v = blocksum[i];
-    blocksum[i] = run;
-    run += v;
-  }
-  if (t == 1023) *total = part[1023];
+// one workgroup: the exclusive scan of the block sums in place (at most 2^20 of them, 1024 a trip); their sum is below 2^30
+__global__ __launch_bounds__(1024) void ccl_scan_kernel(int* blocksum, int nblocks, int* __restrict__ total) {
+  __shared__ int s_w[16];
+  const long long sum = scan_plane(blocksum, blocksum, nblocks, s_w);
+  if (threadIdx.x == 0) *total = (int)sum;
 }
 
 __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ L,
@@ -123,9 +105,9 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __re
                                                        const int* __restrict__ blockoff, int max_out, int* __restrict__ out_area,
                                                        long long* __restrict__ out_sy, long long* __restrict__ out_sx,
                                                        int* __restrict__ out_root, int* __restrict__ rank_of_root) {
-  // one wave per block of 1024 pixels would suffice; keep it simple: thread 0..255 handle 4 consecutive pixels each and a
-  // block-level exclusive scan of the 256 per-thread counts gives every kept root its rank
-  __shared__ int cnt[256];
+  // thread 0..255 handle 4 consecutive pixels each and a block-level exclusive scan of the 256 per-thread counts gives every
+  // kept root its rank
+  __shared__ int s_w[4];
   const int b = blockIdx.x, base = b * CCL_BLK + threadIdx.x * 4;
   bool k[4];
   int c = 0;
@@ -135,15 +117,7 @@ __global__ __launch_bounds__(256) void ccl_emit_kernel(const unsigned char* __re
     k[j] = i < n && ccl_kept(mask, L, area, i, min_area);
     c += k[j] ? 1 : 0;
   }
-  cnt[threadIdx.x] = c;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int v = threadIdx.x >= o ? cnt[threadIdx.x - o] : 0;
-    __syncthreads();
-    cnt[threadIdx.x] += v;
-    __syncthreads();
-  }
-  int rank = blockoff[b] + cnt[threadIdx.x] - c;
+  int rank = blockoff[b] + block_excl_scan<256>(c, s_w);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!k[j]) continue;

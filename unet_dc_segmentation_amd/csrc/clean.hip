@@ -13,6 +13,7 @@
 // the result depends on no order.  Workspace: L[n], aux[n] (int32 each), 4 count words.
 #include "kernels.h"
 #include "ccl_uf.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -85,18 +86,13 @@ __global__ __launch_bounds__(CLEAN_THREADS) void clean_area_kernel(const unsigne
       const int y = i / w, x = i - y * w;
       border = y == 0 || y == h - 1 || x == 0 || x == w - 1;
     }
-    unsigned long long todo = __ballot(bg);
-    while (todo) {                                          // uniform in the wave: todo comes from ballots
-      const int lead = __ffsll((long long)todo) - 1;
-      const int r0 = __shfl(r, lead, 64);
-      const unsigned long long same = __ballot(bg && r == r0);
+    for_each_wave_key(r, bg, [&](int lead, int r0, unsigned long long same) {
       const unsigned long long edge = __ballot(bg && r == r0 && border);
       if (lane == lead) {
         atomicAdd(&aux[r0], __popcll(same));
         if (edge) atomicOr(&aux[r0], CLEAN_BORDER);
       }
-      todo &= ~same;
-    }
+    });
   }
 }
 

@@ -7,9 +7,9 @@
 //
 //   label_confidence_init     sums and counts 0, minima INT64_MAX, maxima -1 on out[CONF_QUANTITIES][max_out]; out_image zeros
 //   label_confidence_kernel   the frame of label_props_kernel (shape.hip): one wave per 64 consecutive pixels of a row, runs of
-//                             equal labels from a ballot of label[x] != label[x - 1], only a run's head lane issues atomics.
-//                               sums, minima, maxima   segmented suffix reduction with __shfl_down (6 steps); q^2 reaches
-//                                                      2^32 per pixel, so its partials are 64-bit; 64 * 65535 fits 32 bits
+//                             equal labels (row_unit and wave_runs, wave_ops.h), only a run's head lane issues atomics.
+//                               sums, minima, maxima   run_sum / run_min / run_max; q^2 reaches 2^32 per pixel, so its
+//                                                      partials are 64-bit; 64 * 65535 fits 32 bits
 //                               counts                 one ballot per flag, popcount under the run's lane mask
 //                             A wave without a droplet pixel skips all of that.  The image totals stay in registers over the
 //                             grid-stride loop -- the counts as wave-uniform popcounts of ballots, the three sums per lane --
@@ -21,6 +21,7 @@
 //                             load is coalesced; a 512 x 512 plane is 1 MB and stays in L2 while the rows of a 1040 x 1388
 //                             label map walk over it.  The table is 128 KB.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -41,10 +42,6 @@ __global__ void label_confidence_init_kernel(long long* __restrict__ out, int ma
       out_image[i - n] = 0ll;
     }
   }
-}
-
-__device__ __forceinline__ void conf_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
 
 // 0..65535; a NaN gives 0 (fmaxf returns the other operand)
@@ -68,9 +65,7 @@ __global__ __launch_bounds__(64 * CONF_WAVES) void label_confidence_kernel(
   long long t_px = 0, t_fg = 0, t_ball = 0, t_bfg = 0, t_uall = 0;      // wave-uniform counts
   long long t_hall = 0, t_hfg = 0, t_sall = 0;                          // per-lane sums, reduced across the wave after the loop
   for (long u = (long)blockIdx.x * CONF_WAVES + wave; u < units; u += stride) {        // uniform within a wave
-    const int y = (int)(u / chunks), x = ((int)(u - (long)y * chunks) << 6) + lane;
-    const bool in = x < w;
-    const long i = (long)y * w + x;
+    const auto [y, x, in, i] = row_unit(u, chunks, w, lane);
     const int kraw = in ? label[i] : 0;
     const bool fg = kraw > 0;                                // foreground whatever max_out
     const int k = (kraw < 0 || kraw > max_out) ? 0 : kraw;   // labels past the capacity are skipped, never written
@@ -103,53 +98,29 @@ __global__ __launch_bounds__(64 * CONF_WAVES) void label_confidence_kernel(
     t_uall += __popcll(m_un);
     t_sall += spread;
     if (__ballot(k > 0) == 0ull) continue;                   // wave-uniform: no droplet pixel here
-    const int prev = __shfl_up(k, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || k != prev);
-    // the run of this lane ends one lane before the next head above it
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = above ? __ffsll((long long)above) : 64 - lane;     // lanes from this one to the end of its run
-    const int tail = lane + len - 1;
-    int sq = q, qmin = q, qmax = q, sh = hq, ss = spread, smax = spread;
-    long long sqq = (long long)q * q;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int a = __shfl_down(sq, o, 64), b = __shfl_down(qmin, o, 64), c = __shfl_down(qmax, o, 64), d = __shfl_down(sh, o, 64);
-      const long long e = __shfl_down(sqq, o, 64);
-      if (lane + o <= tail) {
-        sq += a;
-        qmin = min(qmin, b);
-        qmax = max(qmax, c);
-        sh += d;
-        sqq += e;
-      }
-    }
-    if (env) {
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int a = __shfl_down(ss, o, 64), b = __shfl_down(smax, o, 64);
-        if (lane + o <= tail) {
-          ss += a;
-          smax = max(smax, b);
-        }
-      }
-    }
-    if (k > 0 && ((heads >> lane) & 1ull)) {
-      const unsigned long long run = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
+    const WaveRuns runs = wave_runs(k, lane);
+    const int sq = run_sum(q, runs, lane), qmin = run_min(q, runs, lane), qmax = run_max(q, runs, lane);
+    const int sh = run_sum(hq, runs, lane);
+    const long long sqq = run_sum((long long)q * q, runs, lane);
+    int ss = spread, smax = spread;
+    if (env) ss = run_sum(spread, runs, lane), smax = run_max(spread, runs, lane);
+    if (k > 0 && runs.head) {
+      const unsigned long long run = run_mask(runs, lane);
       long long* o = out + (k - 1);
       const long r = max_out;
-      conf_add(o + C_N * r, len);
-      conf_add(o + C_SQ * r, sq);
-      conf_add(o + C_SQQ * r, sqq);
+      atomic_add64(o + C_N * r, runs.len);
+      atomic_add64(o + C_SQ * r, sq);
+      atomic_add64(o + C_SQQ * r, sqq);
       atomicMin(o + C_MINQ * r, (long long)qmin);
       atomicMax(o + C_MAXQ * r, (long long)qmax);
       const int nb = __popcll(m_band & run);
-      if (nb) conf_add(o + C_NBAND * r, nb);
-      conf_add(o + C_SH * r, sh);
+      if (nb) atomic_add64(o + C_NBAND * r, nb);
+      atomic_add64(o + C_SH * r, sh);
       if (env) {
-        conf_add(o + C_SSPREAD * r, ss);
+        atomic_add64(o + C_SSPREAD * r, ss);
         atomicMax(o + C_MAXSPREAD * r, (long long)smax);
         const int nu = __popcll(m_un & run);
-        if (nu) conf_add(o + C_NUNSTABLE * r, nu);
+        if (nu) atomic_add64(o + C_NUNSTABLE * r, nu);
       }
     }
   }
@@ -169,7 +140,7 @@ __global__ __launch_bounds__(64 * CONF_WAVES) void label_confidence_kernel(
     long long v = 0;
 #pragma unroll
     for (int j = 0; j < CONF_WAVES; ++j) v += totals[j][threadIdx.x];
-    if (v) conf_add(out_image + threadIdx.x, v);
+    if (v) atomic_add64(out_image + threadIdx.x, v);
   }
 }
 

@@ -8,8 +8,8 @@
 //   diff_merge_kernel   union-find of ccl_uf.h over ALL pixels: of the W, NW, N, NE neighbours of equal class a pixel unites
 //                       with those that the runs and the other unions do not already imply (in a flat region: one per run)
 //   diff_stats_kernel   at the root: area, sums of rows and columns, and the OR of the classes among the 8 neighbours.  The
-//                       lanes of a wave that share a root send ONE add per quantity (the black class is one region of about
-//                       a million pixels on a micrograph: un-aggregated, every pixel would land on the same three words);
+//                       lanes of a wave that share a root send ONE add per quantity (for_each_wave_key, wave_ops.h: the black class is one
+//                       region of about a million pixels on a micrograph, whose pixels would all land on the same three words);
 //                       pixels[] takes one add per wave and class
 //   diff_count_kernel   regions[] and kept[] at the root pixels, and per 1024 pixels the number of table rows
 //   (ccl.hip's scan)    exclusive scan of those numbers; the total is *out_count
@@ -20,6 +20,7 @@
 // or shuffles.  Integer atomics and the shared union-find: the outputs depend on no order.
 #include "kernels.h"
 #include "ccl_uf.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -35,16 +36,6 @@ struct DiffPlanes {
   int *L, *area, *nbr, *blocksum;
   unsigned char* cls;
 };
-
-__device__ __forceinline__ void diff_add64(long long* p, int v) {
-  if (v) atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
-__device__ __forceinline__ int wave_or(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
 
 // A SEGMENT is 64 consecutive pixels of the flat image from a multiple of 64: the lanes of one wave here (256 threads, bases
 // that are multiples of 256).  L[i] = the first pixel of i's run of equal class within its segment and its row: a forest
@@ -142,12 +133,8 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_stats_kernel(DiffPlanes p, 
       px2 += c == 2;
       px3 += c == 3;
     }
-    unsigned long long todo = __ballot(live);
-    while (todo) {                                          // uniform in the wave: todo comes from ballots
-      const int lead = __ffsll((long long)todo) - 1;
-      const int r0 = __shfl(r, lead, 64);
+    for_each_wave_key(r, live, [&](int lead, int r0, unsigned long long same) {
       const bool mine = live && r == r0;
-      const unsigned long long same = __ballot(mine);
       const int cnt = __popcll(same);
       int ys, xs, ms;
       if (cnt > 1) {                                        // uniform
@@ -169,19 +156,14 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_stats_kernel(DiffPlanes p, 
       held.sy += ys;
       held.sx += xs;
       held.mask |= ms;
-      todo &= ~same;
-    }
+    });
   }
   diff_flush(p, held, lane);
-  px0 = wave_sum(px0);
-  px1 = wave_sum(px1);
-  px2 = wave_sum(px2);
-  px3 = wave_sum(px3);
+  const int px[4] = {wave_sum(px0), wave_sum(px1), wave_sum(px2), wave_sum(px3)};
   if (lane == 0) {
-    diff_add64(out_image + 0, px0);
-    diff_add64(out_image + 1, px1);
-    diff_add64(out_image + 2, px2);
-    diff_add64(out_image + 3, px3);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (px[c]) atomic_add64(out_image + c, px[c]);
   }
 }
 
@@ -212,29 +194,16 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_count_kernel(DiffPlanes p, 
       kept3 += big && c == 3;
       rows += big && c != 0;
     }
-    rows = wave_sum(rows);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = rows;
-    __syncthreads();
-    if (threadIdx.x == 0) p.blocksum[b] = red[0] + red[1] + red[2] + red[3];
+    rows = block_sum<DIFF_THREADS>(rows, red);
+    if (threadIdx.x == 0) p.blocksum[b] = rows;
     __syncthreads();                                        // red[] is written again on the next trip
   }
-  reg0 = wave_sum(reg0);
-  reg1 = wave_sum(reg1);
-  reg2 = wave_sum(reg2);
-  reg3 = wave_sum(reg3);
-  kept0 = wave_sum(kept0);
-  kept1 = wave_sum(kept1);
-  kept2 = wave_sum(kept2);
-  kept3 = wave_sum(kept3);
+  const int sums[8] = {wave_sum(reg0),  wave_sum(reg1),  wave_sum(reg2),  wave_sum(reg3),
+                       wave_sum(kept0), wave_sum(kept1), wave_sum(kept2), wave_sum(kept3)};
   if ((threadIdx.x & 63) == 0) {
-    diff_add64(out_image + 4, reg0);
-    diff_add64(out_image + 5, reg1);
-    diff_add64(out_image + 6, reg2);
-    diff_add64(out_image + 7, reg3);
-    diff_add64(out_image + 8, kept0);
-    diff_add64(out_image + 9, kept1);
-    diff_add64(out_image + 10, kept2);
-    diff_add64(out_image + 11, kept3);
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (sums[q]) atomic_add64(out_image + 4 + q, sums[q]);
   }
 }
 
@@ -243,7 +212,7 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_emit_kernel(DiffPlanes p, i
                                                                  int* __restrict__ out_class, int* __restrict__ out_area,
                                                                  long long* __restrict__ out_sy, long long* __restrict__ out_sx,
                                                                  int* __restrict__ out_nbr) {
-  __shared__ int cnt[DIFF_THREADS];
+  __shared__ int s_w[DIFF_THREADS / 64];
   for (int b = blockIdx.x; b < nblocks; b += gridDim.x) {   // uniform in the workgroup
     const int base = b * DIFF_BLK + threadIdx.x * 4;
     bool k[4];
@@ -253,15 +222,7 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_emit_kernel(DiffPlanes p, i
       k[j] = base + j < n && diff_row(p, base + j, min_area);
       c += k[j] ? 1 : 0;
     }
-    cnt[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 1; o < DIFF_THREADS; o <<= 1) {
-      const int v = (int)threadIdx.x >= o ? cnt[threadIdx.x - o] : 0;
-      __syncthreads();
-      cnt[threadIdx.x] += v;
-      __syncthreads();
-    }
-    int rank = p.blocksum[b] + cnt[threadIdx.x] - c;
+    int rank = p.blocksum[b] + block_excl_scan<DIFF_THREADS>(c, s_w);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (!k[j]) continue;
@@ -275,7 +236,6 @@ __global__ __launch_bounds__(DIFF_THREADS) void diff_emit_kernel(DiffPlanes p, i
       }
       ++rank;
     }
-    __syncthreads();                                        // cnt[] is written again on the next trip
   }
 }
 

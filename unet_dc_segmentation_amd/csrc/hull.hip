@@ -6,8 +6,8 @@
 // read as (t, x), the right chain the upper hull of the right ones; the two never share a point.
 //
 //   hull_init_kernel      min_y INT_MAX, max_y -1 per label; out zeros
-//   hull_extent_kernel    the frame of label_props_kernel (shape.hip): one wave per 64 consecutive pixels of a row, run heads
-//                         from a ballot of label[x] != label[x - 1]; one atomicMin / atomicMax of y per run
+//   hull_extent_kernel    the frame of label_props_kernel (shape.hip): one wave per 64 consecutive pixels of a row, runs of
+//                         equal labels (row_unit and wave_runs, wave_ops.h); one atomicMin / atomicMax of y per run
 //   hull_scan_kernel      one workgroup: exclusive scan of (height + 1) over the labels into segment offsets (a label of
 //                         height H has H + 1 corner levels), in coalesced tiles of 4096 labels; the sum of the heights decides
 //                         *out_rows and the overflow flag
@@ -26,6 +26,7 @@
 //                         wave reduces with integer max, and with the minimum of Wc^2 / Wl compared in 128 bits.
 // Integer atomic min / max and sequential chains only: the result does not depend on the order in which anything runs.
 #include "kernels.h"
+#include "wave_ops.h"
 #include "workspace.h"
 
 namespace unetdc {
@@ -80,16 +81,13 @@ struct HullRun {
 };
 __device__ __forceinline__ bool hull_run(const int* __restrict__ label, int max_out, int w, int chunks, long u, HullRun& r) {
   const int lane = threadIdx.x & 63;
-  const int y = (int)(u / chunks), x = ((int)(u - (long)y * chunks) << 6) + lane;
-  int k = x < w ? label[(long)y * w + x] : 0;
+  const RowUnit px = row_unit(u, chunks, w, lane);
+  int k = px.in ? label[px.i] : 0;
   if (k < 0 || k > max_out) k = 0;                          // labels past the capacity are skipped, never written
-  const int prev = __shfl_up(k, 1, 64);
-  const unsigned long long heads = __ballot(lane == 0 || k != prev);
   if (__ballot(k > 0) == 0ull) return false;                // wave-uniform: nothing but background here
-  const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-  const int len = above ? __ffsll((long long)above) : 64 - lane;
-  r.k = k, r.y = y, r.x0 = x, r.x1 = x + len - 1;
-  r.head = k > 0 && ((heads >> lane) & 1ull);
+  const WaveRuns runs = wave_runs(k, lane);
+  r.k = k, r.y = px.y, r.x0 = px.x, r.x1 = px.x + runs.len - 1;
+  r.head = k > 0 && runs.head;
   return true;
 }
 
@@ -127,13 +125,8 @@ __global__ __launch_bounds__(1024) void hull_scan_kernel(HullPlanes p, int max_o
       mine += slots[j];
       rows += height;
     }
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int a = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += a;
-      rows += __shfl_xor(rows, o, 64);
-    }
+    const int incl = wave_incl_scan(mine, lane);
+    rows = wave_sum(rows);
     if (lane == 63) s_slots[wave] = incl, s_rows[wave] = rows;
     __syncthreads();
     int before = 0, tile_slots = 0, tile_rows = 0;
@@ -237,12 +230,7 @@ __global__ __launch_bounds__(64) void hull_chain_kernel(HullPlanes p, int max_ou
         if (x != empty) n = hull_push(seg + lo, n, hull_pack(x, y0 + j), right);
       }
     }
-    int incl = n;                                           // where this lane's points start in the concatenation
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
+    const int incl = wave_incl_scan(n, lane);               // where this lane's points start in the concatenation
     const int total = __shfl(incl, 63, 64), at = incl - n;
     if (total <= HULL_LDS_POINTS) {                         // uniform: the second pass runs in LDS
       if (c == 1) {

@@ -7,10 +7,11 @@
 // addition as the combine step.  This file adds the kernel that fills the table:
 //
 //   match_overlap_kernel   one wave per 64 consecutive pixels of a row, as label_props_kernel.  Only pixels that carry a label
-//                          in range on BOTH maps take part.  Lanes with the same (a, b) next to each other form a run (heads
-//                          from a ballot of key[x] != key[x - 1]); only the run's head inserts, with the run length as its
-//                          count: a few inserts per droplet row, not one per pixel.
+//                          in range on BOTH maps take part.  Lanes with the same (a, b) next to each other form a run
+//                          (wave_runs, wave_ops.h); only the run's head inserts, with the run length as its count: a few
+//                          inserts per droplet row, not one per pixel.
 #include "pair_table.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -31,20 +32,13 @@ __global__ __launch_bounds__(256) void match_overlap_kernel(const int* __restric
   const long units = (long)h * chunks;
   const long stride = (long)gridDim.x * 4;
   for (long u = (long)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += stride) {   // uniform within a wave
-    const int y = (int)(u / chunks), x = ((int)(u - (long)y * chunks) << 6) + lane;
-    const bool in = x < w;
-    const long i = (long)y * w + x;
-    const int a = in ? label_a[i] : 0, b = in ? label_b[i] : 0;
+    const RowUnit px = row_unit(u, chunks, w, lane);
+    const int a = px.in ? label_a[px.i] : 0, b = px.in ? label_b[px.i] : 0;
     // labels below 1 or above the given maxima take no part
     const pair_key_t key = (a > 0 && a <= max_a && b > 0 && b <= max_b) ? ((pair_key_t)(unsigned)a << 32) | (unsigned)b : 0ull;
     if (__ballot(key != 0ull) == 0ull) continue;             // wave-uniform: no shared foreground here
-    const pair_key_t prev = __shfl_up(key, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || key != prev);
-    if (key != 0ull && ((heads >> lane) & 1ull)) {
-      const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-      const int len = above ? __ffsll((long long)above) : 64 - lane;     // lanes from this one to the end of its run
-      pair_insert<PairAdd>(p, key, len);
-    }
+    const WaveRuns r = wave_runs(key, lane);
+    if (key != 0ull && r.head) pair_insert<PairAdd>(p, key, r.len);
   }
 }
 

@@ -27,6 +27,7 @@
 // No launch reads what another workgroup writes in the same launch; nothing waits on another workgroup.  Integer atomic adds and
 // fixed-order scans only: bitwise reproducible.
 #include "kernels.h"
+#include "wave_ops.h"
 #include "workspace.h"
 
 namespace unetdc {
@@ -104,57 +105,6 @@ __device__ __forceinline__ int ol_corner_mask(const int* __restrict__ label, int
   return ol_mask(ol_corner(label, max_out, h, w, x, y));
 }
 
-// Exclusive scan of (a, b) over the 256 threads of a workgroup -> (ea, eb), and the totals.  Every thread calls it.
-__device__ __forceinline__ void ol_block_scan(int a, int b, int& ea, int& eb, int& ta, int& tb) {
-  __shared__ int s_a[OL_THREADS / 64], s_b[OL_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int ia = a, ib = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int ua = __shfl_up(ia, o, 64), ub = __shfl_up(ib, o, 64);
-    if (lane >= o) ia += ua, ib += ub;
-  }
-  if (lane == 63) s_a[wave] = ia, s_b[wave] = ib;
-  __syncthreads();
-  ea = ia - a, eb = ib - b, ta = 0, tb = 0;
-#pragma unroll
-  for (int v = 0; v < OL_THREADS / 64; ++v) {
-    const int qa = s_a[v], qb = s_b[v];
-    ea += v < wave ? qa : 0, eb += v < wave ? qb : 0;
-    ta += qa, tb += qb;
-  }
-  __syncthreads();
-}
-
-// One workgroup of 1024: exclusive scan of in[0 .. n) into at[0 .. n), 1024 entries a trip; the 64-bit total.  A prefix past 2^31
-// is cut: nothing reads the scan then.
-__device__ __forceinline__ long long ol_scan_plane(const int* __restrict__ in, int* __restrict__ at, int n, int* s_w) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  long long run = 0;
-  for (int base = 0; base < n; base += 1024) {
-    const int i = base + t, v = i < n ? in[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    long long before = 0, tile = 0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int q = s_w[u];
-      before += u < wave ? q : 0;
-      tile += q;
-    }
-    if (i < n) at[i] = (int)(run + before + incl - v);
-    run += tile;
-    __syncthreads();
-  }
-  return run;
-}
-
 __global__ void ol_init_kernel(OutlinePlanes p, long n_out, long long* __restrict__ out, int* __restrict__ needed) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (long)gridDim.x * blockDim.x) out[i] = 0ll;
   if (blockIdx.x == 0 && threadIdx.x < 16) {
@@ -166,18 +116,18 @@ __global__ void ol_init_kernel(OutlinePlanes p, long n_out, long long* __restric
 // ---- census --------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(OL_THREADS) void ol_census_kernel(const int* __restrict__ label, int max_out, int h, int w, OutlinePlanes p) {
+  __shared__ int s_w[OL_THREADS / 64];
   const long first = (long)blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS;
   int mine = 0;
 #pragma unroll
   for (int j = 0; j < OL_ITEMS; ++j) mine += __popc(ol_corner_mask(label, max_out, h, w, first + j, p.corners));
-  int ea, eb, ta, tb;
-  ol_block_scan(mine, 0, ea, eb, ta, tb);
-  if (threadIdx.x == 0) p.tile_cracks[blockIdx.x] = ta;
+  const int total = block_sum<OL_THREADS>(mine, s_w);
+  if (threadIdx.x == 0) p.tile_cracks[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(1024) void ol_scan_cracks_kernel(OutlinePlanes p, int max_cracks, int* __restrict__ needed) {
   __shared__ int s_w[16];
-  const long long total = ol_scan_plane(p.tile_cracks, p.tile_base, p.corner_tiles, s_w);
+  const long long total = scan_plane(p.tile_cracks, p.tile_base, p.corner_tiles, s_w);
   if (threadIdx.x == 0) {
     const bool over = total > max_cracks;
     needed[0] = (int)(total > 0x7fffffffll ? 0x7fffffffll : total);
@@ -187,14 +137,13 @@ __global__ __launch_bounds__(1024) void ol_scan_cracks_kernel(OutlinePlanes p, i
 }
 
 __global__ __launch_bounds__(OL_THREADS) void ol_base_kernel(const int* __restrict__ label, int max_out, int h, int w, OutlinePlanes p) {
+  __shared__ int s_w[OL_THREADS / 64];
   if (p.ctl[OL_OVER]) return;                               // uniform: more cracks than the planes hold
   const long first = (long)blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS;
   int count[OL_ITEMS], mine = 0;
 #pragma unroll
   for (int j = 0; j < OL_ITEMS; ++j) mine += count[j] = __popc(ol_corner_mask(label, max_out, h, w, first + j, p.corners));
-  int ea, eb, ta, tb;
-  ol_block_scan(mine, 0, ea, eb, ta, tb);
-  int at = p.tile_base[blockIdx.x] + ea;
+  int at = p.tile_base[blockIdx.x] + block_excl_scan<OL_THREADS>(mine, s_w);
 #pragma unroll
   for (int j = 0; j < OL_ITEMS; ++j) {
     if (first + j < p.corners) p.base[first + j] = at;
@@ -286,6 +235,7 @@ __global__ __launch_bounds__(OL_THREADS) void ol_rank_kernel(OutlinePlanes p, in
 
 // fin: the set the rank rounds ended in.  One workgroup per tile of the crack room; tiles past the cracks count nothing.
 __global__ __launch_bounds__(OL_THREADS) void ol_contour_count_kernel(OutlinePlanes p, int fin, int max_len) {
+  __shared__ int s_w[2 * OL_THREADS / 64];
   if (p.ctl[OL_OVER] | p.ctl[OL_LONG]) return;              // uniform; both were written by earlier launches
   const int n = p.ctl[OL_N];
   const long first = (long)blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS;
@@ -299,9 +249,10 @@ __global__ __launch_bounds__(OL_THREADS) void ol_contour_count_kernel(OutlinePla
       if (p.val[fin][i] > max_len) p.ctl[OL_LEN] = 1;       // read by later launches only
     }
   }
-  int ea, eb, ta, tb;
-  ol_block_scan(leaders, verts, ea, eb, ta, tb);
-  if (threadIdx.x == 0) p.tile_n[0][blockIdx.x] = ta, p.tile_n[1][blockIdx.x] = tb;
+  const int mine[2] = {leaders, verts};
+  int excl[2], total[2];
+  block_excl_scan<OL_THREADS>(mine, excl, total, s_w);
+  if (threadIdx.x == 0) p.tile_n[0][blockIdx.x] = total[0], p.tile_n[1][blockIdx.x] = total[1];
 }
 
 __global__ __launch_bounds__(1024) void ol_scan_contours_kernel(OutlinePlanes p, int* __restrict__ needed) {
@@ -311,15 +262,14 @@ __global__ __launch_bounds__(1024) void ol_scan_contours_kernel(OutlinePlanes p,
     if (threadIdx.x == 0) needed[3] = 1, p.ctl[OL_LONG] = 1;
     return;
   }
-  const long long contours = ol_scan_plane(p.tile_n[0], p.tile_at[0], p.crack_tiles, s_w);
-  const long long verts = ol_scan_plane(p.tile_n[1], p.tile_at[1], p.crack_tiles, s_w);
+  const long long contours = scan_plane(p.tile_n[0], p.tile_at[0], p.crack_tiles, s_w);
+  const long long verts = scan_plane(p.tile_n[1], p.tile_at[1], p.crack_tiles, s_w);
   if (threadIdx.x == 0) needed[1] = (int)contours, needed[2] = (int)verts;       // both at most the number of cracks
 }
 
-__device__ __forceinline__ void ol_add(long long* at, long long v) { atomicAdd(reinterpret_cast<unsigned long long*>(at), (unsigned long long)v); }
-
 __global__ __launch_bounds__(OL_THREADS) void ol_contours_kernel(const int* __restrict__ label, int max_out, int h, int w, OutlinePlanes p, int fin,
                                                                  long long* __restrict__ out, long long* __restrict__ contours, int max_contours) {
+  __shared__ int s_w[2 * OL_THREADS / 64];
   if (p.ctl[OL_OVER] | p.ctl[OL_LONG]) return;
   const int n = p.ctl[OL_N];
   const long first = (long)blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS;
@@ -331,9 +281,10 @@ __global__ __launch_bounds__(OL_THREADS) void ol_contours_kernel(const int* __re
     nv[j] = i < n && p.leader[i] == (int)i ? p.turns[fin][i] : -1;
     if (nv[j] >= 0) ++leaders, verts += nv[j];
   }
-  int ec, ev, tc, tv;
-  ol_block_scan(leaders, verts, ec, ev, tc, tv);
-  int c = p.tile_at[0][blockIdx.x] + ec, at = p.tile_at[1][blockIdx.x] + ev;
+  const int mine[2] = {leaders, verts};
+  int excl[2], total[2];
+  block_excl_scan<OL_THREADS>(mine, excl, total, s_w);
+  int c = p.tile_at[0][blockIdx.x] + excl[0], at = p.tile_at[1][blockIdx.x] + excl[1];
   int* __restrict__ first_of = p.jump[fin ^ 1];             // free since the last rank round: a leader's first vertex
 #pragma unroll
   for (int j = 0; j < OL_ITEMS; ++j) {
@@ -353,11 +304,11 @@ __global__ __launch_bounds__(OL_THREADS) void ol_contours_kernel(const int* __re
     }
     long long* o = out + (k - 1);
     const long rows = max_out;
-    ol_add(o + O_E * rows, len);
-    ol_add(o + (s2 > 0 ? O_NO : O_NH) * rows, 1);
-    ol_add(o + O_NV * rows, nv[j]);
-    if (s2 > 0) ol_add(o + O_F2 * rows, s2);
-    ol_add(o + O_S2 * rows, s2);
+    atomic_add64(o + O_E * rows, len);
+    atomic_add64(o + (s2 > 0 ? O_NO : O_NH) * rows, 1);
+    atomic_add64(o + O_NV * rows, nv[j]);
+    if (s2 > 0) atomic_add64(o + O_F2 * rows, s2);
+    atomic_add64(o + O_S2 * rows, s2);
     ++c, at += nv[j];
   }
 }

@@ -4,7 +4,7 @@
 // its polygon from column k = floor(((Y_r - y0)(x1 - x0) + (x0 - 128)(y1 - y0)) / (256 (y1 - y0))) + 1 on.  A pixel gets the
 // largest label among the polygons that contain its centre.
 //
-//   pf_clear_kernel     the output plane: zeros
+//   fill_kernel<int>    the output plane: zeros (wave_ops.h, as scan_plane and for_each_wave_key below)
 //   pf_items_kernel     one wave per polygon: the rows whose centre line its edges can cross and the columns a toggle can start at, both
 //                       clipped to the image (its box), and the number of those rows.  An item is (polygon, row)
 //   pf_scan_kernel      one workgroup: exclusive scan of the rows per polygon, the item bases; the total behind them
@@ -20,6 +20,7 @@
 #include <climits>
 
 #include "kernels.h"
+#include "wave_ops.h"
 #include "workspace.h"
 
 namespace unetdc {
@@ -53,10 +54,6 @@ long polygon_fill_workspace_bytes(int h, int w, int n_polys, int n_rings, int n_
 }
 
 __device__ __forceinline__ int pf_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-__global__ __launch_bounds__(256) void pf_clear_kernel(int* __restrict__ out, long n) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = 0;
-}
 
 __global__ __launch_bounds__(256) void pf_items_kernel(const int2* __restrict__ verts, const int* __restrict__ ring_first,
                                                         const int* __restrict__ poly_first_ring, const int* __restrict__ poly_label,
@@ -92,34 +89,12 @@ __global__ __launch_bounds__(256) void pf_items_kernel(const int2* __restrict__ 
   }
 }
 
-// One workgroup of 1024: exclusive scan of rows[0 .. n) into base[0 .. n), 1024 entries a trip; base[n] = the total (< 2^31: the
-// layout refuses n * h beyond that).
+// One workgroup of 1024: exclusive scan of rows[0 .. n) into base[0 .. n); base[n] = the total (< 2^31: the layout refuses
+// n * h beyond that).
 __global__ __launch_bounds__(1024) void pf_scan_kernel(PolyfillPlanes p, int n) {
   __shared__ int s_w[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  int run = 0;
-  for (int first = 0; first < n; first += 1024) {
-    const int i = first + t, v = i < n ? p.rows[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int before = 0, tile = 0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int q = s_w[u];
-      before += u < wave ? q : 0;
-      tile += q;
-    }
-    if (i < n) p.base[i] = run + before + incl - v;
-    run += tile;
-    __syncthreads();
-  }
-  if (t == 0) p.base[n] = run;
+  const long long total = scan_plane(p.rows, p.base, n, s_w);
+  if (threadIdx.x == 0) p.base[n] = (int)total;
 }
 
 __global__ __launch_bounds__(PF_THREADS) void pf_fill_kernel(const int2* __restrict__ verts, const int* __restrict__ ring_first,
@@ -197,10 +172,6 @@ __global__ __launch_bounds__(PF_THREADS) void pf_fill_kernel(const int2* __restr
   }
 }
 
-__global__ __launch_bounds__(256) void pf_zero64_kernel(long long* __restrict__ at, long n) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) at[i] = 0ll;
-}
-
 // The lanes of a wave hold consecutive pixels, mostly of one or two labels: one add per distinct value and wave.
 __global__ __launch_bounds__(256) void pf_census_kernel(const int* __restrict__ label, long n, int n_labels, long long* __restrict__ area) {
   const long stride = (long)gridDim.x * blockDim.x;
@@ -208,16 +179,9 @@ __global__ __launch_bounds__(256) void pf_census_kernel(const int* __restrict__ 
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (long t = 0; t < trips; ++t, i += stride) {
     const int v = i < n ? label[i] : 0;
-    bool todo = v >= 1 && v <= n_labels;
-    unsigned long long left = __ballot(todo);
-    while (left) {
-      const int leader = __ffsll((long long)left) - 1;
-      const int lv = __shfl(v, leader, 64);
-      const unsigned long long same = __ballot(todo && v == lv);
-      if ((threadIdx.x & 63) == leader) atomicAdd(reinterpret_cast<unsigned long long*>(area + (lv - 1)), (unsigned long long)__popcll(same));
-      if (todo && v == lv) todo = false;
-      left &= ~same;
-    }
+    for_each_wave_key(v, v >= 1 && v <= n_labels, [&](int lead, int lv, unsigned long long same) {
+      if ((threadIdx.x & 63) == lead) atomic_add64(area + (lv - 1), __popcll(same));
+    });
   }
 }
 
@@ -240,7 +204,7 @@ int launch_polygon_fill(const int* verts, const int* ring_first, const int* poly
   UNETDC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "polygon_fill: workspace must be 16-byte aligned");
   const PolyfillPlanes& p = lay.planes;
   const long n = (long)h * w;
-  hipLaunchKernelGGL(pf_clear_kernel, dim3(grid_for(n, 256 * 4, 4096)), dim3(256), 0, stream, labels_out, n);
+  launch_fill(labels_out, n, 0, grid_for(n, 256 * 4, 4096), stream);
   if (n_polys > 0) {
     const int2* v2 = reinterpret_cast<const int2*>(verts);
     hipLaunchKernelGGL(pf_items_kernel, dim3(grid_for(n_polys, 256 / 64, 4096)), dim3(256), 0, stream, v2, ring_first, poly_first_ring, poly_label,
@@ -259,7 +223,7 @@ int launch_label_census(const int* label, int h, int w, int n_labels, long long*
   UNETDC_REQUIRE(label && (area || n_labels == 0), "label_census: null pointer");
   if (n_labels == 0) return UNETDC_OK;
   const long n = (long)h * w;
-  hipLaunchKernelGGL(pf_zero64_kernel, dim3(grid_for(n_labels, 256, 1024)), dim3(256), 0, stream, area, (long)n_labels);
+  launch_fill(area, (long)n_labels, 0ll, grid_for(n_labels, 256, 1024), stream);
   hipLaunchKernelGGL(pf_census_kernel, dim3(grid_for(n, 256 * 4, 4096)), dim3(256), 0, stream, label, n, n_labels, area);
   return check_launch("label_census kernels");
 }

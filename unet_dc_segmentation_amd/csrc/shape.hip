@@ -4,20 +4,19 @@
 // atomics only: the result does not depend on the order in which anything runs.
 //
 //   label_props_init     sums 0, minima INT64_MAX, maxima -1 on the [SHAPE_QUANTITIES][max_out] output
-//   label_props_kernel   one wave per 64 consecutive pixels of a row.  Lanes that carry the same label next to each other
-//                        form a run (heads from a ballot of label[x] != label[x - 1]); the run is reduced inside the wave
-//                        and only its head lane issues global atomics:
+//   label_props_kernel   one wave per 64 consecutive pixels of a row (row_unit); lanes that carry the same label next to each
+//                        other form a run (wave_runs, wave_ops.h), and only its head lane issues global atomics:
 //                          coordinates  a run is the pixels x0 .. x0 + n - 1 of row y, so n, sum x and sum x^2 are closed
 //                                       forms of (x0, n): no cross-lane traffic at all, min_x = x0, max_x = x0 + n - 1
 //                          perimeter    one ballot per class, popcount under the run's lane mask
-//                          grey         segmented suffix reduction with __shfl_down (6 steps, a lane takes its partner's
-//                                       value only when the partner lies in the same run)
+//                          grey         segmented suffix reductions (run_sum, run_min, run_max)
 //                        A pixel's perimeter code needs the labels within two pixels of it.  They are read straight from
 //                        the label map (5.8 MB at 1040 x 1388: it stays in L2 / the Infinity Cache between the rows),
 //                        in two steps: the 4 neighbours decide whether the pixel is a border pixel at all; only border
 //                        pixels read the other 16 labels of the radius-2 diamond.  Background pixels, the majority, cost the
 //                        one coalesced load of their own label.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -32,10 +31,6 @@ __global__ void label_props_init_kernel(long long* __restrict__ out, int max_out
     const int q = (int)(i / max_out);
     out[i] = (q == Q_MINY || q == Q_MINX || q == Q_MING) ? SHAPE_MIN_INIT : (q == Q_MAXY || q == Q_MAXX || q == Q_MAXG) ? -1ll : 0ll;
   }
-}
-
-__device__ __forceinline__ void shape_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
 
 // perimeter code -> class: bit `code` of the class's mask (codes stay below 1 + 4 * 2 + 4 * 10 = 49)
@@ -84,58 +79,41 @@ __global__ __launch_bounds__(256) void label_props_kernel(const int* __restrict_
   const long units = (long)h * chunks;
   const long stride = (long)gridDim.x * 4;
   for (long u = (long)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += stride) {   // uniform within a wave
-    const int y = (int)(u / chunks), x = ((int)(u - (long)y * chunks) << 6) + lane;
-    const bool in = x < w;
-    const long i = (long)y * w + x;
+    const auto [y, x, in, i] = row_unit(u, chunks, w, lane);
     int k = in ? label[i] : 0;
     if (k < 0 || k > max_out) k = 0;                        // labels past the capacity are skipped, never written
-    const int prev = __shfl_up(k, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || k != prev);
     if (__ballot(k > 0) == 0ull) continue;                  // wave-uniform: nothing but background here
-    // the run of this lane ends one lane before the next head above it
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = above ? __ffsll((long long)above) : 64 - lane;     // lanes from this one to the end of its run
-    const int tail = lane + len - 1;
+    const WaveRuns r = wave_runs(k, lane);
     const int code = k > 0 ? perimeter_code(label, h, w, y, x, k) : 0;
     const unsigned long long c1 = __ballot((PERIM_CLASS1 >> code) & 1ull), c2 = __ballot((PERIM_CLASS2 >> code) & 1ull),
                              c3 = __ballot((PERIM_CLASS3 >> code) & 1ull);
     int sg = 0, sgg = 0, gmin = 0, gmax = 0;
     if (gray) {                                             // uniform
       const int g = in ? (int)gray[i] : 0;
-      sg = g, sgg = g * g, gmin = g, gmax = g;              // 64 * 255^2 < 2^23
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int a = __shfl_down(sg, o, 64), b = __shfl_down(sgg, o, 64), c = __shfl_down(gmin, o, 64),
-                  d = __shfl_down(gmax, o, 64);
-        if (lane + o <= tail) {
-          sg += a;
-          sgg += b;
-          gmin = min(gmin, c);
-          gmax = max(gmax, d);
-        }
-      }
+      sg = run_sum(g, r, lane), sgg = run_sum(g * g, r, lane);     // 64 * 255^2 < 2^23
+      gmin = run_min(g, r, lane), gmax = run_max(g, r, lane);
     }
-    if (k > 0 && ((heads >> lane) & 1ull)) {
-      const unsigned long long run = (len == 64 ? ~0ull : (1ull << len) - 1ull) << lane;
-      const long long n = len, x0 = x, yl = y;
+    if (k > 0 && r.head) {
+      const unsigned long long run = run_mask(r, lane);
+      const long long n = r.len, x0 = x, yl = y;
       const long long sx = n * x0 + n * (n - 1) / 2;
       const long long sxx = n * x0 * x0 + x0 * n * (n - 1) + (n - 1) * n * (2 * n - 1) / 6;
       long long* o = out + (k - 1);
       const long q = max_out;
-      shape_add(o + Q_SYY * q, yl * yl * n);
-      shape_add(o + Q_SXX * q, sxx);
-      shape_add(o + Q_SXY * q, yl * sx);
+      atomic_add64(o + Q_SYY * q, yl * yl * n);
+      atomic_add64(o + Q_SXX * q, sxx);
+      atomic_add64(o + Q_SXY * q, yl * sx);
       atomicMin(o + Q_MINY * q, yl);
       atomicMax(o + Q_MAXY * q, yl);
       atomicMin(o + Q_MINX * q, x0);
       atomicMax(o + Q_MAXX * q, x0 + n - 1);
       const int p1 = __popcll(c1 & run), p2 = __popcll(c2 & run), p3 = __popcll(c3 & run);
-      if (p1) shape_add(o + Q_P1 * q, p1);
-      if (p2) shape_add(o + Q_P2 * q, p2);
-      if (p3) shape_add(o + Q_P3 * q, p3);
+      if (p1) atomic_add64(o + Q_P1 * q, p1);
+      if (p2) atomic_add64(o + Q_P2 * q, p2);
+      if (p3) atomic_add64(o + Q_P3 * q, p3);
       if (gray) {
-        shape_add(o + Q_SG * q, sg);
-        shape_add(o + Q_SGG * q, sgg);
+        atomic_add64(o + Q_SG * q, sg);
+        atomic_add64(o + Q_SGG * q, sgg);
         atomicMin(o + Q_MING * q, (long long)gmin);
         atomicMax(o + Q_MAXG * q, (long long)gmax);
       }

@@ -25,6 +25,7 @@
 //                           flushes once with 64-bit global atomics.  Nothing waits for another workgroup.
 #include "hash32.h"
 #include "kernels.h"
+#include "wave_ops.h"
 #include "workspace.h"
 
 namespace unetdc {
@@ -117,13 +118,8 @@ __global__ __launch_bounds__(256) void spatial_window_count_kernel(const unsigne
   __shared__ int part[4];
   int c = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) c += window[i] != 0;
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int s = part[0] + part[1] + part[2] + part[3];
-    if (s) atomicAdd(out_a, s);
-  }
+  const int s = block_sum<256>(c, part);
+  if (threadIdx.x == 0 && s) atomicAdd(out_a, s);
 }
 
 int launch_droplet_points(const int* count, const int* area, const long long* sum_y, const long long* sum_x, int max_points,
@@ -162,22 +158,12 @@ __global__ __launch_bounds__(256) void spatial_window_rows_kernel(const unsigned
   }
 }
 
-// rowpre[1 .. h] holds the rows' counts on entry, the inclusive prefix on exit; rowpre[0] = 0
+// rowpre[1 .. h] holds the rows' counts on entry, the inclusive prefix on exit; rowpre[0] = 0.  The exclusive scan of the counts
+// written one place down is just that: rowpre[0 .. h) = the counts above a row, and the total goes to rowpre[h].
 __global__ __launch_bounds__(256) void spatial_window_scan_kernel(int h, RipleyPlanes p) {
-  __shared__ int part[256];
-  const int per = (h + 255) / 256;
-  const int y0 = threadIdx.x * per, y1 = y0 + per < h ? y0 + per : h;
-  int s = 0;
-  for (int y = y0; y < y1; ++y) s += p.rowpre[y + 1];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  int before = 0;
-  for (int t = 0; t < (int)threadIdx.x; ++t) before += part[t];
-  for (int y = y0; y < y1; ++y) {
-    before += p.rowpre[y + 1];
-    p.rowpre[y + 1] = before;
-  }
-  if (threadIdx.x == 0) p.rowpre[0] = 0;
+  __shared__ int s_w[4];
+  const long long total = scan_plane<256>(p.rowpre + 1, p.rowpre, h, s_w);
+  if (threadIdx.x == 0) p.rowpre[h] = (int)total;
 }
 
 // ---- the point sets -----------------------------------------------------------------------------------------------------------
@@ -330,12 +316,7 @@ __global__ __launch_bounds__(256) void spatial_pairs_kernel(const int* __restric
       if ((q << 6) > R) break;                                 // uniform
       int v = r <= R ? hist[r] : 0;
       if (r <= R) hist[r] = 0;                                 // for the wave's next i
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-      }
-      v += carry;
+      v = wave_incl_scan(v, lane) + carry;
       carry = __shfl(v, 63, 64);
       sum_all[q] += (unsigned)v;
       if (r <= ei) sum_pairs[q] += (unsigned)v;

@@ -12,10 +12,11 @@
 //   linear       the 8-bit bilinear v of mask_linear_kernel changes only where a tap changes: the pixel's level is the largest
 //                tap level L with v != 0 when exactly the taps of level >= L are set (four evaluations of the integer formula)
 //   histogram    per workgroup [2][K + 1] int32 in LDS; the lanes of a wave that share a bin send ONE add of their number
-//                (match by ballot, as clean_area_kernel: in a micrograph nearly every pixel is background at level 0); the
+//                (for_each_wave_key, wave_ops.h: in a micrograph nearly every pixel is background at level 0); the
 //                nonzero bins go out as 64-bit integer atomics.  Integers only: the result depends on no order.
 #include "kernels.h"
 #include "linear_u8.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -81,14 +82,9 @@ __global__ __launch_bounds__(SWEEP_THREADS) void thresh_sweep_kernel(const float
       }
       bin = (gt[i] != 0 ? K + 1 : 0) + lev;
     }
-    unsigned long long todo = __ballot(live);
-    while (todo) {                                  // uniform in the wave: todo comes from ballots
-      const int lead = __ffsll((long long)todo) - 1;
-      const int lead_bin = __shfl(bin, lead, 64);
-      const unsigned long long same = __ballot(live && bin == lead_bin);
+    for_each_wave_key(bin, live, [&](int lead, int lead_bin, unsigned long long same) {
       if (lane == lead) atomicAdd(&bins[lead_bin], __popcll(same));
-      todo &= ~same;
-    }
+    });
   }
   __syncthreads();
   for (int b = threadIdx.x; b < nbins; b += SWEEP_THREADS) {

@@ -3,7 +3,7 @@
 //
 //   ranks     value[ch][j] = the k_j-th smallest value of channel ch, k_j = max(1, ceil(p_j n / 10^6)), with below = #{v < value}
 //             and equal = #{v == value}.  Five launches, nothing returns to the host in between:
-//               win_zero_kernel        the counters (the workspace may hold anything)
+//               fill_kernel<int>       the counters: zeros (wave_ops.h; the workspace may hold anything)
 //               win_hist_kernel<.., 0> pass A: [c][256] histogram of the HIGH bytes
 //               win_select_hi_kernel   per (ch, j): the bin that holds rank k_j, the count below the bin, the rank inside it
 //               win_hist_kernel<.., 1> pass B: [nq][c][256] histograms of the LOW bytes of the values whose high byte is a
@@ -19,6 +19,7 @@
 //   window    t = min(max(v, lo), hi) - lo, dst = (510 t + d) / (2 d) with d = hi - lo > 0 (round half up of 255 t / d; below
 //             2^26), 0 for d <= 0; levels outside 0..65535 are clamped to it first.  Levels are read from device memory.
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace unetdc {
 
@@ -61,10 +62,6 @@ static Layout<WinPlanes> ranks_layout(int h, int w, int c, int nq, void* workspa
   return {true, cv.bytes(), p};
 }
 long u16_ranks_workspace_bytes(int h, int w, int c, int nq) { return ranks_layout(h, w, c, nq, nullptr).bytes; }
-
-__global__ void win_zero_kernel(int* __restrict__ a, int n) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) a[i] = 0;
-}
 
 // The eight keys a lane holds for one channel (a negative key counts nowhere) -> hist.  All 64 lanes call it together.
 __device__ __forceinline__ void win_add_keys(int* hist, const int (&key)[8], bool live, int lane) {
@@ -171,13 +168,7 @@ __device__ __forceinline__ bool win_wave_select(const int* __restrict__ hist, in
   int v[4], s = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q) { v[q] = hist[4 * lane + q]; s += v[q]; }
-  int incl = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  int e = incl - s;
+  int e = wave_incl_scan(s, lane) - s;
   bool found = false;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -345,7 +336,7 @@ int launch_u16_ranks(const unsigned short* src, int h, int w, int c, const int* 
   const WinPlanes p = lay.planes;
   const long npix = (long)h * w;
   const int counters = c * 256 * (1 + nq);          // hist_hi and hist_lo are neighbours in the layout
-  hipLaunchKernelGGL(win_zero_kernel, dim3(grid_for(counters, WIN_THREADS, 64)), dim3(WIN_THREADS), 0, stream, p.hist_hi, counters);
+  launch_fill(p.hist_hi, (long)counters, 0, grid_for(counters, WIN_THREADS, 64), stream);
   const dim3 grid(grid_for(npix / 8, WIN_THREADS, WIN_HIST_MAX_GROUPS)), block(WIN_THREADS);
   const int lds_hi = WIN_WAVES * c * 256 * 4, lds_lo = nq * c * 256 * 4;
   auto hist = [&](auto cn, auto pass) {
