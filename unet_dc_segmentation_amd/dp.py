@@ -254,8 +254,9 @@ def broadcast_scalar(value, device="cpu", src=0, group=None):
     return float(t.item())
 
 
-def init_from_env(backend=None):
-    """Initialise torch.distributed from the torchrun environment; returns (rank, local_rank, world)."""
+def init_from_env(backend=None, timeout=None):
+    """Initialise torch.distributed from the torchrun environment; returns (rank, local_rank, world).
+    timeout (a timedelta): the process group's, instead of torch's default (a test harness wants a short one)."""
     import os
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -267,5 +268,6 @@ def init_from_env(backend=None):
             backend = "nccl" if torch.cuda.is_available() else "gloo"
         if backend == "nccl":
             torch.cuda.set_device(local)
-        dist.init_process_group(backend=backend, rank=rank, world_size=world)
+        kw = {} if timeout is None else {"timeout": timeout}
+        dist.init_process_group(backend=backend, rank=rank, world_size=world, **kw)
     return rank, local, world
