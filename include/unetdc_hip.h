@@ -760,6 +760,55 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                            int32_t* out_cluster_size, unetdc_stream_t s);
 
 
+/* ---- droplets per cell: nearest-label territories and the per-cell table (cells.hip) -------------------
+ * unetdc_label_nearest: label ([h][w] int32; the seed pixels are the pixels q with 1 <= label[q] <= max_label, any other value
+ *   is not a seed; touching labels allowed), radius (0..32767 pixels, 0 = unbounded) -> for every pixel p, with (D, L) = the
+ *   lexicographic minimum over the seed pixels q of (|p - q|^2, label[q]) -- the nearest seed pixel wins, among equidistant
+ *   seed pixels the smallest label --: out_d2[p] = D, always the exact squared distance (below 2^30), and out_label[p] = L,
+ *   or 0 where radius > 0 and D > radius^2.  A seed pixel gets its own label and 0.  Without any seed every out_label is 0
+ *   and every out_d2 is UNETDC_EDT_INF.  out_label and out_d2 [h][w] int32, every pixel written; they and the workspace may
+ *   hold anything on entry, and nothing else is written.  Sides 1..16384, max_label >= 0; workspace:
+ *   unetdc_label_nearest_workspace(h, w) bytes (0 for a geometry the call would refuse), 4-byte aligned.  UNETDC_EINVAL before
+ *   any launch for a null pointer or a refused argument, UNETDC_EWORKSPACE for a workspace too small.  Launches on the given
+ *   stream only; no host wait, no allocation.  Integer minima defined per pixel: bitwise reproducible.
+ * unetdc_cell_table: droplet_label and cell_label ([h][w] int32 each; values outside 1..max_droplet and 1..max_cell are
+ *   background on their map), d2 ([h][w] int32, e.g. out_d2 of unetdc_label_nearest of the nuclei; may be NULL) ->
+ *   out_droplet[UNETDC_CELL_DROPLET_QUANTITIES][max_droplet] int32, row j of droplet k at out_droplet[j * max_droplet + k - 1]:
+ *     0 cell     the cell label that carries the most pixels of the droplet, the smallest label at ties; 0 if no pixel of
+ *                the droplet lies on a cell
+ *     1 n_in     pixels of the droplet on that cell
+ *     2 n_cells  distinct cells the droplet has a pixel on
+ *     3 n_out    pixels of the droplet on cell label 0
+ *     4 area     pixels of the droplet
+ *     5 min_d2   the minimum of d2 over the droplet's pixels; UNETDC_EDT_INF when d2 is NULL or the droplet has no pixel
+ *   out_cell[UNETDC_CELL_QUANTITIES][max_cell] int64, row j of cell c at out_cell[j * max_cell + c - 1]:
+ *     0 area        pixels of the cell
+ *     1 n_border    pixels of the cell on the first or last row or column of the image
+ *     2 fg_px       pixels of the cell that carry a droplet label (pixel-exact, independent of the assignment)
+ *     3 n_droplets  droplets whose row 0 is this cell
+ *     4 S_area      the sum of area over those droplets
+ *     5 S_area2     the sum of area^2 over those droplets
+ *     6 max_area    the largest area among those droplets, 0 without one
+ *     7 nucleus_px  pixels of the cell with d2 == 0; 0 when d2 is NULL
+ *   Every row is written for all max_droplet / max_cell entries.  *out_needed = the number of distinct (droplet, cell) pairs
+ *   that share a pixel; if there are more than max_pairs of them, *out_needed = max_pairs + 1 and all other outputs are
+ *   unspecified: repeat with more room (h * w always suffices).  max_droplet = 0 and max_cell = 0 are allowed (the output of
+ *   that side may then be NULL).  Nothing but the outputs and the workspace is written; both may hold anything on entry.
+ *   Sides 1..16384; max_droplet, max_cell, max_pairs >= 0; workspace: unetdc_cell_table_workspace(h, w, max_droplet,
+ *   max_cell, max_pairs) bytes (0 for arguments the call would refuse; max_cell does not enter it), 8-byte aligned like
+ *   out_cell.  Launches on the given stream only; no host wait, no allocation.  Integer atomics, and an argmax on unique
+ *   keys: bitwise reproducible. */
+#define UNETDC_CELL_DROPLET_QUANTITIES 6
+#define UNETDC_CELL_QUANTITIES 8
+int64_t unetdc_label_nearest_workspace(int h, int w);
+int unetdc_label_nearest(const int32_t* label, int max_label, int h, int w, int radius, void* workspace, int64_t workspace_bytes,
+                         int32_t* out_label, int32_t* out_d2, unetdc_stream_t s);
+int64_t unetdc_cell_table_workspace(int h, int w, int max_droplet, int max_cell, int max_pairs);
+int unetdc_cell_table(const int32_t* droplet_label, int max_droplet, const int32_t* cell_label, int max_cell, const int32_t* d2,
+                      int h, int w, void* workspace, int64_t workspace_bytes, int32_t* out_needed, int max_pairs,
+                      int32_t* out_droplet, int64_t* out_cell, unetdc_stream_t s);
+
+
 /* ---- Ripley's K of the droplet centroids with simulated patterns (spatial.hip; the definition is DESIGN.md section 26) --------
  * unetdc_droplet_points: the droplet table of unetdc_ccl_stats (*count droplets: area, sum of rows, sum of columns; device
  *   memory) -> the centroid pixels y = (2 sum_y + area) div (2 area), x likewise, of the droplets whose pixel lies in the

@@ -26,6 +26,7 @@ and a few integers per droplet come back:
     --outlines        unet_dc_segmentation_amd/outlines.py      csrc/outlines.hip       CPU: utils/droplet_outlines.py
     --spatial_stats   unet_dc_segmentation_amd/spatial.py       csrc/spatial.hip        CPU: utils/spatial_stats.py
     --gt_polygons     unet_dc_segmentation_amd/polygons.py      csrc/polyfill.hip       CPU: utils/polygon_masks.py
+    --cell_dir, --nuclei_dir  unet_dc_segmentation_amd/cells.py (droplets.py)  csrc/cells.hip  CPU: utils/droplet_cells.py
     --intensity_window, --intensity_levels (in front of the preprocessing)
                       unet_dc_segmentation_amd/window.py        csrc/window.hip         CPU: utils/intensity_window.py
 
@@ -141,6 +142,7 @@ class Run:
     spatial: dict | None = None        # spatial_options(); its "table" / "rows" collect spatial_stats.csv and spatial_per_image.csv
     outlines: dict | None = None       # --outlines: {"dir", "images", "jobs"}: outlines/NAME.geojson and what outlines_coco.json collects
     intensity: dict | None = None      # --intensity_window / --intensity_levels: {"spec", "records"}: intensity_per_image.csv
+    cells: dict | None = None          # built in main(): the flags, the files; its "tables" / "rows" collect cells.csv and cells_per_image.csv
 
     @property
     def keep_rgb(self):
@@ -152,7 +154,7 @@ class Run:
         """Whether the forward also keeps the minimum and maximum over the variants: only with both --tta and --confidence."""
         return self.tta is not None and self.confidence is not None
 
-    def droplet_options(self, labels, shape, confidence=False, hull=False):
+    def droplet_options(self, labels, shape, confidence=False, hull=False, cells=False):
         """The device droplet stage of this run.  Without a split depth the label map comes from the labelling of the shape
         route (unetdc_ccl_labels), so asking for labels selects that route, unless a stage that reads the label map
         (DropletOptions.label_map) has selected it already."""
@@ -160,7 +162,7 @@ class Run:
         conf = self.confidence if confidence else None
         opts = DropletOptions(split_depth=self.split_depth, shape=shape, thresh_low=c["low"], max_hole_area=c["holes"],
                               neighbors=self.neighbors, confidence=None if conf is None else conf["band"],
-                              confidence_maps=conf is not None and conf["maps"], hull=hull)
+                              confidence_maps=conf is not None and conf["maps"], hull=hull, cells=cells)
         route = labels and self.split_depth is None and not opts.label_map
         return dataclasses.replace(opts, labels=labels, shape=shape or route)
 
@@ -179,6 +181,8 @@ class Batch:
     rgbs: list = dataclasses.field(default_factory=list)       # --density_maps, --diff_maps: the decoded image (a device tensor on the GPU)
     gt_items: list = dataclasses.field(default_factory=list)   # --gt_dir: the decoded annotations
     windows: list = dataclasses.field(default_factory=list)    # --spatial_window_dir: the decoded windows, uint8 {0, 1}
+    cells: list = dataclasses.field(default_factory=list)      # --cell_dir / --nuclei_dir: the decoded (label map, ids), then (cell_maps) the cells
+    cell_ids: list = dataclasses.field(default_factory=list)   # per image the file's own cell numbers, None where they are 1..K already
 
 
 def predict_tiled_image(model, im, run):
@@ -244,16 +248,18 @@ def _components(bin_mask, min_area):
     return area, cen[:, 0], cen[:, 1]
 
 
-def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None, confidence=None, hull=False):
+def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, labels=False, neighbors=None, confidence=None, hull=False,
+                 cells=None):
     """CPU path: the record that droplets.mask_and_droplets_batch returns per image, in host arrays, from the uint8 mask at
     the image's size.  split_depth: the split droplets (utils/droplet_split.py); shape: the integers of
     utils.droplet_shape.label_props_numpy on the label map and the grey plane, centroids then the integer sums over the
     area as on the device; labels: the int32 label map whose numbers are the rows of the table; neighbors (a radius): the
     record of utils.droplet_neighbors.neighbors_numpy on the label map, centroids from the integer sums as well; confidence
     (the keywords probs, thresh, band, lo, hi, maps of utils.droplet_confidence.confidence_numpy): its record on the label map;
-    hull: the integers of utils.droplet_hull.label_hull_numpy on the label map."""
+    hull: the integers of utils.droplet_hull.label_hull_numpy on the label map; cells ((cell label map, its largest label, the d2
+    plane or None), as cell_maps makes them): the record of utils.droplet_cells.cells_record on the label map."""
     lab, rec = None, {}
-    label_map = shape or neighbors is not None or confidence is not None or hull      # a stage reads it, as DropletOptions.label_map
+    label_map = shape or neighbors is not None or confidence is not None or hull or cells is not None   # a stage reads it, as DropletOptions.label_map
     if split_depth is not None:
         from utils.droplet_split import half_pixels, split_labels
         lab, area, sy, sx, _ = split_labels(bin_mask, half_pixels(split_depth), min_area)
@@ -278,9 +284,13 @@ def droplets_cpu(bin_mask, min_area, split_depth=None, shape=False, gray=None, l
         if hull:
             from utils.droplet_hull import label_hull_numpy
             rec["hull"] = label_hull_numpy(lab, len(area))
+        if cells is not None:
+            from utils.droplet_cells import cells_record
+            rec["cells"] = cells_record(lab, len(area), *cells)
         d = np.maximum(area, 1)
         cen_row, cen_col = sy.astype(np.float64) / d, sx.astype(np.float64) / d
-    return Droplets(bin_mask, area, cen_row, cen_col, labels=lab, **rec)
+    more = {"cells": rec.pop("cells")} if "cells" in rec else {}
+    return Droplets(bin_mask, area, cen_row, cen_col, labels=lab, **rec).with_records(**more)
 
 
 def quantify_shape(bin_mask, min_area, px_per_um, split_depth, gray):
@@ -414,6 +424,64 @@ def add_confidence_outputs(run, df, d, filename, name):
         if rec.get(key) is not None:
             run.submit(_write_map, _host(rec[key]), run.out_dir / f"{name}_{suffix}.png")
     return df
+
+
+def decode_cells(path, as_labels, min_area):
+    """--cell_dir / --nuclei_dir: one mask file -> the int32 label map of its objects: with --cell_labels the label image as it
+    is (decode_gt), else the 4-connected components of at least min_area pixels of the binary mask, numbered in raster order.
+    -> (the map, ids): a label image whose ids have gaps (one object numbered 60000) is renumbered 1..K in ascending order, so that
+    the per-cell buffers are sized by the cells there are, and ids [K] holds the file's own numbers for the tables; None otherwise."""
+    item = decode_gt(path, as_labels)
+    if not as_labels:
+        from utils.droplet_match import gt_labels_numpy
+        return gt_labels_numpy(item, min_area), None
+    ids = np.unique(item[item > 0])
+    if len(ids) == 0 or len(ids) == int(ids[-1]):
+        return item, None
+    return np.where(item > 0, np.searchsorted(ids, item) + 1, 0).astype(np.int32), ids.astype(np.int64)
+
+
+def cell_maps(run, batch, on_device):
+    """--cell_dir / --nuclei_dir: the decoded label maps of the batch -> per image (cell label map, its largest label, the d2 plane
+    or None): DEVICE tensors as cells.CellMap when the run is on the device, host arrays otherwise.  Given cells are taken as they
+    are; nuclei become their nearest-nucleus territories, cut at --cell_radius, and bring the squared distance to the nucleus."""
+    radius, nuclei, out = run.cells["radius"], run.cells["mode"] == "nuclei", []
+    batch.cell_ids = [ids for _, ids in batch.cells]
+    for lab, _ in batch.cells:
+        top, d2 = max(int(lab.max(initial=0)), 0), None
+        if on_device:
+            from unet_dc_segmentation_amd.cells import CellMap, nearest_label
+            lab = torch.from_numpy(np.ascontiguousarray(lab)).to(DEVICE)
+            if nuclei:
+                lab, d2 = nearest_label(lab, top, radius)
+            out.append(CellMap(lab, top, d2))
+        else:
+            if nuclei:
+                from utils.droplet_cells import nearest_label_numpy
+                lab, d2 = nearest_label_numpy(lab, top, radius)
+            out.append((lab, top, d2))
+    batch.cells = out
+
+
+def _write_labels16(labels, path):
+    from utils.droplet_split import labels_u16
+    Image.fromarray(labels_u16(labels)).save(str(path))
+
+
+def add_cell_outputs(run, df, d, filename, name, cells, ids=None):
+    """--cell_dir / --nuclei_dir: the columns of utils.droplet_cells.cell_columns behind the droplet table's own, this image's rows
+    of cells.csv and of cells_per_image.csv, with nuclei the territories as a 16-bit label PNG through the writer pool -> (the
+    table, the numbers its row of summary_per_image.csv gains).  ids: the file's own cell numbers where decode_cells renumbered them."""
+    from utils import droplet_cells as dcell
+    rec = d.cells
+    if not df.empty:
+        df = pd.concat([df, pd.DataFrame(dcell.cell_columns(rec, run.px_per_um, ids), index=df.index)], axis=1)
+    run.cells["tables"].append(pd.DataFrame(dcell.cells_table(filename, rec, run.px_per_um, ids)))
+    more = dcell.per_image_summary(rec)
+    run.cells["rows"].append({"filename": filename, **more})
+    if run.cells["dir"] is not None:
+        run.submit(_write_labels16, dcell.original_ids(_host(cells[0]), ids), run.cells["dir"] / f"{name}_cells.png")
+    return df, more
 
 
 def add_hull_outputs(run, df, d):
@@ -593,19 +661,23 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
     With --droplet_hull (never while sweeping) every Droplets carries the integers of DESIGN.md section 24.
     With --outlines (never while sweeping) every Droplets carries its label map, which finish_batch hands to the outline stage.
     With --confidence (never while sweeping) every Droplets carries the record of DESIGN.md section 23; envelope: the (lo, hi) maps
-    of --tta, shaped like probs."""
+    of --tta, shaped like probs.  With --cell_dir / --nuclei_dir (never while sweeping) every Droplets carries the record of DESIGN.md
+    section 31 against batch.cells, which cell_maps has prepared."""
     gt, hws = run.gt, [m[1] for m in batch.meta]
     radius = run.boundary["R"] if run.boundary is not None and not sweeping else None
     want_labels = gt is not None or run.split_depth is not None or (run.outlines is not None and not sweeping)
     shape = run.shape and not sweeping
     conf = run.confidence if not sweeping else None
     hull = run.hull is not None and not sweeping
+    cells = batch.cells if run.cells is not None and not sweeping else None
     if probs.is_cuda:
         from unet_dc_segmentation_amd.droplets import mask_and_droplets_batch
         gray = [torch.from_numpy(g).to(DEVICE) for g in batch.grays] if shape else None   # up behind the network's launches
         more = {} if conf is None or envelope is None else {"envelope": tuple(e[:, 0] for e in envelope)}
+        if cells is not None:
+            more["cells"] = cells
         out, sums = mask_and_droplets_batch(probs[:, 0], thresh, hws, run.min_area, keep_sums=True, gray=gray,
-                                            options=run.droplet_options(want_labels, shape, conf is not None, hull), **more)
+                                            options=run.droplet_options(want_labels, shape, conf is not None, hull, cells is not None), **more)
         if gt is None:
             return out, None, sums
         from unet_dc_segmentation_amd.evaluate import boundary_batch, match_batch
@@ -625,7 +697,8 @@ def droplets_and_matches(run, batch, probs, thresh, sweeping=False, envelope=Non
         if conf is not None:
             lo, hi = (None, None) if envelope is None else (e[i, 0].numpy() for e in envelope)
             ckw = {"probs": p[i], "thresh": thresh, "band": conf["band"], "lo": lo, "hi": hi, "maps": conf["maps"]}
-        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors, ckw, hull)
+        d = droplets_cpu(mask, run.min_area, run.split_depth, shape, batch.grays[i] if shape else None, want_labels, run.neighbors, ckw, hull,
+                         None if cells is None else cells[i])
         d.clean_counts = np.asarray(counts, np.int64)
         out.append(d)
     if gt is None:
@@ -681,6 +754,8 @@ def finish_batch(run, batch, probs):
         probs, envelope = probs[0], probs[1:]
     if run.gt is not None and run.gt.get("polygons") is not None:
         rasterize_gt(run, batch, probs.is_cuda)           # --gt_polygons: label maps from here on, as --gt_labels decodes them
+    if run.cells is not None:
+        cell_maps(run, batch, probs.is_cuda)              # --nuclei_dir: the territories, ahead of the droplet stage on its stream
     if run.sweep is not None:                           # --thresh_sweep: the raw mask at every threshold, pooled
         sweep_step(run, batch, probs)
     out, mres, sums = droplets_and_matches(run, batch, probs, run.thresh, envelope=envelope)
@@ -716,6 +791,9 @@ def finish_batch(run, batch, probs):
         if orecs is not None:
             df, outline_more = add_outline_outputs(run, df, d, orecs[i], filename, name, hw)
             more = {**more, **outline_more}
+        if run.cells is not None:
+            df, cell_more = add_cell_outputs(run, df, d, filename, name, batch.cells[i], batch.cell_ids[i])
+            more = {**more, **cell_more}
         if run.clean is not None:
             from utils.droplet_clean import COUNT_NAMES
             run.clean["rows"].append({"filename": filename, **{k: int(v) for k, v in zip(COUNT_NAMES, d.clean_counts)}})
@@ -878,6 +956,20 @@ def build_parser():
     p.add_argument("--spatial_window_dir", metavar="D",
                    help="observation windows of --spatial_stats: the window of NAME.ext is D/NAME.<image suffix>, nonzero = "
                         "inside, of its image's size; without it the window is the whole image")
+    p.add_argument("--cell_dir", metavar="C",
+                   help="droplets per cell, the cells given: the mask of NAME.ext is C/NAME.<image suffix> (the rule of --gt_dir), a "
+                        "binary mask whose 4-connected components of at least --cell_min_area pixels are the cells, or with "
+                        "--cell_labels a label image.  Adds cell, cell_overlap_frac, n_cells, outside_cells to the droplet tables, "
+                        "writes cells.csv and cells_per_image.csv and adds the latter's columns to summary_per_image.csv")
+    p.add_argument("--nuclei_dir", metavar="N",
+                   help="droplets per cell, the nuclei given (read like --cell_dir): the cells are the territories of the nearest "
+                        "nucleus, cut at --cell_radius; also nucleus_gap_px per droplet, nucleus_area_px per cell and "
+                        "cell_territories/NAME_cells.png (16-bit labels)")
+    p.add_argument("--cell_radius", type=int, metavar="R",
+                   help="with --nuclei_dir: pixels further than R from every nucleus belong to no cell (default 0: unbounded)")
+    p.add_argument("--cell_min_area", type=int, default=1, help="ignore cells / nuclei of a binary mask smaller than this (pixels^2)")
+    p.add_argument("--cell_labels", action="store_true",
+                   help="the files of --cell_dir / --nuclei_dir are label images (16-bit, or any integer image), taken as they are")
     p.add_argument("--split_depth", type=float, default=2.0,
                    help="depth of the dip, in pixels, that separates two droplets under --split_touching (a multiple of 0.5)")
     return p
@@ -1014,6 +1106,11 @@ def main(argv=None):
         parser.error("--diff_maps compares against annotated masks: it needs --gt_dir")
     if args.diff_maps is not None and args.diff_maps < 1:
         parser.error("--diff_maps MIN_AREA: MIN_AREA is a number of pixels, at least 1")
+    from utils import droplet_cells as dcell
+    try:
+        cell_mode = dcell.check_flags(args.cell_dir, args.nuclei_dir, args.cell_radius, args.cell_labels)
+    except ValueError as e:
+        parser.error(str(e))
     in_dir, out_dir = Path(args.img_dir), Path(args.out_dir)
     try:                                                 # checked before any image, and before any output directory exists
         spec = iw.spec_from_flags(args.intensity_window, args.intensity_levels, args.page)
@@ -1047,6 +1144,12 @@ def main(argv=None):
         gt = {"files": find_gt_files(images, args.gt_dir), "min_area": args.gt_min_area, "labels": args.gt_labels}
     elif args.gt_polygons:                               # every polygon file is there (COCO: read, and of its image's size), or nothing runs
         gt = {"polygons": find_gt_polygons(images, args.gt_polygons), "min_area": 1, "labels": True, "features": 0, "dropped": 0}
+    cells = None
+    if cell_mode is not None:                            # every mask is there and of its image's size, or nothing runs
+        flag = "--cell_dir" if cell_mode == "cells" else "--nuclei_dir"
+        cells = {"mode": cell_mode, "files": find_gt_files(images, args.cell_dir or args.nuclei_dir, flag, "cell mask" if cell_mode == "cells" else "nuclei mask"),
+                 "labels": args.cell_labels, "min_area": args.cell_min_area, "radius": args.cell_radius or 0,
+                 "dir": out_dir / "cell_territories" if cell_mode == "nuclei" else None, "tables": [], "rows": []}
     spatial = spatial_options(args, images)
     mask_dir = out_dir / "predicted_masks"
     overlay_dir = out_dir / "overlays" if args.save_overlays else None
@@ -1071,6 +1174,8 @@ def main(argv=None):
     if args.outlines:
         outlines = {"dir": out_dir / "outlines", "images": [], "jobs": []}
         outlines["dir"].mkdir(exist_ok=True)
+    if cells is not None and cells["dir"] is not None:
+        cells["dir"].mkdir(exist_ok=True)
     model = load_model(args.ckpt_path, args.dtype)
     # File decode runs ahead of the device and the per-image writes behind it, in two small thread pools (both are
     # zlib-bound and release the GIL); the order of the rows in the summary files is the order of `images` as before.
@@ -1084,7 +1189,7 @@ def main(argv=None):
                   shape=args.droplet_shape, clean=clean, sweep=sweep, tile=tile, tta=tta, density=density, gt=gt, out_dir=out_dir,
                   mask_dir=mask_dir, overlay_dir=overlay_dir, writers=(wr_pool, deque(), 4 * max(1, args.batch)),
                   neighbors=args.neighbors, boundary=boundary, confidence=confidence, hull=hull, diff=diff,
-                  spatial=spatial, outlines=outlines, intensity=intensity)
+                  spatial=spatial, outlines=outlines, intensity=intensity, cells=cells)
         ahead = deque()
         it = iter(images)
 
@@ -1097,12 +1202,13 @@ def main(argv=None):
                               None if gt is None else dec_pool.submit(decode_gt_polygons, gt["polygons"][str(nxt)]) if "polygons" in gt
                               else dec_pool.submit(decode_gt, gt["files"][str(nxt)], gt["labels"]),
                               None if spatial is None or spatial["files"] is None
-                              else dec_pool.submit(decode_gt, spatial["files"][str(nxt)], False)))
+                              else dec_pool.submit(decode_gt, spatial["files"][str(nxt)], False),
+                              None if cells is None else dec_pool.submit(decode_cells, cells["files"][str(nxt)], cells["labels"], cells["min_area"])))
 
         refill()
         batch = Batch()
         while ahead:
-            img, fut, gt_fut, win_fut = ahead.popleft()
+            img, fut, gt_fut, win_fut, cell_fut = ahead.popleft()
             refill()
             im = fut.result()
             if intensity is not None:                    # the windowed 8-bit image stands for the original from here on
@@ -1115,6 +1221,8 @@ def main(argv=None):
                 batch.gt_items.append(gt_fut.result())
             if win_fut is not None:
                 batch.windows.append(win_fut.result())
+            if cell_fut is not None:
+                batch.cells.append(cell_fut.result())
             if tile is not None:                         # native size: one map per image, the stages on a batch of one
                 probs, rgb = predict_tiled_image(model, _host(im), run)
                 batch.rgbs.append(rgb)
@@ -1162,6 +1270,11 @@ def main(argv=None):
         from utils import spatial_stats as ss
         pd.DataFrame(spatial["table"], columns=ss.table_columns(run.px_per_um)).to_csv(out_dir / "spatial_stats.csv", index=False)
         pd.DataFrame(spatial["rows"], columns=ss.IMAGE_COLUMNS).to_csv(out_dir / "spatial_per_image.csv", index=False)
+    if cells is not None:
+        tables = [t for t in cells["tables"] if len(t)] or cells["tables"][:1]
+        if tables:
+            pd.concat(tables, ignore_index=True).to_csv(out_dir / "cells.csv", index=False)
+        pd.DataFrame(cells["rows"], columns=("filename",) + dcell.SUMMARY_NAMES).to_csv(out_dir / "cells_per_image.csv", index=False)
     if outlines is not None:                             # one COCO file for the run: annotation ids count through the images
         import json
         anns = [a for job in outlines["jobs"] for a in job.result()]

@@ -7,6 +7,7 @@ mask PNG + CSV writes) on N synthetic 1040 x 1388 micrographs written as PNG fil
                                   [--boundary[=R]] [--boundary_tol=T,T...] [--confidence[=BAND]] [--confidence_maps]
                                   [--droplet_hull[=S]] [--diff_maps[=MIN_AREA]] [--spatial_stats[=R]] [--spatial_sims=S]
                                   [--outlines] [--deep] [--intensity_window[=PLO,PHI]] [--intensity_levels=LO,HI]
+                                  [--nuclei[=N]] [--cell_radius=R]
 --density_maps: the density arm (ROI, radial and spatial maps on the device, two heat-map PNGs per image).
 --split_touching: the split arm (distance transform, basins and merging on the device, one label PNG per image; default depth).
 --droplet_shape: the shape arm (label map, per-droplet shape and intensity integers on the device, the extra CSV columns).
@@ -39,7 +40,10 @@ filled on the device); --gt_labels: its yardstick, the same annotations as the 1
 (--gt_dir DIR --gt_labels).  Both imply --gt.
 --deep: the files are 16-bit grey PNGs (the micrograph's grey x 16 plus four bits of noise, a 12-bit camera's range);
 --intensity_window or --intensity_window=PLO,PHI, --intensity_levels=LO,HI: passed through to the script (the window arm: ranks
-and the window to 8 bits on the device, intensity_per_image.csv).  --deep without a window flag is the clipped decode."""
+and the window to 8 bits on the device, intensity_per_image.csv).  --deep without a window flag is the clipped decode.
+--nuclei or --nuclei=N, --cell_radius=R: the droplets-per-cell arm (--nuclei_dir: N seeded discs per image, default 50, as binary
+masks; their territories and the per-cell table on the device, the extra CSV columns, cells.csv, cells_per_image.csv and one
+16-bit territory PNG per image)."""
 import os
 import sys
 import tempfile
@@ -77,6 +81,8 @@ gt = gt or bool(df_argv)
 sp_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--spatial_stats", "--spatial_sims", "--spatial_seed")]
 ol_argv = [a for a in sys.argv[1:] if a == "--outlines"]
 iw_argv = [a for a in sys.argv[1:] if a.split("=")[0] in ("--intensity_window", "--intensity_levels")]
+nuc_argv = [a for a in sys.argv[1:] if a.split("=")[0] == "--nuclei"]
+cell_argv = [a.replace("=", " ").split() for a in sys.argv[1:] if a.split("=")[0] == "--cell_radius"]
 deep = "--deep" in sys.argv
 gt_polygons, gt_label_files = "--gt_polygons" in sys.argv, "--gt_labels" in sys.argv
 gt = gt or gt_polygons or gt_label_files
@@ -120,6 +126,15 @@ with tempfile.TemporaryDirectory() as d:
         for i, im in enumerate(imgs):
             Image.fromarray((im[..., 0] > 125).astype(np.uint8) * 255).save(os.path.join(gtd, f"img_{i:04d}.png"))
         gt_argv = ["--gt_dir", gtd, "--gt_min_area", "4"]
+    if nuc_argv:                                          # seeded discs of radius 12, one binary mask per image
+        from tools.cells_bench import nuclei
+        nd = os.path.join(d, "nuclei")
+        os.makedirs(nd)
+        n_nuclei = int(nuc_argv[0].split("=")[1]) if "=" in nuc_argv[0] else 50
+        masks = [Image.fromarray((nuclei(n_nuclei, seed) > 0).astype(np.uint8) * 255) for seed in range(8)]
+        for i in range(n):
+            masks[i % 8].save(os.path.join(nd, f"img_{i:04d}.png"))
+        gt_argv += ["--nuclei_dir", nd] + [v for a in cell_argv for v in a]
     torch.manual_seed(0)
     m = UNetDC(in_channels=3, out_channels=1)
     if torch.cuda.is_available():                         # calibrate the head bias so that ~10 % of the pixels are "droplet"
@@ -142,4 +157,4 @@ with tempfile.TemporaryDirectory() as d:
     t0 = time.perf_counter()
     qdb.main(argv)
     dt = time.perf_counter() - t0
-    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{' --gt_polygons' if gt_polygons else ' --gt_labels' if gt_label_files else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''}{', 16-bit files' if deep else ''}{', ' + ' '.join(iw_argv) if iw_argv else ''})")
+    print(f"quantify_droplets_batch.py end to end: {n} files in {dt:.2f} s = {n / dt:.1f} images/s ({dtype}, device {qdb.DEVICE}{', density maps' if density else ''}{', split touching' if split else ''}{', droplet shape' if shape else ''}{', gt matching' if gt else ''}{' --gt_polygons' if gt_polygons else ' --gt_labels' if gt_label_files else ''}{', mask cleaning' if clean_argv else ''}{', threshold sweep' if sweep_argv else ''}{', tiled ' + ' '.join(tile_argv) if tile_argv else ''}{', ' + tta_argv[0] if tta_argv else ''}{', ' + nb_argv[0] if nb_argv else ''}{', ' + bd_argv[0] if bd_argv else ''}{', ' + ' '.join(cf_argv) if cf_argv else ''}{', ' + hl_argv[0] if hl_argv else ''}{', ' + df_argv[0] if df_argv else ''}{', ' + ' '.join(sp_argv) if sp_argv else ''}{', --outlines' if ol_argv else ''}{', 16-bit files' if deep else ''}{', ' + ' '.join(iw_argv) if iw_argv else ''}{', ' + ' '.join(nuc_argv + [' '.join(a) for a in cell_argv]) if nuc_argv else ''})")

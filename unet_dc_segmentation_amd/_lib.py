@@ -118,6 +118,10 @@ SIGNATURES = {
     "unetdc_boundary_distances": (I, [P, I, P, I, I, I, I, P, L, P, P, P, P, P]),
     "unetdc_label_neighbors_workspace": (L, [I, I, I, I]),
     "unetdc_label_neighbors": (I, [P, I, I, I, I, P, L, P, P, P, P, I, P, P, P, P, P, P]),
+    "unetdc_label_nearest_workspace": (L, [I, I]),
+    "unetdc_label_nearest": (I, [P, I, I, I, I, P, L, P, P, P]),
+    "unetdc_cell_table_workspace": (L, [I, I, I, I, I]),
+    "unetdc_cell_table": (I, [P, I, P, I, P, I, I, P, L, P, I, P, P, P]),
     "unetdc_ripley_workspace": (L, [I, I, I, I, I]),
     "unetdc_droplet_points": (I, [P, P, P, P, I, P, I, I, P, P, P, P]),
     "unetdc_ripley_counts": (I, [P, P, P, I, P, I, I, I, I, U, P, L, P, P, P, P]),

@@ -8,7 +8,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["abi.hip", "igemm_conv.hip", "igemm_dma.hip", "igemm_dma16.hip", "igemm_halo.hip", "igemm_lattice.hip", "wgrad.hip", "wgrad_dma.hip", "wgrad_fused.hip", "wgrad_rect.hip", "convt_wgrad.hip", "first_conv.hip", "first_conv_mfma.hip", "partials.hip", "batchnorm.hip", "head.hip", "pack.hip", "loss.hip", "optim.hip", "ccl.hip", "split.hip", "shape.hip", "confidence.hip", "hull.hip", "outlines.hip", "polyfill.hip", "match.hip", "neighbors.hip", "spatial.hip", "boundary.hip", "diffmap.hip", "clean.hip", "sweep.hip", "tile.hip", "tta.hip", "preprocess.hip", "window.hip", "augment.hip", "crop.hip", "density.hip", "border.hip"]
+SOURCES = ["abi.hip", "igemm_conv.hip", "igemm_dma.hip", "igemm_dma16.hip", "igemm_halo.hip", "igemm_lattice.hip", "wgrad.hip", "wgrad_dma.hip", "wgrad_fused.hip", "wgrad_rect.hip", "convt_wgrad.hip", "first_conv.hip", "first_conv_mfma.hip", "partials.hip", "batchnorm.hip", "head.hip", "pack.hip", "loss.hip", "optim.hip", "ccl.hip", "split.hip", "shape.hip", "confidence.hip", "hull.hip", "outlines.hip", "polyfill.hip", "match.hip", "neighbors.hip", "cells.hip", "spatial.hip", "boundary.hip", "diffmap.hip", "clean.hip", "sweep.hip", "tile.hip", "tta.hip", "preprocess.hip", "window.hip", "augment.hip", "crop.hip", "density.hip", "border.hip"]
 HEADERS = ["common.h", "kernels.h", "workspace.h", "partials.h", "bn_bwd_terms.h", "ccl_uf.h", "pair_table.h", "wave_ops.h", "lds_dma.h", "wgrad_frag.h", "igemm_epilogue.h", "igemm_epilogue16.h", "gather_index.h", "linear_u8.h", "hash32.h", os.path.join("..", "..", "include", "unetdc_hip.h")]
 OUT = os.path.join(HERE, "libunetdc_hip.so")
 

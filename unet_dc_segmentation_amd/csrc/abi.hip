@@ -690,6 +690,27 @@ int unetdc_label_neighbors(const int32_t* label, int max_label, int h, int w, in
                                 max_pairs, out_nn_label, out_nn_d2, out_degree, out_cluster, out_cluster_size, (hipStream_t)s);
 }
 
+static_assert(UNETDC_CELL_DROPLET_QUANTITIES == CELL_DROPLET_QUANTITIES && UNETDC_CELL_QUANTITIES == CELL_QUANTITIES,
+              "unetdc_cell_table output rows");
+
+int64_t unetdc_label_nearest_workspace(int h, int w) { return label_nearest_workspace_bytes(h, w); }
+
+int unetdc_label_nearest(const int32_t* label, int max_label, int h, int w, int radius, void* workspace, int64_t workspace_bytes,
+                         int32_t* out_label, int32_t* out_d2, unetdc_stream_t s) {
+  return launch_label_nearest(label, max_label, h, w, radius, workspace, (long)workspace_bytes, out_label, out_d2, (hipStream_t)s);
+}
+
+int64_t unetdc_cell_table_workspace(int h, int w, int max_droplet, int max_cell, int max_pairs) {
+  return cell_table_workspace_bytes(h, w, max_droplet, max_cell, max_pairs);
+}
+
+int unetdc_cell_table(const int32_t* droplet_label, int max_droplet, const int32_t* cell_label, int max_cell, const int32_t* d2,
+                      int h, int w, void* workspace, int64_t workspace_bytes, int32_t* out_needed, int max_pairs,
+                      int32_t* out_droplet, int64_t* out_cell, unetdc_stream_t s) {
+  return launch_cell_table(droplet_label, max_droplet, cell_label, max_cell, d2, h, w, workspace, (long)workspace_bytes, out_needed,
+                           max_pairs, out_droplet, reinterpret_cast<long long*>(out_cell), (hipStream_t)s);
+}
+
 int64_t unetdc_ripley_workspace(int h, int w, int max_points, int rmax, int n_sim) {
   return ripley_workspace_bytes(h, w, max_points, rmax, n_sim);
 }

@@ -342,6 +342,18 @@ int launch_label_neighbors(const int* label, int max_label, int h, int w, int ra
                            int* out_count, int* out_a, int* out_b, int* out_d2, int max_pairs, int* out_nn_label,
                            int* out_nn_d2, int* out_degree, int* out_cluster, int* out_cluster_size, hipStream_t stream);
 
+// cells.hip: the nearest-label transform of a seed label map and the per-cell reduction of the droplet table (DESIGN.md
+// section 31; include/unetdc_hip.h)
+constexpr int CELL_DROPLET_QUANTITIES = 6;
+constexpr int CELL_QUANTITIES = 8;
+long label_nearest_workspace_bytes(int h, int w);                                       // 0 for arguments the call refuses
+int launch_label_nearest(const int* label, int max_label, int h, int w, int radius, void* workspace, long workspace_bytes,
+                         int* out_label, int* out_d2, hipStream_t stream);
+long cell_table_workspace_bytes(int h, int w, int max_droplet, int max_cell, int max_pairs);   // 0 likewise
+int launch_cell_table(const int* droplet_label, int max_droplet, const int* cell_label, int max_cell, const int* d2, int h, int w,
+                      void* workspace, long workspace_bytes, int* out_needed, int max_pairs, int* out_droplet, long long* out_cell,
+                      hipStream_t stream);
+
 // spatial.hip: centroid pixels of a droplet table; Ripley counts of the observed pattern and of simulated ones (DESIGN.md
 // section 26)
 long ripley_workspace_bytes(int h, int w, int max_points, int rmax, int n_sim);         // 0 for arguments the call refuses

@@ -6,7 +6,8 @@ copies every fp32 probability map to the host, labels it twice with scikit-image
 
 Shape: DropletOptions in, one Droplets per image out, one launch-and-readback body (_droplets).  What runs before a label
 map exists (mask, cleaning, the choice of labelling kernel) is the explicit head of _enqueue; every optional stage that measures
-on the label map is one entry of _STAGES, and one _Layout per batch owns every offset into the batch's two shared buffers.
+on the label map is one entry of _STAGES (_MAP_STAGES: those that measure it against maps the caller brings), and one _Layout per
+batch owns every offset into the batch's two shared buffers.
 DESIGN.md section 13 describes both.
 """
 from __future__ import annotations
@@ -17,7 +18,7 @@ from typing import NamedTuple
 
 import numpy as np
 import torch
-from utils import droplet_confidence, droplet_hull, droplet_neighbors, droplet_shape
+from utils import droplet_cells, droplet_confidence, droplet_hull, droplet_neighbors, droplet_shape
 
 from . import _lib
 
@@ -77,6 +78,8 @@ class DropletOptions:
     utils/droplet_confidence.py); confidence_maps: also the uint8 entropy and spread maps, on the device.
     hull: also the per-droplet integers of the convex hull that utils.droplet_hull.hull_columns reads (csrc/hull.hip, DESIGN.md
     section 24).
+    cells: also the per-droplet and per-cell integers of utils.droplet_cells.cells_record against the cell label maps given as
+    the keyword cells= (one cells.CellMap per image; csrc/cells.hip).
     thresh / gray are not kept: the threshold the low one is checked against, and the grey planes, which need shape."""
     split_depth: float | None = None
     shape: bool = False
@@ -87,12 +90,13 @@ class DropletOptions:
     confidence: float | None = None
     confidence_maps: bool = False
     hull: bool = False
+    cells: bool = False
     thresh: dataclasses.InitVar[float | None] = None
     gray: dataclasses.InitVar[object] = None
 
     def __post_init__(self, thresh, gray):
         if self.labels and self.split_depth is None and not self.label_map:
-            raise _lib.UnetdcError("return_labels needs a split_depth or a stage on the label map: " + ", ".join(S.option for S in _STAGES))
+            raise _lib.UnetdcError("return_labels needs a split_depth or a stage on the label map: " + ", ".join(S.option for S in _STAGES + _MAP_STAGES))
         try:
             if self.neighbors is not None:
                 droplet_neighbors.check_radius(self.neighbors)
@@ -110,7 +114,7 @@ class DropletOptions:
     @property
     def label_map(self):
         """Whether a stage of _STAGES reads the int32 label map (without a split depth that selects unetdc_ccl_labels)."""
-        return any(S.on(self) for S in _STAGES)
+        return any(S.on(self) for S in _STAGES + _MAP_STAGES)
 
     @property
     def half_pixels(self):
@@ -131,15 +135,21 @@ class DropletOptions:
 
 def _options(keywords, thresh):
     """The option keywords of the public functions -> (the record, validated against this call's threshold and grey planes;
-    gray).  options=DropletOptions(...), or its fields by name (labels also under its earlier name return_labels)."""
+    gray; envelope; the cell maps).  options=DropletOptions(...), or its fields by name (labels also under its earlier name
+    return_labels; cells= carries the maps themselves and switches the field on)."""
     kw = dict(keywords)
     gray, base, envelope = kw.pop("gray", None), kw.pop("options", None) or DropletOptions(), kw.pop("envelope", None)
+    cells = kw.pop("cells", None)
+    if cells is not None:
+        kw["cells"] = True
     if "return_labels" in kw:
         kw["labels"] = kw.pop("return_labels")
     opts = dataclasses.replace(base, **kw, thresh=thresh, gray=gray)
     if envelope is not None and opts.confidence is None:
         raise _lib.UnetdcError("envelope needs confidence (the band)")
-    return opts, gray, envelope
+    if opts.cells and cells is None:
+        raise _lib.UnetdcError("cells=True needs the cell maps: cells=[cells.CellMap(label, max_label, d2), ...], one per image")
+    return opts, gray, envelope, cells
 
 
 @dataclasses.dataclass(eq=False)
@@ -151,7 +161,8 @@ class Droplets:
     the counts of utils.droplet_clean.COUNT_NAMES (zeros when cleaning is off); neighbors: the record of
     utils.droplet_neighbors.neighbors_numpy, int64 arrays (None unless asked for); confidence: the record of
     utils.droplet_confidence.confidence_numpy (None unless asked for), its two maps DEVICE tensors; hull: the dict of five int64
-    arrays that utils.droplet_hull.hull_columns reads (None unless asked for).  The CPU path of the script fills the same record
+    arrays that utils.droplet_hull.hull_columns reads (None unless asked for); cells: the record of
+    utils.droplet_cells.cells_record (None unless asked for).  The CPU path of the script fills the same record
     with host arrays."""
     mask: object
     area: np.ndarray
@@ -163,9 +174,18 @@ class Droplets:
     neighbors: dict | None = None
     confidence: dict | None = None
     hull: dict | None = None
+    cells = None      # the record of a _MAP_STAGES stage: a plain attribute that with_records sets, not one more constructor argument
 
     def __iter__(self):
         return iter((self.mask, self.area, self.centroid_row, self.centroid_col))
+
+    def with_records(self, **records):
+        """Sets the records of the stages that are not fields (cells) -> self."""
+        for name, rec in records.items():
+            if not hasattr(type(self), name):
+                raise AttributeError(name)
+            setattr(self, name, rec)
+        return self
 
 
 class _Image(NamedTuple):
@@ -182,8 +202,9 @@ class _Image(NamedTuple):
 
 
 # What the launches of one batch share.  ws: the one workspace, uint8, used in stream order; cap: the droplets per image that the
-# outputs hold; rooms: by _Stage.room, the slots per image of each growable room; envelope: (lo, hi) fp32 [B, ph, pw] or None.
-_Batch = collections.namedtuple("_Batch", "opts thresh min_area stream ws cap rooms layout counts envelope")
+# outputs hold; rooms: by _Stage.room, the slots per image of each growable room; envelope: (lo, hi) fp32 [B, ph, pw] or None;
+# cells: B cells.CellMap or None.
+_Batch = collections.namedtuple("_Batch", "opts thresh min_area stream ws cap rooms layout counts envelope cells")
 
 
 class _Layout:
@@ -365,7 +386,50 @@ class _Hull(_Stage):
         return dict(zip(droplet_hull.QUANTITIES, b.layout.rows(sums, self.field)))
 
 
+TRIPLE_ROOM = 1 << 14    # (droplet, cell) pairs per image the first launch has room for; an image with more is run again with twice that
+
+
+class _Cells(_Stage):
+    """csrc/cells.hip: the record of utils.droplet_cells.cells_record against the image's cells.CellMap; the capacity is the
+    kernel's max_droplet.  Its integers are planes of its own: int32 [6, cap] per image and int64 [8, max_cell] per image, the
+    latter with the image's own max_cell as the row length, in a buffer sized for the largest: two more copies."""
+    option, field, slots32, room = "cells", "cells", 1, "triples"
+    # a pixel carries at most one pair: h * w always suffices
+    capacity = staticmethod(lambda cap, out_hws, wanted: int(min(TRIPLE_ROOM if wanted is None else wanted, max(h * w for h, w in out_hws))))
+    limit = staticmethod(lambda hw: (hw[0] * hw[1], "unetdc_cell_table: more (droplet, cell) pairs than the image has pixels"))
+    # max_cell has no plane in the workspace (the per-cell sums go straight to the output): the query does not read it
+    workspace = staticmethod(lambda lib, h, w, cap, rooms: lib.unetdc_cell_table_workspace(h, w, cap, 0, rooms["triples"]))
+    ND, NC = len(droplet_cells.DROPLET_QUANTITIES), len(droplet_cells.CELL_QUANTITIES)
+
+    def __init__(self, b):
+        dev = b.counts.device
+        self.per_droplet = torch.empty(b.layout.B, self.ND, b.cap, dtype=torch.int32, device=dev)
+        self.per_cell = torch.empty(b.layout.B, self.NC * max(c.max_label for c in b.cells), dtype=torch.int64, device=dev)
+
+    def views(self, b, i, hw):
+        m = b.cells[i]
+        return {"map": m, "per_droplet": self.per_droplet[i], "per_cell": self.per_cell[i, :self.NC * m.max_label].view(self.NC, m.max_label)}
+
+    def launch(self, b, im, v):
+        m = v["map"]
+        _lib.call("unetdc_cell_table", im.label.data_ptr(), b.cap, m.label.data_ptr(), m.max_label, _ptr(m.d2), *im.mask.shape,
+                  b.ws.data_ptr(), b.ws.numel(), v["needed"].data_ptr(), b.rooms["triples"], v["per_droplet"].data_ptr(),
+                  v["per_cell"].data_ptr() if m.max_label else None, b.stream)
+
+    def fetch(self, b, ints, nmax):
+        self.per_droplet_h = self.per_droplet[:, :, :nmax].cpu().numpy().astype(np.int64)
+        self.per_cell_h = self.per_cell.cpu().numpy()       # sized by the largest label: a caller with sparse ids renumbers them first
+
+    def record(self, b, i, im, area, sums, raw):
+        m = b.cells[i]
+        return droplet_cells.make_record(self.per_droplet_h[i, :, :len(area)],
+                                         self.per_cell_h[i, :self.NC * m.max_label].reshape(self.NC, m.max_label), m.d2 is not None)
+
+
 _STAGES = (_Props, _Neighbors, _Confidence, _Hull)     # in launch order, which is the order of their slots and rows
+# behind them, the stages that measure the label map against maps the caller brings (the keyword of their field): their slots
+# and rows lie behind those of _STAGES, so a batch without them keeps the layout it had
+_MAP_STAGES = (_Cells,)
 
 
 def _enqueue(im, b, stages):
@@ -404,7 +468,7 @@ def _workspace_bytes(lib, out_hws, opts, clean, stages, cap, rooms):
                    *(S.workspace(lib, h, w, cap, rooms) for S in stages)) for h, w in out_hws)
 
 
-def _droplets(probs, thresh, out_hws, min_area, wanted, gray, opts, envelope=None):
+def _droplets(probs, thresh, out_hws, min_area, wanted, gray, opts, envelope=None, cells=None):
     """The one launch-and-readback body -> (B Droplets, the device outputs (count, area, sumy, sumx) or None when an image
     had more droplets than they hold).  wanted: the rooms asked for by name, "droplets" (the capacity) and optionally those of
     the stages (_Stage.room; their defaults otherwise).  Every launch of the batch is enqueued back to back on the current
@@ -426,14 +490,23 @@ def _droplets(probs, thresh, out_hws, min_area, wanted, gray, opts, envelope=Non
     for g, hw in zip(() if gray is None else gray, out_hws):
         if not g.is_cuda or g.dtype != torch.uint8 or tuple(g.shape) != hw or not g.is_contiguous():
             raise _lib.UnetdcError("gray must be a contiguous uint8 [oh, ow] tensor on the HIP device")
-    on = [S for S in _STAGES if S.on(opts)]
+    if opts.cells:
+        if len(cells) != B:
+            raise _lib.UnetdcError("cells: one cells.CellMap per image")
+        for m, hw in zip(cells, out_hws):
+            for t in (m.label,) + (() if m.d2 is None else (m.d2,)):
+                if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != hw or not t.is_contiguous():
+                    raise _lib.UnetdcError("cells: label and d2 must be contiguous int32 [oh, ow] tensors on the HIP device")
+            if int(m.max_label) < 0:
+                raise _lib.UnetdcError("cells: max_label must not be negative")
+    on = [S for S in _STAGES + _MAP_STAGES if S.on(opts)]
     rooms = {S.room: S.capacity(cap, out_hws, wanted.get(S.room)) for S in on if S.room}
     lay = _Layout(B, on, clean is not None)
     ws = torch.empty(_workspace_bytes(_lib.load(), out_hws, opts, clean, on, cap, rooms), dtype=torch.uint8, device=dev)   # one: stream order
     counts = torch.zeros(lay.n_counts, dtype=torch.int32, device=dev)
     area = torch.empty(B, cap, dtype=torch.int32, device=dev)
     sums = torch.empty(B, lay.n_rows, cap, dtype=torch.int64, device=dev).permute(1, 0, 2)
-    b = _Batch(opts, thresh, min_area, torch.cuda.current_stream().cuda_stream, ws, cap, rooms, lay, counts, envelope)
+    b = _Batch(opts, thresh, min_area, torch.cuda.current_stream().cuda_stream, ws, cap, rooms, lay, counts, envelope, cells if opts.cells else None)
     stages, images = [S(b) for S in on], []
     for i, hw in enumerate(out_hws):
         view = sums[:, i]
@@ -469,12 +542,15 @@ def _droplets(probs, thresh, out_hws, min_area, wanted, gray, opts, envelope=Non
         more = overflowed(i)
         if more:                                  # this image again, alone
             out.append(_droplets(probs[i:i + 1], thresh, out_hws[i:i + 1], min_area, {**wanted, **more}, None if gray is None else gray[i:i + 1],
-                                 opts, None if envelope is None else tuple(t[i:i + 1] for t in envelope))[0][0])
+                                 opts, None if envelope is None else tuple(t[i:i + 1] for t in envelope),
+                                 None if cells is None else cells[i:i + 1])[0][0])
             continue
         a, si = a_h[i, :n[i]], s_h[:, i, :n[i]]
         d = np.maximum(a, 1)
+        recs = {st.field: (st.record(b, i, im, a, si, raw), type(st) in _STAGES) for st in stages}
         out.append(Droplets(im.mask, a, si[0].astype(np.float64) / d, si[1].astype(np.float64) / d, labels=im.label if opts.labels else None,
-                            clean_counts=clean_counts[i], **{st.field: st.record(b, i, im, a, si, raw) for st in stages}))
+                            clean_counts=clean_counts[i], **{f: r for f, (r, field) in recs.items() if field})
+                   .with_records(**{f: r for f, (r, field) in recs.items() if not field}))
     return out, ((lay.int32(counts, "count"), area, sums[0], sums[1]) if n.max(initial=0) <= cap else None)
 
 
@@ -483,19 +559,21 @@ def mask_and_droplets_batch(probs, thresh, out_hws, min_area, max_droplets=1 << 
     ONE host wait for the whole batch (_droplets).  keep_sums=True returns (that list, the device outputs (count, area,
     sumy, sumx) or None when an image had more droplets than they hold) for density.density_maps_batch.
     options: split_depth, shape, return_labels, thresh_low, max_hole_area, neighbors, confidence, confidence_maps, hull by name, or
-    options=DropletOptions(...); gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none); and
+    options=DropletOptions(...); gray=B uint8 [oh, ow] DEVICE tensors for the intensity integers of shape (None: none);
     envelope=(lo, hi), two fp32 DEVICE tensors shaped like probs (tta.predict_tta(..., envelope=True)), for the disagreement
-    integers of confidence (None: those keep their initial values).  Every option adds its launches
+    integers of confidence (None: those keep their initial values); and cells=B cells.CellMap (the cell label map of each image,
+    its largest label and optionally the d2 plane of cells.nearest_label) for the per-cell table.  Every option adds its launches
     behind each image's existing ones and its integers to the copies the host already waits for; all off: no launch is added."""
-    opts, gray, envelope = _options(options, thresh)
-    out, sums = _droplets(probs, thresh, out_hws, min_area, {"droplets": max_droplets}, gray, opts, envelope)
+    opts, gray, envelope, cells = _options(options, thresh)
+    out, sums = _droplets(probs, thresh, out_hws, min_area, {"droplets": max_droplets}, gray, opts, envelope, cells)
     return (out, sums) if keep_sums else out
 
 
 def mask_and_droplets(probs2d, thresh, out_hw, min_area, max_droplets=1 << 16, **options):
     """probs2d: [H, W] fp32 probabilities on the HIP device -> its Droplets: the batch of one.  options as in
-    mask_and_droplets_batch; gray: one uint8 [oh, ow] DEVICE tensor; envelope: two fp32 [H, W] DEVICE tensors."""
-    opts, gray, envelope = _options(options, thresh)
+    mask_and_droplets_batch; gray: one uint8 [oh, ow] DEVICE tensor; envelope: two fp32 [H, W] DEVICE tensors; cells: one
+    cells.CellMap."""
+    opts, gray, envelope, cells = _options(options, thresh)
     return _droplets(probs2d[None], thresh, [out_hw], min_area, {"droplets": max_droplets}, None if gray is None else [gray], opts,
-                     None if envelope is None else tuple(t[None] for t in envelope))[0][0]
+                     None if envelope is None else tuple(t[None] for t in envelope), None if cells is None else [cells])[0][0]
 
